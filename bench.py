@@ -13,6 +13,7 @@ frame k+1 renders; all K frames are complete on rank 0 when the timed region end
     python bench.py --gpus 1 --steps 3 --warmup 1
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus 1 --steps 3 --warmup 1 --dump-outputs DIR     # + the last timed frame as DIR/*.npy
 
 Rank 0 prints ONE JSON line.  `roofline` prices the trace kernel against the f32 VALU peak
 (256 CU x 4 SIMD x 32 lanes x 2.4 GHz = 78.6 T lane-ops/s; no FMA contraction is
@@ -103,7 +104,12 @@ def main():
                          "glibc = this host's glibc expf / logf restated on the GPU — then `value`, `roofline` and the oracle check are all in that arithmetic")
     ap.add_argument("--cpu-columns", type=int, default=0,
                     help="columns of the frame the CPU oracle is timed on (default: 32 per usable host CPU, at least 32)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the frame the last timed step rendered to DIR/*.npy (rank 0; a fixed, seeded pixel sample "
+                         "when the whole frame exceeds the size cap), so that two builds can be compared output for output")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
 
     import numpy as np
     import torch
@@ -227,6 +233,8 @@ def main():
     fence()
     dt = time.perf_counter() - t0
     st = collect()                                # exact counters + HIP-event kernel time of the K timed launches
+    if args.dump_outputs and rank == 0:           # before any side block renders into the slab again
+        dump_outputs(args.dump_outputs, slab if pipe is None else pipe.frame)
 
     # BASELINE.json words configs[2] with "4 spp".  The reference samples once per pixel (Image.fs:28-34) and
     # `value` is measured on that; the 4-sample EXTENSION of the same frame is timed beside it (N = 1 only).
@@ -529,6 +537,31 @@ def main():
     if use_dist:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SAMPLE_PIXELS = 1 << 21                      # 24 MB of float32 RGB + 16 MB of float64 indices
+DUMP_SEED = 20240601
+
+
+def dump_outputs(out_dir, frame):
+    """--dump-outputs: the float32 [W, H, 3] frame of the last timed step as out_dir/image.npy.  A frame larger than the cap is
+    sampled instead: DUMP_SAMPLE_PIXELS pixels drawn without replacement by a fixed seed (the same for every run of the same
+    size), in increasing order of their flat index x * H + y; image.npy is then [n, 3] and image_pixel_index.npy (float64) names
+    the pixels.  Returns the names written."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    W, H, C = frame.shape
+    if frame.numel() * 4 <= DUMP_MAX_BYTES:
+        np.save(os.path.join(out_dir, "image.npy"), frame.detach().cpu().numpy().astype(np.float32, copy=False))
+        return ["image"]
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(W * H, size=min(DUMP_SAMPLE_PIXELS, W * H), replace=False))
+    flat = frame.reshape(W * H, C)
+    pix = flat.index_select(0, torch.from_numpy(idx).to(flat.device)).cpu().numpy().astype(np.float32, copy=False)
+    np.save(os.path.join(out_dir, "image.npy"), pix)
+    np.save(os.path.join(out_dir, "image_pixel_index.npy"), idx.astype(np.float64))
+    return ["image", "image_pixel_index"]
 
 
 def oracle_check_columns(scene, cam, W, H, frame, ncols, libm=False):
