@@ -423,6 +423,7 @@ class Device:
                 obj = realise(scene.Object, self, memo)
                 lights = [realise(l, self, memo) for l in scene.Lights]
                 got = DeviceScene(self, obj, scene.BackgroundColor, lights)
+                got.materials = _materials_by_handle(scene.Object, memo)
                 scene._realised[self.serial] = got
                 self._scenes.append(got)
             return got
@@ -449,12 +450,63 @@ class Device:
         return out
 
 
+def _materials_by_handle(obj, memo):
+    """handle -> SdfMaterial descriptor for every material of a realised object tree"""
+    out, stack = {}, [obj]
+    while stack:
+        node = stack.pop()
+        if isinstance(node, Material):
+            out[memo[id(node)]] = node
+        stack.extend(node.kids)
+    return out
+
+
+class PixelHits:
+    """EXTENSION (ft_render_hits): SdfObject.tryTrace scene.Object of every pixel's camera ray (sample 0), laid out like the
+    frame.  `records` is float32 [n_columns, Y, 16] in the layout of ft_object_trace_result — Ray pulled back by epsilon
+    (Origin = Position, Direction, Length, Epsilon), Normal, Color, hit flag (int32 bits), 0; a miss (ValueNone) is all zero.
+    `material` is int32 [n_columns, Y]: the handle of the material the hit picked, -1 on a miss (None if not asked for)."""
+
+    def __init__(self, records, material=None, materials=None):
+        self.records = records
+        self.material = material
+        self._materials = dict(materials or {})
+
+    @property
+    def ray(self): return self.records[..., 0:8]
+
+    @property
+    def position(self): return self.records[..., 0:3]
+
+    @property
+    def direction(self): return self.records[..., 3:6]
+
+    @property
+    def length(self):
+        """remaining Length of the pulled-back ray: what is left of the ray's length, plus epsilon"""
+        return self.records[..., 6]
+
+    @property
+    def normal(self): return self.records[..., 8:11]
+
+    @property
+    def color(self): return self.records[..., 11:14]
+
+    @property
+    def hit(self): return self.records[..., 14].view(np.int32) != 0
+
+    def descriptor(self, handle):
+        """the SdfMaterial description (SdfMaterial.createSolid / createGlass value) a material handle was realised from; None for -1"""
+        return self._materials.get(int(handle))
+
+
 class DeviceScene:
     """ft_scene: the flattened immutable scene resident in HBM."""
 
     def __init__(self, device, obj, bg, lights):
         self.device = device
         self._object = obj
+        self.materials = {}               # material handle -> SdfMaterial description (filled by Device.scene)
         p = C.c_void_p()
         hs, n = _handles(lights)
         check(lib.ft_scene_create(device._ctx, obj, _f3(bg), hs, n, C.byref(p)))
@@ -522,6 +574,28 @@ class DeviceScene:
         """asynchronous render into device memory (pointer as int); pair with collect_stats()."""
         p = self._params(imageSize, epsilon, length, **tiling)
         check(lib.ft_render_device(self.device._ctx, self._scene, C.byref(camera._c), C.byref(p), C.c_void_p(d_out_ptr)))
+        return p.n_columns
+
+    def render_hits(self, epsilon, length, imageSize, camera, shade=False, material=True, records=True, **tiling_and_ext):
+        """EXTENSION ft_render_hits: per-pixel SdfObject.tryTrace of the camera rays -> (PixelHits, image or None, stats).
+        shade: also render the frame (bit-identical to render() with the same parameters, same launch); without it one ray
+        per pixel is traced and spp / ao_samples / max_bounces / spectral do not apply.  material / records: which planes to return."""
+        p = self._params(imageSize, epsilon, length, **tiling_and_ext)
+        shape = (p.n_columns, p.height)
+        img = np.empty(shape + (3,), np.float32) if shade else None
+        rec = np.empty(shape + (16,), np.float32) if records else None
+        mat = np.empty(shape, np.int32) if material else None
+        ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        st = _lib.Stats()
+        check(lib.ft_render_hits(self.device._ctx, self._scene, C.byref(camera._c), C.byref(p), ptr(img), ptr(rec), ptr(mat), C.byref(st)))
+        return PixelHits(rec, mat, self.materials), img, st.as_dict()
+
+    def render_hits_device(self, epsilon, length, imageSize, camera, d_hits_ptr, d_material_ptr=None, d_out_ptr=None, **tiling_and_ext):
+        """asynchronous ft_render_hits_device into device memory (pointers as int, None = not asked; the records 16-byte
+        aligned, n_columns x Y x 16 float32); pair with collect_stats()."""
+        p = self._params(imageSize, epsilon, length, **tiling_and_ext)
+        ptr = lambda a: None if not a else C.c_void_p(a)
+        check(lib.ft_render_hits_device(self.device._ctx, self._scene, C.byref(camera._c), C.byref(p), ptr(d_out_ptr), ptr(d_hits_ptr), ptr(d_material_ptr)))
         return p.n_columns
 
     def collect_stats(self):
@@ -735,6 +809,14 @@ class Image:
     @staticmethod
     def renderScene(epsilon, length, imageSize, camera, scene, device=None):
         return Image.render(epsilon, length, imageSize, camera, SdfScene.trace(scene, device))
+
+    @staticmethod
+    def renderHits(epsilon, length, imageSize, camera, scene, device=None):
+        """EXTENSION: Image.render's pixel loop (Image.fs:26-35) over SdfObject.tryTrace scene.Object (SdfObject.fs:66-78) instead of
+        SdfScene.trace: the SdfObjectTraceResult voption of every pixel as PixelHits (records [X, Y, 16], material handles)."""
+        dev = device if device is not None else Device.default(0)
+        hits, _, _ = dev.scene(scene).render_hits(epsilon, length, imageSize, camera)
+        return hits
 
     @staticmethod
     def toColors(gamma, rng, image, device=None, bmp_order=False):

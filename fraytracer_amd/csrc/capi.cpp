@@ -73,6 +73,7 @@ struct ft_scene {
     void* dBlob = nullptr;
     FtSceneDev dev{};
     const float* dMaterialsExt = nullptr;    // EXTENSION table, handed to the kernel through FtRenderArgs
+    const int32_t* dMatHandles = nullptr;    // EXTENSION ft_render_hits: dense material index -> context handle (FlatScene::materialHandles)
     FtCarve carve{};                         // fastPath == 3: tail + device pointers of the terminated candidate lists
     bool usesExpLog = false;                 // the program has a unionSmooth (SdfForm.fs:80,82): the only place FT_OPT_MATH matters while tracing
 };
@@ -167,7 +168,8 @@ int uploadScene(ft_ctx* c, ft_scene* s) {
     const size_t oInstr = placed(cur, f.instr), oConsts = placed(cur, f.consts), oGrids = placed(cur, f.grids),
                  oKids = placed(cur, f.children), oCtr = placed(cur, f.cellCenters), oStart = placed(cur, f.cellStart),
                  oItems = placed(cur, f.items), oLights = placed(cur, f.lights), oMats = placed(cur, f.materials),
-                 oMatX = placed(cur, f.materialsExt), oItemsT = placed(cur, f.itemsT), oStartT = placed(cur, f.cellStartT);
+                 oMatX = placed(cur, f.materialsExt), oItemsT = placed(cur, f.itemsT), oStartT = placed(cur, f.cellStartT),
+                 oMatH = placed(cur, f.materialHandles);
     std::vector<unsigned char> host(cur, 0);
     auto put = [&](size_t at, const void* p, size_t n) { if (n) memcpy(host.data() + at, p, n); };
     put(oInstr, f.instr.data(), f.instr.size() * sizeof(FtInstr));
@@ -182,6 +184,7 @@ int uploadScene(ft_ctx* c, ft_scene* s) {
     put(oMatX, f.materialsExt.data(), f.materialsExt.size() * 4);
     put(oItemsT, f.itemsT.data(), f.itemsT.size() * sizeof(FtItemRec));
     put(oStartT, f.cellStartT.data(), f.cellStartT.size() * 4);
+    put(oMatH, f.materialHandles.data(), f.materialHandles.size() * 4);
     FtSceneDev& d = s->dev;
     d = FtSceneDev{};
     d.nInstr = f.nMainInstr; d.nSlots = f.nSlots; d.nLights = (uint32_t)f.lights.size(); d.fastPath = f.fastPath;
@@ -203,6 +206,7 @@ int uploadScene(ft_ctx* c, ft_scene* s) {
     d.lights = reinterpret_cast<const FtLight*>(b + oLights);
     d.materials = reinterpret_cast<const float*>(b + oMats);
     s->dMaterialsExt = reinterpret_cast<const float*>(b + oMatX);
+    s->dMatHandles = reinterpret_cast<const int32_t*>(b + oMatH);
     s->carve = f.carve;
     s->carve.itemsT = reinterpret_cast<const FtItemRec*>(b + oItemsT);
     s->carve.cellStartT = reinterpret_cast<const uint32_t*>(b + oStartT);
@@ -582,10 +586,23 @@ int ft_camera_look_at(const float pos[3], const float look[3], const float up[3]
 }
 
 // ---- hot path ------------------------------------------------------------------------------------
-static int renderLane(ft_ctx* c, const ft_scene* s, const ft_camera* cam, const ft_render_params* p, void* d_out, int lane) {
+// EXTENSION ft_render_hits: device buffers of the per-pixel records (either may be NULL)
+struct HitBufs { void* hits; void* material; };
+
+// hb != NULL: the EXTENSION build also writes the hit buffers; d_out = NULL then means hits only (one ray per pixel, the EXTENSION fields of p
+// do not apply)
+static int renderLane(ft_ctx* c, const ft_scene* s, const ft_camera* cam, const ft_render_params* params, void* d_out, int lane,
+                      const HitBufs* hb = nullptr) {
     int rc = requireDevice(c); if (rc) return rc;
-    if (!s || s->ctx != c || !cam || !d_out) return setErr(FT_ERR_INVALID, "bad argument (scene must belong to this context)");
-    if ((rc = checkParams(p))) return rc;
+    if (!s || s->ctx != c || !cam || (!d_out && !hb)) return setErr(FT_ERR_INVALID, "bad argument (scene must belong to this context)");
+    if ((rc = checkParams(params))) return rc;
+    ft_render_params hitsOnly;
+    const ft_render_params* p = params;
+    if (hb && !d_out) {
+        hitsOnly = *params;
+        hitsOnly.spp = 1; hitsOnly.ao_samples = 0; hitsOnly.max_bounces = 0; hitsOnly.spectral = 0;
+        p = &hitsOnly;
+    }
     if (lane != 0 && p->spp != 1) return setErr(FT_ERR_INVALID, "internal: the sample planes belong to lane 0");
     FtRenderArgs a{};
     memcpy(a.cam, cam, sizeof(float) * 12);
@@ -605,6 +622,12 @@ static int renderLane(ft_ctx* c, const ft_scene* s, const ft_camera* cam, const 
     a.spectral = (uint32_t)p->spectral;
     if (a.spectral) ft::spectralTable((int)a.spectral, a.spec);
     a.ext = (a.spp != 1u || a.aoSamples != 0u || a.maxBounces != 0u || a.spectral != 0u) ? 1u : 0u;
+    if (hb) {                                                      // the hit buffers exist in the EXTENSION builds only
+        a.ext = 1u;
+        a.hits = d_out ? 1u : 2u;
+        a.hitsOut = static_cast<float*>(hb->hits); a.matOut = static_cast<int32_t*>(hb->material);
+        a.matHandles = s->dMatHandles;
+    }
     if (a.spp == 1) { a.out = static_cast<float*>(d_out); return launchTrace(c, s, a, lane); }
     // EXTENSION: one frame per sample, then a fixed-order resolve
     const size_t planeFloats = (size_t)a.planePixels * 3;
@@ -622,6 +645,16 @@ static int renderLane(ft_ctx* c, const ft_scene* s, const ft_camera* cam, const 
 
 int ft_render_device(ft_ctx* c, const ft_scene* s, const ft_camera* cam, const ft_render_params* p, void* d_out) {
     return renderLane(c, s, cam, p, d_out, 0);
+}
+
+int ft_render_hits_device(ft_ctx* c, const ft_scene* s, const ft_camera* cam, const ft_render_params* p, void* d_out_rgb, void* d_hits, void* d_material) {
+    int rc = requireDevice(c); if (rc) return rc;
+    if (!d_out_rgb && !d_hits && !d_material) return setErr(FT_ERR_INVALID, "ft_render_hits: no output asked for");
+    if ((reinterpret_cast<uintptr_t>(d_hits) & 15u) || (reinterpret_cast<uintptr_t>(d_material) & 3u) || (reinterpret_cast<uintptr_t>(d_out_rgb) & 3u))
+        return setErr(FT_ERR_INVALID, "ft_render_hits: the hit buffer must be 16-byte aligned, the image and the material plane 4-byte aligned");
+    if (!d_hits && !d_material) return renderLane(c, s, cam, p, d_out_rgb, 0);     // the frame alone: exactly ft_render_device
+    const HitBufs hb{d_hits, d_material};
+    return renderLane(c, s, cam, p, d_out_rgb, 0, &hb);
 }
 
 int ft_collect_stats(ft_ctx* c, ft_stats* st) {
@@ -777,6 +810,30 @@ int ft_render(ft_ctx* c, const ft_scene* s, const ft_camera* cam, const ft_rende
     if (err == hipSuccess) err = hipStreamSynchronize(c->stream);
     if (err != hipSuccess) return finish(hipFail(err, "ft_render host output"));
     if (pinnedHere) { (void)hipHostUnregister(out); pinnedHere = false; }
+    return ft_collect_stats(c, st);
+}
+
+// EXTENSION: the whole frame on lane 0 into the context's scratch ([image | records | material plane]), then copied out
+int ft_render_hits(ft_ctx* c, const ft_scene* s, const ft_camera* cam, const ft_render_params* p, float* out_rgb, ft_object_trace_result* out_hits,
+                   int32_t* out_material, ft_stats* st) {
+    static_assert(sizeof(ft_object_trace_result) == 64, "layout");
+    int rc = requireDevice(c); if (rc) return rc;
+    if (!out_rgb && !out_hits && !out_material) return setErr(FT_ERR_INVALID, "ft_render_hits: no output asked for");
+    if ((rc = checkParams(p))) return rc;
+    const size_t px = (size_t)p->n_columns * (size_t)p->height;
+    const size_t rgbBytes = out_rgb ? px * 12 : 0, hitBytes = out_hits ? px * 64 : 0, matBytes = out_material ? px * 4 : 0;
+    const size_t oHits = align256(rgbBytes), oMat = oHits + align256(hitBytes);
+    if ((rc = ensureScratch(c, oMat + matBytes))) return rc;
+    unsigned char* base = static_cast<unsigned char*>(c->scratch);
+    rc = ft_render_hits_device(c, s, cam, p, out_rgb ? base : nullptr, out_hits ? base + oHits : nullptr, out_material ? base + oMat : nullptr);
+    hipError_t err = hipSuccess;
+    if (!rc && out_rgb) err = hipMemcpyAsync(out_rgb, base, rgbBytes, hipMemcpyDeviceToHost, c->stream);
+    if (!rc && err == hipSuccess && out_hits) err = hipMemcpyAsync(out_hits, base + oHits, hitBytes, hipMemcpyDeviceToHost, c->stream);
+    if (!rc && err == hipSuccess && out_material) err = hipMemcpyAsync(out_material, base + oMat, matBytes, hipMemcpyDeviceToHost, c->stream);
+    const hipError_t se = hipStreamSynchronize(c->stream);             // nothing of this call is left in flight, whatever happened
+    if (rc) return rc;
+    if (err != hipSuccess) return hipFail(err, "ft_render_hits host output");
+    if (se != hipSuccess) return hipFail(se, "ft_render_hits");
     return ft_collect_stats(c, st);
 }
 

@@ -1276,6 +1276,24 @@ __device__ __forceinline__ void write_ray(float* o, f3 origin, f3 dir, float len
     o[0] = origin.x; o[1] = origin.y; o[2] = origin.z; o[3] = dir.x; o[4] = dir.y; o[5] = dir.z; o[6] = len; o[7] = eps;
 }
 
+// ft_render_hits (EXTENSION builds, mode 0; a.hits != 0 only there): does the segment this lane ends now carry the pixel's hit record?  Only the
+// first segment (no glass interaction yet) of sample 0, whose ray is the reference's pixel ray (spp offset 0)
+__device__ __forceinline__ bool ends_hit_segment(const FtRenderArgs& a, const LaneState& s) {
+    return a.hits != 0u && s.job < a.jobsPerPlane && s.bounce() == 0u;
+}
+// the record as ft_object_try_trace writes it (mode 3 in the round's switch): four 16-byte stores into the 64-byte slot, plus the material handle
+__device__ __forceinline__ void write_hit_record(const FtRenderArgs& a, uint32_t idx, v4f r0, v4f r1, v4f r2, v4f r3, int32_t handle) {
+    if (a.hitsOut != nullptr) {
+        v4f* o = reinterpret_cast<v4f*>(a.hitsOut + 16ull * idx);
+        o[0] = r0; o[1] = r1; o[2] = r2; o[3] = r3;
+    }
+    if (a.matOut != nullptr) a.matOut[idx] = handle;
+}
+__device__ __forceinline__ void write_hit_miss(const FtRenderArgs& a, uint32_t idx) {       // ValueNone: all zero, no material
+    const v4f z = {0.0f, 0.0f, 0.0f, 0.0f};
+    write_hit_record(a, idx, z, z, z, z, -1);
+}
+
 // Can the ray o + t dir, t >= 0, still come within eps of the scene's support sphere (FtSceneDev.escC / escR, scene.cpp supportOf)?  If not,
 // no evaluation along it can be below eps (SdfForm.fs:98), so its march ends in a miss whatever the steps are: the lane takes that exit at
 // once (FT_OPT_ESCAPE).  Outside and heading away (the distance to the centre only grows), or outside and passing by (closest approach
@@ -1327,7 +1345,11 @@ __device__ __forceinline__ void settle(const FtRenderArgs& a, LaneState& s) {
             // -Distance, which is below epsilon everywhere outside the support sphere — the shortcut is for paths outside bodies only)
             if (s.len <= 0.0f || ((!EXT || !s.inside()) && ft_never_enters(a.S, s.o, s.dir, s.eps, s.len))) {
                 if (EXT && a.mode >= 2u) write_try_trace_miss(a, s);   // ValueNone of the tryTrace entries
-                else emit<EXT>(a, s, mk3(a.S.bg[0], a.S.bg[1], a.S.bg[2]));
+                else {
+                    // every miss of a primary ray ends here: Length used up, escape, NaN and the step cap (s.len = -1), the camera shortcuts of start_job
+                    if (EXT && ends_hit_segment(a, s)) write_hit_miss(a, s.outIdx);
+                    if (!EXT || a.hits != 2u) emit<EXT>(a, s, mk3(a.S.bg[0], a.S.bg[1], a.S.bg[2]));
+                }
                 s.phase = PH_IDLE;
             }
             return;
@@ -1689,6 +1711,13 @@ __device__ __forceinline__ void ft_trace_body(const FtRenderArgs& a) {
                 sh_set3(FT_SH_LACC, mk3(a.S.bg[0], a.S.bg[1], a.S.bg[2]));     // SdfScene.fs:12
                 s.lidx = 0;
                 s.phase = PH_LIGHTS;
+                if (EXT && ends_hit_segment(a, s)) {                   // ft_render_hits: the mode-3 record below, before any glass bounce moves the ray
+                    cfp m = as_const(a.S.materials) + 3u * s.leaf;
+                    const float len = s.len - (-s.eps);                // Ray.move -eps: Length - (-eps)
+                    write_hit_record(a, s.outIdx, v4f{hp.x, hp.y, hp.z, s.dir.x}, v4f{s.dir.y, s.dir.z, len, s.eps},
+                                     v4f{nrm.x, nrm.y, nrm.z, m[0]}, v4f{m[1], m[2], __int_as_float(1), 0.0f}, as_const(a.matHandles)[s.leaf]);
+                    if (a.hits == 2u) s.phase = PH_IDLE;               // hits only (no AO, no glass: the host clears those)
+                }
                 if (EXT && a.aoSamples != 0u) { s.xs &= 0xffff0000u; s.phase = PH_AONEXT; }   // EXTENSION: AO counters to 0
                 if (EXT && a.maxBounces != 0u) glass_bounce(a, s);     // EXTENSION
                 if (EXT && a.mode == 3u) {                             // SdfObject.tryTrace result (SdfObject.fs:72-77)
@@ -1759,7 +1788,8 @@ extern "C" __global__ void __launch_bounds__(FT_BLOCK) FT_EXT_OCC ft_trace_kerne
 extern "C" __global__ void __launch_bounds__(FT_BLOCK) ft_trace_kernel_smooth_spheres_ext(const FtRenderArgs a) { ft_trace_body<1, true>(a); }
 // general scenes whose unions have combinator children evaluated on demand (FT_PR_CALL, FtSceneDev.fastPath == 2)
 extern "C" __global__ void __launch_bounds__(FT_BLOCK) FT_CALLS_OCC ft_trace_kernel_calls(const FtRenderArgs a) { ft_trace_body<2, false>(a); }
-extern "C" __global__ void __launch_bounds__(FT_BLOCK) ft_trace_kernel_calls_ext(const FtRenderArgs a) { ft_trace_body<2, true>(a); }
+// (its EXTENSION build is held at 4 waves = 128 VGPRs: the ft_render_hits stores took it to 130, i.e. 3 waves, by themselves)
+extern "C" __global__ void __launch_bounds__(FT_BLOCK) FT_OCC(4) ft_trace_kernel_calls_ext(const FtRenderArgs a) { ft_trace_body<2, true>(a); }
 // scenes that are one grid union of plain primitives of kind K with at most two intersect / subtract steps behind it (ft_device.h "Carved union":
 // the reference's own Program.fs scene is the torus one).  No exponential anywhere: no *_libm twins; EXTENSION launches take ft_trace_kernel_ext.
 // Resident waves per SIMD asked of the register allocator: 6 (80 VGPRs) where the inlined primitive fits without spills — 7 (72) measured the same

@@ -358,6 +358,7 @@ struct Flattener {
             out.materialsExt.push_back(e.glass ? 1.0f : 0.0f); out.materialsExt.push_back(e.ior);
             out.materialsExt.push_back(e.dispersion); out.materialsExt.push_back(0.0f);
             out.nGlass += e.glass;
+            out.materialHandles.push_back(handle);
         }
         return (uint32_t)matRemap[handle];
     }
@@ -906,7 +907,7 @@ bool flatten(const Builder& b, int object, const float bg[3], const int* lights,
         if (lights[i] < 0 || (size_t)lights[i] >= b.lights.size()) { err = "invalid light handle"; return false; }
         out.lights.push_back(b.lights[lights[i]].dev);
     }
-    if (out.materials.empty()) { out.materials.assign(3, 0.0f); out.materialsExt.assign(4, 0.0f); }           // a form-only union under no create(): index 0 must exist
+    if (out.materials.empty()) { out.materials.assign(3, 0.0f); out.materialsExt.assign(4, 0.0f); out.materialHandles.assign(1, -1); }           // a form-only union under no create(): index 0 must exist
     out.bg[0] = bg[0]; out.bg[1] = bg[1]; out.bg[2] = bg[2];
     if (out.cellStart.empty()) out.cellStart.push_back(0);
     // keep every pool non-empty and padded so device-side wide loads never run off the end

@@ -96,6 +96,7 @@ struct FlatScene {                                            // host copy of ev
     std::vector<FtLight> lights;
     std::vector<float> materials;
     std::vector<float> materialsExt;                          // EXTENSION: 4 floats per material (glass flag, ior, dispersion, 0)
+    std::vector<int32_t> materialHandles;                     // EXTENSION ft_render_hits: dense material index -> context handle (-1: none)
     uint32_t nGlass = 0;                                      // glass materials in this scene
     uint32_t nSlots = 1;
     uint32_t nStage = 0;                                      // consts[0, nStage) is mirrored in LDS by every workgroup

@@ -130,6 +130,25 @@ inline std::vector<float> renderScene(float epsilon, float length, ImageSize siz
     if (stats) *stats = st;
     return out;
 }
+// EXTENSION: Image.render's pixel loop (Image.fs:26-35) over SdfObject.tryTrace scene.Object (SdfObject.fs:66-78) instead of SdfScene.trace —
+// every pixel's camera ray as ft_object_trace_result (hit == 0 is ValueNone), laid out like renderScene's image.  `material`, if given, receives
+// the handle of the material each hit picked (-1 on a miss).
+inline std::vector<ft_object_trace_result> renderHits(float epsilon, float length, ImageSize size, const ft_camera& camera, const SdfScene& scene,
+                                                      std::vector<int32_t>* material = nullptr, ft_stats* stats = nullptr) {
+    ft_ctx* ctx = scene.Object.ctx;
+    std::vector<ft_handle> lights; for (auto& l : scene.Lights) lights.push_back(l.Node);
+    ft_scene* s = nullptr;
+    check(ft_scene_create(ctx, scene.Object.Node, &scene.BackgroundColor.v.x, lights.data(), (int)lights.size(), &s));
+    std::vector<ft_object_trace_result> out((size_t)size.X * size.Y);
+    if (material) material->assign(out.size(), -1);
+    ft_render_params p{size.X, size.Y, 0, size.X, size.X, 1, 0, 1, epsilon, length, 0, 0.0f, 0, 0};
+    ft_stats st{};
+    int rc = ft_render_hits(ctx, s, &camera, &p, nullptr, out.data(), material ? material->data() : nullptr, &st);
+    ft_scene_destroy(s);
+    check(rc);
+    if (stats) *stats = st;
+    return out;
+}
 // Image.toColors gamma rng image (Image.fs:37-50) on the GPU: bytes in Color[X,Y] order (R,G,B) or, with bmpOrder, in the scan-line
 // order of Image.toBitmap (Image.fs:61-86: rows from the top, B,G,R).  seed < 0: no dithering noise (the reference's is racy).
 inline std::vector<unsigned char> toColors(ft_ctx* ctx, float gamma, long long seed, const std::vector<float>& image, ImageSize size, bool bmpOrder = false) {

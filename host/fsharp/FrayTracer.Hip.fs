@@ -92,6 +92,8 @@ module Native =
     [<DllImport(Lib)>] extern int ft_form_try_trace(nativeint ctx, nativeint scene, Ray[] rays, int64 n, [<Out>] FtFormTraceResult[] out, FtStats& stats)
     [<DllImport(Lib)>] extern int ft_object_try_trace(nativeint ctx, nativeint scene, Ray[] rays, int64 n, [<Out>] FtObjectTraceResult[] out, FtStats& stats)
     [<DllImport(Lib)>] extern int ft_render(nativeint ctx, nativeint scene, FtCamera& camera, FtRenderParams& p, nativeint out, FtStats& stats)
+    [<DllImport(Lib)>] extern int ft_render_hits(nativeint ctx, nativeint scene, FtCamera& camera, FtRenderParams& p, nativeint outRgb, [<Out>] FtObjectTraceResult[] outHits, [<Out>] int[] outMaterial, FtStats& stats)
+    [<DllImport(Lib)>] extern int ft_render_hits_device(nativeint ctx, nativeint scene, FtCamera& camera, FtRenderParams& p, nativeint dOutRgb, nativeint dHits, nativeint dMaterial)
     // a destination that is reused over many frames can be page-locked once (otherwise ft_render pins it for the duration of each call)
     [<DllImport(Lib)>] extern int ft_host_register(nativeint ctx, nativeint p, uint64 bytes)
     [<DllImport(Lib)>] extern int ft_host_unregister(nativeint ctx, nativeint p)
@@ -288,6 +290,31 @@ module Image =
                 image
             finally
                 pin.Free ()
+        finally
+            Native.ft_scene_destroy handle
+
+    /// EXTENSION: Image.render's pixel loop (Image.fs:26-35) over FrayTracer.SdfObject.tryTrace scene.Object (SdfObject.fs:66-78) instead of
+    /// SdfScene.trace — what every pixel's camera ray hit, laid out like renderScene's image.  Built the way Trace.objectTryTrace builds its results.
+    let renderHits (epsilon : float32) (length : float32) (imageSize : ImageSize) (camera : Camera) (scene : GpuScene) : SdfObjectTraceResult voption[,] =
+        let ctx = Native.ctx.Value
+        let lights = scene.Lights |> List.map (fun l -> l.Node) |> List.toArray
+        let mutable bg = let (FColor v) = scene.BackgroundColor in v
+        let mutable handle = 0n
+        Native.check (Native.ft_scene_create (ctx, scene.Object.Node, &bg, lights, lights.Length, &handle)) |> ignore
+        try
+            let out : FtObjectTraceResult[] = Array.zeroCreate (imageSize.X * imageSize.Y)
+            let mutable cam = FtCamera.ofCamera camera
+            let mutable p =
+                { Width = imageSize.X; Height = imageSize.Y; X0 = 0; NColumns = imageSize.X
+                  StripeWidth = imageSize.X; StripeRanks = 1; StripeRank = 0; Spp = 1
+                  Epsilon = epsilon; Length = length; AoSamples = 0; AoRadius = 0f
+                  MaxBounces = 0; Spectral = 0 }
+            let mutable stats = Unchecked.defaultof<FtStats>
+            Native.check (Native.ft_render_hits (ctx, handle, &cam, &p, 0n, out, null, &stats)) |> ignore
+            Array2D.init imageSize.X imageSize.Y (fun x y ->
+                let r = out.[x * imageSize.Y + y]
+                if r.Hit = 0 then ValueNone
+                else ValueSome { SdfObjectTraceResult.Ray = r.Ray; Normal = r.Normal; Color = FColor r.Color })
         finally
             Native.ft_scene_destroy handle
 

@@ -203,6 +203,19 @@ int ft_render_device(ft_ctx*, const ft_scene*, const ft_camera*, const ft_render
                      void* d_out);
 /* counters / kernel time of the launches since the last call; synchronises the stream */
 int ft_collect_stats(ft_ctx*, ft_stats* stats);
+/* EXTENSION: per-pixel SdfObject.tryTrace scene.Object of the reference's pixel ray (sample 0), laid out like the frame
+ * (n_columns x height, y contiguous).  out_rgb NULL = hits only (no lighting, no shadow / AO / glass rays).
+ * out_hits: ft_object_trace_result per pixel, exactly what ft_object_try_trace returns for that ray (miss = all zero).
+ * out_material: material handle (ft_material_solid / ft_material_glass) the hit picked, -1 on a miss.
+ * Any of the three may be NULL, not all.  With out_rgb the image and the statistics are those of ft_render with the same
+ * parameters (any spp / ao_samples / max_bounces / spectral; the records describe the first segment of sample 0, before any
+ * glass bounce); without it one ray is traced per pixel and the EXTENSION fields of the parameters do not apply.
+ * The host form renders the whole frame before it copies out: 64 B of device scratch per pixel for the records. */
+int ft_render_hits(ft_ctx*, const ft_scene*, const ft_camera*, const ft_render_params*,
+                   float* out_rgb, ft_object_trace_result* out_hits, int32_t* out_material, ft_stats* stats);
+/* Same into device memory, asynchronous like ft_render_device (pair with ft_collect_stats); d_hits 16-byte aligned. */
+int ft_render_hits_device(ft_ctx*, const ft_scene*, const ft_camera*, const ft_render_params*,
+                          void* d_out_rgb, void* d_hits, void* d_material);
 
 /* ---- around the hot path: tone map + 8-bit output -------------------------------- */
 /* Image.toColors gamma rng image (Image.fs:37-50): max = Max(0.01, max over all channels); per channel

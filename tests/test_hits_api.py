@@ -1,0 +1,75 @@
+"""Per-pixel hit buffers (ft_render_hits / ft_render_hits_device): the parts that need no GPU — the ABI, the host-only refusal, the
+PixelHits views over oracle records of pixel rays, and the C++ mirror's renderHits."""
+import ctypes as C
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import fraytracer_amd as ft
+from fraytracer_amd import _lib
+from fraytracer_amd import synthetic as syn
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HEADER = os.path.join(ROOT, "include", "fraytracer_hip.h")
+EPS, LEN = syn.EPSILON, syn.RAY_LENGTH
+
+
+def test_symbols_are_declared_exported_and_bound():
+    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    out = subprocess.check_output(["nm", "-D", "--defined-only", _lib.LIB_PATH], text=True)
+    for name in ("ft_render_hits", "ft_render_hits_device"):
+        assert re.search(r"\b" + name + r"\s*\(", text), name
+        assert re.search(r"\bT " + name + r"\b", out), name
+        assert name in _lib.SYMBOLS
+        getattr(_lib.lib, name)
+
+
+def test_host_only_context_has_no_hit_buffers():
+    ctx = C.c_void_p()
+    _lib.check(_lib.lib.ft_ctx_create(-1, C.byref(ctx)))
+    try:
+        cam = _lib.CameraS()
+        p = _lib.RenderParams(8, 8, 0, 8, 8, 1, 0, 1, EPS, LEN, 0, 0.0, 0, 0)
+        hits = np.empty((8, 8, 16), np.float32)
+        st = _lib.Stats()
+        rc = _lib.lib.ft_render_hits(ctx, None, C.byref(cam), C.byref(p), None, hits.ctypes.data_as(C.c_void_p), None, C.byref(st))
+        assert rc == _lib.FT_ERR_NO_DEVICE
+        rc = _lib.lib.ft_render_hits_device(ctx, None, C.byref(cam), C.byref(p), None, C.c_void_p(256), None)
+        assert rc == _lib.FT_ERR_NO_DEVICE
+    finally:
+        _lib.lib.ft_ctx_destroy(ctx)
+
+
+def test_pixel_hits_views_over_oracle_records(oracle):
+    scene, _ = syn.config2(boxes=True)
+    cam = syn.default_camera().as_array()
+    W, H = 12, 9
+    rays = np.stack([oracle.pixel_ray(cam, W, H, x, y, EPS, LEN) for x in range(W) for y in range(H)])
+    rec, _ = oracle.Oracle().scene(scene).object_try_trace(rays)
+    rec = rec.reshape(W, H, 16)
+    mat = np.where(rec[..., 14].view(np.int32) == 1, 7, -1).astype(np.int32)
+    desc = ft.SdfMaterial.createSolid((0.25, 0.5, 0.75))
+    h = ft.PixelHits(rec, mat, {7: desc})
+    assert h.ray.shape == (W, H, 8) and h.normal.shape == h.color.shape == h.position.shape == (W, H, 3)
+    assert h.length.shape == (W, H) and h.hit.dtype == np.bool_
+    assert 0 < h.hit.sum() < W * H
+    assert np.array_equal(h.hit, rec[..., 14].view(np.int32) == 1)
+    assert np.shares_memory(h.position, rec) and np.array_equal(h.position, rec[..., 0:3])
+    assert np.array_equal(h.ray, rec[..., 0:8])
+    assert np.array_equal(h.direction[h.hit], rays.reshape(W, H, 8)[h.hit][:, 3:6])
+    assert not rec[~h.hit].any()
+    assert h.material.dtype == np.int32 and (h.material[~h.hit] == -1).all()
+    assert h.descriptor(7) is desc and h.descriptor(-1) is None
+
+
+def test_cpp_render_hits_compiles(tmp_path):
+    src = tmp_path / "hits.cpp"
+    src.write_text('#include "FrayTracer.hpp"\n'
+                   "std::vector<ft_object_trace_result> f(const FrayTracer::SdfScene& s, const ft_camera& c, std::vector<int32_t>* m) {\n"
+                   "    return FrayTracer::Image::renderHits(0.01f, 100.0f, FrayTracer::ImageSize{64, 48}, c, s, m);\n"
+                   "}\n")
+    cxx = os.environ.get("CXX", "g++")
+    subprocess.check_call([cxx, "-std=c++17", "-fsyntax-only", "-I", os.path.join(ROOT, "host", "cpp"), "-I", os.path.join(ROOT, "include"), str(src)])
