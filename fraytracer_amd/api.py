@@ -377,7 +377,8 @@ class Device:
 
     OPTIONS = {"refill_min": _lib.FT_OPT_REFILL_MIN, "max_blocks_per_cu": _lib.FT_OPT_MAX_BLOCKS_PER_CU,
                "host_chunks": _lib.FT_OPT_HOST_CHUNKS, "host_pin": _lib.FT_OPT_HOST_PIN, "math": _lib.FT_OPT_MATH,
-               "tail_k": _lib.FT_OPT_TAIL_K, "guided": _lib.FT_OPT_GUIDED, "chunk": _lib.FT_OPT_CHUNK, "cull": _lib.FT_OPT_CULL, "escape": _lib.FT_OPT_ESCAPE, "lazy_union": _lib.FT_OPT_LAZY_UNION, "carved": _lib.FT_OPT_CARVED, "reuse": _lib.FT_OPT_REUSE}
+               "tail_k": _lib.FT_OPT_TAIL_K, "guided": _lib.FT_OPT_GUIDED, "chunk": _lib.FT_OPT_CHUNK, "cull": _lib.FT_OPT_CULL, "escape": _lib.FT_OPT_ESCAPE, "lazy_union": _lib.FT_OPT_LAZY_UNION, "carved": _lib.FT_OPT_CARVED, "reuse": _lib.FT_OPT_REUSE,
+               "cert": _lib.FT_OPT_CERT, "cert_policy": _lib.FT_OPT_CERT_POLICY}
 
     def set_option(self, name, value):
         """ft_ctx_set_option: per-context switches (the library reads no environment variables)"""
@@ -531,6 +532,12 @@ class DeviceScene:
         cr = (C.c_float * 4)()
         check(lib.ft_scene_support_sphere(self._scene, cr))
         return tuple(float(v) for v in cr)
+
+    def miss_certificate(self):
+        """{margin, clip, rho2, len_factor, steps}: the constants of the smooth-union kernel's miss certificate (margin < 0: none)"""
+        v = (C.c_float * 5)()
+        check(lib.ft_scene_miss_certificate(self._scene, v))
+        return dict(zip(("margin", "clip", "rho2", "len_factor", "steps"), (float(x) for x in v)))
 
     def grid(self, g=0):
         info = (C.c_float * 6)()

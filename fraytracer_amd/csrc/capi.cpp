@@ -64,6 +64,8 @@ struct ft_ctx {
     int optCull = 1;                                       // FT_OPT_CULL: exact child culling in the lean kernel (kernels.hip); 0 = every child, every round
     int optReuse = 1;                                      // FT_OPT_REUSE: a secondary ray's first evaluation is taken from the normal's centre probe (kernels.hip FT_SH_D0); 0 = evaluated again, as the reference does
     int optCarved = 1;                                     // FT_OPT_CARVED: scenes of the "carved union" shape take their specialised kernel (kernels.hip ft_eval_carved); 0 = the general interpreter
+    int optCert = 1;                                       // FT_OPT_CERT: the lean kernel's miss certificate (kernels.hip ft_miss_certificate); needs optEscape
+    int optCertPolicy = 0;                                 // FT_OPT_CERT_POLICY: 0 = FT_CERT_POLICY_DEFAULT
     int optGuided = 0;                                     // FT_OPT_GUIDED: smaller chunks at the end of the job queue (lean kernel; measured: no gain)
 };
 
@@ -191,6 +193,7 @@ int uploadScene(ft_ctx* c, ft_scene* s) {
     d.bg[0] = f.bg[0]; d.bg[1] = f.bg[1]; d.bg[2] = f.bg[2];
     d.nStage = f.nStage; d.nearR2 = f.nearR2; d.fastQ = f.fastQ; d.nGlass = f.nGlass;
     d.escC[0] = f.escC[0]; d.escC[1] = f.escC[1]; d.escC[2] = f.escC[2]; d.escR = f.escR; d.escRho2 = f.escRho2; d.cullPc = f.cullPc;
+    d.certM = f.certM; d.certClip = f.certClip; d.certRho2 = f.certRho2; d.certLenF = f.certLenF; d.certSteps = f.certSteps;
     if (!c->hasDevice) return FT_OK;                       // host-only context: introspection only
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipMalloc(&s->dBlob, cur));
@@ -230,6 +233,9 @@ size_t ldsBytes(const ft_scene* s, bool libm = false, bool traceLaunch = false, 
     return floats * 4;
 }
 // Latency-mode thresholds (rays per wave at or below which each ray is evaluated by all 64 lanes; measured)
+// miss certificate (FT_OPT_CERT_POLICY layout): primary rays at their first step (the one taken from the camera's value), shadow rays at their 6th,
+// a wave runs the certificate once 16 of its lanes are due, one try per ray (DESIGN.md section 4 "Miss certificate": the policies measured)
+constexpr int FT_CERT_POLICY_DEFAULT = 1 | (6 << 8) | (16 << 16);
 constexpr int FT_TAIL_K_LEAN = 32, FT_TAIL_K_GENERAL = 2, FT_TAIL_K_CARVED = 1;      // carved: 1.26 ms at 0 / 1 against 1.29 at 2 on the 1000^2 Program.fs frame (profiles/r04_carved_variants.txt)
 // does this launch take the glibc build of the kernels?
 bool libmLaunch(const ft_ctx* c, const ft_scene* s) { return c->optMath != FT_MATH_FIXED && s->usesExpLog; }
@@ -323,6 +329,16 @@ int launchTrace(ft_ctx* c, const ft_scene* s, FtRenderArgs& a, int lane = 0) {
     a.math = libm ? 1u : 0u;
     a.cull = (s->dev.cullPc != 0xffffffffu && variant != 3u && cullRows && c->optCull) ? 1u : 0u;
     if (!c->optEscape) a.S.escR = -1.0f;
+    // miss certificate: lean kernel (and its EXTENSION build: a render and its ft_render_hits twin count the same evaluations), only with the escape
+    // shortcut (it rests on the same support sphere and drift bound)
+    {
+        const uint32_t pol = (uint32_t)(c->optCertPolicy != 0 ? c->optCertPolicy : FT_CERT_POLICY_DEFAULT);
+        a.cert = (variant == 1u && c->optEscape && c->optCert && s->dev.certM >= 0.0f) ? 1u : 0u;
+        a.certPrim = (pol & 255u) == 255u ? 0xffffffffu : (pol & 255u);
+        a.certShadow = ((pol >> 8) & 255u) == 255u ? 0xffffffffu : ((pol >> 8) & 255u);
+        a.certMin = (pol >> 16) & 255u;
+        a.certRepeat = pol >> 24;
+    }
     a.lazy = c->optLazyUnion ? 1u : 0u;
     a.reuse = c->optReuse ? 1u : 0u;
     a.S.mathFma = c->optMath == FT_MATH_GLIBC_FMA ? 1u : 0u;
@@ -381,6 +397,12 @@ int ft_ctx_set_option(ft_ctx* c, int32_t option, int32_t value) {
     case FT_OPT_GUIDED: if (value != 0 && value != 1) return setErr(FT_ERR_INVALID, "FT_OPT_GUIDED: 0 or 1"); c->optGuided = value; return FT_OK;
     case FT_OPT_CARVED: if (value != 0 && value != 1) return setErr(FT_ERR_INVALID, "FT_OPT_CARVED: 0 or 1"); c->optCarved = value; return FT_OK;
     case FT_OPT_REUSE: if (value != 0 && value != 1) return setErr(FT_ERR_INVALID, "FT_OPT_REUSE: 0 or 1"); c->optReuse = value; return FT_OK;
+    case FT_OPT_CERT: if (value != 0 && value != 1) return setErr(FT_ERR_INVALID, "FT_OPT_CERT: 0 or 1"); c->optCert = value; return FT_OK;
+    case FT_OPT_CERT_POLICY: {
+        const uint32_t v = (uint32_t)value, mn = (v >> 16) & 255u;
+        if (value != 0 && (mn < 1u || mn > 64u)) return setErr(FT_ERR_INVALID, "FT_OPT_CERT_POLICY: 0, or bits 16-23 (due lanes) in 1 .. 64");
+        c->optCertPolicy = value; return FT_OK;
+    }
     case FT_OPT_MATH:
         if (value != FT_MATH_FIXED && value != FT_MATH_GLIBC_FMA && value != FT_MATH_GLIBC_SSE2) return setErr(FT_ERR_INVALID, "FT_OPT_MATH: 0 fixed, 1 glibc (FMA build), 2 glibc (SSE2 build)");
         c->optMath = value; return FT_OK;
@@ -399,6 +421,8 @@ int ft_ctx_get_option(const ft_ctx* c, int32_t option, int32_t* value) {
     case FT_OPT_GUIDED: *value = c->optGuided; return FT_OK;
     case FT_OPT_CARVED: *value = c->optCarved; return FT_OK;
     case FT_OPT_REUSE: *value = c->optReuse; return FT_OK;
+    case FT_OPT_CERT: *value = c->optCert; return FT_OK;
+    case FT_OPT_CERT_POLICY: *value = c->optCertPolicy; return FT_OK;
     case FT_OPT_CULL: *value = c->optCull; return FT_OK;
     case FT_OPT_LAZY_UNION: *value = c->optLazyUnion; return FT_OK;
     case FT_OPT_ESCAPE: *value = c->optEscape; return FT_OK;
@@ -1041,6 +1065,12 @@ int ft_scene_grid_shape(const ft_scene* s, int32_t g, float info[6], int32_t cou
 int ft_scene_support_sphere(const ft_scene* s, float cr[4]) {
     if (!s || !cr) return setErr(FT_ERR_INVALID, "null argument");
     cr[0] = s->flat.escC[0]; cr[1] = s->flat.escC[1]; cr[2] = s->flat.escC[2]; cr[3] = s->flat.escR;
+    return FT_OK;
+}
+int ft_scene_miss_certificate(const ft_scene* s, float out[5]) {
+    if (!s || !out) return setErr(FT_ERR_INVALID, "null argument");
+    const ft::FlatScene& f = s->flat;
+    out[0] = f.certM; out[1] = f.certClip; out[2] = f.certRho2; out[3] = f.certLenF; out[4] = (float)f.certSteps;
     return FT_OK;
 }
 

@@ -107,6 +107,13 @@ struct FtSceneDev {             // passed by value as kernel argument
                                 // SMOOTH_RUN of >= 32 children, the longest one; 0xffffffff: none
     float escRho2;              // the escape shortcut is taken only by rays that start within sqrt(escRho2) of escC: the bound on the float32 drift of
                                 // the marched points that escR's padding covers holds from there (scene.cpp "drift of the marched points")
+    // Exact miss certificate (kernels.hip ft_miss_certificate; scene.cpp "miss certificate"): only for a program that is ONE smooth union of staged
+    // spheres (instruction 0 the run, 1 SMOOTH_FIN, 2 SETLEAF) with a support sphere.  certM < 0: none.
+    float certM;                // margin: the certificate holds where sum exp(si (dist(segment, c_i) - r_i)) < exp(si (epsilon + certM))
+    float certClip;             // the segment is the part of the remaining ray within escR + epsilon + certClip of escC
+    float certRho2;             // ... from starts within sqrt(certRho2) of escC (the drift bound's ball)
+    float certLenF;             // ... and along at most Length * certLenF (the float32 Length the reference counts down)
+    uint32_t certSteps;         // steps the rest of a certified march can take at most (the step cap stays out of reach)
 };
 
 // "Carved union" kernels (FtSceneDev.fastPath == 3; kernels.hip ft_eval_carved): the whole program is ONE grid union of plain primitives

@@ -58,6 +58,9 @@ struct FtRenderArgs {
     int32_t* matOut;          // material handle per pixel (-1 on a miss); NULL: not asked
     const int32_t* matHandles;   // dense material index -> context handle (ft_material_*): the inverse of the flattener's remap
     uint32_t hits;            // 0: no hit buffers; 1: with the frame; 2: hits only (no lighting, nothing written to out)
+    // miss certificate (lean kernel; kernels.hip ft_miss_certificate): a ray is due once its step count reaches certPrim (primary) / certShadow (shadow ray);
+    // a wave runs the certificate when at least certMin of its lanes are due; a ray it fails on is due again certRepeat steps later (0: never)
+    uint32_t cert, certPrim, certShadow, certMin, certRepeat;
 };
 
 #ifdef __cplusplus

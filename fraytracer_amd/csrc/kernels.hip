@@ -1232,6 +1232,7 @@ __constant__ float FT_AO_DIRS[16][3] = {
 
 struct LaneState {
     uint32_t phase, job, steps, lidx, leaf, outIdx;
+    uint32_t certAt;      // lean kernel: the step count from which the current ray is due for a miss certificate (0xffffffff: not)
     f3 o, dir;            // current ray (primary, then the shadow ray of light lidx)
     float len, eps;
     // in LDS (ft_sh rows), not here: hp = result.Ray.Origin after Ray.move -eps (SdfObject.fs:73) = result.Position; nrm = the three probes
@@ -1319,6 +1320,62 @@ __device__ __forceinline__ bool ft_never_enters(const FtSceneDev& S, const f3 o,
     const float b = ft_dot(w, dir);
     if (b >= 0.0f) return true;
     return cc * dd - b * b > tol * dd;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Miss certificate (FT_OPT_CERT; lean kernel and its EXTENSION build, paths outside glass bodies).  The scene is ONE smooth union of staged spheres, f(x) = -s ln sum_i exp(si d_i(x))
+// with si = -1 / s < 0 (SdfForm.fs:75-82), so on a segment S every term is at most exp(si dmin_i), dmin_i = dist(S, c_i) - r_i, and
+//     f(x) >= -s ln sum_i exp(si dmin_i)    for every x on S.
+// S is the rest of the lane's line, o + t dir with 0 <= t < Length * certLenF, clipped to the ball of radius escR + epsilon + certClip around escC: outside
+// it the support sphere decides already.  If the sum is below exp(si (epsilon + certM)), no evaluation the reference makes along the rest of its march can come
+// below epsilon (scene.cpp "Miss certificate": the margin covers the float32 drift of the marched points, a minimum step length, the reference's float32
+// evaluation and this function's own arithmetic), so the march ends in a miss exactly as if ft_never_enters had said so.  The bound need not be bit-exact:
+// v_sqrt_f32, v_exp_f32 and fused multiply-adds; 20 VALU instructions per child against 25 for an evaluation, and the loop leaves as soon as every testing
+// lane's sum has reached the threshold (a ray that will hit, or pass close, fails within the first children that matter to it).
+// Gated like the escape shortcut: a support sphere and the certificate's constants (certM >= 0: none with a non-finite constant anywhere), 0 <= epsilon <= escR,
+// Length < 1e9, and the drift bound's own conditions: 0.81 <= |dir|^2 <= 1.44, a start within sqrt(certRho2) of escC, certSteps short of the step cap.
+// Executed by all 64 lanes (wave-uniform loop); `test`: the lanes that ask.  -> the certificate holds in this lane.
+__device__ __forceinline__ bool ft_miss_certificate(const FtSceneDev& S, const float* __restrict__ ldsC, bool test, const f3 o, const f3 dir, float eps, float len,
+                                                    uint32_t steps) {
+    const FtInstr FT_CONST* in = as_const(S.instr);                    // instruction 0: the run (scene.cpp sets certM only for {RUN, FIN, SETLEAF})
+    const float si = in->f0;
+    const uint32_t n = in->count;
+    const float4* c = reinterpret_cast<const float4*>(ldsC + in->data);
+    const f3 w = o - mk3(S.escC[0], S.escC[1], S.escC[2]);
+    const float ww = ft_dot(w, w), dd = ft_dot(dir, dir), b = ft_dot(w, dir);
+    bool ok = test && S.certM >= 0.0f && S.escR >= 0.0f && eps >= 0.0f && eps <= S.escR && len > 0.0f && len < 1e9f && dd >= 0.81f && dd <= 1.44f &&
+              ww <= S.certRho2 && steps < FT_STEP_CAP - S.certSteps;
+    const float R = (S.escR + eps + S.certClip) * 1.001f;              // the 0.1 % covers the rounding of the end points below
+    const float disc = b * b - dd * (ww - R * R);
+    ok = ok && disc > 0.0f;
+    const float sq = __builtin_amdgcn_sqrtf(ok ? disc : 0.0f), idd = 1.0f / dd;
+    const float t0 = __builtin_fmaxf((-b - sq) * idd, 0.0f), t1 = __builtin_fminf((sq - b) * idd, len * S.certLenF);
+    ok = ok && t1 > t0;
+    const float A = si * 1.44269504f;                                  // terms are 2^(A (dist - r))
+    const float xt = A * (eps + S.certM);
+    ok = ok && xt >= -100.0f;                                          // the threshold stays a normal number, far above flushed terms
+    if (__ballot(ok) == 0ull) return false;
+    const float thr = __builtin_amdgcn_exp2f(xt) * 0.9999f;
+    const f3 p0 = ok ? o + dir * t0 : mk3(0.0f, 0.0f, 0.0f);           // the segment p0 + t sv, 0 <= t <= 1
+    const f3 sv = ok ? dir * (t1 - t0) : mk3(1.0f, 0.0f, 0.0f);
+    const float iss = 1.0f / ft_dot(sv, sv);
+    float sum = 0.0f;
+    uint32_t i = 0;
+    auto term = [&](const float4 prm) {
+        const float vx = prm.x - p0.x, vy = prm.y - p0.y, vz = prm.z - p0.z;
+        float t = __builtin_fmaf(vz, sv.z, __builtin_fmaf(vy, sv.y, vx * sv.x)) * iss;
+        t = __builtin_amdgcn_fmed3f(t, 0.0f, 1.0f);
+        const float ex = __builtin_fmaf(-t, sv.x, vx), ey = __builtin_fmaf(-t, sv.y, vy), ez = __builtin_fmaf(-t, sv.z, vz);
+        const float q = __builtin_fmaf(ez, ez, __builtin_fmaf(ey, ey, ex * ex));
+        return __builtin_amdgcn_exp2f((__builtin_amdgcn_sqrtf(q) - prm.w) * A);
+    };
+    for (; i + 8u <= n; i += 8u) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) sum += term(c[i + j]);
+        if (__ballot(ok && sum < thr) == 0ull) return false;           // every testing lane has failed
+    }
+    for (; i < n; ++i) sum += term(c[i]);
+    return ok && sum < thr;
 }
 
 // The first step of a ray that starts at the hit position, from the distance already known there (FT_SH_D0): exactly what the round's switch does with an
@@ -1416,7 +1473,7 @@ __device__ __forceinline__ void settle(const FtRenderArgs& a, LaneState& s) {
                                                                        // intensity lc / distance2 (:40): formed when the ray has missed (PH_SHADOW above)
                 }
                 s.steps = 0; ft_count(FT_C_SHADOW);
-                s.phase = PH_SHADOW;
+                s.phase = PH_SHADOW; s.certAt = a.certShadow;
                 if (a.reuse != 0u) {
                     const int r = first_step_from_cache(s);
                     if (r == 1) { ft_count(FT_C_HITS); s.lidx += 1; s.phase = PH_LIGHTS; }     // shadowed at once (SdfLight.fs:20)
@@ -1464,7 +1521,7 @@ __device__ __forceinline__ void start_job(const FtRenderArgs& a, LaneState& s, c
     }
     if (EXT) s.xs &= 0xffffu;                                          // outside, no interaction yet
     s.steps = 0; ft_count(FT_C_PRIMARY);
-    s.phase = PH_MARCH;
+    s.phase = PH_MARCH; s.certAt = a.certPrim;
     if (camKnown && s.len > 0.0f) {                                    // the ray's first evaluation is Distance(camera position) (SdfForm.fs:94-96): known, see PH_CAM — what the round's
         if (dCam != dCam) { ft_flag(1u); s.len = -1.0f; }              // switch does with it for a PH_MARCH lane: NaN (flagged, a miss),
         else if (dCam < s.eps) { ft_count(FT_C_HITP); s.leaf = leafCam; s.phase = PH_NX; }   // a hit at the camera itself,
@@ -1519,7 +1576,7 @@ __device__ __forceinline__ void glass_bounce(const FtRenderArgs& a, LaneState& s
     }
     s.xs += 0x10000u;
     s.len = a.length; s.steps = 0;
-    s.phase = PH_MARCH;
+    s.phase = PH_MARCH; s.certAt = a.certPrim;                         // a new path segment: due like a primary ray
 }
 
 __device__ __forceinline__ unsigned long long wave_sum(uint32_t v) {
@@ -1554,7 +1611,7 @@ __device__ __forceinline__ void ft_trace_body(const FtRenderArgs& a) {
     uint32_t nEvals = 0;                                               // scene evaluations of this wave's rays (wave-uniform: summed per round)
     bool exhausted = false;
     LaneState s;
-    s.phase = PH_IDLE; s.job = 0; s.steps = 0; s.lidx = 0; s.leaf = 0; s.outIdx = 0;
+    s.phase = PH_IDLE; s.job = 0; s.steps = 0; s.lidx = 0; s.leaf = 0; s.outIdx = 0; s.certAt = 0xffffffffu;
     s.o = s.dir = mk3(0, 0, 0);
     s.len = 0; s.eps = 0;
     s.xs = 0;
@@ -1602,6 +1659,20 @@ __device__ __forceinline__ void ft_trace_body(const FtRenderArgs& a) {
         }
         if (s.phase == PH_IDLE && exhausted && chunkNext == chunkEnd) s.phase = PH_DONE;
         if (__ballot(s.phase != PH_DONE) == 0ull) break;
+
+        // ---- miss certificate (lean kernel): once enough lanes are due, the wave tries it for all of them at once ("Miss certificate") ----
+        if (VARIANT == 1 && a.cert != 0u) {                          // EXTENSION builds: not inside a glass body (the march runs on -Distance there)
+            const bool due = (s.phase == PH_MARCH || s.phase == PH_SHADOW) && s.steps >= s.certAt && (!EXT || !s.inside());
+            if ((uint32_t)__popcll(__ballot(due)) >= a.certMin) {
+                const bool holds = ft_miss_certificate(a.S, ldsC + 0, due, s.o, s.dir, s.eps, s.len, s.steps);
+                if (due) {
+                    if (holds) { s.len = -1.0f; settle<EXT>(a, s); }    // resolved as the miss its march ends in (settle: as for ft_never_enters)
+                    else s.certAt = a.certRepeat != 0u ? s.steps + a.certRepeat : 0xffffffffu;
+                }
+                // every lane resolved (a tile whose rays all miss): refill now instead of spending an empty round
+                if (__ballot(s.phase >= PH_MARCH) == 0ull) continue;
+            }
+        }
 
         // ---- one scene-SDF evaluation per active lane -----------------------------------------
         const bool active = s.phase >= PH_MARCH;

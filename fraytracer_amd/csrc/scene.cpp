@@ -871,6 +871,7 @@ bool flatten(const Builder& b, int object, const float bg[3], const int* lights,
     //     (Short rays — kernels.hip: Length <= 10 escR, the whole march within 2.5 escR of c — make at most Length / g + 1 <= 20 Rp / padDrift + 1 steps of error
     //     <= e(2.5 Rp): inside the near budget whatever |Direction| is.)
     Support sup;
+    double escCInf = -1.0;                                             // |escC|inf where a support sphere is known (the miss certificate below)
     if (finiteTree(b, b.objects[object].form) && supportOf(b, b.objects[object].form, sup) && sup.r < 1e15 && std::fabs(sup.c[0]) + std::fabs(sup.c[1]) + std::fabs(sup.c[2]) < 1e15) {
         out.escC[0] = (float)sup.c[0]; out.escC[1] = (float)sup.c[1]; out.escC[2] = (float)sup.c[2];
         const double cInf = std::max(std::fabs(sup.c[0]), std::max(std::fabs(sup.c[1]), std::fabs(sup.c[2])));
@@ -883,6 +884,7 @@ bool flatten(const Builder& b, int object, const float bg[3], const int* lights,
             padDrift = 1.01 * (0.5 * (k + std::sqrt(k * k + 160.0 * k * Rp)));
         }
         out.escR = (float)((sup.r + padEval + padDrift) * (1.0 + 1e-6));
+        escCInf = cInf;
         auto approach = [&](double rho0) { return (7.5 * std::log(8.0 * rho0 / padDrift) + 1.0) * u3 * (cInf + rho0); };
         double lo = 0.0, hi = 1e15;                                    // largest start distance whose approach drift stays <= padDrift / 4
         if (approach(padDrift) > 0.25 * padDrift) hi = 0.0;
@@ -903,6 +905,59 @@ bool flatten(const Builder& b, int object, const float bg[3], const int* lights,
         if (in.op == FT_OP_SMOOTH_RUN && (in.flags & FT_FLAG_FAST) && in.count >= 32u && in.count > best && in.f0 < 0.0f && in.data + 4u * in.count <= out.nStage) { best = in.count; out.cullPc = pc; }
     }
     if (out.fastPath == 0u && carvedShape(out)) out.fastPath = 3u;
+    // Miss certificate (kernels.hip ft_miss_certificate), for a program that is ONE smooth union of staged spheres:  f(x) = -s ln sum_i exp(si d_i(x)),
+    // si = -1 / s, d_i(x) = |x - c_i| - r_i  (SdfForm.fs:75-82).  On a segment S every d_i(x) >= dmin_i = dist(S, c_i) - r_i, and si < 0, so
+    //     f(x) >= F_lo(S) = -s ln sum_i exp(si dmin_i)    for every x on S,  and  f(x) >= F_lo(S) - delta  within delta of S.
+    // The kernel ends a ray as a miss when F_lo of the rest of its line, clipped to the ball where the support sphere does not decide already, is at
+    // least epsilon + certM.  What certM has to cover (u = 2^-24; escR, Rp as in "drift of the marched points" above; n children):
+    //   (1) the drift of the marched points: a tube of radius delta around the line;
+    //   (2) a step length h: every evaluation must return >= g = epsilon + h, so that steps cannot get short and the drift stays bounded;
+    //   (3) the float32 evaluation of the reference (distances, sum, exp, log) and the certificate's own float32 arithmetic.
+    // The drift bound (the same per-step error e(rho) = 3 * 2^-23 (|c|inf + rho) as above).  The kernel certifies rays with 0 <= epsilon <= escR,
+    // 0.81 <= |dir|^2 <= 1.44 (a = |dir| in [0.9, 1.2]) that start within Rb = 2.5 escR of c (certRho2).  Suppose the drift so far is <= delta.
+    //   * An evaluated point q with |q - c| >= r + padEval + g is no hit and returns >= g by the support property and padEval.  Any other q lies within
+    //     delta of a line point p with |p - c| < r + padEval + g + delta <= escR + epsilon + h + delta (= the clip radius: certClip = h + delta) and
+    //     parameter t in [0, Length * certLenF) (below): p is on the certified segment, so f(q) >= F_lo - delta and the float32 value is >= F_lo - delta - (3)
+    //     >= epsilon + h.  Every step is >= g >= h; no step is a hit.
+    //   * Steps that start inside the ball B(c, Rb): consecutive starts are >= a h apart along a chord of length <= 2 (Rb + delta), so there are at most
+    //     N = 2 (Rb + delta) / (0.9 h) + 1 of them.  A step is at most |q - c| + escR + padEval <= 1.5 Rb long (Distance <= the nearest child's distance), so
+    //     start and end lie within 3 Rb of c: each adds <= e(3 Rb).  delta = h is the root of  N e(3 Rb) = delta  (times 1.01).
+    //   * The line leaves B(c, Rb) once, moving away: from there every point is >= rho - delta - (r + padEval) >= rho - 2 escR >= 0.2 rho farther from the
+    //     support sphere than epsilon allows, steps are >= 0.19 rho, rho grows by >= 1.014 per step, and the errors of these receding steps form a geometric
+    //     series <= 72 e(rho) <= 0.011 rho (|c|inf <= 1000 Rp) < 0.2 rho: no hit out there either.
+    //   * Length: the reference counts Length down in float32, each step rounding by <= u Length, so an evaluated point's exact parameter is < Length (1 + N 2u):
+    //     certLenF.  Steps left: <= N + 2000 receding ones (Length < 1e9): certSteps, so that no step-cap flag can be lost.
+    // (3): distances on either side: <= 8u (|c_i - q| + |r_i|) for the reference's sqrt(sum of squares) - r, <= 16u (|escC|inf + 10 escR) for the certificate's
+    // segment point and projection; the kernel's clip radius is enlarged by 0.1 %, which covers the rounding of its end points.  Relative errors of the
+    // sums: n + 2 roundings of the reference's float sum, <= 1 ulp for each exp (the fixed ft_exp 0.93 ulp, glibc's expf < 1), log 0.51 ulp; the certificate's
+    // v_exp_f32 / v_sqrt_f32 (1 ulp), its own sum (n roundings), terms below 2^-126 flushed (their sum < n 2^-26 of a threshold >= 2^-100), and the threshold
+    // (scaled by 1 - 1e-4): at most (2n + 4096) 2^-23 + 2e-4 of the sum, which is s times that in distance.
+    if (out.fastPath == 1u && escCInf >= 0.0 && out.escR >= 0.0f && out.instr.size() == 3 && out.nMainInstr == 3) {
+        const FtInstr& run = out.instr[0];
+        const bool shape = run.op == FT_OP_SMOOTH_RUN && (run.flags & FT_FLAG_INIT) && (run.flags & FT_FLAG_FAST) && run.count >= 1u && run.f0 < 0.0f &&
+                           std::isfinite(run.f0) && run.data + 4u * run.count <= out.nStage &&
+                           out.instr[1].op == FT_OP_SMOOTH_FIN && out.instr[2].op == FT_OP_SETLEAF;
+        const double strength = shape ? (double)out.instr[1].f0 : 0.0;
+        if (shape && strength > 0.0 && std::isfinite(strength)) {
+            const double escR = out.escR, u = 0x1p-24;
+            const double Rb = 2.5 * escR * 1.001;                      // the start gate compares |w|^2 in float32
+            const double e3 = 3.0 * 0x1p-23 * (escCInf + 3.0 * Rb);
+            // 0.9 delta^2 = 2 e (Rb + delta) + 0.9 e delta
+            const double delta = 1.01 * ((2.9 * e3) + std::sqrt(2.9 * e3 * 2.9 * e3 + 7.2 * e3 * Rb)) / 1.8;
+            const double h = delta;
+            const double N = 2.0 * (Rb + delta) / (0.9 * h) + 1.0;
+            const double eGeo = 8.0 * u * (3.0 * escR + 2.0 * escR) + 16.0 * u * (escCInf + 10.0 * escR);
+            const double eSum = strength * ((2.0 * run.count + 4096.0) * 0x1p-23 + 2e-4);
+            const double M = (delta + h + 2.0 * eGeo + eSum) * 1.01 + 1e-6;
+            if (N + 2000.0 < 0.25 * FT_STEP_CAP && M < 0.5 * escR) {
+                out.certM = (float)(M * (1.0 + 1e-6));
+                out.certClip = (float)((delta + h) * (1.0 + 1e-6));
+                out.certRho2 = (float)(2.5 * escR * 2.5 * escR);
+                out.certLenF = (float)(1.0 + (N + 2.0) * 4.0 * u);
+                out.certSteps = (uint32_t)(N + 2000.0);
+            }
+        }
+    }
     for (int i = 0; i < nLights; ++i) {
         if (lights[i] < 0 || (size_t)lights[i] >= b.lights.size()) { err = "invalid light handle"; return false; }
         out.lights.push_back(b.lights[lights[i]].dev);

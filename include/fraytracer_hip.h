@@ -133,6 +133,10 @@ typedef enum ft_option {
                                    * has just evaluated the scene (SdfForm.fs:112, SdfObject.fs:73: the same point, bit for bit); the first evaluation of its march is
                                    * that value and is not computed again; likewise every primary ray of ft_render starts at the camera position, which each wave evaluates
                                    * once (same frame, same ray and hit counters, fewer sdf_evals); 0: evaluated once per ray, as the reference does */
+    FT_OPT_CERT = 14,             /* 1 (default): the smooth-union-of-spheres kernel ends a ray as a miss once a bound over the rest of its line proves that no later
+                                   * evaluation can come below epsilon (exact: same frame, counters and flags, fewer sdf_evals); only while FT_OPT_ESCAPE is on; 0: off */
+    FT_OPT_CERT_POLICY = 15,      /* 0 (default policy) or, for experiments, when the miss certificate is tried: bits 0-7 the primary ray's step (255: never),
+                                   * 8-15 the shadow ray's step (255: never), 16-23 the due lanes a wave waits for (1 .. 64), 24-31 steps to the next try (0: once) */
     FT_OPT_GUIDED = 7             /* 1: the last jobs of a launch are handed out in half and quarter tiles (lean kernel); 0 (default): whole tiles only */
 } ft_option;
 /* MathF.Exp / MathF.Log (SdfForm.unionSmooth, SdfForm.fs:80,82) and MathF.Pow (FColor.gammaInverse, FColor.fs:50-55) are the C runtime's
@@ -283,6 +287,9 @@ int ft_scene_grid_dump(const ft_scene*, int32_t g, uint32_t* cell_start, float* 
 /* the scene's support sphere (centre xyz, radius): no point farther than epsilon from it can be a hit, which is what FT_OPT_ESCAPE relies on;
  * radius < 0: none is known for this scene (degenerate shapes, a unionSmooth of strength <= 0) and every ray marches to its end */
 int ft_scene_support_sphere(const ft_scene*, float centre_radius[4]);
+/* the constants of the smooth-union kernel's miss certificate (FT_OPT_CERT; margin < 0: the scene has none):
+ * margin certM, clip padding certClip, squared start radius certRho2, Length factor certLenF, steps left certSteps */
+int ft_scene_miss_certificate(const ft_scene*, float out[5]);
 
 /* math primitives of the device path, evaluated on the GPU: op 0 exp, 1 log, 2 sqrt, 3 a/b, 4 fast sqrt, 5 fast exp
  * (y = second operand, may be NULL otherwise).  Used by tests/test_math_parity.py. */
