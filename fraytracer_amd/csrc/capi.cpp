@@ -11,7 +11,6 @@
 #include "../../include/fraytracer_hip.h"
 #include "build_hash.h"      // FT_SOURCE_HASH: written by the Makefile (source_hash.py)
 #include "ft_kernels.h"
-#include "ft_libm.h"         // FT_LIBM_TAB_DOUBLES (LDS footprint of the *_libm kernels)
 #include "scene.hpp"
 
 #ifndef FT_BUILD_KIND
@@ -51,7 +50,7 @@ struct ft_ctx {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> events; // one pair per kernel launch since last collect (at most FT_MAX_PENDING_EVENTS)
     std::vector<std::pair<hipEvent_t, hipEvent_t>> eventPool;
     double foldedMs = 0.0;                                 // kernel time of launches whose event pair was already recycled
-    // ft_ctx_set_option (experiments / A-B runs; every setting renders the same bits)
+    // ft_ctx_set_option (kOptions; experiments / A-B runs: every setting renders the same bits)
     int optRefillMin = 64;                                 // idle lanes a wave waits for before it takes new rays (kernels.hip "Burst refill")
     int optMaxBlocksPerCU = 0;                             // 0: the occupancy limit
     int optHostChunks = 0;                                 // 0: automatic (4 for frames >= 16 MB)
@@ -216,22 +215,6 @@ int uploadScene(ft_ctx* c, ft_scene* s) {
     return FT_OK;
 }
 
-// statistics header, per-lane value slots (distance + material index), the staged constant-pool prefix; the *_libm kernels keep glibc's
-// tables behind that, 8-byte aligned (kernels.hip ft_libm_lds_offset)
-// (kernels.hip ft_libm_lds_offset); the lean kernel keeps one row of FT_COOP_SEG floats per wave behind everything (16-byte aligned) for
-// the latency mode (kernels.hip ft_coop_lds_offset)
-#define FT_COOP_SEG_FLOATS FT_CULL_ROW        // the wave's row of culled children's records (ft_kernels.h); its first 256 floats serve the latency mode
-// traceLaunch: the lean trace kernel keeps its accumulator in a register and is launched with nSlots = 0 (launchTrace) — 2 KB per workgroup
-// that decide between 6 and 7 resident workgroups per CU; every other user of a lean scene (ft_eval_distance) runs the general interpreter
-// variant: the kernel family of a trace launch (launchTrace: FtSceneDev.fastPath, or 0 where a carved scene takes the general kernel)
-size_t ldsBytes(const ft_scene* s, bool libm = false, bool traceLaunch = false, unsigned variant = 0, bool cullRows = true) {
-    const size_t nSlots = (traceLaunch && (variant == 1u || variant == 3u)) ? 0 : s->dev.nSlots;       // the lean and the carved kernels keep their values in registers
-    size_t floats = (size_t)FT_LDS_HDR_FLOATS + nSlots * FT_BLOCK * 2 + (size_t)s->dev.nStage;
-    if (libm) floats = ((floats + 1) & ~(size_t)1) + (size_t)FT_LIBM_TAB_DOUBLES * 2;
-    // one row per wave behind everything: the lean kernel's latency mode and culled children; any other trace kernel's culled children where the scene has a cull site
-    if (s->dev.fastPath == 1u || (cullRows && traceLaunch && variant != 3u && s->dev.cullPc != 0xffffffffu)) floats = ((floats + 3) & ~(size_t)3) + (size_t)FT_COOP_SEG_FLOATS * (FT_BLOCK / 64);
-    return floats * 4;
-}
 // Latency-mode thresholds (rays per wave at or below which each ray is evaluated by all 64 lanes; measured)
 // miss certificate (FT_OPT_CERT_POLICY layout): primary rays at their first step (the one taken from the camera's value), shadow rays at their 6th,
 // a wave runs the certificate once 16 of its lanes are due, one try per ray (DESIGN.md section 4 "Miss certificate": the policies measured)
@@ -239,6 +222,32 @@ constexpr int FT_CERT_POLICY_DEFAULT = 1 | (6 << 8) | (16 << 16);
 constexpr int FT_TAIL_K_LEAN = 32, FT_TAIL_K_GENERAL = 2, FT_TAIL_K_CARVED = 1;      // carved: 1.26 ms at 0 / 1 against 1.29 at 2 on the 1000^2 Program.fs frame (profiles/r04_carved_variants.txt)
 // does this launch take the glibc build of the kernels?
 bool libmLaunch(const ft_ctx* c, const ft_scene* s) { return c->optMath != FT_MATH_FIXED && s->usesExpLog; }
+
+// What a trace launch runs: the kernel family (FtSceneDev.fastPath of the launch; kernels.hip ft_trace_kernel_for), its arithmetic, its value slots,
+// whether the wave rows for culled children are kept, and the LDS footprint (ft_lds_layout).  The only place these rules live:
+//   * a carved union takes the general kernels for EXTENSION launches, with FT_OPT_CARVED = 0 and with glibc math: the carved kernels have no such builds;
+//   * the lean and the carved kernels keep their values in registers and are launched with nSlots = 0 — for the lean kernel 2 KB per workgroup
+//     that decide between 6 and 7 resident workgroups per CU (every other user of a lean scene, ft_eval_distance, runs the general interpreter);
+//   * one row per wave behind everything: the lean kernel's latency mode and culled children; any other non-carved kernel's culled children where
+//     the scene has a cull site.  Those are optional: without them the culling pass is off, so they are dropped where the footprint would exceed
+//     the device's limit.  A scene too large even then is refused here, not by a launch failure.
+struct TracePlan { unsigned variant; bool libm, cullRows; uint32_t nSlots; size_t lds; };
+int planTrace(const ft_ctx* c, const ft_scene* s, bool ext, TracePlan& p) {
+    const bool hasCull = s->dev.cullPc != 0xffffffffu;
+    p.libm = libmLaunch(c, s);
+    p.variant = (s->dev.fastPath == 3u && (ext || !c->optCarved || p.libm)) ? 0u : s->dev.fastPath;
+    p.nSlots = (p.variant == 1u || p.variant == 3u) ? 0u : s->dev.nSlots;
+    p.cullRows = p.variant == 1u || (p.variant != 3u && hasCull);
+    int maxLds = 0;
+    HIP_TRY(hipDeviceGetAttribute(&maxLds, hipDeviceAttributeMaxSharedMemoryPerBlock, c->device));
+    p.lds = 4u * (size_t)ft_lds_layout(p.nSlots, s->dev.nStage, p.libm, p.cullRows).total;
+    if (p.lds > (size_t)maxLds && p.variant != 1u && p.cullRows) {
+        p.cullRows = false;
+        p.lds = 4u * (size_t)ft_lds_layout(p.nSlots, s->dev.nStage, p.libm, false).total;
+    }
+    if (p.lds > (size_t)maxLds) return setErr(FT_ERR_UNSUPPORTED, "scene needs " + std::to_string(p.lds) + " bytes of LDS per workgroup; the device offers " + std::to_string(maxLds));
+    return FT_OK;
+}
 
 // A frame loop that never calls ft_collect_stats must not grow the event list: beyond this many pending pairs the
 // oldest one is folded into foldedMs (it has long completed: launches on one stream finish in order) and recycled.
@@ -269,22 +278,11 @@ int acquireEvents(ft_ctx* c, hipEvent_t& a, hipEvent_t& b) {
 int launchTrace(ft_ctx* c, const ft_scene* s, FtRenderArgs& a, int lane = 0) {
     hipStream_t stream = lane ? c->lane1 : c->stream;
     uint32_t* counter = c->dCounter + (lane ? 16 : 0);
+    TracePlan plan;
+    int rc = planTrace(c, s, a.ext != 0u, plan); if (rc) return rc;
+    const unsigned variant = plan.variant;
     int perCU = 0;
-    const bool libm = libmLaunch(c, s);
-    // kernel family: a "carved union" scene takes the general kernels for EXTENSION launches and with FT_OPT_CARVED = 0
-    const unsigned variant = (s->dev.fastPath == 3u && (a.ext != 0u || !c->optCarved)) ? 0u : s->dev.fastPath;
-    size_t lds = ldsBytes(s, libm, true, variant);
-    bool cullRows = true;
-    {   // a scene too large for the workgroup's LDS is refused here, not by a launch failure
-        int maxLds = 0;
-        HIP_TRY(hipDeviceGetAttribute(&maxLds, hipDeviceAttributeMaxSharedMemoryPerBlock, c->device));
-        if (lds > (size_t)maxLds && variant != 1u && s->dev.cullPc != 0xffffffffu) {       // the general kernels' culling rows are optional: without them the pass is off
-            cullRows = false;
-            lds = ldsBytes(s, libm, true, variant, false);
-        }
-        if (lds > (size_t)maxLds) return setErr(FT_ERR_UNSUPPORTED, "scene needs " + std::to_string(lds) + " bytes of LDS per workgroup; the device offers " + std::to_string(maxLds));
-    }
-    HIP_TRY(ft_trace_occupancy(variant, s->carve.kind, a.ext != 0u, libm, lds, &perCU));
+    HIP_TRY(ft_trace_occupancy(variant, s->carve.kind, a.ext != 0u, plan.libm, plan.lds, &perCU));
     if (perCU < 1) return setErr(FT_ERR_UNSUPPORTED, "the trace kernel does not fit a compute unit with this scene's LDS footprint");
     perCU = std::min(perCU, 8);
     if (c->optMaxBlocksPerCU > 0) perCU = std::min(perCU, c->optMaxBlocksPerCU);       // FT_OPT_MAX_BLOCKS_PER_CU (experiments)
@@ -325,9 +323,9 @@ int launchTrace(ft_ctx* c, const ft_scene* s, FtRenderArgs& a, int lane = 0) {
     a.S = s->dev;
     a.S.fastPath = variant;
     a.carve = s->carve;
-    if (variant == 1u || variant == 3u) a.S.nSlots = 0;    // the lean and carved kernels use no value slots: their LDS layout has none (ldsBytes)
-    a.math = libm ? 1u : 0u;
-    a.cull = (s->dev.cullPc != 0xffffffffu && variant != 3u && cullRows && c->optCull) ? 1u : 0u;
+    a.S.nSlots = plan.nSlots;
+    a.math = plan.libm ? 1u : 0u;
+    a.cull = (s->dev.cullPc != 0xffffffffu && plan.cullRows && c->optCull) ? 1u : 0u;
     if (!c->optEscape) a.S.escR = -1.0f;
     // miss certificate: lean kernel (and its EXTENSION build: a render and its ft_render_hits twin count the same evaluations), only with the escape
     // shortcut (it rests on the same support sphere and drift bound)
@@ -345,13 +343,44 @@ int launchTrace(ft_ctx* c, const ft_scene* s, FtRenderArgs& a, int lane = 0) {
     a.materialsExt = s->dMaterialsExt;
     HIP_TRY(hipMemsetAsync(counter, 0, sizeof(uint32_t), stream));
     hipEvent_t e0, e1;
-    int rc = foldOldestEvents(c); if (rc) return rc;
+    if ((rc = foldOldestEvents(c))) return rc;
     if ((rc = acquireEvents(c, e0, e1))) return rc;
     HIP_TRY(hipEventRecord(e0, stream));
-    HIP_TRY(ft_launch_trace(&a, blocks, lds, stream));
+    HIP_TRY(ft_launch_trace(&a, blocks, plan.lds, stream));
     HIP_TRY(hipEventRecord(e1, stream));
     c->events.emplace_back(e0, e1);
     return FT_OK;
+}
+
+// ft_ctx_set_option / ft_ctx_get_option: every option's field on ft_ctx (which holds its default), the range it accepts and the message for a
+// value outside it.  Two options accept less than their range: FT_OPT_CHUNK 64, 32 or 16 only, FT_OPT_CERT_POLICY 0 or due lanes in 1 .. 64.
+struct OptionSpec { int32_t id; int ft_ctx::*field; int32_t lo, hi; const char* err; };
+constexpr OptionSpec kOptions[] = {
+    {FT_OPT_REFILL_MIN, &ft_ctx::optRefillMin, 1, 64, "FT_OPT_REFILL_MIN: 1 .. 64"},
+    {FT_OPT_MAX_BLOCKS_PER_CU, &ft_ctx::optMaxBlocksPerCU, 0, 8, "FT_OPT_MAX_BLOCKS_PER_CU: 0 (no cap) .. 8"},
+    {FT_OPT_HOST_CHUNKS, &ft_ctx::optHostChunks, 0, 16, "FT_OPT_HOST_CHUNKS: 0 (automatic) .. 16"},
+    {FT_OPT_HOST_PIN, &ft_ctx::optHostPin, 0, 1, "FT_OPT_HOST_PIN: 0 or 1"},
+    {FT_OPT_TAIL_K, &ft_ctx::optTailK, -1, 64, "FT_OPT_TAIL_K: -1 (default), 0 (off) .. 64"},
+    {FT_OPT_MATH, &ft_ctx::optMath, FT_MATH_FIXED, FT_MATH_GLIBC_SSE2, "FT_OPT_MATH: 0 fixed, 1 glibc (FMA build), 2 glibc (SSE2 build)"},
+    {FT_OPT_GUIDED, &ft_ctx::optGuided, 0, 1, "FT_OPT_GUIDED: 0 or 1"},
+    {FT_OPT_CHUNK, &ft_ctx::optChunk, 16, 64, "FT_OPT_CHUNK: 64, 32 or 16"},
+    {FT_OPT_CULL, &ft_ctx::optCull, 0, 1, "FT_OPT_CULL: 0 or 1"},
+    {FT_OPT_ESCAPE, &ft_ctx::optEscape, 0, 1, "FT_OPT_ESCAPE: 0 or 1"},
+    {FT_OPT_LAZY_UNION, &ft_ctx::optLazyUnion, 0, 1, "FT_OPT_LAZY_UNION: 0 or 1"},
+    {FT_OPT_CARVED, &ft_ctx::optCarved, 0, 1, "FT_OPT_CARVED: 0 or 1"},
+    {FT_OPT_REUSE, &ft_ctx::optReuse, 0, 1, "FT_OPT_REUSE: 0 or 1"},
+    {FT_OPT_CERT, &ft_ctx::optCert, 0, 1, "FT_OPT_CERT: 0 or 1"},
+    {FT_OPT_CERT_POLICY, &ft_ctx::optCertPolicy, INT32_MIN, INT32_MAX, "FT_OPT_CERT_POLICY: 0, or bits 16-23 (due lanes) in 1 .. 64"},
+};
+const OptionSpec* findOption(int32_t id) {
+    for (const OptionSpec& o : kOptions) if (o.id == id) return &o;
+    return nullptr;
+}
+bool optionAccepts(const OptionSpec& o, int32_t v) {
+    if (v < o.lo || v > o.hi) return false;
+    if (o.id == FT_OPT_CHUNK) return v == 64 || v == 32 || v == 16;
+    if (o.id == FT_OPT_CERT_POLICY) { const uint32_t mn = ((uint32_t)v >> 16) & 255u; return v == 0 || (mn >= 1u && mn <= 64u); }
+    return true;
 }
 
 int checkParams(const ft_render_params* p) {
@@ -384,51 +413,18 @@ const char* ft_build_info(void) { return "src=" FT_SOURCE_HASH ";kind=" FT_BUILD
 
 int ft_ctx_set_option(ft_ctx* c, int32_t option, int32_t value) {
     if (!c) return setErr(FT_ERR_INVALID, "null context");
-    switch (option) {
-    case FT_OPT_REFILL_MIN: if (value < 1 || value > 64) return setErr(FT_ERR_INVALID, "FT_OPT_REFILL_MIN: 1 .. 64"); c->optRefillMin = value; return FT_OK;
-    case FT_OPT_MAX_BLOCKS_PER_CU: if (value < 0 || value > 8) return setErr(FT_ERR_INVALID, "FT_OPT_MAX_BLOCKS_PER_CU: 0 (no cap) .. 8"); c->optMaxBlocksPerCU = value; return FT_OK;
-    case FT_OPT_HOST_CHUNKS: if (value < 0 || value > 16) return setErr(FT_ERR_INVALID, "FT_OPT_HOST_CHUNKS: 0 (automatic) .. 16"); c->optHostChunks = value; return FT_OK;
-    case FT_OPT_HOST_PIN: if (value != 0 && value != 1) return setErr(FT_ERR_INVALID, "FT_OPT_HOST_PIN: 0 or 1"); c->optHostPin = value; return FT_OK;
-    case FT_OPT_TAIL_K: if (value < -1 || value > 64) return setErr(FT_ERR_INVALID, "FT_OPT_TAIL_K: -1 (default), 0 (off) .. 64"); c->optTailK = value; return FT_OK;
-    case FT_OPT_CHUNK: if (value != 64 && value != 32 && value != 16) return setErr(FT_ERR_INVALID, "FT_OPT_CHUNK: 64, 32 or 16"); c->optChunk = value; return FT_OK;
-    case FT_OPT_ESCAPE: if (value != 0 && value != 1) return setErr(FT_ERR_INVALID, "FT_OPT_ESCAPE: 0 or 1"); c->optEscape = value; return FT_OK;
-    case FT_OPT_LAZY_UNION: if (value != 0 && value != 1) return setErr(FT_ERR_INVALID, "FT_OPT_LAZY_UNION: 0 or 1"); c->optLazyUnion = value; return FT_OK;
-    case FT_OPT_CULL: if (value != 0 && value != 1) return setErr(FT_ERR_INVALID, "FT_OPT_CULL: 0 or 1"); c->optCull = value; return FT_OK;
-    case FT_OPT_GUIDED: if (value != 0 && value != 1) return setErr(FT_ERR_INVALID, "FT_OPT_GUIDED: 0 or 1"); c->optGuided = value; return FT_OK;
-    case FT_OPT_CARVED: if (value != 0 && value != 1) return setErr(FT_ERR_INVALID, "FT_OPT_CARVED: 0 or 1"); c->optCarved = value; return FT_OK;
-    case FT_OPT_REUSE: if (value != 0 && value != 1) return setErr(FT_ERR_INVALID, "FT_OPT_REUSE: 0 or 1"); c->optReuse = value; return FT_OK;
-    case FT_OPT_CERT: if (value != 0 && value != 1) return setErr(FT_ERR_INVALID, "FT_OPT_CERT: 0 or 1"); c->optCert = value; return FT_OK;
-    case FT_OPT_CERT_POLICY: {
-        const uint32_t v = (uint32_t)value, mn = (v >> 16) & 255u;
-        if (value != 0 && (mn < 1u || mn > 64u)) return setErr(FT_ERR_INVALID, "FT_OPT_CERT_POLICY: 0, or bits 16-23 (due lanes) in 1 .. 64");
-        c->optCertPolicy = value; return FT_OK;
-    }
-    case FT_OPT_MATH:
-        if (value != FT_MATH_FIXED && value != FT_MATH_GLIBC_FMA && value != FT_MATH_GLIBC_SSE2) return setErr(FT_ERR_INVALID, "FT_OPT_MATH: 0 fixed, 1 glibc (FMA build), 2 glibc (SSE2 build)");
-        c->optMath = value; return FT_OK;
-    default: return setErr(FT_ERR_INVALID, "unknown option");
-    }
+    const OptionSpec* o = findOption(option);
+    if (!o) return setErr(FT_ERR_INVALID, "unknown option");
+    if (!optionAccepts(*o, value)) return setErr(FT_ERR_INVALID, o->err);
+    c->*o->field = value;
+    return FT_OK;
 }
 int ft_ctx_get_option(const ft_ctx* c, int32_t option, int32_t* value) {
     if (!c || !value) return setErr(FT_ERR_INVALID, "null argument");
-    switch (option) {
-    case FT_OPT_REFILL_MIN: *value = c->optRefillMin; return FT_OK;
-    case FT_OPT_MAX_BLOCKS_PER_CU: *value = c->optMaxBlocksPerCU; return FT_OK;
-    case FT_OPT_HOST_CHUNKS: *value = c->optHostChunks; return FT_OK;
-    case FT_OPT_HOST_PIN: *value = c->optHostPin; return FT_OK;
-    case FT_OPT_MATH: *value = c->optMath; return FT_OK;
-    case FT_OPT_TAIL_K: *value = c->optTailK; return FT_OK;
-    case FT_OPT_GUIDED: *value = c->optGuided; return FT_OK;
-    case FT_OPT_CARVED: *value = c->optCarved; return FT_OK;
-    case FT_OPT_REUSE: *value = c->optReuse; return FT_OK;
-    case FT_OPT_CERT: *value = c->optCert; return FT_OK;
-    case FT_OPT_CERT_POLICY: *value = c->optCertPolicy; return FT_OK;
-    case FT_OPT_CULL: *value = c->optCull; return FT_OK;
-    case FT_OPT_LAZY_UNION: *value = c->optLazyUnion; return FT_OK;
-    case FT_OPT_ESCAPE: *value = c->optEscape; return FT_OK;
-    case FT_OPT_CHUNK: *value = c->optChunk; return FT_OK;
-    default: return setErr(FT_ERR_INVALID, "unknown option");
-    }
+    const OptionSpec* o = findOption(option);
+    if (!o) return setErr(FT_ERR_INVALID, "unknown option");
+    *value = c->*o->field;
+    return FT_OK;
 }
 
 int ft_ctx_create(int device, ft_ctx** out) {
@@ -973,8 +969,9 @@ int ft_eval_distance(ft_ctx* c, const ft_scene* s, const ft_vec3* pts, int64_t n
     const bool libm = libmLaunch(c, s);
     FtSceneDev dev = s->dev;
     dev.mathFma = c->optMath == FT_MATH_GLIBC_FMA ? 1u : 0u;
+    const size_t lds = 4u * (size_t)ft_lds_layout(dev.nSlots, dev.nStage, libm, dev.fastPath == 1u).total;    // all slots: the general interpreter
     HIP_TRY(ft_launch_eval_points(&dev, libm ? 1 : 0, reinterpret_cast<const float*>(base), n, reinterpret_cast<float*>(base + pBytes),
-                                  reinterpret_cast<int*>(base + pBytes + dBytes), blocks, ldsBytes(s, libm), c->stream));
+                                  reinterpret_cast<int*>(base + pBytes + dBytes), blocks, lds, c->stream));
     HIP_TRY(hipMemcpyAsync(outD, base + pBytes, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
     if (outM) HIP_TRY(hipMemcpyAsync(outM, base + pBytes + dBytes, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));

@@ -5,6 +5,7 @@
 
 #include "../../include/fraytracer_hip.h"
 #include "ft_device.h"
+#include "ft_libm.h"          // FT_LIBM_TAB_DOUBLES: the *_libm kernels' tables in LDS (ft_lds_layout)
 
 #define FT_BLOCK 256          // 4 waves; every wave is an independent persistent worker
 // dynamic LDS of a trace workgroup starts with a header: 64 words (per-wave statistics, the reporting wave's start clocks), in the diagnostic
@@ -23,6 +24,23 @@
 // are the ones dropped most often (the running sum is largest in front of them) — C3 4096^2 34.3 ms at 256, 36.5 at 224
 #define FT_CULL_MAX 256
 #define FT_CULL_ROW (4 * FT_CULL_MAX)
+
+// Dynamic LDS of a trace or eval-points workgroup, in floats: the header above, nSlots x FT_BLOCK value slots (distance), as many
+// (material index), the staged prefix of the constant pool (nStage floats), glibc's tables (*_libm kernels; 8-byte aligned) and one
+// FT_CULL_ROW row per wave (16-byte aligned: written and read as float4).  The one definition of the layout: the kernels take their
+// addresses from it, the host its footprint (4 x total bytes; capi.cpp planTrace).
+struct FtLdsLayout { uint32_t slotD, slotL, consts, libmTab, rows, total; };
+FT_HD FtLdsLayout ft_lds_layout(uint32_t nSlots, uint32_t nStage, bool libm, bool rows) {
+    FtLdsLayout L;
+    L.slotD = FT_LDS_HDR_FLOATS;
+    L.slotL = FT_LDS_HDR_FLOATS + nSlots * FT_BLOCK;
+    L.consts = FT_LDS_HDR_FLOATS + 2u * nSlots * FT_BLOCK;
+    L.libmTab = (L.consts + nStage + 1u) & ~1u;
+    const uint32_t end = libm ? L.libmTab + 2u * FT_LIBM_TAB_DOUBLES : L.consts + nStage;
+    L.rows = (end + 3u) & ~3u;
+    L.total = rows ? L.rows + FT_CULL_ROW * (FT_BLOCK / 64) : end;
+    return L;
+}
 
 struct FtRenderArgs {
     FtSceneDev S;

@@ -63,11 +63,10 @@ __device__ __forceinline__ FtLight ld_light(const FtLight FT_CONST* q) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// Dynamic LDS of a workgroup: [ FT_C_COUNT x FT_BLOCK per-lane statistics words | nSlots x FT_BLOCK value
-// slots (distance) | nSlots x FT_BLOCK slots (material) | staged prefix of the constant pool ].
-// Per-lane statistics live in LDS (word k * FT_BLOCK + tid), not in registers: seven counters would otherwise
-// stay live across the whole SDF evaluation.  One ds_add per event.  They sit first so that their address
-// does not depend on the scene: primitives can raise a flag without being handed a pointer.
+// Dynamic LDS of a workgroup: [ header (statistics words, shading rows) | nSlots x FT_BLOCK value slots (distance) |
+// nSlots x FT_BLOCK slots (material) | staged prefix of the constant pool | glibc's tables (*_libm) | one row per wave ],
+// at the offsets ft_lds_layout (ft_kernels.h) gives the host as well.
+// Statistics live in LDS, not in registers: seven counters would otherwise stay live across the whole SDF evaluation.
 // ------------------------------------------------------------------------------------------------
 extern __shared__ float ft_lds[];
 enum : uint32_t { FT_C_SHADOW = 0, FT_C_HITP, FT_C_HITS, FT_C_PRIMARY, FT_C_FLAGS, FT_C_EXT, FT_C_COUNT };
@@ -106,10 +105,11 @@ __device__ __forceinline__ void sh_set3(uint32_t row, f3 v) { float* q = ft_sh(r
 // MATH = 0: the fixed algorithms of ft_math.h (same bits on every machine; the default).  MATH = 1: glibc's expf / logf restated
 // (ft_libm.h) — what the reference's MathF.Exp / Log (SdfForm.fs:80,82) return under .NET on Linux x86-64.  The MATH = 1 kernels are
 // separate instantiations (the default kernels carry no double-precision code); which of glibc's two builds — FMA or SSE2 — is the
-// wave-uniform FtSceneDev.mathFma.  The 640-byte table block sits in LDS behind the staged constants (8-byte aligned).
+// wave-uniform FtSceneDev.mathFma.  The 640-byte table block sits in LDS behind the staged constants (ft_lds_layout).
 __device__ const ft_u64 ft_libm_tab_g[FT_LIBM_TAB_DOUBLES] = FT_LIBM_TAB_INIT;
-__device__ __forceinline__ uint32_t ft_libm_lds_offset(const FtSceneDev& S) { return (FT_LDS_HDR_FLOATS + 2u * S.nSlots * FT_BLOCK + S.nStage + 1u) & ~1u; }
-__device__ __forceinline__ const ft_u64* ft_libm_tab(const FtSceneDev& S) { return reinterpret_cast<const ft_u64*>(ft_lds + ft_libm_lds_offset(S)); }
+__device__ __forceinline__ const ft_u64* ft_libm_tab(const FtSceneDev& S) {
+    return reinterpret_cast<const ft_u64*>(ft_lds + ft_lds_layout(S.nSlots, S.nStage, true, false).libmTab);
+}
 template <int MATH> __device__ __forceinline__ float ft_exp_m(float x, const FtSceneDev& S) {
     if (MATH == 0) return ft_exp(x);
     return S.mathFma ? ft_glibc_expf<true>(x, ft_libm_tab(S)) : ft_glibc_expf<false>(x, ft_libm_tab(S));
@@ -995,10 +995,6 @@ __device__ __forceinline__ void ft_eval_smooth_spheres(const FtSceneDev& S, cons
 // whenever a wave is that empty, not only at the end of a launch.
 // ------------------------------------------------------------------------------------------------
 #define FT_COOP_SEG 256                       // children per segment = floats of the wave's LDS row the mode uses
-__device__ __forceinline__ uint32_t ft_coop_lds_offset(const FtSceneDev& S, bool libm) {
-    const uint32_t end = libm ? ft_libm_lds_offset(S) + 2u * FT_LIBM_TAB_DOUBLES : FT_LDS_HDR_FLOATS + 2u * S.nSlots * FT_BLOCK + S.nStage;
-    return (end + 3u) & ~3u;                  // 16-byte aligned: the row is written and read as float4
-}
 // one child's term exp(si * (|c - p| - r)) in the regime the point allows: 2 = near (exponent-add exp), 1 = far (ldexp exp), 0 = exact
 // forms — all three give the same bits wherever two of them are valid (ft_selftest_fastmath), so the choice is only about cost
 template <int MATH>
@@ -1591,9 +1587,10 @@ __device__ __forceinline__ void ft_trace_body(const FtRenderArgs& a) {
     // the first wave of block 0 reports the shader clock it ran at (statistics only); its start clocks wait in LDS, not in registers
     unsigned long long* clk0 = reinterpret_cast<unsigned long long*>(ft_lds + 32);
     if (blockIdx.x == 0 && tid == 0) { clk0[0] = clock64(); clk0[1] = wall_clock64(); }
-    float* sd = ft_lds + FT_LDS_HDR_FLOATS + tid;
-    uint32_t* sl = reinterpret_cast<uint32_t*>(ft_lds + FT_LDS_HDR_FLOATS + a.S.nSlots * FT_BLOCK) + tid;
-    float* ldsC = ft_lds + FT_LDS_HDR_FLOATS + 2u * a.S.nSlots * FT_BLOCK; // staged constant pool ("SDF op stack" in LDS)
+    const FtLdsLayout L = ft_lds_layout(a.S.nSlots, a.S.nStage, MATH != 0, true);
+    float* sd = ft_lds + L.slotD + tid;
+    uint32_t* sl = reinterpret_cast<uint32_t*>(ft_lds + L.slotL) + tid;
+    float* ldsC = ft_lds + L.consts;                                   // staged constant pool ("SDF op stack" in LDS)
     for (uint32_t i = tid; i < a.S.nStage; i += FT_BLOCK) ldsC[i] = a.S.consts[i];
     if (MATH != 0 && tid < FT_LIBM_TAB_DOUBLES) const_cast<ft_u64*>(ft_libm_tab(a.S))[tid] = ft_libm_tab_g[tid];   // FT_OPT_MATH: glibc's tables
     if (tid < 32u) reinterpret_cast<uint32_t*>(ft_lds)[tid] = 0u;       // the per-wave statistics words
@@ -1602,8 +1599,9 @@ __device__ __forceinline__ void ft_trace_body(const FtRenderArgs& a) {
 #endif
     __syncthreads();
 
-    // this wave's row (lean kernel: latency mode and culled children; other kernels: culled children of the scene's cull site) — a wave-uniform address
-    float* coopRow = ft_lds + ft_coop_lds_offset(a.S, MATH != 0) + (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6)) * FT_CULL_ROW;
+    // this wave's row (lean kernel: latency mode and culled children; other kernels: culled children of the scene's cull site) — a wave-uniform address.
+    // The offset is formed here, not kept from L: holding it across the staging loop changes the lean kernel's machine code.
+    float* coopRow = ft_lds + ft_lds_layout(a.S.nSlots, a.S.nStage, MATH != 0, true).rows + (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6)) * FT_CULL_ROW;
     uint32_t cullSkipped = 0, cullTotal = 0;                           // (child, ray) pairs the culling pass dropped / looked at (wave-uniform sums)
     uint32_t chunkNext = 0, chunkEnd = 0;                              // wave-uniform
     uint32_t waveEvals = 0;                                            // evaluation rounds of this wave (lane-utilisation statistic)
@@ -1872,15 +1870,6 @@ FT_CARVE_KERNEL(ft_trace_kernel_carved_capsules, FT_PR_CAPSULE, 6)
 FT_CARVE_KERNEL(ft_trace_kernel_carved_tori, FT_PR_TORUS, 6)
 FT_CARVE_KERNEL(ft_trace_kernel_carved_triangles, FT_PR_TRIANGLE, 5)
 FT_CARVE_KERNEL(ft_trace_kernel_carved_mixed, FT_CARVE_MIXED, 5)
-static const void* ft_carved_kernel(unsigned kind) {
-    switch (kind) {
-        case FT_PR_SPHERE: return (const void*)ft_trace_kernel_carved_spheres;
-        case FT_PR_CAPSULE: return (const void*)ft_trace_kernel_carved_capsules;
-        case FT_PR_TORUS: return (const void*)ft_trace_kernel_carved_tori;
-        case FT_PR_TRIANGLE: return (const void*)ft_trace_kernel_carved_triangles;
-        default: return (const void*)ft_trace_kernel_carved_mixed;     // boxes (EXTENSION) and mixed kinds
-    }
-}
 // FT_OPT_MATH = glibc: the same six with MathF.Exp / Log as glibc's expf / logf (scenes that contain a unionSmooth only; every other scene
 // has no exponential and runs the kernels above whatever the option says)
 extern "C" __global__ void __launch_bounds__(FT_BLOCK) ft_trace_kernel_libm(const FtRenderArgs a) { ft_trace_body<0, false, 1>(a); }
@@ -1889,14 +1878,35 @@ extern "C" __global__ void __launch_bounds__(FT_BLOCK) ft_trace_kernel_ext_libm(
 extern "C" __global__ void __launch_bounds__(FT_BLOCK) ft_trace_kernel_smooth_spheres_ext_libm(const FtRenderArgs a) { ft_trace_body<1, true, 1>(a); }
 extern "C" __global__ void __launch_bounds__(FT_BLOCK) ft_trace_kernel_calls_libm(const FtRenderArgs a) { ft_trace_body<2, false, 1>(a); }
 extern "C" __global__ void __launch_bounds__(FT_BLOCK) ft_trace_kernel_calls_ext_libm(const FtRenderArgs a) { ft_trace_body<2, true, 1>(a); }
+// The one table of trace kernels, for launches and occupancy queries alike.  variant: the kernel family (FtSceneDev.fastPath as capi.cpp planTrace
+// decides it: 0 general, 1 lean smooth-sphere, 2 general with call children, 3 carved union).  nullptr where no kernel exists: a carved union has
+// no EXTENSION and no *_libm build.
+static const void* ft_trace_kernel_for(unsigned variant, unsigned carveKind, bool ext, bool libm) {
+    static const void* const families[3][2][2] = {     // [variant][libm][ext]
+        {{(const void*)ft_trace_kernel, (const void*)ft_trace_kernel_ext}, {(const void*)ft_trace_kernel_libm, (const void*)ft_trace_kernel_ext_libm}},
+        {{(const void*)ft_trace_kernel_smooth_spheres, (const void*)ft_trace_kernel_smooth_spheres_ext},
+         {(const void*)ft_trace_kernel_smooth_spheres_libm, (const void*)ft_trace_kernel_smooth_spheres_ext_libm}},
+        {{(const void*)ft_trace_kernel_calls, (const void*)ft_trace_kernel_calls_ext}, {(const void*)ft_trace_kernel_calls_libm, (const void*)ft_trace_kernel_calls_ext_libm}},
+    };
+    if (variant < 3) return families[variant][libm][ext];
+    if (variant > 3 || ext || libm) return nullptr;
+    switch (carveKind) {
+        case FT_PR_SPHERE: return (const void*)ft_trace_kernel_carved_spheres;
+        case FT_PR_CAPSULE: return (const void*)ft_trace_kernel_carved_capsules;
+        case FT_PR_TORUS: return (const void*)ft_trace_kernel_carved_tori;
+        case FT_PR_TRIANGLE: return (const void*)ft_trace_kernel_carved_triangles;
+        default: return (const void*)ft_trace_kernel_carved_mixed;     // boxes (EXTENSION) and mixed kinds
+    }
+}
 
 // scene.Object.Form.Distance at explicit points (test / diagnostic entry)
 template <int MATH>
 __device__ __forceinline__ void ft_eval_points_body(const FtSceneDev& S, const float* __restrict__ pts, long long n, float* __restrict__ outD, int* __restrict__ outM) {
     const uint32_t tid = threadIdx.x;
-    float* sd = ft_lds + FT_LDS_HDR_FLOATS + tid;                  // same LDS layout as the trace kernel (flag words first, unused here)
-    uint32_t* sl = reinterpret_cast<uint32_t*>(ft_lds + FT_LDS_HDR_FLOATS + S.nSlots * FT_BLOCK) + tid;
-    float* ldsC = ft_lds + FT_LDS_HDR_FLOATS + 2u * S.nSlots * FT_BLOCK;
+    const FtLdsLayout L = ft_lds_layout(S.nSlots, S.nStage, MATH != 0, false);   // the trace kernel's layout (header unused here)
+    float* sd = ft_lds + L.slotD + tid;
+    uint32_t* sl = reinterpret_cast<uint32_t*>(ft_lds + L.slotL) + tid;
+    float* ldsC = ft_lds + L.consts;
     for (uint32_t i = tid; i < S.nStage; i += FT_BLOCK) ldsC[i] = S.consts[i];
     if (MATH != 0 && tid < FT_LIBM_TAB_DOUBLES) const_cast<ft_u64*>(ft_libm_tab(S))[tid] = ft_libm_tab_g[tid];
     __syncthreads();
@@ -2195,37 +2205,20 @@ extern "C" int ft_debug_set_hsaco(const char* path) {
 }
 #endif
 extern "C" hipError_t ft_launch_trace(const FtRenderArgs* a, unsigned blocks, size_t ldsBytes, hipStream_t st) {
-    const bool ext = a->ext != 0u;
-    const unsigned v = a->S.fastPath;
-    if (a->math != 0u) {                // FT_OPT_MATH = glibc, scene with a unionSmooth
-        if (v == 1 && ext) hipLaunchKernelGGL(ft_trace_kernel_smooth_spheres_ext_libm, dim3(blocks), dim3(FT_BLOCK), ldsBytes, st, *a);
-        else if (v == 1) hipLaunchKernelGGL(ft_trace_kernel_smooth_spheres_libm, dim3(blocks), dim3(FT_BLOCK), ldsBytes, st, *a);
-        else if (v == 2 && ext) hipLaunchKernelGGL(ft_trace_kernel_calls_ext_libm, dim3(blocks), dim3(FT_BLOCK), ldsBytes, st, *a);
-        else if (v == 2) hipLaunchKernelGGL(ft_trace_kernel_calls_libm, dim3(blocks), dim3(FT_BLOCK), ldsBytes, st, *a);
-        else if (ext) hipLaunchKernelGGL(ft_trace_kernel_ext_libm, dim3(blocks), dim3(FT_BLOCK), ldsBytes, st, *a);
-        else hipLaunchKernelGGL(ft_trace_kernel_libm, dim3(blocks), dim3(FT_BLOCK), ldsBytes, st, *a);
-        return hipGetLastError();
-    }
+    const bool ext = a->ext != 0u, libm = a->math != 0u;
 #ifdef FT_EXPERIMENT
-    if (v == 1 && !ext && ft_exp_fn) {
+    if (a->S.fastPath == 1 && !ext && !libm && ft_exp_fn) {
         FtRenderArgs args = *a;
         size_t size = sizeof(args);
         void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &args, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
         return hipModuleLaunchKernel(ft_exp_fn, blocks, 1, 1, FT_BLOCK, 1, 1, (unsigned)ldsBytes, st, nullptr, extra);
     }
-#endif                                  // 0 general, 1 lean smooth-sphere, 2 general with call children, 3 carved union
-    if (v == 3 && !ext) {
-        FtRenderArgs args = *a;
-        void* kp[] = {&args};
-        return hipLaunchKernel(ft_carved_kernel(a->carve.kind), dim3(blocks), dim3(FT_BLOCK), kp, ldsBytes, st);
-    }
-    if (v == 1 && ext) hipLaunchKernelGGL(ft_trace_kernel_smooth_spheres_ext, dim3(blocks), dim3(FT_BLOCK), ldsBytes, st, *a);
-    else if (v == 1) hipLaunchKernelGGL(ft_trace_kernel_smooth_spheres, dim3(blocks), dim3(FT_BLOCK), ldsBytes, st, *a);
-    else if (v == 2 && ext) hipLaunchKernelGGL(ft_trace_kernel_calls_ext, dim3(blocks), dim3(FT_BLOCK), ldsBytes, st, *a);
-    else if (v == 2) hipLaunchKernelGGL(ft_trace_kernel_calls, dim3(blocks), dim3(FT_BLOCK), ldsBytes, st, *a);
-    else if (ext) hipLaunchKernelGGL(ft_trace_kernel_ext, dim3(blocks), dim3(FT_BLOCK), ldsBytes, st, *a);
-    else hipLaunchKernelGGL(ft_trace_kernel, dim3(blocks), dim3(FT_BLOCK), ldsBytes, st, *a);
-    return hipGetLastError();
+#endif
+    const void* k = ft_trace_kernel_for(a->S.fastPath, a->carve.kind, ext, libm);
+    if (!k) return hipErrorInvalidDeviceFunction;
+    FtRenderArgs args = *a;
+    void* kp[] = {&args};
+    return hipLaunchKernel(k, dim3(blocks), dim3(FT_BLOCK), kp, ldsBytes, st);
 }
 extern "C" hipError_t ft_launch_eval_points(const FtSceneDev* S, int math, const float* pts, long long n, float* outD, int* outM,
                                             unsigned blocks, size_t ldsBytes, hipStream_t st) {
@@ -2316,15 +2309,7 @@ extern "C" hipError_t ft_debug_union_counters(unsigned long long out[12]) {
 }
 #endif
 extern "C" hipError_t ft_trace_occupancy(unsigned fastPath, unsigned carveKind, bool ext, bool libm, size_t ldsBytes, int* blocksPerCU) {
-    if (fastPath == 3 && !ext) return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocksPerCU, ft_carved_kernel(carveKind), FT_BLOCK, ldsBytes);
-    if (libm) {
-        const void* kl = fastPath == 1 ? (ext ? (const void*)ft_trace_kernel_smooth_spheres_ext_libm : (const void*)ft_trace_kernel_smooth_spheres_libm)
-                       : fastPath == 2 ? (ext ? (const void*)ft_trace_kernel_calls_ext_libm : (const void*)ft_trace_kernel_calls_libm)
-                                       : (ext ? (const void*)ft_trace_kernel_ext_libm : (const void*)ft_trace_kernel_libm);
-        return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocksPerCU, kl, FT_BLOCK, ldsBytes);
-    }
-    const void* k = fastPath == 1 ? (ext ? (const void*)ft_trace_kernel_smooth_spheres_ext : (const void*)ft_trace_kernel_smooth_spheres)
-                  : fastPath == 2 ? (ext ? (const void*)ft_trace_kernel_calls_ext : (const void*)ft_trace_kernel_calls)
-                                  : (ext ? (const void*)ft_trace_kernel_ext : (const void*)ft_trace_kernel);
+    const void* k = ft_trace_kernel_for(fastPath, carveKind, ext, libm);
+    if (!k) return hipErrorInvalidDeviceFunction;
     return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocksPerCU, k, FT_BLOCK, ldsBytes);
 }

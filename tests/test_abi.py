@@ -69,6 +69,10 @@ def test_the_library_reads_no_environment_variables():
         assert "getenv" not in open(os.path.join(ROOT, "fraytracer_amd", "csrc", f)).read(), f
     host = ft.Device(-1)                       # options are plain context state: usable without a GPU
     try:
+        defaults = {"refill_min": 64, "max_blocks_per_cu": 0, "host_chunks": 0, "host_pin": 1, "math": 0, "tail_k": -1, "guided": 0, "chunk": 64,
+                    "cull": 1, "escape": 1, "lazy_union": 1, "carved": 1, "reuse": 1, "cert": 1, "cert_policy": 0}
+        assert set(defaults) == set(ft.Device.OPTIONS)
+        assert {k: host.get_option(k) for k in defaults} == defaults
         assert host.get_option("refill_min") == 64 and host.get_option("host_pin") == 1
         host.set_option("refill_min", 32); host.set_option("host_chunks", 2); host.set_option("host_pin", 0); host.set_option("max_blocks_per_cu", 3)
         assert [host.get_option(k) for k in ("refill_min", "host_chunks", "host_pin", "max_blocks_per_cu")] == [32, 2, 0, 3]
@@ -81,7 +85,8 @@ def test_the_library_reads_no_environment_variables():
             host.set_option(k, 0); assert host.get_option(k) == 0
             host.set_option(k, 1)
         for name, bad in (("refill_min", 0), ("refill_min", 65), ("host_chunks", 17), ("host_pin", 2), ("max_blocks_per_cu", -1),
-                          ("math", 3), ("tail_k", 65), ("tail_k", -2), ("guided", 2), ("chunk", 48), ("cull", 2), ("escape", -1), ("lazy_union", 2)):
+                          ("math", 3), ("tail_k", 65), ("tail_k", -2), ("guided", 2), ("chunk", 48), ("cull", 2), ("escape", -1), ("lazy_union", 2),
+                          ("carved", 2), ("reuse", -1), ("cert", 2), ("cert_policy", 1), ("cert_policy", 65 << 16)):
             try:
                 host.set_option(name, bad)
             except ft.FrayTracerError as e:
