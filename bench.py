@@ -14,8 +14,13 @@ frame k+1 renders; all K frames are complete on rank 0 when the timed region end
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
     python bench.py --gpus 1 --steps 3 --warmup 1 --dump-outputs DIR     # + the last timed frame as DIR/*.npy
+    python bench.py --gpus 1 --steps 3 --warmup 1 --full                 # + everything below that takes runs of its own
 
-Rank 0 prints ONE JSON line.  `roofline` prices the trace kernel against the f32 VALU peak
+Rank 0 prints ONE JSON line.  A plain run does only what that line's headline needs: it sets up, warms up, times the K steps, writes
+--dump-outputs and prints the line, with the roofline of the timed launches.  --full adds the rest: before the warm-up, the untimed
+launch that counts the reference's work (`*_reference_work`, `config.sdf_evals_per_frame`); after the timed region, the side measurements
+(4 spp, two lanes, host output, primary + AO target, Program.fs scene, glibc arithmetic; N > 1: C4 at 8192x8192), `cpu_baseline` and
+the checks against the CPU oracle (`config.max_abs_delta_vs_oracle`).  `roofline` prices the trace kernel against the f32 VALU peak
 (256 CU x 4 SIMD x 32 lanes x 2.4 GHz = 78.6 T lane-ops/s; no FMA contraction is
 allowed by the parity requirement).  `roofline.achieved / frac` are the HARDWARE fraction: the algorithmic lane-ops of the work the timed
 launches EXECUTED (their own exact counters: evaluations after the escape shortcut, children after the culling pass) per second over
@@ -90,20 +95,24 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--size", type=int, default=4096, help="frame is size x size (default: the metric's 4096)")
     ap.add_argument("--spheres", type=int, default=256)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: the reference's work (an untimed launch before the warm-up) and, "
+                         "after the timed region, the side measurements, the CPU baseline and the comparisons with the CPU oracle (the --no-* options "
+                         "below switch parts off)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full, N = 1: skip the CPU baseline and with it the oracle check of the frame")
     ap.add_argument("--no-side", "--no-spp4", dest="no_spp4", action="store_true",
-                    help="skip the side measurements (4 spp, two lanes, host output, primary + AO target, Program.fs scene)")
+                    help="--full: skip the side measurements (4 spp, two lanes, host output, primary + AO target, Program.fs scene)")
     ap.add_argument("--no-reference-launch", action="store_true",
-                    help="profiling passes (tools/profile.sh): skip the untimed launch that counts the reference's evaluations, so that every launch of the "
-                         "trace kernel in the profile is a timed one; the roofline then prices the executed evaluation count")
-    ap.add_argument("--no-c4", action="store_true", help="N > 1: skip the side block that renders BASELINE.json config 4 (the same scene at 8192x8192, sharded the same way)")
+                    help="profiling passes (tools/profile.sh): skip the untimed launch before the warm-up (with --full, the one that counts the reference's "
+                         "evaluations), so that every launch of the trace kernel in the profile is a timed one; --full then prices the executed evaluation count")
+    ap.add_argument("--no-c4", action="store_true", help="--full, N > 1: skip the side block that renders BASELINE.json config 4 (the same scene at 8192x8192, sharded the same way)")
     ap.add_argument("--force-dist", action="store_true",
                     help="rehearsal on one GPU: initialise RCCL and run the gather path in a 1-rank group")
     ap.add_argument("--math", choices=("fixed", "glibc"), default="fixed",
                     help="arithmetic of MathF.Exp / Log in the timed launches (FT_OPT_MATH): fixed = the library's one fixed algorithm (default), "
                          "glibc = this host's glibc expf / logf restated on the GPU — then `value`, `roofline` and the oracle check are all in that arithmetic")
     ap.add_argument("--cpu-columns", type=int, default=0,
-                    help="columns of the frame the CPU oracle is timed on (default: 32 per usable host CPU, at least 32)")
+                    help="--full: columns of the frame the CPU oracle is timed on (default: 32 per usable host CPU, at least 32)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write the frame the last timed step rendered to DIR/*.npy (rank 0; a fixed, seeded pixel sample "
                          "when the whole frame exceeds the size cap), so that two builds can be compared output for output")
@@ -208,14 +217,19 @@ def main():
         torch.cuda.synchronize()
 
     # The REFERENCE's work for this rank's share of the frame: one untimed launch with the escape shortcut off marches every ray to its end as
-    # the reference does (its counters are the oracle's); the roofline prices that work, the timed launches run the product's defaults
+    # the reference does (its counters are the oracle's); the roofline prices that work, the timed launches run the product's defaults.
+    # A plain run makes the same untimed launch in the product's defaults and counts nothing, so that warm-up and timed steps start as they do under --full
     ref = None
-    if not args.no_reference_launch:
+    if args.full and not args.no_reference_launch:
         dev.set_option("escape", 0); dev.set_option("reuse", 0)
         ds.render_device(syn.EPSILON, syn.RAY_LENGTH, size, cam, slab.data_ptr(), **tiling)
         torch.cuda.synchronize()
         ref = ds.collect_stats()
         dev.set_option("escape", 1); dev.set_option("reuse", 1)
+    elif not args.no_reference_launch:
+        render(slab)
+        torch.cuda.synchronize()
+        ds.collect_stats()
 
     if pipe is not None:                          # both render lanes settle (lean-kernel placement is timed per context) before anything counts
         for d_ in lanes:
@@ -236,10 +250,13 @@ def main():
     if args.dump_outputs and rank == 0:           # before any side block renders into the slab again
         dump_outputs(args.dump_outputs, slab if pipe is None else pipe.frame)
 
+    # --full: the side measurements (N = 1), each after the timed region and on its own launches
+    side = args.full and world == 1 and pipe is None and not args.no_spp4
+
     # BASELINE.json words configs[2] with "4 spp".  The reference samples once per pixel (Image.fs:28-34) and
     # `value` is measured on that; the 4-sample EXTENSION of the same frame is timed beside it (N = 1 only).
     spp4 = None
-    if world == 1 and pipe is None and not args.no_spp4:
+    if side:
         ds.render_device(syn.EPSILON, syn.RAY_LENGTH, size, cam, slab.data_ptr(), spp=4)
         torch.cuda.synchronize(); ds.collect_stats()
         t4 = time.perf_counter()
@@ -259,7 +276,7 @@ def main():
     # frame ends on drain while the next frame already fills the GPU (what the N > 1 pipeline does on every rank).
     # Reported beside `value`, which stays the one-stream figure that `roofline` describes.
     streamed = None
-    if world == 1 and pipe is None and not args.no_spp4:
+    if side:
         lane_streams = [torch.cuda.Stream(), torch.cuda.Stream()]
         devs2 = [ft.Device(local_rank), ft.Device(local_rank)]
         for d_, s_ in zip(devs2, lane_streams):
@@ -290,7 +307,7 @@ def main():
     # Image.render returns a HOST FColor[,] (Image.fs:26-35): the same K frames through ft_render into a page-locked host
     # array (ft_host_register) — four column chunks on two streams, every finished chunk copied behind the rendering.
     host_out = None
-    if world == 1 and pipe is None and not args.no_spp4:
+    if side:
         host = np.zeros((W, H, 3), np.float32)
         dev.host_register(host)
         ds.render(syn.EPSILON, syn.RAY_LENGTH, size, cam, out=host)
@@ -310,7 +327,7 @@ def main():
     # no AO; 4 rays of radius 0.5 per primary hit), and the reference's own workload, Program.fs:14-83, at 4000^2.
     target = None
     console = None
-    if world == 1 and pipe is None and not args.no_spp4 and W == 4096:
+    if side and W == 4096:
         kw = dict(ao_samples=4, ao_radius=0.5)
         ds.render_device(syn.EPSILON, syn.RAY_LENGTH, size, cam, slab.data_ptr(), **kw)
         torch.cuda.synchronize(); ds.collect_stats()
@@ -351,7 +368,7 @@ def main():
     # the GPU, csrc/ft_libm.h) — the arithmetic the reference's CPU path would use on this very machine.  Checked further down against the
     # oracle switched to the real libm; `value` stays the default (fixed) arithmetic.
     libm = None
-    if world == 1 and pipe is None and not args.no_spp4 and math_variant == 0:
+    if side and math_variant == 0:
         variant = ft.glibc_build_of_this_host()
         fixed_frame = slab.clone()
         dev.set_option("math", variant)
@@ -388,7 +405,7 @@ def main():
     # BASELINE.json config 4 beside the metric's config (N > 1 only): the same scene at 8192x8192 in the same interleaved column stripes, the slabs
     # brought to rank 0 by the path's ONE gather — frame by frame, not pipelined, so that the per-rank kernel time and the gather time stand alone
     c4 = None
-    if use_dist and not args.no_c4 and W == 4096:
+    if args.full and use_dist and not args.no_c4 and W == 4096:
         W8 = 8192
         size8, tiling8 = ft.ImageSize(W8, W8), ftd.tiling(W8, world, rank, STRIPE)
         slab8 = torch.empty((W8 // world, W8, 3), dtype=torch.float32, device="cuda")
@@ -492,7 +509,7 @@ def main():
                          "work_note": "achieved / frac (= achieved_executed / frac_executed) price what the timed launches EXECUTED — the kernel ends rays that can no "
                                       "longer reach the scene's support sphere (sdf_evals_executed_per_frame) and drops, per wave and round, the children whose terms are "
                                       "below half an ulp of the running sum (children_culled_fraction); both are exact (DESIGN.md section 4) — i.e. the hardware fraction, "
-                                      "next to the counter view valu_busy_pmc.  achieved_reference_work / frac_reference_work price the REFERENCE's work over the same "
+                                      "next to the counter view valu_busy_pmc.  achieved_reference_work / frac_reference_work (--full) price the REFERENCE's work over the same "
                                       "time (SURVEY.md section 8d: every SDF evaluation of every ray marched to its end, all children in each; counters of an untimed "
                                       "launch with the escape shortcut off = the oracle's): an algorithmic speed-up figure, not a hardware fraction",
                          "note": "f32 lane-ops (FMA counted once; contraction is forbidden by parity); sqrt and exp count as 1 "
@@ -503,6 +520,10 @@ def main():
                                  "sustains shader_mhz under this load (power management), which is the box-to-box spread. "
                                  "HBM traffic = 12 B/pixel output."},
         }
+        if not args.full:                         # the reference's work is counted by the untimed launch of --full alone
+            del out["config"]["sdf_evals_per_frame"]
+            for k in ("achieved_reference_work", "frac_reference_work", "algorithmic_flops_per_launch_reference_work"):
+                del out["roofline"][k]
         if per_rank is not None:
             out["config"]["per_rank"] = per_rank
             out["config"]["per_rank_note"] = ("per frame: kernel_ms = mean start-to-end time of this rank's launches (two overlapping lanes), gather_ms = "
@@ -518,7 +539,7 @@ def main():
             out["config"]["host_output"] = host_out
         if target is not None:
             out["config"]["north_star_target"] = target
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"], check = cpu_baseline(scene, cam, W, H, args.cpu_columns, slab if pipe is None else pipe.frame, libm=math_variant != 0)
             out["config"]["max_abs_delta_vs_oracle"] = check["max_abs_delta"]      # second half of the metric: 0.0 = bit-exact
             out["config"]["pixels_compared_with_oracle"] = check["pixels"]
@@ -526,7 +547,7 @@ def main():
                 out["config"]["program_fs_scene"] = program_fs_block(console, cam, args.steps, build["src"])
             if libm is not None:
                 out["config"]["glibc_math_mode"] = libm_block(libm, scene, cam, W, H)
-        elif world > 1:
+        elif args.full and world > 1:
             # N > 1: the gathered frame gets its own parity flag — a few columns against the oracle, after the timed region
             out["config"].update(oracle_check_columns(scene, cam, W, H, pipe.frame, 16, libm=math_variant != 0))
         if c4 is not None:

@@ -948,11 +948,11 @@ def test_frame_pipeline_over_rccl():
 
 
 def test_bench_line_contract():
-    """bench.py prints ONE JSON line with the fields the driver and the judge read (reduced frame so it takes seconds)"""
+    """bench.py --full prints ONE JSON line with the fields the driver and the judge read (reduced frame so it takes seconds)"""
     import json, os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--size", "512", "--steps", "2", "--warmup", "1", "--cpu-columns", "32"],
-                       capture_output=True, text=True, timeout=600)
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--size", "512", "--steps", "2", "--warmup", "1", "--cpu-columns", "32",
+                        "--full"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [l for l in r.stdout.strip().splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -968,6 +968,29 @@ def test_bench_line_contract():
     assert d["config"]["max_abs_delta_vs_oracle"] == 0.0 and d["config"]["same_frame_at_4_spp"]["value"] > 0
     assert d["config"]["frames_streamed_on_two_lanes"]["value"] > 0
     assert abs(d["ms_per_step"] - d["roofline"]["kernel_ms"]) < 0.35 * d["ms_per_step"]       # one kernel per step dominates
+
+
+def test_bench_plain_line(tmp_path, oracle):
+    """a plain bench.py run prints the headline line without what --full adds, and the frame it dumps is the oracle's"""
+    import json, os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--size", "512", "--steps", "2", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    lines = [l for l in r.stdout.strip().splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "config", "roofline"):
+        assert k in d, k
+    assert d["unit"] == "Mrays/s" and d["steps"] == 2 and d["warmup"] == 1 and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["value"] > 0 and d["config"]["nan_or_cap_flags"] == 0 and d["config"]["rays_per_frame"] > 512 * 512
+    assert abs(d["roofline"]["frac"] - d["roofline"]["achieved"] / d["roofline"]["peak"]) < 1e-3
+    assert "cpu_baseline" not in d and "frac_reference_work" not in d["roofline"]
+    assert not {"sdf_evals_per_frame", "max_abs_delta_vs_oracle", "same_frame_at_4_spp", "frames_streamed_on_two_lanes", "host_output",
+                "north_star_target", "program_fs_scene", "glibc_math_mode"} & set(d["config"])
+    scene, _ = syn.config3(size=512)
+    want, _ = oracle.Oracle().scene(scene).render(syn.EPSILON, syn.RAY_LENGTH, 512, 512, syn.default_camera().as_array(), xstep=8)
+    assert_bit_equal(np.load(tmp_path / "image.npy")[::8], want, "bench.py --dump-outputs vs oracle")
 
 
 def test_maximum_nesting_and_lds_footprint(gpu, oracle):

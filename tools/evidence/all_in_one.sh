@@ -16,11 +16,11 @@ bash tools/profile_scene.sh evall_pfs4000 "Program.fs scene 4000^2" > $O/pfs4000
 cp gpurun_out/prof_evall/summary.txt $O/final_summary.txt; cp gpurun_out/prof_evall_pfs1000/summary.txt $O/program_fs_1000_summary.txt; cp gpurun_out/prof_evall_pfs4000/summary.txt $O/program_fs_4000_summary.txt
 cp $O/final_summary.txt profiles/r03_final_summary.txt; cp $O/program_fs_1000_summary.txt profiles/r03_program_fs_1000_summary.txt; cp $O/program_fs_4000_summary.txt profiles/r03_program_fs_4000_summary.txt
 echo profiles done
-timeout -k 10 400 python bench.py > $O/bench.json 2> $O/bench.err; echo bench rc=$?
+timeout -k 10 400 python bench.py --full > $O/bench.json 2> $O/bench.err; echo bench rc=$?
 timeout -k 10 300 python3 tools/bench_scenes.py > $O/bench_scenes.jsonl 2> $O/bench_scenes.err; echo scenes rc=$?
 timeout -k 10 300 python3 tools/bench_ext.py > $O/bench_ext.jsonl 2> $O/bench_ext.err; echo ext rc=$?
 timeout -k 10 120 python3 tools/tail_probe.py > $O/tail_probe.json 2>/dev/null; cat $O/tail_probe.json
-MASTER_ADDR=127.0.0.1 MASTER_PORT=29546 timeout -k 10 300 python bench.py --force-dist --steps 6 --warmup 2 --no-cpu-baseline > $O/bench_force_dist.json 2> $O/bench_force_dist.err; echo dist rc=$?
+MASTER_ADDR=127.0.0.1 MASTER_PORT=29546 timeout -k 10 300 python bench.py --force-dist --steps 6 --warmup 2 --no-cpu-baseline --full > $O/bench_force_dist.json 2> $O/bench_force_dist.err; echo dist rc=$?
 timeout -k 10 600 python tools/full_frame_check.py > $O/full_frame.jsonl 2> $O/full_frame.err; echo full rc=$?
 python3 -c "
 import json
