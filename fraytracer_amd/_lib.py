@@ -144,6 +144,7 @@ SYMBOLS = {
     "ft_scene_grid_dump": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P]),
     "ft_scene_support_sphere": (C.c_int, [_P, C.POINTER(C.c_float)]),
     "ft_scene_miss_certificate": (C.c_int, [_P, C.POINTER(C.c_float)]),
+    "ft_scene_miss_certificate_clusters": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_int32]),
     "ft_math_eval": (C.c_int, [_P, C.c_int32, _P, _P, C.c_int64, _P]),
     "ft_selftest_fastmath": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
     "ft_selftest_libm": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_float, C.c_uint32, C.c_int32, C.POINTER(C.c_uint64)]),

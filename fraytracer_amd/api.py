@@ -539,6 +539,20 @@ class DeviceScene:
         check(lib.ft_scene_miss_certificate(self._scene, v))
         return dict(zip(("margin", "clip", "rho2", "len_factor", "steps"), (float(x) for x in v)))
 
+    def miss_certificate_clusters(self):
+        """(clusters, members): clusters a float32 array (K, 4) of centre xyz and radius, members a list of K arrays (n_c, 4) of the children
+        (x, y, z, r) in cluster order; K = 0: the certificate sums every child"""
+        k, n = C.c_int32(), C.c_int32()
+        check(lib.ft_scene_miss_certificate_clusters(self._scene, C.byref(k), C.byref(n), None, 0))
+        size = 8 * k.value + 4 * n.value
+        buf = (C.c_float * max(size, 1))()
+        check(lib.ft_scene_miss_certificate_clusters(self._scene, C.byref(k), C.byref(n), buf, size))
+        a = np.frombuffer(buf, np.float32, size).copy()
+        rec = a[:8 * k.value].reshape(-1, 8)
+        kids = a[8 * k.value:].reshape(-1, 4)
+        ints = rec[:, 4:6].copy().view(np.int32)
+        return rec[:, :4].copy(), [kids[f:f + c] for c, f in ints]
+
     def grid(self, g=0):
         info = (C.c_float * 6)()
         counts = (C.c_int32 * 3)()

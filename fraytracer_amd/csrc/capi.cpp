@@ -170,7 +170,7 @@ int uploadScene(ft_ctx* c, ft_scene* s) {
                  oKids = placed(cur, f.children), oCtr = placed(cur, f.cellCenters), oStart = placed(cur, f.cellStart),
                  oItems = placed(cur, f.items), oLights = placed(cur, f.lights), oMats = placed(cur, f.materials),
                  oMatX = placed(cur, f.materialsExt), oItemsT = placed(cur, f.itemsT), oStartT = placed(cur, f.cellStartT),
-                 oMatH = placed(cur, f.materialHandles);
+                 oMatH = placed(cur, f.materialHandles), oCertCl = placed(cur, f.certCl);
     std::vector<unsigned char> host(cur, 0);
     auto put = [&](size_t at, const void* p, size_t n) { if (n) memcpy(host.data() + at, p, n); };
     put(oInstr, f.instr.data(), f.instr.size() * sizeof(FtInstr));
@@ -186,6 +186,7 @@ int uploadScene(ft_ctx* c, ft_scene* s) {
     put(oItemsT, f.itemsT.data(), f.itemsT.size() * sizeof(FtItemRec));
     put(oStartT, f.cellStartT.data(), f.cellStartT.size() * 4);
     put(oMatH, f.materialHandles.data(), f.materialHandles.size() * 4);
+    put(oCertCl, f.certCl.data(), f.certCl.size() * 4);
     FtSceneDev& d = s->dev;
     d = FtSceneDev{};
     d.nInstr = f.nMainInstr; d.nSlots = f.nSlots; d.nLights = (uint32_t)f.lights.size(); d.fastPath = f.fastPath;
@@ -193,6 +194,7 @@ int uploadScene(ft_ctx* c, ft_scene* s) {
     d.nStage = f.nStage; d.nearR2 = f.nearR2; d.fastQ = f.fastQ; d.nGlass = f.nGlass;
     d.escC[0] = f.escC[0]; d.escC[1] = f.escC[1]; d.escC[2] = f.escC[2]; d.escR = f.escR; d.escRho2 = f.escRho2; d.cullPc = f.cullPc;
     d.certM = f.certM; d.certClip = f.certClip; d.certRho2 = f.certRho2; d.certLenF = f.certLenF; d.certSteps = f.certSteps;
+    d.certK = f.certK;
     if (!c->hasDevice) return FT_OK;                       // host-only context: introspection only
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipMalloc(&s->dBlob, cur));
@@ -209,6 +211,7 @@ int uploadScene(ft_ctx* c, ft_scene* s) {
     d.materials = reinterpret_cast<const float*>(b + oMats);
     s->dMaterialsExt = reinterpret_cast<const float*>(b + oMatX);
     s->dMatHandles = reinterpret_cast<const int32_t*>(b + oMatH);
+    d.certCl = reinterpret_cast<const float*>(b + oCertCl);
     s->carve = f.carve;
     s->carve.itemsT = reinterpret_cast<const FtItemRec*>(b + oItemsT);
     s->carve.cellStartT = reinterpret_cast<const uint32_t*>(b + oStartT);
@@ -216,9 +219,9 @@ int uploadScene(ft_ctx* c, ft_scene* s) {
 }
 
 // Latency-mode thresholds (rays per wave at or below which each ray is evaluated by all 64 lanes; measured)
-// miss certificate (FT_OPT_CERT_POLICY layout): primary rays at their first step (the one taken from the camera's value), shadow rays at their 6th,
-// a wave runs the certificate once 16 of its lanes are due, one try per ray (DESIGN.md section 4 "Miss certificate": the policies measured)
-constexpr int FT_CERT_POLICY_DEFAULT = 1 | (6 << 8) | (16 << 16);
+// miss certificate (FT_OPT_CERT_POLICY layout): primary rays from their first evaluation, shadow rays from their 6th step, a wave runs the certificate
+// once 16 of its lanes are due, and a ray it fails on is due again 6 steps later (DESIGN.md section 4 "Miss certificate": the policies measured)
+constexpr int FT_CERT_POLICY_DEFAULT = 0 | (6 << 8) | (16 << 16) | (6 << 24);
 constexpr int FT_TAIL_K_LEAN = 32, FT_TAIL_K_GENERAL = 2, FT_TAIL_K_CARVED = 1;      // carved: 1.26 ms at 0 / 1 against 1.29 at 2 on the 1000^2 Program.fs frame (profiles/r04_carved_variants.txt)
 // does this launch take the glibc build of the kernels?
 bool libmLaunch(const ft_ctx* c, const ft_scene* s) { return c->optMath != FT_MATH_FIXED && s->usesExpLog; }
@@ -1068,6 +1071,16 @@ int ft_scene_miss_certificate(const ft_scene* s, float out[5]) {
     if (!s || !out) return setErr(FT_ERR_INVALID, "null argument");
     const ft::FlatScene& f = s->flat;
     out[0] = f.certM; out[1] = f.certClip; out[2] = f.certRho2; out[3] = f.certLenF; out[4] = (float)f.certSteps;
+    return FT_OK;
+}
+int ft_scene_miss_certificate_clusters(const ft_scene* s, int32_t* nClusters, int32_t* nChildren, float* out, int32_t capacity) {
+    if (!s || !nClusters || !nChildren) return setErr(FT_ERR_INVALID, "null argument");
+    const ft::FlatScene& f = s->flat;
+    *nClusters = (int32_t)f.certK;
+    *nChildren = (int32_t)((f.certCl.size() - 8u * f.certK) / 4u);
+    if (!out) return FT_OK;
+    if (capacity < 0 || (size_t)capacity < f.certCl.size()) return setErr(FT_ERR_INVALID, "capacity below 8 n_clusters + 4 n_children floats");
+    if (!f.certCl.empty()) memcpy(out, f.certCl.data(), f.certCl.size() * 4);
     return FT_OK;
 }
 

@@ -114,6 +114,8 @@ struct FtSceneDev {             // passed by value as kernel argument
     float certRho2;             // ... from starts within sqrt(certRho2) of escC (the drift bound's ball)
     float certLenF;             // ... and along at most Length * certLenF (the float32 Length the reference counts down)
     uint32_t certSteps;         // steps the rest of a certified march can take at most (the step cap stays out of reach)
+    const float* certCl;        // clusters of the run's children for the certificate's bound (scene.cpp certClusters): certK records {C, R, n_c, first} of 8 floats,
+    uint32_t certK;             // then the children in cluster order (4 floats each); read-only, wave-uniform.  certK = 0: the flat loop over the staged children
 };
 
 // "Carved union" kernels (FtSceneDev.fastPath == 3; kernels.hip ft_eval_carved): the whole program is ONE grid union of plain primitives

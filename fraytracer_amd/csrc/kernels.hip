@@ -1330,6 +1330,7 @@ __device__ __forceinline__ bool ft_never_enters(const FtSceneDev& S, const f3 o,
 // lane's sum has reached the threshold (a ray that will hit, or pass close, fails within the first children that matter to it).
 // Gated like the escape shortcut: a support sphere and the certificate's constants (certM >= 0: none with a non-finite constant anywhere), 0 <= epsilon <= escR,
 // Length < 1e9, and the drift bound's own conditions: 0.81 <= |dir|^2 <= 1.44, a start within sqrt(certRho2) of escC, certSteps short of the step cap.
+// A run of >= 32 children sums cluster bounds first and refines only the clusters a lane needs (certK != 0, below).
 // Executed by all 64 lanes (wave-uniform loop); `test`: the lanes that ask.  -> the certificate holds in this lane.
 __device__ __forceinline__ bool ft_miss_certificate(const FtSceneDev& S, const float* __restrict__ ldsC, bool test, const f3 o, const f3 dir, float eps, float len,
                                                     uint32_t steps) {
@@ -1357,7 +1358,7 @@ __device__ __forceinline__ bool ft_miss_certificate(const FtSceneDev& S, const f
     const float iss = 1.0f / ft_dot(sv, sv);
     float sum = 0.0f;
     uint32_t i = 0;
-    auto term = [&](const float4 prm) {
+    auto term = [&](const auto prm) {
         const float vx = prm.x - p0.x, vy = prm.y - p0.y, vz = prm.z - p0.z;
         float t = __builtin_fmaf(vz, sv.z, __builtin_fmaf(vy, sv.y, vx * sv.x)) * iss;
         t = __builtin_amdgcn_fmed3f(t, 0.0f, 1.0f);
@@ -1365,6 +1366,38 @@ __device__ __forceinline__ bool ft_miss_certificate(const FtSceneDev& S, const f
         const float q = __builtin_fmaf(ez, ez, __builtin_fmaf(ey, ey, ex * ex));
         return __builtin_amdgcn_exp2f((__builtin_amdgcn_sqrtf(q) - prm.w) * A);
     };
+    if (S.certK != 0u) {
+        // Cluster bound (scene.cpp certClusters): n_c 2^(A (dist(S, C) - R)) >= the sum of the cluster's member terms, since dist(S, c_i) - r_i >=
+        // dist(S, C) - R for each member and A < 0.  Pass 1 sums the K bounds: a lane below thr holds.  Each lane marks the clusters whose bound reaches
+        // thr / 2K; pass 2 visits the clusters some open lane marked, and a lane's total is the sum of its unmarked bounds plus its marked clusters' exact
+        // terms, summed apart and added once at the end.  Any mix of bounds and exact terms is an upper bound, so the marking rule sets the cost only
+        // (tools/miss_certificate_cluster_sim.py).  Records and the cluster-ordered children are wave-uniform loads from the constant address space.
+        const v4f FT_CONST* cl = reinterpret_cast<const v4f FT_CONST*>(as_const(S.certCl));
+        const v4f FT_CONST* kid = cl + 2u * S.certK;
+        const float mthr = thr * (0.5f / (float)S.certK);
+        float all = 0.0f, rest = 0.0f;
+        uint32_t mark = 0u;
+        for (uint32_t k = 0; k < S.certK; ++k) {
+            const float bnd = term(cl[2u * k]) * (float)__float_as_uint(cl[2u * k + 1u].x);
+            all += bnd;
+            if (bnd >= mthr) mark |= 1u << k;
+            else rest += bnd;
+        }
+        const bool held = ok && all < thr, open = ok && !held;
+        if (__ballot(open) == 0ull) return held;
+        float exact = 0.0f;
+        for (uint32_t k = 0; k < S.certK; ++k) {
+            const bool mine = (mark >> k) & 1u;
+            if (__ballot(open && mine) == 0ull) continue;
+            const v4f r = cl[2u * k + 1u];
+            const uint32_t cnt = __float_as_uint(r.x), first = __float_as_uint(r.y);
+            float part = 0.0f;
+            for (uint32_t j = 0; j < cnt; ++j) part += term(kid[first + j]);
+            exact += mine ? part : 0.0f;
+            if (__ballot(open && exact < thr) == 0ull) return held;    // every open lane's exact terms alone have reached thr: it has failed
+        }
+        return held || (open && rest + exact < thr);
+    }
     for (; i + 8u <= n; i += 8u) {
 #pragma unroll
         for (int j = 0; j < 8; ++j) sum += term(c[i + j]);

@@ -841,6 +841,59 @@ static bool finiteTree(const Builder& b, int h, int depth = 0) {
     return true;
 }
 
+// Clusters of the miss certificate (flatten, "Miss certificate"): a recursive median split of the run's n staged spheres (x, y, z, r) on the longest axis
+// of their centres' box, down to leaves of at most max(16, ceil(n / 32)) children, so K <= 32 (a lane marks its clusters in one 32-bit mask).  Each
+// cluster: centre C = the float32 mean of its members' centres, radius R >= |c_i - C| + r_i for every member, in double from the float32 values, padded
+// by a relative 1e-6 and rounded up to float32.  rec: K records {C, R, n_c, first} (the last two as bits), then the n children again in cluster order.
+static void certClusters(const float* kid, uint32_t n, std::vector<float>& rec, uint32_t& K) {
+    const uint32_t leaf = std::max<uint32_t>(16u, (n + 31u) / 32u);
+    std::vector<uint32_t> idx(n);
+    for (uint32_t i = 0; i < n; ++i) idx[i] = i;
+    std::vector<std::pair<uint32_t, uint32_t>> leaves;                 // [begin, end) of idx
+    std::vector<std::pair<uint32_t, uint32_t>> todo{{0u, n}};
+    while (!todo.empty()) {
+        const auto [b0, e0] = todo.back(); todo.pop_back();
+        if (e0 - b0 <= leaf) { leaves.push_back({b0, e0}); continue; }
+        float lo[3] = {kid[4 * idx[b0]], kid[4 * idx[b0] + 1], kid[4 * idx[b0] + 2]}, hi[3] = {lo[0], lo[1], lo[2]};
+        for (uint32_t i = b0; i < e0; ++i)
+            for (int a = 0; a < 3; ++a) { lo[a] = std::min(lo[a], kid[4 * idx[i] + a]); hi[a] = std::max(hi[a], kid[4 * idx[i] + a]); }
+        int ax = 0;
+        for (int a = 1; a < 3; ++a) if ((double)hi[a] - lo[a] > (double)hi[ax] - lo[ax]) ax = a;
+        const uint32_t mid = b0 + (e0 - b0) / 2;
+        std::nth_element(idx.begin() + b0, idx.begin() + mid, idx.begin() + e0, [&](uint32_t p, uint32_t q) {
+            const float cp = kid[4 * p + ax], cq = kid[4 * q + ax];
+            return cp < cq || (cp == cq && p < q);                     // a total order: the same split on every machine
+        });
+        todo.push_back({mid, e0}); todo.push_back({b0, mid});           // the lower half first: clusters in ascending order along each split
+    }
+    K = (uint32_t)leaves.size();
+    if (K > 32u) { K = 0; rec.clear(); return; }                       // (cannot happen: n / leaf <= 32)
+    rec.assign(8u * K + 4u * n, 0.0f);
+    uint32_t at = 0;
+    for (uint32_t c = 0; c < K; ++c) {
+        const auto [b0, e0] = leaves[c];
+        double m[3] = {0, 0, 0};
+        for (uint32_t i = b0; i < e0; ++i) for (int a = 0; a < 3; ++a) m[a] += kid[4 * idx[i] + a];
+        float C[3];
+        for (int a = 0; a < 3; ++a) C[a] = (float)(m[a] / (e0 - b0));
+        double R = 0.0;
+        for (uint32_t i = b0; i < e0; ++i) {
+            const float* k = kid + 4 * idx[i];
+            const double dx = (double)k[0] - C[0], dy = (double)k[1] - C[1], dz = (double)k[2] - C[2];
+            R = std::max(R, std::sqrt(dx * dx + dy * dy + dz * dz) + (double)k[3]);
+            for (int a = 0; a < 4; ++a) rec[8u * K + 4u * (at + i - b0) + a] = k[a];
+        }
+        R *= 1.0 + 1e-6;
+        float Rf = (float)R;
+        if ((double)Rf < R) Rf = std::nextafter(Rf, INFINITY);
+        const uint32_t cnt = e0 - b0, first = at;
+        float* r = &rec[8u * c];
+        r[0] = C[0]; r[1] = C[1]; r[2] = C[2]; r[3] = Rf;
+        memcpy(&r[4], &cnt, 4); memcpy(&r[5], &first, 4);
+        at += cnt;
+    }
+}
+
 bool flatten(const Builder& b, int object, const float bg[3], const int* lights, int nLights, FlatScene& out, std::string& err) {
     if (!b.okObject(object)) { err = "invalid object handle"; return false; }
     out = FlatScene{};
@@ -932,6 +985,14 @@ bool flatten(const Builder& b, int object, const float bg[3], const int* lights,
     // sums: n + 2 roundings of the reference's float sum, <= 1 ulp for each exp (the fixed ft_exp 0.93 ulp, glibc's expf < 1), log 0.51 ulp; the certificate's
     // v_exp_f32 / v_sqrt_f32 (1 ulp), its own sum (n roundings), terms below 2^-126 flushed (their sum < n 2^-26 of a threshold >= 2^-100), and the threshold
     // (scaled by 1 - 1e-4): at most (2n + 4096) 2^-23 + 2e-4 of the sum, which is s times that in distance.
+    // Cluster bound (runs of >= 32 children; certClusters, kernels.hip ft_miss_certificate): the certificate may replace the terms of a cluster's members
+    // by n_c exp(si (dist(S, C) - R)) with R >= |c_i - C| + r_i for each member.  By the triangle inequality dist(S, c_i) - r_i >= dist(S, C) - R, and
+    // si < 0, so the cluster term is >= the sum of its members' exact terms, and any mix of cluster terms and member terms bounds the sum from above.
+    // The margin needs nothing new: the cluster's centre is a float32 mean of its members' centres, so its distance to the segment carries the same
+    // error as a child's (<= 8u (|C - q| + R) and 16u (|escC|inf + 10 escR)); R is computed in double from the stored float32 values, padded by
+    // 1e-6 and rounded up; the cluster term is one more exp (1 ulp) and one multiply by n_c (exact count, one rounding); flushed cluster terms lose
+    // < n 2^-126 in all, as flushed child terms do; the total gets at most K <= 32 more roundings (the unmarked bounds are summed apart from the exact
+    // terms and added once).  All of it stays inside the (2n + 4096) 2^-23 budget of eSum, so certM and the other constants keep their values.
     if (out.fastPath == 1u && escCInf >= 0.0 && out.escR >= 0.0f && out.instr.size() == 3 && out.nMainInstr == 3) {
         const FtInstr& run = out.instr[0];
         const bool shape = run.op == FT_OP_SMOOTH_RUN && (run.flags & FT_FLAG_INIT) && (run.flags & FT_FLAG_FAST) && run.count >= 1u && run.f0 < 0.0f &&
@@ -955,6 +1016,7 @@ bool flatten(const Builder& b, int object, const float bg[3], const int* lights,
                 out.certRho2 = (float)(2.5 * escR * 2.5 * escR);
                 out.certLenF = (float)(1.0 + (N + 2.0) * 4.0 * u);
                 out.certSteps = (uint32_t)(N + 2000.0);
+                if (run.count >= 32u) certClusters(&out.consts[run.data], run.count, out.certCl, out.certK);
             }
         }
     }

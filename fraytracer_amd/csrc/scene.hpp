@@ -106,6 +106,8 @@ struct FlatScene {                                            // host copy of ev
     float escRho2 = 0.0f;                                     // see FtSceneDev::escRho2
     float certM = -1.0f, certClip = 0.0f, certRho2 = 0.0f, certLenF = 1.0f;   // see FtSceneDev::certM ... (-1: no miss certificate)
     uint32_t certSteps = 0;
+    std::vector<float> certCl;                                // see FtSceneDev::certCl (scene.cpp certClusters); empty: the certificate's flat loop
+    uint32_t certK = 0;
     uint32_t cullPc = 0xffffffffu;                            // see FtSceneDev::cullPc
     uint32_t fastPath = 0;
     FtCarve carve{};                                          // fastPath == 3 (ft_device.h "Carved union"); the two pointers are set at upload

@@ -290,6 +290,10 @@ int ft_scene_support_sphere(const ft_scene*, float centre_radius[4]);
 /* the constants of the smooth-union kernel's miss certificate (FT_OPT_CERT; margin < 0: the scene has none):
  * margin certM, clip padding certClip, squared start radius certRho2, Length factor certLenF, steps left certSteps */
 int ft_scene_miss_certificate(const ft_scene*, float out[5]);
+/* the clusters of the certificate's bound (n_clusters = 0: the scene has none, and the certificate sums every child): n_clusters records of 8 floats
+ * {centre xyz, radius, member count, first member} (the last two are int32 bits), then the n_children children (x, y, z, r) in cluster order.
+ * out = NULL: only the counts; otherwise capacity >= 8 n_clusters + 4 n_children floats */
+int ft_scene_miss_certificate_clusters(const ft_scene*, int32_t* n_clusters, int32_t* n_children, float* out, int32_t capacity);
 
 /* math primitives of the device path, evaluated on the GPU: op 0 exp, 1 log, 2 sqrt, 3 a/b, 4 fast sqrt, 5 fast exp
  * (y = second operand, may be NULL otherwise).  Used by tests/test_math_parity.py. */
