@@ -619,6 +619,37 @@ class DeviceScene:
         check(lib.ft_render_hits_device(self.device._ctx, self._scene, C.byref(camera._c), C.byref(p), ptr(d_out_ptr), ptr(d_hits_ptr), ptr(d_material_ptr)))
         return p.n_columns
 
+    @staticmethod
+    def _cameras(cameras):
+        cams = list(cameras)
+        arr = (_lib.CameraS * max(len(cams), 1))()
+        for k, cam in enumerate(cams):
+            arr[k] = cam._c
+        return arr, len(cams)
+
+    def render_views(self, epsilon, length, imageSize, cameras, out=None, **tiling_and_ext):
+        """ft_render_views: Image.render of one scene from each camera of `cameras` in one job queue -> (float32 [K, n_columns, Y, 3],
+        stats dict of the whole batch).  Block k is bit for bit render(..., cameras[k], **tiling_and_ext)[0].  `out`: a float32 array of
+        that shape to render into."""
+        p = self._params(imageSize, epsilon, length, **tiling_and_ext)
+        arr, k = self._cameras(cameras)
+        shape = (k, p.n_columns, p.height, 3)
+        if out is None:
+            out = np.empty(shape, np.float32)
+        elif out.dtype != np.float32 or out.shape != shape or not out.flags.c_contiguous:
+            raise ValueError("out must be a C-contiguous float32 array of shape (n_views, n_columns, Y, 3)")
+        st = _lib.Stats()
+        check(lib.ft_render_views(self.device._ctx, self._scene, arr, k, C.byref(p), out.ctypes.data_as(C.c_void_p), C.byref(st)))
+        return out, st.as_dict()
+
+    def render_views_device(self, epsilon, length, imageSize, cameras, d_out_ptr, **tiling_and_ext):
+        """asynchronous ft_render_views_device into device memory (pointer as int; n_views x n_columns x Y x 3 float32); pair with
+        collect_stats()."""
+        p = self._params(imageSize, epsilon, length, **tiling_and_ext)
+        arr, k = self._cameras(cameras)
+        check(lib.ft_render_views_device(self.device._ctx, self._scene, arr, k, C.byref(p), C.c_void_p(d_out_ptr)))
+        return p.n_columns
+
     def collect_stats(self):
         st = _lib.Stats()
         check(lib.ft_collect_stats(self.device._ctx, C.byref(st)))
@@ -830,6 +861,14 @@ class Image:
     @staticmethod
     def renderScene(epsilon, length, imageSize, camera, scene, device=None):
         return Image.render(epsilon, length, imageSize, camera, SdfScene.trace(scene, device))
+
+    @staticmethod
+    def renderViews(epsilon, length, imageSize, cameras, scene, device=None):
+        """Image.render of one scene from every camera of `cameras` in one launch (ft_render_views) -> float32 [K, X, Y, 3]; image k is
+        Image.renderScene epsilon length imageSize cameras[k] scene."""
+        dev = device if device is not None else Device.default(0)
+        img, _ = dev.scene(scene).render_views(epsilon, length, imageSize, cameras)
+        return img
 
     @staticmethod
     def renderHits(epsilon, length, imageSize, camera, scene, device=None):

@@ -44,6 +44,7 @@ struct ft_ctx {
     void* scratch = nullptr; size_t scratchBytes = 0;     // staging for host-output entry points
     void* planes = nullptr; size_t planesBytes = 0;       // EXTENSION spp > 1: per-sample frames before the resolve
     void* aux = nullptr; size_t auxBytes = 0;             // tone map: [256 B: max bits | 8-bit image]
+    void* cams = nullptr; size_t camsBytes = 0;           // ft_render_views: the batch's cameras (12 floats each)
     hipStream_t lane1 = nullptr, copyStream = nullptr;    // ft_render's host-output pipeline: second render lane, DMA stream (lazily created)
     std::vector<hipEvent_t> syncEvents;                   // untimed events of that pipeline
     std::vector<std::pair<void*, size_t>> hostRegs;       // ranges pinned through ft_host_register
@@ -285,7 +286,7 @@ int launchTrace(ft_ctx* c, const ft_scene* s, FtRenderArgs& a, int lane = 0) {
     int rc = planTrace(c, s, a.ext != 0u, plan); if (rc) return rc;
     const unsigned variant = plan.variant;
     int perCU = 0;
-    HIP_TRY(ft_trace_occupancy(variant, s->carve.kind, a.ext != 0u, plan.libm, plan.lds, &perCU));
+    HIP_TRY(ft_trace_occupancy(variant, s->carve.kind, a.ext != 0u, plan.libm, a.views != nullptr, plan.lds, &perCU));
     if (perCU < 1) return setErr(FT_ERR_UNSUPPORTED, "the trace kernel does not fit a compute unit with this scene's LDS footprint");
     perCU = std::min(perCU, 8);
     if (c->optMaxBlocksPerCU > 0) perCU = std::min(perCU, c->optMaxBlocksPerCU);       // FT_OPT_MAX_BLOCKS_PER_CU (experiments)
@@ -470,6 +471,7 @@ void ft_ctx_destroy(ft_ctx* c) {
         if (c->scratch) (void)hipFree(c->scratch);
         if (c->planes) (void)hipFree(c->planes);
         if (c->aux) (void)hipFree(c->aux);
+        if (c->cams) (void)hipFree(c->cams);
         for (auto& r : c->hostRegs) (void)hipHostUnregister(r.first);
         for (auto e : c->syncEvents) (void)hipEventDestroy(e);
         if (c->lane1) { (void)hipStreamSynchronize(c->lane1); (void)hipStreamDestroy(c->lane1); }
@@ -611,13 +613,16 @@ int ft_camera_look_at(const float pos[3], const float look[3], const float up[3]
 // ---- hot path ------------------------------------------------------------------------------------
 // EXTENSION ft_render_hits: device buffers of the per-pixel records (either may be NULL)
 struct HitBufs { void* hits; void* material; };
+// ft_render_views: n <= FT_MAX_VIEWS cameras (12 floats each) in device memory, rendered by one launch of the *_views kernel
+struct ViewBatch { const float* cams; uint32_t n; };
 
 // hb != NULL: the EXTENSION build also writes the hit buffers; d_out = NULL then means hits only (one ray per pixel, the EXTENSION fields of p
-// do not apply)
+// do not apply).  vb != NULL: vb->n views instead of `cam`, written view after view (n x n_columns x height x 3 floats at d_out)
 static int renderLane(ft_ctx* c, const ft_scene* s, const ft_camera* cam, const ft_render_params* params, void* d_out, int lane,
-                      const HitBufs* hb = nullptr) {
+                      const HitBufs* hb = nullptr, const ViewBatch* vb = nullptr) {
     int rc = requireDevice(c); if (rc) return rc;
-    if (!s || s->ctx != c || !cam || (!d_out && !hb)) return setErr(FT_ERR_INVALID, "bad argument (scene must belong to this context)");
+    if (!s || s->ctx != c || !(vb ? vb->cams : (const void*)cam) || (!d_out && !hb)) return setErr(FT_ERR_INVALID, "bad argument (scene must belong to this context)");
+    if (vb && (hb || vb->n < 1u || vb->n > FT_MAX_VIEWS)) return setErr(FT_ERR_INVALID, "internal: a view batch has 1 .. 64 views and no hit buffers");
     if ((rc = checkParams(params))) return rc;
     ft_render_params hitsOnly;
     const ft_render_params* p = params;
@@ -628,7 +633,9 @@ static int renderLane(ft_ctx* c, const ft_scene* s, const ft_camera* cam, const 
     }
     if (lane != 0 && p->spp != 1) return setErr(FT_ERR_INVALID, "internal: the sample planes belong to lane 0");
     FtRenderArgs a{};
-    memcpy(a.cam, cam, sizeof(float) * 12);
+    if (vb) { a.views = vb->cams; a.nViews = vb->n; }
+    else memcpy(a.cam, cam, sizeof(float) * 12);
+    const uint32_t nViews = vb ? vb->n : 1u;
     a.W = p->width; a.H = p->height; a.x0 = p->x0; a.nCols = p->n_columns;
     a.stripeW = (uint32_t)p->stripe_width; a.stripeRanks = (uint32_t)p->stripe_ranks; a.stripeRank = (uint32_t)p->stripe_rank;
     a.mode = 0;
@@ -639,7 +646,7 @@ static int renderLane(ft_ctx* c, const ft_scene* s, const ft_camera* cam, const 
     a.spp = (uint32_t)p->spp; a.sppN = 1; while (a.sppN * a.sppN < a.spp) ++a.sppN;
     a.aoSamples = (uint32_t)p->ao_samples; a.aoRadius = p->ao_radius;
     a.planePixels = (uint32_t)p->n_columns * (uint32_t)p->height;
-    a.nJobs = a.jobsPerPlane * a.spp;
+    a.nJobs = a.jobsPerPlane * a.spp * nViews;                     // views: view after view, each its spp sample planes (kernels.hip start_job)
     // EXTENSION glass / wavelengths: without a glass material in the scene bounces change nothing
     a.maxBounces = s->dev.nGlass ? (uint32_t)p->max_bounces : 0u;
     a.spectral = (uint32_t)p->spectral;
@@ -652,9 +659,9 @@ static int renderLane(ft_ctx* c, const ft_scene* s, const ft_camera* cam, const 
         a.matHandles = s->dMatHandles;
     }
     if (a.spp == 1) { a.out = static_cast<float*>(d_out); return launchTrace(c, s, a, lane); }
-    // EXTENSION: one frame per sample, then a fixed-order resolve
+    // EXTENSION: one frame per sample, then a fixed-order resolve (per view)
     const size_t planeFloats = (size_t)a.planePixels * 3;
-    const size_t need = planeFloats * a.spp * sizeof(float);
+    const size_t need = planeFloats * a.spp * nViews * sizeof(float);
     if (need > c->planesBytes) {
         if (c->planes) { HIP_TRY(hipFree(c->planes)); c->planes = nullptr; c->planesBytes = 0; }
         HIP_TRY(hipMalloc(&c->planes, need));
@@ -662,7 +669,8 @@ static int renderLane(ft_ctx* c, const ft_scene* s, const ft_camera* cam, const 
     }
     a.out = static_cast<float*>(c->planes);
     if ((rc = launchTrace(c, s, a))) return rc;
-    HIP_TRY(ft_launch_resolve(static_cast<const float*>(c->planes), static_cast<float*>(d_out), planeFloats, a.spp, c->stream));
+    for (uint32_t k = 0; k < nViews; ++k)
+        HIP_TRY(ft_launch_resolve(static_cast<const float*>(c->planes) + k * a.spp * planeFloats, static_cast<float*>(d_out) + k * planeFloats, planeFloats, a.spp, c->stream));
     return FT_OK;
 }
 
@@ -857,6 +865,64 @@ int ft_render_hits(ft_ctx* c, const ft_scene* s, const ft_camera* cam, const ft_
     if (rc) return rc;
     if (err != hipSuccess) return hipFail(err, "ft_render_hits host output");
     if (se != hipSuccess) return hipFail(se, "ft_render_hits");
+    return ft_collect_stats(c, st);
+}
+
+// ---- ft_render_views: K cameras, one scene, one set of parameters ------------------------------------------------------
+namespace {
+
+// everything that can be refused before any device work: arguments, parameters and the job count of the whole batch
+int checkViews(ft_ctx* c, const ft_camera* cameras, int32_t n, const ft_render_params* p, const void* out) {
+    if (!c) return setErr(FT_ERR_INVALID, "null context");
+    if (!cameras || !out) return setErr(FT_ERR_INVALID, "null argument");
+    if (n < 1) return setErr(FT_ERR_INVALID, "ft_render_views: n_views must be at least 1");
+    int rc = checkParams(p); if (rc) return rc;
+    const uint64_t tiles = (uint64_t)((p->n_columns + 7) / 8) * (uint64_t)((p->height + 7) / 8);
+    if ((uint64_t)n * (uint64_t)p->spp * tiles * 64 >= 0xFFFF0000ull) return setErr(FT_ERR_UNSUPPORTED, "more than 2^32 samples in one call");
+    return requireDevice(c);
+}
+
+}  // namespace
+
+int ft_render_views_device(ft_ctx* c, const ft_scene* s, const ft_camera* cameras, int32_t n, const ft_render_params* p, void* d_out) {
+    int rc = checkViews(c, cameras, n, p, d_out); if (rc) return rc;
+    if (n == 1) return renderLane(c, s, cameras, p, d_out, 0);        // exactly ft_render_device
+    static_assert(sizeof(ft_camera) == 12 * sizeof(float), "layout");
+    const size_t bytes = (size_t)n * sizeof(ft_camera);
+    if (bytes > c->camsBytes) {
+        if (c->cams) { HIP_TRY(hipFree(c->cams)); c->cams = nullptr; c->camsBytes = 0; }
+        HIP_TRY(hipMalloc(&c->cams, bytes));
+        c->camsBytes = bytes;
+    }
+    // on the context's stream, behind the launches that may still read the previous batch's table; from a pageable copy, so that the caller's
+    // array is free when this returns (a pageable source is copied before hipMemcpyAsync returns)
+    const std::vector<ft_camera> staged(cameras, cameras + n);
+    HIP_TRY(hipMemcpyAsync(c->cams, staged.data(), bytes, hipMemcpyHostToDevice, c->stream));
+    // launches of at most FT_MAX_VIEWS views (one PH_CAM value per lane of a wave); their counters add up in the context's statistics
+    const size_t viewFloats = (size_t)p->n_columns * (size_t)p->height * 3;
+    for (int32_t k0 = 0; k0 < n; k0 += FT_MAX_VIEWS) {
+        const ViewBatch vb{static_cast<const float*>(c->cams) + 12 * (size_t)k0, (uint32_t)std::min<int32_t>(FT_MAX_VIEWS, n - k0)};
+        if ((rc = renderLane(c, s, nullptr, p, static_cast<float*>(d_out) + (size_t)k0 * viewFloats, 0, nullptr, &vb))) return rc;
+    }
+    return FT_OK;
+}
+
+// the whole batch into the context's scratch, then one copy to the (page-locked for the call) destination
+int ft_render_views(ft_ctx* c, const ft_scene* s, const ft_camera* cameras, int32_t n, const ft_render_params* p, float* out, ft_stats* st) {
+    int rc = checkViews(c, cameras, n, p, out); if (rc) return rc;
+    if (n == 1) return ft_render(c, s, cameras, p, out, st);           // exactly ft_render (its column-chunk pipeline included)
+    const size_t bytes = (size_t)n * (size_t)p->n_columns * (size_t)p->height * 3 * sizeof(float);
+    if ((rc = ensureScratch(c, bytes))) return rc;
+    bool pinnedHere = false;
+    rc = ft_render_views_device(c, s, cameras, n, p, c->scratch);
+    if (!rc) pinnedHere = pinForCall(c, out, bytes);                    // the GPU is rendering: page-lock the destination meanwhile
+    hipError_t err = hipSuccess;
+    if (!rc) err = hipMemcpyAsync(out, c->scratch, bytes, hipMemcpyDeviceToHost, c->stream);
+    const hipError_t se = hipStreamSynchronize(c->stream);             // nothing of this call is left in flight, whatever happened
+    if (pinnedHere) (void)hipHostUnregister(out);
+    if (rc) return rc;
+    if (err != hipSuccess) return hipFail(err, "ft_render_views host output");
+    if (se != hipSuccess) return hipFail(se, "ft_render_views");
     return ft_collect_stats(c, st);
 }
 

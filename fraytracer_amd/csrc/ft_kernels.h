@@ -79,7 +79,12 @@ struct FtRenderArgs {
     // miss certificate (lean kernel; kernels.hip ft_miss_certificate): a ray is due once its step count reaches certPrim (primary) / certShadow (shadow ray);
     // a wave runs the certificate when at least certMin of its lanes are due; a ray it fails on is due again certRepeat steps later (0: never)
     uint32_t cert, certPrim, certShadow, certMin, certRepeat;
+    // ft_render_views (the *_views builds only; appended so that no field above moves): one launch over nViews cameras of one scene.  Job j is view
+    // (j / jobsPerPlane) / spp, sample plane (j / jobsPerPlane) % spp; view k writes planes k * spp .. k * spp + spp - 1 (kernels.hip "Views")
+    const float* views;       // nViews x 12 floats (ft_camera) in device memory; cam above is unused
+    uint32_t nViews;          // 1 .. FT_MAX_VIEWS: PH_CAM evaluates camera l % nViews in lane l
 };
+#define FT_MAX_VIEWS 64       // views per launch (one PH_CAM value per lane); ft_render_views splits larger batches
 
 #ifdef __cplusplus
 extern "C" {
@@ -111,7 +116,7 @@ hipError_t ft_launch_tonemap(const float* frame, uint32_t X, uint32_t Y, uint32_
 // ft_render_multi: gathered slabs [rank][stripe][...] -> frame [stripe][rank][...] on the device
 hipError_t ft_launch_deinterleave(const float* recv, float* frame, unsigned long long stripeFloats, uint32_t nStripes, uint32_t nRanks, hipStream_t st);
 hipError_t ft_launch_selftest(int op, uint32_t lo, uint32_t hi, unsigned long long* d_mismatches, hipStream_t st);
-hipError_t ft_trace_occupancy(unsigned fastPath, unsigned carveKind, bool ext, bool libm, size_t ldsBytes, int* blocksPerCU);
+hipError_t ft_trace_occupancy(unsigned fastPath, unsigned carveKind, bool ext, bool libm, bool views, size_t ldsBytes, int* blocksPerCU);
 #ifdef __cplusplus
 }
 #endif

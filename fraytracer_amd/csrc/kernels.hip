@@ -1517,8 +1517,12 @@ __device__ __forceinline__ void settle(const FtRenderArgs& a, LaneState& s) {
     }
 }
 
-template <bool EXT>
-__device__ __forceinline__ void start_job(const FtRenderArgs& a, LaneState& s, const bool camKnown, const float dCam, const uint32_t leafCam) {
+// Views (ft_render_views, the *_views builds): the camera of the view a refill hands out, read once per refill round with scalar loads, and the
+// PH_CAM value of that camera (lane v of the wave's per-lane dCam / leafCam)
+struct ViewCam { f3 o, fw, up, rt; float d; uint32_t leaf; };
+
+template <bool EXT, bool VIEWS = false>
+__device__ __forceinline__ void start_job(const FtRenderArgs& a, LaneState& s, const bool camKnown, float dCam, uint32_t leafCam, const ViewCam& vc) {
     if (a.mode >= 1) {                                                 // explicit ray buffer (SdfScene.trace scene ray; 2, 3: tryTrace entries)
         const ft_ray r = a.rays[s.job];
         s.o = mk3(r.origin.x, r.origin.y, r.origin.z);
@@ -1527,7 +1531,9 @@ __device__ __forceinline__ void start_job(const FtRenderArgs& a, LaneState& s, c
         s.outIdx = s.job;
         if (EXT) { s.thr = splat3(1.0f); s.seed = s.job; }
     } else {                                                           // Image.render (Image.fs:28-34)
-        const uint32_t smp = EXT ? s.job / a.jobsPerPlane : 0u, jp = s.job - smp * a.jobsPerPlane;   // EXTENSION: sample plane (0 for spp = 1)
+        // EXTENSION: sample plane (0 for spp = 1); views: plane = view * spp + sample, the plane the output goes to
+        const uint32_t plane = (EXT || VIEWS) ? s.job / a.jobsPerPlane : 0u;
+        const uint32_t smp = VIEWS ? (EXT ? plane % a.spp : 0u) : plane, jp = s.job - plane * a.jobsPerPlane;
         const uint32_t t = jp >> 6, i = jp & 63u;
         const uint32_t tx = t / a.tilesY, ty = t - tx * a.tilesY;
         const uint32_t cl = tx * 8u + (i >> 3), y = ty * 8u + (i & 7u);
@@ -1537,11 +1543,13 @@ __device__ __forceinline__ void start_job(const FtRenderArgs& a, LaneState& s, c
         const float ox = EXT ? (float)(smp % a.sppN) / (float)a.sppN : 0.0f, oy = EXT ? (float)(smp / a.sppN) / (float)a.sppN : 0.0f;
         const float px = EXT ? ((float)x + ox) / a.maxSize : (float)x / a.maxSize;
         const float py = EXT ? ((float)y + oy) / a.maxSize : (float)y / a.maxSize;
-        const f3 fw = mk3(a.cam[3], a.cam[4], a.cam[5]), up = mk3(a.cam[6], a.cam[7], a.cam[8]), rt = mk3(a.cam[9], a.cam[10], a.cam[11]);
-        s.o = mk3(a.cam[0], a.cam[1], a.cam[2]);
+        const f3 fw = VIEWS ? vc.fw : mk3(a.cam[3], a.cam[4], a.cam[5]), up = VIEWS ? vc.up : mk3(a.cam[6], a.cam[7], a.cam[8]);
+        const f3 rt = VIEWS ? vc.rt : mk3(a.cam[9], a.cam[10], a.cam[11]);
+        s.o = VIEWS ? vc.o : mk3(a.cam[0], a.cam[1], a.cam[2]);
         s.dir = ft_normalize(fw + (px - 0.5f) * rt + (py - 0.5f) * up);       // Camera.fs:48-51
         s.len = a.length; s.eps = a.eps;
-        s.outIdx = smp * a.planePixels + cl * (uint32_t)a.H + y;
+        s.outIdx = plane * a.planePixels + cl * (uint32_t)a.H + y;
+        if (VIEWS) { dCam = vc.d; leafCam = vc.leaf; }
         if (EXT) {                                                     // EXTENSION: wavelength weight, hash seed (global pixel)
             s.thr = splat3(1.0f);
             if (a.spectral != 0u) { const uint32_t bin = smp % a.spectral; s.thr = mk3(a.spec[bin][0], a.spec[bin][1], a.spec[bin][2]); }
@@ -1576,7 +1584,7 @@ __device__ __forceinline__ void glass_bounce(const FtRenderArgs& a, LaneState& s
     if (!(cosi > 0.0f)) cosi = 0.0f;
     float n = mx[1];
     if (a.spectral != 0u) {
-        const uint32_t smp = s.job / a.jobsPerPlane;
+        const uint32_t smp = s.job / a.jobsPerPlane;                   // views: view * spp + sample, the same bin (spectral divides spp)
         n = mx[1] + mx[2] * a.spec[smp % a.spectral][3];
     }
     const float n1 = !s.inside() ? 1.0f : n, n2 = !s.inside() ? n : 1.0f;
@@ -1614,7 +1622,7 @@ __device__ __forceinline__ unsigned long long wave_sum(uint32_t v) {
     return x;
 }
 
-template <int VARIANT, bool EXT, int MATH = 0, int K = 0>
+template <int VARIANT, bool EXT, int MATH = 0, int K = 0, bool VIEWS = false>
 __device__ __forceinline__ void ft_trace_body(const FtRenderArgs& a) {
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     // the first wave of block 0 reports the shader clock it ran at (statistics only); its start clocks wait in LDS, not in registers
@@ -1647,10 +1655,17 @@ __device__ __forceinline__ void ft_trace_body(const FtRenderArgs& a) {
     s.len = 0; s.eps = 0;
     s.xs = 0;
     s.thr = splat3(1.0f); s.seed = 0;
-    // FT_OPT_REUSE: the first round of a wave in Image.render mode evaluates the scene at the camera position in every lane (PH_CAM)
+    // FT_OPT_REUSE: the first round of a wave in Image.render mode evaluates the scene at the camera position in every lane (PH_CAM); views: lane l
+    // at the position of camera l % nViews, and lane v keeps the value of view v
     bool camKnown = false;
-    float dCam = 0.0f; uint32_t leafCam = 0u;                          // wave-uniform
-    if (a.reuse != 0u && a.mode == 0u) { s.phase = PH_CAM; s.o = mk3(a.cam[0], a.cam[1], a.cam[2]); s.eps = a.eps; }
+    float dCam = 0.0f; uint32_t leafCam = 0u;                          // wave-uniform (views: per lane)
+    if (a.reuse != 0u && a.mode == 0u) {
+        s.phase = PH_CAM;
+        if (VIEWS) { const float* c = a.views + 12u * (lane % a.nViews); s.o = mk3(c[0], c[1], c[2]); }
+        else s.o = mk3(a.cam[0], a.cam[1], a.cam[2]);
+        s.eps = a.eps;
+    }
+    ViewCam vc{};
 
     for (;;) {
         // ---- refill idle lanes from the wave's chunk ------------------------------------------
@@ -1682,10 +1697,20 @@ __device__ __forceinline__ void ft_trace_body(const FtRenderArgs& a) {
                 chunkNext = base;
                 chunkEnd = (a.nJobs - base < took) ? a.nJobs : base + took;
             }
-            const uint32_t avail = chunkEnd - chunkNext;
+            uint32_t avail = chunkEnd - chunkNext;
+            if (VIEWS && a.mode == 0u) {
+                // the view of the chunk's next job (wave-uniform).  A chunk lies inside one view (views are whole multiples of 64 jobs, chunks start
+                // on multiples of their size) except where the guided hand-out's sizes change under a race: this round then stops at the view's end
+                const uint32_t jobsPerView = a.jobsPerPlane * (EXT ? a.spp : 1u);
+                const uint32_t v = chunkNext / jobsPerView, viewEnd = (v + 1u) * jobsPerView;
+                if (viewEnd - chunkNext < avail) avail = viewEnd - chunkNext;
+                cfp c = as_const(a.views) + 12u * v;
+                vc.o = ld3(c); vc.fw = ld3(c + 3); vc.up = ld3(c + 6); vc.rt = ld3(c + 9);
+                vc.d = ft_readlane_f(dCam, (int)v); vc.leaf = (uint32_t)__builtin_amdgcn_readlane((int)leafCam, (int)v);
+            }
             const uint32_t nIdle = (uint32_t)__popcll(idle);
             const uint32_t rank = (uint32_t)__popcll(idle & ((1ull << lane) - 1ull));
-            if (s.phase == PH_IDLE && rank < avail) { s.job = chunkNext + rank; start_job<EXT>(a, s, camKnown, dCam, leafCam); }
+            if (s.phase == PH_IDLE && rank < avail) { s.job = chunkNext + rank; start_job<EXT, VIEWS>(a, s, camKnown, dCam, leafCam, vc); }
             chunkNext += (nIdle < avail) ? nIdle : avail;
         }
         if (s.phase == PH_IDLE && exhausted && chunkNext == chunkEnd) s.phase = PH_DONE;
@@ -1798,7 +1823,9 @@ __device__ __forceinline__ void ft_trace_body(const FtRenderArgs& a) {
                 break;
             }
             case PH_CAM:                                               // all 64 lanes, the same point: the value every primary ray's first step is taken from
-                dCam = ft_readlane_f(d, 0); leafCam = (uint32_t)__builtin_amdgcn_readlane((int)leaf, 0); camKnown = true;
+                if (VIEWS) { dCam = d; leafCam = leaf; }               // views: lane l holds camera l % nViews
+                else { dCam = ft_readlane_f(d, 0); leafCam = (uint32_t)__builtin_amdgcn_readlane((int)leaf, 0); }
+                camKnown = true;
                 s.phase = PH_IDLE;
                 break;
             case PH_NX: *ft_sh(FT_SH_NRM) = d; s.phase = PH_NY; break;
@@ -1911,24 +1938,51 @@ extern "C" __global__ void __launch_bounds__(FT_BLOCK) ft_trace_kernel_ext_libm(
 extern "C" __global__ void __launch_bounds__(FT_BLOCK) ft_trace_kernel_smooth_spheres_ext_libm(const FtRenderArgs a) { ft_trace_body<1, true, 1>(a); }
 extern "C" __global__ void __launch_bounds__(FT_BLOCK) ft_trace_kernel_calls_libm(const FtRenderArgs a) { ft_trace_body<2, false, 1>(a); }
 extern "C" __global__ void __launch_bounds__(FT_BLOCK) ft_trace_kernel_calls_ext_libm(const FtRenderArgs a) { ft_trace_body<2, true, 1>(a); }
+// ft_render_views: every kernel above once more with the job queue over FtRenderArgs.nViews cameras (ft_trace_body VIEWS; the builds above are
+// untouched by it), same occupancy hints
+#define FT_VIEWS_KERNEL(name, occ, ...) extern "C" __global__ void __launch_bounds__(FT_BLOCK) occ name(const FtRenderArgs a) { ft_trace_body<__VA_ARGS__, true>(a); }
+#define FT_NO_OCC
+FT_VIEWS_KERNEL(ft_trace_kernel_views, FT_OCC(FT_GENERAL_WAVES), 0, false, 0, 0)
+FT_VIEWS_KERNEL(ft_trace_kernel_smooth_spheres_views, FT_NO_OCC, 1, false, 0, 0)
+FT_VIEWS_KERNEL(ft_trace_kernel_ext_views, FT_EXT_OCC, 0, true, 0, 0)
+FT_VIEWS_KERNEL(ft_trace_kernel_smooth_spheres_ext_views, FT_NO_OCC, 1, true, 0, 0)
+FT_VIEWS_KERNEL(ft_trace_kernel_calls_views, FT_CALLS_OCC, 2, false, 0, 0)
+FT_VIEWS_KERNEL(ft_trace_kernel_calls_ext_views, FT_OCC(4), 2, true, 0, 0)
+FT_VIEWS_KERNEL(ft_trace_kernel_carved_spheres_views, FT_OCC(6), 3, false, 0, (int)FT_PR_SPHERE)
+FT_VIEWS_KERNEL(ft_trace_kernel_carved_capsules_views, FT_OCC(6), 3, false, 0, (int)FT_PR_CAPSULE)
+FT_VIEWS_KERNEL(ft_trace_kernel_carved_tori_views, FT_OCC(6), 3, false, 0, (int)FT_PR_TORUS)
+FT_VIEWS_KERNEL(ft_trace_kernel_carved_triangles_views, FT_OCC(5), 3, false, 0, (int)FT_PR_TRIANGLE)
+FT_VIEWS_KERNEL(ft_trace_kernel_carved_mixed_views, FT_OCC(5), 3, false, 0, (int)FT_CARVE_MIXED)
+FT_VIEWS_KERNEL(ft_trace_kernel_libm_views, FT_NO_OCC, 0, false, 1, 0)
+FT_VIEWS_KERNEL(ft_trace_kernel_smooth_spheres_libm_views, FT_NO_OCC, 1, false, 1, 0)
+FT_VIEWS_KERNEL(ft_trace_kernel_ext_libm_views, FT_NO_OCC, 0, true, 1, 0)
+FT_VIEWS_KERNEL(ft_trace_kernel_smooth_spheres_ext_libm_views, FT_NO_OCC, 1, true, 1, 0)
+FT_VIEWS_KERNEL(ft_trace_kernel_calls_libm_views, FT_NO_OCC, 2, false, 1, 0)
+FT_VIEWS_KERNEL(ft_trace_kernel_calls_ext_libm_views, FT_NO_OCC, 2, true, 1, 0)
 // The one table of trace kernels, for launches and occupancy queries alike.  variant: the kernel family (FtSceneDev.fastPath as capi.cpp planTrace
 // decides it: 0 general, 1 lean smooth-sphere, 2 general with call children, 3 carved union).  nullptr where no kernel exists: a carved union has
-// no EXTENSION and no *_libm build.
-static const void* ft_trace_kernel_for(unsigned variant, unsigned carveKind, bool ext, bool libm) {
-    static const void* const families[3][2][2] = {     // [variant][libm][ext]
-        {{(const void*)ft_trace_kernel, (const void*)ft_trace_kernel_ext}, {(const void*)ft_trace_kernel_libm, (const void*)ft_trace_kernel_ext_libm}},
-        {{(const void*)ft_trace_kernel_smooth_spheres, (const void*)ft_trace_kernel_smooth_spheres_ext},
-         {(const void*)ft_trace_kernel_smooth_spheres_libm, (const void*)ft_trace_kernel_smooth_spheres_ext_libm}},
-        {{(const void*)ft_trace_kernel_calls, (const void*)ft_trace_kernel_calls_ext}, {(const void*)ft_trace_kernel_calls_libm, (const void*)ft_trace_kernel_calls_ext_libm}},
+// no EXTENSION and no *_libm build.  views: the ft_render_views build of the same kernel.
+static const void* ft_trace_kernel_for(unsigned variant, unsigned carveKind, bool ext, bool libm, bool views) {
+    static const void* const families[2][3][2][2] = {     // [views][variant][libm][ext]
+        {{{(const void*)ft_trace_kernel, (const void*)ft_trace_kernel_ext}, {(const void*)ft_trace_kernel_libm, (const void*)ft_trace_kernel_ext_libm}},
+         {{(const void*)ft_trace_kernel_smooth_spheres, (const void*)ft_trace_kernel_smooth_spheres_ext},
+          {(const void*)ft_trace_kernel_smooth_spheres_libm, (const void*)ft_trace_kernel_smooth_spheres_ext_libm}},
+         {{(const void*)ft_trace_kernel_calls, (const void*)ft_trace_kernel_calls_ext}, {(const void*)ft_trace_kernel_calls_libm, (const void*)ft_trace_kernel_calls_ext_libm}}},
+        {{{(const void*)ft_trace_kernel_views, (const void*)ft_trace_kernel_ext_views},
+          {(const void*)ft_trace_kernel_libm_views, (const void*)ft_trace_kernel_ext_libm_views}},
+         {{(const void*)ft_trace_kernel_smooth_spheres_views, (const void*)ft_trace_kernel_smooth_spheres_ext_views},
+          {(const void*)ft_trace_kernel_smooth_spheres_libm_views, (const void*)ft_trace_kernel_smooth_spheres_ext_libm_views}},
+         {{(const void*)ft_trace_kernel_calls_views, (const void*)ft_trace_kernel_calls_ext_views},
+          {(const void*)ft_trace_kernel_calls_libm_views, (const void*)ft_trace_kernel_calls_ext_libm_views}}},
     };
-    if (variant < 3) return families[variant][libm][ext];
+    if (variant < 3) return families[views][variant][libm][ext];
     if (variant > 3 || ext || libm) return nullptr;
     switch (carveKind) {
-        case FT_PR_SPHERE: return (const void*)ft_trace_kernel_carved_spheres;
-        case FT_PR_CAPSULE: return (const void*)ft_trace_kernel_carved_capsules;
-        case FT_PR_TORUS: return (const void*)ft_trace_kernel_carved_tori;
-        case FT_PR_TRIANGLE: return (const void*)ft_trace_kernel_carved_triangles;
-        default: return (const void*)ft_trace_kernel_carved_mixed;     // boxes (EXTENSION) and mixed kinds
+        case FT_PR_SPHERE: return views ? (const void*)ft_trace_kernel_carved_spheres_views : (const void*)ft_trace_kernel_carved_spheres;
+        case FT_PR_CAPSULE: return views ? (const void*)ft_trace_kernel_carved_capsules_views : (const void*)ft_trace_kernel_carved_capsules;
+        case FT_PR_TORUS: return views ? (const void*)ft_trace_kernel_carved_tori_views : (const void*)ft_trace_kernel_carved_tori;
+        case FT_PR_TRIANGLE: return views ? (const void*)ft_trace_kernel_carved_triangles_views : (const void*)ft_trace_kernel_carved_triangles;
+        default: return views ? (const void*)ft_trace_kernel_carved_mixed_views : (const void*)ft_trace_kernel_carved_mixed;   // boxes (EXTENSION) and mixed kinds
     }
 }
 
@@ -2240,14 +2294,14 @@ extern "C" int ft_debug_set_hsaco(const char* path) {
 extern "C" hipError_t ft_launch_trace(const FtRenderArgs* a, unsigned blocks, size_t ldsBytes, hipStream_t st) {
     const bool ext = a->ext != 0u, libm = a->math != 0u;
 #ifdef FT_EXPERIMENT
-    if (a->S.fastPath == 1 && !ext && !libm && ft_exp_fn) {
+    if (a->S.fastPath == 1 && !ext && !libm && !a->views && ft_exp_fn) {
         FtRenderArgs args = *a;
         size_t size = sizeof(args);
         void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &args, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
         return hipModuleLaunchKernel(ft_exp_fn, blocks, 1, 1, FT_BLOCK, 1, 1, (unsigned)ldsBytes, st, nullptr, extra);
     }
 #endif
-    const void* k = ft_trace_kernel_for(a->S.fastPath, a->carve.kind, ext, libm);
+    const void* k = ft_trace_kernel_for(a->S.fastPath, a->carve.kind, ext, libm, a->views != nullptr);
     if (!k) return hipErrorInvalidDeviceFunction;
     FtRenderArgs args = *a;
     void* kp[] = {&args};
@@ -2341,8 +2395,8 @@ extern "C" hipError_t ft_debug_union_counters(unsigned long long out[12]) {
     return hipMemcpyToSymbol(HIP_SYMBOL(ft_union_dbg), zero, sizeof(zero));
 }
 #endif
-extern "C" hipError_t ft_trace_occupancy(unsigned fastPath, unsigned carveKind, bool ext, bool libm, size_t ldsBytes, int* blocksPerCU) {
-    const void* k = ft_trace_kernel_for(fastPath, carveKind, ext, libm);
+extern "C" hipError_t ft_trace_occupancy(unsigned fastPath, unsigned carveKind, bool ext, bool libm, bool views, size_t ldsBytes, int* blocksPerCU) {
+    const void* k = ft_trace_kernel_for(fastPath, carveKind, ext, libm, views);
     if (!k) return hipErrorInvalidDeviceFunction;
     return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocksPerCU, k, FT_BLOCK, ldsBytes);
 }

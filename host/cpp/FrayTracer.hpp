@@ -11,6 +11,7 @@
 //   SdfLight::directional/point                         src/FrayTracer/SdfLight.fs:6-42
 //   Lens::create, Camera::lookAt                        src/FrayTracer/Camera.fs:11-42
 //   Image::renderScene                                  src/FrayTracer/Image.fs:26-35 + SdfScene.fs:7-28
+//   Image::renderViews                                  renderScene over several cameras in one launch (ft_render_views)
 #pragma once
 #include <stdexcept>
 #include <string>
@@ -125,6 +126,23 @@ inline std::vector<float> renderScene(float epsilon, float length, ImageSize siz
     ft_render_params p{size.X, size.Y, 0, size.X, size.X, 1, 0, 1, epsilon, length, 0, 0.0f, 0, 0};
     ft_stats st{};
     int rc = ft_render(ctx, s, &camera, &p, out.data(), &st);
+    ft_scene_destroy(s);
+    check(rc);
+    if (stats) *stats = st;
+    return out;
+}
+// renderScene of one scene from every camera of `cameras` in one launch: image k at 3 * (k * X * Y + x * Y + y), bit for bit renderScene's
+// image for cameras[k]; stats of the whole batch
+inline std::vector<float> renderViews(float epsilon, float length, ImageSize size, const std::vector<ft_camera>& cameras, const SdfScene& scene,
+                                      ft_stats* stats = nullptr) {
+    ft_ctx* ctx = scene.Object.ctx;
+    std::vector<ft_handle> lights; for (auto& l : scene.Lights) lights.push_back(l.Node);
+    ft_scene* s = nullptr;
+    check(ft_scene_create(ctx, scene.Object.Node, &scene.BackgroundColor.v.x, lights.data(), (int)lights.size(), &s));
+    std::vector<float> out(cameras.size() * (size_t)size.X * size.Y * 3);
+    ft_render_params p{size.X, size.Y, 0, size.X, size.X, 1, 0, 1, epsilon, length, 0, 0.0f, 0, 0};
+    ft_stats st{};
+    int rc = ft_render_views(ctx, s, cameras.data(), (int32_t)cameras.size(), &p, out.data(), &st);
     ft_scene_destroy(s);
     check(rc);
     if (stats) *stats = st;

@@ -220,6 +220,17 @@ int ft_render_hits(ft_ctx*, const ft_scene*, const ft_camera*, const ft_render_p
 /* Same into device memory, asynchronous like ft_render_device (pair with ft_collect_stats); d_hits 16-byte aligned. */
 int ft_render_hits_device(ft_ctx*, const ft_scene*, const ft_camera*, const ft_render_params*,
                           void* d_out_rgb, void* d_hits, void* d_material);
+/* n_views cameras (host memory; the library uploads them), one scene, one set of render params: out = n_views x n_columns x height x 3
+ * float32, view-major; block k is bit for bit what ft_render(ctx, scene, &cameras[k], params, ...) writes, every field of the params applied
+ * to each view.  One job queue covers the views, so one launch pays one drain for all of them (batches of more than 64 views take one launch
+ * per 64).  stats: one ft_stats for the batch — each count the sum of the single-view calls' counts.  FT_ERR_UNSUPPORTED when
+ * n_views x spp x tiles x 64 reaches 2^32.  n_views = 1 is exactly ft_render.  The host form renders the batch into device scratch and copies
+ * it out once (a pageable destination is page-locked for the call, like ft_render's). */
+int ft_render_views(ft_ctx*, const ft_scene*, const ft_camera* cameras, int32_t n_views,
+                    const ft_render_params*, float* out, ft_stats* stats);
+/* Same into device memory, asynchronous like ft_render_device (pair with ft_collect_stats).  n_views = 1 is exactly ft_render_device. */
+int ft_render_views_device(ft_ctx*, const ft_scene*, const ft_camera* cameras, int32_t n_views,
+                           const ft_render_params*, void* d_out);
 
 /* ---- around the hot path: tone map + 8-bit output -------------------------------- */
 /* Image.toColors gamma rng image (Image.fs:37-50): max = Max(0.01, max over all channels); per channel
