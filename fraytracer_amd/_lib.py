@@ -133,6 +133,8 @@ SYMBOLS = {
     "ft_render_hits_device": (C.c_int, [_P, _P, C.POINTER(CameraS), C.POINTER(RenderParams), _P, _P, _P]),
     "ft_render_views": (C.c_int, [_P, _P, C.POINTER(CameraS), C.c_int32, C.POINTER(RenderParams), _P, C.POINTER(Stats)]),
     "ft_render_views_device": (C.c_int, [_P, _P, C.POINTER(CameraS), C.c_int32, C.POINTER(RenderParams), _P]),
+    "ft_render_views_hits": (C.c_int, [_P, _P, C.POINTER(CameraS), C.c_int32, C.POINTER(RenderParams), _P, _P, _P, C.POINTER(Stats)]),
+    "ft_render_views_hits_device": (C.c_int, [_P, _P, C.POINTER(CameraS), C.c_int32, C.POINTER(RenderParams), _P, _P, _P]),
     "ft_tone_map_device": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.POINTER(TonemapParams), _P]),
     "ft_tone_map": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.POINTER(TonemapParams), _P, C.POINTER(C.c_float)]),
     "ft_tone_map_host": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.POINTER(TonemapParams), _P, C.POINTER(C.c_float)]),

@@ -466,7 +466,8 @@ class PixelHits:
     """EXTENSION (ft_render_hits): SdfObject.tryTrace scene.Object of every pixel's camera ray (sample 0), laid out like the
     frame.  `records` is float32 [n_columns, Y, 16] in the layout of ft_object_trace_result — Ray pulled back by epsilon
     (Origin = Position, Direction, Length, Epsilon), Normal, Color, hit flag (int32 bits), 0; a miss (ValueNone) is all zero.
-    `material` is int32 [n_columns, Y]: the handle of the material the hit picked, -1 on a miss (None if not asked for)."""
+    `material` is int32 [n_columns, Y]: the handle of the material the hit picked, -1 on a miss (None if not asked for).
+    ft_render_views_hits: every array has a leading view axis, [K, n_columns, Y, ...]; the properties keep it."""
 
     def __init__(self, records, material=None, materials=None):
         self.records = records
@@ -648,6 +649,30 @@ class DeviceScene:
         p = self._params(imageSize, epsilon, length, **tiling_and_ext)
         arr, k = self._cameras(cameras)
         check(lib.ft_render_views_device(self.device._ctx, self._scene, arr, k, C.byref(p), C.c_void_p(d_out_ptr)))
+        return p.n_columns
+
+    def render_views_hits(self, epsilon, length, imageSize, cameras, shade=False, material=True, records=True, **tiling_and_ext):
+        """EXTENSION ft_render_views_hits: render_hits of one scene from each camera of `cameras` in one job queue -> (PixelHits with
+        records float32 [K, n_columns, Y, 16] and material int32 [K, n_columns, Y], image float32 [K, n_columns, Y, 3] or None, stats
+        of the whole batch).  Block k of each is bit for bit render_hits(..., cameras[k], shade, **tiling_and_ext)'s."""
+        p = self._params(imageSize, epsilon, length, **tiling_and_ext)
+        arr, k = self._cameras(cameras)
+        shape = (k, p.n_columns, p.height)
+        img = np.empty(shape + (3,), np.float32) if shade else None
+        rec = np.empty(shape + (16,), np.float32) if records else None
+        mat = np.empty(shape, np.int32) if material else None
+        ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        st = _lib.Stats()
+        check(lib.ft_render_views_hits(self.device._ctx, self._scene, arr, k, C.byref(p), ptr(img), ptr(rec), ptr(mat), C.byref(st)))
+        return PixelHits(rec, mat, self.materials), img, st.as_dict()
+
+    def render_views_hits_device(self, epsilon, length, imageSize, cameras, d_hits_ptr, d_material_ptr=None, d_out_ptr=None, **tiling_and_ext):
+        """asynchronous ft_render_views_hits_device into device memory (pointers as int, None = not asked; view-major, the records
+        16-byte aligned, n_views x n_columns x Y x 16 float32); pair with collect_stats()."""
+        p = self._params(imageSize, epsilon, length, **tiling_and_ext)
+        arr, k = self._cameras(cameras)
+        ptr = lambda a: None if not a else C.c_void_p(a)
+        check(lib.ft_render_views_hits_device(self.device._ctx, self._scene, arr, k, C.byref(p), ptr(d_out_ptr), ptr(d_hits_ptr), ptr(d_material_ptr)))
         return p.n_columns
 
     def collect_stats(self):
@@ -876,6 +901,14 @@ class Image:
         SdfScene.trace: the SdfObjectTraceResult voption of every pixel as PixelHits (records [X, Y, 16], material handles)."""
         dev = device if device is not None else Device.default(0)
         hits, _, _ = dev.scene(scene).render_hits(epsilon, length, imageSize, camera)
+        return hits
+
+    @staticmethod
+    def renderViewsHits(epsilon, length, imageSize, cameras, scene, device=None):
+        """EXTENSION: Image.renderHits of one scene from every camera of `cameras` in one launch (ft_render_views_hits) -> PixelHits with
+        records [K, X, Y, 16] and material handles [K, X, Y]; view k is Image.renderHits epsilon length imageSize cameras[k] scene."""
+        dev = device if device is not None else Device.default(0)
+        hits, _, _ = dev.scene(scene).render_views_hits(epsilon, length, imageSize, cameras)
         return hits
 
     @staticmethod

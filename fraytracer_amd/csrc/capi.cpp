@@ -617,12 +617,13 @@ struct HitBufs { void* hits; void* material; };
 struct ViewBatch { const float* cams; uint32_t n; };
 
 // hb != NULL: the EXTENSION build also writes the hit buffers; d_out = NULL then means hits only (one ray per pixel, the EXTENSION fields of p
-// do not apply).  vb != NULL: vb->n views instead of `cam`, written view after view (n x n_columns x height x 3 floats at d_out)
+// do not apply).  vb != NULL: vb->n views instead of `cam`, written view after view (n x n_columns x height x 3 floats at d_out; with hb,
+// n x n_columns x height records and material handles)
 static int renderLane(ft_ctx* c, const ft_scene* s, const ft_camera* cam, const ft_render_params* params, void* d_out, int lane,
                       const HitBufs* hb = nullptr, const ViewBatch* vb = nullptr) {
     int rc = requireDevice(c); if (rc) return rc;
     if (!s || s->ctx != c || !(vb ? vb->cams : (const void*)cam) || (!d_out && !hb)) return setErr(FT_ERR_INVALID, "bad argument (scene must belong to this context)");
-    if (vb && (hb || vb->n < 1u || vb->n > FT_MAX_VIEWS)) return setErr(FT_ERR_INVALID, "internal: a view batch has 1 .. 64 views and no hit buffers");
+    if (vb && (vb->n < 1u || vb->n > FT_MAX_VIEWS)) return setErr(FT_ERR_INVALID, "internal: a view batch has 1 .. 64 views");
     if ((rc = checkParams(params))) return rc;
     ft_render_params hitsOnly;
     const ft_render_params* p = params;
@@ -871,22 +872,20 @@ int ft_render_hits(ft_ctx* c, const ft_scene* s, const ft_camera* cam, const ft_
 // ---- ft_render_views: K cameras, one scene, one set of parameters ------------------------------------------------------
 namespace {
 
-// everything that can be refused before any device work: arguments, parameters and the job count of the whole batch
-int checkViews(ft_ctx* c, const ft_camera* cameras, int32_t n, const ft_render_params* p, const void* out) {
+// everything that can be refused before any device work: arguments, parameters and the job count of the whole batch (hitsOnly: one sample
+// plane a view, whatever spp says)
+int checkViews(ft_ctx* c, const ft_camera* cameras, int32_t n, const ft_render_params* p, const void* out, bool hitsOnly = false) {
     if (!c) return setErr(FT_ERR_INVALID, "null context");
     if (!cameras || !out) return setErr(FT_ERR_INVALID, "null argument");
     if (n < 1) return setErr(FT_ERR_INVALID, "ft_render_views: n_views must be at least 1");
     int rc = checkParams(p); if (rc) return rc;
     const uint64_t tiles = (uint64_t)((p->n_columns + 7) / 8) * (uint64_t)((p->height + 7) / 8);
-    if ((uint64_t)n * (uint64_t)p->spp * tiles * 64 >= 0xFFFF0000ull) return setErr(FT_ERR_UNSUPPORTED, "more than 2^32 samples in one call");
+    if ((uint64_t)n * (uint64_t)(hitsOnly ? 1 : p->spp) * tiles * 64 >= 0xFFFF0000ull) return setErr(FT_ERR_UNSUPPORTED, "more than 2^32 samples in one call");
     return requireDevice(c);
 }
 
-}  // namespace
-
-int ft_render_views_device(ft_ctx* c, const ft_scene* s, const ft_camera* cameras, int32_t n, const ft_render_params* p, void* d_out) {
-    int rc = checkViews(c, cameras, n, p, d_out); if (rc) return rc;
-    if (n == 1) return renderLane(c, s, cameras, p, d_out, 0);        // exactly ft_render_device
+// the batch's cameras into the context's device table (12 floats each)
+int stageCameras(ft_ctx* c, const ft_camera* cameras, int32_t n) {
     static_assert(sizeof(ft_camera) == 12 * sizeof(float), "layout");
     const size_t bytes = (size_t)n * sizeof(ft_camera);
     if (bytes > c->camsBytes) {
@@ -898,13 +897,29 @@ int ft_render_views_device(ft_ctx* c, const ft_scene* s, const ft_camera* camera
     // array is free when this returns (a pageable source is copied before hipMemcpyAsync returns)
     const std::vector<ft_camera> staged(cameras, cameras + n);
     HIP_TRY(hipMemcpyAsync(c->cams, staged.data(), bytes, hipMemcpyHostToDevice, c->stream));
-    // launches of at most FT_MAX_VIEWS views (one PH_CAM value per lane of a wave); their counters add up in the context's statistics
-    const size_t viewFloats = (size_t)p->n_columns * (size_t)p->height * 3;
+    return FT_OK;
+}
+
+// launches of at most FT_MAX_VIEWS views (one PH_CAM value per lane of a wave), each at its views' offsets into the outputs; their counters add
+// up in the context's statistics.  hb: the hit buffers of the whole batch (NULL: none).
+int launchViews(ft_ctx* c, const ft_scene* s, const ft_camera* cameras, int32_t n, const ft_render_params* p, void* d_out, const HitBufs* hb) {
+    int rc = stageCameras(c, cameras, n); if (rc) return rc;
+    const size_t px = (size_t)p->n_columns * (size_t)p->height;
+    auto at = [](void* base, size_t bytes) { return base ? static_cast<void*>(static_cast<unsigned char*>(base) + bytes) : nullptr; };
     for (int32_t k0 = 0; k0 < n; k0 += FT_MAX_VIEWS) {
         const ViewBatch vb{static_cast<const float*>(c->cams) + 12 * (size_t)k0, (uint32_t)std::min<int32_t>(FT_MAX_VIEWS, n - k0)};
-        if ((rc = renderLane(c, s, nullptr, p, static_cast<float*>(d_out) + (size_t)k0 * viewFloats, 0, nullptr, &vb))) return rc;
+        const HitBufs part = hb ? HitBufs{at(hb->hits, (size_t)k0 * px * 64), at(hb->material, (size_t)k0 * px * 4)} : HitBufs{};
+        if ((rc = renderLane(c, s, nullptr, p, at(d_out, (size_t)k0 * px * 12), 0, hb ? &part : nullptr, &vb))) return rc;
     }
     return FT_OK;
+}
+
+}  // namespace
+
+int ft_render_views_device(ft_ctx* c, const ft_scene* s, const ft_camera* cameras, int32_t n, const ft_render_params* p, void* d_out) {
+    int rc = checkViews(c, cameras, n, p, d_out); if (rc) return rc;
+    if (n == 1) return renderLane(c, s, cameras, p, d_out, 0);        // exactly ft_render_device
+    return launchViews(c, s, cameras, n, p, d_out, nullptr);
 }
 
 // the whole batch into the context's scratch, then one copy to the (page-locked for the call) destination
@@ -923,6 +938,63 @@ int ft_render_views(ft_ctx* c, const ft_scene* s, const ft_camera* cameras, int3
     if (rc) return rc;
     if (err != hipSuccess) return hipFail(err, "ft_render_views host output");
     if (se != hipSuccess) return hipFail(se, "ft_render_views");
+    return ft_collect_stats(c, st);
+}
+
+// ---- ft_render_views_hits: the hit buffers of K cameras, one scene, one set of parameters ------------------------------------------
+namespace {
+
+int checkViewsHits(ft_ctx* c, const ft_camera* cameras, int32_t n, const ft_render_params* p, const void* rgb, const void* hits, const void* mat) {
+    if (!rgb && !hits && !mat) return setErr(FT_ERR_INVALID, "ft_render_views_hits: no output asked for");
+    return checkViews(c, cameras, n, p, rgb ? rgb : hits ? hits : mat, !rgb);
+}
+
+}  // namespace
+
+int ft_render_views_hits_device(ft_ctx* c, const ft_scene* s, const ft_camera* cameras, int32_t n, const ft_render_params* p, void* d_out_rgb,
+                                void* d_hits, void* d_material) {
+    if ((reinterpret_cast<uintptr_t>(d_hits) & 15u) || (reinterpret_cast<uintptr_t>(d_material) & 3u) || (reinterpret_cast<uintptr_t>(d_out_rgb) & 3u))
+        return setErr(FT_ERR_INVALID, "ft_render_views_hits: the hit buffer must be 16-byte aligned, the image and the material plane 4-byte aligned");
+    int rc = checkViewsHits(c, cameras, n, p, d_out_rgb, d_hits, d_material); if (rc) return rc;
+    if (!d_hits && !d_material) return ft_render_views_device(c, s, cameras, n, p, d_out_rgb);         // the frames alone
+    if (n == 1) return ft_render_hits_device(c, s, cameras, p, d_out_rgb, d_hits, d_material);        // exactly ft_render_hits_device
+    const HitBufs hb{d_hits, d_material};
+    return launchViews(c, s, cameras, n, p, d_out_rgb, &hb);
+}
+
+// EXTENSION: one launch group (<= FT_MAX_VIEWS views) at a time into the context's scratch ([images | records | material planes]), each copied out
+// behind its launch on the context's stream before the next group reuses the scratch: device memory stays bounded by one group.  The destinations
+// are page-locked for the call while the first group renders (like ft_render_views'), so the copies run at link rate; a group's copy and the next
+// group's render share the stream, one after the other.
+int ft_render_views_hits(ft_ctx* c, const ft_scene* s, const ft_camera* cameras, int32_t n, const ft_render_params* p, float* out_rgb,
+                         ft_object_trace_result* out_hits, int32_t* out_material, ft_stats* st) {
+    static_assert(sizeof(ft_object_trace_result) == 64, "layout");
+    int rc = checkViewsHits(c, cameras, n, p, out_rgb, out_hits, out_material); if (rc) return rc;
+    if (!out_hits && !out_material) return ft_render_views(c, s, cameras, n, p, out_rgb, st);         // the frames alone
+    if (n == 1) return ft_render_hits(c, s, cameras, p, out_rgb, out_hits, out_material, st);         // exactly ft_render_hits
+    const size_t px = (size_t)p->n_columns * (size_t)p->height, g = (size_t)std::min<int32_t>(n, FT_MAX_VIEWS);
+    const size_t oHits = align256(out_rgb ? g * px * 12 : 0), oMat = oHits + align256(out_hits ? g * px * 64 : 0);
+    if ((rc = ensureScratch(c, oMat + (out_material ? g * px * 4 : 0)))) return rc;
+    unsigned char* base = static_cast<unsigned char*>(c->scratch);
+    hipError_t err = hipSuccess;
+    void* const dst[3] = {out_rgb, out_hits, out_material};
+    const size_t dstBytes[3] = {(size_t)n * px * 12, (size_t)n * px * 64, (size_t)n * px * 4};
+    bool pinnedHere[3] = {false, false, false};
+    for (int32_t k0 = 0; k0 < n && !rc && err == hipSuccess; k0 += FT_MAX_VIEWS) {
+        const size_t m = (size_t)std::min<int32_t>(FT_MAX_VIEWS, n - k0), k = (size_t)k0;
+        rc = ft_render_views_hits_device(c, s, cameras + k0, (int32_t)m, p, out_rgb ? base : nullptr, out_hits ? base + oHits : nullptr,
+                                         out_material ? base + oMat : nullptr);
+        if (!rc && k0 == 0)                                            // the GPU renders the first group: page-lock the destinations meanwhile
+            for (int i = 0; i < 3; ++i) if (dst[i]) pinnedHere[i] = pinForCall(c, dst[i], dstBytes[i]);
+        if (!rc && out_rgb) err = hipMemcpyAsync(out_rgb + k * px * 3, base, m * px * 12, hipMemcpyDeviceToHost, c->stream);
+        if (!rc && err == hipSuccess && out_hits) err = hipMemcpyAsync(out_hits + k * px, base + oHits, m * px * 64, hipMemcpyDeviceToHost, c->stream);
+        if (!rc && err == hipSuccess && out_material) err = hipMemcpyAsync(out_material + k * px, base + oMat, m * px * 4, hipMemcpyDeviceToHost, c->stream);
+    }
+    const hipError_t se = hipStreamSynchronize(c->stream);             // nothing of this call is left in flight, whatever happened
+    for (int i = 0; i < 3; ++i) if (pinnedHere[i]) (void)hipHostUnregister(dst[i]);
+    if (rc) return rc;
+    if (err != hipSuccess) return hipFail(err, "ft_render_views_hits host output");
+    if (se != hipSuccess) return hipFail(se, "ft_render_views_hits");
     return ft_collect_stats(c, st);
 }
 

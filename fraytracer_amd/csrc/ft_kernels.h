@@ -72,7 +72,7 @@ struct FtRenderArgs {
     uint32_t reuse;           // 1: a secondary ray's first evaluation — at the hit position — is the value the normal's centre probe computed there (FT_OPT_REUSE; kernels.hip FT_SH_D0)
     FtCarve carve;            // FtSceneDev.fastPath == 3: the union's tail and its terminated candidate lists (ft_device.h "Carved union")
     // EXTENSION ft_render_hits (EXTENSION builds only; appended so that no field above moves): per pixel, SdfObject.tryTrace of its sample-0 ray
-    float* hitsOut;           // 16 dwords per pixel (ft_object_trace_result) at cl * H + y; NULL: not asked
+    float* hitsOut;           // 16 dwords per pixel (ft_object_trace_result) at cl * H + y (*_views builds: view * planePixels + cl * H + y); NULL: not asked
     int32_t* matOut;          // material handle per pixel (-1 on a miss); NULL: not asked
     const int32_t* matHandles;   // dense material index -> context handle (ft_material_*): the inverse of the flattener's remap
     uint32_t hits;            // 0: no hit buffers; 1: with the frame; 2: hits only (no lighting, nothing written to out)

@@ -1274,9 +1274,20 @@ __device__ __forceinline__ void write_ray(float* o, f3 origin, f3 dir, float len
 }
 
 // ft_render_hits (EXTENSION builds, mode 0; a.hits != 0 only there): does the segment this lane ends now carry the pixel's hit record?  Only the
-// first segment (no glass interaction yet) of sample 0, whose ray is the reference's pixel ray (spp offset 0)
+// first segment (no glass interaction yet) of sample 0, whose ray is the reference's pixel ray (spp offset 0).  Views: sample 0 of every view, i.e.
+// the job's plane (view * spp + sample, start_job) a multiple of spp
+template <bool VIEWS = false>
 __device__ __forceinline__ bool ends_hit_segment(const FtRenderArgs& a, const LaneState& s) {
+    if (VIEWS) return a.hits != 0u && (s.job / a.jobsPerPlane) % a.spp == 0u && s.bounce() == 0u;
     return a.hits != 0u && s.job < a.jobsPerPlane && s.bounce() == 0u;
+}
+// the pixel's slot in the hit buffers: s.outIdx, the image's index; views: the image's index counts spp planes per view, the hit buffers one, so
+// view * planePixels + pixel = outIdx - view * (spp - 1) * planePixels (plane = view * spp for sample 0)
+template <bool VIEWS = false>
+__device__ __forceinline__ uint32_t hit_index(const FtRenderArgs& a, const LaneState& s) {
+    if (!VIEWS) return s.outIdx;
+    const uint32_t plane = s.job / a.jobsPerPlane;
+    return s.outIdx - (plane - plane / a.spp) * a.planePixels;
 }
 // the record as ft_object_try_trace writes it (mode 3 in the round's switch): four 16-byte stores into the 64-byte slot, plus the material handle
 __device__ __forceinline__ void write_hit_record(const FtRenderArgs& a, uint32_t idx, v4f r0, v4f r1, v4f r2, v4f r3, int32_t handle) {
@@ -1422,7 +1433,7 @@ __device__ __forceinline__ int first_step_from_cache(LaneState& s) {
 
 // advance a lane until it needs an SDF evaluation (or is idle): everything in SdfScene.trace that
 // is not a Distance call.
-template <bool EXT>
+template <bool EXT, bool VIEWS = false>
 __device__ __forceinline__ void settle(const FtRenderArgs& a, LaneState& s) {
     const float piInv = 1.0f / 3.14159274101257324f;                   // Math.fs:28-30
     for (;;) {
@@ -1433,7 +1444,7 @@ __device__ __forceinline__ void settle(const FtRenderArgs& a, LaneState& s) {
                 if (EXT && a.mode >= 2u) write_try_trace_miss(a, s);   // ValueNone of the tryTrace entries
                 else {
                     // every miss of a primary ray ends here: Length used up, escape, NaN and the step cap (s.len = -1), the camera shortcuts of start_job
-                    if (EXT && ends_hit_segment(a, s)) write_hit_miss(a, s.outIdx);
+                    if (EXT && ends_hit_segment<VIEWS>(a, s)) write_hit_miss(a, hit_index<VIEWS>(a, s));
                     if (!EXT || a.hits != 2u) emit<EXT>(a, s, mk3(a.S.bg[0], a.S.bg[1], a.S.bg[2]));
                 }
                 s.phase = PH_IDLE;
@@ -1564,7 +1575,7 @@ __device__ __forceinline__ void start_job(const FtRenderArgs& a, LaneState& s, c
         else if (dCam < s.eps) { ft_count(FT_C_HITP); s.leaf = leafCam; s.phase = PH_NX; }   // a hit at the camera itself,
         else { s.o = s.o + s.dir * dCam; s.len = s.len - dCam; s.steps = 1; }               // or the first step (Ray.fs:9-13)
     }
-    settle<EXT>(a, s);
+    settle<EXT, VIEWS>(a, s);
 }
 
 // EXTENSION (BASELINE.json config 5): a path segment ended on leaf s.leaf with normal s.nrm at s.hp.  Glass leaf:
@@ -1722,7 +1733,7 @@ __device__ __forceinline__ void ft_trace_body(const FtRenderArgs& a) {
             if ((uint32_t)__popcll(__ballot(due)) >= a.certMin) {
                 const bool holds = ft_miss_certificate(a.S, ldsC + 0, due, s.o, s.dir, s.eps, s.len, s.steps);
                 if (due) {
-                    if (holds) { s.len = -1.0f; settle<EXT>(a, s); }    // resolved as the miss its march ends in (settle: as for ft_never_enters)
+                    if (holds) { s.len = -1.0f; settle<EXT, VIEWS>(a, s); }    // resolved as the miss its march ends in (settle: as for ft_never_enters)
                     else s.certAt = a.certRepeat != 0u ? s.steps + a.certRepeat : 0xffffffffu;
                 }
                 // every lane resolved (a tile whose rays all miss): refill now instead of spending an empty round
@@ -1840,10 +1851,10 @@ __device__ __forceinline__ void ft_trace_body(const FtRenderArgs& a) {
                 sh_set3(FT_SH_LACC, mk3(a.S.bg[0], a.S.bg[1], a.S.bg[2]));     // SdfScene.fs:12
                 s.lidx = 0;
                 s.phase = PH_LIGHTS;
-                if (EXT && ends_hit_segment(a, s)) {                   // ft_render_hits: the mode-3 record below, before any glass bounce moves the ray
+                if (EXT && ends_hit_segment<VIEWS>(a, s)) {            // ft_render_hits: the mode-3 record below, before any glass bounce moves the ray
                     cfp m = as_const(a.S.materials) + 3u * s.leaf;
                     const float len = s.len - (-s.eps);                // Ray.move -eps: Length - (-eps)
-                    write_hit_record(a, s.outIdx, v4f{hp.x, hp.y, hp.z, s.dir.x}, v4f{s.dir.y, s.dir.z, len, s.eps},
+                    write_hit_record(a, hit_index<VIEWS>(a, s), v4f{hp.x, hp.y, hp.z, s.dir.x}, v4f{s.dir.y, s.dir.z, len, s.eps},
                                      v4f{nrm.x, nrm.y, nrm.z, m[0]}, v4f{m[1], m[2], __int_as_float(1), 0.0f}, as_const(a.matHandles)[s.leaf]);
                     if (a.hits == 2u) s.phase = PH_IDLE;               // hits only (no AO, no glass: the host clears those)
                 }
@@ -1861,7 +1872,7 @@ __device__ __forceinline__ void ft_trace_body(const FtRenderArgs& a) {
             }
             default: break;
             }
-            settle<EXT>(a, s);
+            settle<EXT, VIEWS>(a, s);
         }
         FT_UDBG_T1(7, tRound);
     }

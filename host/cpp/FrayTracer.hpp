@@ -12,6 +12,7 @@
 //   Lens::create, Camera::lookAt                        src/FrayTracer/Camera.fs:11-42
 //   Image::renderScene                                  src/FrayTracer/Image.fs:26-35 + SdfScene.fs:7-28
 //   Image::renderViews                                  renderScene over several cameras in one launch (ft_render_views)
+//   Image::renderViewsHits                              renderHits over several cameras in one launch (ft_render_views_hits)
 #pragma once
 #include <stdexcept>
 #include <string>
@@ -162,6 +163,24 @@ inline std::vector<ft_object_trace_result> renderHits(float epsilon, float lengt
     ft_render_params p{size.X, size.Y, 0, size.X, size.X, 1, 0, 1, epsilon, length, 0, 0.0f, 0, 0};
     ft_stats st{};
     int rc = ft_render_hits(ctx, s, &camera, &p, nullptr, out.data(), material ? material->data() : nullptr, &st);
+    ft_scene_destroy(s);
+    check(rc);
+    if (stats) *stats = st;
+    return out;
+}
+// EXTENSION: renderHits of one scene from every camera of `cameras` in one launch: view k's record of pixel (x, y) at k * X * Y + x * Y + y,
+// bit for bit renderHits' record for cameras[k]; `material` likewise; stats of the whole batch
+inline std::vector<ft_object_trace_result> renderViewsHits(float epsilon, float length, ImageSize size, const std::vector<ft_camera>& cameras,
+                                                           const SdfScene& scene, std::vector<int32_t>* material = nullptr, ft_stats* stats = nullptr) {
+    ft_ctx* ctx = scene.Object.ctx;
+    std::vector<ft_handle> lights; for (auto& l : scene.Lights) lights.push_back(l.Node);
+    ft_scene* s = nullptr;
+    check(ft_scene_create(ctx, scene.Object.Node, &scene.BackgroundColor.v.x, lights.data(), (int)lights.size(), &s));
+    std::vector<ft_object_trace_result> out(cameras.size() * (size_t)size.X * size.Y);
+    if (material) material->assign(out.size(), -1);
+    ft_render_params p{size.X, size.Y, 0, size.X, size.X, 1, 0, 1, epsilon, length, 0, 0.0f, 0, 0};
+    ft_stats st{};
+    int rc = ft_render_views_hits(ctx, s, cameras.data(), (int32_t)cameras.size(), &p, nullptr, out.data(), material ? material->data() : nullptr, &st);
     ft_scene_destroy(s);
     check(rc);
     if (stats) *stats = st;

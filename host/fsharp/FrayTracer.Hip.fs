@@ -97,6 +97,9 @@ module Native =
     // one scene from n cameras in one launch: out = n x X x Y FColor, view after view
     [<DllImport(Lib)>] extern int ft_render_views(nativeint ctx, nativeint scene, FtCamera[] cameras, int n, FtRenderParams& p, nativeint out, FtStats& stats)
     [<DllImport(Lib)>] extern int ft_render_views_device(nativeint ctx, nativeint scene, FtCamera[] cameras, int n, FtRenderParams& p, nativeint dOut)
+    // the hit buffers of n cameras in one launch: n x X x Y records / material handles, view after view
+    [<DllImport(Lib)>] extern int ft_render_views_hits(nativeint ctx, nativeint scene, FtCamera[] cameras, int n, FtRenderParams& p, nativeint outRgb, [<Out>] FtObjectTraceResult[] outHits, [<Out>] int[] outMaterial, FtStats& stats)
+    [<DllImport(Lib)>] extern int ft_render_views_hits_device(nativeint ctx, nativeint scene, FtCamera[] cameras, int n, FtRenderParams& p, nativeint dOutRgb, nativeint dHits, nativeint dMaterial)
     // a destination that is reused over many frames can be page-locked once (otherwise ft_render pins it for the duration of each call)
     [<DllImport(Lib)>] extern int ft_host_register(nativeint ctx, nativeint p, uint64 bytes)
     [<DllImport(Lib)>] extern int ft_host_unregister(nativeint ctx, nativeint p)
@@ -345,6 +348,33 @@ module Image =
                 let r = out.[x * imageSize.Y + y]
                 if r.Hit = 0 then ValueNone
                 else ValueSome { SdfObjectTraceResult.Ray = r.Ray; Normal = r.Normal; Color = FColor r.Color })
+        finally
+            Native.ft_scene_destroy handle
+
+    /// EXTENSION: `cameras |> Array.map (fun camera -> renderHits epsilon length imageSize camera scene)` in one launch (ft_render_views_hits):
+    /// the per-view hit buffers of multi-view datasets.  Element k is bit for bit renderHits' result for cameras.[k].
+    let renderViewsHits (epsilon : float32) (length : float32) (imageSize : ImageSize) (cameras : Camera[]) (scene : GpuScene) : SdfObjectTraceResult voption[,][] =
+        let ctx = Native.ctx.Value
+        let lights = scene.Lights |> List.map (fun l -> l.Node) |> List.toArray
+        let mutable bg = let (FColor v) = scene.BackgroundColor in v
+        let mutable handle = 0n
+        Native.check (Native.ft_scene_create (ctx, scene.Object.Node, &bg, lights, lights.Length, &handle)) |> ignore
+        try
+            let n = imageSize.X * imageSize.Y
+            let out : FtObjectTraceResult[] = Array.zeroCreate (cameras.Length * n)               // the library's layout: view after view
+            let cams = cameras |> Array.map FtCamera.ofCamera
+            let mutable p =
+                { Width = imageSize.X; Height = imageSize.Y; X0 = 0; NColumns = imageSize.X
+                  StripeWidth = imageSize.X; StripeRanks = 1; StripeRank = 0; Spp = 1
+                  Epsilon = epsilon; Length = length; AoSamples = 0; AoRadius = 0f
+                  MaxBounces = 0; Spectral = 0 }
+            let mutable stats = Unchecked.defaultof<FtStats>
+            Native.check (Native.ft_render_views_hits (ctx, handle, cams, cams.Length, &p, 0n, out, null, &stats)) |> ignore
+            Array.init cameras.Length (fun k ->
+                Array2D.init imageSize.X imageSize.Y (fun x y ->
+                    let r = out.[k * n + x * imageSize.Y + y]
+                    if r.Hit = 0 then ValueNone
+                    else ValueSome { SdfObjectTraceResult.Ray = r.Ray; Normal = r.Normal; Color = FColor r.Color }))
         finally
             Native.ft_scene_destroy handle
 

@@ -231,6 +231,18 @@ int ft_render_views(ft_ctx*, const ft_scene*, const ft_camera* cameras, int32_t 
 /* Same into device memory, asynchronous like ft_render_device (pair with ft_collect_stats).  n_views = 1 is exactly ft_render_device. */
 int ft_render_views_device(ft_ctx*, const ft_scene*, const ft_camera* cameras, int32_t n_views,
                            const ft_render_params*, void* d_out);
+/* EXTENSION: ft_render_hits for a batch of views, in the job queues of ft_render_views.  Every buffer is view-major: n_views x n_columns x
+ * height x 3 float32 for out_rgb, one ft_object_trace_result per pixel for out_hits, one int32 per pixel for out_material; block k of each is
+ * bit for bit what ft_render_hits(ctx, scene, &cameras[k], params, ...) writes.  Any of the three may be NULL, not all: with out_rgb alone
+ * the call is ft_render_views; without out_rgb one ray is traced per pixel per view and the EXTENSION fields of the params do not apply
+ * (the 2^32 job limit then counts one sample a view).  stats: the sums of the single-view calls' counts.  n_views = 1 is exactly
+ * ft_render_hits.  The host form stages one launch group (up to 64 views) at a time in device scratch and copies it out before the next. */
+int ft_render_views_hits(ft_ctx*, const ft_scene*, const ft_camera* cameras, int32_t n_views, const ft_render_params*,
+                         float* out_rgb, ft_object_trace_result* out_hits, int32_t* out_material, ft_stats* stats);
+/* Same into device memory, asynchronous like ft_render_device (pair with ft_collect_stats); d_hits 16-byte aligned, d_out_rgb and
+ * d_material 4-byte aligned.  n_views = 1 is exactly ft_render_hits_device. */
+int ft_render_views_hits_device(ft_ctx*, const ft_scene*, const ft_camera* cameras, int32_t n_views, const ft_render_params*,
+                                void* d_out_rgb, void* d_hits, void* d_material);
 
 /* ---- around the hot path: tone map + 8-bit output -------------------------------- */
 /* Image.toColors gamma rng image (Image.fs:37-50): max = Max(0.01, max over all channels); per channel
