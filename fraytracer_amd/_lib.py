@@ -140,6 +140,11 @@ SYMBOLS = {
     "ft_tone_map_host": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.POINTER(TonemapParams), _P, C.POINTER(C.c_float)]),
     "ft_render_colors": (C.c_int, [_P, _P, C.POINTER(CameraS), C.POINTER(RenderParams), C.POINTER(TonemapParams), _P, C.POINTER(C.c_float), C.POINTER(Stats)]),
     "ft_trace_rays": (C.c_int, [_P, _P, _P, C.c_int64, _P, C.POINTER(Stats)]),
+    "ft_trace_rays_device": (C.c_int, [_P, _P, _P, C.c_int64, _P]),
+    "ft_form_try_trace_device": (C.c_int, [_P, _P, _P, C.c_int64, _P]),
+    "ft_object_try_trace_device": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P]),
+    "ft_trace_rays_hits": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, _P, C.POINTER(Stats)]),
+    "ft_trace_rays_hits_device": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, _P]),
     "ft_eval_distance": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P]),
     "ft_scene_clone": (C.c_int, [_P, _P, C.POINTER(_P)]),
     "ft_render_multi": (C.c_int, [C.POINTER(_P), C.POINTER(_P), C.c_int32, C.POINTER(CameraS), C.POINTER(RenderParams), _P, C.POINTER(Stats)]),

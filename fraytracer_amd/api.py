@@ -18,6 +18,7 @@ They are realised through libfraytracer_hip's constructor twins the first time t
 on a device.  The same descriptions can be realised on any object offering the small backend
 protocol below (tests realise them on the CPU oracle to compare results).
 """
+import contextlib
 import ctypes as C
 import threading
 
@@ -374,6 +375,28 @@ class Device:
 
     def set_stream(self, hip_stream):
         check(lib.ft_ctx_set_stream(self._ctx, C.c_void_p(hip_stream)))
+        self._adopted = hip_stream or None
+
+    @contextlib.contextmanager
+    def on_current_stream(self, tensor):
+        """Order the context's launches inside the block with the caller's torch work, without a synchronise: they go to torch's current stream
+        of the tensor's device (ft_ctx_set_stream), after the kernels that produced the tensor and before whatever the caller queues next.
+        torch's default stream is the null stream, which a context cannot adopt (NULL gives it a stream of its own); the launches then go to
+        a side stream of this Device that waits for the default stream before the block and that the default stream waits for after it."""
+        import torch              # a device tensor was passed in: torch is loaded
+        cur = torch.cuda.current_stream(tensor.device)
+        side = None
+        if int(cur.cuda_stream) == 0:
+            side = self._side_stream = getattr(self, "_side_stream", None) or torch.cuda.Stream(tensor.device)
+            side.wait_stream(cur)
+        handle = int((side or cur).cuda_stream)
+        if getattr(self, "_adopted", None) != handle:
+            self.set_stream(handle)
+        try:
+            yield
+        finally:
+            if side is not None:
+                cur.wait_stream(side)
 
     OPTIONS = {"refill_min": _lib.FT_OPT_REFILL_MIN, "max_blocks_per_cu": _lib.FT_OPT_MAX_BLOCKS_PER_CU,
                "host_chunks": _lib.FT_OPT_HOST_CHUNKS, "host_pin": _lib.FT_OPT_HOST_PIN, "math": _lib.FT_OPT_MATH,
@@ -462,12 +485,40 @@ def _materials_by_handle(obj, memo):
     return out
 
 
+def _dptr(p):
+    return None if not p else C.c_void_p(p)
+
+
+def is_device_tensor(x):
+    """Duck-typed device tensor (a torch CUDA / HIP tensor, without importing torch): anything with data_ptr(), is_cuda, shape, dtype and
+    is_contiguous() whose is_cuda is true.  The ray-buffer calls trace such a tensor where it lies."""
+    return all(hasattr(x, k) for k in ("data_ptr", "is_cuda", "shape", "dtype", "is_contiguous")) and bool(x.is_cuda)
+
+
+def check_device_rays(t):
+    """n of a device ray buffer: float32, shape [n, 8], contiguous — anything else is a ValueError (no silent copy on the device)"""
+    if str(t.dtype).rsplit(".", 1)[-1] != "float32":
+        raise ValueError(f"device ray buffer: dtype must be float32, not {t.dtype}")
+    shape = tuple(t.shape)
+    if len(shape) != 2 or shape[1] != 8:
+        raise ValueError(f"device ray buffer: shape must be [n, 8] (Origin, Direction, Length, Epsilon), not {list(shape)}")
+    if not t.is_contiguous():
+        raise ValueError("device ray buffer: the tensor must be contiguous (call .contiguous() first)")
+    return int(shape[0])
+
+
+def _torch_int32(t):
+    import torch                  # a device tensor was passed in: torch is loaded
+    return torch.int32
+
+
 class PixelHits:
     """EXTENSION (ft_render_hits): SdfObject.tryTrace scene.Object of every pixel's camera ray (sample 0), laid out like the
     frame.  `records` is float32 [n_columns, Y, 16] in the layout of ft_object_trace_result — Ray pulled back by epsilon
     (Origin = Position, Direction, Length, Epsilon), Normal, Color, hit flag (int32 bits), 0; a miss (ValueNone) is all zero.
     `material` is int32 [n_columns, Y]: the handle of the material the hit picked, -1 on a miss (None if not asked for).
-    ft_render_views_hits: every array has a leading view axis, [K, n_columns, Y, ...]; the properties keep it."""
+    ft_render_views_hits: every array has a leading view axis, [K, n_columns, Y, ...]; the properties keep it.
+    ft_trace_rays_hits: one record per ray of a ray buffer, [n, 16] and [n]; device tensors where the rays were one."""
 
     def __init__(self, records, material=None, materials=None):
         self.records = records
@@ -495,7 +546,9 @@ class PixelHits:
     def color(self): return self.records[..., 11:14]
 
     @property
-    def hit(self): return self.records[..., 14].view(np.int32) != 0
+    def hit(self):
+        flag = self.records[..., 14]
+        return flag.view(np.int32 if isinstance(flag, np.ndarray) else _torch_int32(flag)) != 0
 
     def descriptor(self, handle):
         """the SdfMaterial description (SdfMaterial.createSolid / createGlass value) a material handle was realised from; None for -1"""
@@ -693,8 +746,21 @@ class DeviceScene:
                                    out.ctypes.data_as(C.c_void_p), C.byref(mx), C.byref(st)))
         return out, float(mx.value), st.as_dict()
 
+    # ---- ray buffers: host arrays (numpy) or device tensors ------------------------------------------------------------
+    def _device_rays(self, rays):
+        """n of a ray buffer given as a device tensor (checked: float32 [n, 8], contiguous); None for host input"""
+        return check_device_rays(rays) if is_device_tensor(rays) else None
+
     def trace_rays(self, rays):
-        """SdfScene.trace over n rays given as float32 [n, 8] (Origin, Direction, Length, Epsilon)."""
+        """SdfScene.trace over n rays given as float32 [n, 8] (Origin, Direction, Length, Epsilon) -> (float32 [n, 3], stats).
+        A device tensor (see is_device_tensor) is traced in place by ft_trace_rays_device on the caller's current stream and the colours come
+        back as a tensor of the same device; stats is then None: fetch them with collect_stats() when needed."""
+        n = self._device_rays(rays)
+        if n is not None:
+            out = rays.new_empty((n, 3))
+            with self.device.on_current_stream(rays):
+                self.trace_rays_device(rays.data_ptr(), n, out.data_ptr())
+            return out, None
         rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)
         out = np.empty((rays.shape[0], 3), np.float32)
         st = _lib.Stats()
@@ -703,6 +769,12 @@ class DeviceScene:
         return out, st.as_dict()
 
     def _try_trace(self, fn, rays, width):
+        n = self._device_rays(rays)
+        if n is not None:
+            out = rays.new_empty((n, width))
+            with self.device.on_current_stream(rays):
+                (self.form_try_trace_device if width == 10 else self.object_try_trace_device)(rays.data_ptr(), n, out.data_ptr())
+            return out, None
         rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)
         out = np.empty((rays.shape[0], width), np.float32)
         st = _lib.Stats()
@@ -711,13 +783,58 @@ class DeviceScene:
 
     def form_try_trace(self, rays):
         """SdfForm.tryTrace scene.Object.Form over rays [n, 8] (SdfForm.fs:93-104) -> float32 [n, 10]:
-        Ray at the hit (8), Distance, hit flag (int32 bits; 0 = ValueNone, row is zeros)"""
+        Ray at the hit (8), Distance, hit flag (int32 bits; 0 = ValueNone, row is zeros).  Device tensors as in trace_rays."""
         return self._try_trace(lib.ft_form_try_trace, rays, 10)
 
     def object_try_trace(self, rays):
         """SdfObject.tryTrace scene.Object over rays [n, 8] (SdfObject.fs:66-78) -> float32 [n, 16]:
-        Ray pulled back by epsilon (8), Normal (3), Color (3), hit flag (int32 bits), 0"""
+        Ray pulled back by epsilon (8), Normal (3), Color (3), hit flag (int32 bits), 0.  Device tensors as in trace_rays."""
         return self._try_trace(lib.ft_object_try_trace, rays, 16)
+
+    def trace_rays_hits(self, rays, shade=True, records=True, material=True):
+        """EXTENSION ft_trace_rays_hits: SdfScene.trace and SdfObject.tryTrace of every ray [n, 8] in one launch -> (PixelHits with records
+        float32 [n, 16] and material int32 [n], colours float32 [n, 3] or None, stats).  Ray i: colours = trace_rays, records =
+        object_try_trace, material = the handle render_hits reports for a pixel with that camera ray.  shade=False: hits only, no lighting
+        and no shadow rays.  Device tensors as in trace_rays: results are tensors of the rays' device (material int32), stats is None."""
+        if not (shade or records or material):
+            raise ValueError("trace_rays_hits: no output asked for")
+        n = self._device_rays(rays)
+        if n is not None:
+            rgb = rays.new_empty((n, 3)) if shade else None
+            rec = rays.new_empty((n, 16)) if records else None
+            mat = rays.new_empty((n,), dtype=_torch_int32(rays)) if material else None
+            ptr = lambda t: None if t is None else t.data_ptr()
+            with self.device.on_current_stream(rays):
+                self.trace_rays_hits_device(rays.data_ptr(), n, ptr(rgb), ptr(rec), ptr(mat))
+            return PixelHits(rec, mat, self.materials), rgb, None
+        rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)
+        n = rays.shape[0]
+        rgb = np.empty((n, 3), np.float32) if shade else None
+        rec = np.empty((n, 16), np.float32) if records else None
+        mat = np.empty((n,), np.int32) if material else None
+        ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        st = _lib.Stats()
+        check(lib.ft_trace_rays_hits(self.device._ctx, self._scene, rays.ctypes.data_as(C.c_void_p), n, ptr(rgb), ptr(rec), ptr(mat), C.byref(st)))
+        return PixelHits(rec, mat, self.materials), rgb, st.as_dict()
+
+    # raw device pointers (int; None = not asked): rays n x 32 B and object records 16-byte aligned, no scratch, no copy, asynchronous on the
+    # context's stream; pair with collect_stats()
+    def trace_rays_device(self, d_rays_ptr, n, d_out_ptr):
+        """asynchronous ft_trace_rays_device: n x 3 float32 colours at d_out_ptr"""
+        check(lib.ft_trace_rays_device(self.device._ctx, self._scene, _dptr(d_rays_ptr), n, _dptr(d_out_ptr)))
+
+    def form_try_trace_device(self, d_rays_ptr, n, d_out_ptr):
+        """asynchronous ft_form_try_trace_device: n x 10 dwords at d_out_ptr"""
+        check(lib.ft_form_try_trace_device(self.device._ctx, self._scene, _dptr(d_rays_ptr), n, _dptr(d_out_ptr)))
+
+    def object_try_trace_device(self, d_rays_ptr, n, d_out_ptr, d_material_ptr=None):
+        """asynchronous ft_object_try_trace_device: n x 16 dwords at d_out_ptr and, if asked, n int32 material handles (-1: miss)"""
+        check(lib.ft_object_try_trace_device(self.device._ctx, self._scene, _dptr(d_rays_ptr), n, _dptr(d_out_ptr), _dptr(d_material_ptr)))
+
+    def trace_rays_hits_device(self, d_rays_ptr, n, d_out_ptr=None, d_hits_ptr=None, d_material_ptr=None):
+        """asynchronous ft_trace_rays_hits_device: colours, records and material handles of n rays in one launch (any two may be None)"""
+        check(lib.ft_trace_rays_hits_device(self.device._ctx, self._scene, _dptr(d_rays_ptr), n, _dptr(d_out_ptr), _dptr(d_hits_ptr),
+                                            _dptr(d_material_ptr)))
 
     def eval_distance(self, points):
         pts = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
@@ -790,6 +907,8 @@ class SceneTrace:
         return dev.scene(self.scene)
 
     def __call__(self, ray):
+        if is_device_tensor(ray):                                  # a ray buffer [n, 8] in device memory -> colours [n, 3] there
+            return self.resolve().trace_rays(ray)[0]
         out, _ = self.resolve().trace_rays(np.asarray(ray, np.float32).reshape(1, 8))
         return FColor(tuple(float(c) for c in out[0]))
 

@@ -1065,37 +1065,91 @@ int ft_render_colors(ft_ctx* c, const ft_scene* s, const ft_camera* cam, const f
     return ft_collect_stats(c, st);
 }
 
-// mode 1: SdfScene.trace (3 floats per ray); 2: SdfForm.tryTrace (10 dwords); 3: SdfObject.tryTrace (16 dwords)
-static int traceRayBuffer(ft_ctx* c, const ft_scene* s, const ft_ray* rays, int64_t n, void* out, uint32_t mode, ft_stats* st) {
+// ---- ray buffers ------------------------------------------------------------------------------------
+// mode 1: SdfScene.trace (3 floats per ray); 2: SdfForm.tryTrace (10 dwords); 3: SdfObject.tryTrace (16 dwords).  Everything is device memory: the
+// kernel reads d_rays and writes the caller's buffers on the context's stream, with no scratch, no copy and no synchronisation.
+//   mode 1: out (may be NULL: hits only) and, EXTENSION builds, hits / material: the mode-3 record and the material handle of every ray (ft_trace_rays_hits)
+//   mode 2: out;   mode 3: out and, optionally, material
+struct RayOuts { void* out; void* hits; void* material; };
+
+static int launchRayBuffer(ft_ctx* c, const ft_scene* s, const void* d_rays, int64_t n, uint32_t mode, const RayOuts& o) {
     int rc = requireDevice(c); if (rc) return rc;
-    if (!s || s->ctx != c || !rays || !out || n < 0) return setErr(FT_ERR_INVALID, "bad argument");
+    if (!s || s->ctx != c || !d_rays || n < 0) return setErr(FT_ERR_INVALID, "bad argument (scene must belong to this context)");
+    if (mode == 1 ? (!o.out && !o.hits && !o.material) : !o.out) return setErr(FT_ERR_INVALID, "ray buffer: no output asked for");
+    const uintptr_t rec = reinterpret_cast<uintptr_t>(mode == 3 ? o.out : o.hits), word = reinterpret_cast<uintptr_t>(mode == 3 ? nullptr : o.out);
+    if ((reinterpret_cast<uintptr_t>(d_rays) & 15u) || (rec & 15u) || (word & 3u) || (reinterpret_cast<uintptr_t>(o.material) & 3u))
+        return setErr(FT_ERR_INVALID, "ray buffer: the rays and the ft_object_trace_result records must be 16-byte aligned, every other buffer 4-byte aligned");
+    if (d_rays == o.out || d_rays == o.hits || d_rays == o.material) return setErr(FT_ERR_INVALID, "ray buffer: input and output must not overlap");
+    if (n == 0) return FT_OK;
+    if (n >= 0xFFFF0000ll) return setErr(FT_ERR_UNSUPPORTED, "more than 2^32 rays in one call");
+    // The kernel knows two kinds of ray buffer: SdfScene.trace (mode 1), which in the EXTENSION builds can also store every ray's SdfObject.tryTrace record
+    // and material handle (hits = 1) or only those, without shading (hits = 2: SdfObject.tryTrace itself); and SdfForm.tryTrace (mode 2, EXTENSION builds)
+    FtRenderArgs a{};
+    a.mode = mode == 2 ? 2u : 1u; a.rays = static_cast<const ft_ray*>(d_rays);
+    a.nJobs = (uint32_t)n; a.stripeW = 1; a.stripeRanks = 1; a.tilesY = 1; a.H = 1; a.W = 1; a.nCols = 1; a.maxSize = 1.0f;
+    a.spp = 1; a.sppN = 1; a.jobsPerPlane = a.nJobs; a.planePixels = a.nJobs;
+    if (mode == 3) { a.ext = 1u; a.hits = 2u; a.hitsOut = static_cast<float*>(o.out); }
+    else {
+        a.out = static_cast<float*>(o.out);
+        a.ext = (mode == 2 || o.hits || o.material) ? 1u : 0u;         // plain SdfScene.trace stays on the reference kernels (carved ones included)
+        if (o.hits || o.material) { a.hits = o.out ? 1u : 2u; a.hitsOut = static_cast<float*>(o.hits); }
+    }
+    a.matOut = static_cast<int32_t*>(o.material); a.matHandles = s->dMatHandles;
+    return launchTrace(c, s, a);
+}
+
+int ft_trace_rays_device(ft_ctx* c, const ft_scene* s, const void* d_rays, int64_t n, void* d_out_rgb) {
+    return launchRayBuffer(c, s, d_rays, n, 1, RayOuts{d_out_rgb, nullptr, nullptr});
+}
+int ft_form_try_trace_device(ft_ctx* c, const ft_scene* s, const void* d_rays, int64_t n, void* d_out) {
+    return launchRayBuffer(c, s, d_rays, n, 2, RayOuts{d_out, nullptr, nullptr});
+}
+int ft_object_try_trace_device(ft_ctx* c, const ft_scene* s, const void* d_rays, int64_t n, void* d_out, void* d_material) {
+    return launchRayBuffer(c, s, d_rays, n, 3, RayOuts{d_out, nullptr, d_material});
+}
+int ft_trace_rays_hits_device(ft_ctx* c, const ft_scene* s, const void* d_rays, int64_t n, void* d_out_rgb, void* d_hits, void* d_material) {
+    return launchRayBuffer(c, s, d_rays, n, 1, RayOuts{d_out_rgb, d_hits, d_material});
+}
+
+// The host forms: rays up into the context's scratch ([rays | out | records | material plane], each part 256-byte aligned), the device form,
+// every output asked for down again; nothing of the call is left in flight when it returns.
+static int traceRayBuffer(ft_ctx* c, const ft_scene* s, const ft_ray* rays, int64_t n, uint32_t mode, void* out, void* hits, void* material, ft_stats* st) {
+    static_assert(sizeof(ft_ray) == 32 && sizeof(ft_form_trace_result) == 40 && sizeof(ft_object_trace_result) == 64, "layout");
+    int rc = requireDevice(c); if (rc) return rc;
+    if (!s || s->ctx != c || !rays || (!out && !hits && !material) || n < 0) return setErr(FT_ERR_INVALID, "bad argument");
     if (n == 0) { if (st) memset(st, 0, sizeof(*st)); return FT_OK; }
     if (n >= 0xFFFF0000ll) return setErr(FT_ERR_UNSUPPORTED, "more than 2^32 rays in one call");
     const size_t perRay = mode == 1 ? 3 : mode == 2 ? 10 : 16;
-    const size_t rayBytes = align256((size_t)n * sizeof(ft_ray)), outBytes = (size_t)n * perRay * sizeof(float);
-    if ((rc = ensureScratch(c, rayBytes + outBytes))) return rc;
+    const size_t rayBytes = (size_t)n * sizeof(ft_ray), outBytes = out ? (size_t)n * perRay * sizeof(float) : 0;
+    const size_t hitBytes = hits ? (size_t)n * 64 : 0, matBytes = material ? (size_t)n * 4 : 0;
+    const size_t oOut = align256(rayBytes), oHits = oOut + align256(outBytes), oMat = oHits + align256(hitBytes);
+    if ((rc = ensureScratch(c, oMat + matBytes))) return rc;
     unsigned char* base = static_cast<unsigned char*>(c->scratch);
-    HIP_TRY(hipMemcpyAsync(base, rays, (size_t)n * sizeof(ft_ray), hipMemcpyHostToDevice, c->stream));
-    FtRenderArgs a{};
-    a.mode = mode; a.rays = reinterpret_cast<const ft_ray*>(base); a.out = reinterpret_cast<float*>(base + rayBytes);
-    a.nJobs = (uint32_t)n; a.stripeW = 1; a.stripeRanks = 1; a.tilesY = 1; a.H = 1; a.W = 1; a.nCols = 1; a.maxSize = 1.0f;
-    a.spp = 1; a.sppN = 1; a.jobsPerPlane = a.nJobs; a.planePixels = a.nJobs;
-    a.ext = mode >= 2 ? 1u : 0u;                           // the tryTrace outputs exist in the EXTENSION builds of the kernel only
-    if ((rc = launchTrace(c, s, a))) return rc;
-    HIP_TRY(hipMemcpyAsync(out, base + rayBytes, outBytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(base, rays, rayBytes, hipMemcpyHostToDevice, c->stream));
+    rc = launchRayBuffer(c, s, base, n, mode, RayOuts{out ? base + oOut : nullptr, hits ? base + oHits : nullptr, material ? base + oMat : nullptr});
+    hipError_t err = hipSuccess;
+    if (!rc && out) err = hipMemcpyAsync(out, base + oOut, outBytes, hipMemcpyDeviceToHost, c->stream);
+    if (!rc && err == hipSuccess && hits) err = hipMemcpyAsync(hits, base + oHits, hitBytes, hipMemcpyDeviceToHost, c->stream);
+    if (!rc && err == hipSuccess && material) err = hipMemcpyAsync(material, base + oMat, matBytes, hipMemcpyDeviceToHost, c->stream);
+    const hipError_t se = hipStreamSynchronize(c->stream);     // the scratch is reused: nothing of this call stays in flight, whatever happened
+    if (rc) return rc;
+    if (err != hipSuccess) return hipFail(err, "ray buffer host output");
+    if (se != hipSuccess) return hipFail(se, "ray buffer");
     return ft_collect_stats(c, st);
 }
 
 int ft_trace_rays(ft_ctx* c, const ft_scene* s, const ft_ray* rays, int64_t n, float* out, ft_stats* st) {
-    return traceRayBuffer(c, s, rays, n, out, 1, st);
+    return traceRayBuffer(c, s, rays, n, 1, out, nullptr, nullptr, st);
 }
 int ft_form_try_trace(ft_ctx* c, const ft_scene* s, const ft_ray* rays, int64_t n, ft_form_trace_result* out, ft_stats* st) {
-    static_assert(sizeof(ft_form_trace_result) == 40, "layout");
-    return traceRayBuffer(c, s, rays, n, out, 2, st);
+    return traceRayBuffer(c, s, rays, n, 2, out, nullptr, nullptr, st);
 }
 int ft_object_try_trace(ft_ctx* c, const ft_scene* s, const ft_ray* rays, int64_t n, ft_object_trace_result* out, ft_stats* st) {
-    static_assert(sizeof(ft_object_trace_result) == 64, "layout");
-    return traceRayBuffer(c, s, rays, n, out, 3, st);
+    return traceRayBuffer(c, s, rays, n, 3, out, nullptr, nullptr, st);
+}
+int ft_trace_rays_hits(ft_ctx* c, const ft_scene* s, const ft_ray* rays, int64_t n, float* out_rgb, ft_object_trace_result* out_hits,
+                       int32_t* out_material, ft_stats* st) {
+    return traceRayBuffer(c, s, rays, n, 1, out_rgb, out_hits, out_material, st);
 }
 
 int ft_eval_distance(ft_ctx* c, const ft_scene* s, const ft_vec3* pts, int64_t n, float* outD, int32_t* outM) {

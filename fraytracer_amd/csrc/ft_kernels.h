@@ -46,7 +46,7 @@ struct FtRenderArgs {
     FtSceneDev S;
     float cam[12];            // Position, Forward, UpScaled, RightScaled (Camera.fs:16-22)
     int32_t W, H, x0, nCols;
-    uint32_t stripeW, stripeRanks, stripeRank, mode;    // mode 0: Image.render pixels, 1: explicit ray buffer
+    uint32_t stripeW, stripeRanks, stripeRank, mode;    // mode 0: Image.render pixels, 1: explicit ray buffer (SdfScene.trace, hits below), 2: ray buffer, SdfForm.tryTrace
     float maxSize, eps, length, pad0;
     const ft_ray* rays;
     float* out;
@@ -71,7 +71,8 @@ struct FtRenderArgs {
     float spec[16][4];        // per bin: RGB weight, Cauchy term (ft_spectral_table)
     uint32_t reuse;           // 1: a secondary ray's first evaluation — at the hit position — is the value the normal's centre probe computed there (FT_OPT_REUSE; kernels.hip FT_SH_D0)
     FtCarve carve;            // FtSceneDev.fastPath == 3: the union's tail and its terminated candidate lists (ft_device.h "Carved union")
-    // EXTENSION ft_render_hits (EXTENSION builds only; appended so that no field above moves): per pixel, SdfObject.tryTrace of its sample-0 ray
+    // EXTENSION ft_render_hits (EXTENSION builds only; appended so that no field above moves): per pixel, SdfObject.tryTrace of its sample-0 ray;
+    // mode 1 (ft_trace_rays_hits, ft_object_try_trace): per ray of the buffer, at the ray's index
     float* hitsOut;           // 16 dwords per pixel (ft_object_trace_result) at cl * H + y (*_views builds: view * planePixels + cl * H + y); NULL: not asked
     int32_t* matOut;          // material handle per pixel (-1 on a miss); NULL: not asked
     const int32_t* matHandles;   // dense material index -> context handle (ft_material_*): the inverse of the flattener's remap

@@ -1262,20 +1262,20 @@ __device__ __forceinline__ uint32_t ft_glass_hash(uint32_t seed, uint32_t bounce
     return h;
 }
 
-// ft_form_try_trace / ft_object_try_trace (modes 2 / 3, EXTENSION builds of the kernel only): results are
-// 10 / 16 dwords per ray — ft_form_trace_result / ft_object_trace_result
+// ft_form_try_trace (mode 2, EXTENSION builds of the kernel only): 10 dwords per ray — ft_form_trace_result.  ft_object_try_trace is no mode of
+// its own: its ft_object_trace_result is the hit record of a ray buffer traced "hits only" (mode 1, a.hits = 2: ends_hit_segment below)
 __device__ __forceinline__ void write_try_trace_miss(const FtRenderArgs& a, const LaneState& s) {
-    const uint32_t n = a.mode == 2u ? 10u : 16u;
-    float* o = a.out + (size_t)n * s.outIdx;
-    for (uint32_t i = 0; i < n; ++i) o[i] = 0.0f;
+    float* o = a.out + 10ull * s.outIdx;
+    for (uint32_t i = 0; i < 10u; ++i) o[i] = 0.0f;
 }
 __device__ __forceinline__ void write_ray(float* o, f3 origin, f3 dir, float len, float eps) {
     o[0] = origin.x; o[1] = origin.y; o[2] = origin.z; o[3] = dir.x; o[4] = dir.y; o[5] = dir.z; o[6] = len; o[7] = eps;
 }
 
-// ft_render_hits (EXTENSION builds, mode 0; a.hits != 0 only there): does the segment this lane ends now carry the pixel's hit record?  Only the
-// first segment (no glass interaction yet) of sample 0, whose ray is the reference's pixel ray (spp offset 0).  Views: sample 0 of every view, i.e.
-// the job's plane (view * spp + sample, start_job) a multiple of spp
+// ft_render_hits (EXTENSION builds, mode 0) and ft_trace_rays_hits (mode 1); a.hits != 0 only there: does the segment this lane ends now carry the
+// pixel's / ray's hit record?  Only the first segment (no glass interaction yet) of sample 0, whose ray is the reference's pixel ray (spp offset 0).
+// Views: sample 0 of every view, i.e. the job's plane (view * spp + sample, start_job) a multiple of spp.  A ray buffer is one plane of nJobs rays
+// (jobsPerPlane = nJobs, spp = 1, no bounces: capi.cpp launchRayBuffer), so every ray's only segment carries its record, stored at s.outIdx = s.job
 template <bool VIEWS = false>
 __device__ __forceinline__ bool ends_hit_segment(const FtRenderArgs& a, const LaneState& s) {
     if (VIEWS) return a.hits != 0u && (s.job / a.jobsPerPlane) % a.spp == 0u && s.bounce() == 0u;
@@ -1441,7 +1441,7 @@ __device__ __forceinline__ void settle(const FtRenderArgs& a, LaneState& s) {
             // SdfForm.fs:94 -> SdfScene.fs:10; or every further step is known to miss (EXTENSION glass: a path inside a body marches on
             // -Distance, which is below epsilon everywhere outside the support sphere — the shortcut is for paths outside bodies only)
             if (s.len <= 0.0f || ((!EXT || !s.inside()) && ft_never_enters(a.S, s.o, s.dir, s.eps, s.len))) {
-                if (EXT && a.mode >= 2u) write_try_trace_miss(a, s);   // ValueNone of the tryTrace entries
+                if (EXT && a.mode == 2u) write_try_trace_miss(a, s);   // ValueNone of SdfForm.tryTrace
                 else {
                     // every miss of a primary ray ends here: Length used up, escape, NaN and the step cap (s.len = -1), the camera shortcuts of start_job
                     if (EXT && ends_hit_segment<VIEWS>(a, s)) write_hit_miss(a, hit_index<VIEWS>(a, s));
@@ -1534,7 +1534,7 @@ struct ViewCam { f3 o, fw, up, rt; float d; uint32_t leaf; };
 
 template <bool EXT, bool VIEWS = false>
 __device__ __forceinline__ void start_job(const FtRenderArgs& a, LaneState& s, const bool camKnown, float dCam, uint32_t leafCam, const ViewCam& vc) {
-    if (a.mode >= 1) {                                                 // explicit ray buffer (SdfScene.trace scene ray; 2, 3: tryTrace entries)
+    if (a.mode >= 1) {                                                 // explicit ray buffer (1: SdfScene.trace scene ray, with or instead of its hit record; 2: SdfForm.tryTrace)
         const ft_ray r = a.rays[s.job];
         s.o = mk3(r.origin.x, r.origin.y, r.origin.z);
         s.dir = mk3(r.direction.x, r.direction.y, r.direction.z);
@@ -1851,8 +1851,8 @@ __device__ __forceinline__ void ft_trace_body(const FtRenderArgs& a) {
                 sh_set3(FT_SH_LACC, mk3(a.S.bg[0], a.S.bg[1], a.S.bg[2]));     // SdfScene.fs:12
                 s.lidx = 0;
                 s.phase = PH_LIGHTS;
-                if (EXT && ends_hit_segment<VIEWS>(a, s)) {            // ft_render_hits: the mode-3 record below, before any glass bounce moves the ray
-                    cfp m = as_const(a.S.materials) + 3u * s.leaf;
+                if (EXT && ends_hit_segment<VIEWS>(a, s)) {            // the SdfObject.tryTrace result (SdfObject.fs:72-77), before any glass bounce moves the ray:
+                    cfp m = as_const(a.S.materials) + 3u * s.leaf;     // ft_render_hits per pixel; ft_trace_rays_hits and ft_object_try_trace per ray of a ray buffer
                     const float len = s.len - (-s.eps);                // Ray.move -eps: Length - (-eps)
                     write_hit_record(a, hit_index<VIEWS>(a, s), v4f{hp.x, hp.y, hp.z, s.dir.x}, v4f{s.dir.y, s.dir.z, len, s.eps},
                                      v4f{nrm.x, nrm.y, nrm.z, m[0]}, v4f{m[1], m[2], __int_as_float(1), 0.0f}, as_const(a.matHandles)[s.leaf]);
@@ -1860,14 +1860,6 @@ __device__ __forceinline__ void ft_trace_body(const FtRenderArgs& a) {
                 }
                 if (EXT && a.aoSamples != 0u) { s.xs &= 0xffff0000u; s.phase = PH_AONEXT; }   // EXTENSION: AO counters to 0
                 if (EXT && a.maxBounces != 0u) glass_bounce(a, s);     // EXTENSION
-                if (EXT && a.mode == 3u) {                             // SdfObject.tryTrace result (SdfObject.fs:72-77)
-                    float* o = a.out + 16ull * s.outIdx;
-                    write_ray(o, hp, s.dir, s.len - (-s.eps), s.eps);              // Ray.move -eps: Length - (-eps)
-                    cfp m = as_const(a.S.materials) + 3u * s.leaf;
-                    o[8] = nrm.x; o[9] = nrm.y; o[10] = nrm.z; o[11] = m[0]; o[12] = m[1]; o[13] = m[2];
-                    reinterpret_cast<int32_t*>(o)[14] = 1; o[15] = 0.0f;
-                    s.phase = PH_IDLE;
-                }
                 break;
             }
             default: break;

@@ -13,6 +13,7 @@
 //   Image::renderScene                                  src/FrayTracer/Image.fs:26-35 + SdfScene.fs:7-28
 //   Image::renderViews                                  renderScene over several cameras in one launch (ft_render_views)
 //   Image::renderViewsHits                              renderHits over several cameras in one launch (ft_render_views_hits)
+//   Image::traceRaysHits                                SdfObject.tryTrace (+ SdfScene.trace) over an explicit ray buffer in one launch (ft_trace_rays_hits)
 #pragma once
 #include <stdexcept>
 #include <string>
@@ -181,6 +182,25 @@ inline std::vector<ft_object_trace_result> renderViewsHits(float epsilon, float 
     ft_render_params p{size.X, size.Y, 0, size.X, size.X, 1, 0, 1, epsilon, length, 0, 0.0f, 0, 0};
     ft_stats st{};
     int rc = ft_render_views_hits(ctx, s, cameras.data(), (int32_t)cameras.size(), &p, nullptr, out.data(), material ? material->data() : nullptr, &st);
+    ft_scene_destroy(s);
+    check(rc);
+    if (stats) *stats = st;
+    return out;
+}
+// EXTENSION: SdfObject.tryTrace scene.Object of every ray of an explicit ray buffer (`rays |> Array.map (SdfObject.tryTrace scene.Object)`) and, if
+// `colors` is given, SdfScene.trace scene of the same rays (3 floats per ray) from the same launch (ft_trace_rays_hits); `material` as in renderHits
+inline std::vector<ft_object_trace_result> traceRaysHits(const std::vector<ft_ray>& rays, const SdfScene& scene, std::vector<float>* colors = nullptr,
+                                                         std::vector<int32_t>* material = nullptr, ft_stats* stats = nullptr) {
+    ft_ctx* ctx = scene.Object.ctx;
+    std::vector<ft_handle> lights; for (auto& l : scene.Lights) lights.push_back(l.Node);
+    ft_scene* s = nullptr;
+    check(ft_scene_create(ctx, scene.Object.Node, &scene.BackgroundColor.v.x, lights.data(), (int)lights.size(), &s));
+    std::vector<ft_object_trace_result> out(rays.size());
+    if (colors) colors->assign(rays.size() * 3, 0.0f);
+    if (material) material->assign(rays.size(), -1);
+    ft_stats st{};
+    int rc = ft_trace_rays_hits(ctx, s, rays.data(), (int64_t)rays.size(), colors ? colors->data() : nullptr, out.data(),
+                                material ? material->data() : nullptr, &st);
     ft_scene_destroy(s);
     check(rc);
     if (stats) *stats = st;

@@ -91,6 +91,13 @@ module Native =
     [<DllImport(Lib)>] extern void ft_scene_destroy(nativeint scene)
     [<DllImport(Lib)>] extern int ft_form_try_trace(nativeint ctx, nativeint scene, Ray[] rays, int64 n, [<Out>] FtFormTraceResult[] out, FtStats& stats)
     [<DllImport(Lib)>] extern int ft_object_try_trace(nativeint ctx, nativeint scene, Ray[] rays, int64 n, [<Out>] FtObjectTraceResult[] out, FtStats& stats)
+    // ray buffers in device memory (rays 16-byte aligned, 32 B each): no scratch, no copy, not synchronised; pair with ft_collect_stats
+    [<DllImport(Lib)>] extern int ft_trace_rays_device(nativeint ctx, nativeint scene, nativeint dRays, int64 n, nativeint dOutRgb)
+    [<DllImport(Lib)>] extern int ft_form_try_trace_device(nativeint ctx, nativeint scene, nativeint dRays, int64 n, nativeint dOut)
+    [<DllImport(Lib)>] extern int ft_object_try_trace_device(nativeint ctx, nativeint scene, nativeint dRays, int64 n, nativeint dOut, nativeint dMaterial)
+    // SdfScene.trace and SdfObject.tryTrace of every ray in one launch: colours, records, material handles (any may be null, not all)
+    [<DllImport(Lib)>] extern int ft_trace_rays_hits(nativeint ctx, nativeint scene, Ray[] rays, int64 n, nativeint outRgb, [<Out>] FtObjectTraceResult[] outHits, [<Out>] int[] outMaterial, FtStats& stats)
+    [<DllImport(Lib)>] extern int ft_trace_rays_hits_device(nativeint ctx, nativeint scene, nativeint dRays, int64 n, nativeint dOutRgb, nativeint dHits, nativeint dMaterial)
     [<DllImport(Lib)>] extern int ft_render(nativeint ctx, nativeint scene, FtCamera& camera, FtRenderParams& p, nativeint out, FtStats& stats)
     [<DllImport(Lib)>] extern int ft_render_hits(nativeint ctx, nativeint scene, FtCamera& camera, FtRenderParams& p, nativeint outRgb, [<Out>] FtObjectTraceResult[] outHits, [<Out>] int[] outMaterial, FtStats& stats)
     [<DllImport(Lib)>] extern int ft_render_hits_device(nativeint ctx, nativeint scene, FtCamera& camera, FtRenderParams& p, nativeint dOutRgb, nativeint dHits, nativeint dMaterial)

@@ -280,6 +280,28 @@ int ft_form_try_trace(ft_ctx*, const ft_scene*, const ft_ray* rays, int64_t n, f
 /* SdfObject.tryTrace scene.Object ray (SdfObject.fs:66-78) over a ray buffer: march, normalFromRay, Ray.move -eps,
  * material colour picked at the un-pulled hit origin. */
 int ft_object_try_trace(ft_ctx*, const ft_scene*, const ft_ray* rays, int64_t n, ft_object_trace_result* out, ft_stats* stats);
+/* The three above with rays and results in device memory: the kernel reads d_rays (n x ft_ray, 32 B each) and writes the caller's buffers.
+ * No device scratch, no copy; launched on the context's stream and NOT synchronised (pair with ft_collect_stats), like ft_render_device.
+ * d_rays and the ft_object_trace_result records (d_out of the object form) must be 16-byte aligned — a lane loads its ray as two 16-byte
+ * words —, every other buffer 4-byte aligned; a misaligned buffer, or NULL where none is allowed, is FT_ERR_INVALID and nothing is launched.
+ * n = 0: FT_OK, nothing launched.  n >= 0xFFFF0000: FT_ERR_UNSUPPORTED.  Input and output must not overlap (only identical pointers
+ * are detected: FT_ERR_INVALID).  ft_object_try_trace_device: d_material, if not NULL, receives per ray the handle of the ft_material_* the
+ * hit picked, -1 on a miss (n x int32) — the rule of ft_render_hits; with d_material = NULL it is exactly ft_object_try_trace. */
+int ft_trace_rays_device(ft_ctx*, const ft_scene*, const void* d_rays, int64_t n, void* d_out_rgb);
+int ft_form_try_trace_device(ft_ctx*, const ft_scene*, const void* d_rays, int64_t n, void* d_out);
+int ft_object_try_trace_device(ft_ctx*, const ft_scene*, const void* d_rays, int64_t n, void* d_out, void* d_material);
+/* EXTENSION: SdfScene.trace and SdfObject.tryTrace of every ray of a ray buffer in ONE launch — ft_render_hits for explicit rays.  Ray i:
+ * out_rgb[i] = what ft_trace_rays writes; out_hits[i] = what ft_object_try_trace writes (a miss is all zero); out_material[i] = handle of the
+ * ft_material_* the hit picked, -1 on a miss.  Any of the three may be NULL, not all.  With out_rgb the counters are those of ft_trace_rays
+ * on the same rays (with out_rgb alone the call is ft_trace_rays); without it no lighting and no shadow rays are traced and the counters
+ * are those of ft_object_try_trace.  There are no render params: a glass material shades as its solid tint, as in ft_trace_rays.
+ * The host form stages rays and results in device scratch (32 B + up to 80 B per ray). */
+int ft_trace_rays_hits(ft_ctx*, const ft_scene*, const ft_ray* rays, int64_t n,
+                       float* out_rgb, ft_object_trace_result* out_hits, int32_t* out_material, ft_stats* stats);
+/* Same in device memory, under the contract of the *_device forms above: d_rays and d_hits 16-byte aligned, d_out_rgb and d_material
+ * 4-byte aligned; no scratch, no copy, not synchronised. */
+int ft_trace_rays_hits_device(ft_ctx*, const ft_scene*, const void* d_rays, int64_t n,
+                              void* d_out_rgb, void* d_hits, void* d_material);
 
 /* scene.Object.Form.Distance at n points (+ index of the material the hit would pick, or
  * NULL).  Test/diagnostic entry: lets parity tests compare single SDF evaluations. */
