@@ -486,7 +486,21 @@ def _materials_by_handle(obj, memo):
 
 
 def _dptr(p):
+    """a device address (int; None or 0: not asked for) as the void* of a C call"""
     return None if not p else C.c_void_p(p)
+
+
+def _hptr(a):
+    """a numpy array (None: not asked for) as the void* of a C call"""
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def _host_outputs(lead, image, records, material):
+    """The host arrays a hits form fills, by flags: image float32 lead + (3,), records float32 lead + (16,), material int32 lead; None for
+    what is not asked for -> ((image, records, material), their pointers in the C calls' order)"""
+    arrays = (np.empty(lead + (3,), np.float32) if image else None, np.empty(lead + (16,), np.float32) if records else None,
+              np.empty(lead, np.int32) if material else None)
+    return arrays, tuple(_hptr(a) for a in arrays)
 
 
 def is_device_tensor(x):
@@ -633,45 +647,20 @@ class DeviceScene:
                                  int(spp), float(epsilon), float(length), int(ao_samples), float(ao_radius),
                                  int(max_bounces), int(spectral))
 
-    def render(self, epsilon, length, imageSize, camera, out=None, **tiling):
-        """Image.render (Image.fs:26-35) -> (FColor[X,Y] as float32 [n_columns, Y, 3], stats dict).  `out`: a float32 array
-        of that shape to render into (e.g. one page-locked with Device.host_register)."""
-        p = self._params(imageSize, epsilon, length, **tiling)
+    def _call(self, fn, *args):
+        """fn(ctx, scene, *args, &stats) of a host form -> the stats dict"""
+        st = _lib.Stats()
+        check(fn(self.device._ctx, self._scene, *args, C.byref(st)))
+        return st.as_dict()
+
+    @staticmethod
+    def _image(out, shape, what):
+        """the float32 array a frame form renders into: a new one, or the caller's `out` if it has this shape"""
         if out is None:
-            out = np.empty((p.n_columns, p.height, 3), np.float32)
-        elif out.dtype != np.float32 or out.shape != (p.n_columns, p.height, 3) or not out.flags.c_contiguous:
-            raise ValueError("out must be a C-contiguous float32 array of shape (n_columns, Y, 3)")
-        st = _lib.Stats()
-        check(lib.ft_render(self.device._ctx, self._scene, C.byref(camera._c), C.byref(p), out.ctypes.data_as(C.c_void_p), C.byref(st)))
-        return out, st.as_dict()
-
-    def render_device(self, epsilon, length, imageSize, camera, d_out_ptr, **tiling):
-        """asynchronous render into device memory (pointer as int); pair with collect_stats()."""
-        p = self._params(imageSize, epsilon, length, **tiling)
-        check(lib.ft_render_device(self.device._ctx, self._scene, C.byref(camera._c), C.byref(p), C.c_void_p(d_out_ptr)))
-        return p.n_columns
-
-    def render_hits(self, epsilon, length, imageSize, camera, shade=False, material=True, records=True, **tiling_and_ext):
-        """EXTENSION ft_render_hits: per-pixel SdfObject.tryTrace of the camera rays -> (PixelHits, image or None, stats).
-        shade: also render the frame (bit-identical to render() with the same parameters, same launch); without it one ray
-        per pixel is traced and spp / ao_samples / max_bounces / spectral do not apply.  material / records: which planes to return."""
-        p = self._params(imageSize, epsilon, length, **tiling_and_ext)
-        shape = (p.n_columns, p.height)
-        img = np.empty(shape + (3,), np.float32) if shade else None
-        rec = np.empty(shape + (16,), np.float32) if records else None
-        mat = np.empty(shape, np.int32) if material else None
-        ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
-        st = _lib.Stats()
-        check(lib.ft_render_hits(self.device._ctx, self._scene, C.byref(camera._c), C.byref(p), ptr(img), ptr(rec), ptr(mat), C.byref(st)))
-        return PixelHits(rec, mat, self.materials), img, st.as_dict()
-
-    def render_hits_device(self, epsilon, length, imageSize, camera, d_hits_ptr, d_material_ptr=None, d_out_ptr=None, **tiling_and_ext):
-        """asynchronous ft_render_hits_device into device memory (pointers as int, None = not asked; the records 16-byte
-        aligned, n_columns x Y x 16 float32); pair with collect_stats()."""
-        p = self._params(imageSize, epsilon, length, **tiling_and_ext)
-        ptr = lambda a: None if not a else C.c_void_p(a)
-        check(lib.ft_render_hits_device(self.device._ctx, self._scene, C.byref(camera._c), C.byref(p), ptr(d_out_ptr), ptr(d_hits_ptr), ptr(d_material_ptr)))
-        return p.n_columns
+            return np.empty(shape, np.float32)
+        if out.dtype != np.float32 or out.shape != shape or not out.flags.c_contiguous:
+            raise ValueError(f"out must be a C-contiguous float32 array of shape {what}")
+        return out
 
     @staticmethod
     def _cameras(cameras):
@@ -681,27 +670,50 @@ class DeviceScene:
             arr[k] = cam._c
         return arr, len(cams)
 
+    def render(self, epsilon, length, imageSize, camera, out=None, **tiling):
+        """Image.render (Image.fs:26-35) -> (FColor[X,Y] as float32 [n_columns, Y, 3], stats dict).  `out`: a float32 array
+        of that shape to render into (e.g. one page-locked with Device.host_register)."""
+        p = self._params(imageSize, epsilon, length, **tiling)
+        out = self._image(out, (p.n_columns, p.height, 3), "(n_columns, Y, 3)")
+        return out, self._call(lib.ft_render, C.byref(camera._c), C.byref(p), _hptr(out))
+
+    def render_device(self, epsilon, length, imageSize, camera, d_out_ptr, **tiling):
+        """asynchronous render into device memory (pointer as int); pair with collect_stats()."""
+        p = self._params(imageSize, epsilon, length, **tiling)
+        check(lib.ft_render_device(self.device._ctx, self._scene, C.byref(camera._c), C.byref(p), _dptr(d_out_ptr)))
+        return p.n_columns
+
+    def render_hits(self, epsilon, length, imageSize, camera, shade=False, material=True, records=True, **tiling_and_ext):
+        """EXTENSION ft_render_hits: per-pixel SdfObject.tryTrace of the camera rays -> (PixelHits, image or None, stats).
+        shade: also render the frame (bit-identical to render() with the same parameters, same launch); without it one ray
+        per pixel is traced and spp / ao_samples / max_bounces / spectral do not apply.  material / records: which planes to return."""
+        p = self._params(imageSize, epsilon, length, **tiling_and_ext)
+        (img, rec, mat), ptrs = _host_outputs((p.n_columns, p.height), shade, records, material)
+        st = self._call(lib.ft_render_hits, C.byref(camera._c), C.byref(p), *ptrs)
+        return PixelHits(rec, mat, self.materials), img, st
+
+    def render_hits_device(self, epsilon, length, imageSize, camera, d_hits_ptr, d_material_ptr=None, d_out_ptr=None, **tiling_and_ext):
+        """asynchronous ft_render_hits_device into device memory (pointers as int, None = not asked; the records 16-byte
+        aligned, n_columns x Y x 16 float32); pair with collect_stats()."""
+        p = self._params(imageSize, epsilon, length, **tiling_and_ext)
+        check(lib.ft_render_hits_device(self.device._ctx, self._scene, C.byref(camera._c), C.byref(p), _dptr(d_out_ptr), _dptr(d_hits_ptr), _dptr(d_material_ptr)))
+        return p.n_columns
+
     def render_views(self, epsilon, length, imageSize, cameras, out=None, **tiling_and_ext):
         """ft_render_views: Image.render of one scene from each camera of `cameras` in one job queue -> (float32 [K, n_columns, Y, 3],
         stats dict of the whole batch).  Block k is bit for bit render(..., cameras[k], **tiling_and_ext)[0].  `out`: a float32 array of
         that shape to render into."""
         p = self._params(imageSize, epsilon, length, **tiling_and_ext)
         arr, k = self._cameras(cameras)
-        shape = (k, p.n_columns, p.height, 3)
-        if out is None:
-            out = np.empty(shape, np.float32)
-        elif out.dtype != np.float32 or out.shape != shape or not out.flags.c_contiguous:
-            raise ValueError("out must be a C-contiguous float32 array of shape (n_views, n_columns, Y, 3)")
-        st = _lib.Stats()
-        check(lib.ft_render_views(self.device._ctx, self._scene, arr, k, C.byref(p), out.ctypes.data_as(C.c_void_p), C.byref(st)))
-        return out, st.as_dict()
+        out = self._image(out, (k, p.n_columns, p.height, 3), "(n_views, n_columns, Y, 3)")
+        return out, self._call(lib.ft_render_views, arr, k, C.byref(p), _hptr(out))
 
     def render_views_device(self, epsilon, length, imageSize, cameras, d_out_ptr, **tiling_and_ext):
         """asynchronous ft_render_views_device into device memory (pointer as int; n_views x n_columns x Y x 3 float32); pair with
         collect_stats()."""
         p = self._params(imageSize, epsilon, length, **tiling_and_ext)
         arr, k = self._cameras(cameras)
-        check(lib.ft_render_views_device(self.device._ctx, self._scene, arr, k, C.byref(p), C.c_void_p(d_out_ptr)))
+        check(lib.ft_render_views_device(self.device._ctx, self._scene, arr, k, C.byref(p), _dptr(d_out_ptr)))
         return p.n_columns
 
     def render_views_hits(self, epsilon, length, imageSize, cameras, shade=False, material=True, records=True, **tiling_and_ext):
@@ -710,22 +722,16 @@ class DeviceScene:
         of the whole batch).  Block k of each is bit for bit render_hits(..., cameras[k], shade, **tiling_and_ext)'s."""
         p = self._params(imageSize, epsilon, length, **tiling_and_ext)
         arr, k = self._cameras(cameras)
-        shape = (k, p.n_columns, p.height)
-        img = np.empty(shape + (3,), np.float32) if shade else None
-        rec = np.empty(shape + (16,), np.float32) if records else None
-        mat = np.empty(shape, np.int32) if material else None
-        ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
-        st = _lib.Stats()
-        check(lib.ft_render_views_hits(self.device._ctx, self._scene, arr, k, C.byref(p), ptr(img), ptr(rec), ptr(mat), C.byref(st)))
-        return PixelHits(rec, mat, self.materials), img, st.as_dict()
+        (img, rec, mat), ptrs = _host_outputs((k, p.n_columns, p.height), shade, records, material)
+        st = self._call(lib.ft_render_views_hits, arr, k, C.byref(p), *ptrs)
+        return PixelHits(rec, mat, self.materials), img, st
 
     def render_views_hits_device(self, epsilon, length, imageSize, cameras, d_hits_ptr, d_material_ptr=None, d_out_ptr=None, **tiling_and_ext):
         """asynchronous ft_render_views_hits_device into device memory (pointers as int, None = not asked; view-major, the records
         16-byte aligned, n_views x n_columns x Y x 16 float32); pair with collect_stats()."""
         p = self._params(imageSize, epsilon, length, **tiling_and_ext)
         arr, k = self._cameras(cameras)
-        ptr = lambda a: None if not a else C.c_void_p(a)
-        check(lib.ft_render_views_hits_device(self.device._ctx, self._scene, arr, k, C.byref(p), ptr(d_out_ptr), ptr(d_hits_ptr), ptr(d_material_ptr)))
+        check(lib.ft_render_views_hits_device(self.device._ctx, self._scene, arr, k, C.byref(p), _dptr(d_out_ptr), _dptr(d_hits_ptr), _dptr(d_material_ptr)))
         return p.n_columns
 
     def collect_stats(self):
@@ -740,56 +746,45 @@ class DeviceScene:
         p = self._params(imageSize, epsilon, length, **ext)
         tm = _tonemap_params(gamma, seed, bmp_order)
         out = np.empty((p.height, p.width, 3) if bmp_order else (p.width, p.height, 3), np.uint8)
-        st = _lib.Stats()
         mx = C.c_float()
-        check(lib.ft_render_colors(self.device._ctx, self._scene, C.byref(camera._c), C.byref(p), C.byref(tm),
-                                   out.ctypes.data_as(C.c_void_p), C.byref(mx), C.byref(st)))
-        return out, float(mx.value), st.as_dict()
+        st = self._call(lib.ft_render_colors, C.byref(camera._c), C.byref(p), C.byref(tm), _hptr(out), C.byref(mx))
+        return out, float(mx.value), st
 
     # ---- ray buffers: host arrays (numpy) or device tensors ------------------------------------------------------------
-    def _device_rays(self, rays):
-        """n of a ray buffer given as a device tensor (checked: float32 [n, 8], contiguous); None for host input"""
-        return check_device_rays(rays) if is_device_tensor(rays) else None
+    def _trace_buffer(self, rays, host_fn, device_fn, widths):
+        """The one place a ray-buffer method decides between a host array and a device tensor (see is_device_tensor) -> (outputs, stats).
+        widths: per output of the C call its row width — float32 [n, w]; 0: int32 [n]; None: not asked for.  A host array goes through
+        host_fn (the ft_* host form); a device tensor (checked: float32 [n, 8], contiguous) is traced where it lies by device_fn on the
+        caller's current stream, the outputs are tensors of its device and stats is None: fetch them with collect_stats() when needed."""
+        if is_device_tensor(rays):
+            n = check_device_rays(rays)
+            outs = [None if w is None else rays.new_empty((n, w)) if w else rays.new_empty((n,), dtype=_torch_int32(rays)) for w in widths]
+            with self.device.on_current_stream(rays):
+                device_fn(rays.data_ptr(), n, *(None if o is None else o.data_ptr() for o in outs))
+            return outs, None
+        rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)
+        n = rays.shape[0]
+        outs = [None if w is None else np.empty((n, w), np.float32) if w else np.empty((n,), np.int32) for w in widths]
+        return outs, self._call(host_fn, _hptr(rays), n, *map(_hptr, outs))
 
     def trace_rays(self, rays):
         """SdfScene.trace over n rays given as float32 [n, 8] (Origin, Direction, Length, Epsilon) -> (float32 [n, 3], stats).
         A device tensor (see is_device_tensor) is traced in place by ft_trace_rays_device on the caller's current stream and the colours come
         back as a tensor of the same device; stats is then None: fetch them with collect_stats() when needed."""
-        n = self._device_rays(rays)
-        if n is not None:
-            out = rays.new_empty((n, 3))
-            with self.device.on_current_stream(rays):
-                self.trace_rays_device(rays.data_ptr(), n, out.data_ptr())
-            return out, None
-        rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)
-        out = np.empty((rays.shape[0], 3), np.float32)
-        st = _lib.Stats()
-        check(lib.ft_trace_rays(self.device._ctx, self._scene, rays.ctypes.data_as(C.c_void_p), rays.shape[0],
-                                out.ctypes.data_as(C.c_void_p), C.byref(st)))
-        return out, st.as_dict()
-
-    def _try_trace(self, fn, rays, width):
-        n = self._device_rays(rays)
-        if n is not None:
-            out = rays.new_empty((n, width))
-            with self.device.on_current_stream(rays):
-                (self.form_try_trace_device if width == 10 else self.object_try_trace_device)(rays.data_ptr(), n, out.data_ptr())
-            return out, None
-        rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)
-        out = np.empty((rays.shape[0], width), np.float32)
-        st = _lib.Stats()
-        check(fn(self.device._ctx, self._scene, rays.ctypes.data_as(C.c_void_p), rays.shape[0], out.ctypes.data_as(C.c_void_p), C.byref(st)))
-        return out, st.as_dict()
+        (out,), st = self._trace_buffer(rays, lib.ft_trace_rays, self.trace_rays_device, (3,))
+        return out, st
 
     def form_try_trace(self, rays):
         """SdfForm.tryTrace scene.Object.Form over rays [n, 8] (SdfForm.fs:93-104) -> float32 [n, 10]:
         Ray at the hit (8), Distance, hit flag (int32 bits; 0 = ValueNone, row is zeros).  Device tensors as in trace_rays."""
-        return self._try_trace(lib.ft_form_try_trace, rays, 10)
+        (out,), st = self._trace_buffer(rays, lib.ft_form_try_trace, self.form_try_trace_device, (10,))
+        return out, st
 
     def object_try_trace(self, rays):
         """SdfObject.tryTrace scene.Object over rays [n, 8] (SdfObject.fs:66-78) -> float32 [n, 16]:
         Ray pulled back by epsilon (8), Normal (3), Color (3), hit flag (int32 bits), 0.  Device tensors as in trace_rays."""
-        return self._try_trace(lib.ft_object_try_trace, rays, 16)
+        (out,), st = self._trace_buffer(rays, lib.ft_object_try_trace, self.object_try_trace_device, (16,))
+        return out, st
 
     def trace_rays_hits(self, rays, shade=True, records=True, material=True):
         """EXTENSION ft_trace_rays_hits: SdfScene.trace and SdfObject.tryTrace of every ray [n, 8] in one launch -> (PixelHits with records
@@ -798,24 +793,9 @@ class DeviceScene:
         and no shadow rays.  Device tensors as in trace_rays: results are tensors of the rays' device (material int32), stats is None."""
         if not (shade or records or material):
             raise ValueError("trace_rays_hits: no output asked for")
-        n = self._device_rays(rays)
-        if n is not None:
-            rgb = rays.new_empty((n, 3)) if shade else None
-            rec = rays.new_empty((n, 16)) if records else None
-            mat = rays.new_empty((n,), dtype=_torch_int32(rays)) if material else None
-            ptr = lambda t: None if t is None else t.data_ptr()
-            with self.device.on_current_stream(rays):
-                self.trace_rays_hits_device(rays.data_ptr(), n, ptr(rgb), ptr(rec), ptr(mat))
-            return PixelHits(rec, mat, self.materials), rgb, None
-        rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)
-        n = rays.shape[0]
-        rgb = np.empty((n, 3), np.float32) if shade else None
-        rec = np.empty((n, 16), np.float32) if records else None
-        mat = np.empty((n,), np.int32) if material else None
-        ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
-        st = _lib.Stats()
-        check(lib.ft_trace_rays_hits(self.device._ctx, self._scene, rays.ctypes.data_as(C.c_void_p), n, ptr(rgb), ptr(rec), ptr(mat), C.byref(st)))
-        return PixelHits(rec, mat, self.materials), rgb, st.as_dict()
+        widths = (3 if shade else None, 16 if records else None, 0 if material else None)
+        (rgb, rec, mat), st = self._trace_buffer(rays, lib.ft_trace_rays_hits, self.trace_rays_hits_device, widths)
+        return PixelHits(rec, mat, self.materials), rgb, st
 
     # raw device pointers (int; None = not asked): rays n x 32 B and object records 16-byte aligned, no scratch, no copy, asynchronous on the
     # context's stream; pair with collect_stats()

@@ -90,23 +90,18 @@ int requireDevice(ft_ctx* c) {
     return FT_OK;
 }
 
-int ensureScratch(ft_ctx* c, size_t bytes) {
-    if (bytes <= c->scratchBytes) return FT_OK;
-    if (c->scratch) { HIP_TRY(hipFree(c->scratch)); c->scratch = nullptr; c->scratchBytes = 0; }
-    HIP_TRY(hipMalloc(&c->scratch, bytes));
-    c->scratchBytes = bytes;
+// the context's device buffers (scratch, aux, planes, cams) only ever grow
+int ensureBytes(void*& p, size_t& have, size_t need) {
+    if (need <= have) return FT_OK;
+    if (p) { HIP_TRY(hipFree(p)); p = nullptr; have = 0; }
+    HIP_TRY(hipMalloc(&p, need));
+    have = need;
     return FT_OK;
 }
+int ensureScratch(ft_ctx* c, size_t bytes) { return ensureBytes(c->scratch, c->scratchBytes, bytes); }
+int ensureAux(ft_ctx* c, size_t bytes) { return ensureBytes(c->aux, c->auxBytes, bytes); }
 
 size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-int ensureAux(ft_ctx* c, size_t bytes) {
-    if (bytes <= c->auxBytes) return FT_OK;
-    if (c->aux) { HIP_TRY(hipFree(c->aux)); c->aux = nullptr; c->auxBytes = 0; }
-    HIP_TRY(hipMalloc(&c->aux, bytes));
-    c->auxBytes = bytes;
-    return FT_OK;
-}
 
 // Device-side per-cell grid build (kernels.hip ft_grid_build_kernel).  Declines (host build) for tiny grids,
 // more than FT_GRID_BUILD_MAX_ITEMS items or a scratch need above 512 MB.
@@ -387,6 +382,13 @@ bool optionAccepts(const OptionSpec& o, int32_t v) {
     return true;
 }
 
+// The job counter is 32 bits wide: `views` views of `samples` sample planes each, 64 jobs a tile.  The only place the limit is computed.
+int checkJobCount(uint64_t views, uint64_t samples, const ft_render_params* p) {
+    const uint64_t tiles = (uint64_t)((p->n_columns + 7) / 8) * (uint64_t)((p->height + 7) / 8);
+    if (views * samples * tiles * 64 >= 0xFFFF0000ull) return setErr(FT_ERR_UNSUPPORTED, "more than 2^32 samples in one call");
+    return FT_OK;
+}
+
 int checkParams(const ft_render_params* p) {
     if (!p) return setErr(FT_ERR_INVALID, "null render params");
     if (p->width <= 0 || p->height <= 0 || p->n_columns <= 0) return setErr(FT_ERR_INVALID, "empty image");
@@ -402,9 +404,7 @@ int checkParams(const ft_render_params* p) {
     const int64_t c = (int64_t)p->n_columns - 1;
     const int64_t x = p->x0 + (c / p->stripe_width) * (int64_t)p->stripe_width * p->stripe_ranks + (int64_t)p->stripe_rank * p->stripe_width + c % p->stripe_width;
     if (p->x0 < 0 || x >= p->width) return setErr(FT_ERR_INVALID, "column range leaves the image");
-    const uint64_t tiles = (uint64_t)((p->n_columns + 7) / 8) * (uint64_t)((p->height + 7) / 8);
-    if (tiles * 64 * (uint64_t)p->spp >= 0xFFFF0000ull) return setErr(FT_ERR_UNSUPPORTED, "more than 2^32 samples in one call");
-    return FT_OK;
+    return checkJobCount(1, (uint64_t)p->spp, p);
 }
 
 }  // namespace
@@ -611,82 +611,153 @@ int ft_camera_look_at(const float pos[3], const float look[3], const float up[3]
 }
 
 // ---- hot path ------------------------------------------------------------------------------------
-// EXTENSION ft_render_hits: device buffers of the per-pixel records (either may be NULL)
-struct HitBufs { void* hits; void* material; };
-// ft_render_views: n <= FT_MAX_VIEWS cameras (12 floats each) in device memory, rendered by one launch of the *_views kernel
-struct ViewBatch { const float* cams; uint32_t n; };
+namespace {
 
-// hb != NULL: the EXTENSION build also writes the hit buffers; d_out = NULL then means hits only (one ray per pixel, the EXTENSION fields of p
-// do not apply).  vb != NULL: vb->n views instead of `cam`, written view after view (n x n_columns x height x 3 floats at d_out; with hb,
-// n x n_columns x height records and material handles)
-static int renderLane(ft_ctx* c, const ft_scene* s, const ft_camera* cam, const ft_render_params* params, void* d_out, int lane,
-                      const HitBufs* hb = nullptr, const ViewBatch* vb = nullptr) {
-    int rc = requireDevice(c); if (rc) return rc;
-    if (!s || s->ctx != c || !(vb ? vb->cams : (const void*)cam) || (!d_out && !hb)) return setErr(FT_ERR_INVALID, "bad argument (scene must belong to this context)");
-    if (vb && (vb->n < 1u || vb->n > FT_MAX_VIEWS)) return setErr(FT_ERR_INVALID, "internal: a view batch has 1 .. 64 views");
-    if ((rc = checkParams(params))) return rc;
-    ft_render_params hitsOnly;
-    const ft_render_params* p = params;
-    if (hb && !d_out) {
-        hitsOnly = *params;
-        hitsOnly.spp = 1; hitsOnly.ao_samples = 0; hitsOnly.max_bounces = 0; hitsOnly.spectral = 0;
-        p = &hitsOnly;
+// What a call writes per pixel or ray: colours (3 floats; SdfForm.tryTrace: its 10-dword results) and, in the EXTENSION builds, the 64-byte
+// ft_object_trace_result records and the int32 material handles.  Any may be NULL: not asked for.
+struct Outputs {
+    void* rgb; void* hits; void* material;
+    bool any() const { return rgb || hits || material; }
+    bool extra() const { return hits || material; }                // something only the EXTENSION builds write
+    Outputs at(size_t px) const {                                  // a frame's buffers `px` pixels further on
+        auto step = [](void* p, size_t bytes) { return p ? static_cast<void*>(static_cast<unsigned char*>(p) + bytes) : nullptr; };
+        return Outputs{step(rgb, px * 12), step(hits, px * 64), step(material, px * 4)};
     }
-    if (lane != 0 && p->spp != 1) return setErr(FT_ERR_INVALID, "internal: the sample planes belong to lane 0");
+};
+
+// What every form asks of its outputs, stated once: at least one of them and, in device memory, records on 16 bytes, the rest on 4.  The
+// entry points differ in whether they ask for the device before or after this, and keep that order.
+int checkOutputs(const Outputs& o, bool deviceMemory) {
+    if (!o.any()) return setErr(FT_ERR_INVALID, "no output asked for");
+    if (deviceMemory && ((reinterpret_cast<uintptr_t>(o.hits) & 15u) || (reinterpret_cast<uintptr_t>(o.material) & 3u) || (reinterpret_cast<uintptr_t>(o.rgb) & 3u)))
+        return setErr(FT_ERR_INVALID, "the ft_object_trace_result records must be 16-byte aligned, every other output buffer 4-byte aligned");
+    return FT_OK;
+}
+
+// nViews cameras (host memory), one set of parameters, outputs in device memory written view after view: every render entry point is a check
+// plus one of these, and a new form (per-view parameters, a region of interest, a depth plane) is a field here
+struct FrameRequest { const ft_camera* cams; int32_t nViews; const ft_render_params* p; Outputs dev; };
+
+// The kernel arguments of one launch: nViews views (`views`: their cameras in device memory, 12 floats each; NULL: the single camera `cam`)
+// with the parameters p.  No HIP call, no context: launchTrace adds what depends on those.
+FtRenderArgs frameArgs(const ft_scene* s, const ft_render_params& p, const ft_camera* cam, const float* views, uint32_t nViews, const Outputs& o) {
     FtRenderArgs a{};
-    if (vb) { a.views = vb->cams; a.nViews = vb->n; }
+    if (views) { a.views = views; a.nViews = nViews; }
     else memcpy(a.cam, cam, sizeof(float) * 12);
-    const uint32_t nViews = vb ? vb->n : 1u;
-    a.W = p->width; a.H = p->height; a.x0 = p->x0; a.nCols = p->n_columns;
-    a.stripeW = (uint32_t)p->stripe_width; a.stripeRanks = (uint32_t)p->stripe_ranks; a.stripeRank = (uint32_t)p->stripe_rank;
+    a.W = p.width; a.H = p.height; a.x0 = p.x0; a.nCols = p.n_columns;
+    a.stripeW = (uint32_t)p.stripe_width; a.stripeRanks = (uint32_t)p.stripe_ranks; a.stripeRank = (uint32_t)p.stripe_rank;
     a.mode = 0;
-    a.maxSize = (float)std::max(p->width, p->height);              // Image.fs:18
-    a.eps = p->epsilon; a.length = p->length;
-    a.tilesY = (uint32_t)((p->height + 7) / 8);
-    a.jobsPerPlane = (uint32_t)((p->n_columns + 7) / 8) * a.tilesY * 64u;
-    a.spp = (uint32_t)p->spp; a.sppN = 1; while (a.sppN * a.sppN < a.spp) ++a.sppN;
-    a.aoSamples = (uint32_t)p->ao_samples; a.aoRadius = p->ao_radius;
-    a.planePixels = (uint32_t)p->n_columns * (uint32_t)p->height;
+    a.maxSize = (float)std::max(p.width, p.height);                // Image.fs:18
+    a.eps = p.epsilon; a.length = p.length;
+    a.tilesY = (uint32_t)((p.height + 7) / 8);
+    a.jobsPerPlane = (uint32_t)((p.n_columns + 7) / 8) * a.tilesY * 64u;
+    a.spp = (uint32_t)p.spp; a.sppN = 1; while (a.sppN * a.sppN < a.spp) ++a.sppN;
+    a.aoSamples = (uint32_t)p.ao_samples; a.aoRadius = p.ao_radius;
+    a.planePixels = (uint32_t)p.n_columns * (uint32_t)p.height;
     a.nJobs = a.jobsPerPlane * a.spp * nViews;                     // views: view after view, each its spp sample planes (kernels.hip start_job)
     // EXTENSION glass / wavelengths: without a glass material in the scene bounces change nothing
-    a.maxBounces = s->dev.nGlass ? (uint32_t)p->max_bounces : 0u;
-    a.spectral = (uint32_t)p->spectral;
+    a.maxBounces = s->dev.nGlass ? (uint32_t)p.max_bounces : 0u;
+    a.spectral = (uint32_t)p.spectral;
     if (a.spectral) ft::spectralTable((int)a.spectral, a.spec);
     a.ext = (a.spp != 1u || a.aoSamples != 0u || a.maxBounces != 0u || a.spectral != 0u) ? 1u : 0u;
-    if (hb) {                                                      // the hit buffers exist in the EXTENSION builds only
+    if (o.extra()) {                                               // the hit buffers exist in the EXTENSION builds only
         a.ext = 1u;
-        a.hits = d_out ? 1u : 2u;
-        a.hitsOut = static_cast<float*>(hb->hits); a.matOut = static_cast<int32_t*>(hb->material);
+        a.hits = o.rgb ? 1u : 2u;
+        a.hitsOut = static_cast<float*>(o.hits); a.matOut = static_cast<int32_t*>(o.material);
         a.matHandles = s->dMatHandles;
     }
+    return a;
+}
+
+// Launches `a` on a render lane, its colours to d_out.  EXTENSION spp > 1: one frame per sample into the context's planes, then a fixed-order
+// resolve per view; the planes belong to lane 0.
+int launchFrameArgs(ft_ctx* c, const ft_scene* s, FtRenderArgs& a, void* d_out, int lane) {
     if (a.spp == 1) { a.out = static_cast<float*>(d_out); return launchTrace(c, s, a, lane); }
-    // EXTENSION: one frame per sample, then a fixed-order resolve (per view)
+    if (lane != 0) return setErr(FT_ERR_INVALID, "internal: the sample planes belong to lane 0");
+    const uint32_t nViews = a.views ? a.nViews : 1u;
     const size_t planeFloats = (size_t)a.planePixels * 3;
-    const size_t need = planeFloats * a.spp * nViews * sizeof(float);
-    if (need > c->planesBytes) {
-        if (c->planes) { HIP_TRY(hipFree(c->planes)); c->planes = nullptr; c->planesBytes = 0; }
-        HIP_TRY(hipMalloc(&c->planes, need));
-        c->planesBytes = need;
-    }
+    int rc = ensureBytes(c->planes, c->planesBytes, planeFloats * a.spp * nViews * sizeof(float)); if (rc) return rc;
     a.out = static_cast<float*>(c->planes);
-    if ((rc = launchTrace(c, s, a))) return rc;
+    if ((rc = launchTrace(c, s, a, 0))) return rc;
     for (uint32_t k = 0; k < nViews; ++k)
         HIP_TRY(ft_launch_resolve(static_cast<const float*>(c->planes) + k * a.spp * planeFloats, static_cast<float*>(d_out) + k * planeFloats, planeFloats, a.spp, c->stream));
     return FT_OK;
 }
 
+// what every frame launch asks: a device, a scene of this context, cameras, an output, sound parameters — in this order
+int checkFrame(ft_ctx* c, const ft_scene* s, const FrameRequest& r) {
+    int rc = requireDevice(c); if (rc) return rc;
+    if (!s || s->ctx != c || !r.cams || !r.dev.any()) return setErr(FT_ERR_INVALID, "bad argument (scene must belong to this context)");
+    return checkParams(r.p);
+}
+
+// the batch's cameras into the context's device table (12 floats each)
+int stageCameras(ft_ctx* c, const ft_camera* cameras, int32_t n) {
+    static_assert(sizeof(ft_camera) == 12 * sizeof(float), "layout");
+    const size_t bytes = (size_t)n * sizeof(ft_camera);
+    int rc = ensureBytes(c->cams, c->camsBytes, bytes); if (rc) return rc;
+    // on the context's stream, behind the launches that may still read the previous batch's table; from a pageable copy, so that the caller's
+    // array is free when this returns (a pageable source is copied before hipMemcpyAsync returns)
+    const std::vector<ft_camera> staged(cameras, cameras + n);
+    HIP_TRY(hipMemcpyAsync(c->cams, staged.data(), bytes, hipMemcpyHostToDevice, c->stream));
+    return FT_OK;
+}
+
+// The one path of every frame form, on the context's stream.  One view has its camera in the kernel arguments (ft_render_device's kernels);
+// several go through the context's camera table in launches of at most FT_MAX_VIEWS views (one PH_CAM value per lane of a wave), each at its
+// views' offsets into the outputs.  Without colours one ray per pixel is traced and the EXTENSION fields of p do not apply.
+int launchFrame(ft_ctx* c, const ft_scene* s, const FrameRequest& r) {
+    int rc = checkFrame(c, s, r); if (rc) return rc;
+    ft_render_params p = *r.p;
+    if (!r.dev.rgb) { p.spp = 1; p.ao_samples = 0; p.max_bounces = 0; p.spectral = 0; }
+    if (r.nViews > 1 && (rc = stageCameras(c, r.cams, r.nViews))) return rc;
+    const size_t px = (size_t)p.n_columns * (size_t)p.height;
+    for (int32_t k0 = 0; k0 < r.nViews; k0 += FT_MAX_VIEWS) {
+        const uint32_t m = (uint32_t)std::min<int32_t>(FT_MAX_VIEWS, r.nViews - k0);
+        const Outputs part = r.dev.at((size_t)k0 * px);
+        FtRenderArgs a = frameArgs(s, p, r.cams, r.nViews > 1 ? static_cast<const float*>(c->cams) + 12 * (size_t)k0 : nullptr, m, part);
+        if ((rc = launchFrameArgs(c, s, a, part.rgb, 0))) return rc;
+    }
+    return FT_OK;
+}
+
+// everything a views form can refuse before any device work: arguments, parameters and the job count of the whole batch (without colours:
+// one sample plane a view, whatever spp says); the device is asked for last
+int checkViews(ft_ctx* c, const ft_camera* cameras, int32_t n, const ft_render_params* p, const Outputs& o) {
+    if (!c) return setErr(FT_ERR_INVALID, "null context");
+    if (!cameras || !o.any()) return setErr(FT_ERR_INVALID, "null argument");
+    if (n < 1) return setErr(FT_ERR_INVALID, "ft_render_views: n_views must be at least 1");
+    int rc = checkParams(p); if (rc) return rc;
+    if ((rc = checkJobCount((uint64_t)n, o.rgb ? (uint64_t)p->spp : 1u, p))) return rc;
+    return requireDevice(c);
+}
+
+}  // namespace
+
+// The four device forms: each a check, in the order it always had, and the one launch path.
 int ft_render_device(ft_ctx* c, const ft_scene* s, const ft_camera* cam, const ft_render_params* p, void* d_out) {
-    return renderLane(c, s, cam, p, d_out, 0);
+    return launchFrame(c, s, FrameRequest{cam, 1, p, Outputs{d_out, nullptr, nullptr}});
 }
 
 int ft_render_hits_device(ft_ctx* c, const ft_scene* s, const ft_camera* cam, const ft_render_params* p, void* d_out_rgb, void* d_hits, void* d_material) {
-    int rc = requireDevice(c); if (rc) return rc;
-    if (!d_out_rgb && !d_hits && !d_material) return setErr(FT_ERR_INVALID, "ft_render_hits: no output asked for");
-    if ((reinterpret_cast<uintptr_t>(d_hits) & 15u) || (reinterpret_cast<uintptr_t>(d_material) & 3u) || (reinterpret_cast<uintptr_t>(d_out_rgb) & 3u))
-        return setErr(FT_ERR_INVALID, "ft_render_hits: the hit buffer must be 16-byte aligned, the image and the material plane 4-byte aligned");
-    if (!d_hits && !d_material) return renderLane(c, s, cam, p, d_out_rgb, 0);     // the frame alone: exactly ft_render_device
-    const HitBufs hb{d_hits, d_material};
-    return renderLane(c, s, cam, p, d_out_rgb, 0, &hb);
+    const Outputs o{d_out_rgb, d_hits, d_material};
+    int rc = requireDevice(c); if (rc) return rc;                      // the device first, then the outputs
+    if ((rc = checkOutputs(o, true))) return rc;
+    return launchFrame(c, s, FrameRequest{cam, 1, p, o});
+}
+
+int ft_render_views_device(ft_ctx* c, const ft_scene* s, const ft_camera* cameras, int32_t n, const ft_render_params* p, void* d_out) {
+    const Outputs o{d_out, nullptr, nullptr};
+    int rc = checkViews(c, cameras, n, p, o); if (rc) return rc;
+    return launchFrame(c, s, FrameRequest{cameras, n, p, o});
+}
+
+int ft_render_views_hits_device(ft_ctx* c, const ft_scene* s, const ft_camera* cameras, int32_t n, const ft_render_params* p, void* d_out_rgb,
+                                void* d_hits, void* d_material) {
+    const Outputs o{d_out_rgb, d_hits, d_material};
+    int rc = checkOutputs(o, true); if (rc) return rc;                 // the outputs first, the device last (checkViews)
+    if ((rc = checkViews(c, cameras, n, p, o))) return rc;
+    return launchFrame(c, s, FrameRequest{cameras, n, p, o});
 }
 
 int ft_collect_stats(ft_ctx* c, ft_stats* st) {
@@ -768,9 +839,58 @@ int ensurePipeline(ft_ctx* c, size_t nEvents) {
     return FT_OK;
 }
 
-}  // namespace
+// page-lock `p` unless it already is; true if this call pinned it (the caller unpins)
+bool pinForCall(ft_ctx* c, void* p, size_t bytes) {
+    if (bytes < ((size_t)1 << 20) || !c->optHostPin || isPageLocked(c, p, bytes)) return false;
+    if (hipHostRegister(p, bytes, hipHostRegisterDefault) == hipSuccess) return true;
+    (void)hipGetLastError();                                   // not fatal: the runtime's pageable path still works
+    return false;
+}
 
-namespace {
+// The host forms' output ritual, once: [input | colours | records | material plane] in the context's scratch, each part asked for on a 256-byte
+// boundary; the launch writes there; every part is copied to the caller's buffer behind it on the context's stream; finish() ends the call.
+// A form that bounds its scratch plans one launch group and calls copyOut once per group.
+// pin: page-lock the caller's buffers for the call while the GPU renders the first group, so that the copies run at link rate.  The views forms
+// pin (like ft_render and ft_render_colors); ft_render_hits and the ray-buffer forms never did: whether they should is a measurement to make.
+class HostStaging {
+public:
+    HostStaging(ft_ctx* c, const char* what, const Outputs& host, size_t rgbStride, bool pin)
+        : c_(c), what_(what), host_{host.rgb, host.hits, host.material}, stride_{rgbStride, 64, 4}, pin_(pin) {}
+    // scratch for `count` pixels or rays behind inputBytes of input
+    int plan(size_t inputBytes, size_t count) {
+        size_t end = inputBytes;
+        for (int i = 0; i < 3; ++i) { off_[i] = align256(end); end = off_[i] + (host_[i] ? count * stride_[i] : 0); }
+        return ensureScratch(c_, end);
+    }
+    void* input() const { return c_->scratch; }
+    Outputs dev() const { return Outputs{part(0), part(1), part(2)}; }
+    bool ok() const { return !rc_ && err_ == hipSuccess; }
+    // behind a launch that returned rc: `count` items from the scratch to the caller's buffers at item `first`; `total`: the items of the whole call
+    void copyOut(int rc, size_t first, size_t count, size_t total) {
+        rc_ = rc;
+        if (!rc_ && pin_ && first == 0)                                // the GPU is rendering: page-lock the destinations meanwhile
+            for (int i = 0; i < 3; ++i) if (host_[i]) pinned_[i] = pinForCall(c_, host_[i], total * stride_[i]);
+        for (int i = 0; i < 3 && ok(); ++i)
+            if (host_[i]) err_ = hipMemcpyAsync(static_cast<unsigned char*>(host_[i]) + first * stride_[i], part(i), count * stride_[i], hipMemcpyDeviceToHost, c_->stream);
+    }
+    // nothing of the call is left in flight, whatever happened (the scratch and the caller's buffers are reused); what was pinned here is
+    // released; then the launch's error, the copies', the synchronisation's, and at last the statistics
+    int finish(ft_stats* st) {
+        const hipError_t se = hipStreamSynchronize(c_->stream);
+        for (int i = 0; i < 3; ++i) if (pinned_[i]) (void)hipHostUnregister(host_[i]);
+        if (rc_) return rc_;
+        if (err_ != hipSuccess) return hipFail(err_, (std::string(what_) + " host output").c_str());
+        if (se != hipSuccess) return hipFail(se, what_);
+        return ft_collect_stats(c_, st);
+    }
+private:
+    void* part(int i) const { return host_[i] ? static_cast<unsigned char*>(c_->scratch) + off_[i] : nullptr; }
+    ft_ctx* c_; const char* what_;
+    void* host_[3]; size_t stride_[3]; bool pin_;
+    size_t off_[3] = {0, 0, 0};
+    bool pinned_[3] = {false, false, false};
+    int rc_ = FT_OK; hipError_t err_ = hipSuccess;
+};
 
 // The frame of `p` rendered into the context's scratch buffer in column chunks on the two render lanes (the drain of one chunk
 // overlaps the start of the next); chunk i's completion is syncEvents[2 + i].  c0 receives the chunk boundaries (columns).
@@ -792,28 +912,30 @@ int launchChunks(ft_ctx* c, const ft_scene* s, const ft_camera* cam, const ft_re
     for (int i = 0; i < plan.n; ++i) plan.c0[i] = (int)(((int64_t)p->n_columns * i / plan.n) & ~(int64_t)7);   // chunks start on a tile boundary
     plan.c0[plan.n] = p->n_columns;
     char* dFrame = static_cast<char*>(c->scratch);
+    if ((rc = checkFrame(c, s, FrameRequest{cam, 1, p, Outputs{dFrame, nullptr, nullptr}}))) return rc;
     for (int i = 0; i < plan.n; ++i) {
         ft_render_params q = *p;
         q.x0 = p->x0 + plan.c0[i]; q.n_columns = plan.c0[i + 1] - plan.c0[i];
         if (p->stripe_ranks == 1) q.stripe_width = q.n_columns;
         const int lane = plan.n > 1 ? (i & 1) : 0;
-        if ((rc = renderLane(c, s, cam, &q, dFrame + (size_t)plan.c0[i] * plan.colBytes, lane))) return rc;
+        void* const dChunk = dFrame + (size_t)plan.c0[i] * plan.colBytes;
+        FtRenderArgs a = frameArgs(s, q, cam, nullptr, 1, Outputs{dChunk, nullptr, nullptr});
+        if ((rc = launchFrameArgs(c, s, a, dChunk, lane))) return rc;
         HIP_TRY(hipEventRecord(c->syncEvents[2 + i], lane ? c->lane1 : c->stream));
     }
     return FT_OK;
 }
 
-void drainPipeline(ft_ctx* c) {
-    (void)hipStreamSynchronize(c->copyStream); (void)hipStreamSynchronize(c->lane1); (void)hipStreamSynchronize(c->stream);
-}
-
-// page-lock `p` unless it already is; true if this call pinned it (the caller unpins)
-bool pinForCall(ft_ctx* c, void* p, size_t bytes) {
-    if (bytes < ((size_t)1 << 20) || !c->optHostPin || isPageLocked(c, p, bytes)) return false;
-    if (hipHostRegister(p, bytes, hipHostRegisterDefault) == hipSuccess) return true;
-    (void)hipGetLastError();                                   // not fatal: the runtime's pageable path still works
-    return false;
-}
+// The scope of a call that runs the chunk pipeline (ft_render, ft_render_colors).  Whatever goes wrong, nothing of the call may still be in
+// flight when it returns (the scratch frame and the caller's buffer are reused), and a buffer pinned here is released.
+struct ChunkedCall {
+    ft_ctx* c; void* pinned = nullptr; bool waitedFor = false;     // waitedFor: the call synchronised everything itself
+    void pin(void* p, size_t bytes) { if (pinForCall(c, p, bytes)) pinned = p; }
+    ~ChunkedCall() {
+        if (!waitedFor && c->copyStream) { (void)hipStreamSynchronize(c->copyStream); (void)hipStreamSynchronize(c->lane1); (void)hipStreamSynchronize(c->stream); }
+        if (pinned) (void)hipHostUnregister(pinned);
+    }
+};
 
 }  // namespace
 
@@ -822,12 +944,9 @@ int ft_render(ft_ctx* c, const ft_scene* s, const ft_camera* cam, const ft_rende
     if (!out) return setErr(FT_ERR_INVALID, "null output");
     if ((rc = checkParams(p))) return rc;
     ChunkPlan plan;
-    bool pinnedHere = false;
-    // whatever goes wrong, nothing of this call may still be in flight when it returns (the scratch frame and the caller's
-    // buffer are reused), and a buffer pinned here is released
-    auto finish = [&](int code) { if (c->copyStream) drainPipeline(c); if (pinnedHere) (void)hipHostUnregister(out); return code; };
-    if ((rc = launchChunks(c, s, cam, p, plan))) return finish(rc);
-    pinnedHere = pinForCall(c, out, plan.bytes);               // the GPU is rendering: page-lock the destination meanwhile
+    ChunkedCall call{c};
+    if ((rc = launchChunks(c, s, cam, p, plan))) return rc;
+    call.pin(out, plan.bytes);                                 // the GPU is rendering: page-lock the destination meanwhile
     char* dFrame = static_cast<char*>(c->scratch);
     hipError_t err = hipSuccess;
     for (int i = 0; i < plan.n && err == hipSuccess; ++i) {
@@ -840,162 +959,59 @@ int ft_render(ft_ctx* c, const ft_scene* s, const ft_camera* cam, const ft_rende
     if (err == hipSuccess) err = hipStreamSynchronize(c->copyStream);
     if (err == hipSuccess) err = hipStreamSynchronize(c->lane1);
     if (err == hipSuccess) err = hipStreamSynchronize(c->stream);
-    if (err != hipSuccess) return finish(hipFail(err, "ft_render host output"));
-    if (pinnedHere) { (void)hipHostUnregister(out); pinnedHere = false; }
+    if (err != hipSuccess) return hipFail(err, "ft_render host output");
+    call.waitedFor = true;
     return ft_collect_stats(c, st);
 }
 
-// EXTENSION: the whole frame on lane 0 into the context's scratch ([image | records | material plane]), then copied out
+// EXTENSION: the whole frame on lane 0 into the context's scratch, then copied out
 int ft_render_hits(ft_ctx* c, const ft_scene* s, const ft_camera* cam, const ft_render_params* p, float* out_rgb, ft_object_trace_result* out_hits,
                    int32_t* out_material, ft_stats* st) {
     static_assert(sizeof(ft_object_trace_result) == 64, "layout");
+    const Outputs host{out_rgb, out_hits, out_material};
     int rc = requireDevice(c); if (rc) return rc;
-    if (!out_rgb && !out_hits && !out_material) return setErr(FT_ERR_INVALID, "ft_render_hits: no output asked for");
+    if ((rc = checkOutputs(host, false))) return rc;
     if ((rc = checkParams(p))) return rc;
     const size_t px = (size_t)p->n_columns * (size_t)p->height;
-    const size_t rgbBytes = out_rgb ? px * 12 : 0, hitBytes = out_hits ? px * 64 : 0, matBytes = out_material ? px * 4 : 0;
-    const size_t oHits = align256(rgbBytes), oMat = oHits + align256(hitBytes);
-    if ((rc = ensureScratch(c, oMat + matBytes))) return rc;
-    unsigned char* base = static_cast<unsigned char*>(c->scratch);
-    rc = ft_render_hits_device(c, s, cam, p, out_rgb ? base : nullptr, out_hits ? base + oHits : nullptr, out_material ? base + oMat : nullptr);
-    hipError_t err = hipSuccess;
-    if (!rc && out_rgb) err = hipMemcpyAsync(out_rgb, base, rgbBytes, hipMemcpyDeviceToHost, c->stream);
-    if (!rc && err == hipSuccess && out_hits) err = hipMemcpyAsync(out_hits, base + oHits, hitBytes, hipMemcpyDeviceToHost, c->stream);
-    if (!rc && err == hipSuccess && out_material) err = hipMemcpyAsync(out_material, base + oMat, matBytes, hipMemcpyDeviceToHost, c->stream);
-    const hipError_t se = hipStreamSynchronize(c->stream);             // nothing of this call is left in flight, whatever happened
-    if (rc) return rc;
-    if (err != hipSuccess) return hipFail(err, "ft_render_hits host output");
-    if (se != hipSuccess) return hipFail(se, "ft_render_hits");
-    return ft_collect_stats(c, st);
+    HostStaging stage(c, "ft_render_hits", host, 12, false);
+    if ((rc = stage.plan(0, px))) return rc;
+    stage.copyOut(launchFrame(c, s, FrameRequest{cam, 1, p, stage.dev()}), 0, px, px);
+    return stage.finish(st);
 }
 
 // ---- ft_render_views: K cameras, one scene, one set of parameters ------------------------------------------------------
-namespace {
-
-// everything that can be refused before any device work: arguments, parameters and the job count of the whole batch (hitsOnly: one sample
-// plane a view, whatever spp says)
-int checkViews(ft_ctx* c, const ft_camera* cameras, int32_t n, const ft_render_params* p, const void* out, bool hitsOnly = false) {
-    if (!c) return setErr(FT_ERR_INVALID, "null context");
-    if (!cameras || !out) return setErr(FT_ERR_INVALID, "null argument");
-    if (n < 1) return setErr(FT_ERR_INVALID, "ft_render_views: n_views must be at least 1");
-    int rc = checkParams(p); if (rc) return rc;
-    const uint64_t tiles = (uint64_t)((p->n_columns + 7) / 8) * (uint64_t)((p->height + 7) / 8);
-    if ((uint64_t)n * (uint64_t)(hitsOnly ? 1 : p->spp) * tiles * 64 >= 0xFFFF0000ull) return setErr(FT_ERR_UNSUPPORTED, "more than 2^32 samples in one call");
-    return requireDevice(c);
-}
-
-// the batch's cameras into the context's device table (12 floats each)
-int stageCameras(ft_ctx* c, const ft_camera* cameras, int32_t n) {
-    static_assert(sizeof(ft_camera) == 12 * sizeof(float), "layout");
-    const size_t bytes = (size_t)n * sizeof(ft_camera);
-    if (bytes > c->camsBytes) {
-        if (c->cams) { HIP_TRY(hipFree(c->cams)); c->cams = nullptr; c->camsBytes = 0; }
-        HIP_TRY(hipMalloc(&c->cams, bytes));
-        c->camsBytes = bytes;
-    }
-    // on the context's stream, behind the launches that may still read the previous batch's table; from a pageable copy, so that the caller's
-    // array is free when this returns (a pageable source is copied before hipMemcpyAsync returns)
-    const std::vector<ft_camera> staged(cameras, cameras + n);
-    HIP_TRY(hipMemcpyAsync(c->cams, staged.data(), bytes, hipMemcpyHostToDevice, c->stream));
-    return FT_OK;
-}
-
-// launches of at most FT_MAX_VIEWS views (one PH_CAM value per lane of a wave), each at its views' offsets into the outputs; their counters add
-// up in the context's statistics.  hb: the hit buffers of the whole batch (NULL: none).
-int launchViews(ft_ctx* c, const ft_scene* s, const ft_camera* cameras, int32_t n, const ft_render_params* p, void* d_out, const HitBufs* hb) {
-    int rc = stageCameras(c, cameras, n); if (rc) return rc;
-    const size_t px = (size_t)p->n_columns * (size_t)p->height;
-    auto at = [](void* base, size_t bytes) { return base ? static_cast<void*>(static_cast<unsigned char*>(base) + bytes) : nullptr; };
-    for (int32_t k0 = 0; k0 < n; k0 += FT_MAX_VIEWS) {
-        const ViewBatch vb{static_cast<const float*>(c->cams) + 12 * (size_t)k0, (uint32_t)std::min<int32_t>(FT_MAX_VIEWS, n - k0)};
-        const HitBufs part = hb ? HitBufs{at(hb->hits, (size_t)k0 * px * 64), at(hb->material, (size_t)k0 * px * 4)} : HitBufs{};
-        if ((rc = renderLane(c, s, nullptr, p, at(d_out, (size_t)k0 * px * 12), 0, hb ? &part : nullptr, &vb))) return rc;
-    }
-    return FT_OK;
-}
-
-}  // namespace
-
-int ft_render_views_device(ft_ctx* c, const ft_scene* s, const ft_camera* cameras, int32_t n, const ft_render_params* p, void* d_out) {
-    int rc = checkViews(c, cameras, n, p, d_out); if (rc) return rc;
-    if (n == 1) return renderLane(c, s, cameras, p, d_out, 0);        // exactly ft_render_device
-    return launchViews(c, s, cameras, n, p, d_out, nullptr);
-}
-
 // the whole batch into the context's scratch, then one copy to the (page-locked for the call) destination
 int ft_render_views(ft_ctx* c, const ft_scene* s, const ft_camera* cameras, int32_t n, const ft_render_params* p, float* out, ft_stats* st) {
-    int rc = checkViews(c, cameras, n, p, out); if (rc) return rc;
+    const Outputs host{out, nullptr, nullptr};
+    int rc = checkViews(c, cameras, n, p, host); if (rc) return rc;
     if (n == 1) return ft_render(c, s, cameras, p, out, st);           // exactly ft_render (its column-chunk pipeline included)
-    const size_t bytes = (size_t)n * (size_t)p->n_columns * (size_t)p->height * 3 * sizeof(float);
-    if ((rc = ensureScratch(c, bytes))) return rc;
-    bool pinnedHere = false;
-    rc = ft_render_views_device(c, s, cameras, n, p, c->scratch);
-    if (!rc) pinnedHere = pinForCall(c, out, bytes);                    // the GPU is rendering: page-lock the destination meanwhile
-    hipError_t err = hipSuccess;
-    if (!rc) err = hipMemcpyAsync(out, c->scratch, bytes, hipMemcpyDeviceToHost, c->stream);
-    const hipError_t se = hipStreamSynchronize(c->stream);             // nothing of this call is left in flight, whatever happened
-    if (pinnedHere) (void)hipHostUnregister(out);
-    if (rc) return rc;
-    if (err != hipSuccess) return hipFail(err, "ft_render_views host output");
-    if (se != hipSuccess) return hipFail(se, "ft_render_views");
-    return ft_collect_stats(c, st);
+    const size_t px = (size_t)p->n_columns * (size_t)p->height;
+    HostStaging stage(c, "ft_render_views", host, 12, true);
+    if ((rc = stage.plan(0, (size_t)n * px))) return rc;
+    stage.copyOut(launchFrame(c, s, FrameRequest{cameras, n, p, stage.dev()}), 0, (size_t)n * px, (size_t)n * px);
+    return stage.finish(st);
 }
 
 // ---- ft_render_views_hits: the hit buffers of K cameras, one scene, one set of parameters ------------------------------------------
-namespace {
-
-int checkViewsHits(ft_ctx* c, const ft_camera* cameras, int32_t n, const ft_render_params* p, const void* rgb, const void* hits, const void* mat) {
-    if (!rgb && !hits && !mat) return setErr(FT_ERR_INVALID, "ft_render_views_hits: no output asked for");
-    return checkViews(c, cameras, n, p, rgb ? rgb : hits ? hits : mat, !rgb);
-}
-
-}  // namespace
-
-int ft_render_views_hits_device(ft_ctx* c, const ft_scene* s, const ft_camera* cameras, int32_t n, const ft_render_params* p, void* d_out_rgb,
-                                void* d_hits, void* d_material) {
-    if ((reinterpret_cast<uintptr_t>(d_hits) & 15u) || (reinterpret_cast<uintptr_t>(d_material) & 3u) || (reinterpret_cast<uintptr_t>(d_out_rgb) & 3u))
-        return setErr(FT_ERR_INVALID, "ft_render_views_hits: the hit buffer must be 16-byte aligned, the image and the material plane 4-byte aligned");
-    int rc = checkViewsHits(c, cameras, n, p, d_out_rgb, d_hits, d_material); if (rc) return rc;
-    if (!d_hits && !d_material) return ft_render_views_device(c, s, cameras, n, p, d_out_rgb);         // the frames alone
-    if (n == 1) return ft_render_hits_device(c, s, cameras, p, d_out_rgb, d_hits, d_material);        // exactly ft_render_hits_device
-    const HitBufs hb{d_hits, d_material};
-    return launchViews(c, s, cameras, n, p, d_out_rgb, &hb);
-}
-
-// EXTENSION: one launch group (<= FT_MAX_VIEWS views) at a time into the context's scratch ([images | records | material planes]), each copied out
-// behind its launch on the context's stream before the next group reuses the scratch: device memory stays bounded by one group.  The destinations
-// are page-locked for the call while the first group renders (like ft_render_views'), so the copies run at link rate; a group's copy and the next
-// group's render share the stream, one after the other.
+// EXTENSION: one launch group (<= FT_MAX_VIEWS views) at a time into the context's scratch, each copied out behind its launch on the context's
+// stream before the next group reuses the scratch: device memory stays bounded by one group.  The destinations are page-locked for the call
+// while the first group renders (like ft_render_views'), so the copies run at link rate; a group's copy and the next group's render share the
+// stream, one after the other.
 int ft_render_views_hits(ft_ctx* c, const ft_scene* s, const ft_camera* cameras, int32_t n, const ft_render_params* p, float* out_rgb,
                          ft_object_trace_result* out_hits, int32_t* out_material, ft_stats* st) {
-    static_assert(sizeof(ft_object_trace_result) == 64, "layout");
-    int rc = checkViewsHits(c, cameras, n, p, out_rgb, out_hits, out_material); if (rc) return rc;
-    if (!out_hits && !out_material) return ft_render_views(c, s, cameras, n, p, out_rgb, st);         // the frames alone
+    const Outputs host{out_rgb, out_hits, out_material};
+    int rc = checkOutputs(host, false); if (rc) return rc;
+    if ((rc = checkViews(c, cameras, n, p, host))) return rc;
+    if (!host.extra()) return ft_render_views(c, s, cameras, n, p, out_rgb, st);                      // the frames alone: staged as a whole batch
     if (n == 1) return ft_render_hits(c, s, cameras, p, out_rgb, out_hits, out_material, st);         // exactly ft_render_hits
-    const size_t px = (size_t)p->n_columns * (size_t)p->height, g = (size_t)std::min<int32_t>(n, FT_MAX_VIEWS);
-    const size_t oHits = align256(out_rgb ? g * px * 12 : 0), oMat = oHits + align256(out_hits ? g * px * 64 : 0);
-    if ((rc = ensureScratch(c, oMat + (out_material ? g * px * 4 : 0)))) return rc;
-    unsigned char* base = static_cast<unsigned char*>(c->scratch);
-    hipError_t err = hipSuccess;
-    void* const dst[3] = {out_rgb, out_hits, out_material};
-    const size_t dstBytes[3] = {(size_t)n * px * 12, (size_t)n * px * 64, (size_t)n * px * 4};
-    bool pinnedHere[3] = {false, false, false};
-    for (int32_t k0 = 0; k0 < n && !rc && err == hipSuccess; k0 += FT_MAX_VIEWS) {
-        const size_t m = (size_t)std::min<int32_t>(FT_MAX_VIEWS, n - k0), k = (size_t)k0;
-        rc = ft_render_views_hits_device(c, s, cameras + k0, (int32_t)m, p, out_rgb ? base : nullptr, out_hits ? base + oHits : nullptr,
-                                         out_material ? base + oMat : nullptr);
-        if (!rc && k0 == 0)                                            // the GPU renders the first group: page-lock the destinations meanwhile
-            for (int i = 0; i < 3; ++i) if (dst[i]) pinnedHere[i] = pinForCall(c, dst[i], dstBytes[i]);
-        if (!rc && out_rgb) err = hipMemcpyAsync(out_rgb + k * px * 3, base, m * px * 12, hipMemcpyDeviceToHost, c->stream);
-        if (!rc && err == hipSuccess && out_hits) err = hipMemcpyAsync(out_hits + k * px, base + oHits, m * px * 64, hipMemcpyDeviceToHost, c->stream);
-        if (!rc && err == hipSuccess && out_material) err = hipMemcpyAsync(out_material + k * px, base + oMat, m * px * 4, hipMemcpyDeviceToHost, c->stream);
+    const size_t px = (size_t)p->n_columns * (size_t)p->height;
+    HostStaging stage(c, "ft_render_views_hits", host, 12, true);
+    if ((rc = stage.plan(0, (size_t)std::min<int32_t>(n, FT_MAX_VIEWS) * px))) return rc;
+    for (int32_t k0 = 0; k0 < n && stage.ok(); k0 += FT_MAX_VIEWS) {
+        const int32_t m = std::min<int32_t>(FT_MAX_VIEWS, n - k0);
+        stage.copyOut(launchFrame(c, s, FrameRequest{cameras + k0, m, p, stage.dev()}), (size_t)k0 * px, (size_t)m * px, (size_t)n * px);
     }
-    const hipError_t se = hipStreamSynchronize(c->stream);             // nothing of this call is left in flight, whatever happened
-    for (int i = 0; i < 3; ++i) if (pinnedHere[i]) (void)hipHostUnregister(dst[i]);
-    if (rc) return rc;
-    if (err != hipSuccess) return hipFail(err, "ft_render_views_hits host output");
-    if (se != hipSuccess) return hipFail(se, "ft_render_views_hits");
-    return ft_collect_stats(c, st);
+    return stage.finish(st);
 }
 
 // ---- tone map: Image.toColors / toBitmap order on the device ---------------------------------
@@ -1053,103 +1069,91 @@ int ft_render_colors(ft_ctx* c, const ft_scene* s, const ft_camera* cam, const f
     // lanes are done — its normalisation needs every pixel — and only the bytes are copied out
     ChunkPlan plan;
     const size_t outBytes = (size_t)p->width * p->height * 3;
-    bool pinnedHere = false;
-    auto finish = [&](int code) { if (c->copyStream) drainPipeline(c); if (pinnedHere) (void)hipHostUnregister(out); return code; };
-    if ((rc = launchChunks(c, s, cam, p, plan))) return finish(rc);
-    pinnedHere = pinForCall(c, out, outBytes);
+    ChunkedCall call{c};
+    if ((rc = launchChunks(c, s, cam, p, plan))) return rc;
+    call.pin(out, outBytes);
     hipError_t err = hipSuccess;
     for (int i = 0; i < plan.n && err == hipSuccess; ++i) err = hipStreamWaitEvent(c->stream, c->syncEvents[2 + i], 0);
-    if (err != hipSuccess) return finish(hipFail(err, "ft_render_colors"));
-    if ((rc = ft_tone_map(c, c->scratch, p->width, p->height, tm, out, max_out))) return finish(rc);
-    if (pinnedHere) { (void)hipHostUnregister(out); pinnedHere = false; }
+    if (err != hipSuccess) return hipFail(err, "ft_render_colors");
+    if ((rc = ft_tone_map(c, c->scratch, p->width, p->height, tm, out, max_out))) return rc;
+    call.waitedFor = true;
     return ft_collect_stats(c, st);
 }
 
 // ---- ray buffers ------------------------------------------------------------------------------------
-// mode 1: SdfScene.trace (3 floats per ray); 2: SdfForm.tryTrace (10 dwords); 3: SdfObject.tryTrace (16 dwords).  Everything is device memory: the
-// kernel reads d_rays and writes the caller's buffers on the context's stream, with no scratch, no copy and no synchronisation.
-//   mode 1: out (may be NULL: hits only) and, EXTENSION builds, hits / material: the mode-3 record and the material handle of every ray (ft_trace_rays_hits)
-//   mode 2: out;   mode 3: out and, optionally, material
-struct RayOuts { void* out; void* hits; void* material; };
+// The kernel knows two kinds of ray buffer: SdfScene.trace, which in the EXTENSION builds can also store every ray's SdfObject.tryTrace record and
+// material handle, or only those, without shading; and SdfForm.tryTrace, whose 10-dword results take the colours' place.  SdfObject.tryTrace
+// itself is the first kind asked for its records, which it cannot do without.
+enum class RayKind { Trace, Form, Object };
 
-static int launchRayBuffer(ft_ctx* c, const ft_scene* s, const void* d_rays, int64_t n, uint32_t mode, const RayOuts& o) {
+namespace {
+
+// Everything is device memory: the kernel reads d_rays and writes the caller's buffers on the context's stream, with no scratch, no copy and
+// no synchronisation.  The device is asked for first, then the arguments.
+int launchRayBuffer(ft_ctx* c, const ft_scene* s, const void* d_rays, int64_t n, RayKind kind, const Outputs& o) {
     int rc = requireDevice(c); if (rc) return rc;
     if (!s || s->ctx != c || !d_rays || n < 0) return setErr(FT_ERR_INVALID, "bad argument (scene must belong to this context)");
-    if (mode == 1 ? (!o.out && !o.hits && !o.material) : !o.out) return setErr(FT_ERR_INVALID, "ray buffer: no output asked for");
-    const uintptr_t rec = reinterpret_cast<uintptr_t>(mode == 3 ? o.out : o.hits), word = reinterpret_cast<uintptr_t>(mode == 3 ? nullptr : o.out);
-    if ((reinterpret_cast<uintptr_t>(d_rays) & 15u) || (rec & 15u) || (word & 3u) || (reinterpret_cast<uintptr_t>(o.material) & 3u))
-        return setErr(FT_ERR_INVALID, "ray buffer: the rays and the ft_object_trace_result records must be 16-byte aligned, every other buffer 4-byte aligned");
-    if (d_rays == o.out || d_rays == o.hits || d_rays == o.material) return setErr(FT_ERR_INVALID, "ray buffer: input and output must not overlap");
+    if ((rc = checkOutputs(o, true))) return rc;
+    if (kind == RayKind::Object && !o.hits) return setErr(FT_ERR_INVALID, "ray buffer: no output asked for");
+    if (reinterpret_cast<uintptr_t>(d_rays) & 15u) return setErr(FT_ERR_INVALID, "ray buffer: the rays must be 16-byte aligned");
+    if (d_rays == o.rgb || d_rays == o.hits || d_rays == o.material) return setErr(FT_ERR_INVALID, "ray buffer: input and output must not overlap");
     if (n == 0) return FT_OK;
     if (n >= 0xFFFF0000ll) return setErr(FT_ERR_UNSUPPORTED, "more than 2^32 rays in one call");
-    // The kernel knows two kinds of ray buffer: SdfScene.trace (mode 1), which in the EXTENSION builds can also store every ray's SdfObject.tryTrace record
-    // and material handle (hits = 1) or only those, without shading (hits = 2: SdfObject.tryTrace itself); and SdfForm.tryTrace (mode 2, EXTENSION builds)
     FtRenderArgs a{};
-    a.mode = mode == 2 ? 2u : 1u; a.rays = static_cast<const ft_ray*>(d_rays);
+    a.mode = kind == RayKind::Form ? 2u : 1u; a.rays = static_cast<const ft_ray*>(d_rays);
     a.nJobs = (uint32_t)n; a.stripeW = 1; a.stripeRanks = 1; a.tilesY = 1; a.H = 1; a.W = 1; a.nCols = 1; a.maxSize = 1.0f;
     a.spp = 1; a.sppN = 1; a.jobsPerPlane = a.nJobs; a.planePixels = a.nJobs;
-    if (mode == 3) { a.ext = 1u; a.hits = 2u; a.hitsOut = static_cast<float*>(o.out); }
-    else {
-        a.out = static_cast<float*>(o.out);
-        a.ext = (mode == 2 || o.hits || o.material) ? 1u : 0u;         // plain SdfScene.trace stays on the reference kernels (carved ones included)
-        if (o.hits || o.material) { a.hits = o.out ? 1u : 2u; a.hitsOut = static_cast<float*>(o.hits); }
-    }
+    // the same rules as a frame's (frameArgs): the hit buffers exist in the EXTENSION builds only, and plain SdfScene.trace stays on the
+    // reference kernels (carved ones included)
+    a.out = static_cast<float*>(o.rgb);
+    a.ext = (kind == RayKind::Form || o.extra()) ? 1u : 0u;
+    if (o.extra()) { a.hits = o.rgb ? 1u : 2u; a.hitsOut = static_cast<float*>(o.hits); }
     a.matOut = static_cast<int32_t*>(o.material); a.matHandles = s->dMatHandles;
     return launchTrace(c, s, a);
 }
 
-int ft_trace_rays_device(ft_ctx* c, const ft_scene* s, const void* d_rays, int64_t n, void* d_out_rgb) {
-    return launchRayBuffer(c, s, d_rays, n, 1, RayOuts{d_out_rgb, nullptr, nullptr});
-}
-int ft_form_try_trace_device(ft_ctx* c, const ft_scene* s, const void* d_rays, int64_t n, void* d_out) {
-    return launchRayBuffer(c, s, d_rays, n, 2, RayOuts{d_out, nullptr, nullptr});
-}
-int ft_object_try_trace_device(ft_ctx* c, const ft_scene* s, const void* d_rays, int64_t n, void* d_out, void* d_material) {
-    return launchRayBuffer(c, s, d_rays, n, 3, RayOuts{d_out, nullptr, d_material});
-}
-int ft_trace_rays_hits_device(ft_ctx* c, const ft_scene* s, const void* d_rays, int64_t n, void* d_out_rgb, void* d_hits, void* d_material) {
-    return launchRayBuffer(c, s, d_rays, n, 1, RayOuts{d_out_rgb, d_hits, d_material});
-}
-
-// The host forms: rays up into the context's scratch ([rays | out | records | material plane], each part 256-byte aligned), the device form,
-// every output asked for down again; nothing of the call is left in flight when it returns.
-static int traceRayBuffer(ft_ctx* c, const ft_scene* s, const ft_ray* rays, int64_t n, uint32_t mode, void* out, void* hits, void* material, ft_stats* st) {
+// The host forms: rays up into the context's scratch, the device form, every output asked for down again (HostStaging; the destinations are
+// not pinned); nothing of the call is left in flight when it returns.
+int traceRayBuffer(ft_ctx* c, const ft_scene* s, const ft_ray* rays, int64_t n, RayKind kind, const Outputs& host, ft_stats* st) {
     static_assert(sizeof(ft_ray) == 32 && sizeof(ft_form_trace_result) == 40 && sizeof(ft_object_trace_result) == 64, "layout");
     int rc = requireDevice(c); if (rc) return rc;
-    if (!s || s->ctx != c || !rays || (!out && !hits && !material) || n < 0) return setErr(FT_ERR_INVALID, "bad argument");
+    if (!s || s->ctx != c || !rays || !host.any() || n < 0) return setErr(FT_ERR_INVALID, "bad argument");
     if (n == 0) { if (st) memset(st, 0, sizeof(*st)); return FT_OK; }
     if (n >= 0xFFFF0000ll) return setErr(FT_ERR_UNSUPPORTED, "more than 2^32 rays in one call");
-    const size_t perRay = mode == 1 ? 3 : mode == 2 ? 10 : 16;
-    const size_t rayBytes = (size_t)n * sizeof(ft_ray), outBytes = out ? (size_t)n * perRay * sizeof(float) : 0;
-    const size_t hitBytes = hits ? (size_t)n * 64 : 0, matBytes = material ? (size_t)n * 4 : 0;
-    const size_t oOut = align256(rayBytes), oHits = oOut + align256(outBytes), oMat = oHits + align256(hitBytes);
-    if ((rc = ensureScratch(c, oMat + matBytes))) return rc;
-    unsigned char* base = static_cast<unsigned char*>(c->scratch);
-    HIP_TRY(hipMemcpyAsync(base, rays, rayBytes, hipMemcpyHostToDevice, c->stream));
-    rc = launchRayBuffer(c, s, base, n, mode, RayOuts{out ? base + oOut : nullptr, hits ? base + oHits : nullptr, material ? base + oMat : nullptr});
-    hipError_t err = hipSuccess;
-    if (!rc && out) err = hipMemcpyAsync(out, base + oOut, outBytes, hipMemcpyDeviceToHost, c->stream);
-    if (!rc && err == hipSuccess && hits) err = hipMemcpyAsync(hits, base + oHits, hitBytes, hipMemcpyDeviceToHost, c->stream);
-    if (!rc && err == hipSuccess && material) err = hipMemcpyAsync(material, base + oMat, matBytes, hipMemcpyDeviceToHost, c->stream);
-    const hipError_t se = hipStreamSynchronize(c->stream);     // the scratch is reused: nothing of this call stays in flight, whatever happened
-    if (rc) return rc;
-    if (err != hipSuccess) return hipFail(err, "ray buffer host output");
-    if (se != hipSuccess) return hipFail(se, "ray buffer");
-    return ft_collect_stats(c, st);
+    HostStaging stage(c, "ray buffer", host, kind == RayKind::Form ? sizeof(ft_form_trace_result) : 12, false);
+    if ((rc = stage.plan((size_t)n * sizeof(ft_ray), (size_t)n))) return rc;
+    HIP_TRY(hipMemcpyAsync(stage.input(), rays, (size_t)n * sizeof(ft_ray), hipMemcpyHostToDevice, c->stream));
+    stage.copyOut(launchRayBuffer(c, s, stage.input(), n, kind, stage.dev()), 0, (size_t)n, (size_t)n);
+    return stage.finish(st);
+}
+
+}  // namespace
+
+int ft_trace_rays_device(ft_ctx* c, const ft_scene* s, const void* d_rays, int64_t n, void* d_out_rgb) {
+    return launchRayBuffer(c, s, d_rays, n, RayKind::Trace, Outputs{d_out_rgb, nullptr, nullptr});
+}
+int ft_form_try_trace_device(ft_ctx* c, const ft_scene* s, const void* d_rays, int64_t n, void* d_out) {
+    return launchRayBuffer(c, s, d_rays, n, RayKind::Form, Outputs{d_out, nullptr, nullptr});
+}
+int ft_object_try_trace_device(ft_ctx* c, const ft_scene* s, const void* d_rays, int64_t n, void* d_out, void* d_material) {
+    return launchRayBuffer(c, s, d_rays, n, RayKind::Object, Outputs{nullptr, d_out, d_material});
+}
+int ft_trace_rays_hits_device(ft_ctx* c, const ft_scene* s, const void* d_rays, int64_t n, void* d_out_rgb, void* d_hits, void* d_material) {
+    return launchRayBuffer(c, s, d_rays, n, RayKind::Trace, Outputs{d_out_rgb, d_hits, d_material});
 }
 
 int ft_trace_rays(ft_ctx* c, const ft_scene* s, const ft_ray* rays, int64_t n, float* out, ft_stats* st) {
-    return traceRayBuffer(c, s, rays, n, 1, out, nullptr, nullptr, st);
+    return traceRayBuffer(c, s, rays, n, RayKind::Trace, Outputs{out, nullptr, nullptr}, st);
 }
 int ft_form_try_trace(ft_ctx* c, const ft_scene* s, const ft_ray* rays, int64_t n, ft_form_trace_result* out, ft_stats* st) {
-    return traceRayBuffer(c, s, rays, n, 2, out, nullptr, nullptr, st);
+    return traceRayBuffer(c, s, rays, n, RayKind::Form, Outputs{out, nullptr, nullptr}, st);
 }
 int ft_object_try_trace(ft_ctx* c, const ft_scene* s, const ft_ray* rays, int64_t n, ft_object_trace_result* out, ft_stats* st) {
-    return traceRayBuffer(c, s, rays, n, 3, out, nullptr, nullptr, st);
+    return traceRayBuffer(c, s, rays, n, RayKind::Object, Outputs{nullptr, out, nullptr}, st);
 }
 int ft_trace_rays_hits(ft_ctx* c, const ft_scene* s, const ft_ray* rays, int64_t n, float* out_rgb, ft_object_trace_result* out_hits,
                        int32_t* out_material, ft_stats* st) {
-    return traceRayBuffer(c, s, rays, n, 1, out_rgb, out_hits, out_material, st);
+    return traceRayBuffer(c, s, rays, n, RayKind::Trace, Outputs{out_rgb, out_hits, out_material}, st);
 }
 
 int ft_eval_distance(ft_ctx* c, const ft_scene* s, const ft_vec3* pts, int64_t n, float* outD, int32_t* outM) {

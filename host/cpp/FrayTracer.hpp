@@ -116,38 +116,52 @@ inline ft_camera lookAt(const LookAt& c) {
 }
 struct ImageSize { int X, Y; };
 
+// The ft_scene of one call: realised from an SdfScene — or from an object alone, in front of a black background and without lights, for tryTrace /
+// formTryTrace — and destroyed on every path out of the call, exceptions included.
+class SceneOfCall {
+public:
+    explicit SceneOfCall(const SdfScene& scene) : ctx(scene.Object.ctx) {
+        std::vector<ft_handle> lights; for (auto& l : scene.Lights) lights.push_back(l.Node);
+        check(ft_scene_create(ctx, scene.Object.Node, &scene.BackgroundColor.v.x, lights.data(), (int)lights.size(), &s_));
+    }
+    explicit SceneOfCall(const SdfObjectV& object) : ctx(object.ctx) {
+        const float black[3] = {0.0f, 0.0f, 0.0f};
+        check(ft_scene_create(ctx, object.Node, black, nullptr, 0, &s_));
+    }
+    ~SceneOfCall() { ft_scene_destroy(s_); }
+    SceneOfCall(const SceneOfCall&) = delete;
+    SceneOfCall& operator=(const SceneOfCall&) = delete;
+    ft_scene* get() const { return s_; }
+    // the end of every call: the error, if any, as an exception; the statistics to the caller who asked for them
+    void done(int rc, ft_stats* stats) const { check(rc); if (stats) *stats = st; }
+    ft_ctx* const ctx;
+    ft_stats st{};
+private:
+    ft_scene* s_ = nullptr;
+};
+// the reference's parameters of a whole frame: every column, one rank, no EXTENSION
+inline ft_render_params frameParams(float epsilon, float length, ImageSize size) {
+    return ft_render_params{size.X, size.Y, 0, size.X, size.X, 1, 0, 1, epsilon, length, 0, 0.0f, 0, 0};
+}
+
 namespace Image {
 // FColor[X,Y] as a flat vector, x-major / y contiguous (Array2D.fs:30-38): element (x, y) at 3 * (x * Y + y)
 inline std::vector<float> renderScene(float epsilon, float length, ImageSize size, const ft_camera& camera, const SdfScene& scene,
                                       ft_stats* stats = nullptr) {
-    ft_ctx* ctx = scene.Object.ctx;
-    std::vector<ft_handle> lights; for (auto& l : scene.Lights) lights.push_back(l.Node);
-    ft_scene* s = nullptr;
-    check(ft_scene_create(ctx, scene.Object.Node, &scene.BackgroundColor.v.x, lights.data(), (int)lights.size(), &s));
+    SceneOfCall s(scene);
     std::vector<float> out((size_t)size.X * size.Y * 3);
-    ft_render_params p{size.X, size.Y, 0, size.X, size.X, 1, 0, 1, epsilon, length, 0, 0.0f, 0, 0};
-    ft_stats st{};
-    int rc = ft_render(ctx, s, &camera, &p, out.data(), &st);
-    ft_scene_destroy(s);
-    check(rc);
-    if (stats) *stats = st;
+    const ft_render_params p = frameParams(epsilon, length, size);
+    s.done(ft_render(s.ctx, s.get(), &camera, &p, out.data(), &s.st), stats);
     return out;
 }
 // renderScene of one scene from every camera of `cameras` in one launch: image k at 3 * (k * X * Y + x * Y + y), bit for bit renderScene's
 // image for cameras[k]; stats of the whole batch
 inline std::vector<float> renderViews(float epsilon, float length, ImageSize size, const std::vector<ft_camera>& cameras, const SdfScene& scene,
                                       ft_stats* stats = nullptr) {
-    ft_ctx* ctx = scene.Object.ctx;
-    std::vector<ft_handle> lights; for (auto& l : scene.Lights) lights.push_back(l.Node);
-    ft_scene* s = nullptr;
-    check(ft_scene_create(ctx, scene.Object.Node, &scene.BackgroundColor.v.x, lights.data(), (int)lights.size(), &s));
+    SceneOfCall s(scene);
     std::vector<float> out(cameras.size() * (size_t)size.X * size.Y * 3);
-    ft_render_params p{size.X, size.Y, 0, size.X, size.X, 1, 0, 1, epsilon, length, 0, 0.0f, 0, 0};
-    ft_stats st{};
-    int rc = ft_render_views(ctx, s, cameras.data(), (int32_t)cameras.size(), &p, out.data(), &st);
-    ft_scene_destroy(s);
-    check(rc);
-    if (stats) *stats = st;
+    const ft_render_params p = frameParams(epsilon, length, size);
+    s.done(ft_render_views(s.ctx, s.get(), cameras.data(), (int32_t)cameras.size(), &p, out.data(), &s.st), stats);
     return out;
 }
 // EXTENSION: Image.render's pixel loop (Image.fs:26-35) over SdfObject.tryTrace scene.Object (SdfObject.fs:66-78) instead of SdfScene.trace —
@@ -155,55 +169,35 @@ inline std::vector<float> renderViews(float epsilon, float length, ImageSize siz
 // the handle of the material each hit picked (-1 on a miss).
 inline std::vector<ft_object_trace_result> renderHits(float epsilon, float length, ImageSize size, const ft_camera& camera, const SdfScene& scene,
                                                       std::vector<int32_t>* material = nullptr, ft_stats* stats = nullptr) {
-    ft_ctx* ctx = scene.Object.ctx;
-    std::vector<ft_handle> lights; for (auto& l : scene.Lights) lights.push_back(l.Node);
-    ft_scene* s = nullptr;
-    check(ft_scene_create(ctx, scene.Object.Node, &scene.BackgroundColor.v.x, lights.data(), (int)lights.size(), &s));
+    SceneOfCall s(scene);
     std::vector<ft_object_trace_result> out((size_t)size.X * size.Y);
     if (material) material->assign(out.size(), -1);
-    ft_render_params p{size.X, size.Y, 0, size.X, size.X, 1, 0, 1, epsilon, length, 0, 0.0f, 0, 0};
-    ft_stats st{};
-    int rc = ft_render_hits(ctx, s, &camera, &p, nullptr, out.data(), material ? material->data() : nullptr, &st);
-    ft_scene_destroy(s);
-    check(rc);
-    if (stats) *stats = st;
+    const ft_render_params p = frameParams(epsilon, length, size);
+    s.done(ft_render_hits(s.ctx, s.get(), &camera, &p, nullptr, out.data(), material ? material->data() : nullptr, &s.st), stats);
     return out;
 }
 // EXTENSION: renderHits of one scene from every camera of `cameras` in one launch: view k's record of pixel (x, y) at k * X * Y + x * Y + y,
 // bit for bit renderHits' record for cameras[k]; `material` likewise; stats of the whole batch
 inline std::vector<ft_object_trace_result> renderViewsHits(float epsilon, float length, ImageSize size, const std::vector<ft_camera>& cameras,
                                                            const SdfScene& scene, std::vector<int32_t>* material = nullptr, ft_stats* stats = nullptr) {
-    ft_ctx* ctx = scene.Object.ctx;
-    std::vector<ft_handle> lights; for (auto& l : scene.Lights) lights.push_back(l.Node);
-    ft_scene* s = nullptr;
-    check(ft_scene_create(ctx, scene.Object.Node, &scene.BackgroundColor.v.x, lights.data(), (int)lights.size(), &s));
+    SceneOfCall s(scene);
     std::vector<ft_object_trace_result> out(cameras.size() * (size_t)size.X * size.Y);
     if (material) material->assign(out.size(), -1);
-    ft_render_params p{size.X, size.Y, 0, size.X, size.X, 1, 0, 1, epsilon, length, 0, 0.0f, 0, 0};
-    ft_stats st{};
-    int rc = ft_render_views_hits(ctx, s, cameras.data(), (int32_t)cameras.size(), &p, nullptr, out.data(), material ? material->data() : nullptr, &st);
-    ft_scene_destroy(s);
-    check(rc);
-    if (stats) *stats = st;
+    const ft_render_params p = frameParams(epsilon, length, size);
+    s.done(ft_render_views_hits(s.ctx, s.get(), cameras.data(), (int32_t)cameras.size(), &p, nullptr, out.data(), material ? material->data() : nullptr, &s.st),
+           stats);
     return out;
 }
 // EXTENSION: SdfObject.tryTrace scene.Object of every ray of an explicit ray buffer (`rays |> Array.map (SdfObject.tryTrace scene.Object)`) and, if
 // `colors` is given, SdfScene.trace scene of the same rays (3 floats per ray) from the same launch (ft_trace_rays_hits); `material` as in renderHits
 inline std::vector<ft_object_trace_result> traceRaysHits(const std::vector<ft_ray>& rays, const SdfScene& scene, std::vector<float>* colors = nullptr,
                                                          std::vector<int32_t>* material = nullptr, ft_stats* stats = nullptr) {
-    ft_ctx* ctx = scene.Object.ctx;
-    std::vector<ft_handle> lights; for (auto& l : scene.Lights) lights.push_back(l.Node);
-    ft_scene* s = nullptr;
-    check(ft_scene_create(ctx, scene.Object.Node, &scene.BackgroundColor.v.x, lights.data(), (int)lights.size(), &s));
+    SceneOfCall s(scene);
     std::vector<ft_object_trace_result> out(rays.size());
     if (colors) colors->assign(rays.size() * 3, 0.0f);
     if (material) material->assign(rays.size(), -1);
-    ft_stats st{};
-    int rc = ft_trace_rays_hits(ctx, s, rays.data(), (int64_t)rays.size(), colors ? colors->data() : nullptr, out.data(),
-                                material ? material->data() : nullptr, &st);
-    ft_scene_destroy(s);
-    check(rc);
-    if (stats) *stats = st;
+    s.done(ft_trace_rays_hits(s.ctx, s.get(), rays.data(), (int64_t)rays.size(), colors ? colors->data() : nullptr, out.data(),
+                              material ? material->data() : nullptr, &s.st), stats);
     return out;
 }
 // Image.toColors gamma rng image (Image.fs:37-50) on the GPU: bytes in Color[X,Y] order (R,G,B) or, with bmpOrder, in the scan-line
@@ -218,23 +212,15 @@ inline std::vector<unsigned char> toColors(ft_ctx* ctx, float gamma, long long s
 
 // SdfObject.tryTrace / SdfForm.tryTrace (SdfObject.fs:66-78, SdfForm.fs:93-104) over a ray buffer; hit == 0 is ValueNone
 inline std::vector<ft_object_trace_result> tryTrace(const SdfObjectV& object, const std::vector<ft_ray>& rays) {
-    const float bg[3] = {0.0f, 0.0f, 0.0f};
-    ft_scene* s = nullptr;
-    check(ft_scene_create(object.ctx, object.Node, bg, nullptr, 0, &s));
+    SceneOfCall s(object);
     std::vector<ft_object_trace_result> out(rays.size());
-    int rc = ft_object_try_trace(object.ctx, s, rays.data(), (int64_t)rays.size(), out.data(), nullptr);
-    ft_scene_destroy(s);
-    check(rc);
+    s.done(ft_object_try_trace(s.ctx, s.get(), rays.data(), (int64_t)rays.size(), out.data(), nullptr), nullptr);
     return out;
 }
 inline std::vector<ft_form_trace_result> formTryTrace(const SdfObjectV& object, const std::vector<ft_ray>& rays) {
-    const float bg[3] = {0.0f, 0.0f, 0.0f};
-    ft_scene* s = nullptr;
-    check(ft_scene_create(object.ctx, object.Node, bg, nullptr, 0, &s));
+    SceneOfCall s(object);
     std::vector<ft_form_trace_result> out(rays.size());
-    int rc = ft_form_try_trace(object.ctx, s, rays.data(), (int64_t)rays.size(), out.data(), nullptr);
-    ft_scene_destroy(s);
-    check(rc);
+    s.done(ft_form_try_trace(s.ctx, s.get(), rays.data(), (int64_t)rays.size(), out.data(), nullptr), nullptr);
     return out;
 }
 

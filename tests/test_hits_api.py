@@ -1,46 +1,30 @@
 """Per-pixel hit buffers (ft_render_hits / ft_render_hits_device): the parts that need no GPU — the ABI, the host-only refusal, the
 PixelHits views over oracle records of pixel rays, and the C++ mirror's renderHits."""
 import ctypes as C
-import os
-import re
-import subprocess
 
 import numpy as np
-import pytest
 
 import fraytracer_amd as ft
 from fraytracer_amd import _lib
 from fraytracer_amd import synthetic as syn
+from helpers import assert_cpp_compiles, assert_declared_exported_bound, dev_ptr, host_ctx, host_ptr, render_params  # noqa: F401  (host_ctx: a fixture)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "fraytracer_hip.h")
 EPS, LEN = syn.EPSILON, syn.RAY_LENGTH
 
 
 def test_symbols_are_declared_exported_and_bound():
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    out = subprocess.check_output(["nm", "-D", "--defined-only", _lib.LIB_PATH], text=True)
-    for name in ("ft_render_hits", "ft_render_hits_device"):
-        assert re.search(r"\b" + name + r"\s*\(", text), name
-        assert re.search(r"\bT " + name + r"\b", out), name
-        assert name in _lib.SYMBOLS
-        getattr(_lib.lib, name)
+    assert_declared_exported_bound(("ft_render_hits", "ft_render_hits_device"))
 
 
-def test_host_only_context_has_no_hit_buffers():
-    ctx = C.c_void_p()
-    _lib.check(_lib.lib.ft_ctx_create(-1, C.byref(ctx)))
-    try:
-        cam = _lib.CameraS()
-        p = _lib.RenderParams(8, 8, 0, 8, 8, 1, 0, 1, EPS, LEN, 0, 0.0, 0, 0)
-        hits = np.empty((8, 8, 16), np.float32)
-        st = _lib.Stats()
-        rc = _lib.lib.ft_render_hits(ctx, None, C.byref(cam), C.byref(p), None, hits.ctypes.data_as(C.c_void_p), None, C.byref(st))
-        assert rc == _lib.FT_ERR_NO_DEVICE
-        rc = _lib.lib.ft_render_hits_device(ctx, None, C.byref(cam), C.byref(p), None, C.c_void_p(256), None)
-        assert rc == _lib.FT_ERR_NO_DEVICE
-    finally:
-        _lib.lib.ft_ctx_destroy(ctx)
+def test_host_only_context_has_no_hit_buffers(host_ctx):
+    cam = _lib.CameraS()
+    p = render_params()
+    hits = np.empty((8, 8, 16), np.float32)
+    st = _lib.Stats()
+    rc = _lib.lib.ft_render_hits(host_ctx, None, C.byref(cam), C.byref(p), None, host_ptr(hits), None, C.byref(st))
+    assert rc == _lib.FT_ERR_NO_DEVICE
+    rc = _lib.lib.ft_render_hits_device(host_ctx, None, C.byref(cam), C.byref(p), None, dev_ptr(256), None)
+    assert rc == _lib.FT_ERR_NO_DEVICE
 
 
 def test_pixel_hits_views_over_oracle_records(oracle):
@@ -66,10 +50,7 @@ def test_pixel_hits_views_over_oracle_records(oracle):
 
 
 def test_cpp_render_hits_compiles(tmp_path):
-    src = tmp_path / "hits.cpp"
-    src.write_text('#include "FrayTracer.hpp"\n'
-                   "std::vector<ft_object_trace_result> f(const FrayTracer::SdfScene& s, const ft_camera& c, std::vector<int32_t>* m) {\n"
-                   "    return FrayTracer::Image::renderHits(0.01f, 100.0f, FrayTracer::ImageSize{64, 48}, c, s, m);\n"
-                   "}\n")
-    cxx = os.environ.get("CXX", "g++")
-    subprocess.check_call([cxx, "-std=c++17", "-fsyntax-only", "-I", os.path.join(ROOT, "host", "cpp"), "-I", os.path.join(ROOT, "include"), str(src)])
+    assert_cpp_compiles(tmp_path, "hits.cpp",
+                        "std::vector<ft_object_trace_result> f(const FrayTracer::SdfScene& s, const ft_camera& c, std::vector<int32_t>* m) {\n"
+                        "    return FrayTracer::Image::renderHits(0.01f, 100.0f, FrayTracer::ImageSize{64, 48}, c, s, m);\n"
+                        "}\n")

@@ -12,21 +12,14 @@ import pytest
 import fraytracer_amd as ft
 from fraytracer_amd import _lib, api
 from fraytracer_amd import synthetic as syn
+from helpers import HEADER, ROOT, assert_cpp_compiles, assert_declared_exported_bound, dev_ptr as _p, host_ctx, host_ptr as ptr  # noqa: F401  (host_ctx: a fixture)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "fraytracer_hip.h")
 EPS, LEN = syn.EPSILON, syn.RAY_LENGTH
 NAMES = ("ft_trace_rays_device", "ft_form_try_trace_device", "ft_object_try_trace_device", "ft_trace_rays_hits", "ft_trace_rays_hits_device")
 
 
 def test_symbols_are_declared_exported_and_bound():
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    out = subprocess.check_output(["nm", "-D", "--defined-only", _lib.LIB_PATH], text=True)
-    for name in NAMES:
-        assert re.search(r"\b" + name + r"\s*\(", text), name
-        assert re.search(r"\bT " + name + r"\b", out), name
-        assert name in _lib.SYMBOLS
-        getattr(_lib.lib, name)
+    assert_declared_exported_bound(NAMES)
 
 
 def test_abi_version_is_unchanged():
@@ -52,18 +45,6 @@ def test_header_states_the_contract():
     assert m and "ft_object_try_trace" in m.group(0) and "-1 on a miss" in m.group(0)
 
 
-@pytest.fixture
-def host_ctx():
-    ctx = C.c_void_p()
-    _lib.check(_lib.lib.ft_ctx_create(-1, C.byref(ctx)))
-    yield ctx
-    _lib.lib.ft_ctx_destroy(ctx)
-
-
-def _p(a):
-    return None if a is None else C.c_void_p(a)
-
-
 def test_host_only_context_traces_no_ray_buffer(host_ctx):
     L = _lib.lib
     assert L.ft_trace_rays_device(host_ctx, None, _p(256), 4, _p(1024)) == _lib.FT_ERR_NO_DEVICE
@@ -75,7 +56,6 @@ def test_host_only_context_traces_no_ray_buffer(host_ctx):
     rays = np.zeros((4, 8), np.float32)
     rgb, rec, mat = np.empty((4, 3), np.float32), np.empty((4, 16), np.float32), np.empty(4, np.int32)
     st = _lib.Stats()
-    ptr = lambda a: a.ctypes.data_as(C.c_void_p)
     assert L.ft_trace_rays_hits(host_ctx, None, ptr(rays), 4, ptr(rgb), ptr(rec), ptr(mat), C.byref(st)) == _lib.FT_ERR_NO_DEVICE
     assert L.ft_trace_rays_hits(host_ctx, None, ptr(rays), 4, None, ptr(rec), None, C.byref(st)) == _lib.FT_ERR_NO_DEVICE
     for fn in (L.ft_trace_rays_device, L.ft_form_try_trace_device):
@@ -134,14 +114,11 @@ def test_pixel_hits_over_a_ray_buffer(oracle):
 
 
 def test_cpp_trace_rays_hits_compiles(tmp_path):
-    src = tmp_path / "rays_hits.cpp"
-    src.write_text('#include "FrayTracer.hpp"\n'
-                   "std::vector<ft_object_trace_result> f(const FrayTracer::SdfScene& s, const std::vector<ft_ray>& r, std::vector<float>* c,\n"
-                   "                                      std::vector<int32_t>* m, ft_stats* st) {\n"
-                   "    return FrayTracer::Image::traceRaysHits(r, s, c, m, st);\n"
-                   "}\n")
-    cxx = os.environ.get("CXX", "g++")
-    subprocess.check_call([cxx, "-std=c++17", "-fsyntax-only", "-I", os.path.join(ROOT, "host", "cpp"), "-I", os.path.join(ROOT, "include"), str(src)])
+    assert_cpp_compiles(tmp_path, "rays_hits.cpp",
+                        "std::vector<ft_object_trace_result> f(const FrayTracer::SdfScene& s, const std::vector<ft_ray>& r, std::vector<float>* c,\n"
+                        "                                      std::vector<int32_t>* m, ft_stats* st) {\n"
+                        "    return FrayTracer::Image::traceRaysHits(r, s, c, m, st);\n"
+                        "}\n")
 
 
 def test_fsharp_binding_imports_the_ray_buffer_forms():

@@ -3,44 +3,23 @@ any device work, the Python argument checks and the C++ mirror's renderViews."""
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
-import pytest
 
 import fraytracer_amd as ft
 from fraytracer_amd import _lib
 from fraytracer_amd import synthetic as syn
+from helpers import HEADER, ROOT, assert_cpp_compiles, assert_declared_exported_bound, dev_ptr, host_ctx, host_ptr, render_params as _params  # noqa: F401  (host_ctx: a fixture)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "fraytracer_hip.h")
 EPS, LEN = syn.EPSILON, syn.RAY_LENGTH
 
 
 def test_symbols_are_declared_exported_and_bound():
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    out = subprocess.check_output(["nm", "-D", "--defined-only", _lib.LIB_PATH], text=True)
-    for name in ("ft_render_views", "ft_render_views_device"):
-        assert re.search(r"\b" + name + r"\s*\(", text), name
-        assert re.search(r"\bT " + name + r"\b", out), name
-        assert name in _lib.SYMBOLS
-        getattr(_lib.lib, name)
+    assert_declared_exported_bound(("ft_render_views", "ft_render_views_device"))
 
 
 def test_abi_version_is_unchanged():
     assert _lib.lib.ft_abi_version() == 5
-
-
-@pytest.fixture
-def host_ctx():
-    ctx = C.c_void_p()
-    _lib.check(_lib.lib.ft_ctx_create(-1, C.byref(ctx)))
-    yield ctx
-    _lib.lib.ft_ctx_destroy(ctx)
-
-
-def _params(w=8, h=8, spp=1):
-    return _lib.RenderParams(w, h, 0, w, w, 1, 0, spp, EPS, LEN, 0, 0.0, 0, 0)
 
 
 def test_host_only_context_renders_no_views(host_ctx):
@@ -48,9 +27,9 @@ def test_host_only_context_renders_no_views(host_ctx):
     p = _params()
     out = np.empty((3, 8, 8, 3), np.float32)
     st = _lib.Stats()
-    rc = _lib.lib.ft_render_views(host_ctx, None, cams, 3, C.byref(p), out.ctypes.data_as(C.c_void_p), C.byref(st))
+    rc = _lib.lib.ft_render_views(host_ctx, None, cams, 3, C.byref(p), host_ptr(out), C.byref(st))
     assert rc == _lib.FT_ERR_NO_DEVICE
-    rc = _lib.lib.ft_render_views_device(host_ctx, None, cams, 3, C.byref(p), C.c_void_p(256))
+    rc = _lib.lib.ft_render_views_device(host_ctx, None, cams, 3, C.byref(p), dev_ptr(256))
     assert rc == _lib.FT_ERR_NO_DEVICE
 
 
@@ -59,13 +38,13 @@ def test_bad_batches_are_refused_before_device_work(host_ctx):
     cams = (_lib.CameraS * 2)()
     p = _params()
     out = np.empty((2, 8, 8, 3), np.float32)
-    o = out.ctypes.data_as(C.c_void_p)
+    o = host_ptr(out)
     st = _lib.Stats()
     for n in (0, -1):
         assert _lib.lib.ft_render_views(host_ctx, None, cams, n, C.byref(p), o, C.byref(st)) == _lib.FT_ERR_INVALID
-        assert _lib.lib.ft_render_views_device(host_ctx, None, cams, n, C.byref(p), C.c_void_p(256)) == _lib.FT_ERR_INVALID
+        assert _lib.lib.ft_render_views_device(host_ctx, None, cams, n, C.byref(p), dev_ptr(256)) == _lib.FT_ERR_INVALID
     assert _lib.lib.ft_render_views(host_ctx, None, None, 2, C.byref(p), o, C.byref(st)) == _lib.FT_ERR_INVALID
-    assert _lib.lib.ft_render_views_device(host_ctx, None, None, 2, C.byref(p), C.c_void_p(256)) == _lib.FT_ERR_INVALID
+    assert _lib.lib.ft_render_views_device(host_ctx, None, None, 2, C.byref(p), dev_ptr(256)) == _lib.FT_ERR_INVALID
     assert _lib.lib.ft_render_views(host_ctx, None, cams, 2, None, o, C.byref(st)) == _lib.FT_ERR_INVALID
     assert _lib.lib.ft_render_views(host_ctx, None, cams, 2, C.byref(p), None, C.byref(st)) == _lib.FT_ERR_INVALID
     assert _lib.lib.ft_render_views_device(host_ctx, None, cams, 2, C.byref(p), None) == _lib.FT_ERR_INVALID
@@ -80,13 +59,13 @@ def test_batch_job_limit_is_refused_before_device_work(host_ctx):
     many = (_lib.CameraS * 8)()
     big = _params(4096, 4096, 64)
     for n, want in ((3, _lib.FT_ERR_NO_DEVICE), (4, _lib.FT_ERR_UNSUPPORTED), (8, _lib.FT_ERR_UNSUPPORTED)):
-        assert _lib.lib.ft_render_views_device(host_ctx, None, many, n, C.byref(big), C.c_void_p(256)) == want, n
+        assert _lib.lib.ft_render_views_device(host_ctx, None, many, n, C.byref(big), dev_ptr(256)) == want, n
     # smaller frames, many views: 2^32 / (64^2 x 64) views of 64 x 64 at spp 64
     small = _params(64, 64, 64)
     n = (1 << 32) // (64 * 64 * 64)
     cams = (_lib.CameraS * n)()
-    assert _lib.lib.ft_render_views_device(host_ctx, None, cams, n, C.byref(small), C.c_void_p(256)) == _lib.FT_ERR_UNSUPPORTED
-    assert _lib.lib.ft_render_views_device(host_ctx, None, cams, n - 1, C.byref(small), C.c_void_p(256)) == _lib.FT_ERR_NO_DEVICE
+    assert _lib.lib.ft_render_views_device(host_ctx, None, cams, n, C.byref(small), dev_ptr(256)) == _lib.FT_ERR_UNSUPPORTED
+    assert _lib.lib.ft_render_views_device(host_ctx, None, cams, n - 1, C.byref(small), dev_ptr(256)) == _lib.FT_ERR_NO_DEVICE
 
 
 def test_header_documents_the_layout():
@@ -102,13 +81,10 @@ def test_python_api_has_the_batch_forms():
 
 
 def test_cpp_render_views_compiles(tmp_path):
-    src = tmp_path / "views.cpp"
-    src.write_text('#include "FrayTracer.hpp"\n'
-                   "std::vector<float> f(const FrayTracer::SdfScene& s, const std::vector<ft_camera>& c, ft_stats* st) {\n"
-                   "    return FrayTracer::Image::renderViews(0.01f, 100.0f, FrayTracer::ImageSize{64, 48}, c, s, st);\n"
-                   "}\n")
-    cxx = os.environ.get("CXX", "g++")
-    subprocess.check_call([cxx, "-std=c++17", "-fsyntax-only", "-I", os.path.join(ROOT, "host", "cpp"), "-I", os.path.join(ROOT, "include"), str(src)])
+    assert_cpp_compiles(tmp_path, "views.cpp",
+                        "std::vector<float> f(const FrayTracer::SdfScene& s, const std::vector<ft_camera>& c, ft_stats* st) {\n"
+                        "    return FrayTracer::Image::renderViews(0.01f, 100.0f, FrayTracer::ImageSize{64, 48}, c, s, st);\n"
+                        "}\n")
 
 
 def test_fsharp_binding_has_render_views():

@@ -3,56 +3,33 @@ refusals that come before any device work, PixelHits over stacked views, the C++
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
-import pytest
 
 import fraytracer_amd as ft
 from fraytracer_amd import _lib
 from fraytracer_amd import synthetic as syn
+from helpers import HEADER, ROOT, assert_cpp_compiles, assert_declared_exported_bound, dev_ptr, host_ctx, host_ptr, render_params as _params  # noqa: F401  (host_ctx: a fixture)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "fraytracer_hip.h")
 EPS, LEN = syn.EPSILON, syn.RAY_LENGTH
 NAMES = ("ft_render_views_hits", "ft_render_views_hits_device")
 
 
 def test_symbols_are_declared_exported_and_bound():
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    out = subprocess.check_output(["nm", "-D", "--defined-only", _lib.LIB_PATH], text=True)
-    for name in NAMES:
-        assert re.search(r"\b" + name + r"\s*\(", text), name
-        assert re.search(r"\bT " + name + r"\b", out), name
-        assert name in _lib.SYMBOLS
-        getattr(_lib.lib, name)
+    assert_declared_exported_bound(NAMES)
 
 
 def test_abi_version_is_unchanged():
     assert _lib.lib.ft_abi_version() == 5
 
 
-@pytest.fixture
-def host_ctx():
-    ctx = C.c_void_p()
-    _lib.check(_lib.lib.ft_ctx_create(-1, C.byref(ctx)))
-    yield ctx
-    _lib.lib.ft_ctx_destroy(ctx)
-
-
-def _params(w=8, h=8, spp=1):
-    return _lib.RenderParams(w, h, 0, w, w, 1, 0, spp, EPS, LEN, 0, 0.0, 0, 0)
-
-
 def _host(ctx, cams, n, p, rgb=None, hits=None, mat=None):
-    ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
     st = _lib.Stats()
-    return _lib.lib.ft_render_views_hits(ctx, None, cams, n, p, ptr(rgb), ptr(hits), ptr(mat), C.byref(st))
+    return _lib.lib.ft_render_views_hits(ctx, None, cams, n, p, host_ptr(rgb), host_ptr(hits), host_ptr(mat), C.byref(st))
 
 
 def _device(ctx, cams, n, p, rgb=None, hits=None, mat=None):
-    ptr = lambda a: None if a is None else C.c_void_p(a)
-    return _lib.lib.ft_render_views_hits_device(ctx, None, cams, n, p, ptr(rgb), ptr(hits), ptr(mat))
+    return _lib.lib.ft_render_views_hits_device(ctx, None, cams, n, p, dev_ptr(rgb), dev_ptr(hits), dev_ptr(mat))
 
 
 def test_host_only_context_has_no_view_hit_buffers(host_ctx):
@@ -153,14 +130,11 @@ def test_pixel_hits_over_stacked_views(oracle):
 
 
 def test_cpp_render_views_hits_compiles(tmp_path):
-    src = tmp_path / "views_hits.cpp"
-    src.write_text('#include "FrayTracer.hpp"\n'
-                   "std::vector<ft_object_trace_result> f(const FrayTracer::SdfScene& s, const std::vector<ft_camera>& c, std::vector<int32_t>* m,\n"
-                   "                                      ft_stats* st) {\n"
-                   "    return FrayTracer::Image::renderViewsHits(0.01f, 100.0f, FrayTracer::ImageSize{64, 48}, c, s, m, st);\n"
-                   "}\n")
-    cxx = os.environ.get("CXX", "g++")
-    subprocess.check_call([cxx, "-std=c++17", "-fsyntax-only", "-I", os.path.join(ROOT, "host", "cpp"), "-I", os.path.join(ROOT, "include"), str(src)])
+    assert_cpp_compiles(tmp_path, "views_hits.cpp",
+                        "std::vector<ft_object_trace_result> f(const FrayTracer::SdfScene& s, const std::vector<ft_camera>& c, std::vector<int32_t>* m,\n"
+                        "                                      ft_stats* st) {\n"
+                        "    return FrayTracer::Image::renderViewsHits(0.01f, 100.0f, FrayTracer::ImageSize{64, 48}, c, s, m, st);\n"
+                        "}\n")
 
 
 def test_fsharp_binding_has_render_views_hits():
