@@ -261,6 +261,13 @@ class SdfScene:
         """SdfScene.trace scene : Ray -> FColor (SdfScene.fs:7-8), evaluated on the GPU."""
         return SceneTrace(scene, device)
 
+    @staticmethod
+    def shade(scene, hits, device=None):
+        """SdfScene.trace from its `| ValueSome result ->` arm on (SdfScene.fs:11-28) over hit records (SdfObjectTraceResult voption values:
+        a PixelHits, float32 [..., 16] or a device tensor) -> colours [..., 3], evaluated on the GPU (ft_shade_hits)."""
+        dev = device if device is not None else Device.default(0)
+        return dev.scene(scene).shade_hits(hits)[0]
+
 
 def realise(node, backend, memo=None):
     """Build `node` on a backend (libfraytracer_hip context or the test oracle); returns its handle."""
@@ -521,6 +528,19 @@ def check_device_rays(t):
     return int(shape[0])
 
 
+def check_hit_records(t):
+    """leading shape of a buffer of hit records (a numpy array or a device tensor): float32, shape [..., 16] (ft_object_trace_result), and for
+    a device tensor contiguous — anything else is a ValueError (no silent conversion)"""
+    if str(t.dtype).rsplit(".", 1)[-1] != "float32":
+        raise ValueError(f"hit records: dtype must be float32, not {t.dtype}")
+    shape = tuple(int(d) for d in t.shape)
+    if len(shape) < 1 or shape[-1] != 16:
+        raise ValueError(f"hit records: shape must be [..., 16] (Ray, Normal, Color, hit, 0), not {list(shape)}")
+    if is_device_tensor(t) and not t.is_contiguous():
+        raise ValueError("hit records: the tensor must be contiguous (call .contiguous() first)")
+    return shape[:-1]
+
+
 def _torch_int32(t):
     import torch                  # a device tensor was passed in: torch is loaded
     return torch.int32
@@ -585,6 +605,19 @@ class DeviceScene:
         if self._scene:
             lib.ft_scene_destroy(self._scene)
             self._scene = None
+
+    def relight(self, BackgroundColor, Lights):
+        """ft_scene_relight: a DeviceScene of the same Object under another background and other lights (SdfLight descriptions).  The flattened
+        object — program, grids, support sphere, certificate clusters — is copied, not rebuilt; the result equals Device.scene(SdfScene(Object,
+        BackgroundColor, Lights)) in every uploaded byte and is independent of this scene (either may be closed first)."""
+        dev = self.device
+        hs, n = _handles([realise(l, dev) for l in Lights])
+        p = C.c_void_p()
+        check(lib.ft_scene_relight(self._scene, _f3(_v3(BackgroundColor)), hs, n, C.byref(p)))
+        new = DeviceScene.__new__(DeviceScene)
+        new.device, new._object, new.materials, new._scene = dev, getattr(self, "_object", None), getattr(self, "materials", {}), p
+        dev._scenes.append(new)
+        return new
 
     def boundary(self):
         """scene.Object.Form.Boundary as (cx, cy, cz, radius)"""
@@ -815,6 +848,35 @@ class DeviceScene:
         """asynchronous ft_trace_rays_hits_device: colours, records and material handles of n rays in one launch (any two may be None)"""
         check(lib.ft_trace_rays_hits_device(self.device._ctx, self._scene, _dptr(d_rays_ptr), n, _dptr(d_out_ptr), _dptr(d_hits_ptr),
                                             _dptr(d_material_ptr)))
+
+    # ---- relighting: hit records in, colours out ------------------------------------------------------------------------
+    def shade_hits(self, hits):
+        """ft_shade_hits: SdfScene.trace from its hit on (SdfScene.fs:11-28) for every record of `hits` — a PixelHits, a float32 array
+        [..., 16] or a device tensor of that shape (see is_device_tensor) -> (float32 [..., 3], stats).  Records written under a scene that
+        shares this scene's Object (see relight) shade to what this scene's trace_rays / render gives, bit for bit, without a primary march;
+        records are data and may be edited first (colour, normal; hit = 0 gives the background).  A device tensor is shaded where it lies
+        by ft_shade_hits_device on the caller's current stream, the colours are a tensor of its device and stats is None."""
+        rec = hits.records if isinstance(hits, PixelHits) else hits
+        if not is_device_tensor(rec) and not isinstance(rec, np.ndarray):
+            rec = np.asarray(rec)
+        lead = check_hit_records(rec)
+        n = int(np.prod(lead, dtype=np.int64))
+        if is_device_tensor(rec):
+            out = rec.new_empty(lead + (3,))
+            if n:
+                with self.device.on_current_stream(rec):
+                    self.shade_hits_device(rec.data_ptr(), n, out.data_ptr())
+            return out, None
+        rec = np.ascontiguousarray(rec)
+        out = np.empty(lead + (3,), np.float32)
+        if n == 0:
+            return out, _lib.Stats().as_dict()
+        return out, self._call(lib.ft_shade_hits, _hptr(rec), n, _hptr(out))
+
+    def shade_hits_device(self, d_hits_ptr, n, d_out_ptr):
+        """asynchronous ft_shade_hits_device: n records (64 B each, 16-byte aligned) at d_hits_ptr -> n x 3 float32 colours at d_out_ptr
+        (pointers as int); no scratch, no copy; pair with collect_stats()."""
+        check(lib.ft_shade_hits_device(self.device._ctx, self._scene, _dptr(d_hits_ptr), n, _dptr(d_out_ptr)))
 
     def eval_distance(self, points):
         pts = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)

@@ -230,9 +230,13 @@ bool libmLaunch(const ft_ctx* c, const ft_scene* s) { return c->optMath != FT_MA
 //   * one row per wave behind everything: the lean kernel's latency mode and culled children; any other non-carved kernel's culled children where
 //     the scene has a cull site.  Those are optional: without them the culling pass is off, so they are dropped where the footprint would exceed
 //     the device's limit.  A scene too large even then is refused here, not by a launch failure.
-struct TracePlan { unsigned variant; bool libm, cullRows; uint32_t nSlots; size_t lds; };
-int planTrace(const ft_ctx* c, const ft_scene* s, bool ext, TracePlan& p) {
+//   * ft_shade_hits (shade) follows the same rules with the *_shade twins: no EXTENSION launch exists, so a carved union leaves the carved walk
+//     only with FT_OPT_CARVED = 0 or glibc math, exactly where a ft_trace_rays of the scene does.
+struct TracePlan { unsigned variant; bool libm, cullRows, shade; uint32_t nSlots; size_t lds; };
+int planTrace(const ft_ctx* c, const ft_scene* s, bool ext, bool shade, TracePlan& p) {
     const bool hasCull = s->dev.cullPc != 0xffffffffu;
+    if (shade && ext) return setErr(FT_ERR_INVALID, "internal: ft_shade_hits has no EXTENSION build");
+    p.shade = shade;
     p.libm = libmLaunch(c, s);
     p.variant = (s->dev.fastPath == 3u && (ext || !c->optCarved || p.libm)) ? 0u : s->dev.fastPath;
     p.nSlots = (p.variant == 1u || p.variant == 3u) ? 0u : s->dev.nSlots;
@@ -278,10 +282,10 @@ int launchTrace(ft_ctx* c, const ft_scene* s, FtRenderArgs& a, int lane = 0) {
     hipStream_t stream = lane ? c->lane1 : c->stream;
     uint32_t* counter = c->dCounter + (lane ? 16 : 0);
     TracePlan plan;
-    int rc = planTrace(c, s, a.ext != 0u, plan); if (rc) return rc;
+    int rc = planTrace(c, s, a.ext != 0u, a.shade != 0u, plan); if (rc) return rc;
     const unsigned variant = plan.variant;
     int perCU = 0;
-    HIP_TRY(ft_trace_occupancy(variant, s->carve.kind, a.ext != 0u, plan.libm, a.views != nullptr, plan.lds, &perCU));
+    HIP_TRY(ft_trace_occupancy(variant, s->carve.kind, a.ext != 0u, plan.libm, a.views != nullptr, plan.shade, plan.lds, &perCU));
     if (perCU < 1) return setErr(FT_ERR_UNSUPPORTED, "the trace kernel does not fit a compute unit with this scene's LDS footprint");
     perCU = std::min(perCU, 8);
     if (c->optMaxBlocksPerCU > 0) perCU = std::min(perCU, c->optMaxBlocksPerCU);       // FT_OPT_MAX_BLOCKS_PER_CU (experiments)
@@ -337,7 +341,7 @@ int launchTrace(ft_ctx* c, const ft_scene* s, FtRenderArgs& a, int lane = 0) {
         a.certRepeat = pol >> 24;
     }
     a.lazy = c->optLazyUnion ? 1u : 0u;
-    a.reuse = c->optReuse ? 1u : 0u;
+    a.reuse = (c->optReuse && !plan.shade) ? 1u : 0u;     // ft_shade_hits: no centre probe ran, nothing to reuse
     a.S.mathFma = c->optMath == FT_MATH_GLIBC_FMA ? 1u : 0u;
     a.materialsExt = s->dMaterialsExt;
     HIP_TRY(hipMemsetAsync(counter, 0, sizeof(uint32_t), stream));
@@ -589,6 +593,28 @@ int ft_scene_clone(const ft_scene* src, ft_ctx* dst, ft_scene** out) {
     s->flat = src->flat;
     s->usesExpLog = src->usesExpLog;
     int rc = uploadScene(dst, s);
+    if (rc) { delete s; return rc; }
+    *out = s;
+    return FT_OK;
+}
+
+// src's flattened Object — program, constants, grids, support sphere, certificate clusters: copied, not rebuilt — under another background and other
+// lights, which the flattener only appends (scene.cpp flatten: lights in the order given, the background as it stands), so the blob uploadScene
+// lays out equals that of ft_scene_create(object, background, lights) byte for byte
+int ft_scene_relight(const ft_scene* src, const float bg[3], const ft_handle* lights, int32_t n, ft_scene** out) {
+    if (!src || !out || !bg || n < 0 || (n > 0 && !lights)) return setErr(FT_ERR_INVALID, "bad argument");
+    *out = nullptr;
+    ft_ctx* c = src->ctx;
+    for (int32_t i = 0; i < n; ++i)
+        if (lights[i] < 0 || (size_t)lights[i] >= c->builder.lights.size()) return setErr(FT_ERR_INVALID, "invalid light handle");
+    ft_scene* s = new ft_scene();
+    s->ctx = c;
+    s->flat = src->flat;
+    s->usesExpLog = src->usesExpLog;
+    s->flat.lights.clear();
+    for (int32_t i = 0; i < n; ++i) s->flat.lights.push_back(c->builder.lights[lights[i]].dev);
+    s->flat.bg[0] = bg[0]; s->flat.bg[1] = bg[1]; s->flat.bg[2] = bg[2];
+    int rc = uploadScene(c, s);
     if (rc) { delete s; return rc; }
     *out = s;
     return FT_OK;
@@ -1083,8 +1109,10 @@ int ft_render_colors(ft_ctx* c, const ft_scene* s, const ft_camera* cam, const f
 // ---- ray buffers ------------------------------------------------------------------------------------
 // The kernel knows two kinds of ray buffer: SdfScene.trace, which in the EXTENSION builds can also store every ray's SdfObject.tryTrace record and
 // material handle, or only those, without shading; and SdfForm.tryTrace, whose 10-dword results take the colours' place.  SdfObject.tryTrace
-// itself is the first kind asked for its records, which it cannot do without.
-enum class RayKind { Trace, Form, Object };
+// itself is the first kind asked for its records, which it cannot do without.  Shade is no ray buffer but runs through the same path: the input is
+// n hit records (ft_object_trace_result, 64 B each), the output their colours under the scene's lights (the *_shade builds of the reference kernels).
+enum class RayKind { Trace, Form, Object, Shade };
+static size_t inputStride(RayKind k) { return k == RayKind::Shade ? sizeof(ft_object_trace_result) : sizeof(ft_ray); }
 
 namespace {
 
@@ -1095,12 +1123,16 @@ int launchRayBuffer(ft_ctx* c, const ft_scene* s, const void* d_rays, int64_t n,
     if (!s || s->ctx != c || !d_rays || n < 0) return setErr(FT_ERR_INVALID, "bad argument (scene must belong to this context)");
     if ((rc = checkOutputs(o, true))) return rc;
     if (kind == RayKind::Object && !o.hits) return setErr(FT_ERR_INVALID, "ray buffer: no output asked for");
-    if (reinterpret_cast<uintptr_t>(d_rays) & 15u) return setErr(FT_ERR_INVALID, "ray buffer: the rays must be 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(d_rays) & 15u) return setErr(FT_ERR_INVALID, "ray buffer: the rays (hit records) must be 16-byte aligned");
     if (d_rays == o.rgb || d_rays == o.hits || d_rays == o.material) return setErr(FT_ERR_INVALID, "ray buffer: input and output must not overlap");
     if (n == 0) return FT_OK;
     if (n >= 0xFFFF0000ll) return setErr(FT_ERR_UNSUPPORTED, "more than 2^32 rays in one call");
     FtRenderArgs a{};
     a.mode = kind == RayKind::Form ? 2u : 1u; a.rays = static_cast<const ft_ray*>(d_rays);
+    if (kind == RayKind::Shade) {                                      // records in, colours out: the SHADE builds read hitsIn and nothing of the ray fields
+        if (!o.rgb || o.extra()) return setErr(FT_ERR_INVALID, "internal: ft_shade_hits writes colours only");
+        a.mode = 3u; a.rays = nullptr; a.shade = 1u; a.hitsIn = static_cast<const float*>(d_rays);
+    }
     a.nJobs = (uint32_t)n; a.stripeW = 1; a.stripeRanks = 1; a.tilesY = 1; a.H = 1; a.W = 1; a.nCols = 1; a.maxSize = 1.0f;
     a.spp = 1; a.sppN = 1; a.jobsPerPlane = a.nJobs; a.planePixels = a.nJobs;
     // the same rules as a frame's (frameArgs): the hit buffers exist in the EXTENSION builds only, and plain SdfScene.trace stays on the
@@ -1114,15 +1146,16 @@ int launchRayBuffer(ft_ctx* c, const ft_scene* s, const void* d_rays, int64_t n,
 
 // The host forms: rays up into the context's scratch, the device form, every output asked for down again (HostStaging; the destinations are
 // not pinned); nothing of the call is left in flight when it returns.
-int traceRayBuffer(ft_ctx* c, const ft_scene* s, const ft_ray* rays, int64_t n, RayKind kind, const Outputs& host, ft_stats* st) {
+int traceRayBuffer(ft_ctx* c, const ft_scene* s, const void* rays, int64_t n, RayKind kind, const Outputs& host, ft_stats* st) {
     static_assert(sizeof(ft_ray) == 32 && sizeof(ft_form_trace_result) == 40 && sizeof(ft_object_trace_result) == 64, "layout");
+    const size_t inBytes = (size_t)n * inputStride(kind);
     int rc = requireDevice(c); if (rc) return rc;
     if (!s || s->ctx != c || !rays || !host.any() || n < 0) return setErr(FT_ERR_INVALID, "bad argument");
     if (n == 0) { if (st) memset(st, 0, sizeof(*st)); return FT_OK; }
     if (n >= 0xFFFF0000ll) return setErr(FT_ERR_UNSUPPORTED, "more than 2^32 rays in one call");
     HostStaging stage(c, "ray buffer", host, kind == RayKind::Form ? sizeof(ft_form_trace_result) : 12, false);
-    if ((rc = stage.plan((size_t)n * sizeof(ft_ray), (size_t)n))) return rc;
-    HIP_TRY(hipMemcpyAsync(stage.input(), rays, (size_t)n * sizeof(ft_ray), hipMemcpyHostToDevice, c->stream));
+    if ((rc = stage.plan(inBytes, (size_t)n))) return rc;
+    HIP_TRY(hipMemcpyAsync(stage.input(), rays, inBytes, hipMemcpyHostToDevice, c->stream));
     stage.copyOut(launchRayBuffer(c, s, stage.input(), n, kind, stage.dev()), 0, (size_t)n, (size_t)n);
     return stage.finish(st);
 }
@@ -1154,6 +1187,34 @@ int ft_object_try_trace(ft_ctx* c, const ft_scene* s, const ft_ray* rays, int64_
 int ft_trace_rays_hits(ft_ctx* c, const ft_scene* s, const ft_ray* rays, int64_t n, float* out_rgb, ft_object_trace_result* out_hits,
                        int32_t* out_material, ft_stats* st) {
     return traceRayBuffer(c, s, rays, n, RayKind::Trace, Outputs{out_rgb, out_hits, out_material}, st);
+}
+
+// ---- ft_shade_hits: hit records shaded under the scene's lights (SdfScene.fs:11-28) ------------------------------------
+// Everything that can be refused without a device is refused first, the device is asked for last (like the views forms): the statuses do not
+// depend on the context having a GPU.  *nothing: n = 0, FT_OK with nothing to do.
+static int checkShade(const ft_ctx* c, const ft_scene* s, const void* hits, int64_t n, const void* out, bool deviceMemory, bool* nothing) {
+    *nothing = false;
+    if (!c) return setErr(FT_ERR_INVALID, "null context");
+    if (!s || s->ctx != c || !hits || !out || n < 0) return setErr(FT_ERR_INVALID, "bad argument (scene must belong to this context)");
+    if (deviceMemory) {
+        if (reinterpret_cast<uintptr_t>(hits) & 15u) return setErr(FT_ERR_INVALID, "ft_shade_hits_device: the hit records must be 16-byte aligned");
+        if (reinterpret_cast<uintptr_t>(out) & 3u) return setErr(FT_ERR_INVALID, "ft_shade_hits_device: the colours must be 4-byte aligned");
+    }
+    if (hits == out) return setErr(FT_ERR_INVALID, "ft_shade_hits: input and output must not overlap");
+    if (n >= 0xFFFF0000ll) return setErr(FT_ERR_UNSUPPORTED, "more than 2^32 records in one call");
+    *nothing = n == 0;
+    return FT_OK;
+}
+int ft_shade_hits_device(ft_ctx* c, const ft_scene* s, const void* d_hits, int64_t n, void* d_out_rgb) {
+    bool nothing;
+    int rc = checkShade(c, s, d_hits, n, d_out_rgb, true, &nothing); if (rc || nothing) return rc;
+    return launchRayBuffer(c, s, d_hits, n, RayKind::Shade, Outputs{d_out_rgb, nullptr, nullptr});
+}
+int ft_shade_hits(ft_ctx* c, const ft_scene* s, const ft_object_trace_result* hits, int64_t n, float* out_rgb, ft_stats* st) {
+    bool nothing;
+    int rc = checkShade(c, s, hits, n, out_rgb, false, &nothing); if (rc) return rc;
+    if (nothing) { if (st) memset(st, 0, sizeof(*st)); return FT_OK; }
+    return traceRayBuffer(c, s, hits, n, RayKind::Shade, Outputs{out_rgb, nullptr, nullptr}, st);
 }
 
 int ft_eval_distance(ft_ctx* c, const ft_scene* s, const ft_vec3* pts, int64_t n, float* outD, int32_t* outM) {

@@ -84,6 +84,10 @@ struct FtRenderArgs {
     // (j / jobsPerPlane) / spp, sample plane (j / jobsPerPlane) % spp; view k writes planes k * spp .. k * spp + spp - 1 (kernels.hip "Views")
     const float* views;       // nViews x 12 floats (ft_camera) in device memory; cam above is unused
     uint32_t nViews;          // 1 .. FT_MAX_VIEWS: PH_CAM evaluates camera l % nViews in lane l
+    // ft_shade_hits (the *_shade builds only; appended so that no field above moves): job j is record j of hitsIn, shaded from SdfScene.fs:11 on
+    // and written to out + 3 j; rays, cam and mode are unused (kernels.hip start_job SHADE)
+    uint32_t shade;           // 1: launch the SHADE build of the kernel (set by the host, see capi.cpp launchRayBuffer)
+    const float* hitsIn;      // nJobs x 16 dwords (ft_object_trace_result), 16-byte aligned: a lane loads its record as four 16-byte words
 };
 #define FT_MAX_VIEWS 64       // views per launch (one PH_CAM value per lane); ft_render_views splits larger batches
 
@@ -117,7 +121,7 @@ hipError_t ft_launch_tonemap(const float* frame, uint32_t X, uint32_t Y, uint32_
 // ft_render_multi: gathered slabs [rank][stripe][...] -> frame [stripe][rank][...] on the device
 hipError_t ft_launch_deinterleave(const float* recv, float* frame, unsigned long long stripeFloats, uint32_t nStripes, uint32_t nRanks, hipStream_t st);
 hipError_t ft_launch_selftest(int op, uint32_t lo, uint32_t hi, unsigned long long* d_mismatches, hipStream_t st);
-hipError_t ft_trace_occupancy(unsigned fastPath, unsigned carveKind, bool ext, bool libm, bool views, size_t ldsBytes, int* blocksPerCU);
+hipError_t ft_trace_occupancy(unsigned fastPath, unsigned carveKind, bool ext, bool libm, bool views, bool shade, size_t ldsBytes, int* blocksPerCU);
 #ifdef __cplusplus
 }
 #endif

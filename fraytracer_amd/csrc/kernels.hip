@@ -1433,11 +1433,13 @@ __device__ __forceinline__ int first_step_from_cache(LaneState& s) {
 
 // advance a lane until it needs an SDF evaluation (or is idle): everything in SdfScene.trace that
 // is not a Distance call.
-template <bool EXT, bool VIEWS = false>
+// SHADE (ft_shade_hits, the *_shade builds): the lanes come from hit records (start_job), so PH_MARCH is never entered, nothing is cached at the hit
+// position (no centre probe ran: every shadow ray's first evaluation is computed) and the final colour is the record's, not a material's
+template <bool EXT, bool VIEWS = false, bool SHADE = false>
 __device__ __forceinline__ void settle(const FtRenderArgs& a, LaneState& s) {
     const float piInv = 1.0f / 3.14159274101257324f;                   // Math.fs:28-30
     for (;;) {
-        if (s.phase == PH_MARCH) {
+        if (!SHADE && s.phase == PH_MARCH) {
             // SdfForm.fs:94 -> SdfScene.fs:10; or every further step is known to miss (EXTENSION glass: a path inside a body marches on
             // -Distance, which is below epsilon everywhere outside the support sphere — the shortcut is for paths outside bodies only)
             if (s.len <= 0.0f || ((!EXT || !s.inside()) && ft_never_enters(a.S, s.o, s.dir, s.eps, s.len))) {
@@ -1488,7 +1490,9 @@ __device__ __forceinline__ void settle(const FtRenderArgs& a, LaneState& s) {
         }
         if (s.phase == PH_LIGHTS) {
             if (s.lidx >= a.S.nLights) {                               // SdfScene.fs:28
-                cfp m = as_const(a.S.materials) + 3u * s.leaf;
+                // SHADE: result.Color of the lane's record, read again here (its line was loaded when the job started) instead of being held in three
+                // registers or LDS rows across every shadow march
+                cfp m = SHADE ? as_const(a.hitsIn) + 16ull * s.job + 11u : as_const(a.S.materials) + 3u * s.leaf;
                 const f3 color = mk3(m[0], m[1], m[2]);
                 emit<EXT>(a, s, color * (sh_get3(FT_SH_LACC) * piInv));
                 s.phase = PH_IDLE;
@@ -1514,7 +1518,7 @@ __device__ __forceinline__ void settle(const FtRenderArgs& a, LaneState& s) {
                 }
                 s.steps = 0; ft_count(FT_C_SHADOW);
                 s.phase = PH_SHADOW; s.certAt = a.certShadow;
-                if (a.reuse != 0u) {
+                if (!SHADE && a.reuse != 0u) {
                     const int r = first_step_from_cache(s);
                     if (r == 1) { ft_count(FT_C_HITS); s.lidx += 1; s.phase = PH_LIGHTS; }     // shadowed at once (SdfLight.fs:20)
                     else if (r == 2) s.len = -1.0f;                    // resolved as a miss by the PH_SHADOW branch above
@@ -1532,8 +1536,30 @@ __device__ __forceinline__ void settle(const FtRenderArgs& a, LaneState& s) {
 // PH_CAM value of that camera (lane v of the wave's per-lane dCam / leafCam)
 struct ViewCam { f3 o, fw, up, rt; float d; uint32_t leaf; };
 
-template <bool EXT, bool VIEWS = false>
+template <bool EXT, bool VIEWS = false, bool SHADE = false>
 __device__ __forceinline__ void start_job(const FtRenderArgs& a, LaneState& s, const bool camKnown, float dCam, uint32_t leafCam, const ViewCam& vc) {
+    if (SHADE) {
+        // ft_shade_hits: SdfScene.trace from its `| ValueSome result ->` arm on (SdfScene.fs:11-28).  Job = record: four 16-byte words
+        // {Origin, Direction.x} {Direction.yz, Length, Epsilon} {Normal, Color.r} {Color.gb, hit, 0}.  A record is data: its position, normal and
+        // epsilon are used as they stand; hit == 0 is the background whatever else it holds.  No primary ray is counted: none is traced.
+        const v4f FT_CONST* r = reinterpret_cast<const v4f FT_CONST*>(as_const(a.hitsIn) + 16ull * s.job);
+        const v4f r0 = r[0], r1 = r[1], r2 = r[2], r3 = r[3];
+        s.outIdx = s.job;
+        s.eps = r1.w;                                                  // result.Ray.Epsilon: the shadow rays' epsilon (SdfLight.fs:14, 34)
+        s.steps = 0;
+        if (__float_as_uint(r3.z) == 0u) {                             // ValueNone: scene.BackgroundColor (SdfScene.fs:10)
+            write_rgb(a.out, s.outIdx, mk3(a.S.bg[0], a.S.bg[1], a.S.bg[2]));
+            s.phase = PH_IDLE;
+            return;
+        }
+        sh_set3(FT_SH_HP, mk3(r0.x, r0.y, r0.z));                      // result.Position = result.Ray.Origin
+        sh_set3(FT_SH_NRM, mk3(r2.x, r2.y, r2.z));
+        sh_set3(FT_SH_LACC, mk3(a.S.bg[0], a.S.bg[1], a.S.bg[2]));     // SdfScene.fs:12
+        s.lidx = 0;
+        s.phase = PH_LIGHTS;
+        settle<EXT, VIEWS, SHADE>(a, s);
+        return;
+    }
     if (a.mode >= 1) {                                                 // explicit ray buffer (1: SdfScene.trace scene ray, with or instead of its hit record; 2: SdfForm.tryTrace)
         const ft_ray r = a.rays[s.job];
         s.o = mk3(r.origin.x, r.origin.y, r.origin.z);
@@ -1633,8 +1659,9 @@ __device__ __forceinline__ unsigned long long wave_sum(uint32_t v) {
     return x;
 }
 
-template <int VARIANT, bool EXT, int MATH = 0, int K = 0, bool VIEWS = false>
+template <int VARIANT, bool EXT, int MATH = 0, int K = 0, bool VIEWS = false, bool SHADE = false>
 __device__ __forceinline__ void ft_trace_body(const FtRenderArgs& a) {
+    static_assert(!SHADE || (!EXT && !VIEWS), "ft_shade_hits has no EXTENSION and no views build");
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     // the first wave of block 0 reports the shader clock it ran at (statistics only); its start clocks wait in LDS, not in registers
     unsigned long long* clk0 = reinterpret_cast<unsigned long long*>(ft_lds + 32);
@@ -1670,7 +1697,7 @@ __device__ __forceinline__ void ft_trace_body(const FtRenderArgs& a) {
     // at the position of camera l % nViews, and lane v keeps the value of view v
     bool camKnown = false;
     float dCam = 0.0f; uint32_t leafCam = 0u;                          // wave-uniform (views: per lane)
-    if (a.reuse != 0u && a.mode == 0u) {
+    if (!SHADE && a.reuse != 0u && a.mode == 0u) {
         s.phase = PH_CAM;
         if (VIEWS) { const float* c = a.views + 12u * (lane % a.nViews); s.o = mk3(c[0], c[1], c[2]); }
         else s.o = mk3(a.cam[0], a.cam[1], a.cam[2]);
@@ -1721,7 +1748,7 @@ __device__ __forceinline__ void ft_trace_body(const FtRenderArgs& a) {
             }
             const uint32_t nIdle = (uint32_t)__popcll(idle);
             const uint32_t rank = (uint32_t)__popcll(idle & ((1ull << lane) - 1ull));
-            if (s.phase == PH_IDLE && rank < avail) { s.job = chunkNext + rank; start_job<EXT, VIEWS>(a, s, camKnown, dCam, leafCam, vc); }
+            if (s.phase == PH_IDLE && rank < avail) { s.job = chunkNext + rank; start_job<EXT, VIEWS, SHADE>(a, s, camKnown, dCam, leafCam, vc); }
             chunkNext += (nIdle < avail) ? nIdle : avail;
         }
         if (s.phase == PH_IDLE && exhausted && chunkNext == chunkEnd) s.phase = PH_DONE;
@@ -1733,7 +1760,7 @@ __device__ __forceinline__ void ft_trace_body(const FtRenderArgs& a) {
             if ((uint32_t)__popcll(__ballot(due)) >= a.certMin) {
                 const bool holds = ft_miss_certificate(a.S, ldsC + 0, due, s.o, s.dir, s.eps, s.len, s.steps);
                 if (due) {
-                    if (holds) { s.len = -1.0f; settle<EXT, VIEWS>(a, s); }    // resolved as the miss its march ends in (settle: as for ft_never_enters)
+                    if (holds) { s.len = -1.0f; settle<EXT, VIEWS, SHADE>(a, s); }    // resolved as the miss its march ends in (settle: as for ft_never_enters)
                     else s.certAt = a.certRepeat != 0u ? s.steps + a.certRepeat : 0xffffffffu;
                 }
                 // every lane resolved (a tile whose rays all miss): refill now instead of spending an empty round
@@ -1747,7 +1774,7 @@ __device__ __forceinline__ void ft_trace_body(const FtRenderArgs& a) {
         FT_UDBG_T0(tRound);
         auto query_point = [&]() {
             f3 q = s.o;
-            if (s.phase >= PH_NX && s.phase <= PH_NC) {                // SdfForm.fs:106-115
+            if (!SHADE && s.phase >= PH_NX && s.phase <= PH_NC) {      // SdfForm.fs:106-115
                 const f3 base = s.o + s.dir * (-s.eps);                // Ray.get (-eps)
                 const float h = s.eps * 0.125f;
                 q = base;
@@ -1806,14 +1833,15 @@ __device__ __forceinline__ void ft_trace_body(const FtRenderArgs& a) {
             FT_UDBG_T1(5, tEval); FT_UDBG_WAVE(6);
             if (EXT) d = __uint_as_float(__float_as_uint(d) ^ (s.xs & 0x80000000u));   // EXTENSION glass: inside, march on -Distance
 
-            switch (s.phase) {
+            const uint32_t ph = SHADE ? (uint32_t)PH_SHADOW : s.phase;    // SHADE: a lane that evaluates is on a shadow march, nothing else exists there
+            switch (ph) {
             case PH_MARCH:
             case PH_SHADOW:
             case PH_AO: {
                 bool miss = false;
                 if (d != d) { ft_flag(1u); miss = true; }           // reference would never terminate
                 else if (d < s.eps) {                                  // SdfForm.fs:98
-                    if (s.phase == PH_MARCH) {
+                    if (ph == PH_MARCH) {
                         ft_count(FT_C_HITP); s.leaf = leaf; s.phase = PH_NX;
                         if (EXT && a.mode == 2u) {                     // SdfForm.tryTrace: {Ray = ray; Distance = distance} (SdfForm.fs:98-102)
                             float* o = a.out + 10ull * s.outIdx;
@@ -1822,7 +1850,7 @@ __device__ __forceinline__ void ft_trace_body(const FtRenderArgs& a) {
                             s.phase = PH_IDLE;
                         }
                     }
-                    else if (s.phase == PH_SHADOW) { ft_count(FT_C_HITS); s.lidx += 1; s.phase = PH_LIGHTS; }   // shadowed (SdfLight.fs:20)
+                    else if (ph == PH_SHADOW) { ft_count(FT_C_HITS); s.lidx += 1; s.phase = PH_LIGHTS; }   // shadowed (SdfLight.fs:20)
                     else { s.xs += 1u; s.phase = PH_AONEXT; }          // EXTENSION: occluded
                 } else {
                     s.o = s.o + s.dir * d;                             // Ray.move (Ray.fs:9-13)
@@ -1864,7 +1892,7 @@ __device__ __forceinline__ void ft_trace_body(const FtRenderArgs& a) {
             }
             default: break;
             }
-            settle<EXT, VIEWS>(a, s);
+            settle<EXT, VIEWS, SHADE>(a, s);
         }
         FT_UDBG_T1(7, tRound);
     }
@@ -1962,10 +1990,41 @@ FT_VIEWS_KERNEL(ft_trace_kernel_ext_libm_views, FT_NO_OCC, 0, true, 1, 0)
 FT_VIEWS_KERNEL(ft_trace_kernel_smooth_spheres_ext_libm_views, FT_NO_OCC, 1, true, 1, 0)
 FT_VIEWS_KERNEL(ft_trace_kernel_calls_libm_views, FT_NO_OCC, 2, false, 1, 0)
 FT_VIEWS_KERNEL(ft_trace_kernel_calls_ext_libm_views, FT_NO_OCC, 2, true, 1, 0)
+// ft_shade_hits: the reference-path kernels once more with the job queue over hit records instead of rays (ft_trace_body SHADE; the builds above are
+// untouched by it).  No EXTENSION and no views build: a relit carved scene stays on the carved walk, a lean one on the sphere loops.  The occupancy
+// hints are the siblings' (registers, waves and LDS of every twin: profiles/shade_hits_kernel_resources.txt)
+#define FT_SHADE_KERNEL(name, occ, ...) extern "C" __global__ void __launch_bounds__(FT_BLOCK) occ name(const FtRenderArgs a) { ft_trace_body<__VA_ARGS__, false, true>(a); }
+FT_SHADE_KERNEL(ft_trace_kernel_shade, FT_OCC(FT_GENERAL_WAVES), 0, false, 0, 0)
+FT_SHADE_KERNEL(ft_trace_kernel_smooth_spheres_shade, FT_NO_OCC, 1, false, 0, 0)
+FT_SHADE_KERNEL(ft_trace_kernel_calls_shade, FT_CALLS_OCC, 2, false, 0, 0)
+FT_SHADE_KERNEL(ft_trace_kernel_carved_spheres_shade, FT_OCC(6), 3, false, 0, (int)FT_PR_SPHERE)
+FT_SHADE_KERNEL(ft_trace_kernel_carved_capsules_shade, FT_OCC(6), 3, false, 0, (int)FT_PR_CAPSULE)
+FT_SHADE_KERNEL(ft_trace_kernel_carved_tori_shade, FT_OCC(6), 3, false, 0, (int)FT_PR_TORUS)
+FT_SHADE_KERNEL(ft_trace_kernel_carved_triangles_shade, FT_OCC(5), 3, false, 0, (int)FT_PR_TRIANGLE)
+FT_SHADE_KERNEL(ft_trace_kernel_carved_mixed_shade, FT_OCC(5), 3, false, 0, (int)FT_CARVE_MIXED)
+FT_SHADE_KERNEL(ft_trace_kernel_libm_shade, FT_NO_OCC, 0, false, 1, 0)
+FT_SHADE_KERNEL(ft_trace_kernel_smooth_spheres_libm_shade, FT_NO_OCC, 1, false, 1, 0)
+FT_SHADE_KERNEL(ft_trace_kernel_calls_libm_shade, FT_NO_OCC, 2, false, 1, 0)
 // The one table of trace kernels, for launches and occupancy queries alike.  variant: the kernel family (FtSceneDev.fastPath as capi.cpp planTrace
 // decides it: 0 general, 1 lean smooth-sphere, 2 general with call children, 3 carved union).  nullptr where no kernel exists: a carved union has
-// no EXTENSION and no *_libm build.  views: the ft_render_views build of the same kernel.
-static const void* ft_trace_kernel_for(unsigned variant, unsigned carveKind, bool ext, bool libm, bool views) {
+// no EXTENSION and no *_libm build.  views: the ft_render_views build of the same kernel.  shade: the ft_shade_hits build (no EXTENSION, no views).
+static const void* ft_trace_kernel_for(unsigned variant, unsigned carveKind, bool ext, bool libm, bool views, bool shade) {
+    if (shade) {
+        static const void* const twins[3][2] = {      // [variant][libm]
+            {(const void*)ft_trace_kernel_shade, (const void*)ft_trace_kernel_libm_shade},
+            {(const void*)ft_trace_kernel_smooth_spheres_shade, (const void*)ft_trace_kernel_smooth_spheres_libm_shade},
+            {(const void*)ft_trace_kernel_calls_shade, (const void*)ft_trace_kernel_calls_libm_shade}};
+        if (ext || views) return nullptr;
+        if (variant < 3) return twins[variant][libm];
+        if (variant > 3 || libm) return nullptr;
+        switch (carveKind) {
+            case FT_PR_SPHERE: return (const void*)ft_trace_kernel_carved_spheres_shade;
+            case FT_PR_CAPSULE: return (const void*)ft_trace_kernel_carved_capsules_shade;
+            case FT_PR_TORUS: return (const void*)ft_trace_kernel_carved_tori_shade;
+            case FT_PR_TRIANGLE: return (const void*)ft_trace_kernel_carved_triangles_shade;
+            default: return (const void*)ft_trace_kernel_carved_mixed_shade;
+        }
+    }
     static const void* const families[2][3][2][2] = {     // [views][variant][libm][ext]
         {{{(const void*)ft_trace_kernel, (const void*)ft_trace_kernel_ext}, {(const void*)ft_trace_kernel_libm, (const void*)ft_trace_kernel_ext_libm}},
          {{(const void*)ft_trace_kernel_smooth_spheres, (const void*)ft_trace_kernel_smooth_spheres_ext},
@@ -2297,14 +2356,14 @@ extern "C" int ft_debug_set_hsaco(const char* path) {
 extern "C" hipError_t ft_launch_trace(const FtRenderArgs* a, unsigned blocks, size_t ldsBytes, hipStream_t st) {
     const bool ext = a->ext != 0u, libm = a->math != 0u;
 #ifdef FT_EXPERIMENT
-    if (a->S.fastPath == 1 && !ext && !libm && !a->views && ft_exp_fn) {
+    if (a->S.fastPath == 1 && !ext && !libm && !a->views && !a->shade && ft_exp_fn) {
         FtRenderArgs args = *a;
         size_t size = sizeof(args);
         void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &args, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
         return hipModuleLaunchKernel(ft_exp_fn, blocks, 1, 1, FT_BLOCK, 1, 1, (unsigned)ldsBytes, st, nullptr, extra);
     }
 #endif
-    const void* k = ft_trace_kernel_for(a->S.fastPath, a->carve.kind, ext, libm, a->views != nullptr);
+    const void* k = ft_trace_kernel_for(a->S.fastPath, a->carve.kind, ext, libm, a->views != nullptr, a->shade != 0u);
     if (!k) return hipErrorInvalidDeviceFunction;
     FtRenderArgs args = *a;
     void* kp[] = {&args};
@@ -2398,8 +2457,8 @@ extern "C" hipError_t ft_debug_union_counters(unsigned long long out[12]) {
     return hipMemcpyToSymbol(HIP_SYMBOL(ft_union_dbg), zero, sizeof(zero));
 }
 #endif
-extern "C" hipError_t ft_trace_occupancy(unsigned fastPath, unsigned carveKind, bool ext, bool libm, bool views, size_t ldsBytes, int* blocksPerCU) {
-    const void* k = ft_trace_kernel_for(fastPath, carveKind, ext, libm, views);
+extern "C" hipError_t ft_trace_occupancy(unsigned fastPath, unsigned carveKind, bool ext, bool libm, bool views, bool shade, size_t ldsBytes, int* blocksPerCU) {
+    const void* k = ft_trace_kernel_for(fastPath, carveKind, ext, libm, views, shade);
     if (!k) return hipErrorInvalidDeviceFunction;
     return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocksPerCU, k, FT_BLOCK, ldsBytes);
 }

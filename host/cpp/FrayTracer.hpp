@@ -14,6 +14,7 @@
 //   Image::renderViews                                  renderScene over several cameras in one launch (ft_render_views)
 //   Image::renderViewsHits                              renderHits over several cameras in one launch (ft_render_views_hits)
 //   Image::traceRaysHits                                SdfObject.tryTrace (+ SdfScene.trace) over an explicit ray buffer in one launch (ft_trace_rays_hits)
+//   Image::shadeHits / shadeHitsRelit                   SdfScene.trace from its hit on (SdfScene.fs:11-28) over hit records (ft_shade_hits, ft_scene_relight)
 #pragma once
 #include <stdexcept>
 #include <string>
@@ -128,6 +129,11 @@ public:
         const float black[3] = {0.0f, 0.0f, 0.0f};
         check(ft_scene_create(ctx, object.Node, black, nullptr, 0, &s_));
     }
+    // src's object under the background and lights of `lit` (ft_scene_relight: no flatten, no grid build); `lit.Object` is not looked at
+    SceneOfCall(const SceneOfCall& src, const SdfScene& lit) : ctx(src.ctx) {
+        std::vector<ft_handle> lights; for (auto& l : lit.Lights) lights.push_back(l.Node);
+        check(ft_scene_relight(src.get(), &lit.BackgroundColor.v.x, lights.data(), (int)lights.size(), &s_));
+    }
     ~SceneOfCall() { ft_scene_destroy(s_); }
     SceneOfCall(const SceneOfCall&) = delete;
     SceneOfCall& operator=(const SceneOfCall&) = delete;
@@ -199,6 +205,26 @@ inline std::vector<ft_object_trace_result> traceRaysHits(const std::vector<ft_ra
     s.done(ft_trace_rays_hits(s.ctx, s.get(), rays.data(), (int64_t)rays.size(), colors ? colors->data() : nullptr, out.data(),
                               material ? material->data() : nullptr, &s.st), stats);
     return out;
+}
+// Relighting without re-tracing: SdfScene.trace from its `| ValueSome result ->` arm on (SdfScene.fs:11-28) for every record of `hits` (what renderHits /
+// traceRaysHits / tryTrace returned for a scene with the same Object; hit == 0 shades to the background) -> 3 floats per record (ft_shade_hits)
+inline std::vector<float> shadeHits(const std::vector<ft_object_trace_result>& hits, const SdfScene& scene, ft_stats* stats = nullptr) {
+    SceneOfCall s(scene);
+    std::vector<float> out(hits.size() * 3);
+    s.done(ft_shade_hits(s.ctx, s.get(), hits.data(), (int64_t)hits.size(), out.data(), &s.st), stats);
+    return out;
+}
+// the same records under the background and lights of each scene of `lit`, whose Object is taken to be scene.Object: the object is flattened
+// once and every further light set costs one ft_scene_relight (a copy and an upload) and one ft_shade_hits
+inline std::vector<std::vector<float>> shadeHitsRelit(const std::vector<ft_object_trace_result>& hits, const SdfScene& scene, const std::vector<SdfScene>& lit) {
+    SceneOfCall base(scene);
+    std::vector<std::vector<float>> frames;
+    for (auto& l : lit) {
+        SceneOfCall s(base, l);
+        frames.emplace_back(hits.size() * 3);
+        s.done(ft_shade_hits(s.ctx, s.get(), hits.data(), (int64_t)hits.size(), frames.back().data(), &s.st), nullptr);
+    }
+    return frames;
 }
 // Image.toColors gamma rng image (Image.fs:37-50) on the GPU: bytes in Color[X,Y] order (R,G,B) or, with bmpOrder, in the scan-line
 // order of Image.toBitmap (Image.fs:61-86: rows from the top, B,G,R).  seed < 0: no dithering noise (the reference's is racy).

@@ -89,6 +89,11 @@ module Native =
     [<DllImport(Lib)>] extern int ft_light_point(nativeint ctx, Vector3& position, Vector3& rgb)
     [<DllImport(Lib)>] extern int ft_scene_create(nativeint ctx, int obj, Vector3& background, int[] lights, int n, nativeint& scene)
     [<DllImport(Lib)>] extern void ft_scene_destroy(nativeint scene)
+    // src's Object under another background and other lights: no flatten, no grid build
+    [<DllImport(Lib)>] extern int ft_scene_relight(nativeint src, Vector3& background, int[] lights, int n, nativeint& scene)
+    // SdfScene.trace from its hit on (SdfScene.fs:11-28) over hit records: relighting without re-tracing (device form: records 16-byte aligned)
+    [<DllImport(Lib)>] extern int ft_shade_hits(nativeint ctx, nativeint scene, FtObjectTraceResult[] hits, int64 n, nativeint outRgb, FtStats& stats)
+    [<DllImport(Lib)>] extern int ft_shade_hits_device(nativeint ctx, nativeint scene, nativeint dHits, int64 n, nativeint dOutRgb)
     [<DllImport(Lib)>] extern int ft_form_try_trace(nativeint ctx, nativeint scene, Ray[] rays, int64 n, [<Out>] FtFormTraceResult[] out, FtStats& stats)
     [<DllImport(Lib)>] extern int ft_object_try_trace(nativeint ctx, nativeint scene, Ray[] rays, int64 n, [<Out>] FtObjectTraceResult[] out, FtStats& stats)
     // ray buffers in device memory (rays 16-byte aligned, 32 B each): no scratch, no copy, not synchronised; pair with ft_collect_stats

@@ -184,6 +184,11 @@ ft_handle ft_light_point(ft_ctx*, const float position[3], const float rgb[3]); 
 int ft_scene_create(ft_ctx*, ft_handle object, const float background_rgb[3],
                     const ft_handle* lights, int32_t n_lights, ft_scene** out);
 void ft_scene_destroy(ft_scene*);
+/* A scene with src's Object — its flattened program, grids, support sphere, certificate clusters: shared work, not redone —
+ * under another background and other lights.  Equal in every uploaded byte to ft_scene_create(object, background, lights); no flatten and
+ * no grid build runs.  The light handles belong to src's context, which the new scene belongs to as well (a host-only context works);
+ * src may be destroyed afterwards.  NULL, a negative count or a handle that is no light of that context: FT_ERR_INVALID. */
+int ft_scene_relight(const ft_scene* src, const float background_rgb[3], const ft_handle* lights, int32_t n_lights, ft_scene** out);
 
 /* Lens.create (Camera.fs:11-14) and Camera.lookAt (Camera.fs:33-42); host-side, once per frame. */
 float ft_lens_create(float field_of_view);
@@ -302,6 +307,24 @@ int ft_trace_rays_hits(ft_ctx*, const ft_scene*, const ft_ray* rays, int64_t n,
  * 4-byte aligned; no scratch, no copy, not synchronised. */
 int ft_trace_rays_hits_device(ft_ctx*, const ft_scene*, const void* d_rays, int64_t n,
                               void* d_out_rgb, void* d_hits, void* d_material);
+
+/* Relighting without re-tracing.  SdfScene.trace from its `| ValueSome result ->` arm on (SdfScene.fs:11-28) over n records:
+ * out_rgb[i] = scene.BackgroundColor where hits[i].hit == 0, else result.Color * (lightColor * piInv) with one shadow ray per light whose
+ * lightCos > 0, cast from hits[i].ray.origin with hits[i].ray.epsilon through scene.Object (SdfLight.fs:10-20, 26-41).  For scenes A and B
+ * that share their Object (ft_scene_relight), shading under B the records ft_object_try_trace / ft_render_hits / ft_trace_rays_hits wrote
+ * under A gives bit for bit what ft_trace_rays / ft_render give under B.  Records are data: colour, normal, origin and epsilon are used as
+ * they stand (a caller may recolour or filter them); a record with hit == 0 is background whatever else it holds.  There are no render
+ * params: a glass material's record carries its tint and shades as a solid, as in ft_trace_rays.
+ * Counters: rays_primary, hits_primary and rays_ext are 0; rays_shadow and hits_shadow are what ft_trace_rays reports for the rays that made
+ * the records; flags come from the shadow marches only.  sdf_evals counts the shadow marches' evaluations: no normal probe ran here, so a
+ * shadow ray's first evaluation (at the hit position) is computed, as with FT_OPT_REUSE = 0, whatever that option says.
+ * The host form stages 64 B + 12 B per record in device scratch.  Arguments are checked before the device is asked for. */
+int ft_shade_hits(ft_ctx*, const ft_scene*, const ft_object_trace_result* hits, int64_t n, float* out_rgb, ft_stats* stats);
+/* Same in device memory, under the contract of the *_device forms above: d_hits 16-byte aligned (a lane loads its record as four 16-byte
+ * words), d_out_rgb 4-byte aligned; no scratch, no copy, launched on the context's stream and not synchronised (pair with ft_collect_stats).
+ * n = 0: FT_OK, nothing launched.  n >= 0xFFFF0000: FT_ERR_UNSUPPORTED.  Input and output must not overlap (only identical pointers are
+ * detected: FT_ERR_INVALID). */
+int ft_shade_hits_device(ft_ctx*, const ft_scene*, const void* d_hits, int64_t n, void* d_out_rgb);
 
 /* scene.Object.Form.Distance at n points (+ index of the material the hit would pick, or
  * NULL).  Test/diagnostic entry: lets parity tests compare single SDF evaluations. */
