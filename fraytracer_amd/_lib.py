@@ -125,6 +125,10 @@ SYMBOLS = {
     "ft_scene_relight": (C.c_int, [_P, _F3, C.POINTER(_H), C.c_int32, C.POINTER(_P)]),
     "ft_shade_hits": (C.c_int, [_P, _P, _P, C.c_int64, _P, C.POINTER(Stats)]),
     "ft_shade_hits_device": (C.c_int, [_P, _P, _P, C.c_int64, _P]),
+    "ft_light_visibility": (C.c_int, [_P, _P, _P, C.c_int64, C.c_uint32, _P, _P, C.POINTER(Stats)]),
+    "ft_light_visibility_device": (C.c_int, [_P, _P, _P, C.c_int64, C.c_uint32, _P, _P]),
+    "ft_shade_visible": (C.c_int, [_P, _P, _P, _P, C.c_int64, _P, C.POINTER(Stats)]),
+    "ft_shade_visible_device": (C.c_int, [_P, _P, _P, _P, C.c_int64, _P]),
     "ft_lens_create": (C.c_float, [C.c_float]),
     "ft_camera_look_at": (C.c_int, [_F3, _F3, _F3, C.c_float, C.POINTER(CameraS)]),
     "ft_render": (C.c_int, [_P, _P, C.POINTER(CameraS), C.POINTER(RenderParams), _P, C.POINTER(Stats)]),

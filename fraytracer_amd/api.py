@@ -268,6 +268,19 @@ class SdfScene:
         dev = device if device is not None else Device.default(0)
         return dev.scene(scene).shade_hits(hits)[0]
 
+    @staticmethod
+    def lightVisibility(scene, hits, select=None, previous=None, device=None):
+        """Which lights reach each hit record: bit i of the uint32 mask is set where `scene.Lights.[i].Intensity scene.Object ray` is ValueSome
+        for a light with lightCos > 0, i.e. where SdfScene.fs:23 executes (ft_light_visibility).  select / previous: re-march some lights only."""
+        dev = device if device is not None else Device.default(0)
+        return dev.scene(scene).light_visibility(hits, select, previous)[0]
+
+    @staticmethod
+    def shadeVisible(scene, hits, visibility, device=None):
+        """SdfScene.shade with every shadow ray answered by the masks of lightVisibility: no march (ft_shade_visible)."""
+        dev = device if device is not None else Device.default(0)
+        return dev.scene(scene).shade_visible(hits, visibility)[0]
+
 
 def realise(node, backend, memo=None):
     """Build `node` on a backend (libfraytracer_hip context or the test oracle); returns its handle."""
@@ -539,6 +552,18 @@ def check_hit_records(t):
     if is_device_tensor(t) and not t.is_contiguous():
         raise ValueError("hit records: the tensor must be contiguous (call .contiguous() first)")
     return shape[:-1]
+
+
+def check_visibility(m, lead, what="visibility"):
+    """a buffer of visibility masks for records of leading shape `lead`: a uint32 numpy array or an int32 device tensor (the same bits; torch's
+    uint32 has no arithmetic), contiguous, of exactly that shape — anything else is a ValueError (no silent conversion)"""
+    want = "int32" if is_device_tensor(m) else "uint32"
+    if str(m.dtype).rsplit(".", 1)[-1] != want:
+        raise ValueError(f"{what}: dtype must be {want}, not {m.dtype}")
+    if tuple(int(d) for d in m.shape) != tuple(lead):
+        raise ValueError(f"{what}: shape must be {list(lead)} (the records' without their last axis), not {list(m.shape)}")
+    if is_device_tensor(m) and not m.is_contiguous():
+        raise ValueError(f"{what}: the tensor must be contiguous (call .contiguous() first)")
 
 
 def _torch_int32(t):
@@ -877,6 +902,77 @@ class DeviceScene:
         """asynchronous ft_shade_hits_device: n records (64 B each, 16-byte aligned) at d_hits_ptr -> n x 3 float32 colours at d_out_ptr
         (pointers as int); no scratch, no copy; pair with collect_stats()."""
         check(lib.ft_shade_hits_device(self.device._ctx, self._scene, _dptr(d_hits_ptr), n, _dptr(d_out_ptr)))
+
+    # ---- light visibility masks: the shadow marches kept as bits, and shading from the bits ------------------------------
+    @staticmethod
+    def _records(hits):
+        """the record buffer of a PixelHits, an array or a device tensor -> (buffer, leading shape, record count)"""
+        rec = hits.records if isinstance(hits, PixelHits) else hits
+        if not is_device_tensor(rec) and not isinstance(rec, np.ndarray):
+            rec = np.asarray(rec)
+        lead = check_hit_records(rec)
+        return rec, lead, int(np.prod(lead, dtype=np.int64))
+
+    def light_visibility(self, hits, select=None, previous=None):
+        """ft_light_visibility: one shadow march per selected light and record of `hits` (a PixelHits, float32 [..., 16] or a device tensor,
+        as for shade_hits) -> (uint32 masks shaped like the records without their last axis, stats): bit i is set where light i reaches the
+        record, i.e. where SdfScene.fs:23 executes.  select: a bit mask of the lights to march (None: all); previous: masks whose other bits
+        are kept (None: none), so that after one light has moved only its own shadow rays are cast.  The bits depend on the Object, the records
+        and the lights' directions and positions, never on a colour.  Device records give an int32 tensor holding the same bits (previous: such
+        a tensor), on the caller's current stream, and stats None."""
+        rec, lead, n = self._records(hits)
+        sel = 0xFFFFFFFF if select is None else int(select) & 0xFFFFFFFF
+        if previous is not None:
+            if not is_device_tensor(previous) and not isinstance(previous, np.ndarray):
+                previous = np.asarray(previous)
+            if is_device_tensor(rec) != is_device_tensor(previous):
+                raise ValueError("previous: must lie where the records lie (device tensor or numpy array)")
+            check_visibility(previous, lead, "previous")
+        if is_device_tensor(rec):
+            out = rec.new_empty(lead, dtype=_torch_int32(rec))
+            if n:
+                with self.device.on_current_stream(rec):
+                    self.light_visibility_device(rec.data_ptr(), n, out.data_ptr(), sel, None if previous is None else previous.data_ptr())
+            return out, None
+        rec = np.ascontiguousarray(rec)
+        prev = None if previous is None else np.ascontiguousarray(previous)
+        out = np.empty(lead, np.uint32)
+        if n == 0:
+            return out, _lib.Stats().as_dict()
+        return out, self._call(lib.ft_light_visibility, _hptr(rec), n, sel, _hptr(prev), _hptr(out))
+
+    def light_visibility_device(self, d_hits_ptr, n, d_vis_out_ptr, select=0xFFFFFFFF, d_vis_in_ptr=None):
+        """asynchronous ft_light_visibility_device: n records (64 B each, 16-byte aligned) at d_hits_ptr -> n uint32 masks at d_vis_out_ptr;
+        d_vis_in_ptr: masks to keep the unselected bits of (None: none; may be d_vis_out_ptr).  Pointers as int; pair with collect_stats()."""
+        check(lib.ft_light_visibility_device(self.device._ctx, self._scene, _dptr(d_hits_ptr), n, select, _dptr(d_vis_in_ptr), _dptr(d_vis_out_ptr)))
+
+    def shade_visible(self, hits, visibility):
+        """ft_shade_visible: the colours of `hits` under this scene's lights and background with every shadow ray answered by `visibility`
+        (what light_visibility returned for a scene with the same Object and the same light directions and positions) -> (float32 [..., 3],
+        stats).  No march runs: a memory pass.  Equal bit for bit to shade_hits / trace_rays under this scene; records may be recoloured first.
+        A mask is data: a set bit adds its light whatever the cosine.  Device records take an int32 mask tensor and give a tensor; stats None."""
+        rec, lead, n = self._records(hits)
+        if not is_device_tensor(visibility) and not isinstance(visibility, np.ndarray):
+            visibility = np.asarray(visibility)
+        if is_device_tensor(rec) != is_device_tensor(visibility):
+            raise ValueError("visibility: must lie where the records lie (device tensor or numpy array)")
+        check_visibility(visibility, lead)
+        if is_device_tensor(rec):
+            out = rec.new_empty(lead + (3,))
+            if n:
+                with self.device.on_current_stream(rec):
+                    self.shade_visible_device(rec.data_ptr(), visibility.data_ptr(), n, out.data_ptr())
+            return out, None
+        rec, vis = np.ascontiguousarray(rec), np.ascontiguousarray(visibility)
+        out = np.empty(lead + (3,), np.float32)
+        if n == 0:
+            return out, _lib.Stats().as_dict()
+        return out, self._call(lib.ft_shade_visible, _hptr(rec), _hptr(vis), n, _hptr(out))
+
+    def shade_visible_device(self, d_hits_ptr, d_visibility_ptr, n, d_out_ptr):
+        """asynchronous ft_shade_visible_device: n records and n uint32 masks -> n x 3 float32 colours (pointers as int; records 16-byte
+        aligned); a streaming kernel on the context's stream; pair with collect_stats()."""
+        check(lib.ft_shade_visible_device(self.device._ctx, self._scene, _dptr(d_hits_ptr), _dptr(d_visibility_ptr), n, _dptr(d_out_ptr)))
 
     def eval_distance(self, points):
         pts = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)

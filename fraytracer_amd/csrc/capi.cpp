@@ -231,9 +231,10 @@ bool libmLaunch(const ft_ctx* c, const ft_scene* s) { return c->optMath != FT_MA
 //     the scene has a cull site.  Those are optional: without them the culling pass is off, so they are dropped where the footprint would exceed
 //     the device's limit.  A scene too large even then is refused here, not by a launch failure.
 //   * ft_shade_hits (shade) follows the same rules with the *_shade twins: no EXTENSION launch exists, so a carved union leaves the carved walk
-//     only with FT_OPT_CARVED = 0 or glibc math, exactly where a ft_trace_rays of the scene does.
-struct TracePlan { unsigned variant; bool libm, cullRows, shade; uint32_t nSlots; size_t lds; };
-int planTrace(const ft_ctx* c, const ft_scene* s, bool ext, bool shade, TracePlan& p) {
+//     only with FT_OPT_CARVED = 0 or glibc math, exactly where a ft_trace_rays of the scene does.  ft_light_visibility (shade = 2) is the same
+//     marches with another result, so the same rules with the *_vis twins.
+struct TracePlan { unsigned variant; bool libm, cullRows; unsigned shade; uint32_t nSlots; size_t lds; };
+int planTrace(const ft_ctx* c, const ft_scene* s, bool ext, unsigned shade, TracePlan& p) {
     const bool hasCull = s->dev.cullPc != 0xffffffffu;
     if (shade && ext) return setErr(FT_ERR_INVALID, "internal: ft_shade_hits has no EXTENSION build");
     p.shade = shade;
@@ -282,7 +283,7 @@ int launchTrace(ft_ctx* c, const ft_scene* s, FtRenderArgs& a, int lane = 0) {
     hipStream_t stream = lane ? c->lane1 : c->stream;
     uint32_t* counter = c->dCounter + (lane ? 16 : 0);
     TracePlan plan;
-    int rc = planTrace(c, s, a.ext != 0u, a.shade != 0u, plan); if (rc) return rc;
+    int rc = planTrace(c, s, a.ext != 0u, a.shade, plan); if (rc) return rc;
     const unsigned variant = plan.variant;
     int perCU = 0;
     HIP_TRY(ft_trace_occupancy(variant, s->carve.kind, a.ext != 0u, plan.libm, a.views != nullptr, plan.shade, plan.lds, &perCU));
@@ -1111,14 +1112,19 @@ int ft_render_colors(ft_ctx* c, const ft_scene* s, const ft_camera* cam, const f
 // material handle, or only those, without shading; and SdfForm.tryTrace, whose 10-dword results take the colours' place.  SdfObject.tryTrace
 // itself is the first kind asked for its records, which it cannot do without.  Shade is no ray buffer but runs through the same path: the input is
 // n hit records (ft_object_trace_result, 64 B each), the output their colours under the scene's lights (the *_shade builds of the reference kernels).
-enum class RayKind { Trace, Form, Object, Shade };
-static size_t inputStride(RayKind k) { return k == RayKind::Shade ? sizeof(ft_object_trace_result) : sizeof(ft_ray); }
+// Visibility is Shade with one uint32 mask per record for a result (the *_vis builds): which lights' shadow rays missed.  The masks travel where the
+// material plane does (Outputs::material: 4 B per record, 4-byte aligned); what else the call needs is its VisRequest.
+enum class RayKind { Trace, Form, Object, Shade, Visibility };
+static bool takesRecords(RayKind k) { return k == RayKind::Shade || k == RayKind::Visibility; }
+static size_t inputStride(RayKind k) { return takesRecords(k) ? sizeof(ft_object_trace_result) : sizeof(ft_ray); }
+struct VisRequest { uint32_t select; const void* in; };              // ft_light_visibility: the lights to march, the masks to keep the other bits of (NULL: none)
+static uint32_t lightBits(const ft_scene* s) { return s->dev.nLights >= 32u ? 0xffffffffu : (1u << s->dev.nLights) - 1u; }
 
 namespace {
 
 // Everything is device memory: the kernel reads d_rays and writes the caller's buffers on the context's stream, with no scratch, no copy and
 // no synchronisation.  The device is asked for first, then the arguments.
-int launchRayBuffer(ft_ctx* c, const ft_scene* s, const void* d_rays, int64_t n, RayKind kind, const Outputs& o) {
+int launchRayBuffer(ft_ctx* c, const ft_scene* s, const void* d_rays, int64_t n, RayKind kind, const Outputs& o, const VisRequest* vis = nullptr) {
     int rc = requireDevice(c); if (rc) return rc;
     if (!s || s->ctx != c || !d_rays || n < 0) return setErr(FT_ERR_INVALID, "bad argument (scene must belong to this context)");
     if ((rc = checkOutputs(o, true))) return rc;
@@ -1133,11 +1139,18 @@ int launchRayBuffer(ft_ctx* c, const ft_scene* s, const void* d_rays, int64_t n,
         if (!o.rgb || o.extra()) return setErr(FT_ERR_INVALID, "internal: ft_shade_hits writes colours only");
         a.mode = 3u; a.rays = nullptr; a.shade = 1u; a.hitsIn = static_cast<const float*>(d_rays);
     }
+    if (kind == RayKind::Visibility) {                                 // records in, masks out: the same marches, no colour
+        if (!vis || !o.material || o.rgb || o.hits) return setErr(FT_ERR_INVALID, "internal: ft_light_visibility writes masks only");
+        a.mode = 3u; a.rays = nullptr; a.shade = 2u; a.hitsIn = static_cast<const float*>(d_rays);
+        a.visSel = vis->select & lightBits(s); a.visKeep = ~vis->select & lightBits(s);
+        a.visIn = static_cast<const uint32_t*>(vis->in); a.visOut = static_cast<uint32_t*>(o.material);
+    }
     a.nJobs = (uint32_t)n; a.stripeW = 1; a.stripeRanks = 1; a.tilesY = 1; a.H = 1; a.W = 1; a.nCols = 1; a.maxSize = 1.0f;
     a.spp = 1; a.sppN = 1; a.jobsPerPlane = a.nJobs; a.planePixels = a.nJobs;
     // the same rules as a frame's (frameArgs): the hit buffers exist in the EXTENSION builds only, and plain SdfScene.trace stays on the
     // reference kernels (carved ones included)
     a.out = static_cast<float*>(o.rgb);
+    if (kind == RayKind::Visibility) return launchTrace(c, s, a);     // its masks are no material plane: no EXTENSION build, no hit buffers
     a.ext = (kind == RayKind::Form || o.extra()) ? 1u : 0u;
     if (o.extra()) { a.hits = o.rgb ? 1u : 2u; a.hitsOut = static_cast<float*>(o.hits); }
     a.matOut = static_cast<int32_t*>(o.material); a.matHandles = s->dMatHandles;
@@ -1215,6 +1228,93 @@ int ft_shade_hits(ft_ctx* c, const ft_scene* s, const ft_object_trace_result* hi
     int rc = checkShade(c, s, hits, n, out_rgb, false, &nothing); if (rc) return rc;
     if (nothing) { if (st) memset(st, 0, sizeof(*st)); return FT_OK; }
     return traceRayBuffer(c, s, hits, n, RayKind::Shade, Outputs{out_rgb, nullptr, nullptr}, st);
+}
+
+// ---- ft_light_visibility / ft_shade_visible: the shadow marches kept as one bit per (record, light), and shading from those bits -------------
+// Refusals first, the device last, as in checkShade.  A visibility mask has 32 bits: a scene with more lights is refused by both calls.
+// `masks`: vis_in (may be NULL) or the visibility; `out`: vis_out or the colours.  outIsMasks: vis_in == vis_out is an update in place; shading
+// into the masks is refused.
+static int checkMasked(const char* what, const ft_ctx* c, const ft_scene* s, const void* hits, int64_t n, const void* masks, bool masksNeeded,
+                       const void* out, bool outIsMasks, bool deviceMemory, bool* nothing) {
+    *nothing = false;
+    if (!c) return setErr(FT_ERR_INVALID, "null context");
+    if (!s || s->ctx != c || !hits || !out || (masksNeeded && !masks) || n < 0) return setErr(FT_ERR_INVALID, "bad argument (scene must belong to this context)");
+    if (deviceMemory) {
+        if (reinterpret_cast<uintptr_t>(hits) & 15u) return setErr(FT_ERR_INVALID, std::string(what) + "_device: the hit records must be 16-byte aligned");
+        if ((reinterpret_cast<uintptr_t>(masks) | reinterpret_cast<uintptr_t>(out)) & 3u)
+            return setErr(FT_ERR_INVALID, std::string(what) + "_device: the masks and the colours must be 4-byte aligned");
+    }
+    if (hits == out || (!outIsMasks && masks == out)) return setErr(FT_ERR_INVALID, std::string(what) + ": input and output must not overlap");
+    if (n >= 0xFFFF0000ll) return setErr(FT_ERR_UNSUPPORTED, "more than 2^32 records in one call");
+    if (s->dev.nLights > 32u) return setErr(FT_ERR_UNSUPPORTED, "a visibility mask holds 32 lights; the scene has " + std::to_string(s->dev.nLights));
+    *nothing = n == 0;
+    return FT_OK;
+}
+static int checkVisibility(const ft_ctx* c, const ft_scene* s, const void* hits, int64_t n, const void* visIn, const void* visOut, bool deviceMemory,
+                           bool* nothing) {
+    return checkMasked("ft_light_visibility", c, s, hits, n, visIn, false, visOut, true, deviceMemory, nothing);
+}
+int ft_light_visibility_device(ft_ctx* c, const ft_scene* s, const void* d_hits, int64_t n, uint32_t select, const void* d_vis_in, void* d_vis_out) {
+    bool nothing;
+    int rc = checkVisibility(c, s, d_hits, n, d_vis_in, d_vis_out, true, &nothing); if (rc || nothing) return rc;
+    const VisRequest vis{select, d_vis_in};
+    return launchRayBuffer(c, s, d_hits, n, RayKind::Visibility, Outputs{nullptr, nullptr, d_vis_out}, &vis);
+}
+// host form: [records | masks to keep] up into the scratch, the device form, the masks down (HostStaging's material plane: 4 B per record).  vis_in may
+// be vis_out: it has gone up before anything comes down, on one stream.
+int ft_light_visibility(ft_ctx* c, const ft_scene* s, const ft_object_trace_result* hits, int64_t n, uint32_t select, const uint32_t* vis_in,
+                        uint32_t* vis_out, ft_stats* st) {
+    bool nothing;
+    int rc = checkVisibility(c, s, hits, n, vis_in, vis_out, false, &nothing); if (rc) return rc;
+    if (nothing) { if (st) memset(st, 0, sizeof(*st)); return FT_OK; }
+    if ((rc = requireDevice(c))) return rc;
+    const size_t recBytes = (size_t)n * sizeof(ft_object_trace_result), keepAt = align256(recBytes);
+    HostStaging stage(c, "light visibility", Outputs{nullptr, nullptr, vis_out}, 12, false);
+    if ((rc = stage.plan(keepAt + (vis_in ? (size_t)n * 4 : 0), (size_t)n))) return rc;
+    unsigned char* in = static_cast<unsigned char*>(stage.input());
+    HIP_TRY(hipMemcpyAsync(in, hits, recBytes, hipMemcpyHostToDevice, c->stream));
+    if (vis_in) HIP_TRY(hipMemcpyAsync(in + keepAt, vis_in, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    const VisRequest vis{select, vis_in ? in + keepAt : nullptr};
+    stage.copyOut(launchRayBuffer(c, s, in, n, RayKind::Visibility, stage.dev(), &vis), 0, (size_t)n, (size_t)n);
+    return stage.finish(st);
+}
+
+static int checkShadeVisible(const ft_ctx* c, const ft_scene* s, const void* hits, const void* vis, int64_t n, const void* out, bool deviceMemory,
+                             bool* nothing) {
+    return checkMasked("ft_shade_visible", c, s, hits, n, vis, true, out, false, deviceMemory, nothing);
+}
+// its own kernel, not a trace launch: no job queue, no LDS, no counters; timed like one (ft_collect_stats adds the pair up)
+static int launchShadeVisible(ft_ctx* c, const ft_scene* s, const void* d_hits, const void* d_vis, int64_t n, void* d_out) {
+    int rc = requireDevice(c); if (rc) return rc;
+    hipEvent_t e0, e1;
+    if ((rc = foldOldestEvents(c))) return rc;
+    if ((rc = acquireEvents(c, e0, e1))) return rc;
+    HIP_TRY(hipEventRecord(e0, c->stream));
+    HIP_TRY(ft_launch_shade_visible(s->dev.lights, s->dev.nLights, s->dev.bg, static_cast<const float*>(d_hits), static_cast<const uint32_t*>(d_vis),
+                                    (uint32_t)n, static_cast<float*>(d_out), c->stream));
+    HIP_TRY(hipEventRecord(e1, c->stream));
+    c->events.emplace_back(e0, e1);
+    return FT_OK;
+}
+int ft_shade_visible_device(ft_ctx* c, const ft_scene* s, const void* d_hits, const void* d_visibility, int64_t n, void* d_out_rgb) {
+    bool nothing;
+    int rc = checkShadeVisible(c, s, d_hits, d_visibility, n, d_out_rgb, true, &nothing); if (rc || nothing) return rc;
+    return launchShadeVisible(c, s, d_hits, d_visibility, n, d_out_rgb);
+}
+int ft_shade_visible(ft_ctx* c, const ft_scene* s, const ft_object_trace_result* hits, const uint32_t* visibility, int64_t n, float* out_rgb,
+                     ft_stats* st) {
+    bool nothing;
+    int rc = checkShadeVisible(c, s, hits, visibility, n, out_rgb, false, &nothing); if (rc) return rc;
+    if (nothing) { if (st) memset(st, 0, sizeof(*st)); return FT_OK; }
+    if ((rc = requireDevice(c))) return rc;
+    const size_t recBytes = (size_t)n * sizeof(ft_object_trace_result), visAt = align256(recBytes);
+    HostStaging stage(c, "shade visible", Outputs{out_rgb, nullptr, nullptr}, 12, false);
+    if ((rc = stage.plan(visAt + (size_t)n * 4, (size_t)n))) return rc;
+    unsigned char* in = static_cast<unsigned char*>(stage.input());
+    HIP_TRY(hipMemcpyAsync(in, hits, recBytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(in + visAt, visibility, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    stage.copyOut(launchShadeVisible(c, s, in, in + visAt, n, stage.dev().rgb), 0, (size_t)n, (size_t)n);
+    return stage.finish(st);
 }
 
 int ft_eval_distance(ft_ctx* c, const ft_scene* s, const ft_vec3* pts, int64_t n, float* outD, int32_t* outM) {

@@ -86,8 +86,13 @@ struct FtRenderArgs {
     uint32_t nViews;          // 1 .. FT_MAX_VIEWS: PH_CAM evaluates camera l % nViews in lane l
     // ft_shade_hits (the *_shade builds only; appended so that no field above moves): job j is record j of hitsIn, shaded from SdfScene.fs:11 on
     // and written to out + 3 j; rays, cam and mode are unused (kernels.hip start_job SHADE)
-    uint32_t shade;           // 1: launch the SHADE build of the kernel (set by the host, see capi.cpp launchRayBuffer)
+    uint32_t shade;           // 1: launch the SHADE build of the kernel (set by the host, see capi.cpp launchRayBuffer); 2: its ft_light_visibility twin
     const float* hitsIn;      // nJobs x 16 dwords (ft_object_trace_result), 16-byte aligned: a lane loads its record as four 16-byte words
+    // ft_light_visibility (the *_vis builds only; appended): job j writes visOut[j] = (visIn ? visIn[j] & visKeep : 0) | the bits of the lights in
+    // visSel whose shadow ray from record j missed (kernels.hip settle VIS); out is unused
+    uint32_t visSel, visKeep; // select & (2^nLights - 1); ~select & (2^nLights - 1)
+    const uint32_t* visIn;    // NULL: nothing kept; may equal visOut (a lane reads its word before it writes it)
+    uint32_t* visOut;
 };
 #define FT_MAX_VIEWS 64       // views per launch (one PH_CAM value per lane); ft_render_views splits larger batches
 
@@ -121,7 +126,10 @@ hipError_t ft_launch_tonemap(const float* frame, uint32_t X, uint32_t Y, uint32_
 // ft_render_multi: gathered slabs [rank][stripe][...] -> frame [stripe][rank][...] on the device
 hipError_t ft_launch_deinterleave(const float* recv, float* frame, unsigned long long stripeFloats, uint32_t nStripes, uint32_t nRanks, hipStream_t st);
 hipError_t ft_launch_selftest(int op, uint32_t lo, uint32_t hi, unsigned long long* d_mismatches, hipStream_t st);
-hipError_t ft_trace_occupancy(unsigned fastPath, unsigned carveKind, bool ext, bool libm, bool views, bool shade, size_t ldsBytes, int* blocksPerCU);
+hipError_t ft_trace_occupancy(unsigned fastPath, unsigned carveKind, bool ext, bool libm, bool views, unsigned shade, size_t ldsBytes, int* blocksPerCU);
+// ft_shade_visible: n records + n masks -> n colours, no march (kernels.hip ft_shade_visible_kernel); lights: the scene's, in device memory
+hipError_t ft_launch_shade_visible(const FtLight* lights, uint32_t nLights, const float bg[3], const float* hits, const uint32_t* vis, uint32_t n,
+                                   float* out, hipStream_t st);
 #ifdef __cplusplus
 }
 #endif

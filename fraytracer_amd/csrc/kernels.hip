@@ -100,6 +100,8 @@ static_assert(FT_SH_D0 + 1 <= FT_SH_ROWS, "ft_kernels.h: FT_SH_ROWS");
 __device__ __forceinline__ float* ft_sh(uint32_t row) { return ft_lds + FT_LDS_SH_BASE + row * FT_BLOCK + threadIdx.x; }
 __device__ __forceinline__ f3 sh_get3(uint32_t row) { const float* q = ft_sh(row); return mk3(q[0], q[FT_BLOCK], q[2 * FT_BLOCK]); }
 __device__ __forceinline__ void sh_set3(uint32_t row, f3 v) { float* q = ft_sh(row); q[0] = v.x; q[FT_BLOCK] = v.y; q[2 * FT_BLOCK] = v.z; }
+// ft_light_visibility (the *_vis builds) accumulates no light: the first FT_SH_LACC row holds the lane's visibility mask instead
+__device__ __forceinline__ uint32_t* ft_vis_word() { return reinterpret_cast<uint32_t*>(ft_sh(FT_SH_LACC)); }
 
 // ---- arithmetic of MathF.Exp / MathF.Log (FT_OPT_MATH) ------------------------------------------------------------------------
 // MATH = 0: the fixed algorithms of ft_math.h (same bits on every machine; the default).  MATH = 1: glibc's expf / logf restated
@@ -1435,7 +1437,10 @@ __device__ __forceinline__ int first_step_from_cache(LaneState& s) {
 // is not a Distance call.
 // SHADE (ft_shade_hits, the *_shade builds): the lanes come from hit records (start_job), so PH_MARCH is never entered, nothing is cached at the hit
 // position (no centre probe ran: every shadow ray's first evaluation is computed) and the final colour is the record's, not a material's
-template <bool EXT, bool VIEWS = false, bool SHADE = false>
+// VIS (ft_light_visibility, the *_vis builds; SHADE as well): the same marches, but what a lane keeps is one bit per light — did SdfScene.fs:23 execute —
+// in the row that holds the accumulated light otherwise (ft_vis_word).  Lights outside a.visSel are passed over before anything of them is read; no
+// intensity, no cosine product, no colour: the mask goes to a.visOut when the last light is done
+template <bool EXT, bool VIEWS = false, bool SHADE = false, bool VIS = false>
 __device__ __forceinline__ void settle(const FtRenderArgs& a, LaneState& s) {
     const float piInv = 1.0f / 3.14159274101257324f;                   // Math.fs:28-30
     for (;;) {
@@ -1478,6 +1483,11 @@ __device__ __forceinline__ void settle(const FtRenderArgs& a, LaneState& s) {
         }
         if (s.phase == PH_SHADOW) {
             if (s.len <= 0.0f || ((!EXT || !s.inside()) && ft_never_enters(a.S, s.o, s.dir, s.eps, s.len))) {   // shadow ray missed (or can only miss): light arrives
+                if (VIS) {                                             // SdfScene.fs:23 executes for light lidx: its bit (unsigned shift: bit 31 is a light)
+                    *ft_vis_word() |= 1u << s.lidx;
+                    s.lidx += 1; s.phase = PH_LIGHTS;
+                    continue;
+                }
                 const FtLight L = ld_light(as_const(a.S.lights) + s.lidx);                 // the light this shadow ray was cast for (PH_LIGHTS below)
                 const f3 lv = mk3(L.v[0], L.v[1], L.v[2]), hp = sh_get3(FT_SH_HP);
                 f3 lint = mk3(L.color[0], L.color[1], L.color[2]), ldir = lv;             // SdfLight.fs:9, :16
@@ -1489,7 +1499,13 @@ __device__ __forceinline__ void settle(const FtRenderArgs& a, LaneState& s) {
             return;
         }
         if (s.phase == PH_LIGHTS) {
-            if (s.lidx >= a.S.nLights) {                               // SdfScene.fs:28
+            if (VIS && s.lidx >= a.S.nLights) {                        // every selected light has been asked: kept bits | new bits, one dword
+                a.visOut[s.job] = *ft_vis_word();
+                s.phase = PH_IDLE;
+                return;
+            }
+            if (VIS && ((a.visSel >> s.lidx) & 1u) == 0u) { s.lidx += 1; continue; }     // not selected: no cosine, no ray, nothing counted
+            if (!VIS && s.lidx >= a.S.nLights) {                       // SdfScene.fs:28 (no colour in a VIS build: it has ended above)
                 // SHADE: result.Color of the lane's record, read again here (its line was loaded when the job started) instead of being held in three
                 // registers or LDS rows across every shadow march
                 cfp m = SHADE ? as_const(a.hitsIn) + 16ull * s.job + 11u : as_const(a.S.materials) + 3u * s.leaf;
@@ -1536,7 +1552,7 @@ __device__ __forceinline__ void settle(const FtRenderArgs& a, LaneState& s) {
 // PH_CAM value of that camera (lane v of the wave's per-lane dCam / leafCam)
 struct ViewCam { f3 o, fw, up, rt; float d; uint32_t leaf; };
 
-template <bool EXT, bool VIEWS = false, bool SHADE = false>
+template <bool EXT, bool VIEWS = false, bool SHADE = false, bool VIS = false>
 __device__ __forceinline__ void start_job(const FtRenderArgs& a, LaneState& s, const bool camKnown, float dCam, uint32_t leafCam, const ViewCam& vc) {
     if (SHADE) {
         // ft_shade_hits: SdfScene.trace from its `| ValueSome result ->` arm on (SdfScene.fs:11-28).  Job = record: four 16-byte words
@@ -1547,6 +1563,14 @@ __device__ __forceinline__ void start_job(const FtRenderArgs& a, LaneState& s, c
         s.outIdx = s.job;
         s.eps = r1.w;                                                  // result.Ray.Epsilon: the shadow rays' epsilon (SdfLight.fs:14, 34)
         s.steps = 0;
+        // VIS: the lane's word of vis_in with the selected lights' bits and every bit that is no light cleared (a.visKeep); it may be the very word
+        // the lane writes at the end (vis_in == vis_out), which no other lane touches
+        const uint32_t kept = VIS ? (a.visIn ? a.visIn[s.job] & a.visKeep : 0u) : 0u;
+        if (VIS && __float_as_uint(r3.z) == 0u) {                      // ValueNone: no light is asked, the kept bits are the answer
+            a.visOut[s.job] = kept;
+            s.phase = PH_IDLE;
+            return;
+        }
         if (__float_as_uint(r3.z) == 0u) {                             // ValueNone: scene.BackgroundColor (SdfScene.fs:10)
             write_rgb(a.out, s.outIdx, mk3(a.S.bg[0], a.S.bg[1], a.S.bg[2]));
             s.phase = PH_IDLE;
@@ -1554,10 +1578,11 @@ __device__ __forceinline__ void start_job(const FtRenderArgs& a, LaneState& s, c
         }
         sh_set3(FT_SH_HP, mk3(r0.x, r0.y, r0.z));                      // result.Position = result.Ray.Origin
         sh_set3(FT_SH_NRM, mk3(r2.x, r2.y, r2.z));
-        sh_set3(FT_SH_LACC, mk3(a.S.bg[0], a.S.bg[1], a.S.bg[2]));     // SdfScene.fs:12
+        if (VIS) *ft_vis_word() = kept;
+        else sh_set3(FT_SH_LACC, mk3(a.S.bg[0], a.S.bg[1], a.S.bg[2]));     // SdfScene.fs:12
         s.lidx = 0;
         s.phase = PH_LIGHTS;
-        settle<EXT, VIEWS, SHADE>(a, s);
+        settle<EXT, VIEWS, SHADE, VIS>(a, s);
         return;
     }
     if (a.mode >= 1) {                                                 // explicit ray buffer (1: SdfScene.trace scene ray, with or instead of its hit record; 2: SdfForm.tryTrace)
@@ -1659,9 +1684,10 @@ __device__ __forceinline__ unsigned long long wave_sum(uint32_t v) {
     return x;
 }
 
-template <int VARIANT, bool EXT, int MATH = 0, int K = 0, bool VIEWS = false, bool SHADE = false>
+template <int VARIANT, bool EXT, int MATH = 0, int K = 0, bool VIEWS = false, bool SHADE = false, bool VIS = false>
 __device__ __forceinline__ void ft_trace_body(const FtRenderArgs& a) {
     static_assert(!SHADE || (!EXT && !VIEWS), "ft_shade_hits has no EXTENSION and no views build");
+    static_assert(!VIS || SHADE, "ft_light_visibility is a mode of the SHADE builds");
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     // the first wave of block 0 reports the shader clock it ran at (statistics only); its start clocks wait in LDS, not in registers
     unsigned long long* clk0 = reinterpret_cast<unsigned long long*>(ft_lds + 32);
@@ -1748,7 +1774,7 @@ __device__ __forceinline__ void ft_trace_body(const FtRenderArgs& a) {
             }
             const uint32_t nIdle = (uint32_t)__popcll(idle);
             const uint32_t rank = (uint32_t)__popcll(idle & ((1ull << lane) - 1ull));
-            if (s.phase == PH_IDLE && rank < avail) { s.job = chunkNext + rank; start_job<EXT, VIEWS, SHADE>(a, s, camKnown, dCam, leafCam, vc); }
+            if (s.phase == PH_IDLE && rank < avail) { s.job = chunkNext + rank; start_job<EXT, VIEWS, SHADE, VIS>(a, s, camKnown, dCam, leafCam, vc); }
             chunkNext += (nIdle < avail) ? nIdle : avail;
         }
         if (s.phase == PH_IDLE && exhausted && chunkNext == chunkEnd) s.phase = PH_DONE;
@@ -1760,7 +1786,7 @@ __device__ __forceinline__ void ft_trace_body(const FtRenderArgs& a) {
             if ((uint32_t)__popcll(__ballot(due)) >= a.certMin) {
                 const bool holds = ft_miss_certificate(a.S, ldsC + 0, due, s.o, s.dir, s.eps, s.len, s.steps);
                 if (due) {
-                    if (holds) { s.len = -1.0f; settle<EXT, VIEWS, SHADE>(a, s); }    // resolved as the miss its march ends in (settle: as for ft_never_enters)
+                    if (holds) { s.len = -1.0f; settle<EXT, VIEWS, SHADE, VIS>(a, s); }    // resolved as the miss its march ends in (settle: as for ft_never_enters)
                     else s.certAt = a.certRepeat != 0u ? s.steps + a.certRepeat : 0xffffffffu;
                 }
                 // every lane resolved (a tile whose rays all miss): refill now instead of spending an empty round
@@ -1892,7 +1918,7 @@ __device__ __forceinline__ void ft_trace_body(const FtRenderArgs& a) {
             }
             default: break;
             }
-            settle<EXT, VIEWS, SHADE>(a, s);
+            settle<EXT, VIEWS, SHADE, VIS>(a, s);
         }
         FT_UDBG_T1(7, tRound);
     }
@@ -2005,24 +2031,43 @@ FT_SHADE_KERNEL(ft_trace_kernel_carved_mixed_shade, FT_OCC(5), 3, false, 0, (int
 FT_SHADE_KERNEL(ft_trace_kernel_libm_shade, FT_NO_OCC, 0, false, 1, 0)
 FT_SHADE_KERNEL(ft_trace_kernel_smooth_spheres_libm_shade, FT_NO_OCC, 1, false, 1, 0)
 FT_SHADE_KERNEL(ft_trace_kernel_calls_libm_shade, FT_NO_OCC, 2, false, 1, 0)
+// ft_light_visibility: the *_shade builds once more with a visibility mask per record instead of a colour (ft_trace_body VIS; the builds above are
+// untouched by it): the same eleven, same occupancy hints (profiles/light_visibility_kernel_resources.txt)
+#define FT_VIS_KERNEL(name, occ, ...) extern "C" __global__ void __launch_bounds__(FT_BLOCK) occ name(const FtRenderArgs a) { ft_trace_body<__VA_ARGS__, false, true, true>(a); }
+FT_VIS_KERNEL(ft_trace_kernel_vis, FT_OCC(FT_GENERAL_WAVES), 0, false, 0, 0)
+FT_VIS_KERNEL(ft_trace_kernel_smooth_spheres_vis, FT_NO_OCC, 1, false, 0, 0)
+FT_VIS_KERNEL(ft_trace_kernel_calls_vis, FT_CALLS_OCC, 2, false, 0, 0)
+FT_VIS_KERNEL(ft_trace_kernel_carved_spheres_vis, FT_OCC(6), 3, false, 0, (int)FT_PR_SPHERE)
+FT_VIS_KERNEL(ft_trace_kernel_carved_capsules_vis, FT_OCC(6), 3, false, 0, (int)FT_PR_CAPSULE)
+FT_VIS_KERNEL(ft_trace_kernel_carved_tori_vis, FT_OCC(6), 3, false, 0, (int)FT_PR_TORUS)
+FT_VIS_KERNEL(ft_trace_kernel_carved_triangles_vis, FT_OCC(5), 3, false, 0, (int)FT_PR_TRIANGLE)
+FT_VIS_KERNEL(ft_trace_kernel_carved_mixed_vis, FT_OCC(5), 3, false, 0, (int)FT_CARVE_MIXED)
+FT_VIS_KERNEL(ft_trace_kernel_libm_vis, FT_NO_OCC, 0, false, 1, 0)
+FT_VIS_KERNEL(ft_trace_kernel_smooth_spheres_libm_vis, FT_NO_OCC, 1, false, 1, 0)
+FT_VIS_KERNEL(ft_trace_kernel_calls_libm_vis, FT_NO_OCC, 2, false, 1, 0)
 // The one table of trace kernels, for launches and occupancy queries alike.  variant: the kernel family (FtSceneDev.fastPath as capi.cpp planTrace
 // decides it: 0 general, 1 lean smooth-sphere, 2 general with call children, 3 carved union).  nullptr where no kernel exists: a carved union has
-// no EXTENSION and no *_libm build.  views: the ft_render_views build of the same kernel.  shade: the ft_shade_hits build (no EXTENSION, no views).
-static const void* ft_trace_kernel_for(unsigned variant, unsigned carveKind, bool ext, bool libm, bool views, bool shade) {
+// no EXTENSION and no *_libm build.  views: the ft_render_views build of the same kernel.  shade: the ft_shade_hits build (no EXTENSION, no views), 2: its
+// ft_light_visibility twin.
+static const void* ft_trace_kernel_for(unsigned variant, unsigned carveKind, bool ext, bool libm, bool views, unsigned shade) {
     if (shade) {
-        static const void* const twins[3][2] = {      // [variant][libm]
-            {(const void*)ft_trace_kernel_shade, (const void*)ft_trace_kernel_libm_shade},
-            {(const void*)ft_trace_kernel_smooth_spheres_shade, (const void*)ft_trace_kernel_smooth_spheres_libm_shade},
-            {(const void*)ft_trace_kernel_calls_shade, (const void*)ft_trace_kernel_calls_libm_shade}};
-        if (ext || views) return nullptr;
-        if (variant < 3) return twins[variant][libm];
+        static const void* const twins[2][3][2] = {      // [vis][variant][libm]
+            {{(const void*)ft_trace_kernel_shade, (const void*)ft_trace_kernel_libm_shade},
+             {(const void*)ft_trace_kernel_smooth_spheres_shade, (const void*)ft_trace_kernel_smooth_spheres_libm_shade},
+             {(const void*)ft_trace_kernel_calls_shade, (const void*)ft_trace_kernel_calls_libm_shade}},
+            {{(const void*)ft_trace_kernel_vis, (const void*)ft_trace_kernel_libm_vis},
+             {(const void*)ft_trace_kernel_smooth_spheres_vis, (const void*)ft_trace_kernel_smooth_spheres_libm_vis},
+             {(const void*)ft_trace_kernel_calls_vis, (const void*)ft_trace_kernel_calls_libm_vis}}};
+        const bool vis = shade == 2u;
+        if (ext || views || shade > 2u) return nullptr;
+        if (variant < 3) return twins[vis][variant][libm];
         if (variant > 3 || libm) return nullptr;
         switch (carveKind) {
-            case FT_PR_SPHERE: return (const void*)ft_trace_kernel_carved_spheres_shade;
-            case FT_PR_CAPSULE: return (const void*)ft_trace_kernel_carved_capsules_shade;
-            case FT_PR_TORUS: return (const void*)ft_trace_kernel_carved_tori_shade;
-            case FT_PR_TRIANGLE: return (const void*)ft_trace_kernel_carved_triangles_shade;
-            default: return (const void*)ft_trace_kernel_carved_mixed_shade;
+            case FT_PR_SPHERE: return vis ? (const void*)ft_trace_kernel_carved_spheres_vis : (const void*)ft_trace_kernel_carved_spheres_shade;
+            case FT_PR_CAPSULE: return vis ? (const void*)ft_trace_kernel_carved_capsules_vis : (const void*)ft_trace_kernel_carved_capsules_shade;
+            case FT_PR_TORUS: return vis ? (const void*)ft_trace_kernel_carved_tori_vis : (const void*)ft_trace_kernel_carved_tori_shade;
+            case FT_PR_TRIANGLE: return vis ? (const void*)ft_trace_kernel_carved_triangles_vis : (const void*)ft_trace_kernel_carved_triangles_shade;
+            default: return vis ? (const void*)ft_trace_kernel_carved_mixed_vis : (const void*)ft_trace_kernel_carved_mixed_shade;
         }
     }
     static const void* const families[2][3][2][2] = {     // [views][variant][libm][ext]
@@ -2046,6 +2091,36 @@ static const void* ft_trace_kernel_for(unsigned variant, unsigned carveKind, boo
         case FT_PR_TRIANGLE: return views ? (const void*)ft_trace_kernel_carved_triangles_views : (const void*)ft_trace_kernel_carved_triangles;
         default: return views ? (const void*)ft_trace_kernel_carved_mixed_views : (const void*)ft_trace_kernel_carved_mixed;   // boxes (EXTENSION) and mixed kinds
     }
+}
+
+// ft_shade_visible: SdfScene.fs:11-28 with every `light.Intensity scene.Object ray` answered by a bit of the record's visibility mask instead of a march.
+// One record per lane.  Of the record's four 16-byte words {Origin, Direction.x} {Direction.yz, Length, Epsilon} {Normal, Color.r} {Color.gb, hit, 0} the
+// second is not needed and not loaded; with the mask and the colour a record moves 52 + 12 B (80 B if the skipped word's sector is counted).  The
+// lights are wave-uniform: scalar loads in a uniform loop, a lane only skips the arithmetic of the lights whose bit it does not have.  The arithmetic
+// is settle()'s shadow-miss branch and its final colour, term for term in the same order (this file is compiled without contraction), so that a mask
+// from ft_light_visibility gives ft_shade_hits' colours bit for bit.  No LDS, no atomics.
+extern "C" __global__ void __launch_bounds__(FT_BLOCK) ft_shade_visible_kernel(const FtLight* __restrict__ lights, const uint32_t nLights, const float bg0,
+                                                                              const float bg1, const float bg2, const float* __restrict__ hits,
+                                                                              const uint32_t* __restrict__ vis, const uint32_t n, float* __restrict__ out) {
+    const float piInv = 1.0f / 3.14159274101257324f;                   // Math.fs:28-30
+    const uint32_t idx = blockIdx.x * FT_BLOCK + threadIdx.x;          // n < 0xFFFF0000 and the grid is exact: no wrap
+    if (idx >= n) return;
+    const v4f* r = reinterpret_cast<const v4f*>(hits + 16ull * idx);
+    const v4f r0 = r[0], r2 = r[2], r3 = r[3];
+    const uint32_t mask = vis[idx];
+    const f3 bg = mk3(bg0, bg1, bg2);
+    if (__float_as_uint(r3.z) == 0u) { write_rgb(out, idx, bg); return; }        // ValueNone: scene.BackgroundColor (SdfScene.fs:10)
+    const f3 hp = mk3(r0.x, r0.y, r0.z), nrm = mk3(r2.x, r2.y, r2.z);
+    f3 lacc = bg;                                                      // SdfScene.fs:12
+    for (uint32_t i = 0; i < nLights; ++i) {
+        const FtLight L = ld_light(as_const(lights) + i);
+        if (((mask >> i) & 1u) == 0u) continue;
+        const f3 lv = mk3(L.v[0], L.v[1], L.v[2]);
+        f3 lint = mk3(L.color[0], L.color[1], L.color[2]), ldir = lv;             // SdfLight.fs:9, :16
+        if (L.type != FT_LIGHT_DIRECTIONAL) { ldir = ft_normalize(lv - hp); lint = lint / ft_length2(lv - hp); }      // SdfLight.fs:25, :28, :40
+        lacc = lacc + lint * ft_dot(nrm, ldir);                        // SdfScene.fs:15, :23
+    }
+    write_rgb(out, idx, mk3(r2.w, r3.x, r3.y) * (lacc * piInv));       // SdfScene.fs:28
 }
 
 // scene.Object.Form.Distance at explicit points (test / diagnostic entry)
@@ -2363,7 +2438,7 @@ extern "C" hipError_t ft_launch_trace(const FtRenderArgs* a, unsigned blocks, si
         return hipModuleLaunchKernel(ft_exp_fn, blocks, 1, 1, FT_BLOCK, 1, 1, (unsigned)ldsBytes, st, nullptr, extra);
     }
 #endif
-    const void* k = ft_trace_kernel_for(a->S.fastPath, a->carve.kind, ext, libm, a->views != nullptr, a->shade != 0u);
+    const void* k = ft_trace_kernel_for(a->S.fastPath, a->carve.kind, ext, libm, a->views != nullptr, a->shade);
     if (!k) return hipErrorInvalidDeviceFunction;
     FtRenderArgs args = *a;
     void* kp[] = {&args};
@@ -2457,7 +2532,13 @@ extern "C" hipError_t ft_debug_union_counters(unsigned long long out[12]) {
     return hipMemcpyToSymbol(HIP_SYMBOL(ft_union_dbg), zero, sizeof(zero));
 }
 #endif
-extern "C" hipError_t ft_trace_occupancy(unsigned fastPath, unsigned carveKind, bool ext, bool libm, bool views, bool shade, size_t ldsBytes, int* blocksPerCU) {
+extern "C" hipError_t ft_launch_shade_visible(const FtLight* lights, uint32_t nLights, const float bg[3], const float* hits, const uint32_t* vis, uint32_t n,
+                                              float* out, hipStream_t st) {
+    const unsigned blocks = (unsigned)(((unsigned long long)n + FT_BLOCK - 1) / FT_BLOCK);
+    hipLaunchKernelGGL(ft_shade_visible_kernel, dim3(blocks), dim3(FT_BLOCK), 0, st, lights, nLights, bg[0], bg[1], bg[2], hits, vis, n, out);
+    return hipGetLastError();
+}
+extern "C" hipError_t ft_trace_occupancy(unsigned fastPath, unsigned carveKind, bool ext, bool libm, bool views, unsigned shade, size_t ldsBytes, int* blocksPerCU) {
     const void* k = ft_trace_kernel_for(fastPath, carveKind, ext, libm, views, shade);
     if (!k) return hipErrorInvalidDeviceFunction;
     return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocksPerCU, k, FT_BLOCK, ldsBytes);

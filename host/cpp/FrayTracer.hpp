@@ -15,6 +15,8 @@
 //   Image::renderViewsHits                              renderHits over several cameras in one launch (ft_render_views_hits)
 //   Image::traceRaysHits                                SdfObject.tryTrace (+ SdfScene.trace) over an explicit ray buffer in one launch (ft_trace_rays_hits)
 //   Image::shadeHits / shadeHitsRelit                   SdfScene.trace from its hit on (SdfScene.fs:11-28) over hit records (ft_shade_hits, ft_scene_relight)
+//   Image::lightVisibility / shadeVisible               which lights reach each record, one bit per light, and shading from those bits with no march
+//                                                       (ft_light_visibility, ft_shade_visible)
 #pragma once
 #include <stdexcept>
 #include <string>
@@ -225,6 +227,26 @@ inline std::vector<std::vector<float>> shadeHitsRelit(const std::vector<ft_objec
         s.done(ft_shade_hits(s.ctx, s.get(), hits.data(), (int64_t)hits.size(), frames.back().data(), &s.st), nullptr);
     }
     return frames;
+}
+// Light visibility masks: bit i of a record's mask is set where scene.Lights[i] reaches it, i.e. where SdfScene.fs:23 executes (ft_light_visibility).
+// select: the lights to march (all by default); previous: masks whose other bits are kept, so that a moved light costs only its own shadow rays.
+inline std::vector<uint32_t> lightVisibility(const std::vector<ft_object_trace_result>& hits, const SdfScene& scene, uint32_t select = 0xFFFFFFFFu,
+                                             const std::vector<uint32_t>* previous = nullptr, ft_stats* stats = nullptr) {
+    if (previous && previous->size() != hits.size()) throw std::invalid_argument("lightVisibility: one previous mask per record");
+    SceneOfCall s(scene);
+    std::vector<uint32_t> out(hits.size());
+    s.done(ft_light_visibility(s.ctx, s.get(), hits.data(), (int64_t)hits.size(), select, previous ? previous->data() : nullptr, out.data(), &s.st), stats);
+    return out;
+}
+// shadeHits with every shadow ray answered by `visibility` (masks of a scene with the same Object and the same light directions and positions): no
+// march, bit for bit shadeHits' colours under `scene` (ft_shade_visible)
+inline std::vector<float> shadeVisible(const std::vector<ft_object_trace_result>& hits, const std::vector<uint32_t>& visibility, const SdfScene& scene,
+                                       ft_stats* stats = nullptr) {
+    if (visibility.size() != hits.size()) throw std::invalid_argument("shadeVisible: one mask per record");
+    SceneOfCall s(scene);
+    std::vector<float> out(hits.size() * 3);
+    s.done(ft_shade_visible(s.ctx, s.get(), hits.data(), visibility.data(), (int64_t)hits.size(), out.data(), &s.st), stats);
+    return out;
 }
 // Image.toColors gamma rng image (Image.fs:37-50) on the GPU: bytes in Color[X,Y] order (R,G,B) or, with bmpOrder, in the scan-line
 // order of Image.toBitmap (Image.fs:61-86: rows from the top, B,G,R).  seed < 0: no dithering noise (the reference's is racy).

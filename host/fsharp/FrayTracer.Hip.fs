@@ -94,6 +94,12 @@ module Native =
     // SdfScene.trace from its hit on (SdfScene.fs:11-28) over hit records: relighting without re-tracing (device form: records 16-byte aligned)
     [<DllImport(Lib)>] extern int ft_shade_hits(nativeint ctx, nativeint scene, FtObjectTraceResult[] hits, int64 n, nativeint outRgb, FtStats& stats)
     [<DllImport(Lib)>] extern int ft_shade_hits_device(nativeint ctx, nativeint scene, nativeint dHits, int64 n, nativeint dOutRgb)
+    // light visibility masks: bit i of a record's uint32 is set where light i reaches it (SdfScene.fs:23 executes); select: the lights to march;
+    // visIn (0n: none; may be visOut): masks whose other bits are kept.  ft_shade_visible shades from records + masks with no march.
+    [<DllImport(Lib)>] extern int ft_light_visibility(nativeint ctx, nativeint scene, FtObjectTraceResult[] hits, int64 n, uint32 select, nativeint visIn, nativeint visOut, FtStats& stats)
+    [<DllImport(Lib)>] extern int ft_light_visibility_device(nativeint ctx, nativeint scene, nativeint dHits, int64 n, uint32 select, nativeint dVisIn, nativeint dVisOut)
+    [<DllImport(Lib)>] extern int ft_shade_visible(nativeint ctx, nativeint scene, FtObjectTraceResult[] hits, nativeint visibility, int64 n, nativeint outRgb, FtStats& stats)
+    [<DllImport(Lib)>] extern int ft_shade_visible_device(nativeint ctx, nativeint scene, nativeint dHits, nativeint dVisibility, int64 n, nativeint dOutRgb)
     [<DllImport(Lib)>] extern int ft_form_try_trace(nativeint ctx, nativeint scene, Ray[] rays, int64 n, [<Out>] FtFormTraceResult[] out, FtStats& stats)
     [<DllImport(Lib)>] extern int ft_object_try_trace(nativeint ctx, nativeint scene, Ray[] rays, int64 n, [<Out>] FtObjectTraceResult[] out, FtStats& stats)
     // ray buffers in device memory (rays 16-byte aligned, 32 B each): no scratch, no copy, not synchronised; pair with ft_collect_stats
@@ -283,6 +289,35 @@ module Trace =
             Native.check (Native.ft_form_try_trace (Native.ctx.Value, scene, rays, int64 rays.Length, out, &stats)) |> ignore
             out |> Array.map (fun r ->
                 if r.Hit = 0 then ValueNone else ValueSome { SdfFormTraceResult.Ray = r.Ray; Distance = r.Distance }))
+
+/// Light visibility masks over hit records (FtObjectTraceResult, as ft_object_try_trace / ft_render_hits write them) under a native scene handle.
+module Relight =
+    /// bit i of mask r: `scene.Lights.[i].Intensity scene.Object ray` is ValueSome for record r and lightCos > 0, i.e. SdfScene.fs:23 executes.
+    /// select: the lights to march (0xFFFFFFFFu: all); previous: masks whose other bits are kept (ValueNone: none)
+    let lightVisibility (scene : nativeint) (select : uint32) (previous : uint32[] voption) (hits : FtObjectTraceResult[]) : uint32[] =
+        let out : uint32[] = match previous with ValueSome p -> Array.copy p | ValueNone -> Array.zeroCreate hits.Length
+        if out.Length <> hits.Length then invalidArg "previous" "one mask per record"
+        let pin = GCHandle.Alloc (out, GCHandleType.Pinned)
+        try
+            let mutable stats = Unchecked.defaultof<FtStats>
+            let masks = pin.AddrOfPinnedObject ()                                                // updated in place: vis_in = vis_out
+            Native.check (Native.ft_light_visibility (Native.ctx.Value, scene, hits, int64 hits.Length, select, (if previous.IsSome then masks else 0n), masks, &stats)) |> ignore
+            out
+        finally
+            pin.Free ()
+
+    /// SdfScene.fs:11-28 with every shadow ray answered by the record's mask: no march (ft_shade_visible)
+    let shadeVisible (scene : nativeint) (visibility : uint32[]) (hits : FtObjectTraceResult[]) : FColor[] =
+        if visibility.Length <> hits.Length then invalidArg "visibility" "one mask per record"
+        let out : FColor[] = Array.zeroCreate hits.Length
+        let pinV = GCHandle.Alloc (visibility, GCHandleType.Pinned)
+        let pinO = GCHandle.Alloc (out, GCHandleType.Pinned)
+        try
+            let mutable stats = Unchecked.defaultof<FtStats>
+            Native.check (Native.ft_shade_visible (Native.ctx.Value, scene, hits, pinV.AddrOfPinnedObject (), int64 hits.Length, pinO.AddrOfPinnedObject (), &stats)) |> ignore
+            out
+        finally
+            pinO.Free (); pinV.Free ()
 
 module Image =
     /// GPU sibling of `scene |> FrayTracer.SdfScene.trace |> FrayTracer.Image.render epsilon length imageSize camera`

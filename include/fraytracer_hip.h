@@ -326,6 +326,46 @@ int ft_shade_hits(ft_ctx*, const ft_scene*, const ft_object_trace_result* hits, 
  * detected: FT_ERR_INVALID). */
 int ft_shade_hits_device(ft_ctx*, const ft_scene*, const void* d_hits, int64_t n, void* d_out_rgb);
 
+/* Light visibility masks: the shadow marches of ft_shade_hits kept as one bit per (record, light), and shading from those bits with no march.
+ * A shadow march yields one bit — does `light.Intensity scene.Object ray` return ValueSome or ValueNone (SdfLight.fs:17-20, 38-41) — which
+ * depends on scene.Object, the record and the light's direction or position, and on no colour: it stays what it is when lights are dimmed
+ * or recoloured, the background changes or records are recoloured, and when one light moves only that light's bit changes.
+ *
+ * ft_light_visibility.  Let L = n_lights of the scene and sel = select & (2^L - 1); select = 0xFFFFFFFF: every light.  Bit i of record r's
+ * new bits is set iff i is in sel, hits[r].hit != 0, lightCos > 0 (SdfScene.fs:15-17) and the shadow ray of light i cast from the record
+ * missed, i.e. exactly where SdfScene.fs:23 executes; the ray is cast from hits[r].ray.origin with hits[r].ray.epsilon, as ft_shade_hits
+ * casts it.  vis_out[r] = (vis_in ? vis_in[r] & ~sel & (2^L - 1) : 0) | new bits: bits >= L are always 0.  vis_in may be NULL and may
+ * equal vis_out (update in place).  Lights outside sel are skipped: no cosine is formed, no ray is cast, none is counted; sel == 0 returns
+ * the kept bits.  Counters: rays_primary, hits_primary and rays_ext are 0; rays_shadow, hits_shadow, sdf_evals and flags are those of the
+ * marches that ran — with every light selected, rays_shadow, hits_shadow and flags are ft_shade_hits' on the same records, and so is
+ * sdf_evals with FT_OPT_CERT = 0 (how many evaluations the miss certificate saves is not part of the contract).
+ * The host form stages 64 B + 4 B (+ 4 B with vis_in) per record in device scratch.  Arguments are checked before the device is asked for:
+ * NULL ctx, scene, hits or vis_out, n < 0, hits == vis_out: FT_ERR_INVALID; n = 0: FT_OK, nothing launched; n >= 0xFFFF0000 or a scene
+ * with more than 32 lights: FT_ERR_UNSUPPORTED. */
+int ft_light_visibility(ft_ctx*, const ft_scene*, const ft_object_trace_result* hits, int64_t n,
+                        uint32_t select, const uint32_t* vis_in, uint32_t* vis_out, ft_stats* stats);
+/* Same in device memory, under the contract of ft_shade_hits_device: d_hits 16-byte aligned, the masks 4-byte aligned (else FT_ERR_INVALID);
+ * no scratch, no copy, launched on the context's stream and not synchronised (pair with ft_collect_stats). */
+int ft_light_visibility_device(ft_ctx*, const ft_scene*, const void* d_hits, int64_t n,
+                               uint32_t select, const void* d_vis_in, void* d_vis_out);
+/* ft_shade_visible.  out_rgb[r] = scene.BackgroundColor where hits[r].hit == 0 (SdfScene.fs:10).  Otherwise lightColor = BackgroundColor
+ * (SdfScene.fs:12), then for i = 0 .. L - 1 in order: if bit i of visibility[r] is set, lightColor += intensity_i * lightCos_i (SdfScene.fs:15,
+ * 23) with a directional light's direction and colour as they stand (SdfLight.fs:9, 16) and a point light's normalize(position - origin) and
+ * colour / length2(position - origin) (SdfLight.fs:25, 28, 40); at last result.Color * (lightColor * piInv) (SdfScene.fs:28).  The operations,
+ * operands and order are those of the tracing kernels, so that for scenes that share their Object, bit for bit:
+ *   (a) shade_visible(B, rec, light_visibility(B, rec, all)) = ft_shade_hits(B, rec) = ft_trace_rays(B, rays);
+ *   (b) for B' with B's lights in the same order at the same directions and positions, but other colours, another background or recoloured
+ *       records rec': shade_visible(B', rec', light_visibility(B, rec)) = ft_trace_rays(B', rays);
+ *   (c) for B2 = B with light j moved: light_visibility(B2, rec, 1 << j, vis_in = light_visibility(B, rec)) = light_visibility(B2, rec, all).
+ * A mask is data, as records are: a set bit contributes even where the cosine is <= 0; bits >= L are ignored.  No march runs: every counter
+ * is 0, kernel_ms is filled.  The host form stages 64 B + 4 B + 12 B per record.  Refusals as above, with visibility and out_rgb for vis_out;
+ * visibility == out_rgb: FT_ERR_INVALID. */
+int ft_shade_visible(ft_ctx*, const ft_scene*, const ft_object_trace_result* hits, const uint32_t* visibility,
+                     int64_t n, float* out_rgb, ft_stats* stats);
+/* Same in device memory: d_hits 16-byte aligned, masks and colours 4-byte aligned; a streaming kernel on the context's stream. */
+int ft_shade_visible_device(ft_ctx*, const ft_scene*, const void* d_hits, const void* d_visibility,
+                            int64_t n, void* d_out_rgb);
+
 /* scene.Object.Form.Distance at n points (+ index of the material the hit would pick, or
  * NULL).  Test/diagnostic entry: lets parity tests compare single SDF evaluations. */
 int ft_eval_distance(ft_ctx*, const ft_scene*, const ft_vec3* points, int64_t n, float* out_distance, int32_t* out_material);
