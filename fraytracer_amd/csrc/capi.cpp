@@ -233,11 +233,10 @@ bool libmLaunch(const ft_ctx* c, const ft_scene* s) { return c->optMath != FT_MA
 //   * ft_shade_hits (shade) follows the same rules with the *_shade twins: no EXTENSION launch exists, so a carved union leaves the carved walk
 //     only with FT_OPT_CARVED = 0 or glibc math, exactly where a ft_trace_rays of the scene does.  ft_light_visibility (shade = 2) is the same
 //     marches with another result, so the same rules with the *_vis twins.
-struct TracePlan { unsigned variant; bool libm, cullRows; unsigned shade; uint32_t nSlots; size_t lds; };
+struct TracePlan { unsigned variant; bool libm, cullRows; uint32_t nSlots; size_t lds; };
 int planTrace(const ft_ctx* c, const ft_scene* s, bool ext, unsigned shade, TracePlan& p) {
     const bool hasCull = s->dev.cullPc != 0xffffffffu;
     if (shade && ext) return setErr(FT_ERR_INVALID, "internal: ft_shade_hits has no EXTENSION build");
-    p.shade = shade;
     p.libm = libmLaunch(c, s);
     p.variant = (s->dev.fastPath == 3u && (ext || !c->optCarved || p.libm)) ? 0u : s->dev.fastPath;
     p.nSlots = (p.variant == 1u || p.variant == 3u) ? 0u : s->dev.nSlots;
@@ -285,8 +284,15 @@ int launchTrace(ft_ctx* c, const ft_scene* s, FtRenderArgs& a, int lane = 0) {
     TracePlan plan;
     int rc = planTrace(c, s, a.ext != 0u, a.shade, plan); if (rc) return rc;
     const unsigned variant = plan.variant;
+    // what decides the kernel (ft_kernels.h ft_trace_key; a.ext, a.views and a.shade are the caller's), then the key: the occupancy query here and the
+    // launch below look up the same one
+    a.S = s->dev;
+    a.S.fastPath = variant;
+    a.carve = s->carve;
+    a.math = plan.libm ? 1u : 0u;
+    const FtTraceKey key = ft_trace_key(a);
     int perCU = 0;
-    HIP_TRY(ft_trace_occupancy(variant, s->carve.kind, a.ext != 0u, plan.libm, a.views != nullptr, plan.shade, plan.lds, &perCU));
+    HIP_TRY(ft_trace_occupancy(key, plan.lds, &perCU));
     if (perCU < 1) return setErr(FT_ERR_UNSUPPORTED, "the trace kernel does not fit a compute unit with this scene's LDS footprint");
     perCU = std::min(perCU, 8);
     if (c->optMaxBlocksPerCU > 0) perCU = std::min(perCU, c->optMaxBlocksPerCU);       // FT_OPT_MAX_BLOCKS_PER_CU (experiments)
@@ -324,11 +330,7 @@ int launchTrace(ft_ctx* c, const ft_scene* s, FtRenderArgs& a, int lane = 0) {
     }
     a.counter = counter;
     a.stats = c->dStats;
-    a.S = s->dev;
-    a.S.fastPath = variant;
-    a.carve = s->carve;
     a.S.nSlots = plan.nSlots;
-    a.math = plan.libm ? 1u : 0u;
     a.cull = (s->dev.cullPc != 0xffffffffu && plan.cullRows && c->optCull) ? 1u : 0u;
     if (!c->optEscape) a.S.escR = -1.0f;
     // miss certificate: lean kernel (and its EXTENSION build: a render and its ft_render_hits twin count the same evaluations), only with the escape
@@ -342,7 +344,7 @@ int launchTrace(ft_ctx* c, const ft_scene* s, FtRenderArgs& a, int lane = 0) {
         a.certRepeat = pol >> 24;
     }
     a.lazy = c->optLazyUnion ? 1u : 0u;
-    a.reuse = (c->optReuse && !plan.shade) ? 1u : 0u;     // ft_shade_hits: no centre probe ran, nothing to reuse
+    a.reuse = (c->optReuse && !a.shade) ? 1u : 0u;     // ft_shade_hits: no centre probe ran, nothing to reuse
     a.S.mathFma = c->optMath == FT_MATH_GLIBC_FMA ? 1u : 0u;
     a.materialsExt = s->dMaterialsExt;
     HIP_TRY(hipMemsetAsync(counter, 0, sizeof(uint32_t), stream));

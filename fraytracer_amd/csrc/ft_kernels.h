@@ -1,4 +1,4 @@
-// ft_kernels.h — kernel argument block and host-callable launchers (implemented in kernels.hip / launch.hip).
+// ft_kernels.h — kernel argument block and host-callable launchers (implemented in kernels.hip).
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
@@ -96,6 +96,21 @@ struct FtRenderArgs {
 };
 #define FT_MAX_VIEWS 64       // views per launch (one PH_CAM value per lane); ft_render_views splits larger batches
 
+// The forms of the trace kernel (kernels.hip FT_TRACE_FORMS builds every one of them from the same table of builds): what a job is and what it leaves.
+// FRAME: a pixel or a ray of a ray buffer (no suffix); VIEWS: a pixel of one of nViews cameras (*_views); SHADE: a hit record, shaded (*_shade);
+// VIS: a hit record, one visibility bit per light (*_vis).  NONE: what a launch asks for where no form exists (a shade form has no views build).
+enum { FT_FORM_FRAME = 0, FT_FORM_VIEWS = 1, FT_FORM_SHADE = 2, FT_FORM_VIS = 3, FT_FORM_NONE = 4 };
+FT_HD uint32_t ft_trace_form(bool views, unsigned shade) {
+    if (shade) return (views || shade > 2u) ? FT_FORM_NONE : (shade == 2u ? FT_FORM_VIS : FT_FORM_SHADE);
+    return views ? FT_FORM_VIEWS : FT_FORM_FRAME;
+}
+// Which trace kernel a launch runs: the one key that ft_launch_trace and ft_trace_occupancy look up (kernels.hip ft_trace_kernel_for).  variant: the
+// kernel family (FtSceneDev.fastPath as capi.cpp planTrace decides it); carveKind: FtCarve.kind, read for variant 3 only.
+struct FtTraceKey { uint32_t variant, carveKind, form; bool ext, libm; };
+FT_HD FtTraceKey ft_trace_key(const FtRenderArgs& a) {
+    return FtTraceKey{a.S.fastPath, a.carve.kind, ft_trace_form(a.views != nullptr, a.shade), a.ext != 0u, a.math != 0u};
+}
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -126,7 +141,9 @@ hipError_t ft_launch_tonemap(const float* frame, uint32_t X, uint32_t Y, uint32_
 // ft_render_multi: gathered slabs [rank][stripe][...] -> frame [stripe][rank][...] on the device
 hipError_t ft_launch_deinterleave(const float* recv, float* frame, unsigned long long stripeFloats, uint32_t nStripes, uint32_t nRanks, hipStream_t st);
 hipError_t ft_launch_selftest(int op, uint32_t lo, uint32_t hi, unsigned long long* d_mismatches, hipStream_t st);
-hipError_t ft_trace_occupancy(unsigned fastPath, unsigned carveKind, bool ext, bool libm, bool views, unsigned shade, size_t ldsBytes, int* blocksPerCU);
+// the kernel handle of a key given piecewise, nullptr where no such kernel exists (internal, like ft_trace_occupancy; tests/test_trace_kernel_table.py)
+const void* ft_trace_kernel_for(unsigned variant, unsigned carveKind, bool ext, bool libm, bool views, unsigned shade);
+hipError_t ft_trace_occupancy(const FtTraceKey& key, size_t ldsBytes, int* blocksPerCU);
 // ft_shade_visible: n records + n masks -> n colours, no march (kernels.hip ft_shade_visible_kernel); lights: the scene's, in device memory
 hipError_t ft_launch_shade_visible(const FtLight* lights, uint32_t nLights, const float bg[3], const float* hits, const uint32_t* vis, uint32_t n,
                                    float* out, hipStream_t st);

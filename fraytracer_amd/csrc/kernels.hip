@@ -1440,8 +1440,9 @@ __device__ __forceinline__ int first_step_from_cache(LaneState& s) {
 // VIS (ft_light_visibility, the *_vis builds; SHADE as well): the same marches, but what a lane keeps is one bit per light — did SdfScene.fs:23 execute —
 // in the row that holds the accumulated light otherwise (ft_vis_word).  Lights outside a.visSel are passed over before anything of them is read; no
 // intensity, no cosine product, no colour: the mask goes to a.visOut when the last light is done
-template <bool EXT, bool VIEWS = false, bool SHADE = false, bool VIS = false>
+template <bool EXT, int FORM = FT_FORM_FRAME>
 __device__ __forceinline__ void settle(const FtRenderArgs& a, LaneState& s) {
+    constexpr bool VIEWS = FORM == FT_FORM_VIEWS, SHADE = FORM == FT_FORM_SHADE || FORM == FT_FORM_VIS, VIS = FORM == FT_FORM_VIS;
     const float piInv = 1.0f / 3.14159274101257324f;                   // Math.fs:28-30
     for (;;) {
         if (!SHADE && s.phase == PH_MARCH) {
@@ -1552,8 +1553,9 @@ __device__ __forceinline__ void settle(const FtRenderArgs& a, LaneState& s) {
 // PH_CAM value of that camera (lane v of the wave's per-lane dCam / leafCam)
 struct ViewCam { f3 o, fw, up, rt; float d; uint32_t leaf; };
 
-template <bool EXT, bool VIEWS = false, bool SHADE = false, bool VIS = false>
+template <bool EXT, int FORM = FT_FORM_FRAME>
 __device__ __forceinline__ void start_job(const FtRenderArgs& a, LaneState& s, const bool camKnown, float dCam, uint32_t leafCam, const ViewCam& vc) {
+    constexpr bool VIEWS = FORM == FT_FORM_VIEWS, SHADE = FORM == FT_FORM_SHADE || FORM == FT_FORM_VIS, VIS = FORM == FT_FORM_VIS;
     if (SHADE) {
         // ft_shade_hits: SdfScene.trace from its `| ValueSome result ->` arm on (SdfScene.fs:11-28).  Job = record: four 16-byte words
         // {Origin, Direction.x} {Direction.yz, Length, Epsilon} {Normal, Color.r} {Color.gb, hit, 0}.  A record is data: its position, normal and
@@ -1582,7 +1584,7 @@ __device__ __forceinline__ void start_job(const FtRenderArgs& a, LaneState& s, c
         else sh_set3(FT_SH_LACC, mk3(a.S.bg[0], a.S.bg[1], a.S.bg[2]));     // SdfScene.fs:12
         s.lidx = 0;
         s.phase = PH_LIGHTS;
-        settle<EXT, VIEWS, SHADE, VIS>(a, s);
+        settle<EXT, FORM>(a, s);
         return;
     }
     if (a.mode >= 1) {                                                 // explicit ray buffer (1: SdfScene.trace scene ray, with or instead of its hit record; 2: SdfForm.tryTrace)
@@ -1626,7 +1628,7 @@ __device__ __forceinline__ void start_job(const FtRenderArgs& a, LaneState& s, c
         else if (dCam < s.eps) { ft_count(FT_C_HITP); s.leaf = leafCam; s.phase = PH_NX; }   // a hit at the camera itself,
         else { s.o = s.o + s.dir * dCam; s.len = s.len - dCam; s.steps = 1; }               // or the first step (Ray.fs:9-13)
     }
-    settle<EXT, VIEWS>(a, s);
+    settle<EXT, FORM>(a, s);
 }
 
 // EXTENSION (BASELINE.json config 5): a path segment ended on leaf s.leaf with normal s.nrm at s.hp.  Glass leaf:
@@ -1684,10 +1686,10 @@ __device__ __forceinline__ unsigned long long wave_sum(uint32_t v) {
     return x;
 }
 
-template <int VARIANT, bool EXT, int MATH = 0, int K = 0, bool VIEWS = false, bool SHADE = false, bool VIS = false>
+template <int VARIANT, bool EXT, int MATH = 0, int K = 0, int FORM = FT_FORM_FRAME>
 __device__ __forceinline__ void ft_trace_body(const FtRenderArgs& a) {
-    static_assert(!SHADE || (!EXT && !VIEWS), "ft_shade_hits has no EXTENSION and no views build");
-    static_assert(!VIS || SHADE, "ft_light_visibility is a mode of the SHADE builds");
+    constexpr bool VIEWS = FORM == FT_FORM_VIEWS, SHADE = FORM == FT_FORM_SHADE || FORM == FT_FORM_VIS;
+    static_assert(!SHADE || !EXT, "ft_shade_hits and ft_light_visibility have no EXTENSION build");
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     // the first wave of block 0 reports the shader clock it ran at (statistics only); its start clocks wait in LDS, not in registers
     unsigned long long* clk0 = reinterpret_cast<unsigned long long*>(ft_lds + 32);
@@ -1774,7 +1776,7 @@ __device__ __forceinline__ void ft_trace_body(const FtRenderArgs& a) {
             }
             const uint32_t nIdle = (uint32_t)__popcll(idle);
             const uint32_t rank = (uint32_t)__popcll(idle & ((1ull << lane) - 1ull));
-            if (s.phase == PH_IDLE && rank < avail) { s.job = chunkNext + rank; start_job<EXT, VIEWS, SHADE, VIS>(a, s, camKnown, dCam, leafCam, vc); }
+            if (s.phase == PH_IDLE && rank < avail) { s.job = chunkNext + rank; start_job<EXT, FORM>(a, s, camKnown, dCam, leafCam, vc); }
             chunkNext += (nIdle < avail) ? nIdle : avail;
         }
         if (s.phase == PH_IDLE && exhausted && chunkNext == chunkEnd) s.phase = PH_DONE;
@@ -1786,7 +1788,7 @@ __device__ __forceinline__ void ft_trace_body(const FtRenderArgs& a) {
             if ((uint32_t)__popcll(__ballot(due)) >= a.certMin) {
                 const bool holds = ft_miss_certificate(a.S, ldsC + 0, due, s.o, s.dir, s.eps, s.len, s.steps);
                 if (due) {
-                    if (holds) { s.len = -1.0f; settle<EXT, VIEWS, SHADE, VIS>(a, s); }    // resolved as the miss its march ends in (settle: as for ft_never_enters)
+                    if (holds) { s.len = -1.0f; settle<EXT, FORM>(a, s); }    // resolved as the miss its march ends in (settle: as for ft_never_enters)
                     else s.certAt = a.certRepeat != 0u ? s.steps + a.certRepeat : 0xffffffffu;
                 }
                 // every lane resolved (a tile whose rays all miss): refill now instead of spending an empty round
@@ -1918,7 +1920,7 @@ __device__ __forceinline__ void ft_trace_body(const FtRenderArgs& a) {
             }
             default: break;
             }
-            settle<EXT, VIEWS, SHADE, VIS>(a, s);
+            settle<EXT, FORM>(a, s);
         }
         FT_UDBG_T1(7, tRound);
     }
@@ -1950,9 +1952,8 @@ __device__ __forceinline__ void ft_trace_body(const FtRenderArgs& a) {
 
 // Occupancy hints.  The general kernels are bound by the latency of their dependent steps (grid-union walk: time falls almost in
 // proportion to the resident waves up to 5 per SIMD), so the register allocator is asked for one wave more
-// than it would settle on by itself where that costs (almost) no spills: 6 waves (80 VGPRs) for the plain kernel (1000-torus scene
-// 23.5 -> 22.4 ms; 7 waves spill and are slower), 5 waves (96 VGPRs) for its EXTENSION build (C2 + AO 16.9 -> 14.9 ms) and for the
-// kernel with on-demand sub-programs (24.7 -> 24.1 ms).
+// than it would settle on by itself where that costs (almost) no spills.  Each row of the table below carries its hint and the
+// measurement behind it; a row without one leaves the allocator alone.
 #ifndef FT_GENERAL_WAVES
 #define FT_GENERAL_WAVES 6
 #endif
@@ -1965,132 +1966,82 @@ __device__ __forceinline__ void ft_trace_body(const FtRenderArgs& a) {
 #endif
 #define FT_CALLS_OCC FT_OCC(FT_CALLS_WAVES)
 #define FT_EXT_OCC FT_OCC(FT_EXT_WAVES)
-// general scenes
-extern "C" __global__ void __launch_bounds__(FT_BLOCK) FT_OCC(FT_GENERAL_WAVES) ft_trace_kernel(const FtRenderArgs a) { ft_trace_body<0, false>(a); }
-// scenes that are one smooth union of spheres (BASELINE.json config 3/4)
-extern "C" __global__ void __launch_bounds__(FT_BLOCK) ft_trace_kernel_smooth_spheres(const FtRenderArgs a) { ft_trace_body<1, false>(a); }
-// EXTENSION builds of both (spp > 1 and / or ambient occlusion); the reference path never pays for them
-extern "C" __global__ void __launch_bounds__(FT_BLOCK) FT_EXT_OCC ft_trace_kernel_ext(const FtRenderArgs a) { ft_trace_body<0, true>(a); }
-extern "C" __global__ void __launch_bounds__(FT_BLOCK) ft_trace_kernel_smooth_spheres_ext(const FtRenderArgs a) { ft_trace_body<1, true>(a); }
-// general scenes whose unions have combinator children evaluated on demand (FT_PR_CALL, FtSceneDev.fastPath == 2)
-extern "C" __global__ void __launch_bounds__(FT_BLOCK) FT_CALLS_OCC ft_trace_kernel_calls(const FtRenderArgs a) { ft_trace_body<2, false>(a); }
-// (its EXTENSION build is held at 4 waves = 128 VGPRs: the ft_render_hits stores took it to 130, i.e. 3 waves, by themselves)
-extern "C" __global__ void __launch_bounds__(FT_BLOCK) FT_OCC(4) ft_trace_kernel_calls_ext(const FtRenderArgs a) { ft_trace_body<2, true>(a); }
-// scenes that are one grid union of plain primitives of kind K with at most two intersect / subtract steps behind it (ft_device.h "Carved union":
-// the reference's own Program.fs scene is the torus one).  No exponential anywhere: no *_libm twins; EXTENSION launches take ft_trace_kernel_ext.
-// Resident waves per SIMD asked of the register allocator: 6 (80 VGPRs) where the inlined primitive fits without spills — 7 (72) measured the same
-// and leaves no register to spare — and 5 (96) for triangles and the type switch of mixed kinds (93 registers; at 6 and more they spill into the walk).
-// Measured: profiles/r04_carved_variants.txt.
-#define FT_CARVE_KERNEL(name, kind, waves) extern "C" __global__ void __launch_bounds__(FT_BLOCK) FT_OCC(waves) name(const FtRenderArgs a) { ft_trace_body<3, false, 0, (int)(kind)>(a); }
-FT_CARVE_KERNEL(ft_trace_kernel_carved_spheres, FT_PR_SPHERE, 6)
-FT_CARVE_KERNEL(ft_trace_kernel_carved_capsules, FT_PR_CAPSULE, 6)
-FT_CARVE_KERNEL(ft_trace_kernel_carved_tori, FT_PR_TORUS, 6)
-FT_CARVE_KERNEL(ft_trace_kernel_carved_triangles, FT_PR_TRIANGLE, 5)
-FT_CARVE_KERNEL(ft_trace_kernel_carved_mixed, FT_CARVE_MIXED, 5)
-// FT_OPT_MATH = glibc: the same six with MathF.Exp / Log as glibc's expf / logf (scenes that contain a unionSmooth only; every other scene
-// has no exponential and runs the kernels above whatever the option says)
-extern "C" __global__ void __launch_bounds__(FT_BLOCK) ft_trace_kernel_libm(const FtRenderArgs a) { ft_trace_body<0, false, 1>(a); }
-extern "C" __global__ void __launch_bounds__(FT_BLOCK) ft_trace_kernel_smooth_spheres_libm(const FtRenderArgs a) { ft_trace_body<1, false, 1>(a); }
-extern "C" __global__ void __launch_bounds__(FT_BLOCK) ft_trace_kernel_ext_libm(const FtRenderArgs a) { ft_trace_body<0, true, 1>(a); }
-extern "C" __global__ void __launch_bounds__(FT_BLOCK) ft_trace_kernel_smooth_spheres_ext_libm(const FtRenderArgs a) { ft_trace_body<1, true, 1>(a); }
-extern "C" __global__ void __launch_bounds__(FT_BLOCK) ft_trace_kernel_calls_libm(const FtRenderArgs a) { ft_trace_body<2, false, 1>(a); }
-extern "C" __global__ void __launch_bounds__(FT_BLOCK) ft_trace_kernel_calls_ext_libm(const FtRenderArgs a) { ft_trace_body<2, true, 1>(a); }
-// ft_render_views: every kernel above once more with the job queue over FtRenderArgs.nViews cameras (ft_trace_body VIEWS; the builds above are
-// untouched by it), same occupancy hints
-#define FT_VIEWS_KERNEL(name, occ, ...) extern "C" __global__ void __launch_bounds__(FT_BLOCK) occ name(const FtRenderArgs a) { ft_trace_body<__VA_ARGS__, true>(a); }
-#define FT_NO_OCC
-FT_VIEWS_KERNEL(ft_trace_kernel_views, FT_OCC(FT_GENERAL_WAVES), 0, false, 0, 0)
-FT_VIEWS_KERNEL(ft_trace_kernel_smooth_spheres_views, FT_NO_OCC, 1, false, 0, 0)
-FT_VIEWS_KERNEL(ft_trace_kernel_ext_views, FT_EXT_OCC, 0, true, 0, 0)
-FT_VIEWS_KERNEL(ft_trace_kernel_smooth_spheres_ext_views, FT_NO_OCC, 1, true, 0, 0)
-FT_VIEWS_KERNEL(ft_trace_kernel_calls_views, FT_CALLS_OCC, 2, false, 0, 0)
-FT_VIEWS_KERNEL(ft_trace_kernel_calls_ext_views, FT_OCC(4), 2, true, 0, 0)
-FT_VIEWS_KERNEL(ft_trace_kernel_carved_spheres_views, FT_OCC(6), 3, false, 0, (int)FT_PR_SPHERE)
-FT_VIEWS_KERNEL(ft_trace_kernel_carved_capsules_views, FT_OCC(6), 3, false, 0, (int)FT_PR_CAPSULE)
-FT_VIEWS_KERNEL(ft_trace_kernel_carved_tori_views, FT_OCC(6), 3, false, 0, (int)FT_PR_TORUS)
-FT_VIEWS_KERNEL(ft_trace_kernel_carved_triangles_views, FT_OCC(5), 3, false, 0, (int)FT_PR_TRIANGLE)
-FT_VIEWS_KERNEL(ft_trace_kernel_carved_mixed_views, FT_OCC(5), 3, false, 0, (int)FT_CARVE_MIXED)
-FT_VIEWS_KERNEL(ft_trace_kernel_libm_views, FT_NO_OCC, 0, false, 1, 0)
-FT_VIEWS_KERNEL(ft_trace_kernel_smooth_spheres_libm_views, FT_NO_OCC, 1, false, 1, 0)
-FT_VIEWS_KERNEL(ft_trace_kernel_ext_libm_views, FT_NO_OCC, 0, true, 1, 0)
-FT_VIEWS_KERNEL(ft_trace_kernel_smooth_spheres_ext_libm_views, FT_NO_OCC, 1, true, 1, 0)
-FT_VIEWS_KERNEL(ft_trace_kernel_calls_libm_views, FT_NO_OCC, 2, false, 1, 0)
-FT_VIEWS_KERNEL(ft_trace_kernel_calls_ext_libm_views, FT_NO_OCC, 2, true, 1, 0)
-// ft_shade_hits: the reference-path kernels once more with the job queue over hit records instead of rays (ft_trace_body SHADE; the builds above are
-// untouched by it).  No EXTENSION and no views build: a relit carved scene stays on the carved walk, a lean one on the sphere loops.  The occupancy
-// hints are the siblings' (registers, waves and LDS of every twin: profiles/shade_hits_kernel_resources.txt)
-#define FT_SHADE_KERNEL(name, occ, ...) extern "C" __global__ void __launch_bounds__(FT_BLOCK) occ name(const FtRenderArgs a) { ft_trace_body<__VA_ARGS__, false, true>(a); }
-FT_SHADE_KERNEL(ft_trace_kernel_shade, FT_OCC(FT_GENERAL_WAVES), 0, false, 0, 0)
-FT_SHADE_KERNEL(ft_trace_kernel_smooth_spheres_shade, FT_NO_OCC, 1, false, 0, 0)
-FT_SHADE_KERNEL(ft_trace_kernel_calls_shade, FT_CALLS_OCC, 2, false, 0, 0)
-FT_SHADE_KERNEL(ft_trace_kernel_carved_spheres_shade, FT_OCC(6), 3, false, 0, (int)FT_PR_SPHERE)
-FT_SHADE_KERNEL(ft_trace_kernel_carved_capsules_shade, FT_OCC(6), 3, false, 0, (int)FT_PR_CAPSULE)
-FT_SHADE_KERNEL(ft_trace_kernel_carved_tori_shade, FT_OCC(6), 3, false, 0, (int)FT_PR_TORUS)
-FT_SHADE_KERNEL(ft_trace_kernel_carved_triangles_shade, FT_OCC(5), 3, false, 0, (int)FT_PR_TRIANGLE)
-FT_SHADE_KERNEL(ft_trace_kernel_carved_mixed_shade, FT_OCC(5), 3, false, 0, (int)FT_CARVE_MIXED)
-FT_SHADE_KERNEL(ft_trace_kernel_libm_shade, FT_NO_OCC, 0, false, 1, 0)
-FT_SHADE_KERNEL(ft_trace_kernel_smooth_spheres_libm_shade, FT_NO_OCC, 1, false, 1, 0)
-FT_SHADE_KERNEL(ft_trace_kernel_calls_libm_shade, FT_NO_OCC, 2, false, 1, 0)
-// ft_light_visibility: the *_shade builds once more with a visibility mask per record instead of a colour (ft_trace_body VIS; the builds above are
-// untouched by it): the same eleven, same occupancy hints (profiles/light_visibility_kernel_resources.txt)
-#define FT_VIS_KERNEL(name, occ, ...) extern "C" __global__ void __launch_bounds__(FT_BLOCK) occ name(const FtRenderArgs a) { ft_trace_body<__VA_ARGS__, false, true, true>(a); }
-FT_VIS_KERNEL(ft_trace_kernel_vis, FT_OCC(FT_GENERAL_WAVES), 0, false, 0, 0)
-FT_VIS_KERNEL(ft_trace_kernel_smooth_spheres_vis, FT_NO_OCC, 1, false, 0, 0)
-FT_VIS_KERNEL(ft_trace_kernel_calls_vis, FT_CALLS_OCC, 2, false, 0, 0)
-FT_VIS_KERNEL(ft_trace_kernel_carved_spheres_vis, FT_OCC(6), 3, false, 0, (int)FT_PR_SPHERE)
-FT_VIS_KERNEL(ft_trace_kernel_carved_capsules_vis, FT_OCC(6), 3, false, 0, (int)FT_PR_CAPSULE)
-FT_VIS_KERNEL(ft_trace_kernel_carved_tori_vis, FT_OCC(6), 3, false, 0, (int)FT_PR_TORUS)
-FT_VIS_KERNEL(ft_trace_kernel_carved_triangles_vis, FT_OCC(5), 3, false, 0, (int)FT_PR_TRIANGLE)
-FT_VIS_KERNEL(ft_trace_kernel_carved_mixed_vis, FT_OCC(5), 3, false, 0, (int)FT_CARVE_MIXED)
-FT_VIS_KERNEL(ft_trace_kernel_libm_vis, FT_NO_OCC, 0, false, 1, 0)
-FT_VIS_KERNEL(ft_trace_kernel_smooth_spheres_libm_vis, FT_NO_OCC, 1, false, 1, 0)
-FT_VIS_KERNEL(ft_trace_kernel_calls_libm_vis, FT_NO_OCC, 2, false, 1, 0)
-// The one table of trace kernels, for launches and occupancy queries alike.  variant: the kernel family (FtSceneDev.fastPath as capi.cpp planTrace
-// decides it: 0 general, 1 lean smooth-sphere, 2 general with call children, 3 carved union).  nullptr where no kernel exists: a carved union has
-// no EXTENSION and no *_libm build.  views: the ft_render_views build of the same kernel.  shade: the ft_shade_hits build (no EXTENSION, no views), 2: its
-// ft_light_visibility twin.
-static const void* ft_trace_kernel_for(unsigned variant, unsigned carveKind, bool ext, bool libm, bool views, unsigned shade) {
-    if (shade) {
-        static const void* const twins[2][3][2] = {      // [vis][variant][libm]
-            {{(const void*)ft_trace_kernel_shade, (const void*)ft_trace_kernel_libm_shade},
-             {(const void*)ft_trace_kernel_smooth_spheres_shade, (const void*)ft_trace_kernel_smooth_spheres_libm_shade},
-             {(const void*)ft_trace_kernel_calls_shade, (const void*)ft_trace_kernel_calls_libm_shade}},
-            {{(const void*)ft_trace_kernel_vis, (const void*)ft_trace_kernel_libm_vis},
-             {(const void*)ft_trace_kernel_smooth_spheres_vis, (const void*)ft_trace_kernel_smooth_spheres_libm_vis},
-             {(const void*)ft_trace_kernel_calls_vis, (const void*)ft_trace_kernel_calls_libm_vis}}};
-        const bool vis = shade == 2u;
-        if (ext || views || shade > 2u) return nullptr;
-        if (variant < 3) return twins[vis][variant][libm];
-        if (variant > 3 || libm) return nullptr;
-        switch (carveKind) {
-            case FT_PR_SPHERE: return vis ? (const void*)ft_trace_kernel_carved_spheres_vis : (const void*)ft_trace_kernel_carved_spheres_shade;
-            case FT_PR_CAPSULE: return vis ? (const void*)ft_trace_kernel_carved_capsules_vis : (const void*)ft_trace_kernel_carved_capsules_shade;
-            case FT_PR_TORUS: return vis ? (const void*)ft_trace_kernel_carved_tori_vis : (const void*)ft_trace_kernel_carved_tori_shade;
-            case FT_PR_TRIANGLE: return vis ? (const void*)ft_trace_kernel_carved_triangles_vis : (const void*)ft_trace_kernel_carved_triangles_shade;
-            default: return vis ? (const void*)ft_trace_kernel_carved_mixed_vis : (const void*)ft_trace_kernel_carved_mixed_shade;
-        }
+
+// The one table of trace-kernel builds.  A row: name stem, occupancy hint, then ft_trace_body's VARIANT (the kernel family: FtSceneDev.fastPath as
+// capi.cpp planTrace decides it), EXT (`true` / `false` literally: the forms below select on it), MATH and K.  A new kernel family is one row here.
+#define FT_TRACE_BUILDS(X, ...) \
+    /* general scenes: 6 waves (80 VGPRs), 1000-torus scene 23.5 -> 22.4 ms; 7 waves spill and are slower */ \
+    X(__VA_ARGS__, , FT_OCC(FT_GENERAL_WAVES), 0, false, 0, 0) \
+    /* scenes that are one smooth union of spheres (BASELINE.json config 3/4) */ \
+    X(__VA_ARGS__, _smooth_spheres, , 1, false, 0, 0) \
+    /* EXTENSION builds of both (spp > 1 and / or ambient occlusion); the reference path never pays for them.  5 waves (96 VGPRs) for the */ \
+    /* general one: C2 + AO 16.9 -> 14.9 ms */ \
+    X(__VA_ARGS__, _ext, FT_EXT_OCC, 0, true, 0, 0) \
+    X(__VA_ARGS__, _smooth_spheres_ext, , 1, true, 0, 0) \
+    /* general scenes whose unions have combinator children evaluated on demand (FT_PR_CALL, FtSceneDev.fastPath == 2): 5 waves, 24.7 -> 24.1 ms */ \
+    X(__VA_ARGS__, _calls, FT_CALLS_OCC, 2, false, 0, 0) \
+    /* (its EXTENSION build is held at 4 waves = 128 VGPRs: the ft_render_hits stores took it to 130, i.e. 3 waves, by themselves) */ \
+    X(__VA_ARGS__, _calls_ext, FT_OCC(4), 2, true, 0, 0) \
+    /* scenes that are one grid union of plain primitives of kind K with at most two intersect / subtract steps behind it (ft_device.h "Carved */ \
+    /* union": the reference's own Program.fs scene is the torus one).  No exponential anywhere: no *_libm twins; EXTENSION launches take */ \
+    /* ft_trace_kernel_ext.  Resident waves per SIMD asked of the register allocator: 6 (80 VGPRs) where the inlined primitive fits without */ \
+    /* spills - 7 (72) measured the same and leaves no register to spare - and 5 (96) for triangles and the type switch of mixed kinds (93 */ \
+    /* registers; at 6 and more they spill into the walk).  Measured: profiles/r04_carved_variants.txt. */ \
+    X(__VA_ARGS__, _carved_spheres, FT_OCC(6), 3, false, 0, FT_PR_SPHERE) \
+    X(__VA_ARGS__, _carved_capsules, FT_OCC(6), 3, false, 0, FT_PR_CAPSULE) \
+    X(__VA_ARGS__, _carved_tori, FT_OCC(6), 3, false, 0, FT_PR_TORUS) \
+    X(__VA_ARGS__, _carved_triangles, FT_OCC(5), 3, false, 0, FT_PR_TRIANGLE) \
+    X(__VA_ARGS__, _carved_mixed, FT_OCC(5), 3, false, 0, FT_CARVE_MIXED)      /* boxes (EXTENSION) and mixed kinds */ \
+    /* FT_OPT_MATH = glibc: the first six with MathF.Exp / Log as glibc's expf / logf (scenes that contain a unionSmooth only; every other */ \
+    /* scene has no exponential and runs the kernels above whatever the option says) */ \
+    X(__VA_ARGS__, _libm, , 0, false, 1, 0) \
+    X(__VA_ARGS__, _smooth_spheres_libm, , 1, false, 1, 0) \
+    X(__VA_ARGS__, _ext_libm, , 0, true, 1, 0) \
+    X(__VA_ARGS__, _smooth_spheres_ext_libm, , 1, true, 1, 0) \
+    X(__VA_ARGS__, _calls_libm, , 2, false, 1, 0) \
+    X(__VA_ARGS__, _calls_ext_libm, , 2, true, 1, 0)
+// The forms (ft_kernels.h FT_FORM_*): every build once per form, under the name stem + suffix and with its row's hint (registers, waves and LDS of
+// every twin: profiles/shade_hits_kernel_resources.txt, profiles/light_visibility_kernel_resources.txt).  A form line: FORM, suffix, the rows it takes.
+// A new form is one line here.
+//   frame or ray buffer  the job queue over the pixels of one camera, or over a ray buffer
+//   _views               ft_render_views: the job queue over FtRenderArgs.nViews cameras
+//   _shade               ft_shade_hits: the job queue over hit records instead of rays.  The reference path only: a relit carved scene stays on the
+//                        carved walk, a lean one on the sphere loops
+//   _vis                 ft_light_visibility: the *_shade builds with a visibility mask per record instead of a colour
+// _shade and _vis take the rows with EXT == false: this is the one place that says so (ft_trace_body asserts it).
+#define FT_ROWS_ALL_false(...) __VA_ARGS__
+#define FT_ROWS_ALL_true(...) __VA_ARGS__
+#define FT_ROWS_NO_EXT_false(...) __VA_ARGS__
+#define FT_ROWS_NO_EXT_true(...)
+#define FT_TRACE_FORMS(X) \
+    FT_TRACE_BUILDS(X, FT_FORM_FRAME, , FT_ROWS_ALL) \
+    FT_TRACE_BUILDS(X, FT_FORM_VIEWS, _views, FT_ROWS_ALL) \
+    FT_TRACE_BUILDS(X, FT_FORM_SHADE, _shade, FT_ROWS_NO_EXT) \
+    FT_TRACE_BUILDS(X, FT_FORM_VIS, _vis, FT_ROWS_NO_EXT)
+
+// the 17 + 17 + 11 + 11 kernels
+#define FT_TRACE_KERNEL(FORM, suffix, rows, stem, occ, VARIANT, EXT, MATH, K) \
+    rows##_##EXT(extern "C" __global__ void __launch_bounds__(FT_BLOCK) occ ft_trace_kernel##stem##suffix(const FtRenderArgs a) { ft_trace_body<VARIANT, EXT, MATH, (int)(K), FORM>(a); })
+FT_TRACE_FORMS(FT_TRACE_KERNEL)
+
+// ... and their lookup, for launches and occupancy queries alike: the row whose variant, EXT, math and form are the key's; among the carved rows
+// (variant 3, the only ones whose kind is looked at) the one of the key's kind, or the mixed one where that kind has no row of its own.  nullptr
+// where no kernel exists: variant > 3, a carved union with EXTENSION or glibc math, a shade form with EXTENSION, FT_FORM_NONE.
+struct FtTraceRow { uint32_t variant, kind; bool ext, libm; uint32_t form; const void* handle; };
+#define FT_TRACE_ROW(FORM, suffix, rows, stem, occ, VARIANT, EXT, MATH, K) \
+    rows##_##EXT({VARIANT, (uint32_t)(K), EXT, MATH != 0, FORM, (const void*)ft_trace_kernel##stem##suffix},)
+static const void* ft_trace_kernel_of(const FtTraceKey& k) {
+    static const FtTraceRow table[] = {FT_TRACE_FORMS(FT_TRACE_ROW)};
+    const void* mixed = nullptr;
+    for (const FtTraceRow& r : table) {
+        if (r.variant != k.variant || r.ext != k.ext || r.libm != k.libm || r.form != k.form) continue;
+        if (k.variant != 3u || r.kind == k.carveKind) return r.handle;
+        if (r.kind == FT_CARVE_MIXED) mixed = r.handle;
     }
-    static const void* const families[2][3][2][2] = {     // [views][variant][libm][ext]
-        {{{(const void*)ft_trace_kernel, (const void*)ft_trace_kernel_ext}, {(const void*)ft_trace_kernel_libm, (const void*)ft_trace_kernel_ext_libm}},
-         {{(const void*)ft_trace_kernel_smooth_spheres, (const void*)ft_trace_kernel_smooth_spheres_ext},
-          {(const void*)ft_trace_kernel_smooth_spheres_libm, (const void*)ft_trace_kernel_smooth_spheres_ext_libm}},
-         {{(const void*)ft_trace_kernel_calls, (const void*)ft_trace_kernel_calls_ext}, {(const void*)ft_trace_kernel_calls_libm, (const void*)ft_trace_kernel_calls_ext_libm}}},
-        {{{(const void*)ft_trace_kernel_views, (const void*)ft_trace_kernel_ext_views},
-          {(const void*)ft_trace_kernel_libm_views, (const void*)ft_trace_kernel_ext_libm_views}},
-         {{(const void*)ft_trace_kernel_smooth_spheres_views, (const void*)ft_trace_kernel_smooth_spheres_ext_views},
-          {(const void*)ft_trace_kernel_smooth_spheres_libm_views, (const void*)ft_trace_kernel_smooth_spheres_ext_libm_views}},
-         {{(const void*)ft_trace_kernel_calls_views, (const void*)ft_trace_kernel_calls_ext_views},
-          {(const void*)ft_trace_kernel_calls_libm_views, (const void*)ft_trace_kernel_calls_ext_libm_views}}},
-    };
-    if (variant < 3) return families[views][variant][libm][ext];
-    if (variant > 3 || ext || libm) return nullptr;
-    switch (carveKind) {
-        case FT_PR_SPHERE: return views ? (const void*)ft_trace_kernel_carved_spheres_views : (const void*)ft_trace_kernel_carved_spheres;
-        case FT_PR_CAPSULE: return views ? (const void*)ft_trace_kernel_carved_capsules_views : (const void*)ft_trace_kernel_carved_capsules;
-        case FT_PR_TORUS: return views ? (const void*)ft_trace_kernel_carved_tori_views : (const void*)ft_trace_kernel_carved_tori;
-        case FT_PR_TRIANGLE: return views ? (const void*)ft_trace_kernel_carved_triangles_views : (const void*)ft_trace_kernel_carved_triangles;
-        default: return views ? (const void*)ft_trace_kernel_carved_mixed_views : (const void*)ft_trace_kernel_carved_mixed;   // boxes (EXTENSION) and mixed kinds
-    }
+    return mixed;
+}
+extern "C" const void* ft_trace_kernel_for(unsigned variant, unsigned carveKind, bool ext, bool libm, bool views, unsigned shade) {
+    return ft_trace_kernel_of(FtTraceKey{variant, carveKind, ft_trace_form(views, shade), ext, libm});
 }
 
 // ft_shade_visible: SdfScene.fs:11-28 with every `light.Intensity scene.Object ray` answered by a bit of the record's visibility mask instead of a march.
@@ -2429,16 +2380,16 @@ extern "C" int ft_debug_set_hsaco(const char* path) {
 }
 #endif
 extern "C" hipError_t ft_launch_trace(const FtRenderArgs* a, unsigned blocks, size_t ldsBytes, hipStream_t st) {
-    const bool ext = a->ext != 0u, libm = a->math != 0u;
+    const FtTraceKey key = ft_trace_key(*a);
 #ifdef FT_EXPERIMENT
-    if (a->S.fastPath == 1 && !ext && !libm && !a->views && !a->shade && ft_exp_fn) {
+    if (key.variant == 1u && key.form == FT_FORM_FRAME && !key.ext && !key.libm && ft_exp_fn) {
         FtRenderArgs args = *a;
         size_t size = sizeof(args);
         void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &args, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
         return hipModuleLaunchKernel(ft_exp_fn, blocks, 1, 1, FT_BLOCK, 1, 1, (unsigned)ldsBytes, st, nullptr, extra);
     }
 #endif
-    const void* k = ft_trace_kernel_for(a->S.fastPath, a->carve.kind, ext, libm, a->views != nullptr, a->shade);
+    const void* k = ft_trace_kernel_of(key);
     if (!k) return hipErrorInvalidDeviceFunction;
     FtRenderArgs args = *a;
     void* kp[] = {&args};
@@ -2538,8 +2489,8 @@ extern "C" hipError_t ft_launch_shade_visible(const FtLight* lights, uint32_t nL
     hipLaunchKernelGGL(ft_shade_visible_kernel, dim3(blocks), dim3(FT_BLOCK), 0, st, lights, nLights, bg[0], bg[1], bg[2], hits, vis, n, out);
     return hipGetLastError();
 }
-extern "C" hipError_t ft_trace_occupancy(unsigned fastPath, unsigned carveKind, bool ext, bool libm, bool views, unsigned shade, size_t ldsBytes, int* blocksPerCU) {
-    const void* k = ft_trace_kernel_for(fastPath, carveKind, ext, libm, views, shade);
+extern "C" hipError_t ft_trace_occupancy(const FtTraceKey& key, size_t ldsBytes, int* blocksPerCU) {
+    const void* k = ft_trace_kernel_of(key);
     if (!k) return hipErrorInvalidDeviceFunction;
     return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocksPerCU, k, FT_BLOCK, ldsBytes);
 }
