@@ -3,6 +3,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <string>
@@ -218,6 +219,9 @@ int uploadScene(ft_ctx* c, ft_scene* s) {
 // miss certificate (FT_OPT_CERT_POLICY layout): primary rays from their first evaluation, shadow rays from their 6th step, a wave runs the certificate
 // once 16 of its lanes are due, and a ray it fails on is due again 6 steps later (DESIGN.md section 4 "Miss certificate": the policies measured)
 constexpr int FT_CERT_POLICY_DEFAULT = 0 | (6 << 8) | (16 << 16) | (6 << 24);
+// the bundle certificate's shipped schedule (bits 30-31 of the policy word = 0): every 2nd evaluation round of a wave, from one primary ray on, and from one
+// shadow ray of 2 or more steps on (DESIGN.md section 5 "Bundle certificate on C3": the schedules measured)
+constexpr uint32_t FT_BUNDLE_PERIOD = 2u, FT_BUNDLE_MIN = 1u, FT_BUNDLE_SHADOW = 2u;
 constexpr int FT_TAIL_K_LEAN = 32, FT_TAIL_K_GENERAL = 2, FT_TAIL_K_CARVED = 1;      // carved: 1.26 ms at 0 / 1 against 1.29 at 2 on the 1000^2 Program.fs frame (profiles/r04_carved_variants.txt)
 // does this launch take the glibc build of the kernels?
 bool libmLaunch(const ft_ctx* c, const ft_scene* s) { return c->optMath != FT_MATH_FIXED && s->usesExpLog; }
@@ -341,7 +345,26 @@ int launchTrace(ft_ctx* c, const ft_scene* s, FtRenderArgs& a, int lane = 0) {
         a.certPrim = (pol & 255u) == 255u ? 0xffffffffu : (pol & 255u);
         a.certShadow = ((pol >> 8) & 255u) == 255u ? 0xffffffffu : ((pol >> 8) & 255u);
         a.certMin = (pol >> 16) & 255u;
-        a.certRepeat = pol >> 24;
+        a.certRepeat = (pol >> 24) & 63u;
+        // bits 30-31: the bundle certificate's schedule — 0 shipped, 1 every round from one member on, 2 every second round, 3 off
+        const uint32_t bundle = pol >> 30;
+        a.bundlePeriod = bundle == 0u ? FT_BUNDLE_PERIOD : bundle == 3u ? 0u : bundle;
+        a.bundleMin = bundle == 0u ? FT_BUNDLE_MIN : 1u;
+        a.bundleShadow = bundle == 0u ? FT_BUNDLE_SHADOW : bundle == 2u ? 2u : 0u;
+        // Word 0 on a camera frame whose 8x8 tiles are narrower, at the far side of the support sphere, than the margin certM that every certificate concedes anyway:
+        // the bundle's width W stays below certM, so its bound loses next to nothing against its members' own and the per-lane tries only cost; they are left
+        // out (what 255 / 255 in an explicit word asks for).  Wider tiles (smaller frames, wider lenses), views and ray buffers keep both.  Measured on either
+        // side of the criterion, by frame size, lens and scene: DESIGN.md section 5 "Bundle certificate on C3", profiles/r06_bundle_certificate_tile_width.txt
+        if (c->optCertPolicy == 0 && a.cert && a.mode == 0u && a.views == nullptr && a.maxSize > 0.0f) {
+            const float* cm = a.cam;
+            const double dx = (double)cm[0] - s->dev.escC[0], dy = (double)cm[1] - s->dev.escC[1], dz = (double)cm[2] - s->dev.escC[2];
+            const double up = std::sqrt((double)cm[6] * cm[6] + (double)cm[7] * cm[7] + (double)cm[8] * cm[8]);
+            const double rt = std::sqrt((double)cm[9] * cm[9] + (double)cm[10] * cm[10] + (double)cm[11] * cm[11]);
+            const double fw = std::sqrt((double)cm[3] * cm[3] + (double)cm[4] * cm[4] + (double)cm[5] * cm[5]);
+            const double reach = std::sqrt(dx * dx + dy * dy + dz * dz) + (double)s->dev.escR;
+            const double tile = 8.0 * std::max(up, rt) / (double)a.maxSize * reach / fw;                // an 8x8 tile's side at distance `reach`
+            if (fw > 0.0 && tile <= (double)s->dev.certM) a.certPrim = a.certShadow = 0xffffffffu;
+        }
     }
     a.lazy = c->optLazyUnion ? 1u : 0u;
     a.reuse = (c->optReuse && !a.shade) ? 1u : 0u;     // ft_shade_hits: no centre probe ran, nothing to reuse

@@ -93,6 +93,9 @@ struct FtRenderArgs {
     uint32_t visSel, visKeep; // select & (2^nLights - 1); ~select & (2^nLights - 1)
     const uint32_t* visIn;    // NULL: nothing kept; may equal visOut (a lane reads its word before it writes it)
     uint32_t* visOut;
+    // bundle certificate (lean kernel; kernels.hip ft_bundle_certificate; appended): tried every bundlePeriod-th evaluation round of a wave (0: never) for its
+    // primary rays and for its shadow rays of at least bundleShadow steps, each where at least bundleMin (>= 1) lanes hold such a ray; needs cert
+    uint32_t bundlePeriod, bundleMin, bundleShadow;
 };
 #define FT_MAX_VIEWS 64       // views per launch (one PH_CAM value per lane); ft_render_views splits larger batches
 

@@ -1331,6 +1331,22 @@ __device__ __forceinline__ bool ft_never_enters(const FtSceneDev& S, const f3 o,
     return cc * dd - b * b > tol * dd;
 }
 
+// The gate and the clipped segment that both miss certificates below share (ft_miss_certificate, ft_bundle_certificate): -> the lane passes the gate and its line o + t dir has a non-empty part t0 < t < t1 inside the
+// clip ball (t0 >= 0, t1 <= Length * certLenF).
+__device__ __forceinline__ bool ft_cert_segment(const FtSceneDev& S, bool test, const f3 o, const f3 dir, float eps, float len, uint32_t steps,
+                                                float& t0, float& t1) {
+    const f3 w = o - mk3(S.escC[0], S.escC[1], S.escC[2]);
+    const float ww = ft_dot(w, w), dd = ft_dot(dir, dir), b = ft_dot(w, dir);
+    bool ok = test && S.certM >= 0.0f && S.escR >= 0.0f && eps >= 0.0f && eps <= S.escR && len > 0.0f && len < 1e9f && dd >= 0.81f && dd <= 1.44f &&
+              ww <= S.certRho2 && steps < FT_STEP_CAP - S.certSteps;
+    const float R = (S.escR + eps + S.certClip) * 1.001f;              // the 0.1 % covers the rounding of the end points below
+    const float disc = b * b - dd * (ww - R * R);
+    ok = ok && disc > 0.0f;
+    const float sq = __builtin_amdgcn_sqrtf(ok ? disc : 0.0f), idd = 1.0f / dd;
+    t0 = __builtin_fmaxf((-b - sq) * idd, 0.0f); t1 = __builtin_fminf((sq - b) * idd, len * S.certLenF);
+    return ok && t1 > t0;
+}
+
 // ------------------------------------------------------------------------------------------------
 // Miss certificate (FT_OPT_CERT; lean kernel and its EXTENSION build, paths outside glass bodies).  The scene is ONE smooth union of staged spheres, f(x) = -s ln sum_i exp(si d_i(x))
 // with si = -1 / s < 0 (SdfForm.fs:75-82), so on a segment S every term is at most exp(si dmin_i), dmin_i = dist(S, c_i) - r_i, and
@@ -1351,16 +1367,8 @@ __device__ __forceinline__ bool ft_miss_certificate(const FtSceneDev& S, const f
     const float si = in->f0;
     const uint32_t n = in->count;
     const float4* c = reinterpret_cast<const float4*>(ldsC + in->data);
-    const f3 w = o - mk3(S.escC[0], S.escC[1], S.escC[2]);
-    const float ww = ft_dot(w, w), dd = ft_dot(dir, dir), b = ft_dot(w, dir);
-    bool ok = test && S.certM >= 0.0f && S.escR >= 0.0f && eps >= 0.0f && eps <= S.escR && len > 0.0f && len < 1e9f && dd >= 0.81f && dd <= 1.44f &&
-              ww <= S.certRho2 && steps < FT_STEP_CAP - S.certSteps;
-    const float R = (S.escR + eps + S.certClip) * 1.001f;              // the 0.1 % covers the rounding of the end points below
-    const float disc = b * b - dd * (ww - R * R);
-    ok = ok && disc > 0.0f;
-    const float sq = __builtin_amdgcn_sqrtf(ok ? disc : 0.0f), idd = 1.0f / dd;
-    const float t0 = __builtin_fmaxf((-b - sq) * idd, 0.0f), t1 = __builtin_fminf((sq - b) * idd, len * S.certLenF);
-    ok = ok && t1 > t0;
+    float t0, t1;
+    bool ok = ft_cert_segment(S, test, o, dir, eps, len, steps, t0, t1);
     const float A = si * 1.44269504f;                                  // terms are 2^(A (dist - r))
     const float xt = A * (eps + S.certM);
     ok = ok && xt >= -100.0f;                                          // the threshold stays a normal number, far above flushed terms
@@ -1418,6 +1426,74 @@ __device__ __forceinline__ bool ft_miss_certificate(const FtSceneDev& S, const f
     }
     for (; i < n; ++i) sum += term(c[i]);
     return ok && sum < thr;
+}
+
+// Bundle certificate: ONE test for all the rays of the wave that ask (`cand`), with the children spread over the lanes as in ft_cull_children.  What pays
+// is ending all marching lanes of a tile together (a wave's round count is its longest lane's), and whether that is possible is a property of the tile's
+// bundle of rays.  Members are the candidates that pass ft_cert_segment: exactly the lanes ft_miss_certificate would test, with the same segments
+// o_l + t dir_l, t0_l <= t <= t1_l.  The others are left out and keep marching.
+// Axis: the line o_c + sigma d_c of one member (the first at or after lane 27, else the first: the middle of an 8x8 tile), d_c = its direction as it is.
+// For member l let s_l = (o_l - o_c).d_c / |d_c|^2, a_l = |o_l - o_c - s_l d_c|, b_l = |dir_l - d_c|.  Then for t0_l <= t <= t1_l
+//     (o_l + t dir_l) - (o_c + (s_l + t) d_c)  =  (o_l - o_c - s_l d_c) + t (dir_l - d_c),    of length <= a_l + b_l t1_l      (t >= t0_l >= 0)
+// — an identity in s_l, so neither the rounding of s_l nor |d_c| != 1 matters (for unit directions t is the arc length).  With W >= max_l (a_l + b_l t1_l)
+// and I = [min_l (s_l + t0_l), max_l (s_l + t1_l)] every point x of every member's segment has an axis point y, sigma in I, with |x - y| <= W, hence
+//     d_i(x) >= dist(I, c_i) - W - r_i   for every child i,   and that is <= the member's own dmin_i = dist(S_l, c_i) - r_i.
+// So the bundle's sum  sum_i 2^(A (dist(I, c_i) - W - r_i))  is >= every member's sum in ft_miss_certificate: where it is below the threshold of the
+// strictest member (the largest epsilon), every member's own flat certificate holds, and each takes that certificate's exit.  certM and the other
+// constants keep their values.  Float32: W is padded by 0.1 % + 1e-6 + 4e-6 R and I by 4e-6 R at either end (R: the clip radius; every coordinate
+// difference here is <= 5 escR, so each of the few roundings of a_l, b_l t1_l, s_l + t and the reductions' end points is below 2^-23 of 10 escR);
+// the axis segment's end points, projection, v_sqrt_f32 / v_exp_f32 are ft_miss_certificate's own (scene.cpp eGeo: 16u (|escC|inf + 10 escR));
+// the sum is a tree of 6 + passes roundings per term instead of n, inside eSum's (2n + 4096) 2^-23, and the threshold carries the same 0.9999.
+// Cost: 4 wave maxima, 8 v_readlane and n / 64 passes of ~20 VALU — about 200 wave-instructions for 256 children, whatever the number of members.
+// Executed by all 64 lanes.  minMembers >= 1.  -> this lane is a member and the bundle holds.
+__device__ __forceinline__ bool ft_bundle_certificate(const FtSceneDev& S, const float* __restrict__ ldsC, bool cand, const f3 o, const f3 dir, float eps, float len,
+                                                      uint32_t steps, uint32_t minMembers) {
+    float t0, t1;
+    const bool mem = ft_cert_segment(S, cand, o, dir, eps, len, steps, t0, t1);
+    const unsigned long long mm = __ballot(mem);
+    if (mm == 0ull || (uint32_t)__popcll(mm) < minMembers) return false;
+    const FtInstr FT_CONST* in = as_const(S.instr);                    // instruction 0: the run
+    const float A = in->f0 * 1.44269504f;
+    const uint32_t n = in->count;
+    const float4* c = reinterpret_cast<const float4*>(ldsC + in->data);
+    const int ax = (mm >> 27) != 0ull ? 26 + __ffsll((long long)(mm >> 27)) : __ffsll((long long)mm) - 1;
+    const f3 oc = ft_readlane3(o, ax), dc = ft_readlane3(dir, ax);
+    const float tc0 = ft_readlane_f(t0, ax), tc1 = ft_readlane_f(t1, ax);      // the axis lane's own interval (s = 0): tc0 < tc1
+    const f3 g = o - oc, h = dir - dc;
+    const float sl = ft_dot(g, dc) * (1.0f / ft_dot(dc, dc));
+    const float ex = __builtin_fmaf(-sl, dc.x, g.x), ey = __builtin_fmaf(-sl, dc.y, g.y), ez = __builtin_fmaf(-sl, dc.z, g.z);
+    const float al = __builtin_amdgcn_sqrtf(__builtin_fmaf(ez, ez, __builtin_fmaf(ey, ey, ex * ex)));
+    const float bl = __builtin_amdgcn_sqrtf(__builtin_fmaf(h.z, h.z, __builtin_fmaf(h.y, h.y, h.x * h.x)));
+    // maxima of values >= 0 (other lanes: 0).  A member's values are finite: a NaN or infinite origin or direction fails the gate (dd, ww), so ft_wave_max_all's
+    // v >= 0 holds in every lane; a NaN that got through all the same would be dropped by v_max and is why W is tested as !(W <= escR).  The interval's ends as distances from the axis lane's own: tc1 - lo_l and hi_l - tc0 are >= tc1 - tc0 > 0 there
+    const float Wr = ft_wave_max_all(mem ? __builtin_fmaf(bl, t1, al) : 0.0f);
+    const float epsMax = ft_wave_max_all(mem ? eps : 0.0f);
+    const float Rc = (S.escR + epsMax + S.certClip) * 1.001f;
+    const float W = Wr * 1.001f + (1e-6f + 4e-6f * Rc);
+    const float xt = A * (epsMax + S.certM);
+    if (!(W <= S.escR) || !(xt >= -100.0f)) return false;              // unrelated rays (or a NaN): no bound worth its passes; the threshold stays a normal number
+    const float dLo = ft_wave_max_all(mem ? __builtin_fmaxf(tc1 - (sl + t0), 0.0f) : 0.0f);
+    const float dHi = ft_wave_max_all(mem ? __builtin_fmaxf((sl + t1) - tc0, 0.0f) : 0.0f);
+    const float i0 = (tc1 - dLo) - 4e-6f * Rc, i1 = (tc0 + dHi) + 4e-6f * Rc;
+    const f3 p0 = oc + dc * i0, sv = dc * (i1 - i0);                   // the axis segment p0 + t sv, 0 <= t <= 1
+    const float iss = 1.0f / ft_dot(sv, sv);
+    const float thr = __builtin_amdgcn_exp2f(xt) * 0.9999f;
+    const uint32_t lane = threadIdx.x & 63u;
+    float sum = 0.0f;
+    for (uint32_t base = 0; base < n; base += 64u) {
+        const uint32_t i = base + lane;
+        const float4 prm = c[i < n ? i : n - 1u];
+        const float vx = prm.x - p0.x, vy = prm.y - p0.y, vz = prm.z - p0.z;
+        float t = __builtin_fmaf(vz, sv.z, __builtin_fmaf(vy, sv.y, vx * sv.x)) * iss;
+        t = __builtin_amdgcn_fmed3f(t, 0.0f, 1.0f);
+        const float qx = __builtin_fmaf(-t, sv.x, vx), qy = __builtin_fmaf(-t, sv.y, vy), qz = __builtin_fmaf(-t, sv.z, vz);
+        const float q = __builtin_fmaf(qz, qz, __builtin_fmaf(qy, qy, qx * qx));
+        const float term = __builtin_amdgcn_exp2f((__builtin_amdgcn_sqrtf(q) - (prm.w + W)) * A);
+        sum += i < n ? term : 0.0f;
+    }
+    float total;
+    ft_wave_scan_incl(sum, total);
+    return mem && total < thr;                                         // a NaN anywhere: fails
 }
 
 // The first step of a ray that starts at the hit position, from the distance already known there (FT_SH_D0): exactly what the round's switch does with an
@@ -1782,18 +1858,33 @@ __device__ __forceinline__ void ft_trace_body(const FtRenderArgs& a) {
         if (s.phase == PH_IDLE && exhausted && chunkNext == chunkEnd) s.phase = PH_DONE;
         if (__ballot(s.phase != PH_DONE) == 0ull) break;
 
-        // ---- miss certificate (lean kernel): once enough lanes are due, the wave tries it for all of them at once ("Miss certificate") ----
+        // ---- miss certificates (lean kernel; "Miss certificate") ----
         if (VARIANT == 1 && a.cert != 0u) {                          // EXTENSION builds: not inside a glass body (the march runs on -Distance there)
-            const bool due = (s.phase == PH_MARCH || s.phase == PH_SHADOW) && s.steps >= s.certAt && (!EXT || !s.inside());
+            // the bundle of the wave's primary rays, then that of its shadow rays (never mixed: one axis serves one family of directions), every
+            // bundlePeriod-th evaluation round of the wave; a bundle that fails changes nothing
+            bool ends = false;
+            if (a.bundlePeriod != 0u && waveEvals % a.bundlePeriod == 0u) {
+#pragma unroll 1
+                for (uint32_t ph = SHADE ? PH_SHADOW : PH_MARCH; ph <= PH_SHADOW; ph += PH_SHADOW - PH_MARCH) {
+                    const bool cand = s.phase == ph && (ph == PH_MARCH || s.steps >= a.bundleShadow) && (!EXT || !s.inside());
+                    if ((uint32_t)__popcll(__ballot(cand)) < a.bundleMin) continue;
+                    if (ft_bundle_certificate(a.S, ldsC + 0, cand, s.o, s.dir, s.eps, s.len, s.steps, a.bundleMin)) ends = true;
+                }
+            }
+            // per lane: once enough lanes are due, the wave tries it for all of them at once
+            const bool due = !ends && (s.phase == PH_MARCH || s.phase == PH_SHADOW) && s.steps >= s.certAt && (!EXT || !s.inside());
+            bool tried = false;
             if ((uint32_t)__popcll(__ballot(due)) >= a.certMin) {
+                tried = true;
                 const bool holds = ft_miss_certificate(a.S, ldsC + 0, due, s.o, s.dir, s.eps, s.len, s.steps);
                 if (due) {
-                    if (holds) { s.len = -1.0f; settle<EXT, FORM>(a, s); }    // resolved as the miss its march ends in (settle: as for ft_never_enters)
+                    if (holds) ends = true;
                     else s.certAt = a.certRepeat != 0u ? s.steps + a.certRepeat : 0xffffffffu;
                 }
-                // every lane resolved (a tile whose rays all miss): refill now instead of spending an empty round
-                if (__ballot(s.phase >= PH_MARCH) == 0ull) continue;
             }
+            if (ends) { s.len = -1.0f; settle<EXT, FORM>(a, s); }             // resolved as the miss its march ends in (settle: as for ft_never_enters)
+            // every lane resolved (a tile whose rays all miss): refill now instead of spending an empty round
+            if ((tried || __ballot(ends) != 0ull) && __ballot(s.phase >= PH_MARCH) == 0ull) continue;
         }
 
         // ---- one scene-SDF evaluation per active lane -----------------------------------------

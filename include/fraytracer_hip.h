@@ -136,7 +136,11 @@ typedef enum ft_option {
     FT_OPT_CERT = 14,             /* 1 (default): the smooth-union-of-spheres kernel ends a ray as a miss once a bound over the rest of its line proves that no later
                                    * evaluation can come below epsilon (exact: same frame, counters and flags, fewer sdf_evals); only while FT_OPT_ESCAPE is on; 0: off */
     FT_OPT_CERT_POLICY = 15,      /* 0 (default policy) or, for experiments, when the miss certificate is tried: bits 0-7 the primary ray's step (255: never),
-                                   * 8-15 the shadow ray's step (255: never), 16-23 the due lanes a wave waits for (1 .. 64), 24-31 steps to the next try (0: once) */
+                                   * 8-15 the shadow ray's step (255: never), 16-23 the due lanes a wave waits for (1 .. 64), 24-29 steps to the next try (0: once), 30-31 the
+                                   * bundle certificate (one test per wave for all its primary, then all its shadow rays): 0 the shipped schedule, 1 every evaluation round
+                                   * from one ray on, 2 every second round (shadow rays from their 2nd step), 3 off.  255 / 255 in bits 0-15: the bundle alone.
+                                   * Word 0 = 0 | 6 << 8 | 16 << 16 | 6 << 24 with the shipped bundle schedule, except that a camera frame (ft_render and its hits form) whose 8x8 pixel tiles are at most
+                                   * the certificate's margin wide at the far side of the scene's support sphere gets the bundle alone (255 / 255): an explicit word is always taken as it stands */
     FT_OPT_GUIDED = 7             /* 1: the last jobs of a launch are handed out in half and quarter tiles (lean kernel); 0 (default): whole tiles only */
 } ft_option;
 /* MathF.Exp / MathF.Log (SdfForm.unionSmooth, SdfForm.fs:80,82) and MathF.Pow (FColor.gammaInverse, FColor.fs:50-55) are the C runtime's
