@@ -319,6 +319,11 @@ template <int PW> __device__ __forceinline__ float ft_strength_times_diff(float 
 }
 __device__ __forceinline__ int ft_strength_pw(float si) { return si == -2.0f ? 1 : (si == -4.0f ? 2 : (si == -0.5f ? 3 : 0)); }
 
+// |c - p|^2 of a staged sphere record (c, r), in Vector3.Distance's order of operations (SdfForm.fs:129)
+__device__ __forceinline__ float ft_sphere_q(const float4 prm, const f3 p) {
+    const float dx = prm.x - p.x, dy = prm.y - p.y, dz = prm.z - p.z;
+    return (dx * dx + dy * dy) + dz * dz;
+}
 // CLAMP = false (round 4): the culling pass of this wave and round has established that no ray's point lies within 1e-6 of any child's centre
 // (ft_cull_children: |c - q0| - rho >= 1e-5 |c - q0| + 1e-6 for every child looked at), so every q is >= 1e-12 and the clamp at 2^-96 is a no-op: 25 instructions per child
 template <bool NEAR, int PW = 0, bool CLAMP = true>
@@ -340,8 +345,7 @@ __device__ __forceinline__ float smooth_run_spheres_fast(const float* __restrict
         for (int j = 0; j < FT_UNROLL; ++j) prm[j] = *reinterpret_cast<const float4*>(ldsC + 4 * (i + j));
 #pragma unroll
         for (int j = 0; j < FT_UNROLL; ++j) {
-            const float dx = prm[j].x - p.x, dy = prm[j].y - p.y, dz = prm[j].z - p.z;
-            q[j] = (dx * dx + dy * dy) + dz * dz;
+            q[j] = ft_sphere_q(prm[j], p);
             if (CLAMP) q[j] = __builtin_fmaxf(q[j], FT_FAST_Q_MIN);
         }
 #pragma unroll
@@ -349,8 +353,7 @@ __device__ __forceinline__ float smooth_run_spheres_fast(const float* __restrict
     }
     for (; i < count; ++i) {
         const float4 prm = *reinterpret_cast<const float4*>(ldsC + 4 * i);
-        const float dx = prm.x - p.x, dy = prm.y - p.y, dz = prm.z - p.z;
-        const float q1 = (dx * dx + dy * dy) + dz * dz;
+        const float q1 = ft_sphere_q(prm, p);
         sum = sum + ft_exp_fast<NEAR>(ft_strength_times_diff<PW>(si, FT_LOOP_SQRT(CLAMP ? __builtin_fmaxf(q1, FT_FAST_Q_MIN) : q1), prm.w));
     }
 #ifndef FT_SQRT_5
@@ -374,9 +377,7 @@ __device__ __forceinline__ float smooth_run_spheres_libm(const float* __restrict
         for (int j = 0; j < 4; ++j) prm[j] = *reinterpret_cast<const float4*>(ldsC + 4 * (i + j));
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const float dx = prm[j].x - p.x, dy = prm[j].y - p.y, dz = prm[j].z - p.z;
-            const float q = (dx * dx + dy * dy) + dz * dz;
-            const float t = si * (ft_sq<FQ>(q) - prm[j].w);
+            const float t = si * (ft_sq<FQ>(ft_sphere_q(prm[j], p)) - prm[j].w);
             e[j] = NEAR ? ft_glibc_expf_main<FMA>(t, tab) : ft_glibc_expf<FMA>(t, tab);
         }
 #pragma unroll
@@ -384,8 +385,7 @@ __device__ __forceinline__ float smooth_run_spheres_libm(const float* __restrict
     }
     for (; i < count; ++i) {
         const float4 prm = *reinterpret_cast<const float4*>(ldsC + 4 * i);
-        const float dx = prm.x - p.x, dy = prm.y - p.y, dz = prm.z - p.z;
-        const float t = si * (ft_sq<FQ>((dx * dx + dy * dy) + dz * dz) - prm.w);
+        const float t = si * (ft_sq<FQ>(ft_sphere_q(prm, p)) - prm.w);
         sum = sum + (NEAR ? ft_glibc_expf_main<FMA>(t, tab) : ft_glibc_expf<FMA>(t, tab));
     }
     return sum;
@@ -397,11 +397,17 @@ __device__ __forceinline__ bool near_point_ok(f3 p, float nearR2) {
     return __ballot(!(pp <= nearR2)) == 0ull;
 }
 
-// wave-uniform precondition of the fast sphere runs for this evaluation
-__device__ __forceinline__ bool fast_point_ok(f3 p) {
+// wave-uniform precondition of the fast sphere runs for this evaluation: no `active` lane has a p that is NaN, infinite or FT_FAST_P_MAX or beyond
+__device__ __forceinline__ bool fast_point_ok(f3 p, bool active = true) {
     const float m = __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(p.x), __builtin_fabsf(p.y)), __builtin_fabsf(p.z));
     const bool bad = !(m < FT_FAST_P_MAX) || p.x != p.x || p.y != p.y || p.z != p.z;   // fmax drops NaN operands: test them
-    return __ballot(bad) == 0ull;
+    return __ballot(active && bad) == 0ull;
+}
+
+// the regime of the lean evaluators' sphere runs at p, both wave-uniform: the fast runs' precondition, and with it the near radius
+__device__ __forceinline__ void ft_sphere_regime(const FtSceneDev& S, const f3 p, bool& fastOk, bool& nearOk) {
+    fastOk = fast_point_ok(p);
+    nearOk = fastOk && near_point_ok(p, S.nearR2);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -433,6 +439,26 @@ __device__ __forceinline__ uint32_t ft_dbg_now() { unsigned long long t; asm vol
 #define FT_UDBG_T1(k, v) do {} while (0)
 #endif
 
+// lookup cell of p in grid g, counted from the grid's own first cell (SdfBoundary.fs:276-282)
+__device__ __forceinline__ uint32_t ft_grid_cell(const FtGrid FT_CONST& g, const f3 p) {
+    const f3 cc = (p - mk3(g.aabbMin[0], g.aabbMin[1], g.aabbMin[2])) * mk3(g.cellSizeInv[0], g.cellSizeInv[1], g.cellSizeInv[2]);
+    const int ix = ft_clamp_i(0, g.count[0] - 1, ft_floor_i(cc.x));
+    const int iy = ft_clamp_i(0, g.count[1] - 1, ft_floor_i(cc.y));
+    const int iz = ft_clamp_i(0, g.count[2] - 1, ft_floor_i(cc.z));
+    return (uint32_t)((ix * g.count[1] + iy) * g.count[2] + iz);
+}
+
+// One candidate of a union's list: its distance at p and the material it gives there — a value slot's, or `mat`, the record's own, for a primitive.
+// CALLS: the list may hold sub-program children (FT_PR_CALL), which the caller's call(data, d, l) runs.
+template <bool FQ, bool CALLS, class Call>
+__device__ __forceinline__ void ft_candidate(uint32_t typeData, uint32_t mat, cfp consts, const f3 p, const float* __restrict__ sd,
+                                             const uint32_t* __restrict__ sl, float& d, uint32_t& l, Call call) {
+    const uint32_t type = typeData & 15u, data = typeData >> 4;
+    if (type == FT_PR_SLOT) { d = sd[data * FT_BLOCK]; l = sl[data * FT_BLOCK]; }
+    else if (CALLS && type == FT_PR_CALL) call(data, d, l);
+    else { d = prim_eval_t<FQ>(type, pool_at(consts, data), p); l = mat; }
+}
+
 // cap / capBound ("lazy union", FT_FLAG_LAZY): the union is child 0 of an intersect whose child 1 evaluates to `cap` at p, with pruning bound
 // `capBound` (SdfForm.fs:60-63: max = u; if max < bound then max = Max(max, cap)).  The fold below starts at Items.[0] and only falls, so once
 // Items.[0]'s distance is <= cap (and < capBound) the intersect's result is `cap` whatever the rest of the walk would find: the lane stops there.
@@ -442,11 +468,7 @@ __device__ __forceinline__ void eval_union_prims(const FtSceneDev& S, const FtGr
                                            const float* __restrict__ sd, const uint32_t* __restrict__ sl,
                                            float& outD, uint32_t& outLeaf, float cap, float capBound) {   // unions without FT_PR_CALL children
     FT_UDBG_T0(tWalk);
-    const f3 cc = (p - mk3(g.aabbMin[0], g.aabbMin[1], g.aabbMin[2])) * mk3(g.cellSizeInv[0], g.cellSizeInv[1], g.cellSizeInv[2]);
-    const int ix = ft_clamp_i(0, g.count[0] - 1, ft_floor_i(cc.x));
-    const int iy = ft_clamp_i(0, g.count[1] - 1, ft_floor_i(cc.y));
-    const int iz = ft_clamp_i(0, g.count[2] - 1, ft_floor_i(cc.z));
-    const uint32_t cell = g.cellBase + (uint32_t)((ix * g.count[1] + iy) * g.count[2] + iz);
+    const uint32_t cell = g.cellBase + ft_grid_cell(g, p);
     cfp ctr = as_const(S.cellCenters) + 3u * cell;
     const float distanceToCenter = ft_distance(mk3(ctr[0], ctr[1], ctr[2]), p);          // SdfForm.fs:25
     const uint32_t FT_CONST* cellStart = as_const(S.cellStart);
@@ -509,10 +531,8 @@ __device__ __forceinline__ void eval_union_prims(const FtSceneDev& S, const FtGr
         }
         FT_UDBG(2, 1); FT_UDBG_WAVE(3);
         FT_UDBG_T0(tPrim);
-        const uint32_t type = typeData & 15u, data = typeData >> 4;
         float d; uint32_t l;
-        if (type == FT_PR_SLOT) { d = sd[data * FT_BLOCK]; l = sl[data * FT_BLOCK]; }
-        else { d = prim_eval_t<FQ>(type, pool_at(consts, data), p); l = mat; }
+        ft_candidate<FQ, false>(typeData, mat, consts, p, sd, sl, d, l, [](uint32_t, float&, uint32_t&) {});
         FT_UDBG_T1(9, tPrim);
         if (first) { mn = d; leaf = l; first = false; if (mn <= cap && mn < capBound) break; }   // lazy union: the rest cannot matter
         else {
@@ -537,11 +557,7 @@ template <bool FQ, int MATH>
 __device__ __forceinline__ void eval_union(const FtSceneDev& S, const FtGrid FT_CONST& g, const f3 p,
                                            float* __restrict__ sd, uint32_t* __restrict__ sl, const float* __restrict__ ldsC,
                                            bool fastOk, bool nearOk, float& outD, uint32_t& outLeaf, float cap, float capBound) {
-    const f3 cc = (p - mk3(g.aabbMin[0], g.aabbMin[1], g.aabbMin[2])) * mk3(g.cellSizeInv[0], g.cellSizeInv[1], g.cellSizeInv[2]);
-    const int ix = ft_clamp_i(0, g.count[0] - 1, ft_floor_i(cc.x));
-    const int iy = ft_clamp_i(0, g.count[1] - 1, ft_floor_i(cc.y));
-    const int iz = ft_clamp_i(0, g.count[2] - 1, ft_floor_i(cc.z));
-    const uint32_t cell = g.cellBase + (uint32_t)((ix * g.count[1] + iy) * g.count[2] + iz);
+    const uint32_t cell = g.cellBase + ft_grid_cell(g, p);
     cfp ctr = as_const(S.cellCenters) + 3u * cell;
     const float distanceToCenter = ft_distance(mk3(ctr[0], ctr[1], ctr[2]), p);          // SdfForm.fs:25
     const uint32_t FT_CONST* cellStart = as_const(S.cellStart);
@@ -566,6 +582,7 @@ __device__ __forceinline__ void eval_union(const FtSceneDev& S, const FtGrid FT_
             if (!(mn > ft_dist<FQ>(mk3(cur.a.y, cur.a.z, cur.a.w), p) - __uint_as_float(cur.b.x))) continue;   // :31 getMinDistance
             FT_UDBG(2, 1); FT_UDBG_WAVE(3);
         }
+        // ft_candidate's three arms, written out: with the loop over the lanes' sub-programs handed to it as `call`, the _calls kernels compile to other code
         const uint32_t type = cur.b.y & 15u, data = cur.b.y >> 4;
         float d; uint32_t l;
         if (type == FT_PR_SLOT) { d = sd[data * FT_BLOCK]; l = sl[data * FT_BLOCK]; }
@@ -614,11 +631,7 @@ __device__ __forceinline__ void eval_union_coop(const FtSceneDev& S, const FtGri
                                                 float* __restrict__ sd, uint32_t* __restrict__ sl, const float* __restrict__ ldsC,
                                                 bool fastOk, bool nearOk, float& outD, uint32_t& outLeaf) {
     const uint32_t lane = threadIdx.x & 63u;
-    const f3 cc = (p - mk3(g.aabbMin[0], g.aabbMin[1], g.aabbMin[2])) * mk3(g.cellSizeInv[0], g.cellSizeInv[1], g.cellSizeInv[2]);
-    const int ix = ft_clamp_i(0, g.count[0] - 1, ft_floor_i(cc.x));
-    const int iy = ft_clamp_i(0, g.count[1] - 1, ft_floor_i(cc.y));
-    const int iz = ft_clamp_i(0, g.count[2] - 1, ft_floor_i(cc.z));
-    const uint32_t cell = (uint32_t)__builtin_amdgcn_readfirstlane((int)(g.cellBase + (uint32_t)((ix * g.count[1] + iy) * g.count[2] + iz)));
+    const uint32_t cell = (uint32_t)__builtin_amdgcn_readfirstlane((int)(g.cellBase + ft_grid_cell(g, p)));
     cfp ctr = as_const(S.cellCenters) + 3u * cell;
     const float distanceToCenter = ft_distance(mk3(ctr[0], ctr[1], ctr[2]), p);          // SdfForm.fs:25
     const uint32_t FT_CONST* cellStart = as_const(S.cellStart);
@@ -628,15 +641,12 @@ __device__ __forceinline__ void eval_union_coop(const FtSceneDev& S, const FtGri
 
     // evaluate one candidate in every lane (typeData / mat are wave-uniform)
     auto evaluate = [&](uint32_t typeData, uint32_t mat, float& d, uint32_t& l) {
-        const uint32_t type = typeData & 15u, data = typeData >> 4;
-        if (type == FT_PR_SLOT) { d = sd[data * FT_BLOCK]; l = sl[data * FT_BLOCK]; }
-        else if (CALLS && type == FT_PR_CALL) {
+        ft_candidate<FQ, CALLS>(typeData, mat, consts, p, sd, sl, d, l, [&](uint32_t data, float& d, uint32_t& l) {
             const uint32_t FT_CONST* cr = reinterpret_cast<const uint32_t FT_CONST*>(consts + data);   // (first instr, end instr, slot)
             const uint32_t slot = cr[2];
             ft_exec<false, false, MATH>(S, cr[0], cr[1], p, sd, sl, ldsC, fastOk, nearOk);
             d = sd[slot * FT_BLOCK]; l = sl[slot * FT_BLOCK];
-        }
-        else { d = prim_eval_t<FQ>(type, pool_at(consts, data), p); l = mat; }
+        });
     };
 
     float mn; uint32_t leaf;
@@ -775,25 +785,15 @@ __device__ __forceinline__ void ft_exec(const FtSceneDev& S, uint32_t pc, uint32
     }
 }
 
-template <bool CALLS, int MATH>
+// COOP (latency mode): the same program on one point p that all 64 lanes share; only the grid union is spread over the lanes (eval_union_coop),
+// every other instruction is computed redundantly by every lane
+template <bool CALLS, int MATH, bool COOP = false>
 __device__ __forceinline__ void ft_eval(const FtSceneDev& S, const f3 p, float* __restrict__ sd, uint32_t* __restrict__ sl,
                                         const float* __restrict__ ldsC, float& outD, uint32_t& outLeaf, float epsHit = __builtin_inff(),
                                         const float* __restrict__ cullRow = nullptr, uint32_t cullN = FT_CULL_NONE) {
     const bool fastOk = (S.nStage != 0 || S.fastQ != 0) && fast_point_ok(p);
     const bool nearOk = MATH == 0 && fastOk && S.nStage != 0 && near_point_ok(p, S.nearR2);
-    ft_exec<true, CALLS, MATH>(S, 0u, S.nInstr, p, sd, sl, ldsC, fastOk, nearOk, epsHit, cullRow, cullN);
-    outD = sd[0];
-    outLeaf = sl[0];
-}
-
-// latency mode: the same program on one point p that all 64 lanes share; only the grid union is spread over the lanes (eval_union_coop),
-// every other instruction is computed redundantly by every lane
-template <bool CALLS, int MATH>
-__device__ __forceinline__ void ft_eval_coop(const FtSceneDev& S, const f3 p, float* __restrict__ sd, uint32_t* __restrict__ sl,
-                                             const float* __restrict__ ldsC, float& outD, uint32_t& outLeaf) {
-    const bool fastOk = (S.nStage != 0 || S.fastQ != 0) && fast_point_ok(p);
-    const bool nearOk = MATH == 0 && fastOk && S.nStage != 0 && near_point_ok(p, S.nearR2);
-    ft_exec<true, CALLS, MATH, true>(S, 0u, S.nInstr, p, sd, sl, ldsC, fastOk, nearOk);
+    ft_exec<true, CALLS, MATH, COOP>(S, 0u, S.nInstr, p, sd, sl, ldsC, fastOk, nearOk, epsHit, cullRow, cullN);
     outD = sd[0];
     outLeaf = sl[0];
 }
@@ -861,9 +861,7 @@ __device__ __forceinline__ uint32_t ft_cull_children(const FtSceneDev& S, const 
     const uint32_t flags = in->flags, count = in->count;
     const float si = in->f0;
     if (in->op != FT_OP_SMOOTH_RUN || !(flags & FT_FLAG_FAST) || count < FT_CULL_MIN || !(si < 0.0f)) return FT_CULL_NONE;
-    const float m = __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(p.x), __builtin_fabsf(p.y)), __builtin_fabsf(p.z));
-    const bool bad = !(m < FT_FAST_P_MAX) || p.x != p.x || p.y != p.y || p.z != p.z;
-    if (__ballot(active && bad) != 0ull) return FT_CULL_NONE;         // such evaluations take the exact loop anyway
+    if (!fast_point_ok(p, active)) return FT_CULL_NONE;               // such evaluations take the exact loop anyway
     const uint32_t lane = threadIdx.x & 63u;
     // centre: half way between the first ray's point and the point farthest from it (a cheap stand-in for the smallest enclosing ball:
     // the points of a tile spread mostly along the rays); rho: the largest distance of any ray's point from that centre
@@ -955,8 +953,8 @@ __device__ __forceinline__ void ft_eval_smooth_spheres(const FtSceneDev& S, cons
                                                        float& outD, uint32_t& outLeaf, const float* __restrict__ cullRow = nullptr, uint32_t cullN = FT_CULL_NONE) {
     float acc = 0.0f;
     uint32_t leaf = 0;
-    const bool fastOk = fast_point_ok(p);
-    const bool nearOk = fastOk && near_point_ok(p, S.nearR2);
+    bool fastOk, nearOk;
+    ft_sphere_regime(S, p, fastOk, nearOk);
     for (uint32_t pc = 0; pc < S.nInstr; ++pc) {
         const FtInstr FT_CONST* in = as_const(S.instr) + pc;
         const uint32_t op = in->op;
@@ -1001,8 +999,7 @@ __device__ __forceinline__ void ft_eval_smooth_spheres(const FtSceneDev& S, cons
 // forms — all three give the same bits wherever two of them are valid (ft_selftest_fastmath), so the choice is only about cost
 template <int MATH>
 __device__ __forceinline__ float ft_sphere_term(const float4 prm, const f3 p, const float si, const int regime, const FtSceneDev& S) {
-    const float dx = prm.x - p.x, dy = prm.y - p.y, dz = prm.z - p.z;
-    const float q = (dx * dx + dy * dy) + dz * dz;
+    const float q = ft_sphere_q(prm, p);
     if (MATH != 0) {
         const float t = si * ((regime != 0 ? ft_sq<true>(q) : sqrtf(q)) - prm.w);
         return S.mathFma ? ft_glibc_expf<true>(t, ft_libm_tab(S)) : ft_glibc_expf<false>(t, ft_libm_tab(S));
@@ -1036,8 +1033,8 @@ __device__ __forceinline__ void ft_eval_smooth_spheres_packed(const FtSceneDev& 
     const bool valid = G < nRays;
     const f3 p = valid ? mk3(row[3u * G], row[3u * G + 1u], row[3u * G + 2u]) : mk3(0.0f, 0.0f, 0.0f);     // lanes of unused groups: any harmless point
     wave_sync();
-    const bool fastOk = fast_point_ok(p);                              // wave-uniform, over all the rays of the round (as in the one-ray-per-lane path)
-    const bool nearOk = fastOk && near_point_ok(p, S.nearR2);
+    bool fastOk, nearOk;                                               // wave-uniform, over all the rays of the round
+    ft_sphere_regime(S, p, fastOk, nearOk);
     const int regime = nearOk ? 2 : (fastOk ? 1 : 0);
     const float* mine = row + 4u * (lane & ~(g - 1u));                 // this group's 4g terms of the current segment
     float acc = 0.0f;
@@ -1113,11 +1110,7 @@ __device__ __forceinline__ float carve_child(uint32_t typeData, cfp consts, cons
 template <int K, bool FQ>
 __device__ __forceinline__ void carve_walk(const FtSceneDev& S, const FtCarve& CV, const f3 p, const float cap, float& outD, uint32_t& outLeaf) {
     const FtGrid FT_CONST& g = as_const(S.grids)[0];
-    const f3 cc = (p - mk3(g.aabbMin[0], g.aabbMin[1], g.aabbMin[2])) * mk3(g.cellSizeInv[0], g.cellSizeInv[1], g.cellSizeInv[2]);
-    const int ix = ft_clamp_i(0, g.count[0] - 1, ft_floor_i(cc.x));
-    const int iy = ft_clamp_i(0, g.count[1] - 1, ft_floor_i(cc.y));
-    const int iz = ft_clamp_i(0, g.count[2] - 1, ft_floor_i(cc.z));
-    const uint32_t cell = (uint32_t)((ix * g.count[1] + iy) * g.count[2] + iz);                  // the scene's only grid: cellBase = 0
+    const uint32_t cell = ft_grid_cell(g, p);                          // the scene's only grid: cellBase = 0
     cfp ctr = as_const(S.cellCenters) + 3u * cell;
     const float distanceToCenter = ft_distance(mk3(ctr[0], ctr[1], ctr[2]), p);                   // SdfForm.fs:25
     const char FT_CONST* items = reinterpret_cast<const char FT_CONST*>(as_const(CV.itemsT));
@@ -1251,6 +1244,8 @@ __device__ __forceinline__ void write_rgb(float* __restrict__ out, uint32_t idx,
     o[0] = c.x; o[1] = c.y; o[2] = c.z;
 }
 
+__device__ __forceinline__ f3 ft_background(const FtRenderArgs& a) { return mk3(a.S.bg[0], a.S.bg[1], a.S.bg[2]); }   // scene.BackgroundColor
+
 // EXTENSION builds scale every finished sample by the path throughput (exactly 1 unless glass / wavelengths are on)
 template <bool EXT>
 __device__ __forceinline__ void emit(const FtRenderArgs& a, const LaneState& s, f3 c) {
@@ -1347,6 +1342,20 @@ __device__ __forceinline__ bool ft_cert_segment(const FtSceneDev& S, bool test, 
     return ok && t1 > t0;
 }
 
+// Squared distance of the centre of record prm from the segment p0 + t sv, 0 <= t <= 1 (iss = 1 / |sv|^2): projection, clamp, residual.  Both miss
+// certificates below bound with it: fused multiply-adds, not the reference's arithmetic.
+template <class P>
+__device__ __forceinline__ float ft_seg_dist2(const P prm, const f3 p0, const f3 sv, const float iss) {
+    const float vx = prm.x - p0.x, vy = prm.y - p0.y, vz = prm.z - p0.z;
+    float t = __builtin_fmaf(vz, sv.z, __builtin_fmaf(vy, sv.y, vx * sv.x)) * iss;
+    t = __builtin_amdgcn_fmed3f(t, 0.0f, 1.0f);
+    const float ex = __builtin_fmaf(-t, sv.x, vx), ey = __builtin_fmaf(-t, sv.y, vy), ez = __builtin_fmaf(-t, sv.z, vz);
+    return __builtin_fmaf(ez, ez, __builtin_fmaf(ey, ey, ex * ex));
+}
+
+// the threshold both miss certificates below hold their sums of terms 2^(A (dist - r)) against, from its log2 xt = A (epsilon + certM)
+__device__ __forceinline__ float ft_cert_threshold(float xt) { return __builtin_amdgcn_exp2f(xt) * 0.9999f; }
+
 // ------------------------------------------------------------------------------------------------
 // Miss certificate (FT_OPT_CERT; lean kernel and its EXTENSION build, paths outside glass bodies).  The scene is ONE smooth union of staged spheres, f(x) = -s ln sum_i exp(si d_i(x))
 // with si = -1 / s < 0 (SdfForm.fs:75-82), so on a segment S every term is at most exp(si dmin_i), dmin_i = dist(S, c_i) - r_i, and
@@ -1373,20 +1382,13 @@ __device__ __forceinline__ bool ft_miss_certificate(const FtSceneDev& S, const f
     const float xt = A * (eps + S.certM);
     ok = ok && xt >= -100.0f;                                          // the threshold stays a normal number, far above flushed terms
     if (__ballot(ok) == 0ull) return false;
-    const float thr = __builtin_amdgcn_exp2f(xt) * 0.9999f;
+    const float thr = ft_cert_threshold(xt);
     const f3 p0 = ok ? o + dir * t0 : mk3(0.0f, 0.0f, 0.0f);           // the segment p0 + t sv, 0 <= t <= 1
     const f3 sv = ok ? dir * (t1 - t0) : mk3(1.0f, 0.0f, 0.0f);
     const float iss = 1.0f / ft_dot(sv, sv);
     float sum = 0.0f;
     uint32_t i = 0;
-    auto term = [&](const auto prm) {
-        const float vx = prm.x - p0.x, vy = prm.y - p0.y, vz = prm.z - p0.z;
-        float t = __builtin_fmaf(vz, sv.z, __builtin_fmaf(vy, sv.y, vx * sv.x)) * iss;
-        t = __builtin_amdgcn_fmed3f(t, 0.0f, 1.0f);
-        const float ex = __builtin_fmaf(-t, sv.x, vx), ey = __builtin_fmaf(-t, sv.y, vy), ez = __builtin_fmaf(-t, sv.z, vz);
-        const float q = __builtin_fmaf(ez, ez, __builtin_fmaf(ey, ey, ex * ex));
-        return __builtin_amdgcn_exp2f((__builtin_amdgcn_sqrtf(q) - prm.w) * A);
-    };
+    auto term = [&](const auto prm) { return __builtin_amdgcn_exp2f((__builtin_amdgcn_sqrtf(ft_seg_dist2(prm, p0, sv, iss)) - prm.w) * A); };
     if (S.certK != 0u) {
         // Cluster bound (scene.cpp certClusters): n_c 2^(A (dist(S, C) - R)) >= the sum of the cluster's member terms, since dist(S, c_i) - r_i >=
         // dist(S, C) - R for each member and A < 0.  Pass 1 sums the K bounds: a lane below thr holds.  Each lane marks the clusters whose bound reaches
@@ -1443,7 +1445,7 @@ __device__ __forceinline__ bool ft_miss_certificate(const FtSceneDev& S, const f
 // constants keep their values.  Float32: W is padded by 0.1 % + 1e-6 + 4e-6 R and I by 4e-6 R at either end (R: the clip radius; every coordinate
 // difference here is <= 5 escR, so each of the few roundings of a_l, b_l t1_l, s_l + t and the reductions' end points is below 2^-23 of 10 escR);
 // the axis segment's end points, projection, v_sqrt_f32 / v_exp_f32 are ft_miss_certificate's own (scene.cpp eGeo: 16u (|escC|inf + 10 escR));
-// the sum is a tree of 6 + passes roundings per term instead of n, inside eSum's (2n + 4096) 2^-23, and the threshold carries the same 0.9999.
+// the sum is a tree of 6 + passes roundings per term instead of n, inside eSum's (2n + 4096) 2^-23, and the threshold is ft_cert_threshold's, 0.9999 included.
 // Cost: 4 wave maxima, 8 v_readlane and n / 64 passes of ~20 VALU — about 200 wave-instructions for 256 children, whatever the number of members.
 // Executed by all 64 lanes.  minMembers >= 1.  -> this lane is a member and the bundle holds.
 __device__ __forceinline__ bool ft_bundle_certificate(const FtSceneDev& S, const float* __restrict__ ldsC, bool cand, const f3 o, const f3 dir, float eps, float len,
@@ -1477,18 +1479,13 @@ __device__ __forceinline__ bool ft_bundle_certificate(const FtSceneDev& S, const
     const float i0 = (tc1 - dLo) - 4e-6f * Rc, i1 = (tc0 + dHi) + 4e-6f * Rc;
     const f3 p0 = oc + dc * i0, sv = dc * (i1 - i0);                   // the axis segment p0 + t sv, 0 <= t <= 1
     const float iss = 1.0f / ft_dot(sv, sv);
-    const float thr = __builtin_amdgcn_exp2f(xt) * 0.9999f;
+    const float thr = ft_cert_threshold(xt);
     const uint32_t lane = threadIdx.x & 63u;
     float sum = 0.0f;
     for (uint32_t base = 0; base < n; base += 64u) {
         const uint32_t i = base + lane;
         const float4 prm = c[i < n ? i : n - 1u];
-        const float vx = prm.x - p0.x, vy = prm.y - p0.y, vz = prm.z - p0.z;
-        float t = __builtin_fmaf(vz, sv.z, __builtin_fmaf(vy, sv.y, vx * sv.x)) * iss;
-        t = __builtin_amdgcn_fmed3f(t, 0.0f, 1.0f);
-        const float qx = __builtin_fmaf(-t, sv.x, vx), qy = __builtin_fmaf(-t, sv.y, vy), qz = __builtin_fmaf(-t, sv.z, vz);
-        const float q = __builtin_fmaf(qz, qz, __builtin_fmaf(qy, qy, qx * qx));
-        const float term = __builtin_amdgcn_exp2f((__builtin_amdgcn_sqrtf(q) - (prm.w + W)) * A);
+        const float term = __builtin_amdgcn_exp2f((__builtin_amdgcn_sqrtf(ft_seg_dist2(prm, p0, sv, iss)) - (prm.w + W)) * A);
         sum += i < n ? term : 0.0f;
     }
     float total;
@@ -1507,6 +1504,15 @@ __device__ __forceinline__ int first_step_from_cache(LaneState& s) {
     s.len = s.len - d;
     s.steps = 1;
     return 0;
+}
+
+// A light of kind `type` (lv: its direction, or its position; lc: its colour) seen from hp: the direction to it and the intensity it adds there when
+// unshadowed.  The callers pass the fields of the light's record as they have loaded them.
+struct FtLit { f3 lint, ldir; };
+__device__ __forceinline__ FtLit ft_light_at(const uint32_t type, const f3 lv, const f3 lc, const f3 hp) {
+    f3 lint = lc, ldir = lv;                                                              // SdfLight.fs:9, :16
+    if (type != FT_LIGHT_DIRECTIONAL) { ldir = ft_normalize(lv - hp); lint = lint / ft_length2(lv - hp); }      // SdfLight.fs:25, :28, :40
+    return FtLit{lint, ldir};
 }
 
 // advance a lane until it needs an SDF evaluation (or is idle): everything in SdfScene.trace that
@@ -1529,7 +1535,7 @@ __device__ __forceinline__ void settle(const FtRenderArgs& a, LaneState& s) {
                 else {
                     // every miss of a primary ray ends here: Length used up, escape, NaN and the step cap (s.len = -1), the camera shortcuts of start_job
                     if (EXT && ends_hit_segment<VIEWS>(a, s)) write_hit_miss(a, hit_index<VIEWS>(a, s));
-                    if (!EXT || a.hits != 2u) emit<EXT>(a, s, mk3(a.S.bg[0], a.S.bg[1], a.S.bg[2]));
+                    if (!EXT || a.hits != 2u) emit<EXT>(a, s, ft_background(a));
                 }
                 s.phase = PH_IDLE;
             }
@@ -1542,7 +1548,7 @@ __device__ __forceinline__ void settle(const FtRenderArgs& a, LaneState& s) {
         if (EXT && s.phase == PH_AONEXT) {                             // EXTENSION
             if (s.aoIdx() >= a.aoSamples) {
                 const float f = (float)s.aoOpen() / (float)a.aoSamples;
-                sh_set3(FT_SH_LACC, mk3(a.S.bg[0], a.S.bg[1], a.S.bg[2]) * f);
+                sh_set3(FT_SH_LACC, ft_background(a) * f);
                 s.lidx = 0; s.phase = PH_LIGHTS;
                 continue;
             }
@@ -1567,9 +1573,8 @@ __device__ __forceinline__ void settle(const FtRenderArgs& a, LaneState& s) {
                 }
                 const FtLight L = ld_light(as_const(a.S.lights) + s.lidx);                 // the light this shadow ray was cast for (PH_LIGHTS below)
                 const f3 lv = mk3(L.v[0], L.v[1], L.v[2]), hp = sh_get3(FT_SH_HP);
-                f3 lint = mk3(L.color[0], L.color[1], L.color[2]), ldir = lv;             // SdfLight.fs:9, :16
-                if (L.type != FT_LIGHT_DIRECTIONAL) { ldir = ft_normalize(lv - hp); lint = lint / ft_length2(lv - hp); }      // SdfLight.fs:25, :28, :40
-                sh_set3(FT_SH_LACC, sh_get3(FT_SH_LACC) + lint * ft_dot(sh_get3(FT_SH_NRM), ldir));   // SdfScene.fs:15, :23
+                const FtLit li = ft_light_at(L.type, lv, mk3(L.color[0], L.color[1], L.color[2]), hp);
+                sh_set3(FT_SH_LACC, sh_get3(FT_SH_LACC) + li.lint * ft_dot(sh_get3(FT_SH_NRM), li.ldir));   // SdfScene.fs:15, :23
                 s.lidx += 1; s.phase = PH_LIGHTS;
                 continue;
             }
@@ -1593,10 +1598,9 @@ __device__ __forceinline__ void settle(const FtRenderArgs& a, LaneState& s) {
             }
             const FtLight L = ld_light(as_const(a.S.lights) + s.lidx);
             const f3 lv = mk3(L.v[0], L.v[1], L.v[2]);
-            f3 ldir;
             const f3 hp = sh_get3(FT_SH_HP);
-            if (L.type == FT_LIGHT_DIRECTIONAL) ldir = lv;             // SdfLight.fs:9
-            else ldir = ft_normalize(lv - hp);                         // SdfLight.fs:25
+            // only the direction is used here: the intensity's division is dead code and is dropped (a direction-only helper would state SdfLight.fs:9, :25 twice)
+            const f3 ldir = ft_light_at(L.type, lv, mk3(L.color[0], L.color[1], L.color[2]), hp).ldir;
             const float lightCos = ft_dot(sh_get3(FT_SH_NRM), ldir);   // SdfScene.fs:15
             if (lightCos > 0.0f) {                                     // SdfScene.fs:17
                 s.o = hp;
@@ -1650,14 +1654,14 @@ __device__ __forceinline__ void start_job(const FtRenderArgs& a, LaneState& s, c
             return;
         }
         if (__float_as_uint(r3.z) == 0u) {                             // ValueNone: scene.BackgroundColor (SdfScene.fs:10)
-            write_rgb(a.out, s.outIdx, mk3(a.S.bg[0], a.S.bg[1], a.S.bg[2]));
+            write_rgb(a.out, s.outIdx, ft_background(a));
             s.phase = PH_IDLE;
             return;
         }
         sh_set3(FT_SH_HP, mk3(r0.x, r0.y, r0.z));                      // result.Position = result.Ray.Origin
         sh_set3(FT_SH_NRM, mk3(r2.x, r2.y, r2.z));
         if (VIS) *ft_vis_word() = kept;
-        else sh_set3(FT_SH_LACC, mk3(a.S.bg[0], a.S.bg[1], a.S.bg[2]));     // SdfScene.fs:12
+        else sh_set3(FT_SH_LACC, ft_background(a));                    // SdfScene.fs:12
         s.lidx = 0;
         s.phase = PH_LIGHTS;
         settle<EXT, FORM>(a, s);
@@ -1922,7 +1926,7 @@ __device__ __forceinline__ void ft_trace_body(const FtRenderArgs& a) {
                     const f3 qL = ft_readlane3(qm, L);
                     float dL; uint32_t leafL;
                     if (VARIANT == 3) ft_eval_carved<K, true>(a.S, a.carve, qL, dL, leafL, __builtin_inff());
-                    else ft_eval_coop<VARIANT == 2, MATH>(a.S, qL, sd, sl, ldsC, dL, leafL);
+                    else ft_eval<VARIANT == 2, MATH, true>(a.S, qL, sd, sl, ldsC, dL, leafL);
                     if ((int)lane == L) { dCoop = dL; leafCoop = leafL; }
                     if (!camRound) coopEvals += 1;
                 }
@@ -1995,7 +1999,7 @@ __device__ __forceinline__ void ft_trace_body(const FtRenderArgs& a) {
                 const f3 hp = s.o + s.dir * (-s.eps);                  // SdfObject.fs:73
                 sh_set3(FT_SH_NRM, nrm);
                 sh_set3(FT_SH_HP, hp);
-                sh_set3(FT_SH_LACC, mk3(a.S.bg[0], a.S.bg[1], a.S.bg[2]));     // SdfScene.fs:12
+                sh_set3(FT_SH_LACC, ft_background(a));                 // SdfScene.fs:12
                 s.lidx = 0;
                 s.phase = PH_LIGHTS;
                 if (EXT && ends_hit_segment<VIEWS>(a, s)) {            // the SdfObject.tryTrace result (SdfObject.fs:72-77), before any glass bounce moves the ray:
@@ -2138,9 +2142,9 @@ extern "C" const void* ft_trace_kernel_for(unsigned variant, unsigned carveKind,
 // ft_shade_visible: SdfScene.fs:11-28 with every `light.Intensity scene.Object ray` answered by a bit of the record's visibility mask instead of a march.
 // One record per lane.  Of the record's four 16-byte words {Origin, Direction.x} {Direction.yz, Length, Epsilon} {Normal, Color.r} {Color.gb, hit, 0} the
 // second is not needed and not loaded; with the mask and the colour a record moves 52 + 12 B (80 B if the skipped word's sector is counted).  The
-// lights are wave-uniform: scalar loads in a uniform loop, a lane only skips the arithmetic of the lights whose bit it does not have.  The arithmetic
-// is settle()'s shadow-miss branch and its final colour, term for term in the same order (this file is compiled without contraction), so that a mask
-// from ft_light_visibility gives ft_shade_hits' colours bit for bit.  No LDS, no atomics.
+// lights are wave-uniform: scalar loads in a uniform loop, a lane only skips the arithmetic of the lights whose bit it does not have.  Every light's
+// term is ft_light_at's, added and turned into the final colour in the order of settle()'s shadow-miss branch (this file is compiled without contraction),
+// so that a mask from ft_light_visibility gives ft_shade_hits' colours bit for bit.  No LDS, no atomics.
 extern "C" __global__ void __launch_bounds__(FT_BLOCK) ft_shade_visible_kernel(const FtLight* __restrict__ lights, const uint32_t nLights, const float bg0,
                                                                               const float bg1, const float bg2, const float* __restrict__ hits,
                                                                               const uint32_t* __restrict__ vis, const uint32_t n, float* __restrict__ out) {
@@ -2158,9 +2162,8 @@ extern "C" __global__ void __launch_bounds__(FT_BLOCK) ft_shade_visible_kernel(c
         const FtLight L = ld_light(as_const(lights) + i);
         if (((mask >> i) & 1u) == 0u) continue;
         const f3 lv = mk3(L.v[0], L.v[1], L.v[2]);
-        f3 lint = mk3(L.color[0], L.color[1], L.color[2]), ldir = lv;             // SdfLight.fs:9, :16
-        if (L.type != FT_LIGHT_DIRECTIONAL) { ldir = ft_normalize(lv - hp); lint = lint / ft_length2(lv - hp); }      // SdfLight.fs:25, :28, :40
-        lacc = lacc + lint * ft_dot(nrm, ldir);                        // SdfScene.fs:15, :23
+        const FtLit li = ft_light_at(L.type, lv, mk3(L.color[0], L.color[1], L.color[2]), hp);
+        lacc = lacc + li.lint * ft_dot(nrm, li.ldir);                  // SdfScene.fs:15, :23
     }
     write_rgb(out, idx, mk3(r2.w, r3.x, r3.y) * (lacc * piInv));       // SdfScene.fs:28
 }
