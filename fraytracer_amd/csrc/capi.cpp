@@ -68,6 +68,27 @@ struct ft_ctx {
     int optCert = 1;                                       // FT_OPT_CERT: the lean kernel's miss certificate (kernels.hip ft_miss_certificate); needs optEscape
     int optCertPolicy = 0;                                 // FT_OPT_CERT_POLICY: 0 = FT_CERT_POLICY_DEFAULT
     int optGuided = 0;                                     // FT_OPT_GUIDED: smaller chunks at the end of the job queue (lean kernel; measured: no gain)
+    int optOrder = 1;                                      // FT_OPT_ORDER: 1 = frames hand their heavy tiles out first, from the costs the scene's last launch of the same grid recorded; 2 = record only; 0 = off
+    uint32_t orderNum = 1, orderDen = 1;                   // a tile is heavy from orderNum / orderDen of the mean cost on (ft_ctx_tile_order_rule: the probes' other rules)
+};
+
+// FT_OPT_ORDER: what a scene keeps per render lane between two frame launches (launchTrace; kernels.hip "Tile order").  cost, order and work are one
+// allocation; key is everything that fixes the tile grid and the kernel of the launch that recorded cost — not the camera, epsilon, Length or lights:
+// an order made for another view is only another permutation.
+struct TileOrderKey {
+    int32_t W, H, x0, nCols;
+    uint32_t stripeW, stripeRanks, stripeRank, nJobs, variant, libm;
+    bool operator==(const TileOrderKey& o) const {
+        return W == o.W && H == o.H && x0 == o.x0 && nCols == o.nCols && stripeW == o.stripeW && stripeRanks == o.stripeRanks && stripeRank == o.stripeRank &&
+               nJobs == o.nJobs && variant == o.variant && libm == o.libm;
+    }
+};
+struct TileOrderSlot {
+    uint32_t* cost = nullptr; uint32_t* order = nullptr; void* work = nullptr;
+    uint32_t capTiles = 0;
+    bool keyed = false, hasOrder = false;                  // key describes cost; order was built from cost
+    bool usedOrder = false;                                // the launch that recorded cost handed its tiles out in an order (ft_scene_tile_order_used)
+    TileOrderKey key{};
 };
 
 struct ft_scene {
@@ -79,6 +100,7 @@ struct ft_scene {
     const int32_t* dMatHandles = nullptr;    // EXTENSION ft_render_hits: dense material index -> context handle (FlatScene::materialHandles)
     FtCarve carve{};                         // fastPath == 3: tail + device pointers of the terminated candidate lists
     bool usesExpLog = false;                 // the program has a unionSmooth (SdfForm.fs:80,82): the only place FT_OPT_MATH matters while tracing
+    mutable TileOrderSlot orderSlots[2];     // FT_OPT_ORDER: per render lane (each lane has its own stream and job counter, so two launches in flight never share one)
 };
 
 namespace {
@@ -279,6 +301,22 @@ int acquireEvents(ft_ctx* c, hipEvent_t& a, hipEvent_t& b) {
     return FT_OK;
 }
 
+// FT_OPT_ORDER: the slot of this launch with room for its tiles, nullptr where it cannot be had (the launch then runs in index order and records nothing)
+TileOrderSlot* tileOrderSlot(const ft_scene* s, int lane, uint32_t nTiles) {
+    TileOrderSlot& t = s->orderSlots[lane];
+    if (t.capTiles >= nTiles) return &t;
+    if (t.cost) (void)hipFree(t.cost);                    // waits for whatever still uses it
+    t = TileOrderSlot{};
+    const size_t words = 2 * (size_t)nTiles, bytes = align256(words * sizeof(uint32_t)) + ft_tile_order_work_bytes(nTiles);
+    void* p = nullptr;
+    if (hipMalloc(&p, bytes) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+    t.cost = static_cast<uint32_t*>(p);
+    t.order = t.cost + nTiles;
+    t.work = static_cast<unsigned char*>(p) + align256(words * sizeof(uint32_t));
+    t.capTiles = nTiles;
+    return &t;
+}
+
 // launch the persistent trace kernel over nJobs jobs
 // lane 0 = the context's stream; lane 1 = a second stream with its own job counter, so that two launches can be in flight
 // (the drain of one overlaps the start of the next: DESIGN.md section 6)
@@ -370,6 +408,22 @@ int launchTrace(ft_ctx* c, const ft_scene* s, FtRenderArgs& a, int lane = 0) {
     a.reuse = (c->optReuse && !a.shade) ? 1u : 0u;     // ft_shade_hits: no centre probe ran, nothing to reuse
     a.S.mathFma = c->optMath == FT_MATH_GLIBC_FMA ? 1u : 0u;
     a.materialsExt = s->dMaterialsExt;
+    // FT_OPT_ORDER.  Eligible: a frame of whole tiles taken one at a time, on the kernel that keeps the bookkeeping (the lean kernel).
+    // An eligible launch records what each tile cost.  Where the slot's last launch had the same grid and kernel, it also hands the tiles out in
+    // the order built from that launch's costs.  A context with FT_OPT_GUIDED set is never eligible: the guided hand-out changes the grab size.
+    // A launch that is not eligible leaves the slot alone.
+    a.tileCost = nullptr; a.tileOrder = nullptr;
+    TileOrderSlot* slot = nullptr;
+    if (key.form == FT_FORM_FRAME && !key.ext && key.variant == 1u && a.mode == 0u && a.spp == 1u && a.chunk == 64u && a.refillMin == 64u && !c->optGuided && a.shrink1 == a.nJobs && a.nJobs >= 64u) {
+        if (c->optOrder == 0) { s->orderSlots[lane].keyed = s->orderSlots[lane].hasOrder = s->orderSlots[lane].usedOrder = false; }
+        else slot = tileOrderSlot(s, lane, a.nJobs >> 6);
+    }
+    if (slot) {
+        const TileOrderKey k{a.W, a.H, a.x0, a.nCols, a.stripeW, a.stripeRanks, a.stripeRank, a.nJobs, key.variant, key.libm ? 1u : 0u};
+        a.tileCost = slot->cost;
+        if (c->optOrder == 1 && slot->keyed && slot->hasOrder && slot->key == k) a.tileOrder = slot->order;
+        slot->key = k; slot->keyed = true; slot->hasOrder = false; slot->usedOrder = a.tileOrder != nullptr;
+    }
     HIP_TRY(hipMemsetAsync(counter, 0, sizeof(uint32_t), stream));
     hipEvent_t e0, e1;
     if ((rc = foldOldestEvents(c))) return rc;
@@ -378,6 +432,11 @@ int launchTrace(ft_ctx* c, const ft_scene* s, FtRenderArgs& a, int lane = 0) {
     HIP_TRY(ft_launch_trace(&a, blocks, plan.lds, stream));
     HIP_TRY(hipEventRecord(e1, stream));
     c->events.emplace_back(e0, e1);
+    if (slot && c->optOrder == 1) {                        // behind the frame on its own stream: no synchronisation, nothing comes back to the host
+        // the frame is launched whatever becomes of its order: a failure here only leaves the next frame in index order
+        if (ft_launch_tile_order(slot->cost, a.nJobs >> 6, c->orderNum, c->orderDen, slot->order, slot->work, stream) == hipSuccess) slot->hasOrder = true;
+        else (void)hipGetLastError();
+    }
     return FT_OK;
 }
 
@@ -400,6 +459,7 @@ constexpr OptionSpec kOptions[] = {
     {FT_OPT_REUSE, &ft_ctx::optReuse, 0, 1, "FT_OPT_REUSE: 0 or 1"},
     {FT_OPT_CERT, &ft_ctx::optCert, 0, 1, "FT_OPT_CERT: 0 or 1"},
     {FT_OPT_CERT_POLICY, &ft_ctx::optCertPolicy, INT32_MIN, INT32_MAX, "FT_OPT_CERT_POLICY: 0, or bits 16-23 (due lanes) in 1 .. 64"},
+    {FT_OPT_ORDER, &ft_ctx::optOrder, 0, 2, "FT_OPT_ORDER: 0 off, 1 heavy tiles first, 2 record only"},
 };
 const OptionSpec* findOption(int32_t id) {
     for (const OptionSpec& o : kOptions) if (o.id == id) return &o;
@@ -649,7 +709,32 @@ int ft_scene_relight(const ft_scene* src, const float bg[3], const ft_handle* li
 void ft_scene_destroy(ft_scene* s) {
     if (!s) return;
     if (s->dBlob) { (void)hipSetDevice(s->ctx->device); (void)hipFree(s->dBlob); }
+    for (TileOrderSlot& t : s->orderSlots) if (t.cost) { (void)hipSetDevice(s->ctx->device); (void)hipFree(t.cost); }
     delete s;
+}
+
+// Internal (not in the header, like ft_trace_kernel_for; tests/test_tile_order.py, tools/tile_order_probe.py): the costs the scene's last frame launch
+// on lane 0 recorded per tile, and the order built from them, copied to `out` (room for cap values) once the context's stream has run dry.  Returns the
+// tile count; 0 where the slot holds none (nothing recorded, FT_OPT_ORDER = 0; for the order also FT_OPT_ORDER = 2); a negative error code.
+static long long readTileOrderSlot(const ft_scene* s, bool order, uint32_t* out, long long cap) {
+    if (!s || !s->ctx || (!out && cap > 0) || cap < 0) return setErr(FT_ERR_INVALID, "bad argument");
+    int rc = requireDevice(s->ctx); if (rc) return rc;
+    const TileOrderSlot& t = s->orderSlots[0];
+    if (!t.keyed || (order && !t.hasOrder)) return 0;
+    const long long n = (long long)(t.key.nJobs >> 6);
+    HIP_TRY(hipStreamSynchronize(s->ctx->stream));
+    if (std::min(n, cap) > 0) HIP_TRY(hipMemcpy(out, order ? t.order : t.cost, (size_t)std::min(n, cap) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return n;
+}
+long long ft_scene_tile_costs(const ft_scene* s, uint32_t* out, long long cap) { return readTileOrderSlot(s, false, out, cap); }
+long long ft_scene_tile_order(const ft_scene* s, uint32_t* out, long long cap) { return readTileOrderSlot(s, true, out, cap); }
+// Internal: 1 where the scene's last recording frame launch on lane 0 handed its tiles out in a built order, 0 where it ran in index order
+int ft_scene_tile_order_used(const ft_scene* s) { return s && s->orderSlots[0].keyed && s->orderSlots[0].usedOrder ? 1 : 0; }
+// Internal (tools/tile_order_probe.py): tiles count as heavy from num / den of the mean cost on (the shipped rule is 1 / 1; 0 / 1 sorts every tile)
+int ft_ctx_tile_order_rule(ft_ctx* c, uint32_t num, uint32_t den) {
+    if (!c || den == 0u || num > 16u || den > 16u) return setErr(FT_ERR_INVALID, "bad argument");
+    c->orderNum = num; c->orderDen = den;
+    return FT_OK;
 }
 
 float ft_lens_create(float fov) { return ft::lensCreate(fov); }

@@ -11,6 +11,10 @@
 // dynamic LDS of a trace workgroup starts with a header: 64 words (per-wave statistics, the reporting wave's start clocks), in the diagnostic
 // build 13 rows of per-lane union-walk counters (kernels.hip FT_UDBG: 12 + 1 scratch row), then FT_SH_ROWS rows of per-lane shading state
 #define FT_LDS_CNT_WORDS 64
+// the header's words: 0 .. 31 the per-wave statistics (kernels.hip FT_C_*: FT_BLOCK / 64 words per counter), 32 .. 35 the reporting wave's two start
+// clocks, FT_LDS_TILE_WORD .. + 2 * FT_BLOCK / 64 - 1 per wave the tile it took last and its round count at that grab (kernels.hip "Tile order"), the rest free
+#define FT_LDS_TILE_WORD 40
+static_assert(FT_LDS_TILE_WORD >= 36 && FT_LDS_TILE_WORD + 2 * (256 / 64) <= FT_LDS_CNT_WORDS, "the tile words lie behind the clocks, inside the header");
 #ifdef FT_UNION_PROFILE
 #define FT_LDS_DBG_ROWS 13
 #else
@@ -96,6 +100,11 @@ struct FtRenderArgs {
     // bundle certificate (lean kernel; kernels.hip ft_bundle_certificate; appended): tried every bundlePeriod-th evaluation round of a wave (0: never) for its
     // primary rays and for its shadow rays of at least bundleShadow steps, each where at least bundleMin (>= 1) lanes hold such a ray; needs cert
     uint32_t bundlePeriod, bundleMin, bundleShadow;
+    // tile order (FRAME builds without EXTENSION; kernels.hip refill; appended; set only for mode 0, spp 1, chunk = refillMin = 64, no guided hand-out):
+    // tileCost, where not NULL, receives per 8x8 tile the evaluation rounds its wave spent between taking it and taking its next one; tileOrder,
+    // where not NULL, is a permutation of the tiles: the grab at cursor position 64 k works on tile tileOrder[k] (ft_launch_tile_order builds it)
+    uint32_t* tileCost;
+    const uint32_t* tileOrder;
 };
 #define FT_MAX_VIEWS 64       // views per launch (one PH_CAM value per lane); ft_render_views splits larger batches
 
@@ -147,6 +156,13 @@ hipError_t ft_launch_selftest(int op, uint32_t lo, uint32_t hi, unsigned long lo
 // the kernel handle of a key given piecewise, nullptr where no such kernel exists (internal, like ft_trace_occupancy; tests/test_trace_kernel_table.py)
 const void* ft_trace_kernel_for(unsigned variant, unsigned carveKind, bool ext, bool libm, bool views, unsigned shade);
 hipError_t ft_trace_occupancy(const FtTraceKey& key, size_t ldsBytes, int* blocksPerCU);
+// Tile order (kernels.hip "Tile order"): from the nTiles costs a trace launch recorded, the permutation `order` its next launch hands tiles out in: the
+// tiles of cost >= num / den of the mean first, by non-increasing cost, the rest in ascending index.  Three small launches and one memset on st, no
+// synchronisation.  work: ft_tile_order_work_bytes(nTiles) bytes of device memory that stay the launches' own until they have run.
+#define FT_ORDER_TILES 1024   // tiles per workgroup of the order kernels
+struct FtTileOrderWork { uint32_t hist[256], cursor[256]; unsigned long long sum; uint32_t ticketCount, ticketHeavy, nHeavy, pad; };
+size_t ft_tile_order_work_bytes(uint32_t nTiles);
+hipError_t ft_launch_tile_order(const uint32_t* cost, uint32_t nTiles, uint32_t num, uint32_t den, uint32_t* order, void* work, hipStream_t st);
 // ft_shade_visible: n records + n masks -> n colours, no march (kernels.hip ft_shade_visible_kernel); lights: the scene's, in device memory
 hipError_t ft_launch_shade_visible(const FtLight* lights, uint32_t nLights, const float bg[3], const float* hits, const uint32_t* vis, uint32_t n,
                                    float* out, hipStream_t st);

@@ -1792,6 +1792,15 @@ __device__ __forceinline__ void ft_trace_body(const FtRenderArgs& a) {
     uint32_t cullSkipped = 0, cullTotal = 0;                           // (child, ray) pairs the culling pass dropped / looked at (wave-uniform sums)
     uint32_t chunkNext = 0, chunkEnd = 0;                              // wave-uniform
     uint32_t waveEvals = 0;                                            // evaluation rounds of this wave (lane-utilisation statistic)
+    // tile order: the only builds that record tile costs and follow an order are the lean kernel's.  The interpreter with calls and the carved kernels paid for
+    // it with more spilled registers (calls, carved capsules: profiles/tile_order_kernel_resources.txt); in the plain interpreter a wave may hold rays of
+    // two tiles (a refill while lanes wait to shade), so its wave_evals statistic moved with the order, which tests/test_gpu_views.py compares between launches
+    constexpr bool ORDER = FORM == FT_FORM_FRAME && !EXT && VARIANT == 1;
+    // the tile this wave took last (word 0; none: 0xffffffff) and waveEvals at that grab (word 4), in free words of the LDS header, not in registers:
+    // they are touched once per tile, and two more values alive across the round would cost the general kernels spills
+    uint32_t* tileSt = reinterpret_cast<uint32_t*>(ft_lds) + FT_LDS_TILE_WORD + (tid >> 6);
+    constexpr uint32_t TILE_EVALS = FT_BLOCK / 64;                     // word offset of the second value
+    if (ORDER && lane == 0) tileSt[0] = 0xffffffffu;
     uint32_t coopEvals = 0;                                            // evaluations done in latency mode (wave-uniform)
     uint32_t nEvals = 0;                                               // scene evaluations of this wave's rays (wave-uniform: summed per round)
     bool exhausted = false;
@@ -1825,6 +1834,13 @@ __device__ __forceinline__ void ft_trace_body(const FtRenderArgs& a) {
             if ((uint32_t)__popcll(idle) < a.refillMin && __ballot(s.phase >= PH_MARCH) != 0ull) break;
             if (chunkNext == chunkEnd) {
                 if (exhausted) break;
+                // Tile order: the rounds since the last grab are the cost of the tile taken then (refillMin = 64: its last lane has ended), written
+                // by one lane; every tile is taken once, so every cost is written once, by this grab or by the one that finds the queue empty
+                if (ORDER && a.tileCost != nullptr && lane == 0) {
+                    const uint32_t t = tileSt[0];
+                    if (t < (a.nJobs >> 6)) a.tileCost[t] = waveEvals - tileSt[TILE_EVALS];
+                    tileSt[0] = 0xffffffffu;
+                }
                 // Guided hand-out at the end of the queue (FT_OPT_GUIDED, lean kernel, OFF by default; everywhere else shrink1 = shrink2 = nJobs):
                 // from job shrink1 on a wave takes half a tile, from shrink2 on a quarter, so that the last generation of work is spread over
                 // 2 - 4 times as many waves.  Measured: the 32 / 16-ray rounds of the latency mode cost +34 % / +46 % per ray, more than the
@@ -1842,6 +1858,16 @@ __device__ __forceinline__ void ft_trace_body(const FtRenderArgs& a) {
                 if (base >= a.nJobs) { exhausted = true; break; }
                 chunkNext = base;
                 chunkEnd = (a.nJobs - base < took) ? a.nJobs : base + took;
+                // Tile order: the k-th grab works on tile tileOrder[k] (a permutation of the tiles, heavy ones first: "Tile order" below) in place
+                // of tile k.  Only the moment a tile starts depends on it: chunkNext / chunkEnd are that tile's 64 jobs as before.
+                if (ORDER && a.tileCost != nullptr) {
+                    uint32_t tile = base >> 6;
+                    if (a.tileOrder != nullptr) {
+                        tile = (uint32_t)__builtin_amdgcn_readfirstlane((int)a.tileOrder[tile]);
+                        chunkNext = tile << 6; chunkEnd = chunkNext + 64u;
+                    }
+                    if (lane == 0) { tileSt[0] = tile; tileSt[TILE_EVALS] = waveEvals; }
+                }
             }
             uint32_t avail = chunkEnd - chunkNext;
             if (VIEWS && a.mode == 0u) {
@@ -2454,6 +2480,148 @@ extern "C" __global__ void ft_selftest_kernel(int op, uint32_t lo, uint32_t hi, 
         bad += __float_as_uint(a) != __float_as_uint(b);
     }
     if (bad) atomicAdd(mismatches, bad);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Tile order (FT_OPT_ORDER; DESIGN.md section 4 "Tile order"): from the costs a trace launch recorded per tile (ft_trace_body refill), the order in
+// which the next launch of the same grid hands its tiles out.  Tiles whose cost is at least num / den of the launch's mean cost come first, in
+// non-increasing cost clamped to 255 (equal costs in any order); all other tiles follow in ascending index, so that the many cheap tiles stay
+// mixed with ordinary ones instead of ending the queue as a race on its counter.  Three launches on the trace launch's stream, FT_ORDER_TILES tiles
+// a workgroup, no waiting between workgroups: the last workgroup of a launch to finish (a ticket) does the launch's one-workgroup step.
+//   count:   histogram of the clamped costs and their exact sum; last workgroup: first position of every heavy cost, from 255 down
+//   heavy:   heavy tiles per workgroup; last workgroup: their exclusive prefix over the workgroups, and the total
+//   scatter: a heavy tile takes the next position of its cost; a light tile i goes to total + i - (heavy tiles below i)
+// Whatever the costs hold, every position 0 .. n-1 is taken once.  A mean above 255 leaves heavy tiles only at the clamped cost 255, which starts at 0.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ bool ft_tile_is_heavy(uint32_t cost, unsigned long long sum, uint32_t n, uint32_t num, uint32_t den) {
+    return (unsigned long long)cost * n * den >= sum * num;           // cost >= (num / den) * (sum / n), exactly
+}
+__device__ __forceinline__ uint32_t ft_order_load(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+// this workgroup is the launch's last one to arrive: everything the others wrote before their tickets is visible to it
+__device__ __forceinline__ bool ft_order_last_block(uint32_t* ticket) {
+    __shared__ uint32_t last;
+    __threadfence();
+    __syncthreads();
+    if (threadIdx.x == 0) last = atomicAdd(ticket, 1u) == gridDim.x - 1u ? 1u : 0u;
+    __syncthreads();
+    if (last) __threadfence();
+    return last != 0u;
+}
+// exclusive prefix of v over the 256 threads of the workgroup; total: the sum over all of them
+__device__ __forceinline__ uint32_t ft_order_block_scan(uint32_t v, uint32_t& total) {
+    __shared__ uint32_t waveSum[4];
+    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+    uint32_t inc = v;
+    for (int off = 1; off < 64; off <<= 1) { const uint32_t t = __shfl_up(inc, off, 64); if (lane >= (uint32_t)off) inc += t; }
+    __syncthreads();                                                   // the previous use of waveSum is over
+    if (lane == 63u) waveSum[w] = inc;
+    __syncthreads();
+    uint32_t before = 0;
+    for (uint32_t k = 0; k < w; ++k) before += waveSum[k];
+    total = waveSum[0] + waveSum[1] + waveSum[2] + waveSum[3];
+    return before + inc - v;
+}
+
+extern "C" __global__ void __launch_bounds__(256) ft_tile_order_count_kernel(const uint32_t* __restrict__ cost, uint32_t n, uint32_t num, uint32_t den, FtTileOrderWork* __restrict__ w) {
+    __shared__ uint32_t h[256];
+    __shared__ unsigned long long s;
+    const uint32_t tid = threadIdx.x;
+    h[tid] = 0u;
+    if (tid == 0) s = 0ull;
+    __syncthreads();
+    unsigned long long mine = 0ull;
+    for (uint32_t k = 0; k < FT_ORDER_TILES / 256u; ++k) {
+        const uint32_t i = blockIdx.x * FT_ORDER_TILES + k * 256u + tid;
+        if (i < n) { const uint32_t c = cost[i]; atomicAdd(&h[c < 255u ? c : 255u], 1u); mine += c; }
+    }
+    if (mine) atomicAdd(&s, mine);
+    __syncthreads();
+    if (h[tid]) atomicAdd(&w->hist[tid], h[tid]);
+    if (tid == 0 && s) atomicAdd(&w->sum, s);
+    if (!ft_order_last_block(&w->ticketCount)) return;
+    // first position of cost `tid`: the heavy tiles of every larger cost come before it
+    const unsigned long long sum = __hip_atomic_load(&w->sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const uint32_t cnt = ft_tile_is_heavy(tid, sum, n, num, den) ? ft_order_load(&w->hist[tid]) : 0u;
+    h[tid] = cnt;
+    __syncthreads();
+    uint32_t first = 0;
+    for (uint32_t c = tid + 1u; c < 256u; ++c) first += h[c];
+    w->cursor[tid] = first;
+}
+
+extern "C" __global__ void __launch_bounds__(256) ft_tile_order_heavy_kernel(const uint32_t* __restrict__ cost, uint32_t n, uint32_t num, uint32_t den, FtTileOrderWork* __restrict__ w,
+                                                                           uint32_t* __restrict__ blockHeavy) {
+    __shared__ uint32_t cntS;
+    const uint32_t tid = threadIdx.x;
+    if (tid == 0) cntS = 0u;
+    __syncthreads();
+    const unsigned long long sum = w->sum;
+    uint32_t mine = 0;
+    for (uint32_t k = 0; k < FT_ORDER_TILES / 256u; ++k) {
+        const uint32_t i = blockIdx.x * FT_ORDER_TILES + k * 256u + tid;
+        if (i < n && ft_tile_is_heavy(cost[i], sum, n, num, den)) mine += 1u;
+    }
+    if (mine) atomicAdd(&cntS, mine);
+    __syncthreads();
+    if (tid == 0) blockHeavy[blockIdx.x] = cntS;
+    if (!ft_order_last_block(&w->ticketHeavy)) return;
+    // exclusive prefix over the workgroups, in place: thread t owns a run of consecutive workgroups
+    const uint32_t nb = gridDim.x, per = (nb + 255u) / 256u, lo = tid * per, hi = lo + per < nb ? lo + per : nb;
+    uint32_t run = 0;
+    for (uint32_t b = lo; b < hi; ++b) run += ft_order_load(&blockHeavy[b]);
+    uint32_t total;
+    uint32_t before = ft_order_block_scan(run, total);
+    for (uint32_t b = lo; b < hi; ++b) { const uint32_t c = ft_order_load(&blockHeavy[b]); blockHeavy[b] = before; before += c; }
+    if (tid == 0) w->nHeavy = total;
+}
+
+extern "C" __global__ void __launch_bounds__(256) ft_tile_order_scatter_kernel(const uint32_t* __restrict__ cost, uint32_t n, uint32_t num, uint32_t den, FtTileOrderWork* __restrict__ w,
+                                                                             const uint32_t* __restrict__ blockHeavy, uint32_t* __restrict__ order) {
+    // thread t owns FT_ORDER_TILES / 256 consecutive tiles, so that the scan over the threads is a scan over the tiles in index order
+    constexpr uint32_t PER = FT_ORDER_TILES / 256u;
+    const uint32_t tid = threadIdx.x, i0 = blockIdx.x * FT_ORDER_TILES + tid * PER;
+    const unsigned long long sum = w->sum;
+    const uint32_t nHeavy = w->nHeavy;
+    uint32_t c[PER], heavy = 0, cntHeavy = 0;
+    for (uint32_t k = 0; k < PER; ++k) {
+        c[k] = i0 + k < n ? cost[i0 + k] : 0u;
+        if (i0 + k < n && ft_tile_is_heavy(c[k], sum, n, num, den)) { heavy |= 1u << k; cntHeavy += 1u; }
+    }
+    // the workgroup's heavy tiles of one cost take one run of that cost's positions: ranks inside the run from an LDS counter, one global atomic per
+    // cost and workgroup (thousands of tiles share the costs near the mean; one global atomic per tile took 0.29 ms of a 4096^2 frame's order)
+    __shared__ uint32_t run[256], first[256];
+    run[tid] = 0u;
+    __syncthreads();
+    uint32_t rank[PER];
+    for (uint32_t k = 0; k < PER; ++k) rank[k] = (heavy >> k & 1u) ? atomicAdd(&run[c[k] < 255u ? c[k] : 255u], 1u) : 0u;
+    __syncthreads();
+    if (run[tid]) first[tid] = atomicAdd(&w->cursor[tid], run[tid]);
+    uint32_t total;
+    uint32_t below = blockHeavy[blockIdx.x] + ft_order_block_scan(cntHeavy, total);       // heavy tiles of smaller index (the scan's barriers also publish `first`)
+    for (uint32_t k = 0; k < PER; ++k) {
+        const uint32_t i = i0 + k;
+        if (i >= n) break;
+        uint32_t pos;
+        if (heavy >> k & 1u) { pos = first[c[k] < 255u ? c[k] : 255u] + rank[k]; below += 1u; }
+        else pos = nHeavy + (i - below);
+        if (pos < n) order[pos] = i;
+    }
+}
+
+extern "C" size_t ft_tile_order_work_bytes(uint32_t nTiles) {
+    return sizeof(FtTileOrderWork) + sizeof(uint32_t) * (size_t)((nTiles + FT_ORDER_TILES - 1u) / FT_ORDER_TILES);
+}
+extern "C" hipError_t ft_launch_tile_order(const uint32_t* cost, uint32_t nTiles, uint32_t num, uint32_t den, uint32_t* order, void* work, hipStream_t st) {
+    if (nTiles == 0u || den == 0u) return hipErrorInvalidValue;
+    FtTileOrderWork* w = static_cast<FtTileOrderWork*>(work);
+    uint32_t* blockHeavy = reinterpret_cast<uint32_t*>(w + 1);
+    const uint32_t blocks = (nTiles + FT_ORDER_TILES - 1u) / FT_ORDER_TILES;
+    hipError_t e = hipMemsetAsync(w, 0, sizeof(FtTileOrderWork), st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(ft_tile_order_count_kernel, dim3(blocks), dim3(256), 0, st, cost, nTiles, num, den, w);
+    hipLaunchKernelGGL(ft_tile_order_heavy_kernel, dim3(blocks), dim3(256), 0, st, cost, nTiles, num, den, w, blockHeavy);
+    hipLaunchKernelGGL(ft_tile_order_scatter_kernel, dim3(blocks), dim3(256), 0, st, cost, nTiles, num, den, w, blockHeavy, order);
+    return hipGetLastError();
 }
 
 // ------------------------------------------------------------------------------------------------

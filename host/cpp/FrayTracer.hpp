@@ -44,6 +44,7 @@ public:
     ~Context() { ft_ctx_destroy(ctx_); }
     // per-context switches (ft_option); e.g. setOption(FT_OPT_MATH, FT_MATH_GLIBC_FMA): MathF.Exp / Log / Pow as this host's glibc computes them
     void setOption(ft_option option, int value) { check(ft_ctx_set_option(ctx_, (int32_t)option, value)); }
+    // FT_OPT_ORDER (on by default): a scene's repeated frames hand out last frame's heavy tiles first; setOption(FT_OPT_ORDER, 0) keeps index order
     int getOption(ft_option option) const { int32_t v = 0; check(ft_ctx_get_option(ctx_, (int32_t)option, &v)); return v; }
     static std::string buildInfo() { return ft_build_info(); }
     Context(const Context&) = delete;

@@ -63,7 +63,7 @@ module Native =
     [<DllImport(Lib)>] extern int ft_abi_version()
     [<DllImport(Lib)>] extern nativeint ft_build_info()
     [<DllImport(Lib)>] extern int ft_ctx_create(int device, nativeint& ctx)
-    // per-context switches (ft_option: 1 refill_min, 2 max_blocks_per_cu, 3 host_chunks, 4 host_pin, 5 tail_k, 6 math, 7 guided, 8 chunk); the library reads no environment
+    // per-context switches (ft_option: 1 refill_min, 2 max_blocks_per_cu, 3 host_chunks, 4 host_pin, 5 tail_k, 6 math, 7 guided, 8 chunk, 16 order); the library reads no environment
     [<DllImport(Lib)>] extern int ft_ctx_set_option(nativeint ctx, int option, int value)
     [<DllImport(Lib)>] extern void ft_ctx_destroy(nativeint ctx)
     [<DllImport(Lib)>] extern nativeint ft_last_error()
@@ -146,6 +146,11 @@ module Native =
     let setExactShortcuts (on : bool) =
         for opt in [ 9; 10; 11 ] do
             if ft_ctx_set_option (ctx.Value, opt, (if on then 1 else 0)) < 0 then failwith (Marshal.PtrToStringAnsi (ft_last_error ()))
+
+    /// FT_OPT_ORDER (16), on by default: a frame records what each 8x8 tile cost, and the scene's next frame of the same size hands out the tiles that cost
+    /// at least the mean first, most expensive first (a turntable, any stream of frames: the frame no longer ends on a long tile that started late).
+    /// Same frame, counters and flags; 0 = index order, 2 = record only
+    let setTileOrder (mode : int) = if ft_ctx_set_option (ctx.Value, 16, mode) < 0 then failwith (Marshal.PtrToStringAnsi (ft_last_error ()))
 
     let check (h : int) =
         if h < 0 then failwith (Marshal.PtrToStringAnsi (ft_last_error ())) else h

@@ -141,6 +141,12 @@ typedef enum ft_option {
                                    * from one ray on, 2 every second round (shadow rays from their 2nd step), 3 off.  255 / 255 in bits 0-15: the bundle alone.
                                    * Word 0 = 0 | 6 << 8 | 16 << 16 | 6 << 24 with the shipped bundle schedule, except that a camera frame (ft_render and its hits form) whose 8x8 pixel tiles are at most
                                    * the certificate's margin wide at the far side of the scene's support sphere gets the bundle alone (255 / 255): an explicit word is always taken as it stands */
+    FT_OPT_ORDER = 16,            /* 1 (default): a frame (ft_render_device and the entry points built on it; the reference's sampling, whole 8x8 tiles) records per tile how many
+                                   * evaluation rounds it took, and the scene's next frame of the same size, column range and stripe layout on the same render lane hands out first
+                                   * the tiles that cost at least the mean, most expensive first, so that no long tile starts late and the frame's drain shortens; the other
+                                   * tiles keep their index order.  Only when a tile starts changes: same frame, counters and flags.  The camera, epsilon, Length and the
+                                   * lights may differ between the two frames (a stale order is only another order); a first frame runs in index order.  2: record only;
+                                   * 0: off.  Not combined with FT_OPT_GUIDED = 1, which stays in index order */
     FT_OPT_GUIDED = 7             /* 1: the last jobs of a launch are handed out in half and quarter tiles (lean kernel); 0 (default): whole tiles only */
 } ft_option;
 /* MathF.Exp / MathF.Log (SdfForm.unionSmooth, SdfForm.fs:80,82) and MathF.Pow (FColor.gammaInverse, FColor.fs:50-55) are the C runtime's

@@ -30,6 +30,7 @@ if "math" in applied and applied["math"] != 0:
     ob.lib.orc_set_libm(1)
 bad, culled, rays, lean = [], [], 0, 0
 t0 = time.time()
+REPEAT = int(os.environ.get("FT_REPEAT", "1"))           # renders per scene, each checked
 for seed in range(first, first + count):
     rng = np.random.default_rng(seed)
     n = int(rng.integers(32, 401))
@@ -61,12 +62,13 @@ for seed in range(first, first + count):
     length = float(spread * rng.uniform(2.0, 40.0))
     ds = dev.scene(scene)
     lean += ds.info()["fast_path"] == 1
-    g, st = ds.render(eps, length, ft.ImageSize(W, H), cam)
     o, cnt = ob.Oracle().scene(scene).render(eps, length, W, H, cam.as_array(), nthreads=16)
-    same = np.array_equal(g.view(np.uint32), o.view(np.uint32))
     keys = ("rays_primary", "rays_shadow", "hits_primary", "hits_shadow", "flags")
-    if not same or any(st[k] != cnt[k] for k in keys):
-        bad.append((seed, int((g.view(np.uint32) != o.view(np.uint32)).sum()), {k: (st[k], cnt[k]) for k in keys if st[k] != cnt[k]}))
+    for rep in range(REPEAT):                                     # FT_REPEAT=2: the second launch hands its tiles out in the order built behind the first (FT_OPT_ORDER)
+        g, st = ds.render(eps, length, ft.ImageSize(W, H), cam)
+        same = np.array_equal(g.view(np.uint32), o.view(np.uint32))
+        if not same or any(st[k] != cnt[k] for k in keys):
+            bad.append((seed, rep, int((g.view(np.uint32) != o.view(np.uint32)).sum()), {k: (st[k], cnt[k]) for k in keys if st[k] != cnt[k]}))
     culled.append(st["culled_fraction"]); rays += st["rays_primary"] + st["rays_shadow"]
     if (seed - first + 1) % (5 if wide else 25) == 0:
         print(f"... {seed - first + 1} scenes, {len(bad)} mismatches, {time.time() - t0:.0f} s", flush=True)

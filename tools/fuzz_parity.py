@@ -26,6 +26,7 @@ if "math" in applied and applied["math"] != 0:
     assert applied["math"] == ft.glibc_build_of_this_host(), "FT_MATH must be the glibc build of this host"
 bad, skipped, flagged, rays, glassy = [], 0, 0, 0, 0
 t0 = time.time()
+REPEAT = int(os.environ.get("FT_REPEAT", "1"))           # renders per scene, each checked
 for seed in range(first, first + count):
     length = syn.RAY_LENGTH
     if edge: scene, cam, size, eps, length, ext = syn.fuzz_scene_edge(seed)
@@ -39,12 +40,13 @@ for seed in range(first, first + count):
         except ob.OracleError:
             skipped += 1
         continue
-    g, st = ds.render(eps, length, size, cam, **ext)
     o, cnt = ob.Oracle().scene(scene).render(eps, length, size.X, size.Y, cam.as_array(), nthreads=8, **ext)
-    same = np.array_equal(g.view(np.uint32), o.view(np.uint32))
     keys = ("rays_primary", "rays_shadow", "rays_ext", "hits_primary", "hits_shadow", "flags")
-    if not same or any(st[k] != cnt[k] for k in keys):
-        bad.append((seed, int((g.view(np.uint32) != o.view(np.uint32)).sum()), {k: (st[k], cnt[k]) for k in keys if st[k] != cnt[k]}, ext))
+    for rep in range(REPEAT):                        # FT_REPEAT=2: the second launch hands its tiles out in the order built behind the first (FT_OPT_ORDER)
+        g, st = ds.render(eps, length, size, cam, **ext)
+        same = np.array_equal(g.view(np.uint32), o.view(np.uint32))
+        if not same or any(st[k] != cnt[k] for k in keys):
+            bad.append((seed, rep, int((g.view(np.uint32) != o.view(np.uint32)).sum()), {k: (st[k], cnt[k]) for k in keys if st[k] != cnt[k]}, ext))
     flagged += st["flags"] != 0
     glassy += st["rays_ext"] > 0
     rays += st["rays_primary"] + st["rays_shadow"] + st["rays_ext"]

@@ -54,15 +54,16 @@ def bundle(idx, pts, dirs, Ls, axis, pad):
     return mem if total < thr else mem[:0]
 
 
-def replay(cert, prim, shad, minDue, repeat, axis=None, period=1, minMem=1, shadowFrom=0, B=200.0, pad=0.0, latency=False):
-    """lock-step waves; -> evaluation rounds, priced evaluation VALU, certificate VALU, bundle tries, bundles that held"""
+def replay(cert, prim, shad, minDue, repeat, axis=None, period=1, minMem=1, shadowFrom=0, B=200.0, pad=0.0, latency=False, per_tile=None):
+    """lock-step waves; -> evaluation rounds, priced evaluation VALU, certificate VALU, bundle tries, bundles that held; per_tile: a list that receives
+    every tile's rounds"""
     rounds = 0; ev = 0.0; cv = 0.0; tries = 0; held = 0
     for t in range(T):
         ph = np.zeros(64, int); stp = np.zeros(64, int); due = np.zeros(64)
         L = [lanes[t * 64 + j] for j in range(64)]
         for j in range(64): ph[j] = 0 if len(L[j][0]) else (1 if L[j][1] else 3); due[j] = prim
         nrmLeft = np.full(64, 4)
-        wave = 0
+        wave = 0; before = rounds
         while True:
             for j in range(64):
                 while True:
@@ -101,6 +102,7 @@ def replay(cert, prim, shad, minDue, repeat, axis=None, period=1, minMem=1, shad
             rounds += 1; wave += 1
             ev += E * min(1.0, 1.34 * act / 64.0) if latency and act <= 32 else E
             stp[(ph == 0) | (ph == 2)] += 1; nrmLeft[ph == 1] -= 1
+        if per_tile is not None: per_tile.append(rounds - before)
     return rounds, ev, cv, tries, held
 
 
