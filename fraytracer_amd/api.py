@@ -428,6 +428,10 @@ class Device:
     # "order" = FT_OPT_ORDER, 1 (default) heavy tiles of the last frame first, 2 record tile costs only, 0 off
     SCHEDULE_OPTIONS = {"order": _lib.FT_OPT_ORDER}
 
+    # exact shortcuts like "cert" / "cert_policy" (same frame, counters and flags; sdf_evals falls), apart from OPTIONS for the same pin:
+    # "occl" = FT_OPT_OCCL, the occlusion certificate (1 default, 0 off), "occl_policy" = FT_OPT_OCCL_POLICY, its schedule word
+    CERTIFICATE_OPTIONS = {"occl": _lib.FT_OPT_OCCL, "occl_policy": _lib.FT_OPT_OCCL_POLICY}
+
     def set_option(self, name, value):
         """ft_ctx_set_option: per-context switches (the library reads no environment variables)"""
         check(lib.ft_ctx_set_option(self._ctx, self._option_id(name), int(value)))
@@ -438,7 +442,10 @@ class Device:
         return int(v.value)
 
     def _option_id(self, name):
-        return self.OPTIONS[name] if name in self.OPTIONS else self.SCHEDULE_OPTIONS[name]
+        for table in (self.OPTIONS, self.SCHEDULE_OPTIONS):
+            if name in table:
+                return table[name]
+        return self.CERTIFICATE_OPTIONS[name]
 
     # constructor twins ---------------------------------------------------------------------------
     def sphere(self, c, r): return check(lib.ft_form_sphere(self._ctx, C.byref(_lib.Sphere(_vec(c), r))))
@@ -672,6 +679,12 @@ class DeviceScene:
         v = (C.c_float * 5)()
         check(lib.ft_scene_miss_certificate(self._scene, v))
         return dict(zip(("margin", "clip", "rho2", "len_factor", "steps"), (float(x) for x in v)))
+
+    def occlusion_certificate(self):
+        """{step, base, eps_min, cap, len_inv, near, reach}: the constants of the smooth-union kernel's occlusion certificate (base < 0: none)"""
+        v = (C.c_float * 7)()
+        check(lib.ft_scene_occlusion_certificate(self._scene, v))
+        return dict(zip(("step", "base", "eps_min", "cap", "len_inv", "near", "reach"), (float(x) for x in v)))
 
     def miss_certificate_clusters(self):
         """(clusters, members): clusters a float32 array (K, 4) of centre xyz and radius, members a list of K arrays (n_c, 4) of the children

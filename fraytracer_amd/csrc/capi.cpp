@@ -68,6 +68,8 @@ struct ft_ctx {
     int optCert = 1;                                       // FT_OPT_CERT: the lean kernel's miss certificate (kernels.hip ft_miss_certificate); needs optEscape
     int optCertPolicy = 0;                                 // FT_OPT_CERT_POLICY: 0 = FT_CERT_POLICY_DEFAULT
     int optGuided = 0;                                     // FT_OPT_GUIDED: smaller chunks at the end of the job queue (lean kernel; measured: no gain)
+    int optOccl = 1;                                       // FT_OPT_OCCL: the lean kernel's occlusion certificate (kernels.hip ft_occlusion_certificate); needs optEscape
+    int optOcclPolicy = 0;                                 // FT_OPT_OCCL_POLICY: 0 = the shipped schedule (FT_OCCL_PERIOD ...)
     int optOrder = 1;                                      // FT_OPT_ORDER: 1 = frames hand their heavy tiles out first, from the costs the scene's last launch of the same grid recorded; 2 = record only; 0 = off
     uint32_t orderNum = 1, orderDen = 1;                   // a tile is heavy from orderNum / orderDen of the mean cost on (ft_ctx_tile_order_rule: the probes' other rules)
 };
@@ -244,6 +246,9 @@ constexpr int FT_CERT_POLICY_DEFAULT = 0 | (6 << 8) | (16 << 16) | (6 << 24);
 // the bundle certificate's shipped schedule (bits 30-31 of the policy word = 0): every 2nd evaluation round of a wave, from one primary ray on, and from one
 // shadow ray of 2 or more steps on (DESIGN.md section 5 "Bundle certificate on C3": the schedules measured)
 constexpr uint32_t FT_BUNDLE_PERIOD = 2u, FT_BUNDLE_MIN = 1u, FT_BUNDLE_SHADOW = 2u;
+// the occlusion certificate's shipped schedule (FT_OPT_OCCL_POLICY = 0): every 2nd evaluation round of a wave, for the shadow rays that have come into being
+// since its last try, from one such ray on (DESIGN.md section 5 "Occlusion certificate on C3": the schedules measured)
+constexpr uint32_t FT_OCCL_PERIOD = 2u, FT_OCCL_MIN = 1u;
 constexpr int FT_TAIL_K_LEAN = 32, FT_TAIL_K_GENERAL = 2, FT_TAIL_K_CARVED = 1;      // carved: 1.26 ms at 0 / 1 against 1.29 at 2 on the 1000^2 Program.fs frame (profiles/r04_carved_variants.txt)
 // does this launch take the glibc build of the kernels?
 bool libmLaunch(const ft_ctx* c, const ft_scene* s) { return c->optMath != FT_MATH_FIXED && s->usesExpLog; }
@@ -406,6 +411,18 @@ int launchTrace(ft_ctx* c, const ft_scene* s, FtRenderArgs& a, int lane = 0) {
     }
     a.lazy = c->optLazyUnion ? 1u : 0u;
     a.reuse = (c->optReuse && !a.shade) ? 1u : 0u;     // ft_shade_hits: no centre probe ran, nothing to reuse
+    // occlusion certificate: lean kernel (and its EXTENSION build: a render and its ft_render_hits twin count the same evaluations), only with the escape shortcut (the same support sphere and per-step drift) and with FT_OPT_CERT, which
+    // switches every certificate: with it off a launch evaluates exactly what its rays' marches ask for.  Policy word: bits 0-7
+    // the period in evaluation rounds (0: shipped, 255: off), 8-15 steps a shadow ray takes before its try, 16-23 the candidates a try waits for (0: shipped).
+    // A ray's first evaluation taken from the cache (FT_OPT_REUSE) is its step 0: it comes into being with one step taken
+    {
+        const uint32_t pol = (uint32_t)c->optOcclPolicy, per = pol & 255u, mn = (pol >> 16) & 255u;
+        const bool on = variant == 1u && c->optEscape && c->optCert && c->optOccl && s->flat.occB >= 0.0f && s->dev.certM >= 0.0f && per != 255u;
+        a.occPeriod = on ? (per != 0u ? per : FT_OCCL_PERIOD) : 0u;
+        a.occFrom = ((pol >> 8) & 255u) + a.reuse;
+        a.occMin = mn != 0u ? mn : FT_OCCL_MIN;
+        a.occE = s->flat.occE; a.occB = s->flat.occB; a.occEpsMin = s->flat.occEpsMin; a.occCap = s->flat.occCap; a.occLenInv = s->flat.occLenInv; a.occNear = s->flat.occNear; a.occReach = s->flat.occReach;
+    }
     a.S.mathFma = c->optMath == FT_MATH_GLIBC_FMA ? 1u : 0u;
     a.materialsExt = s->dMaterialsExt;
     // FT_OPT_ORDER.  Eligible: a frame of whole tiles taken one at a time, on the kernel that keeps the bookkeeping (the lean kernel).
@@ -460,6 +477,8 @@ constexpr OptionSpec kOptions[] = {
     {FT_OPT_CERT, &ft_ctx::optCert, 0, 1, "FT_OPT_CERT: 0 or 1"},
     {FT_OPT_CERT_POLICY, &ft_ctx::optCertPolicy, INT32_MIN, INT32_MAX, "FT_OPT_CERT_POLICY: 0, or bits 16-23 (due lanes) in 1 .. 64"},
     {FT_OPT_ORDER, &ft_ctx::optOrder, 0, 2, "FT_OPT_ORDER: 0 off, 1 heavy tiles first, 2 record only"},
+    {FT_OPT_OCCL, &ft_ctx::optOccl, 0, 1, "FT_OPT_OCCL: 0 or 1"},
+    {FT_OPT_OCCL_POLICY, &ft_ctx::optOcclPolicy, 0, 0x40ffff, "FT_OPT_OCCL_POLICY: 0, or bits 0-7 period, 8-15 first step, 16-23 candidates (0 .. 64)"},
 };
 const OptionSpec* findOption(int32_t id) {
     for (const OptionSpec& o : kOptions) if (o.id == id) return &o;
@@ -1538,6 +1557,12 @@ int ft_scene_miss_certificate(const ft_scene* s, float out[5]) {
     if (!s || !out) return setErr(FT_ERR_INVALID, "null argument");
     const ft::FlatScene& f = s->flat;
     out[0] = f.certM; out[1] = f.certClip; out[2] = f.certRho2; out[3] = f.certLenF; out[4] = (float)f.certSteps;
+    return FT_OK;
+}
+int ft_scene_occlusion_certificate(const ft_scene* s, float out[7]) {
+    if (!s || !out) return setErr(FT_ERR_INVALID, "null argument");
+    const ft::FlatScene& f = s->flat;
+    out[0] = f.occE; out[1] = f.occB; out[2] = f.occEpsMin; out[3] = f.occCap; out[4] = f.occLenInv; out[5] = f.occNear; out[6] = f.occReach;
     return FT_OK;
 }
 int ft_scene_miss_certificate_clusters(const ft_scene* s, int32_t* nClusters, int32_t* nChildren, float* out, int32_t capacity) {

@@ -105,6 +105,11 @@ struct FtRenderArgs {
     // where not NULL, is a permutation of the tiles: the grab at cursor position 64 k works on tile tileOrder[k] (ft_launch_tile_order builds it)
     uint32_t* tileCost;
     const uint32_t* tileOrder;
+    // occlusion certificate (lean kernel; kernels.hip ft_occlusion_certificate; appended; the constants are the scene's, scene.cpp
+    // "Occlusion certificate"): tried every occPeriod-th evaluation round of a wave (0: never) for its shadow rays of occFrom .. occFrom + occPeriod - 1
+    // steps — each ray meets exactly one such round — where at least occMin (>= 1) lanes hold such a ray
+    uint32_t occPeriod, occFrom, occMin;
+    float occE, occB, occEpsMin, occCap, occLenInv, occNear, occReach;
 };
 #define FT_MAX_VIEWS 64       // views per launch (one PH_CAM value per lane); ft_render_views splits larger batches
 

@@ -1493,6 +1493,92 @@ __device__ __forceinline__ bool ft_bundle_certificate(const FtSceneDev& S, const
     return mem && total < thr;                                         // a NaN anywhere: fails
 }
 
+// Occlusion certificate (FT_OPT_OCCL; lean kernel and its EXTENSION build, shadow rays outside glass bodies): the counterpart of the miss certificates for shadow rays that are bound to HIT.  Of such a
+// ray only the fact is used (SdfLight.fs:20), never position or leaf, and where its line o + t dir has a point with f <= -hitM at a parameter t* short of its
+// Length, the reference's march cannot get past t* and ends in a hit (scene.cpp "Occlusion certificate": f is 1-Lipschitz, the drift of the at most
+// t* / epsilon marched points, the float32 evaluation; hitM = occE (t* / epsilon + 2) + occB).  The lane then takes the exit of an evaluation below epsilon.
+// One try for all the shadow rays of the wave that ask (`cand`), children across the lanes as in ft_bundle_certificate:
+//   axis    one candidate's line (the first at or after lane 27, else the first), its rest 0 <= t <= Length occLenInv;
+//   pass A  lane k of pass j: depth r_i - dist(axis, c_i) of child 64 j + k; a wave maximum names the deepest child i* and its closest approach sigma*.
+//           No child within occNear = s ln n of the axis: f > 0 all along it, and the wave leaves (most tiles hold no occluder);
+//   pass B  the same layout sums S = sum_i 2^(A (|c_i - y| - r_i)) at the witness y = axis(sigma*): D = s ln S = -f(y), v_sqrt_f32 / v_exp_f32 / v_log_f32 with
+//           their errors inside eGeo and eSum, which occB carries.  Every point within rho of y has f <= rho - D;
+//   lanes   every candidate tests its OWN line — closest approach t* clamped to its own rest, its own epsilon and hitM — against the sphere i* (f <= d_i*) and
+//           against the ball around y: dist + hitM < r_i*, or dist + hitM < D.  So the lit lanes of a tile at a shadow edge do not stop the occluded ones, and
+//           the axis decides nothing but which sphere and which witness are asked.
+// Gate, never wider than the miss certificate's: its constants and the support sphere exist, occEpsMin <= epsilon <= escR, 0 < Length < 1e9,
+// 0.81 <= |dir|^2 <= 1 + 1e-6 (a longer direction over-steps: a point light's rays march on), a start within sqrt(certRho2) of escC, steps below half the cap.
+// Reach: t* <= occReach = 100 ln 2 s - occCap.  Up to t* every marched point has f <= t* + occCap, so the true sum is >= 2^-100 there: the reference's float32 sum
+// cannot underflow to 0 (its value would be +inf, a miss), and the terms it flushes are the n 2^-26 of the sum that eSum already carries.
+// Float32: closest approaches and distances are eGeo's (in occB); the comparisons carry 0.1 % more.  A NaN anywhere fails a comparison: no certificate.
+// Executed by all 64 lanes.  -> this lane's march ends in a hit.
+__device__ __forceinline__ bool ft_occlusion_certificate(const FtRenderArgs& a, const float* __restrict__ ldsC, bool cand, const f3 o, const f3 dir, float eps, float len,
+                                                         uint32_t steps) {
+    const FtSceneDev& S = a.S;
+    const f3 w = o - mk3(S.escC[0], S.escC[1], S.escC[2]);
+    const float dd = ft_dot(dir, dir);
+    const bool ok = cand && a.occB >= 0.0f && S.escR >= 0.0f && eps >= a.occEpsMin && eps <= S.escR && len > 0.0f && len < 1e9f && dd >= 0.81f && dd <= 1.000001f &&
+                    ft_dot(w, w) <= S.certRho2 && steps < FT_STEP_CAP / 2u;
+    const unsigned long long mm = __ballot(ok);
+    if (mm == 0ull) return false;
+    const FtInstr FT_CONST* in = as_const(S.instr);                    // instruction 0: the run
+    const uint32_t n = in->count;
+    const float si = in->f0;
+    const float4* c = reinterpret_cast<const float4*>(ldsC + in->data);
+    const float tEnd = len * a.occLenInv;
+    const int ax = (mm >> 27) != 0ull ? 26 + __ffsll((long long)(mm >> 27)) : __ffsll((long long)mm) - 1;
+    const f3 oc = ft_readlane3(o, ax), dc = ft_readlane3(dir, ax);
+    const float tc = ft_readlane_f(tEnd, ax), idc = 1.0f / ft_dot(dc, dc);
+    const uint32_t lane = threadIdx.x & 63u;
+    // the distance of p from the line q + t e, 0 <= t <= tMaxi (ie = 1 / |e|^2), and that t
+    auto approach = [](const f3 p, const f3 q, const f3 e, const float ie, const float tMaxi, float& t) {
+        const float vx = p.x - q.x, vy = p.y - q.y, vz = p.z - q.z;
+        t = __builtin_amdgcn_fmed3f(__builtin_fmaf(vz, e.z, __builtin_fmaf(vy, e.y, vx * e.x)) * ie, 0.0f, tMaxi);
+        const float ex = __builtin_fmaf(-t, e.x, vx), ey = __builtin_fmaf(-t, e.y, vy), ez = __builtin_fmaf(-t, e.z, vz);
+        return __builtin_amdgcn_sqrtf(__builtin_fmaf(ez, ez, __builtin_fmaf(ey, ey, ex * ex)));
+    };
+    float best = 0.0f, tAx;                                            // nearness depth + occNear, kept >= 0 for the wave maximum
+    uint32_t bi = 0u;
+    for (uint32_t base = 0; base < n; base += 64u) {
+        const uint32_t i = base + lane;
+        const float4 prm = c[i < n ? i : n - 1u];
+        const float nr = (prm.w + a.occNear) - approach(mk3(prm.x, prm.y, prm.z), oc, dc, idc, tc, tAx);
+        if (i < n && nr > best) { best = nr; bi = i; }
+    }
+    const float nearest = ft_wave_max_all(best);
+    if (!(nearest > 0.0f)) return false;
+    const int src = __ffsll((long long)__ballot(best == nearest)) - 1;
+    const float4 sp = c[(uint32_t)__builtin_amdgcn_readlane((int)bi, src)];    // bi < n in every lane
+    (void)approach(mk3(sp.x, sp.y, sp.z), oc, dc, idc, tc, tAx);
+    const f3 y = oc + dc * tAx;                                        // the witness, as the float32 triple every lane uses below
+    const float A = si * 1.44269504f;
+    float sum = 0.0f;
+    for (uint32_t base = 0; base < n; base += 64u) {
+        const uint32_t i = base + lane;
+        const float4 prm = c[i < n ? i : n - 1u];
+        const float dx = prm.x - y.x, dy = prm.y - y.y, dz = prm.z - y.z;
+        const float term = __builtin_amdgcn_exp2f((__builtin_amdgcn_sqrtf(__builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx))) - prm.w) * A);
+        sum += i < n ? term : 0.0f;
+    }
+    float total;
+    ft_wave_scan_incl(sum, total);
+    const float D = __builtin_amdgcn_logf(total) * (-0.693147181f / si);          // s ln S = -f(y)
+    const float ie = 1.0f / eps, idd = 1.0f / dd;
+    float t;
+    bool holds = false;
+    {
+        const float dist = approach(mk3(sp.x, sp.y, sp.z), o, dir, idd, tEnd, t);
+        const float nSteps = __builtin_fmaf(t, ie, 2.0f), hitM = __builtin_fmaf(a.occE, nSteps, a.occB);
+        holds = t <= a.occReach && nSteps < 131072.0f && hitM <= a.occCap && (dist + hitM) * 1.001f < sp.w;
+    }
+    {
+        const float dist = approach(y, o, dir, idd, tEnd, t);
+        const float nSteps = __builtin_fmaf(t, ie, 2.0f), hitM = __builtin_fmaf(a.occE, nSteps, a.occB);
+        holds = holds || (t <= a.occReach && nSteps < 131072.0f && hitM <= a.occCap && (dist + hitM) * 1.001f < D);
+    }
+    return ok && holds;
+}
+
 // The first step of a ray that starts at the hit position, from the distance already known there (FT_SH_D0): exactly what the round's switch does with an
 // evaluated distance for a PH_SHADOW / PH_AO lane (SdfForm.fs:94-104).  -> 0 the ray marches on (s.o, s.len, s.steps advanced), 1 it is a hit at once, 2 it
 // ends as a miss (NaN distance, flagged like there).
@@ -1888,6 +1974,18 @@ __device__ __forceinline__ void ft_trace_body(const FtRenderArgs& a) {
         if (s.phase == PH_IDLE && exhausted && chunkNext == chunkEnd) s.phase = PH_DONE;
         if (__ballot(s.phase != PH_DONE) == 0ull) break;
 
+        // ---- occlusion certificate (lean kernel; "Occlusion certificate") ----
+        // every occPeriod-th evaluation round, for the shadow rays in their occPeriod steps from occFrom on: a marching lane takes one step per round, so each
+        // ray meets exactly one try and no lane state records it.  A certified lane leaves as from an evaluation below epsilon (the switch below)
+        if (VARIANT == 1 && a.occPeriod != 0u && waveEvals % a.occPeriod == 0u) {                // EXTENSION builds: shadow rays outside glass bodies; AO rays march
+            const bool cand = s.phase == PH_SHADOW && s.steps - a.occFrom < a.occPeriod && (!EXT || !s.inside());
+            if ((uint32_t)__popcll(__ballot(cand)) >= a.occMin) {
+                const bool hit = ft_occlusion_certificate(a, ldsC + 0, cand, s.o, s.dir, s.eps, s.len, s.steps);
+                if (hit) { ft_count(FT_C_HITS); s.lidx += 1; s.phase = PH_LIGHTS; settle<EXT, FORM>(a, s); }      // shadowed (SdfLight.fs:20)
+                if (__ballot(hit) != 0ull && __ballot(s.phase >= PH_MARCH) == 0ull) continue;                     // every lane resolved: refill now
+            }
+        }
+
         // ---- miss certificates (lean kernel; "Miss certificate") ----
         if (VARIANT == 1 && a.cert != 0u) {                          // EXTENSION builds: not inside a glass body (the march runs on -Distance there)
             // the bundle of the wave's primary rays, then that of its shadow rays (never mixed: one axis serves one family of directions), every
@@ -1919,7 +2017,7 @@ __device__ __forceinline__ void ft_trace_body(const FtRenderArgs& a) {
 
         // ---- one scene-SDF evaluation per active lane -----------------------------------------
         const bool active = s.phase >= PH_MARCH;
-        waveEvals += 1;
+        waveEvals += 1;                                                // one round = one step of every marching lane: the occlusion certificate's "one try per ray" (above) rests on it
         FT_UDBG_T0(tRound);
         auto query_point = [&]() {
             f3 q = s.o;

@@ -1017,6 +1017,45 @@ bool flatten(const Builder& b, int object, const float bg[3], const int* lights,
                 out.certLenF = (float)(1.0 + (N + 2.0) * 4.0 * u);
                 out.certSteps = (uint32_t)(N + 2000.0);
                 if (run.count >= 32u) certClusters(&out.consts[run.data], run.count, out.certCl, out.certK);
+                // Occlusion certificate (kernels.hip ft_occlusion_certificate): a shadow ray's hit carries one bit, so that its march ENDS IN A HIT may be
+                // proved from its line as well.  f is 1-Lipschitz (its gradient is a convex mix of unit vectors) and f <= min_i d_i (si < 0: the sum is at
+                // least its largest term).  Let the ray stand at o with direction dir, |dir|^2 <= 1 + 1e-6, remaining Length len, and let the line have a
+                // parameter t* >= 0 with  t* occLenF < len  and  f(y*) <= -hitM  at y* = o + t* dir.  The kernel shows such a point in two ways: one child with
+                // d_i(y*) <= -hitM, or a witness y with f(y) <= -D (evaluated there, errors as e_eval below) within D - hitM of y*.
+                // T_k: the sum of the steps taken so far (real numbers), p_k the marched float32 point, x_k = o + T_k dir.  Invariant: T_k <= t*.
+                //   * Every evaluation that is no hit returns >= epsilon, so at most t* / epsilon steps are taken while T <= t*; each adds at most
+                //     e(3 Rb) to the drift (start within Rb of c as above, y* inside the support sphere since f(y*) < 0, so the line between them stays within Rb, steps
+                //     are <= t* <= tMax = (Rb + escR) / 0.9 long, the drift itself stays below occCap = escR / 20):  |p_k - x_k| <= delta_h = (t* / epsilon) e.
+                //   * The reference's value at p_k is at most  f(y*) + |p_k - y*| + e_eval <= -hitM + (t* - T_k) |dir| + delta_h + e_eval.  With
+                //     hitM >= delta_h + e_eval + 1e-6 tMax (|dir| - 1 <= 5.1e-7) it is <= t* - T_k: either it is below epsilon — the hit — or
+                //     T_k+1 = T_k + value <= t*.  At T_k = t* the value is <= 0 < epsilon.  So the march cannot pass t* and must end in a hit there or before.
+                //   * Length: the float32 count-down loses <= u len per step, so after k <= Ncap = 2^17 steps it is still > len (1 - Ncap u) - t* > 0
+                //     by occLenF = 1 + (Ncap + 2) 4u; the kernel holds t* / epsilon + 2 below Ncap and the ray's steps below half the step cap: no
+                //     cap flag is lost.  No NaN: every d_i >= -r_i, so an exp argument is at most rMax / s <= 60 and the sum stays finite.
+                //   * Underflow: the reference returns -Log(sum) s, and a float32 sum whose every term has flushed to 0 gives +inf — a miss, whatever f is.  The kernel
+                //     takes only t* <= occReach = 100 ln 2 s - occCap.  By the invariant every marched point has f(p_k) <= (t* - T_k) |dir| + delta_h <= t* + occCap,
+                //     so the true sum there is exp(-f / s) >= 2^-100: its largest term is a normal number >= 2^-100 / n with an exp argument of at most 70 + ln n in
+                //     size (argument rounding inside eSum's 4096 2^-23), and what the terms below 2^-126 lose by being flushed is < n 2^-26 of the sum, which eSum
+                //     carries as it does for the miss certificate's threshold.  Log and the product with s round a value of size <= t* + occCap: 2u tMax, inside
+                //     the 1e-6 tMax of occB next to the 5.1e-7 tMax that |dir| needs.
+                //   e_eval: the reference's float32 evaluation (eGeo's first term, eSum as above) and the kernel's closest approach and distance in
+                //   float32 (eGeo's second term; its comparison carries 0.1 % more): occB = (2 eGeo + eSum + 1e-6 tMax) 1.01 + 1e-6.  The kernel forms
+                //   hitM = occE (t* / epsilon + 2) + occB per lane from its own t*, occE = 1.01 e, and tries only epsilon >= occEpsMin, where hitM <= occCap
+                //   and the step bound hold for every t* <= tMax.
+                double rMax = 0.0;
+                for (uint32_t i = 0; i < run.count; ++i) rMax = std::max(rMax, std::fabs((double)out.consts[run.data + 4u * i + 3u]));
+                const double tMax = (Rb + escR) / 0.9, nCap = 131072.0;
+                const double occE = 1.01 * e3, occB = (2.0 * eGeo + eSum + 1e-6 * tMax) * 1.01 + 1e-6, occCap = 0.05 * escR;
+                const double occReach = 100.0 * 0.6931471805599453 * strength - occCap;
+                if (rMax <= 60.0 * strength && 2.0 * occB + 4.0 * occE < occCap && occReach > 0.0) {
+                    out.occE = (float)(occE * (1.0 + 1e-6));
+                    out.occB = (float)(occB * (1.0 + 1e-6));
+                    out.occCap = (float)(occCap * (1.0 - 1e-6));
+                    out.occEpsMin = (float)(1.01 * std::max(tMax * occE / (occCap - occB - 2.0 * occE), tMax / (nCap - 4.0)));
+                    out.occLenInv = (float)((1.0 - 1e-6) / (1.0 + (nCap + 2.0) * 4.0 * u));
+                    out.occReach = (float)(occReach * (1.0 - 1e-6));
+                    out.occNear = (float)(strength * std::log((double)run.count) * 1.001 + occB);   // f(x) <= 0 needs one d_i(x) <= s ln n: the try's cheap exit, nothing rests on it
+                }
             }
         }
     }

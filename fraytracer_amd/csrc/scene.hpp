@@ -106,7 +106,10 @@ struct FlatScene {                                            // host copy of ev
     float escRho2 = 0.0f;                                     // see FtSceneDev::escRho2
     float certM = -1.0f, certClip = 0.0f, certRho2 = 0.0f, certLenF = 1.0f;   // see FtSceneDev::certM ... (-1: no miss certificate)
     uint32_t certSteps = 0;
-    std::vector<float> certCl;                                // see FtSceneDev::certCl (scene.cpp certClusters); empty: the certificate's flat loop
+    // occlusion certificate (scene.cpp "Occlusion certificate"; FtRenderArgs::occE ...): drift per step, the margin's constant part, the smallest epsilon
+    // tried, the largest margin conceded, 1 / the count-down's padding factor, how far from a sphere f can still be <= 0, the largest t* (the float32 sum cannot underflow before it).  occB < 0: none
+    float occE = 0.0f, occB = -1.0f, occEpsMin = 0.0f, occCap = 0.0f, occLenInv = 0.0f, occNear = 0.0f, occReach = 0.0f;
+    std::vector<float> certCl;                               // see FtSceneDev::certCl (scene.cpp certClusters); empty: the certificate's flat loop
     uint32_t certK = 0;
     uint32_t cullPc = 0xffffffffu;                            // see FtSceneDev::cullPc
     uint32_t fastPath = 0;

@@ -63,7 +63,7 @@ module Native =
     [<DllImport(Lib)>] extern int ft_abi_version()
     [<DllImport(Lib)>] extern nativeint ft_build_info()
     [<DllImport(Lib)>] extern int ft_ctx_create(int device, nativeint& ctx)
-    // per-context switches (ft_option: 1 refill_min, 2 max_blocks_per_cu, 3 host_chunks, 4 host_pin, 5 tail_k, 6 math, 7 guided, 8 chunk, 16 order); the library reads no environment
+    // per-context switches (ft_option: 1 refill_min, 2 max_blocks_per_cu, 3 host_chunks, 4 host_pin, 5 tail_k, 6 math, 7 guided, 8 chunk, 16 order, 17 occl, 18 occl_policy); the library reads no environment
     [<DllImport(Lib)>] extern int ft_ctx_set_option(nativeint ctx, int option, int value)
     [<DllImport(Lib)>] extern void ft_ctx_destroy(nativeint ctx)
     [<DllImport(Lib)>] extern nativeint ft_last_error()
@@ -143,8 +143,10 @@ module Native =
     /// specialised one for a union of primitives with at most two intersect / subtract steps behind it — Program.fs's own scene — or the interpreter;
     /// FT_OPT_REUSE (13, on) takes a ray's first evaluation from a value already known — a shadow ray's from the normal's centre probe, a primary ray's
     /// from one evaluation at the camera position per wave — where the reference computes it again for every ray.)
+    /// FT_OPT_OCCL (17), on by default: a shadow ray whose line is proved to pass deep enough through one sphere of a smooth union ends as the hit its
+    /// march is bound to end in; exact as well, and only while FT_OPT_ESCAPE is on (FT_OPT_OCCL_POLICY (18): its schedule, for experiments).
     let setExactShortcuts (on : bool) =
-        for opt in [ 9; 10; 11 ] do
+        for opt in [ 9; 10; 11; 17 ] do
             if ft_ctx_set_option (ctx.Value, opt, (if on then 1 else 0)) < 0 then failwith (Marshal.PtrToStringAnsi (ft_last_error ()))
 
     /// FT_OPT_ORDER (16), on by default: a frame records what each 8x8 tile cost, and the scene's next frame of the same size hands out the tiles that cost

@@ -147,6 +147,11 @@ typedef enum ft_option {
                                    * tiles keep their index order.  Only when a tile starts changes: same frame, counters and flags.  The camera, epsilon, Length and the
                                    * lights may differ between the two frames (a stale order is only another order); a first frame runs in index order.  2: record only;
                                    * 0: off.  Not combined with FT_OPT_GUIDED = 1, which stays in index order */
+    FT_OPT_OCCL = 17,             /* 1 (default): the smooth-union-of-spheres kernel ends a shadow ray as the hit its march is bound to end in once its line is proved to pass
+                                   * deep enough through one of the spheres (exact: same frame, counters and flags, fewer sdf_evals); only while FT_OPT_ESCAPE and FT_OPT_CERT are on; rays of
+                                   * |direction| > 1 (a point light's) and EXTENSION ambient-occlusion rays keep marching; 0: off */
+    FT_OPT_OCCL_POLICY = 18,      /* 0 (default schedule) or, for experiments, when that proof is tried: bits 0-7 every how many evaluation rounds of a wave (0: the shipped 2,
+                                   * 1: every round, 255: off), 8-15 the steps a shadow ray takes first, 16-23 the shadow rays a try waits for (0: the shipped 1; .. 64) */
     FT_OPT_GUIDED = 7             /* 1: the last jobs of a launch are handed out in half and quarter tiles (lean kernel); 0 (default): whole tiles only */
 } ft_option;
 /* MathF.Exp / MathF.Log (SdfForm.unionSmooth, SdfForm.fs:80,82) and MathF.Pow (FColor.gammaInverse, FColor.fs:50-55) are the C runtime's
@@ -408,6 +413,11 @@ int ft_scene_support_sphere(const ft_scene*, float centre_radius[4]);
 /* the constants of the smooth-union kernel's miss certificate (FT_OPT_CERT; margin < 0: the scene has none):
  * margin certM, clip padding certClip, squared start radius certRho2, Length factor certLenF, steps left certSteps */
 int ft_scene_miss_certificate(const ft_scene*, float out[5]);
+/* the constants of the smooth-union kernel's occlusion certificate (FT_OPT_OCCL; out[1] < 0: the scene has none): drift per step occE, the margin's
+ * constant part occB, the smallest epsilon tried occEpsMin, the largest margin occCap, 1 / the Length padding occLenInv, the distance occNear
+ * from a sphere beyond which the form is positive, the largest parameter occReach (up to it the float32 sum of the form cannot underflow).  A shadow ray ends as a hit where its line has a point at which the form is proved to be at most
+ * -(occE (t / epsilon + 2) + occB), at a parameter t <= min(Length * occLenInv, occReach) */
+int ft_scene_occlusion_certificate(const ft_scene*, float out[7]);
 /* the clusters of the certificate's bound (n_clusters = 0: the scene has none, and the certificate sums every child): n_clusters records of 8 floats
  * {centre xyz, radius, member count, first member} (the last two are int32 bits), then the n_children children (x, y, z, r) in cluster order.
  * out = NULL: only the counts; otherwise capacity >= 8 n_clusters + 4 n_children floats */

@@ -1,0 +1,477 @@
+"""The lean kernel's occlusion certificate (FT_OPT_OCCL; kernels.hip ft_occlusion_certificate, scene.cpp "Occlusion certificate").
+
+A shadow ray of a scene that is one smooth union of spheres ends as a hit once its line o + t dir is proved to pass
+a point with f <= -hitM, hitM = occE (t / epsilon + 2) + occB, at a parameter t <= Length * occLenInv.  The CPU tests pin the constants to their
+formula and hold a float64 restatement of that condition against the oracle's own float32 marches; the GPU tests compare colours, ray / hit counters and flags with the oracle, which has no
+certificate at all, with the option off, on, and tried on every round."""
+import math
+
+import numpy as np
+import pytest
+
+import fraytracer_amd as ft
+from fraytracer_amd import synthetic as syn
+from helpers import assert_bit_equal
+
+EPS, LEN = 0.01, 30.0
+EVERY_ROUND = 1                      # FT_OPT_OCCL_POLICY: period 1
+OPTS = {"off": {"occl": 0, "occl_policy": 0}, "on": {"occl": 1, "occl_policy": 0}, "every_round": {"occl": 1, "occl_policy": EVERY_ROUND}}
+N_CAP = 131072.0
+
+
+def constants(escR, cinf, strength, n):
+    """scene.cpp "Occlusion certificate", restated"""
+    u = 2.0 ** -24
+    Rb = 2.5 * escR * 1.001
+    e3 = 3.0 * 2.0 ** -23 * (cinf + 3.0 * Rb)
+    eGeo = 8.0 * u * 5.0 * escR + 16.0 * u * (cinf + 10.0 * escR)
+    eSum = strength * ((2.0 * n + 4096.0) * 2.0 ** -23 + 2e-4)
+    tMax = (Rb + escR) / 0.9
+    step = 1.01 * e3
+    base = (2.0 * eGeo + eSum + 1e-6 * tMax) * 1.01 + 1e-6
+    cap = 0.05 * escR
+    return {"step": step, "base": base, "cap": cap, "eps_min": 1.01 * max(tMax * step / (cap - base - 2.0 * step), tMax / (N_CAP - 4.0)),
+            "len_inv": 1.0 / (1.0 + (N_CAP + 2.0) * 4.0 * u), "near": strength * math.log(n) * 1.001 + base, "reach": 100.0 * math.log(2.0) * strength - cap}
+
+
+def spheres(n=256):
+    src = syn.Rng(3)
+    C, R = [], []
+    for _ in range(n):
+        C.append(src.pointInBall(4.0)); R.append(src.range(0.1, 0.5))
+    return np.array(C, np.float64), np.array(R, np.float64)
+
+
+class Model:
+    """the condition in float64 from the library's own constants"""
+
+    def __init__(self, host, strength, n=256, scene=None, C=None, R=None):
+        self.scene = scene if scene is not None else syn.config3(n=n, size=64, strength=strength)[0]
+        ds = host.scene(self.scene)
+        try:
+            self.sup = ds.support_sphere()
+            self.k = ds.occlusion_certificate()
+            self.rho2 = ds.miss_certificate()["rho2"]
+        finally:
+            ds.close()
+        self.C, self.R = (np.array(C, np.float64), np.array(R, np.float64)) if C is not None else spheres(n)
+        self.strength = strength
+
+    def form(self, P):
+        """f in float64 at points [..., 3]"""
+        d = np.linalg.norm(P[..., None, :] - self.C, axis=-1) - self.R
+        mn = d.min(-1)
+        return mn - self.strength * np.log(np.exp(-(d - mn[..., None]) / self.strength).sum(-1))
+
+    def holds(self, rays, near=24):
+        """rays [m, 8] float32 -> bool [m]: the line has a point y* = o + t dir, 0 <= t <= Length * len_inv, with f(y*) <= -hitM(t) (0.1 % apart).  The
+        points asked are the line's closest approaches to its `near` nearest children: every point the kernel can name lies within the slack of one
+        (it asks the closest approach to one child's centre, or to a witness on a neighbouring line whose ball it proves to reach)"""
+        r = np.asarray(rays, np.float32).astype(np.float64)
+        o, d, L, eps = r[:, 0:3], r[:, 3:6], r[:, 6], r[:, 7]
+        k = self.k
+        dd = (d * d).sum(1)
+        w = o - np.array(self.sup[:3])
+        with np.errstate(all="ignore"):
+            gate = (k["base"] >= 0) & (eps >= k["eps_min"]) & (eps <= self.sup[3]) & (L > 0) & (L < 1e9) & (dd >= 0.81) & (dd <= 1.000001) & ((w * w).sum(1) <= self.rho2)
+            rel = self.C[None] - o[:, None]
+            t = np.clip((rel * d[:, None]).sum(-1) / dd[:, None], 0.0, (L * k["len_inv"])[:, None])
+            dist = np.linalg.norm(rel - t[..., None] * d[:, None], axis=-1) - self.R[None]
+            if near < len(self.R):
+                t = np.take_along_axis(t, np.argpartition(dist, near, axis=1)[:, :near], 1)
+            f = self.form(o[:, None] + t[..., None] * d[:, None])
+            nst = t / eps[:, None] + 2.0
+            hitM = k["step"] * nst + k["base"]
+            ok = (t <= k["reach"]) & (nst < N_CAP) & (hitM <= k["cap"]) & (hitM * 1.001 < -f)
+        self.t_of = np.where(ok, t, np.inf).min(1)                      # the smallest witness parameter (inf: none)
+        return gate & ok.any(1)
+
+
+@pytest.fixture(scope="module")
+def host():
+    d = ft.Device(-1)
+    yield d
+    d.close()
+
+
+START = {0.05: 4.7, 0.25: 6.0, 1.0: 10.0}      # outside the surface; at strength 0.05 every term of the union underflows farther out and nothing is ever hit
+
+
+def shadow_lines(oracle, scene, n, eps, seed, start=6.0):
+    """two shadow lines from every hit record of n random rays into the cloud: towards the scene's light, and a random direction about the normal"""
+    g = np.random.default_rng(seed)
+    o = g.normal(size=(n, 3)); o *= start / np.linalg.norm(o, axis=1, keepdims=True)
+    aim = g.normal(size=(n, 3)); aim *= (3.5 * g.uniform(0.0, 1.0, (n, 1)) ** (1.0 / 3.0)) / np.linalg.norm(aim, axis=1, keepdims=True)
+    d = aim - o; d /= np.linalg.norm(d, axis=1, keepdims=True)
+    rays = np.concatenate([o, d, np.full((n, 1), LEN), np.full((n, 1), EPS)], axis=1).astype(np.float32)
+    with np.errstate(all="ignore"):
+        rec, _ = oracle.Oracle().scene(scene).object_try_trace(rays)
+    rec = rec[rec[:, 14].view(np.int32) != 0]
+    light = -np.array([-0.5, -1.0, 1.0]); light /= np.linalg.norm(light)
+    rnd = g.normal(size=(len(rec), 3)); rnd /= np.linalg.norm(rnd, axis=1, keepdims=True)
+    rnd = rec[:, 8:11] + 0.9 * rnd; rnd /= np.linalg.norm(rnd, axis=1, keepdims=True)
+    out = []
+    for d in (np.repeat(light[None], len(rec), 0), rnd):
+        d32 = d.astype(np.float32)
+        out.append(np.concatenate([rec[:, 0:3], d32, np.full((len(rec), 1), 1000.0, np.float32), np.full((len(rec), 1), eps, np.float32)], axis=1))
+    return np.concatenate(out).astype(np.float32)
+
+
+def march_hits(oracle, scene, rays):
+    """does the oracle's float32 march of each ray end in a hit (SdfForm.tryTrace)"""
+    with np.errstate(all="ignore"):
+        out, _ = oracle.Oracle().scene(scene).form_try_trace(rays)
+    return out[:, 9].view(np.int32) != 0
+
+
+@pytest.mark.parametrize("strength", [0.05, 0.25, 1.0])
+def test_condition_against_the_oracles_marches(host, oracle, strength):
+    """no line on which the condition holds may march to a miss, and the condition holds on at least a quarter of the occluded lines"""
+    m = Model(host, strength)
+    rays = shadow_lines(oracle, m.scene, 2500, EPS, 5, START[strength])
+    assert len(rays) >= 2000
+    cond = m.holds(rays)
+    hit = march_hits(oracle, m.scene, rays)
+    print(f"strength {strength}: lines {len(rays)} occluded {int(hit.sum())} condition holds {int(cond.sum())} of them occluded {int((cond & hit).sum())}")
+    assert not (cond & ~hit).any(), rays[cond & ~hit][:4]
+    assert (cond & hit).sum() >= 0.25 * hit.sum(), (int(cond.sum()), int(hit.sum()))
+
+
+def two_clusters(strength=0.05, light=(-1.0, 0.0, 0.0)):
+    """two spheres of radius 0.5 at x = -6 and x = +6 under a weak union: half way between them every term of the reference's float32 sum has flushed to 0,
+    so the form is +inf there and a ray that crosses the gap marches off as a miss, though its line runs through the far sphere"""
+    C, R = [(-6.0, 0.0, 0.0), (6.0, 0.0, 0.0)], [0.5, 0.5]
+    forms = [ft.SdfForm.Primitive.sphere(Center=c, Radius=r) for c, r in zip(C, R)]
+    obj = ft.SdfObject.create(ft.SdfMaterial.createSolid((0.9, 0.6, 0.3)), ft.SdfForm.unionSmooth(strength, forms))
+    return ft.SdfScene(obj, syn.BACKGROUND, [ft.SdfLight.directional(light, (0.5, 0.5, 0.5))]), C, R
+
+
+def test_reach_where_the_float32_sum_underflows(host, oracle):
+    """shadow lines across the gap: the oracle's marches miss, and the condition must not hold beyond occReach = 100 ln 2 s - occCap; lines that start
+    within reach of the far sphere still pass"""
+    scene, C, R = two_clusters()
+    m = Model(host, 0.05, scene=scene, C=C, R=R)
+    assert 0.0 < m.k["reach"] < 100.0 * math.log(2.0) * 0.05
+    g = np.random.default_rng(3)
+    n = 256
+    off = g.uniform(-0.3, 0.3, (n, 2)); off[0] = 0.0
+    far = np.concatenate([np.full((n, 1), -5.489), off, np.tile([1.0, 0.0, 0.0], (n, 1)), np.full((n, 1), 1000.0), np.full((n, 1), EPS)], axis=1).astype(np.float32)
+    hit = march_hits(oracle, scene, far)
+    # the reference's own arithmetic: the ray on the axis doubles its step up to x = 0.13, evaluates +inf there and the light arrives; off the axis
+    # some rays step over the dead zone and do hit the far sphere
+    assert not hit[0] and 0 < hit.sum() < n
+    assert not m.holds(far).any()
+    near = far.copy(); near[:, 0] = g.uniform(3.0, 5.0, n).astype(np.float32)
+    c = m.holds(near)
+    assert c.any() and not (c & ~march_hits(oracle, scene, near)).any()
+    # sparse clouds at small strengths, gaps of many times 100 ln 2 s: the implication over whole scenes
+    for strength, spread in ((0.05, 12.0), (0.1, 25.0)):
+        src = syn.Rng(11)
+        Cs = [tuple(float(v) for v in src.pointInBall(spread)) for _ in range(48)]
+        Rs = [float(src.range(0.1, 0.5)) for _ in range(48)]
+        forms = [ft.SdfForm.Primitive.sphere(Center=cc, Radius=rr) for cc, rr in zip(Cs, Rs)]
+        sc = ft.SdfScene(ft.SdfObject.create(ft.SdfMaterial.createSolid((0.9, 0.6, 0.3)), ft.SdfForm.unionSmooth(strength, forms)), syn.BACKGROUND, [])
+        ms = Model(host, strength, scene=sc, C=Cs, R=Rs)
+        assert ms.k["base"] > 0.0
+        i = g.integers(0, 48, 1500)
+        o = np.array(Cs)[i] + g.normal(size=(1500, 3)) * (np.array(Rs)[i][:, None] + 0.02) / np.sqrt(3.0) * 1.8
+        d = g.normal(size=(1500, 3)); d /= np.linalg.norm(d, axis=1, keepdims=True)
+        rays = np.concatenate([o, d, np.full((1500, 1), 1000.0), np.full((1500, 1), EPS)], axis=1).astype(np.float32)
+        c = ms.holds(rays, near=16)
+        h = march_hits(oracle, sc, rays)
+        print(f"sparse cloud s={strength}: condition holds {int(c.sum())}, occluded {int(h.sum())} of {len(rays)}")
+        assert c.any() and not (c & ~h).any()
+
+
+def test_where_the_proof_is_thinnest(host, oracle):
+    g = np.random.default_rng(7)
+    # (a) lines that pass a single sphere at a depth of hitM -2 .. +2 margins (two spheres 1.9 apart: a union of one is folded into a plain sphere)
+    m = Model(host, 0.25, n=2)
+    k = m.k
+    n = 600
+    i = g.integers(0, 2, n)
+    u = g.normal(size=(n, 3)); u /= np.linalg.norm(u, axis=1, keepdims=True)
+    v = np.cross(u, g.normal(size=(n, 3))); v /= np.linalg.norm(v, axis=1, keepdims=True)
+    back = g.choice([0.3, 1.0, 3.0], (n, 1))
+    hitM = k["step"] * (back / EPS + 2.0) + k["base"]
+    closest = m.C[i] + u * (m.R[i][:, None] - hitM * (1.0 + g.integers(-2, 3, (n, 1)) * 0.5) - g.integers(-2, 3, (n, 1)) * k["base"])
+    graze = np.concatenate([closest - v * back, v, np.full((n, 1), 1000.0), np.full((n, 1), EPS)], axis=1).astype(np.float32)
+    cond = m.holds(graze); hit = march_hits(oracle, m.scene, graze)
+    assert cond.any() and (~cond).any()
+    assert not (cond & ~hit).any()
+    # (b) epsilon at the gate's floor and just below it
+    m = Model(host, 0.25)
+    k = m.k
+    base = shadow_lines(oracle, m.scene, 400, EPS, 9)[:240]
+    floor = np.float32(k["eps_min"])
+    at = base.copy(); at[:, 7] = np.nextafter(floor, np.float32(1.0))
+    below = base.copy(); below[:, 7] = floor * np.float32(0.999)
+    c_at = m.holds(at)
+    assert c_at.any() and not m.holds(below).any()
+    assert not (c_at & ~march_hits(oracle, m.scene, at)).any()
+    # (c) |dir|^2 at 0.81, 1 and 1 + 1e-5
+    for scale, may in ((0.9001, True), (1.0, True), (math.sqrt(1.0 + 1e-5), False)):
+        r = base.copy(); r[:, 3:6] *= np.float32(scale)
+        c = m.holds(r)
+        assert c.any() == may, scale
+        assert not (c & ~march_hits(oracle, m.scene, r)).any(), scale
+    short = base.copy(); short[:, 3:6] *= np.float32(0.8999)
+    assert not m.holds(short).any()
+    # (d) Length ending just after and just before the witness
+    c = m.holds(base); t = m.t_of.copy()
+    assert c.any()
+    for f, may in ((1.0 + 1e-4, True), (1.0 - 1e-4, False)):
+        r = base[c].copy(); r[:, 6] = (t[c] / k["len_inv"] * f).astype(np.float32) + np.float32(1e-6 if may else 0.0)
+        cc = m.holds(r)
+        if not may:
+            assert (m.t_of[cc] < t[c][cc] * (1.0 - 5e-5)).all()        # where it still holds, it is by an earlier witness
+        else:
+            assert cc.any()
+        assert not (cc & ~march_hits(oracle, m.scene, r)).any(), f
+
+
+@pytest.mark.parametrize("strength", [0.05, 0.25, 1.0])
+def test_constants_are_the_stated_formula(host, strength):
+    m = Model(host, strength)
+    cinf = max(abs(v) for v in m.sup[:3])
+    want = constants(m.sup[3], cinf, strength, 256)
+    for name, v in want.items():
+        assert m.k[name] == pytest.approx(v, rel=2e-5), (name, m.k[name], v)
+    assert 0.0 < m.k["base"] < 2e-3 and m.k["eps_min"] < EPS and m.k["cap"] < 0.06 * m.sup[3]
+    # the margin of a shadow ray two units long at epsilon 0.01: far below the smallest radius
+    assert m.k["step"] * (2.0 / EPS + 2.0) + m.k["base"] < 0.01
+
+
+def test_no_constants_without_the_shape(host):
+    """only one smooth union of staged spheres whose exp arguments stay small gets constants"""
+    for scene in (syn.config2()[0], syn.mixed_nested()[0], syn.console_like(n=50)[0], syn.config3(n=64, size=16, strength=0.005)[0]):
+        ds = host.scene(scene)
+        try:
+            assert ds.occlusion_certificate()["base"] < 0.0
+        finally:
+            ds.close()
+
+
+def test_option_and_its_mirrors(host):
+    import os
+    import re
+    from fraytracer_amd import _lib
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    header = open(os.path.join(root, "include", "fraytracer_hip.h")).read()
+    assert re.search(r"\bFT_OPT_OCCL\s*=\s*17\b", header) and re.search(r"\bFT_OPT_OCCL_POLICY\s*=\s*18\b", header)
+    assert _lib.FT_OPT_OCCL == 17 and _lib.FT_OPT_OCCL_POLICY == 18
+    assert "FT_OPT_OCCL" in open(os.path.join(root, "host", "cpp", "FrayTracer.hpp")).read()
+    fs = open(os.path.join(root, "host", "fsharp", "FrayTracer.Hip.fs")).read()
+    assert re.search(r"for opt in \[ 9; 10; 11; 17 \] do", fs)
+    assert host.get_option("occl") == 1 and host.get_option("occl_policy") == 0
+    for v in (1, 2 | 3 << 8 | 16 << 16, 255, 0):
+        host.set_option("occl_policy", v)
+        assert host.get_option("occl_policy") == v
+    for name, v in (("occl", 2), ("occl_policy", -1), ("occl_policy", 65 << 16)):
+        with pytest.raises(ft.FrayTracerError):
+            host.set_option(name, v)
+
+
+# ------------------------------------------------------------------------------------------------ GPU
+def _set(gpu, o):
+    for k, v in o.items():
+        gpu.set_option(k, v)
+
+
+RESET = {"occl": 1, "occl_policy": 0, "tail_k": -1, "math": 0, "cert": 1, "cert_policy": 0}
+COUNTERS = ("rays_primary", "rays_shadow", "hits_primary", "hits_shadow", "flags")
+
+
+def _render(gpu, oracle, scene, size, opts=OPTS, eps=EPS, length=LEN, extra=None, **ext):
+    cam = syn.default_camera()
+    ds = gpu.scene(scene)
+    want, ocnt = oracle.Oracle().scene(scene).render(eps, length, size, size, cam.as_array(), nthreads=16, **ext)
+    out = {}
+    try:
+        for name, o in opts.items():
+            _set(gpu, dict(o, **(extra or {})))
+            got, st = ds.render(eps, length, ft.ImageSize(size, size), cam, **ext)
+            assert_bit_equal(got, want, name)
+            for k in COUNTERS:
+                assert st[k] == ocnt[k], (name, k, st[k], ocnt[k])
+            out[name] = st
+    finally:
+        _set(gpu, RESET)
+        ds.close()
+    return out
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("strength", [0.05, 0.25, 0.5, 1.0])
+def test_c3_small_frames(gpu, oracle, strength):
+    scene, _ = syn.config3(n=256, size=96, strength=strength)
+    st = _render(gpu, oracle, scene, 96)
+    print({k: v["sdf_evals"] for k, v in st.items()})
+    if st["off"]["hits_shadow"] == 0:                                   # strength 0.05: every term underflows at the camera and nothing is hit
+        assert st["on"]["sdf_evals"] == st["every_round"]["sdf_evals"] == st["off"]["sdf_evals"]
+    else:
+        assert st["on"]["sdf_evals"] < st["off"]["sdf_evals"]
+        assert st["every_round"]["sdf_evals"] < st["off"]["sdf_evals"]
+
+
+@pytest.mark.gpu
+def test_rays_across_a_gap_where_the_sum_underflows(gpu, oracle):
+    """primary rays that hit the sphere at x = -6 from the gap's side; their shadow rays run along +x through the sphere at x = +6, twelve units
+    away at strength 0.05: the reference's sum underflows half way and the light arrives.  Both light signs, so that one of them casts those rays"""
+    g = np.random.default_rng(5)
+    n = 192
+    off = g.uniform(-0.2, 0.2, (n, 2))
+    rays = np.concatenate([np.full((n, 1), -5.0), off, np.tile([-1.0, 0.0, 0.0], (n, 1)), np.full((n, 1), LEN), np.full((n, 1), EPS)], axis=1).astype(np.float32)
+    cast = 0
+    for light in ((-1.0, 0.0, 0.0), (1.0, 0.0, 0.0)):
+        scene, _, _ = two_clusters(light=light)
+        want, ocnt = oracle.Oracle().scene(scene).trace_rays(rays)
+        ds = gpu.scene(scene)
+        try:
+            for name, o in OPTS.items():
+                _set(gpu, o)
+                got, st = ds.trace_rays(rays)
+                assert_bit_equal(got, want, f"{name} light {light}")
+                for k in COUNTERS[1:]:
+                    assert st[k] == ocnt[k], (name, light, k, st[k], ocnt[k])
+        finally:
+            _set(gpu, RESET)
+            ds.close()
+        assert ocnt["hits_primary"] == n
+        cast += ocnt["rays_shadow"]; missed = locals().get("missed", 0) + ocnt["rays_shadow"] - ocnt["hits_shadow"]
+    assert cast == n and 0 < missed                                    # one light casts every ray's shadow ray across the gap; those that evaluate +inf miss
+
+
+@pytest.mark.gpu
+def test_glibc_arithmetic(gpu, oracle):
+    scene, _ = syn.config3(n=256, size=96)
+    oracle.lib.orc_set_libm(1)
+    try:
+        st = _render(gpu, oracle, scene, 96, extra={"math": ft.glibc_build_of_this_host()})
+    finally:
+        oracle.lib.orc_set_libm(0)
+    assert st["on"]["sdf_evals"] < st["off"]["sdf_evals"]
+
+
+@pytest.mark.gpu
+def test_latency_mode_forced(gpu, oracle):
+    scene, _ = syn.config3(n=256, size=96)
+    _render(gpu, oracle, scene, 96, extra={"tail_k": 64})
+
+
+@pytest.mark.gpu
+def test_cert_off_switches_every_certificate(gpu, oracle):
+    """FT_OPT_CERT = 0: a launch evaluates exactly what its rays' marches ask for, whatever FT_OPT_OCCL says"""
+    scene, _ = syn.config3(n=256, size=96)
+    st = _render(gpu, oracle, scene, 96, extra={"cert": 0})
+    assert st["on"]["sdf_evals"] == st["every_round"]["sdf_evals"] == st["off"]["sdf_evals"]
+
+
+@pytest.mark.gpu
+def test_point_light_rays_keep_marching(gpu, oracle):
+    """|dir| = 1 / distance of a point light's shadow ray is outside the gate wherever the light is nearer than 1 or farther than 1.11: with the
+    light ten units away no ray is tried and the evaluations are the same"""
+    scene, _ = syn.config3(n=256, size=96)
+    scene = ft.SdfScene(scene.Object, syn.BACKGROUND, [ft.SdfLight.point((3.0, 9.0, -4.0), (40.0, 30.0, 20.0))])
+    st = _render(gpu, oracle, scene, 96)
+    assert st["on"]["sdf_evals"] == st["off"]["sdf_evals"] == st["every_round"]["sdf_evals"]
+    assert st["off"]["hits_shadow"] > 0
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("eps", [-0.01, 0.0, 1e-5, "below", "above", 0.05, 0.3])
+def test_epsilon_range(gpu, oracle, eps):
+    """negative, 0, tiny, 2 % either side of the scene's floor, large: below the floor nothing is tried"""
+    scene, _ = syn.config3(n=64, size=48)
+    size = 8 if eps in (-0.01, 0.0) else 48          # epsilon <= 0: the oracle marches every ray that meets the surface to its step cap
+    ds = gpu.scene(scene)
+    floor = ds.occlusion_certificate()["eps_min"]
+    ds.close()
+    assert 1e-4 < floor < 0.005
+    e = floor * 0.98 if eps == "below" else floor * 1.02 if eps == "above" else eps
+    st = _render(gpu, oracle, scene, size, eps=e)
+    if e < floor:
+        assert st["on"]["sdf_evals"] == st["every_round"]["sdf_evals"] == st["off"]["sdf_evals"]
+    elif eps in ("above", 0.05):
+        assert st["off"]["hits_shadow"] > 0 and st["every_round"]["sdf_evals"] < st["off"]["sdf_evals"]
+
+
+@pytest.mark.gpu
+def test_self_shadowed_cloud(gpu, oracle):
+    """a light from behind the cloud as the camera sees it: most lit-side tests fail the cosine, the rest start deep in shadow"""
+    scene, _ = syn.config3(n=256, size=96)
+    scene = ft.SdfScene(scene.Object, syn.BACKGROUND, [ft.SdfLight.directional((0.3, -0.2, -1.0), (0.5, 0.5, 0.5)),
+                                                        ft.SdfLight.directional((1.0, -0.1, 0.4), (0.2, 0.3, 0.4))])
+    st = _render(gpu, oracle, scene, 96)
+    assert st["off"]["hits_shadow"] > 0.3 * st["off"]["rays_shadow"]
+    assert st["on"]["sdf_evals"] < st["off"]["sdf_evals"]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("ext", [dict(spp=4), dict(ao_samples=4, ao_radius=0.5)], ids=["spp4", "ao4"])
+def test_extension_builds(gpu, oracle, ext):
+    """the lean kernel's EXTENSION build tries its shadow rays too (a render and its ft_render_hits twin count the same evaluations); AO rays march"""
+    scene, _ = syn.config3(n=128, size=48)
+    st = _render(gpu, oracle, scene, 48, **ext)
+    assert st["every_round"]["sdf_evals"] < st["off"]["sdf_evals"]
+
+
+@pytest.mark.gpu
+def test_views_launch(gpu, oracle):
+    scene, _ = syn.config3(n=256, size=64)
+    cams = [syn.default_camera(), ft.Camera.lookAt(Position=(7.0, 3.0, -7.0), LookAt=(0.0, 0.0, 0.0), Up=(0.0, 1.0, 0.0), Lens=ft.Lens.create(60.0))]
+    want = [oracle.Oracle().scene(scene).render(EPS, LEN, 64, 64, c.as_array(), nthreads=16) for c in cams]
+    ds = gpu.scene(scene)
+    evals = {}
+    try:
+        for name, o in OPTS.items():
+            _set(gpu, o)
+            got, st = ds.render_views(EPS, LEN, ft.ImageSize(64, 64), cams)
+            for v in range(2):
+                assert_bit_equal(got[v], want[v][0], f"{name} view {v}")
+            for k in COUNTERS:
+                assert st[k] == want[0][1][k] + want[1][1][k], (name, k)
+            evals[name] = st["sdf_evals"]
+    finally:
+        _set(gpu, RESET)
+        ds.close()
+    assert evals["on"] < evals["off"] and evals["every_round"] < evals["off"]
+
+
+def _pixel_rays(oracle, size):
+    cam = syn.default_camera().as_array()
+    return np.array([oracle.pixel_ray(cam, size, size, x, y, EPS, LEN) for x in range(size) for y in range(size)], np.float32).reshape(-1, 8)
+
+
+@pytest.mark.gpu
+def test_ray_buffer_shade_and_visibility_forms(gpu, oracle):
+    """trace_rays, shade_hits and light_visibility over the pixel rays of C3 at 96^2: colours and counters are the oracle's under every setting, the
+    masks are the same words, and their set bits are the oracle's shadow rays that missed"""
+    scene, _ = syn.config3(n=256, size=96)
+    rays = _pixel_rays(oracle, 96)
+    os_ = oracle.Oracle().scene(scene)
+    want, ocnt = os_.trace_rays(rays)
+    rec, _ = os_.object_try_trace(rays)
+    ds = gpu.scene(scene)
+    evals, masks = {}, {}
+    try:
+        for name, o in OPTS.items():
+            _set(gpu, o)
+            got, st = ds.trace_rays(rays)
+            assert_bit_equal(got, want, name + " trace_rays")
+            for k in COUNTERS[1:]:
+                assert st[k] == ocnt[k], (name, k, st[k], ocnt[k])
+            rgb, sh = ds.shade_hits(rec)
+            assert_bit_equal(rgb, want, name + " shade_hits")
+            vis, vs = ds.light_visibility(rec)
+            for s in (sh, vs):
+                assert (s["rays_shadow"], s["hits_shadow"], s["flags"]) == (ocnt["rays_shadow"], ocnt["hits_shadow"], ocnt["flags"]), (name, s)
+            assert int(vis.sum()) == ocnt["rays_shadow"] - ocnt["hits_shadow"] and int(vis.max()) == 1
+            masks[name] = vis
+            evals[name] = (st["sdf_evals"], sh["sdf_evals"], vs["sdf_evals"])
+    finally:
+        _set(gpu, RESET)
+        ds.close()
+    assert np.array_equal(masks["on"], masks["off"]) and np.array_equal(masks["every_round"], masks["off"])
+    for i in range(3):
+        assert evals["on"][i] < evals["off"][i] and evals["every_round"][i] < evals["off"][i], evals

@@ -2,7 +2,8 @@
 """Miss-certificate schedules on the C3 frame (FT_OPT_CERT_POLICY, include/fraytracer_hip.h): HIP-event kernel ms through Scene.render_device for a
 list of policy words, the words alternated over several rounds; per word the median, the spread, sdf_evals and evaluation rounds per frame.
 Usage: cert_policy_probe.py [--size 4096] [--spheres 256] [--strength 0.25] [--fov 60] [--distance 10] [--rounds 3] [--frames 4] word[=label] ...
-(a word as a Python integer literal, e.g. 0x4001ffff).  Every line carries tile_over_margin: the side of an 8x8 pixel tile at the far side of the support
+(a word as a Python integer literal, e.g. 0x4001ffff; word/occl sets FT_OPT_OCCL_POLICY = occl beside it, occl = off switches FT_OPT_OCCL off: 0/1 is
+the shipped miss-certificate schedule with the occlusion certificate tried every round).  Every line carries tile_over_margin: the side of an 8x8 pixel tile at the far side of the support
 sphere over the certificate's margin — at most 1 is where word 0 leaves the per-lane tries out (capi.cpp launchTrace)."""
 import argparse, json, os, statistics, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -28,7 +29,14 @@ def s32(v):
     return v - (1 << 32) if v >= (1 << 31) else v
 
 
-words = [(s32(int(w.split("=")[0], 0)), w.split("=")[1] if "=" in w else w) for w in args.words]
+def parse(w):
+    """word[/occl][=label] -> ((FT_OPT_CERT_POLICY, FT_OPT_OCCL, FT_OPT_OCCL_POLICY), label)"""
+    spec = w.split("=")[0]
+    cert, _, occl = spec.partition("/")
+    return (s32(int(cert, 0)), 0 if occl == "off" else 1, int(occl, 0) if occl not in ("", "off") else 0), w.split("=")[1] if "=" in w else w
+
+
+words = [parse(w) for w in args.words]
 dev = ft.Device(0)
 import numpy as np
 ds = dev.scene(syn.config3(n=args.spheres, strength=args.strength)[0])
@@ -44,7 +52,7 @@ ms = {w: [] for w, _ in words}
 last = {}
 for _ in range(args.rounds):
     for w, _ in words:
-        dev.set_option("cert_policy", w)
+        dev.set_option("cert_policy", w[0]); dev.set_option("occl", w[1]); dev.set_option("occl_policy", w[2])
         for _ in range(args.frames):
             ds.render_device(syn.EPSILON, syn.RAY_LENGTH, size, cam, buf.data_ptr())
         st = ds.collect_stats()
@@ -52,6 +60,6 @@ for _ in range(args.rounds):
         last[w] = st
 for w, label in words:
     st = last[w]
-    print(json.dumps({"build": args.tag, "scene": f"C3 n={args.spheres} s={args.strength} {args.size}^2 fov {args.fov:g} at {args.distance:g}", "tile_over_margin": round(ratio, 3), "policy": f"{w & 0xFFFFFFFF:#010x}", "label": label, "kernel_ms_median": round(statistics.median(ms[w]), 3),
+    print(json.dumps({"build": args.tag, "scene": f"C3 n={args.spheres} s={args.strength} {args.size}^2 fov {args.fov:g} at {args.distance:g}", "tile_over_margin": round(ratio, 3), "policy": f"{w[0] & 0xFFFFFFFF:#010x}", "occl": w[1], "occl_policy": f"{w[2]:#x}", "label": label, "kernel_ms_median": round(statistics.median(ms[w]), 3),
                       "kernel_ms_runs": [round(v, 3) for v in ms[w]], "sdf_evals_per_frame": st["sdf_evals"] // args.frames,
                       "wave_rounds_per_frame": st["wave_evals"] // args.frames, "shader_mhz": round(st["shader_mhz"], 1)}), flush=True)
