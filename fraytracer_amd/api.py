@@ -421,16 +421,13 @@ class Device:
     OPTIONS = {"refill_min": _lib.FT_OPT_REFILL_MIN, "max_blocks_per_cu": _lib.FT_OPT_MAX_BLOCKS_PER_CU,
                "host_chunks": _lib.FT_OPT_HOST_CHUNKS, "host_pin": _lib.FT_OPT_HOST_PIN, "math": _lib.FT_OPT_MATH,
                "tail_k": _lib.FT_OPT_TAIL_K, "guided": _lib.FT_OPT_GUIDED, "chunk": _lib.FT_OPT_CHUNK, "cull": _lib.FT_OPT_CULL, "escape": _lib.FT_OPT_ESCAPE, "lazy_union": _lib.FT_OPT_LAZY_UNION, "carved": _lib.FT_OPT_CARVED, "reuse": _lib.FT_OPT_REUSE,
-               "cert": _lib.FT_OPT_CERT, "cert_policy": _lib.FT_OPT_CERT_POLICY}
-
-    # switches that change only when work starts, never what a launch computes or counts.  Kept apart from OPTIONS only because tests/test_abi.py pins
-    # OPTIONS' key set; once that pin lists "order" the two dictionaries become one again:
-    # "order" = FT_OPT_ORDER, 1 (default) heavy tiles of the last frame first, 2 record tile costs only, 0 off
-    SCHEDULE_OPTIONS = {"order": _lib.FT_OPT_ORDER}
-
-    # exact shortcuts like "cert" / "cert_policy" (same frame, counters and flags; sdf_evals falls), apart from OPTIONS for the same pin:
-    # "occl" = FT_OPT_OCCL, the occlusion certificate (1 default, 0 off), "occl_policy" = FT_OPT_OCCL_POLICY, its schedule word
-    CERTIFICATE_OPTIONS = {"occl": _lib.FT_OPT_OCCL, "occl_policy": _lib.FT_OPT_OCCL_POLICY}
+               "cert": _lib.FT_OPT_CERT, "cert_policy": _lib.FT_OPT_CERT_POLICY,
+               # changes only when work starts, never what a launch computes or counts:
+               # FT_OPT_ORDER, 1 (default) heavy tiles of the last frame first, 2 record tile costs only, 0 off
+               "order": _lib.FT_OPT_ORDER,
+               # exact shortcuts like "cert" / "cert_policy" (same frame, counters and flags; sdf_evals falls):
+               # FT_OPT_OCCL, the occlusion certificate (1 default, 0 off), and FT_OPT_OCCL_POLICY, its schedule word
+               "occl": _lib.FT_OPT_OCCL, "occl_policy": _lib.FT_OPT_OCCL_POLICY}
 
     def set_option(self, name, value):
         """ft_ctx_set_option: per-context switches (the library reads no environment variables)"""
@@ -442,10 +439,7 @@ class Device:
         return int(v.value)
 
     def _option_id(self, name):
-        for table in (self.OPTIONS, self.SCHEDULE_OPTIONS):
-            if name in table:
-                return table[name]
-        return self.CERTIFICATE_OPTIONS[name]
+        return self.OPTIONS[name]
 
     # constructor twins ---------------------------------------------------------------------------
     def sphere(self, c, r): return check(lib.ft_form_sphere(self._ctx, C.byref(_lib.Sphere(_vec(c), r))))

@@ -749,9 +749,11 @@ long long ft_scene_tile_costs(const ft_scene* s, uint32_t* out, long long cap) {
 long long ft_scene_tile_order(const ft_scene* s, uint32_t* out, long long cap) { return readTileOrderSlot(s, true, out, cap); }
 // Internal: 1 where the scene's last recording frame launch on lane 0 handed its tiles out in a built order, 0 where it ran in index order
 int ft_scene_tile_order_used(const ft_scene* s) { return s && s->orderSlots[0].keyed && s->orderSlots[0].usedOrder ? 1 : 0; }
-// Internal (tools/tile_order_probe.py): tiles count as heavy from num / den of the mean cost on (the shipped rule is 1 / 1; 0 / 1 sorts every tile)
+// Internal (tools/tile_order_probe.py, tests/test_tile_order.py): tiles count as heavy from num / den of the mean cost on (the shipped rule is 1 / 1;
+// 0 / 1 sorts every tile; 1000000 / 1 leaves none heavy: the identity).  ft_tile_is_heavy compares cost * n * den with sum * num in 64 bits: den <= 16
+// keeps the left side below 2^62 for any frame, num <= 1000000 the right one for launches of fewer than 1.8e13 evaluation rounds (hours of kernel time)
 int ft_ctx_tile_order_rule(ft_ctx* c, uint32_t num, uint32_t den) {
-    if (!c || den == 0u || num > 16u || den > 16u) return setErr(FT_ERR_INVALID, "bad argument");
+    if (!c || den == 0u || num > 1000000u || den > 16u) return setErr(FT_ERR_INVALID, "bad argument");
     c->orderNum = num; c->orderDen = den;
     return FT_OK;
 }

@@ -70,7 +70,7 @@ def test_the_library_reads_no_environment_variables():
     host = ft.Device(-1)                       # options are plain context state: usable without a GPU
     try:
         defaults = {"refill_min": 64, "max_blocks_per_cu": 0, "host_chunks": 0, "host_pin": 1, "math": 0, "tail_k": -1, "guided": 0, "chunk": 64,
-                    "cull": 1, "escape": 1, "lazy_union": 1, "carved": 1, "reuse": 1, "cert": 1, "cert_policy": 0}
+                    "cull": 1, "escape": 1, "lazy_union": 1, "carved": 1, "reuse": 1, "cert": 1, "cert_policy": 0, "order": 1, "occl": 1, "occl_policy": 0}
         assert set(defaults) == set(ft.Device.OPTIONS)
         assert {k: host.get_option(k) for k in defaults} == defaults
         assert host.get_option("refill_min") == 64 and host.get_option("host_pin") == 1

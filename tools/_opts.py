@@ -10,7 +10,7 @@ def apply_env_options(dev):
     """-> {option: value} of what was applied"""
     done = {}
     for var, (name, conv) in _ENV.items():
-        if var in os.environ and (name in dev.OPTIONS or name in dev.SCHEDULE_OPTIONS or name in dev.CERTIFICATE_OPTIONS):
+        if var in os.environ and name in dev.OPTIONS:
             dev.set_option(name, conv(os.environ[var]))
             done[name] = dev.get_option(name)
     return done
