@@ -76,6 +76,13 @@ class Stats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if not k.startswith("reserved")}
 
 
+class Lattice(C.Structure):                  # ft_lattice: point (i, j, k) = origin + (i, j, k) * step, results at (i * ny + j) * nz + k
+    _fields_ = [("origin", Vec3), ("step", Vec3), ("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32)]
+
+
+FT_FIELD_BOUNDED = 1
+
+
 class TonemapParams(C.Structure):
     _fields_ = [("gamma", C.c_float), ("dither", C.c_int32), ("seed", C.c_uint32), ("bmp_order", C.c_int32)]
 
@@ -153,6 +160,10 @@ SYMBOLS = {
     "ft_trace_rays_hits": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, _P, C.POINTER(Stats)]),
     "ft_trace_rays_hits_device": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, _P]),
     "ft_eval_distance": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P]),
+    "ft_sample_points": (C.c_int, [_P, _P, _P, C.c_int64, C.c_float, C.c_uint32, _P, _P, _P]),
+    "ft_sample_points_device": (C.c_int, [_P, _P, _P, C.c_int64, C.c_float, C.c_uint32, _P, _P, _P]),
+    "ft_sample_lattice": (C.c_int, [_P, _P, C.POINTER(Lattice), C.c_float, C.c_uint32, _P, _P, _P]),
+    "ft_sample_lattice_device": (C.c_int, [_P, _P, C.POINTER(Lattice), C.c_float, C.c_uint32, _P, _P, _P]),
     "ft_scene_clone": (C.c_int, [_P, _P, C.POINTER(_P)]),
     "ft_render_multi": (C.c_int, [C.POINTER(_P), C.POINTER(_P), C.c_int32, C.POINTER(CameraS), C.POINTER(RenderParams), _P, C.POINTER(Stats)]),
     "ft_scene_info_get": (C.c_int, [_P, C.POINTER(SceneInfo)]),

@@ -148,6 +148,19 @@ class SdfForm:
         return out
 
     @staticmethod
+    def normal(form, epsilon, points, device=None):
+        """SdfForm.normal sdf epsilon position (SdfForm.fs:106-112) at points [..., 3] -> float32 [..., 3], the four evaluations and the
+        normalisation on the GPU (DeviceScene.sample_points)"""
+        return _form_scene(form, device).sample_points(points, normal_epsilon=epsilon, distance=False).normal
+
+    @staticmethod
+    def sample(form, origin, step, counts, normal_epsilon=None, bounded=False, device=None):
+        """sdf.Distance (and SdfForm.normal, with normal_epsilon) on the lattice lattice_points(origin, step, counts), computed on the GPU ->
+        FieldSamples with distance float32 [nx, ny, nz] and normal float32 [nx, ny, nz, 3] or None; bounded: SdfForm.tryDistance, NaN
+        standing for ValueNone (DeviceScene.sample_lattice)"""
+        return _form_scene(form, device).sample_lattice(origin, step, counts, normal_epsilon=normal_epsilon, bounded=bounded)
+
+    @staticmethod
     def normalFromRay(form, rays, device=None):
         """SdfForm.normalFromRay (SdfForm.fs:106-115) at the position of each ray [n, 8] -> float32 [n, 3]: forward
         differences with h = Epsilon / 8 at Ray.get(-Epsilon), evaluated on the GPU"""
@@ -575,6 +588,60 @@ def check_visibility(m, lead, what="visibility"):
         raise ValueError(f"{what}: the tensor must be contiguous (call .contiguous() first)")
 
 
+def check_device_points(t):
+    """leading shape of a device point buffer: float32, shape [..., 3], contiguous — anything else is a ValueError (no silent copy on the device)"""
+    if str(t.dtype).rsplit(".", 1)[-1] != "float32":
+        raise ValueError(f"device point buffer: dtype must be float32, not {t.dtype}")
+    shape = tuple(int(d) for d in t.shape)
+    if len(shape) < 1 or shape[-1] != 3:
+        raise ValueError(f"device point buffer: shape must be [..., 3] (x, y, z), not {list(shape)}")
+    if not t.is_contiguous():
+        raise ValueError("device point buffer: the tensor must be contiguous (call .contiguous() first)")
+    return shape[:-1]
+
+
+def lattice_points(origin, step, counts):
+    """The points of the lattice ft_sample_lattice evaluates, float32 [nx, ny, nz, 3]: point (i, j, k) is origin + (i, j, k) * step per
+    coordinate, as ONE float32 product, rounded, then ONE float32 sum, rounded (never fused).  Pure numpy: the definition, for callers and tests."""
+    F = np.float32
+    o, st = np.asarray(origin, F).reshape(3), np.asarray(step, F).reshape(3)
+    n = _lattice_counts(counts)
+    pts = np.empty(n + (3,), F)
+    for a in range(3):
+        prod = np.arange(n[a], dtype=F) * st[a]                       # (float)i is exact: counts are at most 2^24
+        pts[..., a] = (o[a] + prod).reshape([-1 if b == a else 1 for b in range(3)])
+    return pts
+
+
+def _lattice_counts(counts):
+    n = tuple(int(c) for c in counts)
+    if len(n) != 3 or any(c < 1 or c > 16777216 for c in n):
+        raise ValueError(f"lattice: counts must be three integers in 1 .. 16777216, not {counts!r}")
+    return n
+
+
+def _lattice(origin, step, counts):
+    n = _lattice_counts(counts)
+    o, st = _v3(origin), _v3(step)
+    return _lib.Lattice(_lib.Vec3(*o), _lib.Vec3(*st), *n), n
+
+
+class FieldSamples:
+    """What sample_points / sample_lattice return: `distance` float32 [...], `normal` float32 [..., 3], `material` int32 [...] (the handle of the
+    material object.Material.Color picks at the point; -1 where FT_FIELD_BOUNDED left the point out) — each None where not asked for; numpy
+    arrays, or device tensors where the call was given one."""
+
+    def __init__(self, distance=None, normal=None, material=None, materials=None):
+        self.distance = distance
+        self.normal = normal
+        self.material = material
+        self._materials = dict(materials or {})
+
+    def descriptor(self, handle):
+        """the SdfMaterial description (SdfMaterial.createSolid / createGlass value) a material handle was realised from; None for -1"""
+        return self._materials.get(int(handle))
+
+
 def _torch_int32(t):
     import torch                  # a device tensor was passed in: torch is loaded
     return torch.int32
@@ -988,6 +1055,70 @@ class DeviceScene:
         """asynchronous ft_shade_visible_device: n records and n uint32 masks -> n x 3 float32 colours (pointers as int; records 16-byte
         aligned); a streaming kernel on the context's stream; pair with collect_stats()."""
         check(lib.ft_shade_visible_device(self.device._ctx, self._scene, _dptr(d_hits_ptr), _dptr(d_visibility_ptr), n, _dptr(d_out_ptr)))
+
+    # ---- the distance field itself: lattices and point buffers ------------------------------------------------------------
+    def _field(self, lead, like, launch_host, launch_device, normal_epsilon, distance, material, bounded):
+        """The one place a field method decides between host arrays and device tensors -> FieldSamples.  like: None (numpy outputs through
+        launch_host) or a device tensor, whose device the outputs are allocated on and whose current stream launch_device runs on."""
+        normal = normal_epsilon is not None
+        if not (distance or normal or material):
+            raise ValueError("field: no output asked for")
+        eps = float(normal_epsilon) if normal else 0.0
+        flags = _lib.FT_FIELD_BOUNDED if bounded else 0
+        if like is not None:
+            outs = (like.new_empty(lead) if distance else None, like.new_empty(lead + (3,)) if normal else None,
+                    like.new_empty(lead, dtype=_torch_int32(like)) if material else None)
+            if int(np.prod(lead, dtype=np.int64)):
+                with self.device.on_current_stream(like):
+                    launch_device(eps, flags, *(None if o is None else o.data_ptr() for o in outs))
+        else:
+            outs = (np.empty(lead, np.float32) if distance else None, np.empty(lead + (3,), np.float32) if normal else None,
+                    np.empty(lead, np.int32) if material else None)
+            launch_host(eps, flags, *map(_hptr, outs))
+        return FieldSamples(*outs, materials=self.materials)
+
+    def sample_points(self, points, normal_epsilon=None, material=False, bounded=False, distance=True):
+        """ft_sample_points: scene.Object.Form.Distance at points [..., 3] -> FieldSamples shaped like the points without their last axis.
+        normal_epsilon: also SdfForm.normal sdf normal_epsilon p (SdfForm.fs:106-112); material: also the handle of the material
+        object.Material.Color picks at p (FieldSamples.descriptor); bounded: SdfForm.tryDistance — outside SdfBoundary.isInside nothing is
+        evaluated, distance and normal are NaN, the material -1.  A device tensor (see is_device_tensor; float32, contiguous) is sampled where
+        it lies by ft_sample_points_device on the caller's current stream and the results are tensors of its device."""
+        ctx, sc = self.device._ctx, self._scene
+        if is_device_tensor(points):
+            lead = check_device_points(points)
+            n = int(np.prod(lead, dtype=np.int64))
+            return self._field(lead, points, None, lambda e, f, *o: self.sample_points_device(points.data_ptr(), n, *o, normal_epsilon=e, flags=f),
+                               normal_epsilon, distance, material, bounded)
+        pts = np.ascontiguousarray(points, dtype=np.float32)
+        if pts.ndim < 1 or pts.shape[-1] != 3:
+            raise ValueError(f"points: shape must be [..., 3], not {list(pts.shape)}")
+        n = pts.size // 3
+        return self._field(pts.shape[:-1], None, lambda e, f, *o: check(lib.ft_sample_points(ctx, sc, _hptr(pts), n, e, f, *o)), None,
+                           normal_epsilon, distance, material, bounded)
+
+    def sample_lattice(self, origin, step, counts, normal_epsilon=None, material=False, bounded=False, distance=True, like=None):
+        """ft_sample_lattice: sample_points on lattice_points(origin, step, counts) without any point array -> FieldSamples with distance
+        [nx, ny, nz], normal [nx, ny, nz, 3], material [nx, ny, nz].  like: a device tensor — the results are then tensors of its device,
+        written by ft_sample_lattice_device on the caller's current stream."""
+        lat, n = _lattice(origin, step, counts)
+        ctx, sc = self.device._ctx, self._scene
+        if like is not None and not is_device_tensor(like):
+            raise ValueError("like: a device tensor (see is_device_tensor) or None")
+        return self._field(n, like, lambda e, f, *o: check(lib.ft_sample_lattice(ctx, sc, C.byref(lat), e, f, *o)),
+                           lambda e, f, *o: check(lib.ft_sample_lattice_device(ctx, sc, C.byref(lat), e, f, *map(_dptr, o))),
+                           normal_epsilon, distance, material, bounded)
+
+    def sample_points_device(self, d_points_ptr, n, d_distance_ptr=None, d_normal_ptr=None, d_material_ptr=None, normal_epsilon=0.0, flags=0):
+        """asynchronous ft_sample_points_device: n points (12 B each) at d_points_ptr -> n float32 distances, n x 3 float32 normals, n int32
+        material handles (pointers as int, None = not asked; every buffer 4-byte aligned); no scratch, no copy, on the context's stream"""
+        check(lib.ft_sample_points_device(self.device._ctx, self._scene, _dptr(d_points_ptr), n, normal_epsilon, flags,
+                                          _dptr(d_distance_ptr), _dptr(d_normal_ptr), _dptr(d_material_ptr)))
+
+    def sample_lattice_device(self, origin, step, counts, d_distance_ptr=None, d_normal_ptr=None, d_material_ptr=None, normal_epsilon=0.0, flags=0):
+        """asynchronous ft_sample_lattice_device: the lattice's nx x ny x nz results, k contiguous, at the given device addresses (as above)"""
+        lat, _ = _lattice(origin, step, counts)
+        check(lib.ft_sample_lattice_device(self.device._ctx, self._scene, C.byref(lat), normal_epsilon, flags,
+                                           _dptr(d_distance_ptr), _dptr(d_normal_ptr), _dptr(d_material_ptr)))
 
     def eval_distance(self, points):
         pts = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)

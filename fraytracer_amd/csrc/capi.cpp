@@ -71,6 +71,7 @@ struct ft_ctx {
     int optOccl = 1;                                       // FT_OPT_OCCL: the lean kernel's occlusion certificate (kernels.hip ft_occlusion_certificate); needs optEscape
     int optOcclPolicy = 0;                                 // FT_OPT_OCCL_POLICY: 0 = the shipped schedule (FT_OCCL_PERIOD ...)
     int optOrder = 1;                                      // FT_OPT_ORDER: 1 = frames hand their heavy tiles out first, from the costs the scene's last launch of the same grid recorded; 2 = record only; 0 = off
+    int fieldBrick = -1;                                   // brick shape of the lattice launches: -1 by kernel family (launchField), else an index into FT_FIELD_BRICKS (ft_ctx_field_brick: the probe's shapes)
     uint32_t orderNum = 1, orderDen = 1;                   // a tile is heavy from orderNum / orderDen of the mean cost on (ft_ctx_tile_order_rule: the probes' other rules)
 };
 
@@ -1466,6 +1467,175 @@ int ft_eval_distance(ft_ctx* c, const ft_scene* s, const ft_vec3* pts, int64_t n
     HIP_TRY(hipMemcpyAsync(outD, base + pBytes, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
     if (outM) HIP_TRY(hipMemcpyAsync(outM, base + pBytes + dBytes, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
+    return FT_OK;
+}
+
+// ---- field sampling: ft_sample_points, ft_sample_lattice and their *_device forms (kernels.hip "Field sampling") -----------------
+namespace {
+
+// What a field launch runs, beside planTrace and by its rules: the kernel family, its arithmetic, its value slots, whether the wave rows of the culling
+// pass are kept, the LDS footprint (ft_lds_layout).  A carved union takes the general kernel under glibc math or FT_OPT_CARVED = 0 (no carved *_libm
+// build exists); the lean and carved kernels keep their values in registers (nSlots = 0); the lean kernel always has its rows, any other non-carved
+// kernel where the scene has a cull site, and those optional rows are dropped where the footprint would exceed the device's limit.
+struct FieldPlan { unsigned variant; bool libm, cullRows; uint32_t nSlots; size_t lds; };
+int planField(const ft_ctx* c, const ft_scene* s, FieldPlan& p) {
+    const bool hasCull = s->dev.cullPc != 0xffffffffu;
+    p.libm = libmLaunch(c, s);
+    p.variant = (s->dev.fastPath == 3u && (!c->optCarved || p.libm)) ? 0u : s->dev.fastPath;
+    p.nSlots = (p.variant == 1u || p.variant == 3u) ? 0u : s->dev.nSlots;
+    p.cullRows = p.variant == 1u || (p.variant != 3u && hasCull);
+    int maxLds = 0;
+    HIP_TRY(hipDeviceGetAttribute(&maxLds, hipDeviceAttributeMaxSharedMemoryPerBlock, c->device));
+    p.lds = 4u * (size_t)ft_lds_layout(p.nSlots, s->dev.nStage, p.libm, p.cullRows).total;
+    if (p.lds > (size_t)maxLds && p.variant != 1u && p.cullRows) {
+        p.cullRows = false;
+        p.lds = 4u * (size_t)ft_lds_layout(p.nSlots, s->dev.nStage, p.libm, false).total;
+    }
+    if (p.lds > (size_t)maxLds) return setErr(FT_ERR_UNSUPPORTED, "scene needs " + std::to_string(p.lds) + " bytes of LDS per workgroup; the device offers " + std::to_string(maxLds));
+    return FT_OK;
+}
+
+// points (n of them) or a lattice, and where the results go: every address is host or device memory as the entry point says
+struct FieldRequest { const void* points; int64_t n; const ft_lattice* lat; float eps; uint32_t flags; void* dist; void* normal; void* material; };
+int64_t fieldCount(const FieldRequest& r) { return r.lat ? (int64_t)r.lat->nx * r.lat->ny * r.lat->nz : r.n; }
+
+// Everything that can be refused without a device, in the header's order.  *nothing: FT_OK with nothing to launch.
+int checkField(const ft_ctx* c, const ft_scene* s, const FieldRequest& r, bool deviceMemory, bool* nothing) {
+    static_assert(sizeof(ft_lattice) == 36, "layout");
+    *nothing = false;
+    if (!c) return setErr(FT_ERR_INVALID, "null context");
+    if (!s || s->ctx != c) return setErr(FT_ERR_INVALID, "bad argument (scene must belong to this context)");
+    if (!r.dist && !r.normal && !r.material) return setErr(FT_ERR_INVALID, "field: no output asked for");
+    if (r.flags & ~(uint32_t)FT_FIELD_BOUNDED) return setErr(FT_ERR_INVALID, "field: unknown flag bits");
+    if (r.lat) {
+        const int32_t cnt[3] = {r.lat->nx, r.lat->ny, r.lat->nz};
+        for (int32_t v : cnt) if (v < 1 || v > 16777216) return setErr(FT_ERR_INVALID, "lattice: every count must be 1 .. 16777216");
+    } else if (!r.points || r.n < 0) return setErr(FT_ERR_INVALID, "field: null points or a negative count");
+    if (deviceMemory) {
+        const void* all[4] = {r.points, r.dist, r.normal, r.material};
+        for (const void* p : all) if (reinterpret_cast<uintptr_t>(p) & 3u) return setErr(FT_ERR_INVALID, "field: every device buffer must be 4-byte aligned");
+    }
+    if (r.points && (r.points == r.dist || r.points == r.normal || r.points == r.material)) return setErr(FT_ERR_INVALID, "field: input and output must not overlap");
+    if ((r.dist && (r.dist == r.normal || r.dist == r.material)) || (r.normal && r.normal == r.material)) return setErr(FT_ERR_INVALID, "field: outputs must not overlap");
+    // three counts of at most 2^24: the product of two fits 2^48, and the third is applied only below the limit
+    const uint64_t total = r.lat ? (uint64_t)r.lat->nx * (uint64_t)r.lat->ny : (uint64_t)r.n;
+    if (total >= 0xFFFF0000ull || (r.lat && total * (uint64_t)r.lat->nz >= 0xFFFF0000ull)) return setErr(FT_ERR_UNSUPPORTED, "more than 2^32 points in one call");
+    *nothing = !r.lat && r.n == 0;
+    return FT_OK;
+}
+
+// the launch: device memory throughout, the context's stream, not synchronised; the arguments have passed checkField and the context has a device
+int launchField(ft_ctx* c, const ft_scene* s, const FieldRequest& r) {
+    FieldPlan plan;
+    int rc = planField(c, s, plan); if (rc) return rc;
+    FtFieldArgs a{};
+    a.S = s->dev;
+    a.S.fastPath = plan.variant;
+    a.S.nSlots = plan.nSlots;
+    a.S.mathFma = c->optMath == FT_MATH_GLIBC_FMA ? 1u : 0u;
+    a.carve = s->carve;
+    a.math = plan.libm ? 1u : 0u;
+    a.cull = (s->dev.cullPc != 0xffffffffu && plan.cullRows && c->optCull) ? 1u : 0u;
+    // The brick of a wave, by measurement (256^3 lattices, kernel ms for 4x4x4 / 2x4x8 / 2x2x16, profiles/field_probe.jsonl): the lean kernel gains from the
+    // tightest culling ball, C3 1.78 / 1.86 / 1.91; the grid-union kernels from longer runs along k, whose lanes share lookup cells and whose stores are
+    // contiguous — 1000 tori 0.395 / 0.378 / 0.403, combinator crowd (128^3) 0.393 / 0.357 / 0.363
+    static const uint32_t bricks[3][2] = FT_FIELD_BRICKS;
+    const int brick = c->fieldBrick >= 0 ? c->fieldBrick : (plan.variant == 1u ? 0 : FT_FIELD_BRICK_DEFAULT);
+    a.lgJ = bricks[brick][0]; a.lgK = bricks[brick][1];
+    if (r.lat) {
+        const ft_lattice& l = *r.lat;
+        a.origin[0] = l.origin.x; a.origin[1] = l.origin.y; a.origin[2] = l.origin.z;
+        a.step[0] = l.step.x; a.step[1] = l.step.y; a.step[2] = l.step.z;
+        a.nx = (uint32_t)l.nx; a.ny = (uint32_t)l.ny; a.nz = (uint32_t)l.nz;
+        const uint32_t lgI = 6u - a.lgJ - a.lgK;
+        const uint64_t bi = ((uint64_t)a.nx + (1u << lgI) - 1u) >> lgI, bj = ((uint64_t)a.ny + (1u << a.lgJ) - 1u) >> a.lgJ, bk = ((uint64_t)a.nz + (1u << a.lgK) - 1u) >> a.lgK;
+        a.bricksJ = (uint32_t)bj; a.bricksK = (uint32_t)bk;
+        a.nJobs = (uint32_t)(bi * bj * bk);                            // a brick count is at most its axis' point count: the product stays below 2^32
+    } else {
+        a.pts = static_cast<const float*>(r.points);
+        a.n = (uint32_t)r.n;
+        a.nJobs = (uint32_t)(((uint64_t)r.n + 63u) >> 6);
+    }
+    a.bounded = (r.flags & FT_FIELD_BOUNDED) ? 1u : 0u;
+    const ft::Boundary& b = s->flat.boundary;
+    a.bc[0] = b.center.x; a.bc[1] = b.center.y; a.bc[2] = b.center.z; a.br2 = b.radius * b.radius;
+    a.normalEps = r.normal ? r.eps : 0.0f;
+    a.outD = static_cast<float*>(r.dist); a.outN = static_cast<float*>(r.normal); a.outM = static_cast<int32_t*>(r.material);
+    a.matHandles = s->dMatHandles; a.nMaterials = (uint32_t)s->flat.materialHandles.size();
+    int perCU = 0;
+    HIP_TRY(ft_field_occupancy(plan.variant, a.carve.kind, plan.libm, plan.lds, &perCU));
+    if (perCU < 1) return setErr(FT_ERR_UNSUPPORTED, "the field kernel does not fit a compute unit with this scene's LDS footprint");
+    perCU = std::min(perCU, 8);
+    if (c->optMaxBlocksPerCU > 0) perCU = std::min(perCU, c->optMaxBlocksPerCU);       // FT_OPT_MAX_BLOCKS_PER_CU
+    const uint64_t wantBlocks = ((uint64_t)a.nJobs + (FT_BLOCK / 64) - 1) / (FT_BLOCK / 64);
+    const unsigned blocks = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)c->numCUs * perCU, wantBlocks));
+    hipEvent_t e0, e1;
+    if ((rc = foldOldestEvents(c))) return rc;
+    if ((rc = acquireEvents(c, e0, e1))) return rc;
+    HIP_TRY(hipEventRecord(e0, c->stream));
+    HIP_TRY(ft_launch_field(&a, blocks, plan.lds, c->stream));
+    HIP_TRY(hipEventRecord(e1, c->stream));
+    c->events.emplace_back(e0, e1);
+    return FT_OK;
+}
+
+int sampleDevice(ft_ctx* c, const ft_scene* s, const FieldRequest& r) {
+    bool nothing;
+    int rc = checkField(c, s, r, true, &nothing); if (rc || nothing) return rc;
+    if ((rc = requireDevice(c))) return rc;
+    return launchField(c, s, r);
+}
+
+// the host forms: [points | distance | normal | material] in the context's scratch, each on a 256-byte boundary; the lattice form uploads nothing
+int sampleHost(ft_ctx* c, const ft_scene* s, const FieldRequest& r) {
+    bool nothing;
+    int rc = checkField(c, s, r, false, &nothing); if (rc || nothing) return rc;
+    if ((rc = requireDevice(c))) return rc;
+    const size_t n = (size_t)fieldCount(r);
+    const size_t oD = align256(r.points ? n * 12 : 0), oN = align256(oD + (r.dist ? n * 4 : 0)), oM = align256(oN + (r.normal ? n * 12 : 0));
+    if ((rc = ensureScratch(c, oM + (r.material ? n * 4 : 0)))) return rc;
+    unsigned char* base = static_cast<unsigned char*>(c->scratch);
+    if (r.points) HIP_TRY(hipMemcpyAsync(base, r.points, n * 12, hipMemcpyHostToDevice, c->stream));
+    FieldRequest d = r;
+    d.points = r.points ? base : nullptr;
+    d.dist = r.dist ? base + oD : nullptr; d.normal = r.normal ? base + oN : nullptr; d.material = r.material ? base + oM : nullptr;
+    rc = launchField(c, s, d);
+    hipError_t err = hipSuccess;
+    if (!rc && r.dist) err = hipMemcpyAsync(r.dist, d.dist, n * 4, hipMemcpyDeviceToHost, c->stream);
+    if (!rc && r.normal && err == hipSuccess) err = hipMemcpyAsync(r.normal, d.normal, n * 12, hipMemcpyDeviceToHost, c->stream);
+    if (!rc && r.material && err == hipSuccess) err = hipMemcpyAsync(r.material, d.material, n * 4, hipMemcpyDeviceToHost, c->stream);
+    const hipError_t se = hipStreamSynchronize(c->stream);             // nothing of the call is left in flight, whatever happened
+    if (rc) return rc;
+    if (err != hipSuccess) return hipFail(err, "field host output");
+    if (se != hipSuccess) return hipFail(se, "field");
+    return FT_OK;
+}
+
+}  // namespace
+
+int ft_sample_points(ft_ctx* c, const ft_scene* s, const ft_vec3* points, int64_t n, float normal_epsilon, uint32_t flags,
+                     float* out_distance, ft_vec3* out_normal, int32_t* out_material) {
+    return sampleHost(c, s, FieldRequest{points, n, nullptr, normal_epsilon, flags, out_distance, out_normal, out_material});
+}
+int ft_sample_points_device(ft_ctx* c, const ft_scene* s, const void* d_points, int64_t n, float normal_epsilon, uint32_t flags,
+                            void* d_distance, void* d_normal, void* d_material) {
+    return sampleDevice(c, s, FieldRequest{d_points, n, nullptr, normal_epsilon, flags, d_distance, d_normal, d_material});
+}
+int ft_sample_lattice(ft_ctx* c, const ft_scene* s, const ft_lattice* lattice, float normal_epsilon, uint32_t flags,
+                      float* out_distance, ft_vec3* out_normal, int32_t* out_material) {
+    if (!lattice) return setErr(FT_ERR_INVALID, "null lattice");
+    return sampleHost(c, s, FieldRequest{nullptr, 0, lattice, normal_epsilon, flags, out_distance, out_normal, out_material});
+}
+int ft_sample_lattice_device(ft_ctx* c, const ft_scene* s, const ft_lattice* lattice, float normal_epsilon, uint32_t flags,
+                             void* d_distance, void* d_normal, void* d_material) {
+    if (!lattice) return setErr(FT_ERR_INVALID, "null lattice");
+    return sampleDevice(c, s, FieldRequest{nullptr, 0, lattice, normal_epsilon, flags, d_distance, d_normal, d_material});
+}
+// Internal (not in the header, like ft_ctx_tile_order_rule; tools/field_probe.py): the brick shape of this context's lattice launches, an index into
+// FT_FIELD_BRICKS (0: 4x4x4, 1: 2x4x8, 2: 2x2x16), or -1 for the shipped rule (launchField: by kernel family).  Every shape gives the same bits.
+int ft_ctx_field_brick(ft_ctx* c, int32_t shape) {
+    if (!c || shape < -1 || shape > 2) return setErr(FT_ERR_INVALID, "bad argument");
+    c->fieldBrick = shape;
     return FT_OK;
 }
 

@@ -128,9 +128,40 @@ FT_HD FtTraceKey ft_trace_key(const FtRenderArgs& a) {
     return FtTraceKey{a.S.fastPath, a.carve.kind, ft_trace_form(a.views != nullptr, a.shade), a.ext != 0u, a.math != 0u};
 }
 
+// Field sampling (ft_sample_points / ft_sample_lattice; kernels.hip "Field sampling"): one point per lane, one job per wave.  A job is 64 consecutive
+// points of a point buffer (pts != NULL) or one brick of 64 lattice points: 2^lgI x 2^lgJ x 2^lgK of them along i, j and k (lgI = 6 - lgJ - lgK), lane
+// l at (l >> (lgJ + lgK), (l >> lgK) & (2^lgJ - 1), l & (2^lgK - 1)) in its brick; brick b lies at (b / (bricksJ * bricksK), (b / bricksK) % bricksJ,
+// b % bricksK) bricks.  A block of its own, like FtGridBuildArgs: nothing in FtRenderArgs or FtSceneDev moves.
+struct FtFieldArgs {
+    FtSceneDev S;             // fastPath: the kernel family as capi.cpp planField decides it (1 lean, 3 carved, otherwise the general interpreter)
+    FtCarve carve;            // fastPath == 3 only
+    const float* pts;         // points form: n x 3 floats; NULL: the lattice below
+    float origin[3], step[3];
+    uint32_t ny, nz, nx;      // lattice counts (points form: unused)
+    uint32_t bricksJ, bricksK;
+    uint32_t lgJ, lgK;        // the brick's shape
+    uint32_t nJobs;           // bricks, or ceil(n / 64)
+    uint32_t n;               // points form: the number of points (< 0xFFFF0000)
+    uint32_t cull;            // 1: ft_cull_children before every evaluation round (needs the wave rows in LDS)
+    uint32_t math;            // 1: the *_libm build
+    uint32_t bounded;         // FT_FIELD_BOUNDED: evaluate only where (dx dx + dy dy) + dz dz < br2, d = p - bc
+    float bc[3], br2;
+    float normalEps;          // read only with outN
+    uint32_t nMaterials;      // entries of matHandles
+    float* outD;              // any of the three may be NULL, not all
+    float* outN;              // 3 floats per point
+    int32_t* outM;
+    const int32_t* matHandles;   // dense material index -> context handle, as in FtRenderArgs
+};
+// the brick shapes a launch may ask for: lgJ, lgK of 4x4x4, 2x4x8 and 2x2x16
+#define FT_FIELD_BRICKS {{2u, 2u}, {2u, 3u}, {1u, 4u}}
+#define FT_FIELD_BRICK_DEFAULT 1
+
 #ifdef __cplusplus
 extern "C" {
 #endif
+hipError_t ft_launch_field(const FtFieldArgs* a, unsigned blocks, size_t ldsBytes, hipStream_t st);
+hipError_t ft_field_occupancy(unsigned variant, unsigned carveKind, bool libm, size_t ldsBytes, int* blocksPerCU);
 hipError_t ft_launch_trace(const FtRenderArgs* a, unsigned blocks, size_t ldsBytes, hipStream_t st);
 hipError_t ft_launch_eval_points(const FtSceneDev* S, int math, const float* pts, long long n, float* outD, int* outM,
                                  unsigned blocks, size_t ldsBytes, hipStream_t st);

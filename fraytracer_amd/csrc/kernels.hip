@@ -2319,6 +2319,126 @@ extern "C" __global__ void __launch_bounds__(FT_BLOCK) ft_eval_points_kernel_lib
     ft_eval_points_body<1>(S, pts, n, outD, outM);
 }
 
+// ------------------------------------------------------------------------------------------------
+// Field sampling (ft_sample_points, ft_sample_lattice and their *_device forms): scene.Object.Form.Distance, SdfForm.normal and the material
+// object.Material.Color picks, at the points of a lattice or of a point buffer.
+//
+// Persistent and grid-stride: wave w of the launch takes jobs w, w + waves, ...; a job is one brick of 64 lattice points or 64 consecutive points
+// of the buffer (FtFieldArgs), one point per lane.  The evaluators are the trace kernels' own, with the hit threshold at +inf (no lazy union, no
+// early exit of the carved walk), so a value is the bits ft_eval_points_kernel gives for the point.
+//
+// All 64 lanes run every evaluation: ft_cull_children, its DPP scans and the ballots of the regime tests need them.  A lane without a point of its
+// own — beyond the lattice's edge or the buffer's end, or outside the boundary sphere under FT_FIELD_BOUNDED — evaluates a copy of the point of
+// the wave's first lane that has one and stores nothing; a copy changes neither the bounding ball of the culling pass nor any regime.  A wave none
+// of whose lanes has a point to evaluate skips the job (wave-uniform).
+//
+// With a normal a point takes four evaluation rounds, in SdfForm.normal's order: x + epsilon, y + epsilon, z + epsilon, then the point itself, whose
+// value is the distance written — the same evaluation with or without the normal.  The culling pass runs before every round, for that round's 64
+// query points: its bounds are proved for exactly those.
+// ------------------------------------------------------------------------------------------------
+template <int VARIANT, int MATH, int K>
+__device__ __forceinline__ void ft_field_body(const FtFieldArgs& a) {
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    const FtLdsLayout L = ft_lds_layout(a.S.nSlots, a.S.nStage, MATH != 0, true);      // the trace kernels' layout (of the header only the flag words are used)
+    float* sd = ft_lds + L.slotD + tid;
+    uint32_t* sl = reinterpret_cast<uint32_t*>(ft_lds + L.slotL) + tid;
+    float* ldsC = ft_lds + L.consts;
+    for (uint32_t i = tid; i < a.S.nStage; i += FT_BLOCK) ldsC[i] = a.S.consts[i];
+    if (MATH != 0 && tid < FT_LIBM_TAB_DOUBLES) const_cast<ft_u64*>(ft_libm_tab(a.S))[tid] = ft_libm_tab_g[tid];
+    if (tid < 32u) reinterpret_cast<uint32_t*>(ft_lds)[tid] = 0u;       // prim_triangle flags a NaN sign there
+    __syncthreads();
+    const uint32_t waveInBlock = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
+    float* cullRow = ft_lds + L.rows + waveInBlock * FT_CULL_ROW;      // this wave's row; touched only where a.cull says the launch has the rows
+    const uint32_t nWaves = gridDim.x * (FT_BLOCK / 64);
+    const uint32_t lgJK = a.lgJ + a.lgK;
+#pragma unroll 1
+    for (uint32_t job = blockIdx.x * (FT_BLOCK / 64) + waveInBlock; job < a.nJobs; job += nWaves) {
+        // ---- this lane's point: loaded, or computed (one product, one sum per coordinate; this file is compiled without contraction) ----
+        bool have; uint32_t idx; f3 p = mk3(0.0f, 0.0f, 0.0f);
+        if (a.pts != nullptr) {                                        // wave-uniform
+            idx = job * 64u + lane;                                    // n < 0xFFFF0000: no wrap
+            have = idx < a.n;
+            if (have) { const float* q = a.pts + 3ull * idx; p = mk3(q[0], q[1], q[2]); }
+        } else {
+            const uint32_t bk = job % a.bricksK, bij = job / a.bricksK, bj = bij % a.bricksJ, bi = bij / a.bricksJ;
+            const uint32_t i = (bi << (6u - lgJK)) + (lane >> lgJK), j = (bj << a.lgJ) + ((lane >> a.lgK) & ((1u << a.lgJ) - 1u)),
+                           k = (bk << a.lgK) + (lane & ((1u << a.lgK) - 1u));
+            have = i < a.nx && j < a.ny && k < a.nz;
+            idx = (i * a.ny + j) * a.nz + k;                           // < nx ny nz < 0xFFFF0000 where `have`
+            p = mk3(a.origin[0] + (float)i * a.step[0], a.origin[1] + (float)j * a.step[1], a.origin[2] + (float)k * a.step[2]);
+        }
+        bool active = have;
+        if (a.bounded != 0u) {                                         // SdfBoundary.isInside (SdfBoundary.fs:56)
+            const float dx = p.x - a.bc[0], dy = p.y - a.bc[1], dz = p.z - a.bc[2];
+            active = have && (dx * dx + dy * dy) + dz * dz < a.br2;
+        }
+        const unsigned long long am = __ballot(active);
+        float d = __builtin_nanf(""), gx = d, gy = d, gz = d;
+        uint32_t leaf = 0xffffffffu;
+        if (am != 0ull) {                                              // wave-uniform
+            const f3 p0 = ft_readlane3(p, __ffsll((long long)am) - 1);
+            if (!active) p = p0;
+#pragma unroll 1
+            for (int round = a.outN != nullptr ? 0 : 3; round < 4; ++round) {
+                f3 q = p;
+                if (round == 0) q.x = p.x + a.normalEps;               // SdfForm.fs:108-110
+                if (round == 1) q.y = p.y + a.normalEps;
+                if (round == 2) q.z = p.z + a.normalEps;
+                uint32_t cullN = FT_CULL_NONE;
+                if (VARIANT != 3 && a.cull != 0u) cullN = ft_cull_children(a.S, q, true, ~0ull, ldsC, cullRow);
+                float v; uint32_t lf;
+                if (VARIANT == 1) ft_eval_smooth_spheres<MATH>(a.S, q, ldsC, v, lf, cullRow, cullN);
+                else if (VARIANT == 3) ft_eval_carved<K>(a.S, a.carve, q, v, lf, __builtin_inff());
+                else ft_eval<true, MATH>(a.S, q, sd, sl, ldsC, v, lf, __builtin_inff(), cullRow, cullN);
+                if (round == 0) gx = v;
+                if (round == 1) gy = v;
+                if (round == 2) gz = v;
+                if (round == 3) { d = v; leaf = lf; }
+            }
+        }
+        if (!have) continue;
+        if (a.outD != nullptr) a.outD[idx] = active ? d : __builtin_nanf("");
+        if (a.outN != nullptr) {
+            f3 n = splat3(__builtin_nanf(""));
+            if (active) n = ft_normalize(mk3(gx, gy, gz) - splat3(d)); // SdfForm.fs:107-112: three divisions by the root of (x x + y y) + z z
+            float* o = a.outN + 3ull * idx;
+            o[0] = n.x; o[1] = n.y; o[2] = n.z;
+        }
+        if (a.outM != nullptr) a.outM[idx] = active && leaf < a.nMaterials ? as_const(a.matHandles)[leaf] : -1;
+    }
+}
+
+// The table of field-kernel builds: name stem, occupancy hint, VARIANT, MATH, K.  The families and the carved kinds are the trace table's; the general
+// build is the interpreter with on-demand calls (what ft_eval_points_kernel runs), which serves fastPath 0 and 2 alike.  The hints are those of the
+// trace rows with the same evaluator.
+#define FT_FIELD_BUILDS(X) \
+    X(, FT_CALLS_OCC, 0, 0, 0) \
+    X(_libm, , 0, 1, 0) \
+    X(_smooth_spheres, , 1, 0, 0) \
+    X(_smooth_spheres_libm, , 1, 1, 0) \
+    X(_carved_spheres, FT_OCC(6), 3, 0, FT_PR_SPHERE) \
+    X(_carved_capsules, FT_OCC(6), 3, 0, FT_PR_CAPSULE) \
+    X(_carved_tori, FT_OCC(6), 3, 0, FT_PR_TORUS) \
+    X(_carved_triangles, FT_OCC(5), 3, 0, FT_PR_TRIANGLE) \
+    X(_carved_mixed, FT_OCC(5), 3, 0, FT_CARVE_MIXED)
+#define FT_FIELD_KERNEL(stem, occ, VARIANT, MATH, K) \
+    extern "C" __global__ void __launch_bounds__(FT_BLOCK) occ ft_field_kernel##stem(const FtFieldArgs a) { ft_field_body<VARIANT, MATH, (int)(K)>(a); }
+FT_FIELD_BUILDS(FT_FIELD_KERNEL)
+struct FtFieldRow { uint32_t variant, kind; bool libm; const void* handle; };
+#define FT_FIELD_ROW(stem, occ, VARIANT, MATH, K) {VARIANT, (uint32_t)(K), MATH != 0, (const void*)ft_field_kernel##stem},
+// the build of a family (2 counts as 0), arithmetic and — carved only — kind; a kind without a row of its own takes the mixed one; nullptr: none
+static const void* ft_field_kernel_of(uint32_t variant, uint32_t carveKind, bool libm) {
+    static const FtFieldRow table[] = {FT_FIELD_BUILDS(FT_FIELD_ROW)};
+    if (variant == 2u) variant = 0u;
+    const void* mixed = nullptr;
+    for (const FtFieldRow& r : table) {
+        if (r.variant != variant || r.libm != libm) continue;
+        if (variant != 3u || r.kind == carveKind) return r.handle;
+        if (r.kind == FT_CARVE_MIXED) mixed = r.handle;
+    }
+    return mixed;
+}
+
 // device math primitives, for bit-parity tests against the oracle
 extern "C" __global__ void ft_math_kernel(int op, const float* __restrict__ x, const float* __restrict__ y, long long n, float* __restrict__ out) {
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
@@ -2754,6 +2874,18 @@ extern "C" hipError_t ft_launch_trace(const FtRenderArgs* a, unsigned blocks, si
     FtRenderArgs args = *a;
     void* kp[] = {&args};
     return hipLaunchKernel(k, dim3(blocks), dim3(FT_BLOCK), kp, ldsBytes, st);
+}
+extern "C" hipError_t ft_launch_field(const FtFieldArgs* a, unsigned blocks, size_t ldsBytes, hipStream_t st) {
+    const void* k = ft_field_kernel_of(a->S.fastPath, a->carve.kind, a->math != 0u);
+    if (!k) return hipErrorInvalidDeviceFunction;
+    FtFieldArgs args = *a;
+    void* kp[] = {&args};
+    return hipLaunchKernel(k, dim3(blocks), dim3(FT_BLOCK), kp, ldsBytes, st);
+}
+extern "C" hipError_t ft_field_occupancy(unsigned variant, unsigned carveKind, bool libm, size_t ldsBytes, int* blocksPerCU) {
+    const void* k = ft_field_kernel_of(variant, carveKind, libm);
+    if (!k) return hipErrorInvalidDeviceFunction;
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocksPerCU, k, FT_BLOCK, ldsBytes);
 }
 extern "C" hipError_t ft_launch_eval_points(const FtSceneDev* S, int math, const float* pts, long long n, float* outD, int* outM,
                                             unsigned blocks, size_t ldsBytes, hipStream_t st) {

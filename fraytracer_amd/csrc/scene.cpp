@@ -900,6 +900,7 @@ bool flatten(const Builder& b, int object, const float bg[3], const int* lights,
     Flattener fl(b, out, err);
     if (!fl.emitObject(object, 0)) return false;
     fl.linkCalls();
+    out.boundary = b.forms[b.objects[object].form].boundary;
     out.nSlots = fl.maxSlot + 1;
     out.nStage = fl.stageEnd <= FT_MAX_STAGE_FLOATS ? fl.stageEnd : FT_MAX_STAGE_FLOATS;
     out.nearR2 = (fl.stageEnd > 0 && fl.nearR > 0.0 && fl.nearR < 1e29) ? (float)(fl.nearR * fl.nearR * (1.0 - 1e-5)) : 0.0f;

@@ -117,6 +117,7 @@ struct FlatScene {                                            // host copy of ev
     std::vector<FtItemRec> itemsT;                            // fastPath == 3: candidate lists with a terminator per cell
     std::vector<uint32_t> cellStartT;                         // fastPath == 3: byte offsets into itemsT
     float bg[3] = {0, 0, 0};
+    Boundary boundary{};                                      // scene.Object.Form.Boundary (ft_sample_*: FT_FIELD_BOUNDED)
 };
 
 // Boundary algebra (SdfBoundary.fs:7-67) and grid build (SdfBoundary.fs:225-274)

@@ -17,6 +17,8 @@
 //   Image::shadeHits / shadeHitsRelit                   SdfScene.trace from its hit on (SdfScene.fs:11-28) over hit records (ft_shade_hits, ft_scene_relight)
 //   Image::lightVisibility / shadeVisible               which lights reach each record, one bit per light, and shading from those bits with no march
 //                                                       (ft_light_visibility, ft_shade_visible)
+//   Field::sampleLattice / samplePoints                 sdf.Distance, SdfForm.normal and the material at the points of a lattice or a point buffer
+//                                                       (ft_sample_lattice, ft_sample_points; SdfForm.fs:7-12, 106-112)
 #pragma once
 #include <stdexcept>
 #include <string>
@@ -259,6 +261,35 @@ inline std::vector<unsigned char> toColors(ft_ctx* ctx, float gamma, long long s
     return out;
 }
 }  // namespace Image
+
+// The distance field itself.  Samples: distance per point, and where asked for the normal (SdfForm.normal sdf normalEpsilon p) and the handle of the
+// material object.Material.Color p picks.  bounded: SdfForm.tryDistance — outside the form's boundary nothing is evaluated (NaN, NaN, -1).
+namespace Field {
+struct Samples { std::vector<float> distance; std::vector<ft_vec3> normal; std::vector<int32_t> material; };
+struct Request { bool normal = false; float normalEpsilon = 0.0f; bool material = false; bool bounded = false; };
+// point (i, j, k) = origin + (i, j, k) * step per coordinate (one float32 product, one float32 sum); its results at (i * ny + j) * nz + k
+inline Samples sampleLattice(const SdfScene& scene, const ft_lattice& lattice, const Request& r = Request{}) {
+    SceneOfCall s(scene);
+    const size_t n = (size_t)lattice.nx * (size_t)lattice.ny * (size_t)lattice.nz;
+    Samples out;
+    out.distance.resize(n);
+    if (r.normal) out.normal.resize(n);
+    if (r.material) out.material.assign(n, -1);
+    s.done(ft_sample_lattice(s.ctx, s.get(), &lattice, r.normalEpsilon, r.bounded ? FT_FIELD_BOUNDED : 0u, out.distance.data(),
+                             r.normal ? out.normal.data() : nullptr, r.material ? out.material.data() : nullptr), nullptr);
+    return out;
+}
+inline Samples samplePoints(const SdfScene& scene, const std::vector<ft_vec3>& points, const Request& r = Request{}) {
+    SceneOfCall s(scene);
+    Samples out;
+    out.distance.resize(points.size());
+    if (r.normal) out.normal.resize(points.size());
+    if (r.material) out.material.assign(points.size(), -1);
+    s.done(ft_sample_points(s.ctx, s.get(), points.data(), (int64_t)points.size(), r.normalEpsilon, r.bounded ? FT_FIELD_BOUNDED : 0u, out.distance.data(),
+                            r.normal ? out.normal.data() : nullptr, r.material ? out.material.data() : nullptr), nullptr);
+    return out;
+}
+}  // namespace Field
 
 // SdfObject.tryTrace / SdfForm.tryTrace (SdfObject.fs:66-78, SdfForm.fs:93-104) over a ray buffer; hit == 0 is ValueNone
 inline std::vector<ft_object_trace_result> tryTrace(const SdfObjectV& object, const std::vector<ft_ray>& rays) {

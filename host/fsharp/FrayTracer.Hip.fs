@@ -44,6 +44,10 @@ type FtCamera =
 [<Struct; StructLayout(LayoutKind.Sequential)>]
 type FtTonemapParams = { Gamma : float32; Dither : int; Seed : uint32; BmpOrder : int }
 
+/// ft_lattice: point (i, j, k) = Origin + (i, j, k) * Step per coordinate (one float32 product, one float32 sum); results at (i * Ny + j) * Nz + k
+[<Struct; StructLayout(LayoutKind.Sequential)>]
+type FtLattice = { Origin : Vector3; Step : Vector3; Nx : int; Ny : int; Nz : int }
+
 /// ft_form_trace_result: SdfFormTraceResult voption (Types.fs:32-37), Hit = 0 is ValueNone
 [<Struct; StructLayout(LayoutKind.Sequential)>]
 type FtFormTraceResult = { Ray : Ray; Distance : float32; Hit : int }
@@ -100,6 +104,12 @@ module Native =
     [<DllImport(Lib)>] extern int ft_light_visibility_device(nativeint ctx, nativeint scene, nativeint dHits, int64 n, uint32 select, nativeint dVisIn, nativeint dVisOut)
     [<DllImport(Lib)>] extern int ft_shade_visible(nativeint ctx, nativeint scene, FtObjectTraceResult[] hits, nativeint visibility, int64 n, nativeint outRgb, FtStats& stats)
     [<DllImport(Lib)>] extern int ft_shade_visible_device(nativeint ctx, nativeint scene, nativeint dHits, nativeint dVisibility, int64 n, nativeint dOutRgb)
+    // the distance field itself: sdf.Distance, SdfForm.normal (outNormal) and the material handle (outMaterial) at the points of a buffer or of a
+    // lattice (a pinned FtLattice); any output may be 0n, not all; flags 1u = FT_FIELD_BOUNDED (SdfForm.tryDistance: NaN, NaN, -1 outside the boundary)
+    [<DllImport(Lib)>] extern int ft_sample_points(nativeint ctx, nativeint scene, Vector3[] points, int64 n, float32 normalEpsilon, uint32 flags, nativeint outDistance, nativeint outNormal, nativeint outMaterial)
+    [<DllImport(Lib)>] extern int ft_sample_points_device(nativeint ctx, nativeint scene, nativeint dPoints, int64 n, float32 normalEpsilon, uint32 flags, nativeint dDistance, nativeint dNormal, nativeint dMaterial)
+    [<DllImport(Lib)>] extern int ft_sample_lattice(nativeint ctx, nativeint scene, nativeint lattice, float32 normalEpsilon, uint32 flags, nativeint outDistance, nativeint outNormal, nativeint outMaterial)
+    [<DllImport(Lib)>] extern int ft_sample_lattice_device(nativeint ctx, nativeint scene, nativeint lattice, float32 normalEpsilon, uint32 flags, nativeint dDistance, nativeint dNormal, nativeint dMaterial)
     [<DllImport(Lib)>] extern int ft_form_try_trace(nativeint ctx, nativeint scene, Ray[] rays, int64 n, [<Out>] FtFormTraceResult[] out, FtStats& stats)
     [<DllImport(Lib)>] extern int ft_object_try_trace(nativeint ctx, nativeint scene, Ray[] rays, int64 n, [<Out>] FtObjectTraceResult[] out, FtStats& stats)
     // ray buffers in device memory (rays 16-byte aligned, 32 B each): no scratch, no copy, not synchronised; pair with ft_collect_stats
@@ -325,6 +335,19 @@ module Relight =
             out
         finally
             pinO.Free (); pinV.Free ()
+
+/// The distance field itself under a native scene handle: `scene.Object.Form.Distance` on a lattice, computed on the GPU.
+module Field =
+    /// distances of the lattice's Nx * Ny * Nz points, point (i, j, k) at (i * Ny + j) * Nz + k (ft_sample_lattice); bounded: SdfForm.tryDistance, NaN for ValueNone
+    let sampleLattice (scene : nativeint) (bounded : bool) (lattice : FtLattice) : float32[] =
+        let out : float32[] = Array.zeroCreate (lattice.Nx * lattice.Ny * lattice.Nz)
+        let pinL = GCHandle.Alloc (box lattice, GCHandleType.Pinned)
+        let pinO = GCHandle.Alloc (out, GCHandleType.Pinned)
+        try
+            Native.check (Native.ft_sample_lattice (Native.ctx.Value, scene, pinL.AddrOfPinnedObject (), 0.0f, (if bounded then 1u else 0u), pinO.AddrOfPinnedObject (), 0n, 0n)) |> ignore
+            out
+        finally
+            pinO.Free (); pinL.Free ()
 
 module Image =
     /// GPU sibling of `scene |> FrayTracer.SdfScene.trace |> FrayTracer.Image.render epsilon length imageSize camera`

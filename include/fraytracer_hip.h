@@ -27,6 +27,7 @@ extern "C" {
 #endif
 
 #define FT_ABI_VERSION 5
+#define FT_FIELD_BOUNDED 1u   /* flag bit of ft_sample_points / ft_sample_lattice ("Field sampling" below): SdfForm.tryDistance, only where SdfBoundary.isInside */
 
 typedef enum ft_status {
     FT_OK = 0,
@@ -384,6 +385,46 @@ int ft_shade_visible_device(ft_ctx*, const ft_scene*, const void* d_hits, const 
 /* scene.Object.Form.Distance at n points (+ index of the material the hit would pick, or
  * NULL).  Test/diagnostic entry: lets parity tests compare single SDF evaluations. */
 int ft_eval_distance(ft_ctx*, const ft_scene*, const ft_vec3* points, int64_t n, float* out_distance, int32_t* out_material);
+
+/* Field sampling: the distance field itself, on the device — scene.Object.Form.Distance, SdfForm.normal and the material of
+ * object.Material.Color at the points of a regular lattice or of a point buffer (SdfForm.fs:7-12, 106-112; SdfObject.fs:23-46).
+ *
+ * Lattice point (i, j, k), 0 <= i < nx, 0 <= j < ny, 0 <= k < nz, is
+ *     (origin.x + (float)i * step.x, origin.y + (float)j * step.y, origin.z + (float)k * step.z):
+ * per coordinate one float32 product, rounded, then one float32 sum, rounded — never a fused multiply-add.  Its results sit at index
+ * (i * ny + j) * nz + k of every output, so k is contiguous.  Each count is 1 .. 16777216 (so that (float)i is exact); a step may be
+ * zero or negative.  A point buffer is n x ft_vec3, 12 bytes apart; point r's results sit at index r.
+ * Distance: sdf.Distance p — the bits ft_eval_distance gives for the same point.
+ * Normal (asked for with out_normal): SdfForm.normal sdf normal_epsilon p, i.e. four evaluations in the order
+ *     dx = D(p.x + e, p.y, p.z), dy = D(p.x, p.y + e, p.z), dz = D(p.x, p.y, p.z + e), d = D(p);
+ *     g = (dx, dy, dz) - (d, d, d);  n = g / sqrt((g.x * g.x + g.y * g.y) + g.z * g.z), three true divisions;
+ * NaN where the reference gives NaN (g = 0, an infinite distance).  The distance written is the centre evaluation d: the same bits
+ * with or without the normal.  normal_epsilon is read only when a normal is asked for.
+ * Material: the handle of the ft_material_* that object.Material.Color p picks — the argmin of SdfObject.union, the first object's
+ * material under subtract and intersect; the rule of ft_object_try_trace_device's d_material.  There is no miss here: it is always a
+ * handle (-1 only for an object without a material).
+ * flags: FT_FIELD_BOUNDED is SdfForm.tryDistance: a point is evaluated only where SdfBoundary.isInside scene.Object.Form.Boundary p,
+ * i.e. (dx * dx + dy * dy) + dz * dz < Radius * Radius with d = p - Boundary.Center in float32; elsewhere nothing is evaluated, distance
+ * and normal are NaN and the material is -1.
+ * Any output may be NULL, but not all three.  There are no ft_stats: NaN and infinity are in the outputs themselves.
+ * Refusals, all made before the device is asked for: FT_ERR_INVALID for NULL where none is allowed, n < 0, a count < 1 or > 16777216,
+ * unknown flag bits, a misaligned device buffer, identical pointers; FT_ERR_UNSUPPORTED for n or nx * ny * nz >= 0xFFFF0000 (and for a
+ * scene whose LDS footprint no kernel fits); n = 0: FT_OK, nothing launched; then FT_ERR_NO_DEVICE on a host-only context.
+ * The host forms stage through the context's scratch (12 B per point of a point buffer — the lattice form uploads nothing — and 4 + 12
+ * + 4 B per point for the outputs asked for) and synchronise.
+ * FT_OPT_CULL, FT_OPT_CARVED, FT_OPT_LAZY_UNION and FT_OPT_MAX_BLOCKS_PER_CU apply as to a trace launch and never change an output bit. */
+typedef struct ft_lattice { ft_vec3 origin; ft_vec3 step; int32_t nx, ny, nz; } ft_lattice;   /* 36 B */
+int ft_sample_points(ft_ctx*, const ft_scene*, const ft_vec3* points, int64_t n, float normal_epsilon, uint32_t flags,
+                     float* out_distance, ft_vec3* out_normal, int32_t* out_material);
+int ft_sample_lattice(ft_ctx*, const ft_scene*, const ft_lattice*, float normal_epsilon, uint32_t flags,
+                      float* out_distance, ft_vec3* out_normal, int32_t* out_material);
+/* The same in device memory, under the contract of the other *_device forms: launched on the context's stream and NOT synchronised, no
+ * scratch, no copy.  Every buffer 4-byte aligned (points are 12 B apart; d_normal is n x 3 float32, d_material n x int32).  Input and
+ * output must not overlap: only identical pointers are detected (FT_ERR_INVALID). */
+int ft_sample_points_device(ft_ctx*, const ft_scene*, const void* d_points, int64_t n, float normal_epsilon, uint32_t flags,
+                            void* d_distance, void* d_normal, void* d_material);
+int ft_sample_lattice_device(ft_ctx*, const ft_scene*, const ft_lattice*, float normal_epsilon, uint32_t flags,
+                             void* d_distance, void* d_normal, void* d_material);
 
 /* Single-process multi-GPU form (what an F# host would call): the flattened scene is
  * re-uploaded to each further device with ft_scene_clone, every device renders its column
