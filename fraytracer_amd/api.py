@@ -551,6 +551,21 @@ def is_device_tensor(x):
     return all(hasattr(x, k) for k in ("data_ptr", "is_cuda", "shape", "dtype", "is_contiguous")) and bool(x.is_cuda)
 
 
+def _buffer(x):
+    """the buffer behind a PixelHits (its records), an array-like or a device tensor: a device tensor or a numpy array as it is, anything else
+    as a numpy array"""
+    x = x.records if isinstance(x, PixelHits) else x
+    return x if is_device_tensor(x) or isinstance(x, np.ndarray) else np.asarray(x)
+
+
+def _empty(like, shape, kind="float32"):
+    """An uninitialised output of `shape`: a numpy array where `like` is None, else a tensor of like's device (like.new_empty).  kind: "float32",
+    "int32", or "mask" for visibility masks: uint32 in numpy, the same bits as int32 in torch, whose uint32 has no arithmetic."""
+    if like is None:
+        return np.empty(shape, {"float32": np.float32, "int32": np.int32, "mask": np.uint32}[kind])
+    return like.new_empty(shape) if kind == "float32" else like.new_empty(shape, dtype=_torch_int32(like))
+
+
 def check_device_rays(t):
     """n of a device ray buffer: float32, shape [n, 8], contiguous — anything else is a ValueError (no silent copy on the device)"""
     if str(t.dtype).rsplit(".", 1)[-1] != "float32":
@@ -892,20 +907,21 @@ class DeviceScene:
 
     # ---- ray buffers: host arrays (numpy) or device tensors ------------------------------------------------------------
     def _trace_buffer(self, rays, host_fn, device_fn, widths):
-        """The one place a ray-buffer method decides between a host array and a device tensor (see is_device_tensor) -> (outputs, stats).
-        widths: per output of the C call its row width — float32 [n, w]; 0: int32 [n]; None: not asked for.  A host array goes through
-        host_fn (the ft_* host form); a device tensor (checked: float32 [n, 8], contiguous) is traced where it lies by device_fn on the
-        caller's current stream, the outputs are tensors of its device and stats is None: fetch them with collect_stats() when needed."""
-        if is_device_tensor(rays):
-            n = check_device_rays(rays)
-            outs = [None if w is None else rays.new_empty((n, w)) if w else rays.new_empty((n,), dtype=_torch_int32(rays)) for w in widths]
-            with self.device.on_current_stream(rays):
-                device_fn(rays.data_ptr(), n, *(None if o is None else o.data_ptr() for o in outs))
-            return outs, None
-        rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)
-        n = rays.shape[0]
-        outs = [None if w is None else np.empty((n, w), np.float32) if w else np.empty((n,), np.int32) for w in widths]
-        return outs, self._call(host_fn, _hptr(rays), n, *map(_hptr, outs))
+        """Where a ray-buffer method decides between a host array and a device tensor (see is_device_tensor) -> (outputs, stats); the record
+        methods have _record_form, the field methods _field.  widths: per output of the C call its row width — float32 [n, w]; 0: int32 [n];
+        None: not asked for.  A host array goes through host_fn (the ft_* host form), n = 0 included; a device tensor (checked: float32 [n, 8],
+        contiguous) is traced where it lies by device_fn on the caller's current stream, n = 0 included, the outputs are tensors of its device
+        and stats is None: fetch them with collect_stats() when needed."""
+        like = rays if is_device_tensor(rays) else None
+        if like is None:
+            rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)
+        n = rays.shape[0] if like is None else check_device_rays(rays)
+        outs = [None if w is None else _empty(like, (n, w)) if w else _empty(like, (n,), "int32") for w in widths]
+        if like is None:
+            return outs, self._call(host_fn, _hptr(rays), n, *map(_hptr, outs))
+        with self.device.on_current_stream(rays):
+            device_fn(rays.data_ptr(), n, *(None if o is None else o.data_ptr() for o in outs))
+        return outs, None
 
     def trace_rays(self, rays):
         """SdfScene.trace over n rays given as float32 [n, 8] (Origin, Direction, Length, Epsilon) -> (float32 [n, 3], stats).
@@ -963,22 +979,9 @@ class DeviceScene:
         shares this scene's Object (see relight) shade to what this scene's trace_rays / render gives, bit for bit, without a primary march;
         records are data and may be edited first (colour, normal; hit = 0 gives the background).  A device tensor is shaded where it lies
         by ft_shade_hits_device on the caller's current stream, the colours are a tensor of its device and stats is None."""
-        rec = hits.records if isinstance(hits, PixelHits) else hits
-        if not is_device_tensor(rec) and not isinstance(rec, np.ndarray):
-            rec = np.asarray(rec)
-        lead = check_hit_records(rec)
-        n = int(np.prod(lead, dtype=np.int64))
-        if is_device_tensor(rec):
-            out = rec.new_empty(lead + (3,))
-            if n:
-                with self.device.on_current_stream(rec):
-                    self.shade_hits_device(rec.data_ptr(), n, out.data_ptr())
-            return out, None
-        rec = np.ascontiguousarray(rec)
-        out = np.empty(lead + (3,), np.float32)
-        if n == 0:
-            return out, _lib.Stats().as_dict()
-        return out, self._call(lib.ft_shade_hits, _hptr(rec), n, _hptr(out))
+        rec, lead, n = self._records(hits)
+        return self._record_form(rec, n, lead + (3,), "float32", lambda out: self._call(lib.ft_shade_hits, _hptr(rec), n, out),
+                                 lambda out: self.shade_hits_device(rec.data_ptr(), n, out))
 
     def shade_hits_device(self, d_hits_ptr, n, d_out_ptr):
         """asynchronous ft_shade_hits_device: n records (64 B each, 16-byte aligned) at d_hits_ptr -> n x 3 float32 colours at d_out_ptr
@@ -988,12 +991,33 @@ class DeviceScene:
     # ---- light visibility masks: the shadow marches kept as bits, and shading from the bits ------------------------------
     @staticmethod
     def _records(hits):
-        """the record buffer of a PixelHits, an array or a device tensor -> (buffer, leading shape, record count)"""
-        rec = hits.records if isinstance(hits, PixelHits) else hits
-        if not is_device_tensor(rec) and not isinstance(rec, np.ndarray):
-            rec = np.asarray(rec)
+        """the record buffer of a PixelHits, an array or a device tensor (a host array made contiguous) -> (buffer, leading shape, record count)"""
+        rec = _buffer(hits)
         lead = check_hit_records(rec)
-        return rec, lead, int(np.prod(lead, dtype=np.int64))
+        return rec if is_device_tensor(rec) else np.ascontiguousarray(rec), lead, int(np.prod(lead, dtype=np.int64))
+
+    @staticmethod
+    def _masks(m, rec, lead, what):
+        """visibility masks for the records `rec`: checked (check_visibility) and lying where the records lie; a host array made contiguous"""
+        m = _buffer(m)
+        if is_device_tensor(rec) != is_device_tensor(m):
+            raise ValueError(f"{what}: must lie where the records lie (device tensor or numpy array)")
+        check_visibility(m, lead, what)
+        return m if is_device_tensor(m) else np.ascontiguousarray(m)
+
+    def _record_form(self, rec, n, shape, kind, host, device):
+        """Where a record method (shade_hits, light_visibility, shade_visible) decides between host arrays and device tensors -> (output, stats).
+        The output (_empty: shape, kind) lies where the n records `rec` lie.  Device tensor: device(output address) launches on the caller's
+        current stream, only if there is a record, and stats is None.  Host array: host(output pointer) calls the ft_* host form and returns
+        its stats; without a record there is no call and the stats are zero."""
+        if is_device_tensor(rec):
+            out = _empty(rec, shape, kind)
+            if n:
+                with self.device.on_current_stream(rec):
+                    device(out.data_ptr())
+            return out, None
+        out = _empty(None, shape, kind)
+        return out, host(_hptr(out)) if n else _lib.Stats().as_dict()
 
     def light_visibility(self, hits, select=None, previous=None):
         """ft_light_visibility: one shadow march per selected light and record of `hits` (a PixelHits, float32 [..., 16] or a device tensor,
@@ -1004,24 +1028,9 @@ class DeviceScene:
         a tensor), on the caller's current stream, and stats None."""
         rec, lead, n = self._records(hits)
         sel = 0xFFFFFFFF if select is None else int(select) & 0xFFFFFFFF
-        if previous is not None:
-            if not is_device_tensor(previous) and not isinstance(previous, np.ndarray):
-                previous = np.asarray(previous)
-            if is_device_tensor(rec) != is_device_tensor(previous):
-                raise ValueError("previous: must lie where the records lie (device tensor or numpy array)")
-            check_visibility(previous, lead, "previous")
-        if is_device_tensor(rec):
-            out = rec.new_empty(lead, dtype=_torch_int32(rec))
-            if n:
-                with self.device.on_current_stream(rec):
-                    self.light_visibility_device(rec.data_ptr(), n, out.data_ptr(), sel, None if previous is None else previous.data_ptr())
-            return out, None
-        rec = np.ascontiguousarray(rec)
-        prev = None if previous is None else np.ascontiguousarray(previous)
-        out = np.empty(lead, np.uint32)
-        if n == 0:
-            return out, _lib.Stats().as_dict()
-        return out, self._call(lib.ft_light_visibility, _hptr(rec), n, sel, _hptr(prev), _hptr(out))
+        prev = None if previous is None else self._masks(previous, rec, lead, "previous")
+        return self._record_form(rec, n, lead, "mask", lambda out: self._call(lib.ft_light_visibility, _hptr(rec), n, sel, _hptr(prev), out),
+                                 lambda out: self.light_visibility_device(rec.data_ptr(), n, out, sel, None if prev is None else prev.data_ptr()))
 
     def light_visibility_device(self, d_hits_ptr, n, d_vis_out_ptr, select=0xFFFFFFFF, d_vis_in_ptr=None):
         """asynchronous ft_light_visibility_device: n records (64 B each, 16-byte aligned) at d_hits_ptr -> n uint32 masks at d_vis_out_ptr;
@@ -1034,22 +1043,9 @@ class DeviceScene:
         stats).  No march runs: a memory pass.  Equal bit for bit to shade_hits / trace_rays under this scene; records may be recoloured first.
         A mask is data: a set bit adds its light whatever the cosine.  Device records take an int32 mask tensor and give a tensor; stats None."""
         rec, lead, n = self._records(hits)
-        if not is_device_tensor(visibility) and not isinstance(visibility, np.ndarray):
-            visibility = np.asarray(visibility)
-        if is_device_tensor(rec) != is_device_tensor(visibility):
-            raise ValueError("visibility: must lie where the records lie (device tensor or numpy array)")
-        check_visibility(visibility, lead)
-        if is_device_tensor(rec):
-            out = rec.new_empty(lead + (3,))
-            if n:
-                with self.device.on_current_stream(rec):
-                    self.shade_visible_device(rec.data_ptr(), visibility.data_ptr(), n, out.data_ptr())
-            return out, None
-        rec, vis = np.ascontiguousarray(rec), np.ascontiguousarray(visibility)
-        out = np.empty(lead + (3,), np.float32)
-        if n == 0:
-            return out, _lib.Stats().as_dict()
-        return out, self._call(lib.ft_shade_visible, _hptr(rec), _hptr(vis), n, _hptr(out))
+        vis = self._masks(visibility, rec, lead, "visibility")
+        return self._record_form(rec, n, lead + (3,), "float32", lambda out: self._call(lib.ft_shade_visible, _hptr(rec), _hptr(vis), n, out),
+                                 lambda out: self.shade_visible_device(rec.data_ptr(), vis.data_ptr(), n, out))
 
     def shade_visible_device(self, d_hits_ptr, d_visibility_ptr, n, d_out_ptr):
         """asynchronous ft_shade_visible_device: n records and n uint32 masks -> n x 3 float32 colours (pointers as int; records 16-byte
@@ -1058,23 +1054,21 @@ class DeviceScene:
 
     # ---- the distance field itself: lattices and point buffers ------------------------------------------------------------
     def _field(self, lead, like, launch_host, launch_device, normal_epsilon, distance, material, bounded):
-        """The one place a field method decides between host arrays and device tensors -> FieldSamples.  like: None (numpy outputs through
-        launch_host) or a device tensor, whose device the outputs are allocated on and whose current stream launch_device runs on."""
+        """Where a field method decides between host arrays and device tensors -> FieldSamples.  like: None (numpy outputs through launch_host,
+        which is called whatever the point count: ft_sample_points itself has nothing to do for none) or a device tensor, whose device the
+        outputs are allocated on and whose current stream launch_device runs on, only if there is a point."""
         normal = normal_epsilon is not None
         if not (distance or normal or material):
             raise ValueError("field: no output asked for")
         eps = float(normal_epsilon) if normal else 0.0
         flags = _lib.FT_FIELD_BOUNDED if bounded else 0
-        if like is not None:
-            outs = (like.new_empty(lead) if distance else None, like.new_empty(lead + (3,)) if normal else None,
-                    like.new_empty(lead, dtype=_torch_int32(like)) if material else None)
-            if int(np.prod(lead, dtype=np.int64)):
-                with self.device.on_current_stream(like):
-                    launch_device(eps, flags, *(None if o is None else o.data_ptr() for o in outs))
-        else:
-            outs = (np.empty(lead, np.float32) if distance else None, np.empty(lead + (3,), np.float32) if normal else None,
-                    np.empty(lead, np.int32) if material else None)
+        outs = (_empty(like, lead) if distance else None, _empty(like, lead + (3,)) if normal else None,
+                _empty(like, lead, "int32") if material else None)
+        if like is None:
             launch_host(eps, flags, *map(_hptr, outs))
+        elif int(np.prod(lead, dtype=np.int64)):
+            with self.device.on_current_stream(like):
+                launch_device(eps, flags, *(None if o is None else o.data_ptr() for o in outs))
         return FieldSamples(*outs, materials=self.materials)
 
     def sample_points(self, points, normal_epsilon=None, material=False, bounded=False, distance=True):

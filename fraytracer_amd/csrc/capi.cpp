@@ -3,6 +3,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -265,8 +266,10 @@ bool libmLaunch(const ft_ctx* c, const ft_scene* s) { return c->optMath != FT_MA
 //   * ft_shade_hits (shade) follows the same rules with the *_shade twins: no EXTENSION launch exists, so a carved union leaves the carved walk
 //     only with FT_OPT_CARVED = 0 or glibc math, exactly where a ft_trace_rays of the scene does.  ft_light_visibility (shade = 2) is the same
 //     marches with another result, so the same rules with the *_vis twins.
-struct TracePlan { unsigned variant; bool libm, cullRows; uint32_t nSlots; size_t lds; };
-int planTrace(const ft_ctx* c, const ft_scene* s, bool ext, unsigned shade, TracePlan& p) {
+//   * a field launch (launchField: ft_sample_points, ft_sample_lattice) runs the same evaluators, so it plans like a plain trace launch (ext = false,
+//     shade = 0) and looks its kernel up by the plan's variant and arithmetic (kernels.hip FT_FIELD_BUILDS, which has no EXTENSION build either).
+struct KernelPlan { unsigned variant; bool libm, cullRows; uint32_t nSlots; size_t lds; };
+int planTrace(const ft_ctx* c, const ft_scene* s, bool ext, unsigned shade, KernelPlan& p) {
     const bool hasCull = s->dev.cullPc != 0xffffffffu;
     if (shade && ext) return setErr(FT_ERR_INVALID, "internal: ft_shade_hits has no EXTENSION build");
     p.libm = libmLaunch(c, s);
@@ -307,6 +310,31 @@ int acquireEvents(ft_ctx* c, hipEvent_t& a, hipEvent_t& b) {
     return FT_OK;
 }
 
+// One timed launch on `stream`, stated once: the oldest pending pairs are folded, `launch` (a callable that returns the launch's hipError_t; `what`
+// names it in a failure's message) runs between the two events of a pair, and the pair joins the pending ones that ft_collect_stats adds up.  Once
+// the pair is acquired a failure returns it to the pool.
+template <class Launch> int timedLaunch(ft_ctx* c, hipStream_t stream, const char* what, Launch launch) {
+    int rc = foldOldestEvents(c); if (rc) return rc;
+    hipEvent_t e0, e1;
+    if ((rc = acquireEvents(c, e0, e1))) return rc;
+    const char* at = "hipEventRecord";
+    hipError_t e = hipEventRecord(e0, stream);
+    if (e == hipSuccess && (e = launch()) != hipSuccess) at = what;
+    if (e == hipSuccess) e = hipEventRecord(e1, stream);
+    if (e != hipSuccess) { c->eventPool.emplace_back(e0, e1); return hipFail(e, at); }
+    c->events.emplace_back(e0, e1);
+    return FT_OK;
+}
+
+// The workgroups per CU a launch plans with, from what the occupancy query found for the kernel (`kernel` names it in the refusal): none is refused,
+// more than 8 are not used, and FT_OPT_MAX_BLOCKS_PER_CU (experiments) caps them
+int clampPerCU(const ft_ctx* c, const char* kernel, int& perCU) {
+    if (perCU < 1) return setErr(FT_ERR_UNSUPPORTED, std::string("the ") + kernel + " kernel does not fit a compute unit with this scene's LDS footprint");
+    perCU = std::min(perCU, 8);
+    if (c->optMaxBlocksPerCU > 0) perCU = std::min(perCU, c->optMaxBlocksPerCU);
+    return FT_OK;
+}
+
 // FT_OPT_ORDER: the slot of this launch with room for its tiles, nullptr where it cannot be had (the launch then runs in index order and records nothing)
 TileOrderSlot* tileOrderSlot(const ft_scene* s, int lane, uint32_t nTiles) {
     TileOrderSlot& t = s->orderSlots[lane];
@@ -329,7 +357,7 @@ TileOrderSlot* tileOrderSlot(const ft_scene* s, int lane, uint32_t nTiles) {
 int launchTrace(ft_ctx* c, const ft_scene* s, FtRenderArgs& a, int lane = 0) {
     hipStream_t stream = lane ? c->lane1 : c->stream;
     uint32_t* counter = c->dCounter + (lane ? 16 : 0);
-    TracePlan plan;
+    KernelPlan plan;
     int rc = planTrace(c, s, a.ext != 0u, a.shade, plan); if (rc) return rc;
     const unsigned variant = plan.variant;
     // what decides the kernel (ft_kernels.h ft_trace_key; a.ext, a.views and a.shade are the caller's), then the key: the occupancy query here and the
@@ -341,10 +369,8 @@ int launchTrace(ft_ctx* c, const ft_scene* s, FtRenderArgs& a, int lane = 0) {
     const FtTraceKey key = ft_trace_key(a);
     int perCU = 0;
     HIP_TRY(ft_trace_occupancy(key, plan.lds, &perCU));
-    if (perCU < 1) return setErr(FT_ERR_UNSUPPORTED, "the trace kernel does not fit a compute unit with this scene's LDS footprint");
-    perCU = std::min(perCU, 8);
-    if (c->optMaxBlocksPerCU > 0) perCU = std::min(perCU, c->optMaxBlocksPerCU);       // FT_OPT_MAX_BLOCKS_PER_CU (experiments)
-    else if (variant != 1u) {
+    if ((rc = clampPerCU(c, "trace", perCU))) return rc;
+    if (c->optMaxBlocksPerCU <= 0 && variant != 1u) {
         // Small frames: the job queue can only even out the load while there are several tiles per resident wave, and the grid-union kernels lose little
         // throughput at half their occupancy (the 4000^2 Program.fs frame: 5.4 ms at 7 workgroups per CU, 6.0 at 4).  With about as many tiles as waves
         // every tile is handed out at once, the heavy ones sit several deep on some SIMDs while others idle, and the frame lasts as long as the
@@ -443,13 +469,7 @@ int launchTrace(ft_ctx* c, const ft_scene* s, FtRenderArgs& a, int lane = 0) {
         slot->key = k; slot->keyed = true; slot->hasOrder = false; slot->usedOrder = a.tileOrder != nullptr;
     }
     HIP_TRY(hipMemsetAsync(counter, 0, sizeof(uint32_t), stream));
-    hipEvent_t e0, e1;
-    if ((rc = foldOldestEvents(c))) return rc;
-    if ((rc = acquireEvents(c, e0, e1))) return rc;
-    HIP_TRY(hipEventRecord(e0, stream));
-    HIP_TRY(ft_launch_trace(&a, blocks, plan.lds, stream));
-    HIP_TRY(hipEventRecord(e1, stream));
-    c->events.emplace_back(e0, e1);
+    if ((rc = timedLaunch(c, stream, "ft_launch_trace", [&] { return ft_launch_trace(&a, blocks, plan.lds, stream); }))) return rc;
     if (slot && c->optOrder == 1) {                        // behind the frame on its own stream: no synchronisation, nothing comes back to the host
         // the frame is launched whatever becomes of its order: a failure here only leaves the next frame in index order
         if (ft_launch_tile_order(slot->cost, a.nJobs >> 6, c->orderNum, c->orderDen, slot->order, slot->work, stream) == hipSuccess) slot->hasOrder = true;
@@ -1006,50 +1026,63 @@ bool pinForCall(ft_ctx* c, void* p, size_t bytes) {
     return false;
 }
 
-// The host forms' output ritual, once: [input | colours | records | material plane] in the context's scratch, each part asked for on a 256-byte
-// boundary; the launch writes there; every part is copied to the caller's buffer behind it on the context's stream; finish() ends the call.
+// The host forms' staging ritual, once: [input | part 0 | part 1 | part 2] in the context's scratch, each part that is asked for on a 256-byte
+// boundary; upload() brings the input up, the launch writes the parts, copyOut() queues every part to the caller's buffer behind it on the context's
+// stream, finish() ends the call.  A part is a host destination (NULL: not asked for) and its bytes per item: the frame and ray-buffer forms have
+// colours, records and the material plane (outputParts), the field forms distance, normal and material.
 // A form that bounds its scratch plans one launch group and calls copyOut once per group.
 // pin: page-lock the caller's buffers for the call while the GPU renders the first group, so that the copies run at link rate.  The views forms
 // pin (like ft_render and ft_render_colors); ft_render_hits and the ray-buffer forms never did: whether they should is a measurement to make.
+struct HostPart { void* host; size_t stride; };
+using HostParts = std::array<HostPart, 3>;
 class HostStaging {
 public:
-    HostStaging(ft_ctx* c, const char* what, const Outputs& host, size_t rgbStride, bool pin)
-        : c_(c), what_(what), host_{host.rgb, host.hits, host.material}, stride_{rgbStride, 64, 4}, pin_(pin) {}
-    // scratch for `count` pixels or rays behind inputBytes of input
+    HostStaging(ft_ctx* c, const char* what, const HostParts& parts, bool pin) : c_(c), what_(what), parts_(parts), pin_(pin) {}
+    // scratch for `count` pixels, rays, records or points behind inputBytes of input
     int plan(size_t inputBytes, size_t count) {
         size_t end = inputBytes;
-        for (int i = 0; i < 3; ++i) { off_[i] = align256(end); end = off_[i] + (host_[i] ? count * stride_[i] : 0); }
+        for (int i = 0; i < 3; ++i) { off_[i] = align256(end); end = off_[i] + (parts_[i].host ? count * parts_[i].stride : 0); }
         return ensureScratch(c_, end);
     }
-    void* input() const { return c_->scratch; }
+    void* input(size_t offset = 0) const { return static_cast<unsigned char*>(c_->scratch) + offset; }
+    // `bytes` of the caller's input to the input area at `offset`, on the context's stream
+    int upload(size_t offset, const void* src, size_t bytes) {
+        HIP_TRY(hipMemcpyAsync(input(offset), src, bytes, hipMemcpyHostToDevice, c_->stream));
+        return FT_OK;
+    }
+    void* part(int i) const { return parts_[i].host ? static_cast<unsigned char*>(c_->scratch) + off_[i] : nullptr; }
     Outputs dev() const { return Outputs{part(0), part(1), part(2)}; }
     bool ok() const { return !rc_ && err_ == hipSuccess; }
     // behind a launch that returned rc: `count` items from the scratch to the caller's buffers at item `first`; `total`: the items of the whole call
     void copyOut(int rc, size_t first, size_t count, size_t total) {
         rc_ = rc;
         if (!rc_ && pin_ && first == 0)                                // the GPU is rendering: page-lock the destinations meanwhile
-            for (int i = 0; i < 3; ++i) if (host_[i]) pinned_[i] = pinForCall(c_, host_[i], total * stride_[i]);
+            for (int i = 0; i < 3; ++i) if (parts_[i].host) pinned_[i] = pinForCall(c_, parts_[i].host, total * parts_[i].stride);
         for (int i = 0; i < 3 && ok(); ++i)
-            if (host_[i]) err_ = hipMemcpyAsync(static_cast<unsigned char*>(host_[i]) + first * stride_[i], part(i), count * stride_[i], hipMemcpyDeviceToHost, c_->stream);
+            if (parts_[i].host)
+                err_ = hipMemcpyAsync(static_cast<unsigned char*>(parts_[i].host) + first * parts_[i].stride, part(i), count * parts_[i].stride, hipMemcpyDeviceToHost, c_->stream);
     }
     // nothing of the call is left in flight, whatever happened (the scratch and the caller's buffers are reused); what was pinned here is
-    // released; then the launch's error, the copies', the synchronisation's, and at last the statistics
-    int finish(ft_stats* st) {
+    // released; then the launch's error, the copies', the synchronisation's.  The launches' event pairs stay pending: collecting is the next step
+    // of a form that returns statistics (finish(st)), and not a step of one that does not (the field forms)
+    int finish() {
         const hipError_t se = hipStreamSynchronize(c_->stream);
-        for (int i = 0; i < 3; ++i) if (pinned_[i]) (void)hipHostUnregister(host_[i]);
+        for (int i = 0; i < 3; ++i) if (pinned_[i]) (void)hipHostUnregister(parts_[i].host);
         if (rc_) return rc_;
         if (err_ != hipSuccess) return hipFail(err_, (std::string(what_) + " host output").c_str());
         if (se != hipSuccess) return hipFail(se, what_);
-        return ft_collect_stats(c_, st);
+        return FT_OK;
     }
+    int finish(ft_stats* st) { const int rc = finish(); return rc ? rc : ft_collect_stats(c_, st); }
 private:
-    void* part(int i) const { return host_[i] ? static_cast<unsigned char*>(c_->scratch) + off_[i] : nullptr; }
     ft_ctx* c_; const char* what_;
-    void* host_[3]; size_t stride_[3]; bool pin_;
+    HostParts parts_; bool pin_;
     size_t off_[3] = {0, 0, 0};
     bool pinned_[3] = {false, false, false};
     int rc_ = FT_OK; hipError_t err_ = hipSuccess;
 };
+// the parts of a frame or ray-buffer form: colours (SdfForm.tryTrace: its 40-byte results), 64-byte records, the 4-byte material plane or masks
+HostParts outputParts(const Outputs& host, size_t rgbStride = 12) { return HostParts{{{host.rgb, rgbStride}, {host.hits, 64}, {host.material, 4}}}; }
 
 // The frame of `p` rendered into the context's scratch buffer in column chunks on the two render lanes (the drain of one chunk
 // overlaps the start of the next); chunk i's completion is syncEvents[2 + i].  c0 receives the chunk boundaries (columns).
@@ -1132,7 +1165,7 @@ int ft_render_hits(ft_ctx* c, const ft_scene* s, const ft_camera* cam, const ft_
     if ((rc = checkOutputs(host, false))) return rc;
     if ((rc = checkParams(p))) return rc;
     const size_t px = (size_t)p->n_columns * (size_t)p->height;
-    HostStaging stage(c, "ft_render_hits", host, 12, false);
+    HostStaging stage(c, "ft_render_hits", outputParts(host), false);
     if ((rc = stage.plan(0, px))) return rc;
     stage.copyOut(launchFrame(c, s, FrameRequest{cam, 1, p, stage.dev()}), 0, px, px);
     return stage.finish(st);
@@ -1145,7 +1178,7 @@ int ft_render_views(ft_ctx* c, const ft_scene* s, const ft_camera* cameras, int3
     int rc = checkViews(c, cameras, n, p, host); if (rc) return rc;
     if (n == 1) return ft_render(c, s, cameras, p, out, st);           // exactly ft_render (its column-chunk pipeline included)
     const size_t px = (size_t)p->n_columns * (size_t)p->height;
-    HostStaging stage(c, "ft_render_views", host, 12, true);
+    HostStaging stage(c, "ft_render_views", outputParts(host), true);
     if ((rc = stage.plan(0, (size_t)n * px))) return rc;
     stage.copyOut(launchFrame(c, s, FrameRequest{cameras, n, p, stage.dev()}), 0, (size_t)n * px, (size_t)n * px);
     return stage.finish(st);
@@ -1164,7 +1197,7 @@ int ft_render_views_hits(ft_ctx* c, const ft_scene* s, const ft_camera* cameras,
     if (!host.extra()) return ft_render_views(c, s, cameras, n, p, out_rgb, st);                      // the frames alone: staged as a whole batch
     if (n == 1) return ft_render_hits(c, s, cameras, p, out_rgb, out_hits, out_material, st);         // exactly ft_render_hits
     const size_t px = (size_t)p->n_columns * (size_t)p->height;
-    HostStaging stage(c, "ft_render_views_hits", host, 12, true);
+    HostStaging stage(c, "ft_render_views_hits", outputParts(host), true);
     if ((rc = stage.plan(0, (size_t)std::min<int32_t>(n, FT_MAX_VIEWS) * px))) return rc;
     for (int32_t k0 = 0; k0 < n && stage.ok(); k0 += FT_MAX_VIEWS) {
         const int32_t m = std::min<int32_t>(FT_MAX_VIEWS, n - k0);
@@ -1298,9 +1331,9 @@ int traceRayBuffer(ft_ctx* c, const ft_scene* s, const void* rays, int64_t n, Ra
     if (!s || s->ctx != c || !rays || !host.any() || n < 0) return setErr(FT_ERR_INVALID, "bad argument");
     if (n == 0) { if (st) memset(st, 0, sizeof(*st)); return FT_OK; }
     if (n >= 0xFFFF0000ll) return setErr(FT_ERR_UNSUPPORTED, "more than 2^32 rays in one call");
-    HostStaging stage(c, "ray buffer", host, kind == RayKind::Form ? sizeof(ft_form_trace_result) : 12, false);
+    HostStaging stage(c, "ray buffer", outputParts(host, kind == RayKind::Form ? sizeof(ft_form_trace_result) : 12), false);
     if ((rc = stage.plan(inBytes, (size_t)n))) return rc;
-    HIP_TRY(hipMemcpyAsync(stage.input(), rays, inBytes, hipMemcpyHostToDevice, c->stream));
+    if ((rc = stage.upload(0, rays, inBytes))) return rc;
     stage.copyOut(launchRayBuffer(c, s, stage.input(), n, kind, stage.dev()), 0, (size_t)n, (size_t)n);
     return stage.finish(st);
 }
@@ -1335,60 +1368,45 @@ int ft_trace_rays_hits(ft_ctx* c, const ft_scene* s, const ft_ray* rays, int64_t
 }
 
 // ---- ft_shade_hits: hit records shaded under the scene's lights (SdfScene.fs:11-28) ------------------------------------
-// Everything that can be refused without a device is refused first, the device is asked for last (like the views forms): the statuses do not
-// depend on the context having a GPU.  *nothing: n = 0, FT_OK with nothing to do.
-static int checkShade(const ft_ctx* c, const ft_scene* s, const void* hits, int64_t n, const void* out, bool deviceMemory, bool* nothing) {
+// The one check of the three record forms (ft_shade_hits, ft_light_visibility, ft_shade_visible).  Everything that can be refused without a device
+// is refused first, the device is asked for last (like the views forms): the statuses do not depend on the context having a GPU.
+// `masks` and what they are to the call: ft_shade_hits has none; ft_light_visibility's vis_in may be NULL and may be its output vis_out (an update in
+// place); ft_shade_visible needs its visibility and refuses to shade into it.  `out`: the colours, or vis_out.  A visibility mask has 32 bits: a scene
+// with more lights is refused by the two calls that have masks.  *nothing: n = 0, FT_OK with nothing to do.
+enum class Masks { None, Updated, Read };
+static int checkRecords(const char* what, Masks use, const ft_ctx* c, const ft_scene* s, const void* hits, int64_t n, const void* masks, const void* out,
+                        bool deviceMemory, bool* nothing) {
     *nothing = false;
     if (!c) return setErr(FT_ERR_INVALID, "null context");
-    if (!s || s->ctx != c || !hits || !out || n < 0) return setErr(FT_ERR_INVALID, "bad argument (scene must belong to this context)");
+    if (!s || s->ctx != c || !hits || !out || (use == Masks::Read && !masks) || n < 0) return setErr(FT_ERR_INVALID, "bad argument (scene must belong to this context)");
     if (deviceMemory) {
-        if (reinterpret_cast<uintptr_t>(hits) & 15u) return setErr(FT_ERR_INVALID, "ft_shade_hits_device: the hit records must be 16-byte aligned");
-        if (reinterpret_cast<uintptr_t>(out) & 3u) return setErr(FT_ERR_INVALID, "ft_shade_hits_device: the colours must be 4-byte aligned");
+        if (reinterpret_cast<uintptr_t>(hits) & 15u) return setErr(FT_ERR_INVALID, std::string(what) + "_device: the hit records must be 16-byte aligned");
+        if ((reinterpret_cast<uintptr_t>(masks) | reinterpret_cast<uintptr_t>(out)) & 3u)
+            return setErr(FT_ERR_INVALID, std::string(what) + (use == Masks::None ? "_device: the colours must be 4-byte aligned" : "_device: the masks and the colours must be 4-byte aligned"));
     }
-    if (hits == out) return setErr(FT_ERR_INVALID, "ft_shade_hits: input and output must not overlap");
+    if (hits == out || (use == Masks::Read && masks == out)) return setErr(FT_ERR_INVALID, std::string(what) + ": input and output must not overlap");
     if (n >= 0xFFFF0000ll) return setErr(FT_ERR_UNSUPPORTED, "more than 2^32 records in one call");
+    if (use != Masks::None && s->dev.nLights > 32u) return setErr(FT_ERR_UNSUPPORTED, "a visibility mask holds 32 lights; the scene has " + std::to_string(s->dev.nLights));
     *nothing = n == 0;
     return FT_OK;
 }
 int ft_shade_hits_device(ft_ctx* c, const ft_scene* s, const void* d_hits, int64_t n, void* d_out_rgb) {
     bool nothing;
-    int rc = checkShade(c, s, d_hits, n, d_out_rgb, true, &nothing); if (rc || nothing) return rc;
+    int rc = checkRecords("ft_shade_hits", Masks::None, c, s, d_hits, n, nullptr, d_out_rgb, true, &nothing); if (rc || nothing) return rc;
     return launchRayBuffer(c, s, d_hits, n, RayKind::Shade, Outputs{d_out_rgb, nullptr, nullptr});
 }
 int ft_shade_hits(ft_ctx* c, const ft_scene* s, const ft_object_trace_result* hits, int64_t n, float* out_rgb, ft_stats* st) {
     bool nothing;
-    int rc = checkShade(c, s, hits, n, out_rgb, false, &nothing); if (rc) return rc;
+    int rc = checkRecords("ft_shade_hits", Masks::None, c, s, hits, n, nullptr, out_rgb, false, &nothing); if (rc) return rc;
     if (nothing) { if (st) memset(st, 0, sizeof(*st)); return FT_OK; }
     return traceRayBuffer(c, s, hits, n, RayKind::Shade, Outputs{out_rgb, nullptr, nullptr}, st);
 }
 
 // ---- ft_light_visibility / ft_shade_visible: the shadow marches kept as one bit per (record, light), and shading from those bits -------------
-// Refusals first, the device last, as in checkShade.  A visibility mask has 32 bits: a scene with more lights is refused by both calls.
-// `masks`: vis_in (may be NULL) or the visibility; `out`: vis_out or the colours.  outIsMasks: vis_in == vis_out is an update in place; shading
-// into the masks is refused.
-static int checkMasked(const char* what, const ft_ctx* c, const ft_scene* s, const void* hits, int64_t n, const void* masks, bool masksNeeded,
-                       const void* out, bool outIsMasks, bool deviceMemory, bool* nothing) {
-    *nothing = false;
-    if (!c) return setErr(FT_ERR_INVALID, "null context");
-    if (!s || s->ctx != c || !hits || !out || (masksNeeded && !masks) || n < 0) return setErr(FT_ERR_INVALID, "bad argument (scene must belong to this context)");
-    if (deviceMemory) {
-        if (reinterpret_cast<uintptr_t>(hits) & 15u) return setErr(FT_ERR_INVALID, std::string(what) + "_device: the hit records must be 16-byte aligned");
-        if ((reinterpret_cast<uintptr_t>(masks) | reinterpret_cast<uintptr_t>(out)) & 3u)
-            return setErr(FT_ERR_INVALID, std::string(what) + "_device: the masks and the colours must be 4-byte aligned");
-    }
-    if (hits == out || (!outIsMasks && masks == out)) return setErr(FT_ERR_INVALID, std::string(what) + ": input and output must not overlap");
-    if (n >= 0xFFFF0000ll) return setErr(FT_ERR_UNSUPPORTED, "more than 2^32 records in one call");
-    if (s->dev.nLights > 32u) return setErr(FT_ERR_UNSUPPORTED, "a visibility mask holds 32 lights; the scene has " + std::to_string(s->dev.nLights));
-    *nothing = n == 0;
-    return FT_OK;
-}
-static int checkVisibility(const ft_ctx* c, const ft_scene* s, const void* hits, int64_t n, const void* visIn, const void* visOut, bool deviceMemory,
-                           bool* nothing) {
-    return checkMasked("ft_light_visibility", c, s, hits, n, visIn, false, visOut, true, deviceMemory, nothing);
-}
+// Both go through checkRecords: refusals first, the device last.
 int ft_light_visibility_device(ft_ctx* c, const ft_scene* s, const void* d_hits, int64_t n, uint32_t select, const void* d_vis_in, void* d_vis_out) {
     bool nothing;
-    int rc = checkVisibility(c, s, d_hits, n, d_vis_in, d_vis_out, true, &nothing); if (rc || nothing) return rc;
+    int rc = checkRecords("ft_light_visibility", Masks::Updated, c, s, d_hits, n, d_vis_in, d_vis_out, true, &nothing); if (rc || nothing) return rc;
     const VisRequest vis{select, d_vis_in};
     return launchRayBuffer(c, s, d_hits, n, RayKind::Visibility, Outputs{nullptr, nullptr, d_vis_out}, &vis);
 }
@@ -1397,55 +1415,44 @@ int ft_light_visibility_device(ft_ctx* c, const ft_scene* s, const void* d_hits,
 int ft_light_visibility(ft_ctx* c, const ft_scene* s, const ft_object_trace_result* hits, int64_t n, uint32_t select, const uint32_t* vis_in,
                         uint32_t* vis_out, ft_stats* st) {
     bool nothing;
-    int rc = checkVisibility(c, s, hits, n, vis_in, vis_out, false, &nothing); if (rc) return rc;
+    int rc = checkRecords("ft_light_visibility", Masks::Updated, c, s, hits, n, vis_in, vis_out, false, &nothing); if (rc) return rc;
     if (nothing) { if (st) memset(st, 0, sizeof(*st)); return FT_OK; }
     if ((rc = requireDevice(c))) return rc;
     const size_t recBytes = (size_t)n * sizeof(ft_object_trace_result), keepAt = align256(recBytes);
-    HostStaging stage(c, "light visibility", Outputs{nullptr, nullptr, vis_out}, 12, false);
+    HostStaging stage(c, "light visibility", outputParts(Outputs{nullptr, nullptr, vis_out}), false);
     if ((rc = stage.plan(keepAt + (vis_in ? (size_t)n * 4 : 0), (size_t)n))) return rc;
-    unsigned char* in = static_cast<unsigned char*>(stage.input());
-    HIP_TRY(hipMemcpyAsync(in, hits, recBytes, hipMemcpyHostToDevice, c->stream));
-    if (vis_in) HIP_TRY(hipMemcpyAsync(in + keepAt, vis_in, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-    const VisRequest vis{select, vis_in ? in + keepAt : nullptr};
-    stage.copyOut(launchRayBuffer(c, s, in, n, RayKind::Visibility, stage.dev(), &vis), 0, (size_t)n, (size_t)n);
+    if ((rc = stage.upload(0, hits, recBytes))) return rc;
+    if (vis_in && (rc = stage.upload(keepAt, vis_in, (size_t)n * 4))) return rc;
+    const VisRequest vis{select, vis_in ? stage.input(keepAt) : nullptr};
+    stage.copyOut(launchRayBuffer(c, s, stage.input(), n, RayKind::Visibility, stage.dev(), &vis), 0, (size_t)n, (size_t)n);
     return stage.finish(st);
 }
 
-static int checkShadeVisible(const ft_ctx* c, const ft_scene* s, const void* hits, const void* vis, int64_t n, const void* out, bool deviceMemory,
-                             bool* nothing) {
-    return checkMasked("ft_shade_visible", c, s, hits, n, vis, true, out, false, deviceMemory, nothing);
-}
 // its own kernel, not a trace launch: no job queue, no LDS, no counters; timed like one (ft_collect_stats adds the pair up)
 static int launchShadeVisible(ft_ctx* c, const ft_scene* s, const void* d_hits, const void* d_vis, int64_t n, void* d_out) {
     int rc = requireDevice(c); if (rc) return rc;
-    hipEvent_t e0, e1;
-    if ((rc = foldOldestEvents(c))) return rc;
-    if ((rc = acquireEvents(c, e0, e1))) return rc;
-    HIP_TRY(hipEventRecord(e0, c->stream));
-    HIP_TRY(ft_launch_shade_visible(s->dev.lights, s->dev.nLights, s->dev.bg, static_cast<const float*>(d_hits), static_cast<const uint32_t*>(d_vis),
-                                    (uint32_t)n, static_cast<float*>(d_out), c->stream));
-    HIP_TRY(hipEventRecord(e1, c->stream));
-    c->events.emplace_back(e0, e1);
-    return FT_OK;
+    return timedLaunch(c, c->stream, "ft_launch_shade_visible", [&] {
+        return ft_launch_shade_visible(s->dev.lights, s->dev.nLights, s->dev.bg, static_cast<const float*>(d_hits), static_cast<const uint32_t*>(d_vis),
+                                       (uint32_t)n, static_cast<float*>(d_out), c->stream);
+    });
 }
 int ft_shade_visible_device(ft_ctx* c, const ft_scene* s, const void* d_hits, const void* d_visibility, int64_t n, void* d_out_rgb) {
     bool nothing;
-    int rc = checkShadeVisible(c, s, d_hits, d_visibility, n, d_out_rgb, true, &nothing); if (rc || nothing) return rc;
+    int rc = checkRecords("ft_shade_visible", Masks::Read, c, s, d_hits, n, d_visibility, d_out_rgb, true, &nothing); if (rc || nothing) return rc;
     return launchShadeVisible(c, s, d_hits, d_visibility, n, d_out_rgb);
 }
 int ft_shade_visible(ft_ctx* c, const ft_scene* s, const ft_object_trace_result* hits, const uint32_t* visibility, int64_t n, float* out_rgb,
                      ft_stats* st) {
     bool nothing;
-    int rc = checkShadeVisible(c, s, hits, visibility, n, out_rgb, false, &nothing); if (rc) return rc;
+    int rc = checkRecords("ft_shade_visible", Masks::Read, c, s, hits, n, visibility, out_rgb, false, &nothing); if (rc) return rc;
     if (nothing) { if (st) memset(st, 0, sizeof(*st)); return FT_OK; }
     if ((rc = requireDevice(c))) return rc;
     const size_t recBytes = (size_t)n * sizeof(ft_object_trace_result), visAt = align256(recBytes);
-    HostStaging stage(c, "shade visible", Outputs{out_rgb, nullptr, nullptr}, 12, false);
+    HostStaging stage(c, "shade visible", outputParts(Outputs{out_rgb, nullptr, nullptr}), false);
     if ((rc = stage.plan(visAt + (size_t)n * 4, (size_t)n))) return rc;
-    unsigned char* in = static_cast<unsigned char*>(stage.input());
-    HIP_TRY(hipMemcpyAsync(in, hits, recBytes, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(in + visAt, visibility, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-    stage.copyOut(launchShadeVisible(c, s, in, in + visAt, n, stage.dev().rgb), 0, (size_t)n, (size_t)n);
+    if ((rc = stage.upload(0, hits, recBytes))) return rc;
+    if ((rc = stage.upload(visAt, visibility, (size_t)n * 4))) return rc;
+    stage.copyOut(launchShadeVisible(c, s, stage.input(), stage.input(visAt), n, stage.part(0)), 0, (size_t)n, (size_t)n);
     return stage.finish(st);
 }
 
@@ -1472,28 +1479,6 @@ int ft_eval_distance(ft_ctx* c, const ft_scene* s, const ft_vec3* pts, int64_t n
 
 // ---- field sampling: ft_sample_points, ft_sample_lattice and their *_device forms (kernels.hip "Field sampling") -----------------
 namespace {
-
-// What a field launch runs, beside planTrace and by its rules: the kernel family, its arithmetic, its value slots, whether the wave rows of the culling
-// pass are kept, the LDS footprint (ft_lds_layout).  A carved union takes the general kernel under glibc math or FT_OPT_CARVED = 0 (no carved *_libm
-// build exists); the lean and carved kernels keep their values in registers (nSlots = 0); the lean kernel always has its rows, any other non-carved
-// kernel where the scene has a cull site, and those optional rows are dropped where the footprint would exceed the device's limit.
-struct FieldPlan { unsigned variant; bool libm, cullRows; uint32_t nSlots; size_t lds; };
-int planField(const ft_ctx* c, const ft_scene* s, FieldPlan& p) {
-    const bool hasCull = s->dev.cullPc != 0xffffffffu;
-    p.libm = libmLaunch(c, s);
-    p.variant = (s->dev.fastPath == 3u && (!c->optCarved || p.libm)) ? 0u : s->dev.fastPath;
-    p.nSlots = (p.variant == 1u || p.variant == 3u) ? 0u : s->dev.nSlots;
-    p.cullRows = p.variant == 1u || (p.variant != 3u && hasCull);
-    int maxLds = 0;
-    HIP_TRY(hipDeviceGetAttribute(&maxLds, hipDeviceAttributeMaxSharedMemoryPerBlock, c->device));
-    p.lds = 4u * (size_t)ft_lds_layout(p.nSlots, s->dev.nStage, p.libm, p.cullRows).total;
-    if (p.lds > (size_t)maxLds && p.variant != 1u && p.cullRows) {
-        p.cullRows = false;
-        p.lds = 4u * (size_t)ft_lds_layout(p.nSlots, s->dev.nStage, p.libm, false).total;
-    }
-    if (p.lds > (size_t)maxLds) return setErr(FT_ERR_UNSUPPORTED, "scene needs " + std::to_string(p.lds) + " bytes of LDS per workgroup; the device offers " + std::to_string(maxLds));
-    return FT_OK;
-}
 
 // points (n of them) or a lattice, and where the results go: every address is host or device memory as the entry point says
 struct FieldRequest { const void* points; int64_t n; const ft_lattice* lat; float eps; uint32_t flags; void* dist; void* normal; void* material; };
@@ -1526,8 +1511,8 @@ int checkField(const ft_ctx* c, const ft_scene* s, const FieldRequest& r, bool d
 
 // the launch: device memory throughout, the context's stream, not synchronised; the arguments have passed checkField and the context has a device
 int launchField(ft_ctx* c, const ft_scene* s, const FieldRequest& r) {
-    FieldPlan plan;
-    int rc = planField(c, s, plan); if (rc) return rc;
+    KernelPlan plan;
+    int rc = planTrace(c, s, false, 0u, plan); if (rc) return rc;
     FtFieldArgs a{};
     a.S = s->dev;
     a.S.fastPath = plan.variant;
@@ -1564,19 +1549,10 @@ int launchField(ft_ctx* c, const ft_scene* s, const FieldRequest& r) {
     a.matHandles = s->dMatHandles; a.nMaterials = (uint32_t)s->flat.materialHandles.size();
     int perCU = 0;
     HIP_TRY(ft_field_occupancy(plan.variant, a.carve.kind, plan.libm, plan.lds, &perCU));
-    if (perCU < 1) return setErr(FT_ERR_UNSUPPORTED, "the field kernel does not fit a compute unit with this scene's LDS footprint");
-    perCU = std::min(perCU, 8);
-    if (c->optMaxBlocksPerCU > 0) perCU = std::min(perCU, c->optMaxBlocksPerCU);       // FT_OPT_MAX_BLOCKS_PER_CU
+    if ((rc = clampPerCU(c, "field", perCU))) return rc;
     const uint64_t wantBlocks = ((uint64_t)a.nJobs + (FT_BLOCK / 64) - 1) / (FT_BLOCK / 64);
     const unsigned blocks = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)c->numCUs * perCU, wantBlocks));
-    hipEvent_t e0, e1;
-    if ((rc = foldOldestEvents(c))) return rc;
-    if ((rc = acquireEvents(c, e0, e1))) return rc;
-    HIP_TRY(hipEventRecord(e0, c->stream));
-    HIP_TRY(ft_launch_field(&a, blocks, plan.lds, c->stream));
-    HIP_TRY(hipEventRecord(e1, c->stream));
-    c->events.emplace_back(e0, e1);
-    return FT_OK;
+    return timedLaunch(c, c->stream, "ft_launch_field", [&] { return ft_launch_field(&a, blocks, plan.lds, c->stream); });
 }
 
 int sampleDevice(ft_ctx* c, const ft_scene* s, const FieldRequest& r) {
@@ -1586,29 +1562,21 @@ int sampleDevice(ft_ctx* c, const ft_scene* s, const FieldRequest& r) {
     return launchField(c, s, r);
 }
 
-// the host forms: [points | distance | normal | material] in the context's scratch, each on a 256-byte boundary; the lattice form uploads nothing
+// the host forms: [points | distance | normal | material] in the context's scratch (HostStaging); the lattice form uploads nothing.  They return no
+// statistics, so nothing is collected: the launch's event pair stays pending for the caller's next ft_collect_stats
 int sampleHost(ft_ctx* c, const ft_scene* s, const FieldRequest& r) {
     bool nothing;
     int rc = checkField(c, s, r, false, &nothing); if (rc || nothing) return rc;
     if ((rc = requireDevice(c))) return rc;
-    const size_t n = (size_t)fieldCount(r);
-    const size_t oD = align256(r.points ? n * 12 : 0), oN = align256(oD + (r.dist ? n * 4 : 0)), oM = align256(oN + (r.normal ? n * 12 : 0));
-    if ((rc = ensureScratch(c, oM + (r.material ? n * 4 : 0)))) return rc;
-    unsigned char* base = static_cast<unsigned char*>(c->scratch);
-    if (r.points) HIP_TRY(hipMemcpyAsync(base, r.points, n * 12, hipMemcpyHostToDevice, c->stream));
+    const size_t n = (size_t)fieldCount(r), inBytes = r.points ? n * 12 : 0;
+    HostStaging stage(c, "field", HostParts{{{r.dist, 4}, {r.normal, 12}, {r.material, 4}}}, false);
+    if ((rc = stage.plan(inBytes, n))) return rc;
+    if (r.points && (rc = stage.upload(0, r.points, inBytes))) return rc;
     FieldRequest d = r;
-    d.points = r.points ? base : nullptr;
-    d.dist = r.dist ? base + oD : nullptr; d.normal = r.normal ? base + oN : nullptr; d.material = r.material ? base + oM : nullptr;
-    rc = launchField(c, s, d);
-    hipError_t err = hipSuccess;
-    if (!rc && r.dist) err = hipMemcpyAsync(r.dist, d.dist, n * 4, hipMemcpyDeviceToHost, c->stream);
-    if (!rc && r.normal && err == hipSuccess) err = hipMemcpyAsync(r.normal, d.normal, n * 12, hipMemcpyDeviceToHost, c->stream);
-    if (!rc && r.material && err == hipSuccess) err = hipMemcpyAsync(r.material, d.material, n * 4, hipMemcpyDeviceToHost, c->stream);
-    const hipError_t se = hipStreamSynchronize(c->stream);             // nothing of the call is left in flight, whatever happened
-    if (rc) return rc;
-    if (err != hipSuccess) return hipFail(err, "field host output");
-    if (se != hipSuccess) return hipFail(se, "field");
-    return FT_OK;
+    d.points = r.points ? stage.input() : nullptr;
+    d.dist = stage.part(0); d.normal = stage.part(1); d.material = stage.part(2);
+    stage.copyOut(launchField(c, s, d), 0, n, n);
+    return stage.finish();
 }
 
 }  // namespace

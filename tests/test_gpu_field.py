@@ -241,6 +241,38 @@ def test_device_forms_equal_host_forms_and_stay_inside_their_buffers(gpu, oracle
             b.free()
 
 
+def test_host_field_forms_leave_pending_statistics_alone():
+    """ft_sample_lattice and ft_sample_points return no statistics and collect none: a frame launched before them and not yet collected is still
+    there, whole, in the next collect_stats — every ray, hit, evaluation and flag counter of the same frame collected on its own (a field launch
+    counts nothing: FtFieldArgs has no statistics block), and a kernel time (the field launches' event pairs are added to it)."""
+    counters = ("rays_primary", "rays_shadow", "rays_ext", "hits_primary", "hits_shadow", "sdf_evals", "wave_evals", "flags")
+    hip = C.CDLL("libamdhip64.so.7")           # the runtime the library is linked against (already loaded: same instance)
+    hip.hipMalloc.argtypes, hip.hipFree.argtypes = [C.POINTER(C.c_void_p), C.c_size_t], [C.c_void_p]
+
+    def frame_stats(sample_between):
+        """a 16 x 16 frame on a context and scene of its own (nothing pending, no tile order from an earlier frame), collected at the end"""
+        dev = ft.Device(0)
+        frame = C.c_void_p()
+        assert hip.hipMalloc(C.byref(frame), C.c_size_t(16 * 16 * 12)) == 0
+        try:
+            ds = dev.scene(syn.config3(n=8)[0])
+            ds.render_device(syn.EPSILON, syn.RAY_LENGTH, ft.ImageSize(16, 16), syn.default_camera(), frame.value)
+            if sample_between:
+                origin, step = lattice_around(ds.boundary(), 0.5, (2, 3, 4))
+                lat = ds.sample_lattice(origin, step, (2, 3, 4), normal_epsilon=NORMAL_EPS, material=True)
+                pts = ds.sample_points(ft.lattice_points(origin, step, (2, 3, 4)).reshape(-1, 3)[:5], normal_epsilon=NORMAL_EPS, material=True)
+                assert_bit_equal(pts.distance, lat.distance.reshape(-1)[:5], "the two forms on the same points")
+            return ds.collect_stats()
+        finally:
+            dev.close()
+            assert hip.hipFree(frame) == 0
+
+    alone, after = frame_stats(False), frame_stats(True)
+    assert alone["rays_primary"] == 256 and alone["kernel_ms"] > 0.0
+    assert {k: after[k] for k in counters} == {k: alone[k] for k in counters}
+    assert after["kernel_ms"] > 0.0
+
+
 TENSOR_PATH = r"""
 import json, sys
 import numpy as np

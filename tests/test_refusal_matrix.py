@@ -14,6 +14,7 @@ from fraytracer_amd import _lib
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
 import make_refusal_matrix as matrix  # noqa: E402
+import make_refusal_matrix_records_field as records_field  # noqa: E402
 
 ENTRY_POINTS = sorted(list(matrix.FRAMES) + list(matrix.RAY_FORMS))
 
@@ -41,3 +42,29 @@ def test_every_refused_call_returns_the_recorded_status():
         if got[name][i] != want[name][i]:
             wrong.append((name, case, "got " + got[name][i], "recorded " + want[name][i]))
     assert not wrong, f"{len(wrong)} of {sum(at.values())} calls differ; the first: {wrong[:5]}"
+
+
+def test_the_record_and_field_forms_return_the_recorded_status_and_message():
+    """The second table (tests/golden/refusal_matrix_records_field.json, the grid is cases() of make_refusal_matrix_records_field.py): the eleven record
+    and field entry points, recorded before they were routed through the shared host path.  Here a call can also have nothing to do (n = 0: FT_OK),
+    the scene varies (the context's own, one under 33 lights, NULL, another context's) and every refusal's ft_last_error text is pinned too."""
+    table = json.load(open(records_field.TABLE))
+    assert table["recorded_from_commit"] == "bad71da"               # the parent of the refactor: not the code under test
+    cases = records_field.cases()
+    assert len(records_field.FORMS) == 11 and sorted(table["rows"]) == sorted(records_field.FORMS)
+    assert table["calls"] == len(cases) < 20000
+    seen = set("".join(r["status"] for r in table["rows"].values()))
+    assert {"I", "N", "U", "O"} <= seen and "H" not in seen
+    got, messages = records_field.run(_lib)
+    at = dict.fromkeys(records_field.FORMS, 0)
+    wrong = []
+    for name, case in cases:
+        i = at[name]
+        at[name] += 1
+        want_row, got_row = table["rows"][name], got[name]
+        want = (want_row["status"][i], None if want_row["message"][i] < 0 else table["messages"][want_row["message"][i]])
+        have = (got_row["status"][i], None if got_row["message"][i] < 0 else messages[got_row["message"][i]])
+        if have != want:
+            wrong.append((name, case, "got", have, "recorded", want))
+    assert all(at[name] == len(table["rows"][name]["status"]) == len(table["rows"][name]["message"]) for name in at)
+    assert not wrong, f"{len(wrong)} of {len(cases)} calls differ; the first: {wrong[:5]}"
