@@ -180,64 +180,48 @@ struct DeviceGridFiller : ft::GridFiller {
     }
 };
 
-template <class T> size_t placed(size_t& cursor, const std::vector<T>& v) {
-    const size_t at = cursor;
-    cursor = align256(cursor + std::max<size_t>(v.size() * sizeof(T), 16));
-    return at;
+// One vector of a scene's blob: where it lies (256-byte aligned, never empty) and what is copied there
+struct BlobPart { size_t at; const void* data; size_t bytes; };
+template <class T> BlobPart placed(size_t& cursor, const std::vector<T>& v) {
+    const BlobPart p{cursor, v.data(), v.size() * sizeof(T)};
+    cursor = align256(cursor + std::max<size_t>(p.bytes, 16));
+    return p;
 }
 
 int uploadScene(ft_ctx* c, ft_scene* s) {
     const ft::FlatScene& f = s->flat;
     size_t cur = 0;
-    const size_t oInstr = placed(cur, f.instr), oConsts = placed(cur, f.consts), oGrids = placed(cur, f.grids),
-                 oKids = placed(cur, f.children), oCtr = placed(cur, f.cellCenters), oStart = placed(cur, f.cellStart),
-                 oItems = placed(cur, f.items), oLights = placed(cur, f.lights), oMats = placed(cur, f.materials),
-                 oMatX = placed(cur, f.materialsExt), oItemsT = placed(cur, f.itemsT), oStartT = placed(cur, f.cellStartT),
-                 oMatH = placed(cur, f.materialHandles), oCertCl = placed(cur, f.certCl);
+    const BlobPart instr = placed(cur, f.instr), consts = placed(cur, f.consts), grids = placed(cur, f.grids),
+                   kids = placed(cur, f.children), ctr = placed(cur, f.cellCenters), start = placed(cur, f.cellStart),
+                   items = placed(cur, f.items), lights = placed(cur, f.lights), mats = placed(cur, f.materials),
+                   matX = placed(cur, f.materialsExt), itemsT = placed(cur, f.itemsT), startT = placed(cur, f.cellStartT),
+                   matH = placed(cur, f.materialHandles), certCl = placed(cur, f.certCl);
     std::vector<unsigned char> host(cur, 0);
-    auto put = [&](size_t at, const void* p, size_t n) { if (n) memcpy(host.data() + at, p, n); };
-    put(oInstr, f.instr.data(), f.instr.size() * sizeof(FtInstr));
-    put(oConsts, f.consts.data(), f.consts.size() * 4);
-    put(oGrids, f.grids.data(), f.grids.size() * sizeof(FtGrid));
-    put(oKids, f.children.data(), f.children.size() * sizeof(FtChild));
-    put(oCtr, f.cellCenters.data(), f.cellCenters.size() * 4);
-    put(oStart, f.cellStart.data(), f.cellStart.size() * 4);
-    put(oItems, f.items.data(), f.items.size() * sizeof(FtItemRec));
-    put(oLights, f.lights.data(), f.lights.size() * sizeof(FtLight));
-    put(oMats, f.materials.data(), f.materials.size() * 4);
-    put(oMatX, f.materialsExt.data(), f.materialsExt.size() * 4);
-    put(oItemsT, f.itemsT.data(), f.itemsT.size() * sizeof(FtItemRec));
-    put(oStartT, f.cellStartT.data(), f.cellStartT.size() * 4);
-    put(oMatH, f.materialHandles.data(), f.materialHandles.size() * 4);
-    put(oCertCl, f.certCl.data(), f.certCl.size() * 4);
+    for (const BlobPart& p : {instr, consts, grids, kids, ctr, start, items, lights, mats, matX, itemsT, startT, matH, certCl})
+        if (p.bytes) memcpy(host.data() + p.at, p.data, p.bytes);
     FtSceneDev& d = s->dev;
-    d = FtSceneDev{};
-    d.nInstr = f.nMainInstr; d.nSlots = f.nSlots; d.nLights = (uint32_t)f.lights.size(); d.fastPath = f.fastPath;
-    d.bg[0] = f.bg[0]; d.bg[1] = f.bg[1]; d.bg[2] = f.bg[2];
-    d.nStage = f.nStage; d.nearR2 = f.nearR2; d.fastQ = f.fastQ; d.nGlass = f.nGlass;
-    d.escC[0] = f.escC[0]; d.escC[1] = f.escC[1]; d.escC[2] = f.escC[2]; d.escR = f.escR; d.escRho2 = f.escRho2; d.cullPc = f.cullPc;
-    d.certM = f.certM; d.certClip = f.certClip; d.certRho2 = f.certRho2; d.certLenF = f.certLenF; d.certSteps = f.certSteps;
-    d.certK = f.certK;
+    d = f.hdr;                                             // every scalar as the flattener left it; what the blob holds follows: the lights' count, the pointers
+    d.nLights = (uint32_t)f.lights.size();
     if (!c->hasDevice) return FT_OK;                       // host-only context: introspection only
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipMalloc(&s->dBlob, cur));
     HIP_TRY(hipMemcpy(s->dBlob, host.data(), cur, hipMemcpyHostToDevice));
     unsigned char* b = static_cast<unsigned char*>(s->dBlob);
-    d.instr = reinterpret_cast<const FtInstr*>(b + oInstr);
-    d.consts = reinterpret_cast<const float*>(b + oConsts);
-    d.grids = reinterpret_cast<const FtGrid*>(b + oGrids);
-    d.children = reinterpret_cast<const FtChild*>(b + oKids);
-    d.cellCenters = reinterpret_cast<const float*>(b + oCtr);
-    d.cellStart = reinterpret_cast<const uint32_t*>(b + oStart);
-    d.items = reinterpret_cast<const FtItemRec*>(b + oItems);
-    d.lights = reinterpret_cast<const FtLight*>(b + oLights);
-    d.materials = reinterpret_cast<const float*>(b + oMats);
-    s->dMaterialsExt = reinterpret_cast<const float*>(b + oMatX);
-    s->dMatHandles = reinterpret_cast<const int32_t*>(b + oMatH);
-    d.certCl = reinterpret_cast<const float*>(b + oCertCl);
+    d.instr = reinterpret_cast<const FtInstr*>(b + instr.at);
+    d.consts = reinterpret_cast<const float*>(b + consts.at);
+    d.grids = reinterpret_cast<const FtGrid*>(b + grids.at);
+    d.children = reinterpret_cast<const FtChild*>(b + kids.at);
+    d.cellCenters = reinterpret_cast<const float*>(b + ctr.at);
+    d.cellStart = reinterpret_cast<const uint32_t*>(b + start.at);
+    d.items = reinterpret_cast<const FtItemRec*>(b + items.at);
+    d.lights = reinterpret_cast<const FtLight*>(b + lights.at);
+    d.materials = reinterpret_cast<const float*>(b + mats.at);
+    s->dMaterialsExt = reinterpret_cast<const float*>(b + matX.at);
+    s->dMatHandles = reinterpret_cast<const int32_t*>(b + matH.at);
+    d.certCl = reinterpret_cast<const float*>(b + certCl.at);
     s->carve = f.carve;
-    s->carve.itemsT = reinterpret_cast<const FtItemRec*>(b + oItemsT);
-    s->carve.cellStartT = reinterpret_cast<const uint32_t*>(b + oStartT);
+    s->carve.itemsT = reinterpret_cast<const FtItemRec*>(b + itemsT.at);
+    s->carve.cellStartT = reinterpret_cast<const uint32_t*>(b + startT.at);
     return FT_OK;
 }
 
@@ -351,111 +335,109 @@ TileOrderSlot* tileOrderSlot(const ft_scene* s, int lane, uint32_t nTiles) {
     return &t;
 }
 
-// launch the persistent trace kernel over nJobs jobs
-// lane 0 = the context's stream; lane 1 = a second stream with its own job counter, so that two launches can be in flight
-// (the drain of one overlaps the start of the next: DESIGN.md section 6)
-int launchTrace(ft_ctx* c, const ft_scene* s, FtRenderArgs& a, int lane = 0) {
-    hipStream_t stream = lane ? c->lane1 : c->stream;
-    uint32_t* counter = c->dCounter + (lane ? 16 : 0);
-    KernelPlan plan;
-    int rc = planTrace(c, s, a.ext != 0u, a.shade, plan); if (rc) return rc;
-    const unsigned variant = plan.variant;
-    // what decides the kernel (ft_kernels.h ft_trace_key; a.ext, a.views and a.shade are the caller's), then the key: the occupancy query here and the
-    // launch below look up the same one
-    a.S = s->dev;
-    a.S.fastPath = variant;
-    a.carve = s->carve;
-    a.math = plan.libm ? 1u : 0u;
-    const FtTraceKey key = ft_trace_key(a);
+// ---- launchTrace's rules, one function each -------------------------------------------------------------------------------------------------
+
+// Grid size: the workgroups of a launch of `key` over nJobs jobs — what the occupancy query allows per CU (clampPerCU), less on small frames, and
+// never more than the jobs fill.
+// Small frames: the job queue can only even out the load while there are several tiles per resident wave, and the grid-union kernels lose little
+// throughput at half their occupancy (the 4000^2 Program.fs frame: 5.4 ms at 7 workgroups per CU, 6.0 at 4).  With about as many tiles as waves
+// every tile is handed out at once, the heavy ones sit several deep on some SIMDs while others idle, and the frame lasts as long as the
+// slowest of them at full contention.  So: about one resident wave per four tiles, at least two workgroups per CU (measured per size,
+// profiles/r04_blocks_by_frame_size.jsonl: the reference's own 1000^2 frame 1.45 -> 1.27 ms, C2 at 1024^2 0.90 -> 0.61 ms).
+int gridSize(const ft_ctx* c, const FtTraceKey& key, const KernelPlan& plan, uint32_t nJobs, unsigned& blocks) {
     int perCU = 0;
     HIP_TRY(ft_trace_occupancy(key, plan.lds, &perCU));
-    if ((rc = clampPerCU(c, "trace", perCU))) return rc;
-    if (c->optMaxBlocksPerCU <= 0 && variant != 1u) {
-        // Small frames: the job queue can only even out the load while there are several tiles per resident wave, and the grid-union kernels lose little
-        // throughput at half their occupancy (the 4000^2 Program.fs frame: 5.4 ms at 7 workgroups per CU, 6.0 at 4).  With about as many tiles as waves
-        // every tile is handed out at once, the heavy ones sit several deep on some SIMDs while others idle, and the frame lasts as long as the
-        // slowest of them at full contention.  So: about one resident wave per four tiles, at least two workgroups per CU (measured per size,
-        // profiles/r04_blocks_by_frame_size.jsonl: the reference's own 1000^2 frame 1.45 -> 1.27 ms, C2 at 1024^2 0.90 -> 0.61 ms).
-        const uint64_t tiles = ((uint64_t)a.nJobs + (uint64_t)c->optChunk - 1) / (uint64_t)c->optChunk;
+    int rc = clampPerCU(c, "trace", perCU); if (rc) return rc;
+    if (c->optMaxBlocksPerCU <= 0 && key.variant != 1u) {
+        const uint64_t tiles = ((uint64_t)nJobs + (uint64_t)c->optChunk - 1) / (uint64_t)c->optChunk;
         const uint64_t wavesPerLayer = (uint64_t)c->numCUs * (FT_BLOCK / 64);
         const uint64_t want = (tiles + 2 * wavesPerLayer) / (4 * wavesPerLayer);              // round(tiles / (4 x waves of one workgroup per CU))
         perCU = (int)std::min<uint64_t>((uint64_t)perCU, std::max<uint64_t>(2, want));
     }
     const uint64_t maxBlocks = (uint64_t)c->numCUs * perCU;
-    const uint64_t wantBlocks = ((uint64_t)a.nJobs + FT_BLOCK - 1) / FT_BLOCK;
-    const unsigned blocks = (unsigned)std::max<uint64_t>(1, std::min(maxBlocks, wantBlocks));
-    // one 8x8 tile per grab: measured faster than larger chunks (lanes of a wave stay on neighbouring
-    // pixels) and 2.6e5 atomics per 4096^2 frame are far below the rate one counter sustains
+    const uint64_t wantBlocks = ((uint64_t)nJobs + FT_BLOCK - 1) / FT_BLOCK;
+    blocks = (unsigned)std::max<uint64_t>(1, std::min(maxBlocks, wantBlocks));
+    return FT_OK;
+}
+
+// Hand-out: how the waves of `blocks` workgroups take jobs from the queue.
+//   chunk      one 8x8 tile per grab: measured faster than larger chunks (lanes of a wave stay on neighbouring
+//              pixels) and 2.6e5 atomics per 4096^2 frame are far below the rate one counter sustains
+//   refillMin  burst refill (kernels.hip): a wave takes new rays only when all 64 lanes are idle, i.e. it works through one 8x8 tile at a
+//              time.  Measured (profiles/r02_refill_sweep.txt, kernel ms at refillMin = 1 / 32 / 64): 1000-torus scene 4000^2 22.5 /
+//              15.8 / 12.1, at 1000^2 2.98 / 2.72 / 2.24, C2 4096^2 4.90 / 4.40 / 3.84, 300 on-demand combinators 24.6 / 14.8 / 10.3,
+//              glass config 39.1 / 31.5 / 27.3, and even the VALU-bound C3 kernel 61.0 / 66.5 / 60.3: rays that start together stay in
+//              step (march, the four normal probes, shadow rays), so a wave's lanes share lookup cells, list positions and branches.
+//              64 unless FT_OPT_REFILL_MIN says otherwise (experiments)
+//   tailK      the latency mode's threshold, per kernel family unless FT_OPT_TAIL_K sets it (FT_TAIL_K_*)
+//   shrink1/2  guided hand-out of the last jobs (kernels.hip refill): one half tile, then one quarter tile per resident wave — only where the latency
+//              mode makes a part-filled wave cheap (lean kernel, tailK >= 32) and only for the reference's sampling (tile-major job order)
+void handOut(const ft_ctx* c, const ft_scene* s, unsigned variant, unsigned blocks, FtRenderArgs& a) {
     a.chunk = (uint32_t)c->optChunk;
-    // burst refill (kernels.hip): a wave takes new rays only when all 64 lanes are idle, i.e. it works through one 8x8 tile at a
-    // time.  Measured (profiles/r02_refill_sweep.txt, kernel ms at refillMin = 1 / 32 / 64): 1000-torus scene 4000^2 22.5 /
-    // 15.8 / 12.1, at 1000^2 2.98 / 2.72 / 2.24, C2 4096^2 4.90 / 4.40 / 3.84, 300 on-demand combinators 24.6 / 14.8 / 10.3,
-    // glass config 39.1 / 31.5 / 27.3, and even the VALU-bound C3 kernel 61.0 / 66.5 / 60.3: rays that start together stay in
-    // step (march, the four normal probes, shadow rays), so a wave's lanes share lookup cells, list positions and branches.
-    a.refillMin = (uint32_t)c->optRefillMin;               // 64 unless FT_OPT_REFILL_MIN says otherwise (experiments)
+    a.refillMin = (uint32_t)c->optRefillMin;
     a.tailK = (uint32_t)(c->optTailK >= 0 ? c->optTailK : (variant == 1u ? FT_TAIL_K_LEAN : variant == 3u ? FT_TAIL_K_CARVED : FT_TAIL_K_GENERAL));
-    // guided hand-out of the last jobs (kernels.hip refill): one half tile, then one quarter tile per resident wave — only where the latency
-    // mode makes a part-filled wave cheap (lean kernel, tailK >= 32) and only for the reference's sampling (tile-major job order)
     a.shrink1 = a.shrink2 = a.nJobs;
     if (s->dev.fastPath == 1u && a.tailK >= 32u && c->optGuided && a.mode == 0u) {
         const uint64_t waves = (uint64_t)blocks * (FT_BLOCK / 64);
         const uint64_t q = waves * (a.chunk / 4u), h = waves * (a.chunk / 2u);
         if ((uint64_t)a.nJobs > 4u * (q + h)) { a.shrink2 = (uint32_t)(a.nJobs - q); a.shrink1 = (uint32_t)(a.nJobs - q - h); }
     }
-    a.counter = counter;
-    a.stats = c->dStats;
-    a.S.nSlots = plan.nSlots;
-    a.cull = (s->dev.cullPc != 0xffffffffu && plan.cullRows && c->optCull) ? 1u : 0u;
-    if (!c->optEscape) a.S.escR = -1.0f;
-    // miss certificate: lean kernel (and its EXTENSION build: a render and its ft_render_hits twin count the same evaluations), only with the escape
-    // shortcut (it rests on the same support sphere and drift bound)
-    {
-        const uint32_t pol = (uint32_t)(c->optCertPolicy != 0 ? c->optCertPolicy : FT_CERT_POLICY_DEFAULT);
-        a.cert = (variant == 1u && c->optEscape && c->optCert && s->dev.certM >= 0.0f) ? 1u : 0u;
-        a.certPrim = (pol & 255u) == 255u ? 0xffffffffu : (pol & 255u);
-        a.certShadow = ((pol >> 8) & 255u) == 255u ? 0xffffffffu : ((pol >> 8) & 255u);
-        a.certMin = (pol >> 16) & 255u;
-        a.certRepeat = (pol >> 24) & 63u;
-        // bits 30-31: the bundle certificate's schedule — 0 shipped, 1 every round from one member on, 2 every second round, 3 off
-        const uint32_t bundle = pol >> 30;
-        a.bundlePeriod = bundle == 0u ? FT_BUNDLE_PERIOD : bundle == 3u ? 0u : bundle;
-        a.bundleMin = bundle == 0u ? FT_BUNDLE_MIN : 1u;
-        a.bundleShadow = bundle == 0u ? FT_BUNDLE_SHADOW : bundle == 2u ? 2u : 0u;
-        // Word 0 on a camera frame whose 8x8 tiles are narrower, at the far side of the support sphere, than the margin certM that every certificate concedes anyway:
-        // the bundle's width W stays below certM, so its bound loses next to nothing against its members' own and the per-lane tries only cost; they are left
-        // out (what 255 / 255 in an explicit word asks for).  Wider tiles (smaller frames, wider lenses), views and ray buffers keep both.  Measured on either
-        // side of the criterion, by frame size, lens and scene: DESIGN.md section 5 "Bundle certificate on C3", profiles/r06_bundle_certificate_tile_width.txt
-        if (c->optCertPolicy == 0 && a.cert && a.mode == 0u && a.views == nullptr && a.maxSize > 0.0f) {
-            const float* cm = a.cam;
-            const double dx = (double)cm[0] - s->dev.escC[0], dy = (double)cm[1] - s->dev.escC[1], dz = (double)cm[2] - s->dev.escC[2];
-            const double up = std::sqrt((double)cm[6] * cm[6] + (double)cm[7] * cm[7] + (double)cm[8] * cm[8]);
-            const double rt = std::sqrt((double)cm[9] * cm[9] + (double)cm[10] * cm[10] + (double)cm[11] * cm[11]);
-            const double fw = std::sqrt((double)cm[3] * cm[3] + (double)cm[4] * cm[4] + (double)cm[5] * cm[5]);
-            const double reach = std::sqrt(dx * dx + dy * dy + dz * dz) + (double)s->dev.escR;
-            const double tile = 8.0 * std::max(up, rt) / (double)a.maxSize * reach / fw;                // an 8x8 tile's side at distance `reach`
-            if (fw > 0.0 && tile <= (double)s->dev.certM) a.certPrim = a.certShadow = 0xffffffffu;
-        }
+}
+
+// FT_OPT_CERT_POLICY, the word's only decoder: bits 0-7 the step a primary ray is due from and 8-15 a shadow ray's (255: never), 16-23 the due lanes a
+// wave waits for, 24-29 the steps after which a ray the certificate failed on is due again, 30-31 the bundle certificate's schedule — 0 shipped,
+// 1 every round from one member on, 2 every second round, 3 off
+struct CertPolicy { uint32_t prim, shadow, minLanes, repeat, bundle; };
+CertPolicy decodeCertPolicy(uint32_t w) {
+    return CertPolicy{(w & 255u) == 255u ? ~0u : (w & 255u), ((w >> 8) & 255u) == 255u ? ~0u : ((w >> 8) & 255u), (w >> 16) & 255u, (w >> 24) & 63u, w >> 30};
+}
+
+// FT_OPT_OCCL_POLICY, the word's only decoder: bits 0-7 the period in evaluation rounds (0: shipped, 255: off), 8-15 the steps a shadow ray takes before its
+// try, 16-23 the candidates a try waits for (0: shipped)
+struct OcclPolicy { uint32_t period, from, minLanes; };
+OcclPolicy decodeOcclPolicy(uint32_t w) { return OcclPolicy{w & 255u, (w >> 8) & 255u, (w >> 16) & 255u}; }
+
+// Miss certificate and bundle certificate: lean kernel (and its EXTENSION build: a render and its ft_render_hits twin count the same evaluations), only
+// with the escape shortcut (it rests on the same support sphere and drift bound), on a scene that has one (certM >= 0).
+// Tile-width rule: word 0 on a camera frame whose 8x8 tiles are narrower, at the far side of the support sphere, than the margin certM that every certificate concedes anyway:
+// the bundle's width W stays below certM, so its bound loses next to nothing against its members' own and the per-lane tries only cost; they are left
+// out (what 255 / 255 in an explicit word asks for).  Wider tiles (smaller frames, wider lenses), views and ray buffers keep both.  Measured on either
+// side of the criterion, by frame size, lens and scene: DESIGN.md section 5 "Bundle certificate on C3", profiles/r06_bundle_certificate_tile_width.txt
+void certSchedule(const ft_ctx* c, const ft::FlatScene& f, unsigned variant, FtRenderArgs& a) {
+    const CertPolicy pol = decodeCertPolicy((uint32_t)(c->optCertPolicy != 0 ? c->optCertPolicy : FT_CERT_POLICY_DEFAULT));
+    a.cert = (variant == 1u && c->optEscape && c->optCert && f.hdr.certM >= 0.0f) ? 1u : 0u;
+    a.certPrim = pol.prim; a.certShadow = pol.shadow; a.certMin = pol.minLanes; a.certRepeat = pol.repeat;
+    a.bundlePeriod = pol.bundle == 0u ? FT_BUNDLE_PERIOD : pol.bundle == 3u ? 0u : pol.bundle;
+    a.bundleMin = pol.bundle == 0u ? FT_BUNDLE_MIN : 1u;
+    a.bundleShadow = pol.bundle == 0u ? FT_BUNDLE_SHADOW : pol.bundle == 2u ? 2u : 0u;
+    if (c->optCertPolicy == 0 && a.cert && a.mode == 0u && a.views == nullptr && a.maxSize > 0.0f) {
+        const float* cm = a.cam;
+        const double dx = (double)cm[0] - f.hdr.escC[0], dy = (double)cm[1] - f.hdr.escC[1], dz = (double)cm[2] - f.hdr.escC[2];
+        auto len = [cm](int i) { return std::sqrt((double)cm[i] * cm[i] + (double)cm[i + 1] * cm[i + 1] + (double)cm[i + 2] * cm[i + 2]); };
+        const double up = len(6), rt = len(9), fw = len(3);
+        const double reach = std::sqrt(dx * dx + dy * dy + dz * dz) + (double)f.hdr.escR;
+        const double tile = 8.0 * std::max(up, rt) / (double)a.maxSize * reach / fw;                // an 8x8 tile's side at distance `reach`
+        if (fw > 0.0 && tile <= (double)f.hdr.certM) a.certPrim = a.certShadow = 0xffffffffu;
     }
-    a.lazy = c->optLazyUnion ? 1u : 0u;
-    a.reuse = (c->optReuse && !a.shade) ? 1u : 0u;     // ft_shade_hits: no centre probe ran, nothing to reuse
-    // occlusion certificate: lean kernel (and its EXTENSION build: a render and its ft_render_hits twin count the same evaluations), only with the escape shortcut (the same support sphere and per-step drift) and with FT_OPT_CERT, which
-    // switches every certificate: with it off a launch evaluates exactly what its rays' marches ask for.  Policy word: bits 0-7
-    // the period in evaluation rounds (0: shipped, 255: off), 8-15 steps a shadow ray takes before its try, 16-23 the candidates a try waits for (0: shipped).
-    // A ray's first evaluation taken from the cache (FT_OPT_REUSE) is its step 0: it comes into being with one step taken
-    {
-        const uint32_t pol = (uint32_t)c->optOcclPolicy, per = pol & 255u, mn = (pol >> 16) & 255u;
-        const bool on = variant == 1u && c->optEscape && c->optCert && c->optOccl && s->flat.occB >= 0.0f && s->dev.certM >= 0.0f && per != 255u;
-        a.occPeriod = on ? (per != 0u ? per : FT_OCCL_PERIOD) : 0u;
-        a.occFrom = ((pol >> 8) & 255u) + a.reuse;
-        a.occMin = mn != 0u ? mn : FT_OCCL_MIN;
-        a.occE = s->flat.occE; a.occB = s->flat.occB; a.occEpsMin = s->flat.occEpsMin; a.occCap = s->flat.occCap; a.occLenInv = s->flat.occLenInv; a.occNear = s->flat.occNear; a.occReach = s->flat.occReach;
-    }
-    a.S.mathFma = c->optMath == FT_MATH_GLIBC_FMA ? 1u : 0u;
-    a.materialsExt = s->dMaterialsExt;
-    // FT_OPT_ORDER.  Eligible: a frame of whole tiles taken one at a time, on the kernel that keeps the bookkeeping (the lean kernel).
-    // An eligible launch records what each tile cost.  Where the slot's last launch had the same grid and kernel, it also hands the tiles out in
-    // the order built from that launch's costs.  A context with FT_OPT_GUIDED set is never eligible: the guided hand-out changes the grab size.
-    // A launch that is not eligible leaves the slot alone.
+}
+
+// Occlusion certificate: where the miss certificate runs (a.cert: the lean kernel, the escape shortcut — the same support sphere and per-step drift — and
+// FT_OPT_CERT, which switches every certificate: with it off a launch evaluates exactly what its rays' marches ask for), with FT_OPT_OCCL, on a scene
+// that has one (occ.b >= 0).  A ray's first evaluation taken from the cache (FT_OPT_REUSE, a.reuse) is its step 0: it comes into being with one step taken.
+void occlSchedule(const ft_ctx* c, const ft::FlatScene& f, FtRenderArgs& a) {
+    const OcclPolicy pol = decodeOcclPolicy((uint32_t)c->optOcclPolicy);
+    const bool on = a.cert && c->optOccl && f.occ.b >= 0.0f && pol.period != 255u;
+    a.occPeriod = on ? (pol.period != 0u ? pol.period : FT_OCCL_PERIOD) : 0u;
+    a.occFrom = pol.from + a.reuse;
+    a.occMin = pol.minLanes != 0u ? pol.minLanes : FT_OCCL_MIN;
+    a.occ = f.occ;
+}
+
+// FT_OPT_ORDER.  Eligible: a frame of whole tiles taken one at a time, on the kernel that keeps the bookkeeping (the lean kernel).
+// An eligible launch records what each tile cost.  Where the slot's last launch had the same grid and kernel, it also hands the tiles out in
+// the order built from that launch's costs.  A context with FT_OPT_GUIDED set is never eligible: the guided hand-out changes the grab size.
+// A launch that is not eligible leaves the slot alone.  -> the slot the launch records into, nullptr: none
+TileOrderSlot* tileOrder(const ft_ctx* c, const ft_scene* s, int lane, const FtTraceKey& key, FtRenderArgs& a) {
     a.tileCost = nullptr; a.tileOrder = nullptr;
     TileOrderSlot* slot = nullptr;
     if (key.form == FT_FORM_FRAME && !key.ext && key.variant == 1u && a.mode == 0u && a.spp == 1u && a.chunk == 64u && a.refillMin == 64u && !c->optGuided && a.shrink1 == a.nJobs && a.nJobs >= 64u) {
@@ -468,6 +450,35 @@ int launchTrace(ft_ctx* c, const ft_scene* s, FtRenderArgs& a, int lane = 0) {
         if (c->optOrder == 1 && slot->keyed && slot->hasOrder && slot->key == k) a.tileOrder = slot->order;
         slot->key = k; slot->keyed = true; slot->hasOrder = false; slot->usedOrder = a.tileOrder != nullptr;
     }
+    return slot;
+}
+
+// launch the persistent trace kernel over nJobs jobs
+// lane 0 = the context's stream; lane 1 = a second stream with its own job counter, so that two launches can be in flight
+// (the drain of one overlaps the start of the next: DESIGN.md section 6)
+int launchTrace(ft_ctx* c, const ft_scene* s, FtRenderArgs& a, int lane = 0) {
+    hipStream_t stream = lane ? c->lane1 : c->stream;
+    uint32_t* counter = c->dCounter + (lane ? 16 : 0);
+    KernelPlan plan;
+    int rc = planTrace(c, s, a.ext != 0u, a.shade, plan); if (rc) return rc;
+    // what decides the kernel (ft_kernels.h ft_trace_key; a.ext, a.views and a.shade are the caller's), then the key: the occupancy query and the
+    // launch look up the same one
+    a.S = s->dev; a.S.fastPath = plan.variant; a.S.nSlots = plan.nSlots;
+    a.S.mathFma = c->optMath == FT_MATH_GLIBC_FMA ? 1u : 0u;
+    if (!c->optEscape) a.S.escR = -1.0f;
+    a.carve = s->carve; a.materialsExt = s->dMaterialsExt;
+    a.math = plan.libm ? 1u : 0u;
+    a.counter = counter; a.stats = c->dStats;
+    a.cull = (s->dev.cullPc != 0xffffffffu && plan.cullRows && c->optCull) ? 1u : 0u;
+    a.lazy = c->optLazyUnion ? 1u : 0u;
+    a.reuse = (c->optReuse && !a.shade) ? 1u : 0u;     // ft_shade_hits: no centre probe ran, nothing to reuse
+    const FtTraceKey key = ft_trace_key(a);
+    unsigned blocks = 0;
+    if ((rc = gridSize(c, key, plan, a.nJobs, blocks))) return rc;
+    handOut(c, s, plan.variant, blocks, a);
+    certSchedule(c, s->flat, plan.variant, a);
+    occlSchedule(c, s->flat, a);
+    TileOrderSlot* slot = tileOrder(c, s, lane, key, a);
     HIP_TRY(hipMemsetAsync(counter, 0, sizeof(uint32_t), stream));
     if ((rc = timedLaunch(c, stream, "ft_launch_trace", [&] { return ft_launch_trace(&a, blocks, plan.lds, stream); }))) return rc;
     if (slot && c->optOrder == 1) {                        // behind the frame on its own stream: no synchronisation, nothing comes back to the host
@@ -508,7 +519,7 @@ const OptionSpec* findOption(int32_t id) {
 bool optionAccepts(const OptionSpec& o, int32_t v) {
     if (v < o.lo || v > o.hi) return false;
     if (o.id == FT_OPT_CHUNK) return v == 64 || v == 32 || v == 16;
-    if (o.id == FT_OPT_CERT_POLICY) { const uint32_t mn = ((uint32_t)v >> 16) & 255u; return v == 0 || (mn >= 1u && mn <= 64u); }
+    if (o.id == FT_OPT_CERT_POLICY) { const uint32_t mn = decodeCertPolicy((uint32_t)v).minLanes; return v == 0 || (mn >= 1u && mn <= 64u); }
     return true;
 }
 
@@ -739,7 +750,7 @@ int ft_scene_relight(const ft_scene* src, const float bg[3], const ft_handle* li
     s->usesExpLog = src->usesExpLog;
     s->flat.lights.clear();
     for (int32_t i = 0; i < n; ++i) s->flat.lights.push_back(c->builder.lights[lights[i]].dev);
-    s->flat.bg[0] = bg[0]; s->flat.bg[1] = bg[1]; s->flat.bg[2] = bg[2];
+    s->flat.hdr.bg[0] = bg[0]; s->flat.hdr.bg[1] = bg[1]; s->flat.hdr.bg[2] = bg[2];
     int rc = uploadScene(c, s);
     if (rc) { delete s; return rc; }
     *out = s;
@@ -1669,11 +1680,11 @@ void ft_set_error_(int, const char* msg) { g_err = msg ? msg : ""; }
 int ft_scene_info_get(const ft_scene* s, ft_scene_info* o) {
     if (!s || !o) return setErr(FT_ERR_INVALID, "null argument");
     const ft::FlatScene& f = s->flat;
-    o->n_instr = (int32_t)f.instr.size(); o->n_slots = (int32_t)f.nSlots; o->n_consts = (int32_t)f.consts.size();
+    o->n_instr = (int32_t)f.instr.size(); o->n_slots = (int32_t)f.hdr.nSlots; o->n_consts = (int32_t)f.consts.size();
     o->n_grids = (int32_t)f.grids.size(); o->n_children = (int32_t)f.children.size(); o->n_cells = (int32_t)(f.cellCenters.size() / 3);
     o->n_items = (int32_t)f.items.size(); o->n_lights = (int32_t)f.lights.size(); o->n_materials = (int32_t)(f.materials.size() / 3);
-    o->fast_path = (int32_t)f.fastPath;
-    o->cull_pc = (int32_t)f.cullPc;
+    o->fast_path = (int32_t)f.hdr.fastPath;
+    o->cull_pc = (int32_t)f.hdr.cullPc;
     return FT_OK;
 }
 
@@ -1690,26 +1701,26 @@ int ft_scene_grid_shape(const ft_scene* s, int32_t g, float info[6], int32_t cou
 
 int ft_scene_support_sphere(const ft_scene* s, float cr[4]) {
     if (!s || !cr) return setErr(FT_ERR_INVALID, "null argument");
-    cr[0] = s->flat.escC[0]; cr[1] = s->flat.escC[1]; cr[2] = s->flat.escC[2]; cr[3] = s->flat.escR;
+    memcpy(cr, s->flat.hdr.escC, 3 * sizeof(float)); cr[3] = s->flat.hdr.escR;
     return FT_OK;
 }
 int ft_scene_miss_certificate(const ft_scene* s, float out[5]) {
     if (!s || !out) return setErr(FT_ERR_INVALID, "null argument");
-    const ft::FlatScene& f = s->flat;
-    out[0] = f.certM; out[1] = f.certClip; out[2] = f.certRho2; out[3] = f.certLenF; out[4] = (float)f.certSteps;
+    const FtSceneDev& h = s->flat.hdr;
+    out[0] = h.certM; out[1] = h.certClip; out[2] = h.certRho2; out[3] = h.certLenF; out[4] = (float)h.certSteps;
     return FT_OK;
 }
 int ft_scene_occlusion_certificate(const ft_scene* s, float out[7]) {
     if (!s || !out) return setErr(FT_ERR_INVALID, "null argument");
-    const ft::FlatScene& f = s->flat;
-    out[0] = f.occE; out[1] = f.occB; out[2] = f.occEpsMin; out[3] = f.occCap; out[4] = f.occLenInv; out[5] = f.occNear; out[6] = f.occReach;
+    static_assert(sizeof(FtOccl) == 7 * sizeof(float), "out[7] is FtOccl, field by field");
+    memcpy(out, &s->flat.occ, sizeof(FtOccl));
     return FT_OK;
 }
 int ft_scene_miss_certificate_clusters(const ft_scene* s, int32_t* nClusters, int32_t* nChildren, float* out, int32_t capacity) {
     if (!s || !nClusters || !nChildren) return setErr(FT_ERR_INVALID, "null argument");
     const ft::FlatScene& f = s->flat;
-    *nClusters = (int32_t)f.certK;
-    *nChildren = (int32_t)((f.certCl.size() - 8u * f.certK) / 4u);
+    *nClusters = (int32_t)f.hdr.certK;
+    *nChildren = (int32_t)((f.certCl.size() - 8u * f.hdr.certK) / 4u);
     if (!out) return FT_OK;
     if (capacity < 0 || (size_t)capacity < f.certCl.size()) return setErr(FT_ERR_INVALID, "capacity below 8 n_clusters + 4 n_children floats");
     if (!f.certCl.empty()) memcpy(out, f.certCl.data(), f.certCl.size() * 4);

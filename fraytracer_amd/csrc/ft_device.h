@@ -118,6 +118,12 @@ struct FtSceneDev {             // passed by value as kernel argument
     uint32_t certK;             // then the children in cluster order (4 floats each); read-only, wave-uniform.  certK = 0: the flat loop over the staged children
 };
 
+// Occlusion certificate (kernels.hip ft_occlusion_certificate; scene.cpp "Occlusion certificate"): the scene's constants, decided by the flattener and
+// handed to the lean kernel in FtRenderArgs::occ (FtSceneDev's layout does not move for them).  b < 0: none.
+// e: drift per step; b: the margin's constant part; epsMin: the smallest epsilon tried; cap: the largest margin conceded; lenInv: 1 / the count-down's padding
+// factor; near: how far from a sphere f can still be <= 0; reach: the largest t* (the float32 sum cannot underflow before it)
+struct FtOccl { float e, b, epsMin, cap, lenInv, near, reach; };
+
 // "Carved union" kernels (FtSceneDev.fastPath == 3; kernels.hip ft_eval_carved): the whole program is ONE grid union of plain primitives
 // followed by at most FT_CARVE_TAIL intersect / subtract steps with one primitive each — the shape of the reference's own scene,
 // subtract(intersect(union [1000 tori], [sphere]), sphere) (Program.fs:67-77).  The flattener records the tail here and lays the union's

@@ -1,6 +1,7 @@
 // ft_kernels.h — kernel argument block and host-callable launchers (implemented in kernels.hip).
 #pragma once
 #include <hip/hip_runtime_api.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #include "../../include/fraytracer_hip.h"
@@ -109,8 +110,9 @@ struct FtRenderArgs {
     // "Occlusion certificate"): tried every occPeriod-th evaluation round of a wave (0: never) for its shadow rays of occFrom .. occFrom + occPeriod - 1
     // steps — each ray meets exactly one such round — where at least occMin (>= 1) lanes hold such a ray
     uint32_t occPeriod, occFrom, occMin;
-    float occE, occB, occEpsMin, occCap, occLenInv, occNear, occReach;
+    FtOccl occ;
 };
+static_assert(offsetof(FtRenderArgs, occ) == 860 && sizeof(FtRenderArgs) == 888, "the kernels' argument block does not move");
 #define FT_MAX_VIEWS 64       // views per launch (one PH_CAM value per lane); ft_render_views splits larger batches
 
 // The forms of the trace kernel (kernels.hip FT_TRACE_FORMS builds every one of them from the same table of builds): what a job is and what it leaves.
@@ -133,7 +135,7 @@ FT_HD FtTraceKey ft_trace_key(const FtRenderArgs& a) {
 // l at (l >> (lgJ + lgK), (l >> lgK) & (2^lgJ - 1), l & (2^lgK - 1)) in its brick; brick b lies at (b / (bricksJ * bricksK), (b / bricksK) % bricksJ,
 // b % bricksK) bricks.  A block of its own, like FtGridBuildArgs: nothing in FtRenderArgs or FtSceneDev moves.
 struct FtFieldArgs {
-    FtSceneDev S;             // fastPath: the kernel family as capi.cpp planField decides it (1 lean, 3 carved, otherwise the general interpreter)
+    FtSceneDev S;             // fastPath: the kernel family as capi.cpp planTrace decides it (1 lean, 3 carved, otherwise the general interpreter)
     FtCarve carve;            // fastPath == 3 only
     const float* pts;         // points form: n x 3 floats; NULL: the lattice below
     float origin[3], step[3];

@@ -1430,11 +1430,17 @@ __device__ __forceinline__ bool ft_miss_certificate(const FtSceneDev& S, const f
     return ok && sum < thr;
 }
 
+// The axis lane of the bundle and the occlusion certificate: of the lanes in `mm` (not empty) the first at or after lane 27, else the first.  A wave holds
+// an 8x8 tile, lane 27 is its middle: the line of a ray there is the one the tile's other rays stay closest to.
+__device__ __forceinline__ int ft_axis_lane(unsigned long long mm) {
+    return (mm >> 27) != 0ull ? 26 + __ffsll((long long)(mm >> 27)) : __ffsll((long long)mm) - 1;
+}
+
 // Bundle certificate: ONE test for all the rays of the wave that ask (`cand`), with the children spread over the lanes as in ft_cull_children.  What pays
 // is ending all marching lanes of a tile together (a wave's round count is its longest lane's), and whether that is possible is a property of the tile's
 // bundle of rays.  Members are the candidates that pass ft_cert_segment: exactly the lanes ft_miss_certificate would test, with the same segments
 // o_l + t dir_l, t0_l <= t <= t1_l.  The others are left out and keep marching.
-// Axis: the line o_c + sigma d_c of one member (the first at or after lane 27, else the first: the middle of an 8x8 tile), d_c = its direction as it is.
+// Axis: the line o_c + sigma d_c of one member (ft_axis_lane), d_c = its direction as it is.
 // For member l let s_l = (o_l - o_c).d_c / |d_c|^2, a_l = |o_l - o_c - s_l d_c|, b_l = |dir_l - d_c|.  Then for t0_l <= t <= t1_l
 //     (o_l + t dir_l) - (o_c + (s_l + t) d_c)  =  (o_l - o_c - s_l d_c) + t (dir_l - d_c),    of length <= a_l + b_l t1_l      (t >= t0_l >= 0)
 // — an identity in s_l, so neither the rounding of s_l nor |d_c| != 1 matters (for unit directions t is the arc length).  With W >= max_l (a_l + b_l t1_l)
@@ -1458,7 +1464,7 @@ __device__ __forceinline__ bool ft_bundle_certificate(const FtSceneDev& S, const
     const float A = in->f0 * 1.44269504f;
     const uint32_t n = in->count;
     const float4* c = reinterpret_cast<const float4*>(ldsC + in->data);
-    const int ax = (mm >> 27) != 0ull ? 26 + __ffsll((long long)(mm >> 27)) : __ffsll((long long)mm) - 1;
+    const int ax = ft_axis_lane(mm);
     const f3 oc = ft_readlane3(o, ax), dc = ft_readlane3(dir, ax);
     const float tc0 = ft_readlane_f(t0, ax), tc1 = ft_readlane_f(t1, ax);      // the axis lane's own interval (s = 0): tc0 < tc1
     const f3 g = o - oc, h = dir - dc;
@@ -1498,7 +1504,7 @@ __device__ __forceinline__ bool ft_bundle_certificate(const FtSceneDev& S, const
 // Length, the reference's march cannot get past t* and ends in a hit (scene.cpp "Occlusion certificate": f is 1-Lipschitz, the drift of the at most
 // t* / epsilon marched points, the float32 evaluation; hitM = occE (t* / epsilon + 2) + occB).  The lane then takes the exit of an evaluation below epsilon.
 // One try for all the shadow rays of the wave that ask (`cand`), children across the lanes as in ft_bundle_certificate:
-//   axis    one candidate's line (the first at or after lane 27, else the first), its rest 0 <= t <= Length occLenInv;
+//   axis    one candidate's line (ft_axis_lane), its rest 0 <= t <= Length occ.lenInv;
 //   pass A  lane k of pass j: depth r_i - dist(axis, c_i) of child 64 j + k; a wave maximum names the deepest child i* and its closest approach sigma*.
 //           No child within occNear = s ln n of the axis: f > 0 all along it, and the wave leaves (most tiles hold no occluder);
 //   pass B  the same layout sums S = sum_i 2^(A (|c_i - y| - r_i)) at the witness y = axis(sigma*): D = s ln S = -f(y), v_sqrt_f32 / v_exp_f32 / v_log_f32 with
@@ -1517,7 +1523,7 @@ __device__ __forceinline__ bool ft_occlusion_certificate(const FtRenderArgs& a, 
     const FtSceneDev& S = a.S;
     const f3 w = o - mk3(S.escC[0], S.escC[1], S.escC[2]);
     const float dd = ft_dot(dir, dir);
-    const bool ok = cand && a.occB >= 0.0f && S.escR >= 0.0f && eps >= a.occEpsMin && eps <= S.escR && len > 0.0f && len < 1e9f && dd >= 0.81f && dd <= 1.000001f &&
+    const bool ok = cand && a.occ.b >= 0.0f && S.escR >= 0.0f && eps >= a.occ.epsMin && eps <= S.escR && len > 0.0f && len < 1e9f && dd >= 0.81f && dd <= 1.000001f &&
                     ft_dot(w, w) <= S.certRho2 && steps < FT_STEP_CAP / 2u;
     const unsigned long long mm = __ballot(ok);
     if (mm == 0ull) return false;
@@ -1525,8 +1531,8 @@ __device__ __forceinline__ bool ft_occlusion_certificate(const FtRenderArgs& a, 
     const uint32_t n = in->count;
     const float si = in->f0;
     const float4* c = reinterpret_cast<const float4*>(ldsC + in->data);
-    const float tEnd = len * a.occLenInv;
-    const int ax = (mm >> 27) != 0ull ? 26 + __ffsll((long long)(mm >> 27)) : __ffsll((long long)mm) - 1;
+    const float tEnd = len * a.occ.lenInv;
+    const int ax = ft_axis_lane(mm);
     const f3 oc = ft_readlane3(o, ax), dc = ft_readlane3(dir, ax);
     const float tc = ft_readlane_f(tEnd, ax), idc = 1.0f / ft_dot(dc, dc);
     const uint32_t lane = threadIdx.x & 63u;
@@ -1542,7 +1548,7 @@ __device__ __forceinline__ bool ft_occlusion_certificate(const FtRenderArgs& a, 
     for (uint32_t base = 0; base < n; base += 64u) {
         const uint32_t i = base + lane;
         const float4 prm = c[i < n ? i : n - 1u];
-        const float nr = (prm.w + a.occNear) - approach(mk3(prm.x, prm.y, prm.z), oc, dc, idc, tc, tAx);
+        const float nr = (prm.w + a.occ.near) - approach(mk3(prm.x, prm.y, prm.z), oc, dc, idc, tc, tAx);
         if (i < n && nr > best) { best = nr; bi = i; }
     }
     const float nearest = ft_wave_max_all(best);
@@ -1568,13 +1574,13 @@ __device__ __forceinline__ bool ft_occlusion_certificate(const FtRenderArgs& a, 
     bool holds = false;
     {
         const float dist = approach(mk3(sp.x, sp.y, sp.z), o, dir, idd, tEnd, t);
-        const float nSteps = __builtin_fmaf(t, ie, 2.0f), hitM = __builtin_fmaf(a.occE, nSteps, a.occB);
-        holds = t <= a.occReach && nSteps < 131072.0f && hitM <= a.occCap && (dist + hitM) * 1.001f < sp.w;
+        const float nSteps = __builtin_fmaf(t, ie, 2.0f), hitM = __builtin_fmaf(a.occ.e, nSteps, a.occ.b);
+        holds = t <= a.occ.reach && nSteps < 131072.0f && hitM <= a.occ.cap && (dist + hitM) * 1.001f < sp.w;
     }
     {
         const float dist = approach(y, o, dir, idd, tEnd, t);
-        const float nSteps = __builtin_fmaf(t, ie, 2.0f), hitM = __builtin_fmaf(a.occE, nSteps, a.occB);
-        holds = holds || (t <= a.occReach && nSteps < 131072.0f && hitM <= a.occCap && (dist + hitM) * 1.001f < D);
+        const float nSteps = __builtin_fmaf(t, ie, 2.0f), hitM = __builtin_fmaf(a.occ.e, nSteps, a.occ.b);
+        holds = holds || (t <= a.occ.reach && nSteps < 131072.0f && hitM <= a.occ.cap && (dist + hitM) * 1.001f < D);
     }
     return ok && holds;
 }

@@ -357,7 +357,7 @@ struct Flattener {
             const Builder::MatExt& e = b.materialExt[handle];
             out.materialsExt.push_back(e.glass ? 1.0f : 0.0f); out.materialsExt.push_back(e.ior);
             out.materialsExt.push_back(e.dispersion); out.materialsExt.push_back(0.0f);
-            out.nGlass += e.glass;
+            out.hdr.nGlass += e.glass;
             out.materialHandles.push_back(handle);
         }
         return (uint32_t)matRemap[handle];
@@ -647,7 +647,7 @@ struct Flattener {
     // main program | sub-programs: fix up the (first, end) instruction indices of every call record
     void linkCalls() {
         const uint32_t base = (uint32_t)out.instr.size();
-        out.nMainInstr = base;
+        out.hdr.nInstr = base;
         for (const Call& cl : calls) {
             const uint32_t first = base + cl.begin, end = base + cl.end;
             memcpy(&out.consts[cl.constAt], &first, 4);
@@ -773,7 +773,7 @@ static bool supportOf(const Builder& b, int h, Support& out, int depth = 0) {
 // Is the program ONE grid union of plain primitives followed by at most FT_CARVE_TAIL single-primitive intersect / subtract steps
 // (ft_device.h "Carved union": the shape of Program.fs:67-77)?  Then record the tail and lay the candidate lists out with terminators.
 static bool carvedShape(FlatScene& out) {
-    if (out.nMainInstr != out.instr.size() || out.instr.empty() || out.grids.size() != 1) return false;
+    if (out.hdr.nInstr != out.instr.size() || out.instr.empty() || out.grids.size() != 1) return false;
     const FtInstr& u = out.instr[0];
     if (u.op != FT_OP_UNION || u.dst != 0 || u.aux != 0) return false;
     uint32_t kind = FT_PR_SLOT;
@@ -894,178 +894,204 @@ static void certClusters(const float* kid, uint32_t n, std::vector<float>& rec, 
     }
 }
 
+// The sphere no hit can lie outside of (see supportOf), padded twice:
+//   padEval  — what a float32 evaluation may differ from the exact value: 0.1 % of the radius, 0.01, and 0.1 % of the centre's coordinates;
+//   padDrift — "drift of the marched points".  The reference moves the ray's origin step by step in float32 (Ray.fs:9-13: Origin + Direction * d), so the
+//     points it evaluates leave the line the shortcut reasons about (kernels.hip ft_never_enters).  One step that starts or ends at most rho from the centre c
+//     adds at most e(rho) = 3 * 2^-23 * (|c|inf + rho) to that drift (per component: the rounding of a product <= 2 rho and of a sum <= |c|inf + rho).
+//     Let Rp = r + padEval + padDrift (= escR), a = |Direction| >= 1/2, 0 <= epsilon <= Rp, and suppose the drift so far is <= padDrift / 2.  The line stays
+//     >= Rp + epsilon from c, so every evaluated point is >= r + padEval + epsilon + padDrift / 2 from c: no hit there, and each step is d >= g = epsilon + padDrift / 2
+//     (support property), i.e. moves a d >= padDrift / 4 along the line.  Three kinds of steps:
+//       near      (start and end within 5 Rp of c — that is >= 2.5 (Rp + epsilon)): the line's chord through that ball is <= 10 Rp long: at most 40 Rp / padDrift + 1
+//                 steps of error <= e(5 Rp) each.  padDrift is the root of  (40 Rp / padDrift + 1) e(5 Rp) = padDrift / 4.
+//       approach  (start farther than 5 Rp, before the near steps): d >= rho - Rp - epsilon >= rho / 2 moves >= rho / 4 along a line of which at most 2 rho are left
+//                 to the near ball, so that length shrinks by 7/8 per step: N(rho0) = 7.5 ln(8 rho0 / padDrift) + 1 steps from a start at rho0, each
+//                 <= e(rho0).  The kernel takes the shortcut only from starts with N(rho0) e(rho0) <= padDrift / 4 (escRho2, by bisection below).
+//       receding  (rho >= 5 Rp, moving away): rho grows by >= sqrt(1 + a^2 / 4) >= 1.03 per step, so the errors of the steps so far form a geometric series
+//                 <= 34 e-terms of the last one: < 1.3e-5 rho + 1.2e-5 |c|inf ln(rho / 5 Rp) <= rho / 50 (|c|inf <= 1000 Rp: padEval), against a margin
+//                 rho - (r + padEval + epsilon) >= rho - 2 Rp >= 0.6 rho.
+//     Near and approach together stay <= padDrift / 2: the supposition holds step after step, every evaluated point keeps its distance, no step can be a hit.
+//     (Short rays — kernels.hip: Length <= 10 escR, the whole march within 2.5 escR of c — make at most Length / g + 1 <= 20 Rp / padDrift + 1 steps of error
+//     <= e(2.5 Rp): inside the near budget whatever |Direction| is.)
+// -> |escC|inf in double where the scene has a support sphere (the certificates' per-step error needs it), -1 where none is known: escR stays -1
+static double supportSphere(const Builder& b, int form, FtSceneDev& h) {
+    Support sup;
+    if (!(finiteTree(b, form) && supportOf(b, form, sup) && sup.r < 1e15 && std::fabs(sup.c[0]) + std::fabs(sup.c[1]) + std::fabs(sup.c[2]) < 1e15)) return -1.0;
+    h.escC[0] = (float)sup.c[0]; h.escC[1] = (float)sup.c[1]; h.escC[2] = (float)sup.c[2];
+    const double cInf = std::max(std::fabs(sup.c[0]), std::max(std::fabs(sup.c[1]), std::fabs(sup.c[2])));
+    const double padEval = sup.r * 0.001 + 0.01 + 1e-3 * (std::fabs(sup.c[0]) + std::fabs(sup.c[1]) + std::fabs(sup.c[2]));
+    const double u3 = 3.0 * 0x1p-23;
+    double padDrift = 0.0;
+    for (int it = 0; it < 8; ++it) {                                   // padDrift^2 - k padDrift - 40 k Rp = 0 with k = 4 e(5 Rp), Rp depending on padDrift
+        const double Rp = sup.r + padEval + padDrift;
+        const double k = 4.0 * u3 * (cInf + 5.0 * Rp);
+        padDrift = 1.01 * (0.5 * (k + std::sqrt(k * k + 160.0 * k * Rp)));
+    }
+    h.escR = (float)((sup.r + padEval + padDrift) * (1.0 + 1e-6));
+    auto approach = [&](double rho0) { return (7.5 * std::log(8.0 * rho0 / padDrift) + 1.0) * u3 * (cInf + rho0); };
+    double lo = 0.0, hi = 1e15;                                        // largest start distance whose approach drift stays <= padDrift / 4
+    if (approach(padDrift) > 0.25 * padDrift) hi = 0.0;
+    else { lo = padDrift; for (int it = 0; it < 200; ++it) { const double mid = 0.5 * (lo + hi); (approach(mid) <= 0.25 * padDrift ? lo : hi) = mid; } }
+    h.escRho2 = (float)std::min(lo * lo * (1.0 - 1e-6), 1e30);
+    return cInf;
+}
+
+// Kernel family (FtSceneDev.fastPath; capi.cpp planTrace turns it into the launch's variant) and cull site.
+//   1 (lean)    the program is only staged fast sphere runs + SMOOTH_FIN + SETLEAF
+//   3 (carved)  carvedShape
+//   2 / 0       the general interpreter, with / without on-demand sub-programs (FT_PR_CALL children)
+// The child-culling pass serves ONE sphere run of the main program: the longest staged fast one with at least 32 children and a positive strength.
+static void kernelFamily(FlatScene& out, bool hasCalls) {
+    FtSceneDev& h = out.hdr;
+    bool lean = !out.instr.empty() && h.nInstr == out.instr.size();
+    for (const FtInstr& in : out.instr) {
+        if (in.op == FT_OP_SMOOTH_RUN) lean = lean && (in.flags & FT_FLAG_FAST) && in.dst == 0 && in.data + 4u * in.count <= h.nStage;
+        else if (in.op == FT_OP_SMOOTH_FIN || in.op == FT_OP_SETLEAF) lean = lean && in.dst == 0;
+        else lean = false;
+    }
+    h.fastPath = lean ? 1u : (hasCalls ? 2u : 0u);
+    for (uint32_t pc = 0, best = 0; pc < h.nInstr; ++pc) {
+        const FtInstr& in = out.instr[pc];
+        if (in.op == FT_OP_SMOOTH_RUN && (in.flags & FT_FLAG_FAST) && in.count >= 32u && in.count > best && in.f0 < 0.0f && in.data + 4u * in.count <= h.nStage) { best = in.count; h.cullPc = pc; }
+    }
+    if (h.fastPath == 0u && carvedShape(out)) h.fastPath = 3u;
+}
+
+// What the occlusion certificate takes over from the miss certificate's derivation, as computed there (ok: the scene has a miss certificate)
+struct CertTerms { bool ok; double strength, escR, u, Rb, e3, eGeo, eSum; };
+
+// Miss certificate (kernels.hip ft_miss_certificate), for a program that is ONE smooth union of staged spheres:  f(x) = -s ln sum_i exp(si d_i(x)),
+// si = -1 / s, d_i(x) = |x - c_i| - r_i  (SdfForm.fs:75-82).  On a segment S every d_i(x) >= dmin_i = dist(S, c_i) - r_i, and si < 0, so
+//     f(x) >= F_lo(S) = -s ln sum_i exp(si dmin_i)    for every x on S,  and  f(x) >= F_lo(S) - delta  within delta of S.
+// The kernel ends a ray as a miss when F_lo of the rest of its line, clipped to the ball where the support sphere does not decide already, is at
+// least epsilon + certM.  What certM has to cover (u = 2^-24; escR, Rp as in "drift of the marched points" above; n children):
+//   (1) the drift of the marched points: a tube of radius delta around the line;
+//   (2) a step length h: every evaluation must return >= g = epsilon + h, so that steps cannot get short and the drift stays bounded;
+//   (3) the float32 evaluation of the reference (distances, sum, exp, log) and the certificate's own float32 arithmetic.
+// The drift bound (the same per-step error e(rho) = 3 * 2^-23 (|c|inf + rho) as above).  The kernel certifies rays with 0 <= epsilon <= escR,
+// 0.81 <= |dir|^2 <= 1.44 (a = |dir| in [0.9, 1.2]) that start within Rb = 2.5 escR of c (certRho2).  Suppose the drift so far is <= delta.
+//   * An evaluated point q with |q - c| >= r + padEval + g is no hit and returns >= g by the support property and padEval.  Any other q lies within
+//     delta of a line point p with |p - c| < r + padEval + g + delta <= escR + epsilon + h + delta (= the clip radius: certClip = h + delta) and
+//     parameter t in [0, Length * certLenF) (below): p is on the certified segment, so f(q) >= F_lo - delta and the float32 value is >= F_lo - delta - (3)
+//     >= epsilon + h.  Every step is >= g >= h; no step is a hit.
+//   * Steps that start inside the ball B(c, Rb): consecutive starts are >= a h apart along a chord of length <= 2 (Rb + delta), so there are at most
+//     N = 2 (Rb + delta) / (0.9 h) + 1 of them.  A step is at most |q - c| + escR + padEval <= 1.5 Rb long (Distance <= the nearest child's distance), so
+//     start and end lie within 3 Rb of c: each adds <= e(3 Rb).  delta = h is the root of  N e(3 Rb) = delta  (times 1.01).
+//   * The line leaves B(c, Rb) once, moving away: from there every point is >= rho - delta - (r + padEval) >= rho - 2 escR >= 0.2 rho farther from the
+//     support sphere than epsilon allows, steps are >= 0.19 rho, rho grows by >= 1.014 per step, and the errors of these receding steps form a geometric
+//     series <= 72 e(rho) <= 0.011 rho (|c|inf <= 1000 Rp) < 0.2 rho: no hit out there either.
+//   * Length: the reference counts Length down in float32, each step rounding by <= u Length, so an evaluated point's exact parameter is < Length (1 + N 2u):
+//     certLenF.  Steps left: <= N + 2000 receding ones (Length < 1e9): certSteps, so that no step-cap flag can be lost.
+// (3): distances on either side: <= 8u (|c_i - q| + |r_i|) for the reference's sqrt(sum of squares) - r, <= 16u (|escC|inf + 10 escR) for the certificate's
+// segment point and projection; the kernel's clip radius is enlarged by 0.1 %, which covers the rounding of its end points.  Relative errors of the
+// sums: n + 2 roundings of the reference's float sum, <= 1 ulp for each exp (the fixed ft_exp 0.93 ulp, glibc's expf < 1), log 0.51 ulp; the certificate's
+// v_exp_f32 / v_sqrt_f32 (1 ulp), its own sum (n roundings), terms below 2^-126 flushed (their sum < n 2^-26 of a threshold >= 2^-100), and the threshold
+// (scaled by 1 - 1e-4): at most (2n + 4096) 2^-23 + 2e-4 of the sum, which is s times that in distance.
+// Cluster bound (runs of >= 32 children; certClusters, kernels.hip ft_miss_certificate): the certificate may replace the terms of a cluster's members
+// by n_c exp(si (dist(S, C) - R)) with R >= |c_i - C| + r_i for each member.  By the triangle inequality dist(S, c_i) - r_i >= dist(S, C) - R, and
+// si < 0, so the cluster term is >= the sum of its members' exact terms, and any mix of cluster terms and member terms bounds the sum from above.
+// The margin needs nothing new: the cluster's centre is a float32 mean of its members' centres, so its distance to the segment carries the same
+// error as a child's (<= 8u (|C - q| + R) and 16u (|escC|inf + 10 escR)); R is computed in double from the stored float32 values, padded by
+// 1e-6 and rounded up; the cluster term is one more exp (1 ulp) and one multiply by n_c (exact count, one rounding); flushed cluster terms lose
+// < n 2^-126 in all, as flushed child terms do; the total gets at most K <= 32 more roundings (the unmarked bounds are summed apart from the exact
+// terms and added once).  All of it stays inside the (2n + 4096) 2^-23 budget of eSum, so certM and the other constants keep their values.
+static CertTerms missCertificate(FlatScene& out, double escCInf) {
+    FtSceneDev& h = out.hdr;
+    if (!(h.fastPath == 1u && escCInf >= 0.0 && h.escR >= 0.0f && out.instr.size() == 3 && h.nInstr == 3)) return CertTerms{};
+    const FtInstr& run = out.instr[0];
+    const bool shape = run.op == FT_OP_SMOOTH_RUN && (run.flags & FT_FLAG_INIT) && (run.flags & FT_FLAG_FAST) && run.count >= 1u && run.f0 < 0.0f &&
+                       std::isfinite(run.f0) && run.data + 4u * run.count <= h.nStage &&
+                       out.instr[1].op == FT_OP_SMOOTH_FIN && out.instr[2].op == FT_OP_SETLEAF;
+    const double strength = shape ? (double)out.instr[1].f0 : 0.0;
+    if (!(shape && strength > 0.0 && std::isfinite(strength))) return CertTerms{};
+    const double escR = h.escR, u = 0x1p-24;
+    const double Rb = 2.5 * escR * 1.001;                              // the start gate compares |w|^2 in float32
+    const double e3 = 3.0 * 0x1p-23 * (escCInf + 3.0 * Rb);
+    // 0.9 delta^2 = 2 e (Rb + delta) + 0.9 e delta
+    const double delta = 1.01 * ((2.9 * e3) + std::sqrt(2.9 * e3 * 2.9 * e3 + 7.2 * e3 * Rb)) / 1.8;
+    const double hh = delta;
+    const double N = 2.0 * (Rb + delta) / (0.9 * hh) + 1.0;
+    const double eGeo = 8.0 * u * (3.0 * escR + 2.0 * escR) + 16.0 * u * (escCInf + 10.0 * escR);
+    const double eSum = strength * ((2.0 * run.count + 4096.0) * 0x1p-23 + 2e-4);
+    const double M = (delta + hh + 2.0 * eGeo + eSum) * 1.01 + 1e-6;
+    if (!(N + 2000.0 < 0.25 * FT_STEP_CAP && M < 0.5 * escR)) return CertTerms{};
+    h.certM = (float)(M * (1.0 + 1e-6));
+    h.certClip = (float)((delta + hh) * (1.0 + 1e-6));
+    h.certRho2 = (float)(2.5 * escR * 2.5 * escR);
+    h.certLenF = (float)(1.0 + (N + 2.0) * 4.0 * u);
+    h.certSteps = (uint32_t)(N + 2000.0);
+    if (run.count >= 32u) certClusters(&out.consts[run.data], run.count, out.certCl, h.certK);
+    return CertTerms{true, strength, escR, u, Rb, e3, eGeo, eSum};
+}
+
+// Occlusion certificate (kernels.hip ft_occlusion_certificate): a shadow ray's hit carries one bit, so that its march ENDS IN A HIT may be
+// proved from its line as well.  f is 1-Lipschitz (its gradient is a convex mix of unit vectors) and f <= min_i d_i (si < 0: the sum is at
+// least its largest term).  Let the ray stand at o with direction dir, |dir|^2 <= 1 + 1e-6, remaining Length len, and let the line have a
+// parameter t* >= 0 with  t* occLenF < len  and  f(y*) <= -hitM  at y* = o + t* dir.  The kernel shows such a point in two ways: one child with
+// d_i(y*) <= -hitM, or a witness y with f(y) <= -D (evaluated there, errors as e_eval below) within D - hitM of y*.
+// T_k: the sum of the steps taken so far (real numbers), p_k the marched float32 point, x_k = o + T_k dir.  Invariant: T_k <= t*.
+//   * Every evaluation that is no hit returns >= epsilon, so at most t* / epsilon steps are taken while T <= t*; each adds at most
+//     e(3 Rb) to the drift (start within Rb of c as above, y* inside the support sphere since f(y*) < 0, so the line between them stays within Rb, steps
+//     are <= t* <= tMax = (Rb + escR) / 0.9 long, the drift itself stays below occCap = escR / 20):  |p_k - x_k| <= delta_h = (t* / epsilon) e.
+//   * The reference's value at p_k is at most  f(y*) + |p_k - y*| + e_eval <= -hitM + (t* - T_k) |dir| + delta_h + e_eval.  With
+//     hitM >= delta_h + e_eval + 1e-6 tMax (|dir| - 1 <= 5.1e-7) it is <= t* - T_k: either it is below epsilon — the hit — or
+//     T_k+1 = T_k + value <= t*.  At T_k = t* the value is <= 0 < epsilon.  So the march cannot pass t* and must end in a hit there or before.
+//   * Length: the float32 count-down loses <= u len per step, so after k <= Ncap = 2^17 steps it is still > len (1 - Ncap u) - t* > 0
+//     by occLenF = 1 + (Ncap + 2) 4u; the kernel holds t* / epsilon + 2 below Ncap and the ray's steps below half the step cap: no
+//     cap flag is lost.  No NaN: every d_i >= -r_i, so an exp argument is at most rMax / s <= 60 and the sum stays finite.
+//   * Underflow: the reference returns -Log(sum) s, and a float32 sum whose every term has flushed to 0 gives +inf — a miss, whatever f is.  The kernel
+//     takes only t* <= occReach = 100 ln 2 s - occCap.  By the invariant every marched point has f(p_k) <= (t* - T_k) |dir| + delta_h <= t* + occCap,
+//     so the true sum there is exp(-f / s) >= 2^-100: its largest term is a normal number >= 2^-100 / n with an exp argument of at most 70 + ln n in
+//     size (argument rounding inside eSum's 4096 2^-23), and what the terms below 2^-126 lose by being flushed is < n 2^-26 of the sum, which eSum
+//     carries as it does for the miss certificate's threshold.  Log and the product with s round a value of size <= t* + occCap: 2u tMax, inside
+//     the 1e-6 tMax of occB next to the 5.1e-7 tMax that |dir| needs.
+//   e_eval: the reference's float32 evaluation (eGeo's first term, eSum as above) and the kernel's closest approach and distance in
+//   float32 (eGeo's second term; its comparison carries 0.1 % more): occB = (2 eGeo + eSum + 1e-6 tMax) 1.01 + 1e-6.  The kernel forms
+//   hitM = occE (t* / epsilon + 2) + occB per lane from its own t*, occE = 1.01 e, and tries only epsilon >= occEpsMin, where hitM <= occCap
+//   and the step bound hold for every t* <= tMax.
+static void occlusionCertificate(FlatScene& out, const CertTerms& t) {
+    if (!t.ok) return;
+    const FtInstr& run = out.instr[0];
+    const double strength = t.strength, escR = t.escR, u = t.u, Rb = t.Rb, e3 = t.e3, eGeo = t.eGeo, eSum = t.eSum;
+    double rMax = 0.0;
+    for (uint32_t i = 0; i < run.count; ++i) rMax = std::max(rMax, std::fabs((double)out.consts[run.data + 4u * i + 3u]));
+    const double tMax = (Rb + escR) / 0.9, nCap = 131072.0;
+    const double occE = 1.01 * e3, occB = (2.0 * eGeo + eSum + 1e-6 * tMax) * 1.01 + 1e-6, occCap = 0.05 * escR;
+    const double occReach = 100.0 * 0.6931471805599453 * strength - occCap;
+    if (!(rMax <= 60.0 * strength && 2.0 * occB + 4.0 * occE < occCap && occReach > 0.0)) return;
+    out.occ.e = (float)(occE * (1.0 + 1e-6));
+    out.occ.b = (float)(occB * (1.0 + 1e-6));
+    out.occ.cap = (float)(occCap * (1.0 - 1e-6));
+    out.occ.epsMin = (float)(1.01 * std::max(tMax * occE / (occCap - occB - 2.0 * occE), tMax / (nCap - 4.0)));
+    out.occ.lenInv = (float)((1.0 - 1e-6) / (1.0 + (nCap + 2.0) * 4.0 * u));
+    out.occ.reach = (float)(occReach * (1.0 - 1e-6));
+    out.occ.near = (float)(strength * std::log((double)run.count) * 1.001 + occB);   // f(x) <= 0 needs one d_i(x) <= s ln n: the try's cheap exit, nothing rests on it
+}
+
+// Flatten: run the Flattener over the tree, decide the exact shortcuts' constants step by step (each step above carries its proof), append lights,
+// materials and padding.
 bool flatten(const Builder& b, int object, const float bg[3], const int* lights, int nLights, FlatScene& out, std::string& err) {
     if (!b.okObject(object)) { err = "invalid object handle"; return false; }
     out = FlatScene{};
     Flattener fl(b, out, err);
     if (!fl.emitObject(object, 0)) return false;
     fl.linkCalls();
-    out.boundary = b.forms[b.objects[object].form].boundary;
-    out.nSlots = fl.maxSlot + 1;
-    out.nStage = fl.stageEnd <= FT_MAX_STAGE_FLOATS ? fl.stageEnd : FT_MAX_STAGE_FLOATS;
-    out.nearR2 = (fl.stageEnd > 0 && fl.nearR > 0.0 && fl.nearR < 1e29) ? (float)(fl.nearR * fl.nearR * (1.0 - 1e-5)) : 0.0f;
-    out.fastQ = (fl.anyUnion && fl.unionFastQ) ? 1u : 0u;
-    // The sphere no hit can lie outside of (see supportOf), padded twice:
-    //   padEval  — what a float32 evaluation may differ from the exact value: 0.1 % of the radius, 0.01, and 0.1 % of the centre's coordinates;
-    //   padDrift — "drift of the marched points".  The reference moves the ray's origin step by step in float32 (Ray.fs:9-13: Origin + Direction * d), so the
-    //     points it evaluates leave the line the shortcut reasons about (kernels.hip ft_never_enters).  One step that starts or ends at most rho from the centre c
-    //     adds at most e(rho) = 3 * 2^-23 * (|c|inf + rho) to that drift (per component: the rounding of a product <= 2 rho and of a sum <= |c|inf + rho).
-    //     Let Rp = r + padEval + padDrift (= escR), a = |Direction| >= 1/2, 0 <= epsilon <= Rp, and suppose the drift so far is <= padDrift / 2.  The line stays
-    //     >= Rp + epsilon from c, so every evaluated point is >= r + padEval + epsilon + padDrift / 2 from c: no hit there, and each step is d >= g = epsilon + padDrift / 2
-    //     (support property), i.e. moves a d >= padDrift / 4 along the line.  Three kinds of steps:
-    //       near      (start and end within 5 Rp of c — that is >= 2.5 (Rp + epsilon)): the line's chord through that ball is <= 10 Rp long: at most 40 Rp / padDrift + 1
-    //                 steps of error <= e(5 Rp) each.  padDrift is the root of  (40 Rp / padDrift + 1) e(5 Rp) = padDrift / 4.
-    //       approach  (start farther than 5 Rp, before the near steps): d >= rho - Rp - epsilon >= rho / 2 moves >= rho / 4 along a line of which at most 2 rho are left
-    //                 to the near ball, so that length shrinks by 7/8 per step: N(rho0) = 7.5 ln(8 rho0 / padDrift) + 1 steps from a start at rho0, each
-    //                 <= e(rho0).  The kernel takes the shortcut only from starts with N(rho0) e(rho0) <= padDrift / 4 (escRho2, by bisection below).
-    //       receding  (rho >= 5 Rp, moving away): rho grows by >= sqrt(1 + a^2 / 4) >= 1.03 per step, so the errors of the steps so far form a geometric series
-    //                 <= 34 e-terms of the last one: < 1.3e-5 rho + 1.2e-5 |c|inf ln(rho / 5 Rp) <= rho / 50 (|c|inf <= 1000 Rp: padEval), against a margin
-    //                 rho - (r + padEval + epsilon) >= rho - 2 Rp >= 0.6 rho.
-    //     Near and approach together stay <= padDrift / 2: the supposition holds step after step, every evaluated point keeps its distance, no step can be a hit.
-    //     (Short rays — kernels.hip: Length <= 10 escR, the whole march within 2.5 escR of c — make at most Length / g + 1 <= 20 Rp / padDrift + 1 steps of error
-    //     <= e(2.5 Rp): inside the near budget whatever |Direction| is.)
-    Support sup;
-    double escCInf = -1.0;                                             // |escC|inf where a support sphere is known (the miss certificate below)
-    if (finiteTree(b, b.objects[object].form) && supportOf(b, b.objects[object].form, sup) && sup.r < 1e15 && std::fabs(sup.c[0]) + std::fabs(sup.c[1]) + std::fabs(sup.c[2]) < 1e15) {
-        out.escC[0] = (float)sup.c[0]; out.escC[1] = (float)sup.c[1]; out.escC[2] = (float)sup.c[2];
-        const double cInf = std::max(std::fabs(sup.c[0]), std::max(std::fabs(sup.c[1]), std::fabs(sup.c[2])));
-        const double padEval = sup.r * 0.001 + 0.01 + 1e-3 * (std::fabs(sup.c[0]) + std::fabs(sup.c[1]) + std::fabs(sup.c[2]));
-        const double u3 = 3.0 * 0x1p-23;
-        double padDrift = 0.0;
-        for (int it = 0; it < 8; ++it) {                               // padDrift^2 - k padDrift - 40 k Rp = 0 with k = 4 e(5 Rp), Rp depending on padDrift
-            const double Rp = sup.r + padEval + padDrift;
-            const double k = 4.0 * u3 * (cInf + 5.0 * Rp);
-            padDrift = 1.01 * (0.5 * (k + std::sqrt(k * k + 160.0 * k * Rp)));
-        }
-        out.escR = (float)((sup.r + padEval + padDrift) * (1.0 + 1e-6));
-        escCInf = cInf;
-        auto approach = [&](double rho0) { return (7.5 * std::log(8.0 * rho0 / padDrift) + 1.0) * u3 * (cInf + rho0); };
-        double lo = 0.0, hi = 1e15;                                    // largest start distance whose approach drift stays <= padDrift / 4
-        if (approach(padDrift) > 0.25 * padDrift) hi = 0.0;
-        else { lo = padDrift; for (int it = 0; it < 200; ++it) { const double mid = 0.5 * (lo + hi); (approach(mid) <= 0.25 * padDrift ? lo : hi) = mid; } }
-        out.escRho2 = (float)std::min(lo * lo * (1.0 - 1e-6), 1e30);
-    }
-    // kernel variant: 1 = the program is only staged fast sphere runs + SMOOTH_FIN + SETLEAF
-    bool lean = !out.instr.empty() && out.nMainInstr == out.instr.size();
-    for (const FtInstr& in : out.instr) {
-        if (in.op == FT_OP_SMOOTH_RUN) lean = lean && (in.flags & FT_FLAG_FAST) && in.dst == 0 && in.data + 4u * in.count <= out.nStage;
-        else if (in.op == FT_OP_SMOOTH_FIN || in.op == FT_OP_SETLEAF) lean = lean && in.dst == 0;
-        else lean = false;
-    }
-    out.fastPath = lean ? 1u : (fl.calls.empty() ? 0u : 2u);     // kernel variant (ft_launch_trace)
-    // the child-culling pass serves ONE sphere run of the main program: the longest staged fast one with at least 32 children and a positive strength
-    for (uint32_t pc = 0, best = 0; pc < out.nMainInstr; ++pc) {
-        const FtInstr& in = out.instr[pc];
-        if (in.op == FT_OP_SMOOTH_RUN && (in.flags & FT_FLAG_FAST) && in.count >= 32u && in.count > best && in.f0 < 0.0f && in.data + 4u * in.count <= out.nStage) { best = in.count; out.cullPc = pc; }
-    }
-    if (out.fastPath == 0u && carvedShape(out)) out.fastPath = 3u;
-    // Miss certificate (kernels.hip ft_miss_certificate), for a program that is ONE smooth union of staged spheres:  f(x) = -s ln sum_i exp(si d_i(x)),
-    // si = -1 / s, d_i(x) = |x - c_i| - r_i  (SdfForm.fs:75-82).  On a segment S every d_i(x) >= dmin_i = dist(S, c_i) - r_i, and si < 0, so
-    //     f(x) >= F_lo(S) = -s ln sum_i exp(si dmin_i)    for every x on S,  and  f(x) >= F_lo(S) - delta  within delta of S.
-    // The kernel ends a ray as a miss when F_lo of the rest of its line, clipped to the ball where the support sphere does not decide already, is at
-    // least epsilon + certM.  What certM has to cover (u = 2^-24; escR, Rp as in "drift of the marched points" above; n children):
-    //   (1) the drift of the marched points: a tube of radius delta around the line;
-    //   (2) a step length h: every evaluation must return >= g = epsilon + h, so that steps cannot get short and the drift stays bounded;
-    //   (3) the float32 evaluation of the reference (distances, sum, exp, log) and the certificate's own float32 arithmetic.
-    // The drift bound (the same per-step error e(rho) = 3 * 2^-23 (|c|inf + rho) as above).  The kernel certifies rays with 0 <= epsilon <= escR,
-    // 0.81 <= |dir|^2 <= 1.44 (a = |dir| in [0.9, 1.2]) that start within Rb = 2.5 escR of c (certRho2).  Suppose the drift so far is <= delta.
-    //   * An evaluated point q with |q - c| >= r + padEval + g is no hit and returns >= g by the support property and padEval.  Any other q lies within
-    //     delta of a line point p with |p - c| < r + padEval + g + delta <= escR + epsilon + h + delta (= the clip radius: certClip = h + delta) and
-    //     parameter t in [0, Length * certLenF) (below): p is on the certified segment, so f(q) >= F_lo - delta and the float32 value is >= F_lo - delta - (3)
-    //     >= epsilon + h.  Every step is >= g >= h; no step is a hit.
-    //   * Steps that start inside the ball B(c, Rb): consecutive starts are >= a h apart along a chord of length <= 2 (Rb + delta), so there are at most
-    //     N = 2 (Rb + delta) / (0.9 h) + 1 of them.  A step is at most |q - c| + escR + padEval <= 1.5 Rb long (Distance <= the nearest child's distance), so
-    //     start and end lie within 3 Rb of c: each adds <= e(3 Rb).  delta = h is the root of  N e(3 Rb) = delta  (times 1.01).
-    //   * The line leaves B(c, Rb) once, moving away: from there every point is >= rho - delta - (r + padEval) >= rho - 2 escR >= 0.2 rho farther from the
-    //     support sphere than epsilon allows, steps are >= 0.19 rho, rho grows by >= 1.014 per step, and the errors of these receding steps form a geometric
-    //     series <= 72 e(rho) <= 0.011 rho (|c|inf <= 1000 Rp) < 0.2 rho: no hit out there either.
-    //   * Length: the reference counts Length down in float32, each step rounding by <= u Length, so an evaluated point's exact parameter is < Length (1 + N 2u):
-    //     certLenF.  Steps left: <= N + 2000 receding ones (Length < 1e9): certSteps, so that no step-cap flag can be lost.
-    // (3): distances on either side: <= 8u (|c_i - q| + |r_i|) for the reference's sqrt(sum of squares) - r, <= 16u (|escC|inf + 10 escR) for the certificate's
-    // segment point and projection; the kernel's clip radius is enlarged by 0.1 %, which covers the rounding of its end points.  Relative errors of the
-    // sums: n + 2 roundings of the reference's float sum, <= 1 ulp for each exp (the fixed ft_exp 0.93 ulp, glibc's expf < 1), log 0.51 ulp; the certificate's
-    // v_exp_f32 / v_sqrt_f32 (1 ulp), its own sum (n roundings), terms below 2^-126 flushed (their sum < n 2^-26 of a threshold >= 2^-100), and the threshold
-    // (scaled by 1 - 1e-4): at most (2n + 4096) 2^-23 + 2e-4 of the sum, which is s times that in distance.
-    // Cluster bound (runs of >= 32 children; certClusters, kernels.hip ft_miss_certificate): the certificate may replace the terms of a cluster's members
-    // by n_c exp(si (dist(S, C) - R)) with R >= |c_i - C| + r_i for each member.  By the triangle inequality dist(S, c_i) - r_i >= dist(S, C) - R, and
-    // si < 0, so the cluster term is >= the sum of its members' exact terms, and any mix of cluster terms and member terms bounds the sum from above.
-    // The margin needs nothing new: the cluster's centre is a float32 mean of its members' centres, so its distance to the segment carries the same
-    // error as a child's (<= 8u (|C - q| + R) and 16u (|escC|inf + 10 escR)); R is computed in double from the stored float32 values, padded by
-    // 1e-6 and rounded up; the cluster term is one more exp (1 ulp) and one multiply by n_c (exact count, one rounding); flushed cluster terms lose
-    // < n 2^-126 in all, as flushed child terms do; the total gets at most K <= 32 more roundings (the unmarked bounds are summed apart from the exact
-    // terms and added once).  All of it stays inside the (2n + 4096) 2^-23 budget of eSum, so certM and the other constants keep their values.
-    if (out.fastPath == 1u && escCInf >= 0.0 && out.escR >= 0.0f && out.instr.size() == 3 && out.nMainInstr == 3) {
-        const FtInstr& run = out.instr[0];
-        const bool shape = run.op == FT_OP_SMOOTH_RUN && (run.flags & FT_FLAG_INIT) && (run.flags & FT_FLAG_FAST) && run.count >= 1u && run.f0 < 0.0f &&
-                           std::isfinite(run.f0) && run.data + 4u * run.count <= out.nStage &&
-                           out.instr[1].op == FT_OP_SMOOTH_FIN && out.instr[2].op == FT_OP_SETLEAF;
-        const double strength = shape ? (double)out.instr[1].f0 : 0.0;
-        if (shape && strength > 0.0 && std::isfinite(strength)) {
-            const double escR = out.escR, u = 0x1p-24;
-            const double Rb = 2.5 * escR * 1.001;                      // the start gate compares |w|^2 in float32
-            const double e3 = 3.0 * 0x1p-23 * (escCInf + 3.0 * Rb);
-            // 0.9 delta^2 = 2 e (Rb + delta) + 0.9 e delta
-            const double delta = 1.01 * ((2.9 * e3) + std::sqrt(2.9 * e3 * 2.9 * e3 + 7.2 * e3 * Rb)) / 1.8;
-            const double h = delta;
-            const double N = 2.0 * (Rb + delta) / (0.9 * h) + 1.0;
-            const double eGeo = 8.0 * u * (3.0 * escR + 2.0 * escR) + 16.0 * u * (escCInf + 10.0 * escR);
-            const double eSum = strength * ((2.0 * run.count + 4096.0) * 0x1p-23 + 2e-4);
-            const double M = (delta + h + 2.0 * eGeo + eSum) * 1.01 + 1e-6;
-            if (N + 2000.0 < 0.25 * FT_STEP_CAP && M < 0.5 * escR) {
-                out.certM = (float)(M * (1.0 + 1e-6));
-                out.certClip = (float)((delta + h) * (1.0 + 1e-6));
-                out.certRho2 = (float)(2.5 * escR * 2.5 * escR);
-                out.certLenF = (float)(1.0 + (N + 2.0) * 4.0 * u);
-                out.certSteps = (uint32_t)(N + 2000.0);
-                if (run.count >= 32u) certClusters(&out.consts[run.data], run.count, out.certCl, out.certK);
-                // Occlusion certificate (kernels.hip ft_occlusion_certificate): a shadow ray's hit carries one bit, so that its march ENDS IN A HIT may be
-                // proved from its line as well.  f is 1-Lipschitz (its gradient is a convex mix of unit vectors) and f <= min_i d_i (si < 0: the sum is at
-                // least its largest term).  Let the ray stand at o with direction dir, |dir|^2 <= 1 + 1e-6, remaining Length len, and let the line have a
-                // parameter t* >= 0 with  t* occLenF < len  and  f(y*) <= -hitM  at y* = o + t* dir.  The kernel shows such a point in two ways: one child with
-                // d_i(y*) <= -hitM, or a witness y with f(y) <= -D (evaluated there, errors as e_eval below) within D - hitM of y*.
-                // T_k: the sum of the steps taken so far (real numbers), p_k the marched float32 point, x_k = o + T_k dir.  Invariant: T_k <= t*.
-                //   * Every evaluation that is no hit returns >= epsilon, so at most t* / epsilon steps are taken while T <= t*; each adds at most
-                //     e(3 Rb) to the drift (start within Rb of c as above, y* inside the support sphere since f(y*) < 0, so the line between them stays within Rb, steps
-                //     are <= t* <= tMax = (Rb + escR) / 0.9 long, the drift itself stays below occCap = escR / 20):  |p_k - x_k| <= delta_h = (t* / epsilon) e.
-                //   * The reference's value at p_k is at most  f(y*) + |p_k - y*| + e_eval <= -hitM + (t* - T_k) |dir| + delta_h + e_eval.  With
-                //     hitM >= delta_h + e_eval + 1e-6 tMax (|dir| - 1 <= 5.1e-7) it is <= t* - T_k: either it is below epsilon — the hit — or
-                //     T_k+1 = T_k + value <= t*.  At T_k = t* the value is <= 0 < epsilon.  So the march cannot pass t* and must end in a hit there or before.
-                //   * Length: the float32 count-down loses <= u len per step, so after k <= Ncap = 2^17 steps it is still > len (1 - Ncap u) - t* > 0
-                //     by occLenF = 1 + (Ncap + 2) 4u; the kernel holds t* / epsilon + 2 below Ncap and the ray's steps below half the step cap: no
-                //     cap flag is lost.  No NaN: every d_i >= -r_i, so an exp argument is at most rMax / s <= 60 and the sum stays finite.
-                //   * Underflow: the reference returns -Log(sum) s, and a float32 sum whose every term has flushed to 0 gives +inf — a miss, whatever f is.  The kernel
-                //     takes only t* <= occReach = 100 ln 2 s - occCap.  By the invariant every marched point has f(p_k) <= (t* - T_k) |dir| + delta_h <= t* + occCap,
-                //     so the true sum there is exp(-f / s) >= 2^-100: its largest term is a normal number >= 2^-100 / n with an exp argument of at most 70 + ln n in
-                //     size (argument rounding inside eSum's 4096 2^-23), and what the terms below 2^-126 lose by being flushed is < n 2^-26 of the sum, which eSum
-                //     carries as it does for the miss certificate's threshold.  Log and the product with s round a value of size <= t* + occCap: 2u tMax, inside
-                //     the 1e-6 tMax of occB next to the 5.1e-7 tMax that |dir| needs.
-                //   e_eval: the reference's float32 evaluation (eGeo's first term, eSum as above) and the kernel's closest approach and distance in
-                //   float32 (eGeo's second term; its comparison carries 0.1 % more): occB = (2 eGeo + eSum + 1e-6 tMax) 1.01 + 1e-6.  The kernel forms
-                //   hitM = occE (t* / epsilon + 2) + occB per lane from its own t*, occE = 1.01 e, and tries only epsilon >= occEpsMin, where hitM <= occCap
-                //   and the step bound hold for every t* <= tMax.
-                double rMax = 0.0;
-                for (uint32_t i = 0; i < run.count; ++i) rMax = std::max(rMax, std::fabs((double)out.consts[run.data + 4u * i + 3u]));
-                const double tMax = (Rb + escR) / 0.9, nCap = 131072.0;
-                const double occE = 1.01 * e3, occB = (2.0 * eGeo + eSum + 1e-6 * tMax) * 1.01 + 1e-6, occCap = 0.05 * escR;
-                const double occReach = 100.0 * 0.6931471805599453 * strength - occCap;
-                if (rMax <= 60.0 * strength && 2.0 * occB + 4.0 * occE < occCap && occReach > 0.0) {
-                    out.occE = (float)(occE * (1.0 + 1e-6));
-                    out.occB = (float)(occB * (1.0 + 1e-6));
-                    out.occCap = (float)(occCap * (1.0 - 1e-6));
-                    out.occEpsMin = (float)(1.01 * std::max(tMax * occE / (occCap - occB - 2.0 * occE), tMax / (nCap - 4.0)));
-                    out.occLenInv = (float)((1.0 - 1e-6) / (1.0 + (nCap + 2.0) * 4.0 * u));
-                    out.occReach = (float)(occReach * (1.0 - 1e-6));
-                    out.occNear = (float)(strength * std::log((double)run.count) * 1.001 + occB);   // f(x) <= 0 needs one d_i(x) <= s ln n: the try's cheap exit, nothing rests on it
-                }
-            }
-        }
-    }
+    const int form = b.objects[object].form;
+    FtSceneDev& h = out.hdr;
+    out.boundary = b.forms[form].boundary;
+    h.nSlots = fl.maxSlot + 1;
+    h.nStage = fl.stageEnd <= FT_MAX_STAGE_FLOATS ? fl.stageEnd : FT_MAX_STAGE_FLOATS;
+    h.nearR2 = (fl.stageEnd > 0 && fl.nearR > 0.0 && fl.nearR < 1e29) ? (float)(fl.nearR * fl.nearR * (1.0 - 1e-5)) : 0.0f;
+    h.fastQ = (fl.anyUnion && fl.unionFastQ) ? 1u : 0u;
+    const double escCInf = supportSphere(b, form, h);
+    kernelFamily(out, !fl.calls.empty());
+    occlusionCertificate(out, missCertificate(out, escCInf));
     for (int i = 0; i < nLights; ++i) {
         if (lights[i] < 0 || (size_t)lights[i] >= b.lights.size()) { err = "invalid light handle"; return false; }
         out.lights.push_back(b.lights[lights[i]].dev);
     }
+    h.bg[0] = bg[0]; h.bg[1] = bg[1]; h.bg[2] = bg[2];
     if (out.materials.empty()) { out.materials.assign(3, 0.0f); out.materialsExt.assign(4, 0.0f); out.materialHandles.assign(1, -1); }           // a form-only union under no create(): index 0 must exist
-    out.bg[0] = bg[0]; out.bg[1] = bg[1]; out.bg[2] = bg[2];
     if (out.cellStart.empty()) out.cellStart.push_back(0);
     // keep every pool non-empty and padded so device-side wide loads never run off the end
     for (int i = 0; i < 64; ++i) out.consts.push_back(0.0f);

@@ -85,38 +85,27 @@ struct Builder {                                              // one per ft_ctx
 };
 
 struct FlatScene {                                            // host copy of everything that goes to HBM
-    std::vector<FtInstr> instr;                               // main program [0, nMainInstr), then the sub-programs of call children
-    uint32_t nMainInstr = 0;
-    std::vector<float> consts;
+    // Every scalar the kernels get with the scene, in the form they get it (ft_device.h FtSceneDev, where each is described): flatten() decides them, the
+    // upload adds the device pointers (null here) and a launch its own mathFma.  nInstr: the main program; escR = -1: no support sphere; certM = -1: no
+    // miss certificate; cullPc = 0xffffffff: no cull site.
+    static FtSceneDev noShortcuts() { FtSceneDev d{}; d.nSlots = 1; d.escR = -1.0f; d.certM = -1.0f; d.certLenF = 1.0f; d.cullPc = 0xffffffffu; return d; }
+    FtSceneDev hdr = noShortcuts();
+    FtOccl occ{0.0f, -1.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};    // occlusion certificate (scene.cpp "Occlusion certificate"); b = -1: none
+    std::vector<FtInstr> instr;                               // main program [0, hdr.nInstr), then the sub-programs of call children
+    std::vector<float> consts;                                // consts[0, hdr.nStage) is mirrored in LDS by every workgroup
     std::vector<FtGrid> grids;
     std::vector<FtChild> children;
     std::vector<float> cellCenters;
     std::vector<uint32_t> cellStart;                          // global CSR over all cells of all grids (+1)
     std::vector<FtItemRec> items;
-    std::vector<FtLight> lights;
+    std::vector<FtLight> lights;                              // hdr.nLights stays 0: the upload counts them
     std::vector<float> materials;
     std::vector<float> materialsExt;                          // EXTENSION: 4 floats per material (glass flag, ior, dispersion, 0)
     std::vector<int32_t> materialHandles;                     // EXTENSION ft_render_hits: dense material index -> context handle (-1: none)
-    uint32_t nGlass = 0;                                      // glass materials in this scene
-    uint32_t nSlots = 1;
-    uint32_t nStage = 0;                                      // consts[0, nStage) is mirrored in LDS by every workgroup
-    float nearR2 = 0.0f;                                      // see FtSceneDev::nearR2
-    uint32_t fastQ = 0;                                       // see FtSceneDev::fastQ
-    float escC[3] = {0, 0, 0}, escR = -1.0f;                  // see FtSceneDev::escR (support sphere of the scene; -1: none)
-    float escRho2 = 0.0f;                                     // see FtSceneDev::escRho2
-    float certM = -1.0f, certClip = 0.0f, certRho2 = 0.0f, certLenF = 1.0f;   // see FtSceneDev::certM ... (-1: no miss certificate)
-    uint32_t certSteps = 0;
-    // occlusion certificate (scene.cpp "Occlusion certificate"; FtRenderArgs::occE ...): drift per step, the margin's constant part, the smallest epsilon
-    // tried, the largest margin conceded, 1 / the count-down's padding factor, how far from a sphere f can still be <= 0, the largest t* (the float32 sum cannot underflow before it).  occB < 0: none
-    float occE = 0.0f, occB = -1.0f, occEpsMin = 0.0f, occCap = 0.0f, occLenInv = 0.0f, occNear = 0.0f, occReach = 0.0f;
-    std::vector<float> certCl;                               // see FtSceneDev::certCl (scene.cpp certClusters); empty: the certificate's flat loop
-    uint32_t certK = 0;
-    uint32_t cullPc = 0xffffffffu;                            // see FtSceneDev::cullPc
-    uint32_t fastPath = 0;
-    FtCarve carve{};                                          // fastPath == 3 (ft_device.h "Carved union"); the two pointers are set at upload
-    std::vector<FtItemRec> itemsT;                            // fastPath == 3: candidate lists with a terminator per cell
-    std::vector<uint32_t> cellStartT;                         // fastPath == 3: byte offsets into itemsT
-    float bg[3] = {0, 0, 0};
+    std::vector<float> certCl;                                // see FtSceneDev::certCl (scene.cpp certClusters), hdr.certK clusters; empty: the certificate's flat loop
+    FtCarve carve{};                                          // hdr.fastPath == 3 (ft_device.h "Carved union"); the two pointers are set at upload
+    std::vector<FtItemRec> itemsT;                            // hdr.fastPath == 3: candidate lists with a terminator per cell
+    std::vector<uint32_t> cellStartT;                         // hdr.fastPath == 3: byte offsets into itemsT
     Boundary boundary{};                                      // scene.Object.Form.Boundary (ft_sample_*: FT_FIELD_BOUNDED)
 };
 

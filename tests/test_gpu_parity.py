@@ -1636,3 +1636,24 @@ def test_reusing_the_centre_probe_as_a_secondary_rays_first_step_changes_no_pixe
             ds.close()
     finally:
         gpu.set_option("reuse", 1); gpu.set_option("escape", 1)
+
+
+def test_launch_rules_count_what_was_recorded(gpu):
+    """Every rule launchTrace (capi.cpp) applies — kernel plan, grid size, hand-out, the two certificate policy words with the tile-width rule, the
+    occlusion schedule, the tile order — one option at a time from the defaults, and the other launch forms at the defaults, against the counters
+    recorded twice on an MI355X from the library before launchTrace was cut into named steps (tests/golden/launch_counters.json, written by
+    tests/golden/make_launch_counters.py: the cells are cells() there).  Each cell is a function of the tiles alone: a wave owns one tile
+    between two grabs."""
+    import json
+    import os
+    import sys
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
+    import make_launch_counters as pin
+    table = json.load(open(pin.TABLE))
+    assert table["recorded_from_commit"] == "a7fdd52"                  # the parent of the refactor: not the code under test
+    assert table["left_out"] == [] and len(table["cells"]) == 88      # every cell repeated at the parent, so every cell is replayed
+    got = pin.cells(gpu)
+    assert list(got) == list(table["cells"])
+    for name, want in table["cells"].items():
+        print(name, got[name])
+        assert got[name] == want, name

@@ -287,3 +287,29 @@ def test_fuzz_scene_streams():
     assert min(q - p for p, q in zip(pos, pos[1:])) > 10 ** 6, "two scrambled seeds start within a scene's worth of draws of each other"
     late = lambda seed: (lambda r: (r[2].X, r[2].Y, r[3]))(syn.fuzz_scene(seed))            # image size and epsilon: drawn late in the stream
     assert late(base + 7) == late(base + 7)
+
+
+def test_flattener_constants_are_the_recorded_ones(host):
+    """What ft::flatten decides — kernel family, cull site, support sphere, the constants of the miss and the occlusion certificate, the clusters —
+    against the table recorded from the library before flatten() was cut into named steps (tests/golden/flatten_constants.json, written by
+    tests/golden/make_flatten_constants.py: the corpus is named() and fuzzed() there).  Floats bit for bit; of each fuzz scene one SHA-256."""
+    import json
+    import os
+    import sys
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
+    import make_flatten_constants as pin
+    table = json.load(open(pin.TABLE))
+    assert table["recorded_from_commit"] == "a7fdd52"                  # the parent of the refactor: not the code under test
+    scenes, fuzz = pin.corpus(host)
+    assert len(scenes) == 34 and sorted(scenes) == sorted(table["scenes"])
+    assert len(fuzz) == 300 and sorted(fuzz) == sorted(table["fuzz_sha256"])
+    for name, want in table["scenes"].items():
+        assert scenes[name] == want, name
+    wrong = [k for k, v in table["fuzz_sha256"].items() if fuzz[k] != v]
+    assert not wrong, f"{len(wrong)} of {len(fuzz)} fuzz scenes differ; the first: {wrong[:5]}"
+    # the corpus reaches what it is there for: scenes with and without each certificate, with and without clusters, every kernel family
+    some = table["scenes"].values()
+    assert {s["info"]["fast_path"] for s in some} == {0, 1, 2, 3}
+    assert {s["miss_certificate"]["margin"] == "bf800000" for s in some} == {True, False}
+    assert {s["occlusion_certificate"]["base"] == "bf800000" for s in some} == {True, False}
+    assert {len(s["clusters"]) > 0 for s in some if s["info"]["fast_path"] == 1} == {True, False}
