@@ -1588,7 +1588,11 @@ __device__ __forceinline__ bool ft_occlusion_certificate(const FtRenderArgs& a, 
 // The first step of a ray that starts at the hit position, from the distance already known there (FT_SH_D0): exactly what the round's switch does with an
 // evaluated distance for a PH_SHADOW / PH_AO lane (SdfForm.fs:94-104).  -> 0 the ray marches on (s.o, s.len, s.steps advanced), 1 it is a hit at once, 2 it
 // ends as a miss (NaN distance, flagged like there).
+// A ray born with Length <= 0 (ao_radius <= 0; a point light whose distance2 underflows to 0) takes no step from the cache: the reference tests the
+// Length (SdfForm.fs:94-95) before it evaluates anything (:97), so the cached distance — below epsilon or NaN — is never looked at.  -> 0 with nothing
+// advanced; settle()'s PH_AO / PH_SHADOW branch resolves the ray as open / lit.  `<=` and not `!(> 0)`: a NaN Length goes on to evaluate there.
 __device__ __forceinline__ int first_step_from_cache(LaneState& s) {
+    if (s.len <= 0.0f) return 0;                                       // SdfForm.fs:94-95
     const float d = *ft_sh(FT_SH_D0);
     if (d != d) { ft_flag(1u); return 2; }                             // reference would never terminate
     if (d < s.eps) return 1;                                           // SdfForm.fs:98

@@ -75,7 +75,8 @@ typedef struct ft_render_params {
     int32_t spp;                  /* 1 = the reference (one corner sample). >1 is an EXTENSION. */
     float epsilon, length;        /* Image.render's first two arguments */
     int32_t ao_samples;           /* 0 = the reference. >0: EXTENSION ambient-occlusion rays */
-    float ao_radius;
+    float ao_radius;              /* Length of every ambient-occlusion ray. <= 0 (the default 0 included): the rays are cast and counted, and
+                                   * each ends open without an evaluation (SdfForm.tryTrace tests the Length first): the frame of ao_samples = 0 */
     int32_t max_bounces;          /* 0 = the reference (glass shades as createSolid tint). >0: EXTENSION, glass
                                    * materials refract / reflect; a path ends black after this many interactions */
     int32_t spectral;             /* 0 = off. 1..16: EXTENSION, sample k is traced at wavelength bin k % spectral

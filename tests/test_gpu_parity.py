@@ -1579,6 +1579,7 @@ def test_reusing_the_centre_probe_as_a_secondary_rays_first_step_changes_no_pixe
     cases = [("C3 lean", syn.config3(n=64, size=128)[0], {}), ("C2 carved mixed", syn.config2(seed=4, size=128)[0], {}),
              ("Program.fs structure, both lights", syn.console_scene(n=120, size=128)[0], {}), ("mixed nested (general)", syn.mixed_nested()[0], {}),
              ("combinator zoo (calls)", syn.combinator_zoo()[0], {}), ("C2 boxes + AO + 4 spp (EXTENSION)", syn.config2(boxes=True, size=96)[0], dict(spp=4, ao_samples=5, ao_radius=0.6)),
+             ("C2 boxes + AO of radius 0: open without an evaluation (EXTENSION)", syn.config2(boxes=True, size=96)[0], dict(spp=4, ao_samples=5, ao_radius=0.0)),
              ("glass (EXTENSION)", syn.config5()[0], dict(spp=4, spectral=4, max_bounces=4))]
     rr = np.random.default_rng(12)
     o = (rr.normal(size=(300, 3)) * 3.0).astype(np.float32)
@@ -1613,7 +1614,7 @@ def test_reusing_the_centre_probe_as_a_secondary_rays_first_step_changes_no_pixe
                 for reuse in (1, 0):
                     gpu.set_option("reuse", reuse)
                     _, st = ds.render(EPS, LEN, ft.ImageSize(W, H), cam, **{k: v for k, v in kw.items() if k != "max_bounces" and k != "spectral"})
-                    n[reuse] = (st["sdf_evals"], st["rays_primary"] + st["rays_shadow"] + (st["rays_ext"] if "ao_samples" in kw else 0))
+                    n[reuse] = (st["sdf_evals"], st["rays_primary"] + st["rays_shadow"] + (st["rays_ext"] if kw.get("ao_radius", 0.0) > 0.0 else 0))     # an occlusion ray of Length <= 0 makes no evaluation to save
             finally:
                 gpu.set_option("escape", 1)
             if "max_bounces" not in kw:

@@ -255,3 +255,95 @@ def test_mathf_min_max_semantics(oracle):
     assert np.signbit(lib.orc_mathf_min(0.0, -0.0)) and np.signbit(lib.orc_mathf_min(-0.0, 0.0))
     assert not np.signbit(lib.orc_mathf_max(0.0, -0.0)) and not np.signbit(lib.orc_mathf_max(-0.0, 0.0))
     assert lib.orc_mathf_min(2.0, 3.0) == 2.0 and lib.orc_mathf_max(2.0, 3.0) == 3.0
+
+
+# ---- rays born with Length <= 0: the Length is tested before anything is evaluated (SdfForm.fs:94-95, then :97) --------------------------------
+import edge_scenes as edge
+
+
+@pytest.mark.parametrize("radius", [0.0, -1.0])
+def test_occlusion_rays_of_radius_zero_or_less_are_open_on_the_centre_ray(oracle, radius):
+    # EXTENSION ambient occlusion: k rays of Length ao_radius from the pulled-back hit point, colour = Color * ((bg * open / k) * 1/pi).
+    # test_pulled_back_hit_point_shadows_itself shows that a ray which evaluates there hits at once; a ray of Length <= 0 never evaluates
+    # (SdfForm.fs:94-95: ValueNone), so all four are open: 0.8 * ((0.1 * 4/4) * 1/pi).  2 x 2 frame: pixel (1, 1) is the centre ray
+    # (Image.fs:17-23: 1 / max(2, 2) = 0.5), the other three miss the sphere, so exactly 4 occlusion rays are cast.
+    os_ = oracle.Oracle().scene(sphere_scene())
+    cam = syn.default_camera().as_array()
+    np.testing.assert_array_equal(oracle.pixel_ray(cam, 2, 2, 1, 1, EPS, LEN), centre_ray()[0])
+    out, cnt = os_.render(EPS, LEN, 2, 2, cam, ao_samples=4, ao_radius=radius)
+    assert cnt["hits_primary"] == 1 and cnt["rays_ext"] == 4
+    np.testing.assert_array_equal(out[1, 1], np.array([F(0.8) * (F(0.1) * PI_INV)] * 3, F))
+    np.testing.assert_array_equal(np.delete(out.reshape(4, 3), 3, axis=0), np.tile(F(syn.BACKGROUND), (3, 1)))
+    # the smallest positive Length evaluates once and hits: 0 of 4 open, 0.8 * ((0.1 * 0/4) * 1/pi) = 0
+    tiny, cnt = os_.render(EPS, LEN, 2, 2, cam, ao_samples=4, ao_radius=1.4e-45)
+    assert cnt["rays_ext"] == 4
+    np.testing.assert_array_equal(tiny[1, 1], np.zeros(3, F))
+
+
+@pytest.fixture(scope="module", params=["lean", "cavity"])
+def edge_frame(request, oracle):
+    """(scene, camera, oracle scene, the frame without occlusion rays and its counters, the pixels whose cached distance is below epsilon)"""
+    scene, (cam,), _ = edge.FAMILIES[request.param](oracle)
+    near, hit = edge.assert_not_vacuous(oracle, scene, cam)
+    os_ = oracle.Oracle().scene(scene)
+    plain, pcnt = os_.render(EPS, LEN, edge.W, edge.H, cam.as_array())
+    assert pcnt["hits_primary"] == hit.sum()
+    return os_, cam, plain, pcnt, near
+
+
+@pytest.mark.parametrize("k", [1, 4, 16])
+@pytest.mark.parametrize("radius", [0.0, -1.0])
+def test_occlusion_rays_of_radius_zero_or_less_change_no_pixel(edge_frame, radius, k):
+    # every occlusion ray is open: bg * (k / k) = bg, the frame of ao_samples = 0 bit for bit — on frames where a ray that evaluates hits at once
+    # (a camera inside a body: every pixel; a camera in a carved cavity: 210 of 1117 hit pixels)
+    os_, cam, plain, pcnt, _ = edge_frame
+    out, cnt = os_.render(EPS, LEN, edge.W, edge.H, cam.as_array(), ao_samples=k, ao_radius=radius)
+    np.testing.assert_array_equal(out.view(np.uint32), plain.view(np.uint32))
+    assert cnt["rays_ext"] == k * cnt["hits_primary"] and cnt["hits_primary"] == pcnt["hits_primary"]
+    assert cnt["rays_shadow"] == pcnt["rays_shadow"] and cnt["hits_shadow"] == pcnt["hits_shadow"]
+
+
+def test_occlusion_rays_of_subnormal_radius_evaluate_once(edge_frame):
+    # Length 1e-40 > 0: the ray evaluates at its origin (SdfForm.fs:97) and hits where that distance is below epsilon (:98); elsewhere it moves and
+    # its Length is used up.  The frame differs from the one without occlusion rays in exactly the pixels whose distance at the record's origin is
+    # below epsilon (object_try_trace, then form_distance there).
+    os_, cam, plain, _, near = edge_frame
+    out, cnt = os_.render(EPS, LEN, edge.W, edge.H, cam.as_array(), ao_samples=4, ao_radius=1e-40)
+    differs = (out.view(np.uint32) != plain.view(np.uint32)).any(-1)
+    assert near.sum() >= 100
+    np.testing.assert_array_equal(differs, near)
+
+
+def test_point_light_at_the_hit_point_casts_a_shadow_ray_of_length_zero(oracle):
+    # edge_scenes.SHADOW_RAY: a hit on the first evaluation (origin on the sphere), pulled back to exactly (1e-30, 1e-30, -1e-30).
+    # distance2 = 1e-60 + 4e-60 + 4e-60 underflows to 0: direction diff / 0 = (+inf, +inf, -inf), cosine = +inf > 0 -> a shadow ray of Length
+    # sqrt(0) = 0 is cast (SdfLight.fs:27-37, SdfScene.fs:17) and misses without an evaluation (SdfForm.fs:94-95): intensity color / 0 * inf = inf.
+    # 1 march evaluation + 4 normal probes = 5 Distance calls.  Control light: cosine inf + inf - inf = NaN, not > 0: no shadow ray.
+    diff = np.array(edge.LIGHT_ZERO_LENGTH[0], F) - edge.SHADOW_ORIGIN
+    assert F(F(diff[0] * diff[0] + diff[1] * diff[1]) + diff[2] * diff[2]) == 0 and np.all(diff != 0)
+    np.testing.assert_array_equal(F(0) + edge.SHADOW_RAY[3:6] * F(-edge.SHADOW_RAY[7]), edge.SHADOW_ORIGIN)
+    O = oracle.Oracle()
+    obj = edge.shadow_objects()["sphere alone"]
+    with np.errstate(all="ignore"):
+        os_ = O.scene(edge.shadow_scene(obj, edge.LIGHT_ZERO_LENGTH))
+        out, cnt = os_.trace_rays(edge.SHADOW_RAY[None])
+        rec, _ = os_.object_try_trace(edge.SHADOW_RAY[None])
+        ctl, ccnt = O.scene(edge.shadow_scene(obj, edge.LIGHT_CONTROL)).trace_rays(edge.SHADOW_RAY[None])
+    np.testing.assert_array_equal(rec[0, 0:3], edge.SHADOW_ORIGIN)
+    assert abs(float(rec[0, 8]) - 5.72e-4) < 1e-6 and rec[0, 8] == rec[0, 9] and abs(float(rec[0, 10]) + 0.9999997) < 1e-6
+    np.testing.assert_array_equal(out[0], np.array([np.inf] * 3, F))
+    assert (cnt["rays_shadow"], cnt["hits_shadow"], cnt["root_evals"], cnt["hits_primary"], cnt["flags"]) == (1, 0, 5, 1, 0)
+    np.testing.assert_array_equal(ctl[0], np.array([F(0.8) * (F(0.1) * PI_INV)] * 3, F))
+    assert abs(float(ctl[0, 0]) - 0.02546479) < 1e-8
+    assert (ccnt["rays_shadow"], ccnt["hits_shadow"], ccnt["root_evals"], ccnt["hits_primary"], ccnt["flags"]) == (0, 0, 5, 1, 0)
+
+
+def test_every_shadow_edge_object_keeps_the_construction(oracle):
+    # the sphere next to far bodies of each kernel family: the record origin and the infinite colour are those of the sphere alone
+    for name, obj in edge.shadow_objects().items():
+        with np.errstate(all="ignore"):
+            os_ = oracle.Oracle().scene(edge.shadow_scene(obj, edge.LIGHT_ZERO_LENGTH))
+            out, cnt = os_.trace_rays(edge.SHADOW_RAY[None])
+            rec, _ = os_.object_try_trace(edge.SHADOW_RAY[None])
+        np.testing.assert_array_equal(rec[0, 0:3], edge.SHADOW_ORIGIN, name)
+        assert np.isposinf(out[0]).all() and cnt["rays_shadow"] == 1 and cnt["hits_shadow"] == 0, name
