@@ -13,8 +13,12 @@
 // build 13 rows of per-lane union-walk counters (kernels.hip FT_UDBG: 12 + 1 scratch row), then FT_SH_ROWS rows of per-lane shading state
 #define FT_LDS_CNT_WORDS 64
 // the header's words: 0 .. 31 the per-wave statistics (kernels.hip FT_C_*: FT_BLOCK / 64 words per counter), 32 .. 35 the reporting wave's two start
-// clocks, FT_LDS_TILE_WORD .. + 2 * FT_BLOCK / 64 - 1 per wave the tile it took last and its round count at that grab (kernels.hip "Tile order"), the rest free
+// clocks, FT_LDS_REPORT_WORD the lean kernel's mark of the workgroup whose first thread reports them, FT_LDS_TILE_WORD .. + 2 * FT_BLOCK / 64 - 1 per wave the tile it took last and its round count at that grab (kernels.hip "Tile order"),
+// FT_LDS_WAVE_WORD .. + 4 * FT_BLOCK / 64 - 1 per wave the lean kernel's four accumulate-only sums (kernels.hip ft_trace_body waveSt), the rest free
 #define FT_LDS_TILE_WORD 40
+#define FT_LDS_WAVE_WORD 48
+#define FT_LDS_REPORT_WORD 36
+static_assert(FT_LDS_WAVE_WORD >= FT_LDS_TILE_WORD + 2 * (256 / 64) && FT_LDS_WAVE_WORD + 4 * (256 / 64) <= FT_LDS_CNT_WORDS, "the wave sums lie behind the tile words, inside the header");
 static_assert(FT_LDS_TILE_WORD >= 36 && FT_LDS_TILE_WORD + 2 * (256 / 64) <= FT_LDS_CNT_WORDS, "the tile words lie behind the clocks, inside the header");
 #ifdef FT_UNION_PROFILE
 #define FT_LDS_DBG_ROWS 13

@@ -544,6 +544,14 @@ __device__ __forceinline__ void eval_union_prims(const FtSceneDev& S, const FtGr
     outD = mn; outLeaf = leaf;
 }
 
+// A switch of the argument block tested in the round itself (lean kernel, FT_WORD_AT_USE): the 32-bit word stays in its one SGPR and is compared where it is tested
+// (s_cmp, no VALU slot).  Left alone the compiler forms each loop-invariant test once in front of the loop and holds the outcome as a 64-bit lane mask.
+__device__ __forceinline__ uint32_t ft_word_held(uint32_t v) {
+    asm volatile("" : "+s"(v));
+    return v;
+}
+#define FT_WORD_AT_USE(on, v) ((on) ? ft_word_held(v) : (v))
+
 #define FT_CULL_NONE 0xffffffffu
 #define FT_CULL_NOCLAMP 0x10000u               // flag on ft_cull_children's survivor count (<= FT_CULL_MAX = 256): no ray of the wave is within 1e-6 of a child's centre this round
 // the interpreter (below); WITH_UNION = false is the instance the candidate loop uses for FT_PR_CALL children,
@@ -854,9 +862,11 @@ __device__ __forceinline__ float ft_wave_shift_right1(float v) { return ft_dpp<0
 // A run that continues an accumulator (no FT_FLAG_INIT: children of other kinds came first) starts from a sum >= 0, so the prefix sums of the run's own lower
 // bounds are still lower bounds of the running sum in front of each of its children.
 // active / am: lanes that evaluate p this round (am = __ballot(active) != 0).  Wave-uniform result; executed by all 64 lanes.
+// HELD (the lean trace kernel): "the scene has a cull site" is tested on the word itself every round (FT_WORD_AT_USE), not held as a lane mask.
+template <bool HELD = false>
 __device__ __forceinline__ uint32_t ft_cull_children(const FtSceneDev& S, const f3 p, bool active, unsigned long long am,
                                                      const float* __restrict__ ldsC, float* __restrict__ row) {
-    if (S.cullPc == FT_CULL_NONE) return FT_CULL_NONE;
+    if (FT_WORD_AT_USE(HELD, S.cullPc) == FT_CULL_NONE) return FT_CULL_NONE;
     const FtInstr FT_CONST* in = as_const(S.instr) + S.cullPc;
     const uint32_t flags = in->flags, count = in->count;
     const float si = in->f0;
@@ -1246,6 +1256,20 @@ __device__ __forceinline__ void write_rgb(float* __restrict__ out, uint32_t idx,
 
 __device__ __forceinline__ f3 ft_background(const FtRenderArgs& a) { return mk3(a.S.bg[0], a.S.bg[1], a.S.bg[2]); }   // scene.BackgroundColor
 
+// Arguments read at use (lean kernel): the argument block again, through a pointer the compiler cannot trace back to the kernel's parameter.
+// A field read through `a` is loop-invariant, so its load is hoisted in front of the round loop and the value is held in an SGPR across every round —
+// and the lean kernel has none to spare: what does not fit is spilled into VGPR lanes and comes back with a v_readlane per use.  Code off the round's
+// main path (a job's start, a pixel's colour, a light's record, the hand-out) reads its fields through this instead: scalar loads from the constant
+// cache where they are used, no VALU slot.  The kernel's only parameter is the block, so it lies at offset 0 of the kernarg segment.
+// FT_ARGS_AT_USE(on, a): that block where `on`, else `a` itself — as an expression, not through a call, so that a build with `on` false compiles
+// to what it compiled to before (a call's inlining scope alone moved the other families' machine code).
+__device__ __forceinline__ const FtRenderArgs& ft_args_reread() {
+    const FtRenderArgs FT_CONST* p = (const FtRenderArgs FT_CONST*)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    return *(const FtRenderArgs*)p;
+}
+#define FT_ARGS_AT_USE(on, a) ((on) ? ft_args_reread() : (a))
+
 // EXTENSION builds scale every finished sample by the path throughput (exactly 1 unless glass / wavelengths are on)
 template <bool EXT>
 __device__ __forceinline__ void emit(const FtRenderArgs& a, const LaneState& s, f3 c) {
@@ -1618,20 +1642,26 @@ __device__ __forceinline__ FtLit ft_light_at(const uint32_t type, const f3 lv, c
 // VIS (ft_light_visibility, the *_vis builds; SHADE as well): the same marches, but what a lane keeps is one bit per light — did SdfScene.fs:23 execute —
 // in the row that holds the accumulated light otherwise (ft_vis_word).  Lights outside a.visSel are passed over before anything of them is read; no
 // intensity, no cosine product, no colour: the mask goes to a.visOut when the last light is done
-template <bool EXT, int FORM = FT_FORM_FRAME>
+// LEAN (the lean kernel): what a lane reads of the argument block only when a ray ends or a light is taken up — the output, the background, the lights,
+// the materials — is read there (FT_ARGS_AT_USE); the march's own test, ft_never_enters, runs every round and keeps its constants in registers
+template <bool EXT, int FORM = FT_FORM_FRAME, bool LEAN = false>
 __device__ __forceinline__ void settle(const FtRenderArgs& a, LaneState& s) {
     constexpr bool VIEWS = FORM == FT_FORM_VIEWS, SHADE = FORM == FT_FORM_SHADE || FORM == FT_FORM_VIS, VIS = FORM == FT_FORM_VIS;
     const float piInv = 1.0f / 3.14159274101257324f;                   // Math.fs:28-30
+    // the block as this lane's exits read it: `a` itself, or (LEAN) read again at the exit.  One pointer declared out here and assigned at the exits:
+    // a reference declared inside the loop's branches moved the other families' machine code
+    const FtRenderArgs* u = &a;
     for (;;) {
         if (!SHADE && s.phase == PH_MARCH) {
             // SdfForm.fs:94 -> SdfScene.fs:10; or every further step is known to miss (EXTENSION glass: a path inside a body marches on
             // -Distance, which is below epsilon everywhere outside the support sphere — the shortcut is for paths outside bodies only)
             if (s.len <= 0.0f || ((!EXT || !s.inside()) && ft_never_enters(a.S, s.o, s.dir, s.eps, s.len))) {
-                if (EXT && a.mode == 2u) write_try_trace_miss(a, s);   // ValueNone of SdfForm.tryTrace
+                if (LEAN) u = &ft_args_reread();
+                if (EXT && u->mode == 2u) write_try_trace_miss(*u, s);   // ValueNone of SdfForm.tryTrace
                 else {
                     // every miss of a primary ray ends here: Length used up, escape, NaN and the step cap (s.len = -1), the camera shortcuts of start_job
-                    if (EXT && ends_hit_segment<VIEWS>(a, s)) write_hit_miss(a, hit_index<VIEWS>(a, s));
-                    if (!EXT || a.hits != 2u) emit<EXT>(a, s, ft_background(a));
+                    if (EXT && ends_hit_segment<VIEWS>(*u, s)) write_hit_miss(*u, hit_index<VIEWS>(*u, s));
+                    if (!EXT || u->hits != 2u) emit<EXT>(*u, s, ft_background(*u));
                 }
                 s.phase = PH_IDLE;
             }
@@ -1662,12 +1692,13 @@ __device__ __forceinline__ void settle(const FtRenderArgs& a, LaneState& s) {
         }
         if (s.phase == PH_SHADOW) {
             if (s.len <= 0.0f || ((!EXT || !s.inside()) && ft_never_enters(a.S, s.o, s.dir, s.eps, s.len))) {   // shadow ray missed (or can only miss): light arrives
+                if (LEAN) u = &ft_args_reread();
                 if (VIS) {                                             // SdfScene.fs:23 executes for light lidx: its bit (unsigned shift: bit 31 is a light)
                     *ft_vis_word() |= 1u << s.lidx;
                     s.lidx += 1; s.phase = PH_LIGHTS;
                     continue;
                 }
-                const FtLight L = ld_light(as_const(a.S.lights) + s.lidx);                 // the light this shadow ray was cast for (PH_LIGHTS below)
+                const FtLight L = ld_light(as_const(u->S.lights) + s.lidx);                 // the light this shadow ray was cast for (PH_LIGHTS below)
                 const f3 lv = mk3(L.v[0], L.v[1], L.v[2]), hp = sh_get3(FT_SH_HP);
                 const FtLit li = ft_light_at(L.type, lv, mk3(L.color[0], L.color[1], L.color[2]), hp);
                 sh_set3(FT_SH_LACC, sh_get3(FT_SH_LACC) + li.lint * ft_dot(sh_get3(FT_SH_NRM), li.ldir));   // SdfScene.fs:15, :23
@@ -1677,22 +1708,23 @@ __device__ __forceinline__ void settle(const FtRenderArgs& a, LaneState& s) {
             return;
         }
         if (s.phase == PH_LIGHTS) {
-            if (VIS && s.lidx >= a.S.nLights) {                        // every selected light has been asked: kept bits | new bits, one dword
-                a.visOut[s.job] = *ft_vis_word();
+            if (LEAN) u = &ft_args_reread();
+            if (VIS && s.lidx >= u->S.nLights) {                        // every selected light has been asked: kept bits | new bits, one dword
+                u->visOut[s.job] = *ft_vis_word();
                 s.phase = PH_IDLE;
                 return;
             }
-            if (VIS && ((a.visSel >> s.lidx) & 1u) == 0u) { s.lidx += 1; continue; }     // not selected: no cosine, no ray, nothing counted
-            if (!VIS && s.lidx >= a.S.nLights) {                       // SdfScene.fs:28 (no colour in a VIS build: it has ended above)
+            if (VIS && ((u->visSel >> s.lidx) & 1u) == 0u) { s.lidx += 1; continue; }     // not selected: no cosine, no ray, nothing counted
+            if (!VIS && s.lidx >= u->S.nLights) {                       // SdfScene.fs:28 (no colour in a VIS build: it has ended above)
                 // SHADE: result.Color of the lane's record, read again here (its line was loaded when the job started) instead of being held in three
                 // registers or LDS rows across every shadow march
-                cfp m = SHADE ? as_const(a.hitsIn) + 16ull * s.job + 11u : as_const(a.S.materials) + 3u * s.leaf;
+                cfp m = SHADE ? as_const(u->hitsIn) + 16ull * s.job + 11u : as_const(u->S.materials) + 3u * s.leaf;
                 const f3 color = mk3(m[0], m[1], m[2]);
-                emit<EXT>(a, s, color * (sh_get3(FT_SH_LACC) * piInv));
+                emit<EXT>(*u, s, color * (sh_get3(FT_SH_LACC) * piInv));
                 s.phase = PH_IDLE;
                 return;
             }
-            const FtLight L = ld_light(as_const(a.S.lights) + s.lidx);
+            const FtLight L = ld_light(as_const(u->S.lights) + s.lidx);
             const f3 lv = mk3(L.v[0], L.v[1], L.v[2]);
             const f3 hp = sh_get3(FT_SH_HP);
             // only the direction is used here: the intensity's division is dead code and is dropped (a direction-only helper would state SdfLight.fs:9, :25 twice)
@@ -1710,8 +1742,8 @@ __device__ __forceinline__ void settle(const FtRenderArgs& a, LaneState& s) {
                                                                        // intensity lc / distance2 (:40): formed when the ray has missed (PH_SHADOW above)
                 }
                 s.steps = 0; ft_count(FT_C_SHADOW);
-                s.phase = PH_SHADOW; s.certAt = a.certShadow;
-                if (!SHADE && a.reuse != 0u) {
+                s.phase = PH_SHADOW; s.certAt = u->certShadow;
+                if (!SHADE && u->reuse != 0u) {
                     const int r = first_step_from_cache(s);
                     if (r == 1) { ft_count(FT_C_HITS); s.lidx += 1; s.phase = PH_LIGHTS; }     // shadowed at once (SdfLight.fs:20)
                     else if (r == 2) s.len = -1.0f;                    // resolved as a miss by the PH_SHADOW branch above
@@ -1729,9 +1761,10 @@ __device__ __forceinline__ void settle(const FtRenderArgs& a, LaneState& s) {
 // PH_CAM value of that camera (lane v of the wave's per-lane dCam / leafCam)
 struct ViewCam { f3 o, fw, up, rt; float d; uint32_t leaf; };
 
-template <bool EXT, int FORM = FT_FORM_FRAME>
-__device__ __forceinline__ void start_job(const FtRenderArgs& a, LaneState& s, const bool camKnown, float dCam, uint32_t leafCam, const ViewCam& vc) {
+template <bool EXT, int FORM = FT_FORM_FRAME, bool LEAN = false>
+__device__ __forceinline__ void start_job(const FtRenderArgs& a_, LaneState& s, const bool camKnown, float dCam, uint32_t leafCam, const ViewCam& vc) {
     constexpr bool VIEWS = FORM == FT_FORM_VIEWS, SHADE = FORM == FT_FORM_SHADE || FORM == FT_FORM_VIS, VIS = FORM == FT_FORM_VIS;
+    const FtRenderArgs& a = FT_ARGS_AT_USE(LEAN, a_);                  // the camera, the stripes, the frame's geometry: once per job, read here
     if (SHADE) {
         // ft_shade_hits: SdfScene.trace from its `| ValueSome result ->` arm on (SdfScene.fs:11-28).  Job = record: four 16-byte words
         // {Origin, Direction.x} {Direction.yz, Length, Epsilon} {Normal, Color.r} {Color.gb, hit, 0}.  A record is data: its position, normal and
@@ -1760,7 +1793,7 @@ __device__ __forceinline__ void start_job(const FtRenderArgs& a, LaneState& s, c
         else sh_set3(FT_SH_LACC, ft_background(a));                    // SdfScene.fs:12
         s.lidx = 0;
         s.phase = PH_LIGHTS;
-        settle<EXT, FORM>(a, s);
+        settle<EXT, FORM, LEAN>(a_, s);
         return;
     }
     if (a.mode >= 1) {                                                 // explicit ray buffer (1: SdfScene.trace scene ray, with or instead of its hit record; 2: SdfForm.tryTrace)
@@ -1804,7 +1837,7 @@ __device__ __forceinline__ void start_job(const FtRenderArgs& a, LaneState& s, c
         else if (dCam < s.eps) { ft_count(FT_C_HITP); s.leaf = leafCam; s.phase = PH_NX; }   // a hit at the camera itself,
         else { s.o = s.o + s.dir * dCam; s.len = s.len - dCam; s.steps = 1; }               // or the first step (Ray.fs:9-13)
     }
-    settle<EXT, FORM>(a, s);
+    settle<EXT, FORM, LEAN>(a_, s);
 }
 
 // EXTENSION (BASELINE.json config 5): a path segment ended on leaf s.leaf with normal s.nrm at s.hp.  Glass leaf:
@@ -1856,6 +1889,11 @@ __device__ __forceinline__ void glass_bounce(const FtRenderArgs& a, LaneState& s
     s.phase = PH_MARCH; s.certAt = a.certPrim;                         // a new path segment: due like a primary ray
 }
 
+// a wave-uniform number added to one of the wave's own words of the LDS header by its lane 0
+__device__ __forceinline__ void ft_wave_word_add(uint32_t* word, uint32_t v) {
+    if ((threadIdx.x & 63u) == 0u) __hip_atomic_fetch_add(word, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+
 __device__ __forceinline__ unsigned long long wave_sum(uint32_t v) {
     unsigned long long x = v;
     for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
@@ -1866,6 +1904,9 @@ template <int VARIANT, bool EXT, int MATH = 0, int K = 0, int FORM = FT_FORM_FRA
 __device__ __forceinline__ void ft_trace_body(const FtRenderArgs& a) {
     constexpr bool VIEWS = FORM == FT_FORM_VIEWS, SHADE = FORM == FT_FORM_SHADE || FORM == FT_FORM_VIS;
     static_assert(!SHADE || !EXT, "ft_shade_hits and ft_light_visibility have no EXTENSION build");
+    // the lean kernel's round runs at the SGPR ceiling: its accumulate-only statistics live in LDS and its off-path arguments are read at use (below; FT_ARGS_AT_USE)
+    // (not its EXTENSION builds: they run far from that ceiling at 100 VGPRs and more, and ft_trace_kernel_smooth_spheres_ext paid for the change with 20 bytes of scratch)
+    constexpr bool LEAN = VARIANT == 1 && !EXT;
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     // the first wave of block 0 reports the shader clock it ran at (statistics only); its start clocks wait in LDS, not in registers
     unsigned long long* clk0 = reinterpret_cast<unsigned long long*>(ft_lds + 32);
@@ -1876,11 +1917,13 @@ __device__ __forceinline__ void ft_trace_body(const FtRenderArgs& a) {
     float* ldsC = ft_lds + L.consts;                                   // staged constant pool ("SDF op stack" in LDS)
     for (uint32_t i = tid; i < a.S.nStage; i += FT_BLOCK) ldsC[i] = a.S.consts[i];
     if (MATH != 0 && tid < FT_LIBM_TAB_DOUBLES) const_cast<ft_u64*>(ft_libm_tab(a.S))[tid] = ft_libm_tab_g[tid];   // FT_OPT_MATH: glibc's tables
-    if (tid < 32u) reinterpret_cast<uint32_t*>(ft_lds)[tid] = 0u;       // the per-wave statistics words
+    if (tid < 32u || (LEAN && (tid - FT_LDS_WAVE_WORD < 4u * (FT_BLOCK / 64) || tid == FT_LDS_REPORT_WORD))) reinterpret_cast<uint32_t*>(ft_lds)[tid] = 0u;   // the per-wave statistics words
 #ifdef FT_UNION_PROFILE
     for (uint32_t k = 0; k < FT_LDS_DBG_ROWS; ++k) reinterpret_cast<uint32_t*>(ft_lds)[FT_LDS_CNT_WORDS + tid + k * FT_BLOCK] = 0u;
 #endif
     __syncthreads();
+    // LEAN: "this thread reports the clocks" waits in a header word as well, not as a lane mask held to the kernel's end
+    if (LEAN && blockIdx.x == 0 && tid == 0) reinterpret_cast<uint32_t*>(ft_lds)[FT_LDS_REPORT_WORD] = 1u;
 
     // this wave's row (lean kernel: latency mode and culled children; other kernels: culled children of the scene's cull site) — a wave-uniform address.
     // The offset is formed here, not kept from L: holding it across the staging loop changes the lean kernel's machine code.
@@ -1899,6 +1942,10 @@ __device__ __forceinline__ void ft_trace_body(const FtRenderArgs& a) {
     if (ORDER && lane == 0) tileSt[0] = 0xffffffffu;
     uint32_t coopEvals = 0;                                            // evaluations done in latency mode (wave-uniform)
     uint32_t nEvals = 0;                                               // scene evaluations of this wave's rays (wave-uniform: summed per round)
+    // LEAN: those four sums are only ever added to, so they wait in this wave's words of the LDS header (as tileSt does) instead of in four SGPRs that
+    // would stay live across the whole round: one ds_add by lane 0 per sum and round.  Same addends, same 32-bit sums.
+    uint32_t* waveSt = reinterpret_cast<uint32_t*>(ft_lds) + FT_LDS_WAVE_WORD + (tid >> 6);
+    enum : uint32_t { ST_EVALS = 0, ST_COOP = FT_BLOCK / 64, ST_CULL_TOTAL = 2 * (FT_BLOCK / 64), ST_CULL_SKIPPED = 3 * (FT_BLOCK / 64) };
     bool exhausted = false;
     LaneState s;
     s.phase = PH_IDLE; s.job = 0; s.steps = 0; s.lidx = 0; s.leaf = 0; s.outIdx = 0; s.certAt = 0xffffffffu;
@@ -1930,36 +1977,37 @@ __device__ __forceinline__ void ft_trace_body(const FtRenderArgs& a) {
             if ((uint32_t)__popcll(idle) < a.refillMin && __ballot(s.phase >= PH_MARCH) != 0ull) break;
             if (chunkNext == chunkEnd) {
                 if (exhausted) break;
+                const FtRenderArgs& u = FT_ARGS_AT_USE(LEAN, a);      // the hand-out's arguments: once per tile, read here
                 // Tile order: the rounds since the last grab are the cost of the tile taken then (refillMin = 64: its last lane has ended), written
                 // by one lane; every tile is taken once, so every cost is written once, by this grab or by the one that finds the queue empty
-                if (ORDER && a.tileCost != nullptr && lane == 0) {
+                if (ORDER && u.tileCost != nullptr && lane == 0) {
                     const uint32_t t = tileSt[0];
-                    if (t < (a.nJobs >> 6)) a.tileCost[t] = waveEvals - tileSt[TILE_EVALS];
+                    if (t < (u.nJobs >> 6)) u.tileCost[t] = waveEvals - tileSt[TILE_EVALS];
                     tileSt[0] = 0xffffffffu;
                 }
                 // Guided hand-out at the end of the queue (FT_OPT_GUIDED, lean kernel, OFF by default; everywhere else shrink1 = shrink2 = nJobs):
                 // from job shrink1 on a wave takes half a tile, from shrink2 on a quarter, so that the last generation of work is spread over
                 // 2 - 4 times as many waves.  Measured: the 32 / 16-ray rounds of the latency mode cost +34 % / +46 % per ray, more than the
                 // shorter drain returns (N = 8 share of C3 8.67 -> 9.13 ms).  The cursor is read first to pick the size.
-                uint32_t base = 0, take = a.chunk;
+                uint32_t base = 0, take = u.chunk;
                 if (lane == 0) {
-                    if (a.shrink1 < a.nJobs) {
-                        const uint32_t cur = __hip_atomic_load(a.counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        take = cur >= a.shrink2 ? a.chunk / 4u : (cur >= a.shrink1 ? a.chunk / 2u : a.chunk);
+                    if (u.shrink1 < u.nJobs) {
+                        const uint32_t cur = __hip_atomic_load(u.counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        take = cur >= u.shrink2 ? u.chunk / 4u : (cur >= u.shrink1 ? u.chunk / 2u : u.chunk);
                     }
-                    base = atomicAdd(a.counter, take);
+                    base = atomicAdd(u.counter, take);
                 }
                 base = __builtin_amdgcn_readfirstlane(base);
                 const uint32_t took = (uint32_t)__builtin_amdgcn_readfirstlane((int)take);
-                if (base >= a.nJobs) { exhausted = true; break; }
+                if (base >= u.nJobs) { exhausted = true; break; }
                 chunkNext = base;
-                chunkEnd = (a.nJobs - base < took) ? a.nJobs : base + took;
+                chunkEnd = (u.nJobs - base < took) ? u.nJobs : base + took;
                 // Tile order: the k-th grab works on tile tileOrder[k] (a permutation of the tiles, heavy ones first: "Tile order" below) in place
                 // of tile k.  Only the moment a tile starts depends on it: chunkNext / chunkEnd are that tile's 64 jobs as before.
-                if (ORDER && a.tileCost != nullptr) {
+                if (ORDER && u.tileCost != nullptr) {
                     uint32_t tile = base >> 6;
-                    if (a.tileOrder != nullptr) {
-                        tile = (uint32_t)__builtin_amdgcn_readfirstlane((int)a.tileOrder[tile]);
+                    if (u.tileOrder != nullptr) {
+                        tile = (uint32_t)__builtin_amdgcn_readfirstlane((int)u.tileOrder[tile]);
                         chunkNext = tile << 6; chunkEnd = chunkNext + 64u;
                     }
                     if (lane == 0) { tileSt[0] = tile; tileSt[TILE_EVALS] = waveEvals; }
@@ -1978,7 +2026,7 @@ __device__ __forceinline__ void ft_trace_body(const FtRenderArgs& a) {
             }
             const uint32_t nIdle = (uint32_t)__popcll(idle);
             const uint32_t rank = (uint32_t)__popcll(idle & ((1ull << lane) - 1ull));
-            if (s.phase == PH_IDLE && rank < avail) { s.job = chunkNext + rank; start_job<EXT, FORM>(a, s, camKnown, dCam, leafCam, vc); }
+            if (s.phase == PH_IDLE && rank < avail) { s.job = chunkNext + rank; start_job<EXT, FORM, LEAN>(a, s, camKnown, dCam, leafCam, vc); }
             chunkNext += (nIdle < avail) ? nIdle : avail;
         }
         if (s.phase == PH_IDLE && exhausted && chunkNext == chunkEnd) s.phase = PH_DONE;
@@ -1987,26 +2035,26 @@ __device__ __forceinline__ void ft_trace_body(const FtRenderArgs& a) {
         // ---- occlusion certificate (lean kernel; "Occlusion certificate") ----
         // every occPeriod-th evaluation round, for the shadow rays in their occPeriod steps from occFrom on: a marching lane takes one step per round, so each
         // ray meets exactly one try and no lane state records it.  A certified lane leaves as from an evaluation below epsilon (the switch below)
-        if (VARIANT == 1 && a.occPeriod != 0u && waveEvals % a.occPeriod == 0u) {                // EXTENSION builds: shadow rays outside glass bodies; AO rays march
+        if (VARIANT == 1 && FT_WORD_AT_USE(LEAN, a.occPeriod) != 0u && waveEvals % a.occPeriod == 0u) {                // EXTENSION builds: shadow rays outside glass bodies; AO rays march
             const bool cand = s.phase == PH_SHADOW && s.steps - a.occFrom < a.occPeriod && (!EXT || !s.inside());
             if ((uint32_t)__popcll(__ballot(cand)) >= a.occMin) {
-                const bool hit = ft_occlusion_certificate(a, ldsC + 0, cand, s.o, s.dir, s.eps, s.len, s.steps);
-                if (hit) { ft_count(FT_C_HITS); s.lidx += 1; s.phase = PH_LIGHTS; settle<EXT, FORM>(a, s); }      // shadowed (SdfLight.fs:20)
+                const bool hit = ft_occlusion_certificate(FT_ARGS_AT_USE(LEAN, a), ldsC + 0, cand, s.o, s.dir, s.eps, s.len, s.steps);   // its constants: read in the rounds that try
+                if (hit) { ft_count(FT_C_HITS); s.lidx += 1; s.phase = PH_LIGHTS; settle<EXT, FORM, LEAN>(a, s); }      // shadowed (SdfLight.fs:20)
                 if (__ballot(hit) != 0ull && __ballot(s.phase >= PH_MARCH) == 0ull) continue;                     // every lane resolved: refill now
             }
         }
 
         // ---- miss certificates (lean kernel; "Miss certificate") ----
-        if (VARIANT == 1 && a.cert != 0u) {                          // EXTENSION builds: not inside a glass body (the march runs on -Distance there)
+        if (VARIANT == 1 && FT_WORD_AT_USE(LEAN, a.cert) != 0u) {                          // EXTENSION builds: not inside a glass body (the march runs on -Distance there)
             // the bundle of the wave's primary rays, then that of its shadow rays (never mixed: one axis serves one family of directions), every
             // bundlePeriod-th evaluation round of the wave; a bundle that fails changes nothing
             bool ends = false;
-            if (a.bundlePeriod != 0u && waveEvals % a.bundlePeriod == 0u) {
+            if (FT_WORD_AT_USE(LEAN, a.bundlePeriod) != 0u && waveEvals % a.bundlePeriod == 0u) {
 #pragma unroll 1
                 for (uint32_t ph = SHADE ? PH_SHADOW : PH_MARCH; ph <= PH_SHADOW; ph += PH_SHADOW - PH_MARCH) {
                     const bool cand = s.phase == ph && (ph == PH_MARCH || s.steps >= a.bundleShadow) && (!EXT || !s.inside());
                     if ((uint32_t)__popcll(__ballot(cand)) < a.bundleMin) continue;
-                    if (ft_bundle_certificate(a.S, ldsC + 0, cand, s.o, s.dir, s.eps, s.len, s.steps, a.bundleMin)) ends = true;
+                    if (ft_bundle_certificate(FT_ARGS_AT_USE(LEAN, a).S, ldsC + 0, cand, s.o, s.dir, s.eps, s.len, s.steps, a.bundleMin)) ends = true;
                 }
             }
             // per lane: once enough lanes are due, the wave tries it for all of them at once
@@ -2014,13 +2062,14 @@ __device__ __forceinline__ void ft_trace_body(const FtRenderArgs& a) {
             bool tried = false;
             if ((uint32_t)__popcll(__ballot(due)) >= a.certMin) {
                 tried = true;
-                const bool holds = ft_miss_certificate(a.S, ldsC + 0, due, s.o, s.dir, s.eps, s.len, s.steps);
+                const FtRenderArgs& u = FT_ARGS_AT_USE(LEAN, a);      // the certificate's constants and the retry rule: read in the rounds that try
+                const bool holds = ft_miss_certificate(u.S, ldsC + 0, due, s.o, s.dir, s.eps, s.len, s.steps);
                 if (due) {
                     if (holds) ends = true;
-                    else s.certAt = a.certRepeat != 0u ? s.steps + a.certRepeat : 0xffffffffu;
+                    else s.certAt = u.certRepeat != 0u ? s.steps + u.certRepeat : 0xffffffffu;
                 }
             }
-            if (ends) { s.len = -1.0f; settle<EXT, FORM>(a, s); }             // resolved as the miss its march ends in (settle: as for ft_never_enters)
+            if (ends) { s.len = -1.0f; settle<EXT, FORM, LEAN>(a, s); }             // resolved as the miss its march ends in (settle: as for ft_never_enters)
             // every lane resolved (a tile whose rays all miss): refill now instead of spending an empty round
             if ((tried || __ballot(ends) != 0ull) && __ballot(s.phase >= PH_MARCH) == 0ull) continue;
         }
@@ -2044,14 +2093,16 @@ __device__ __forceinline__ void ft_trace_body(const FtRenderArgs& a) {
         // ---- latency mode: at most tailK rays left in this wave -> each is evaluated by all 64 lanes together ("Latency (tail) mode") ----
         const unsigned long long am = __ballot(active);
         const bool camRound = __ballot(s.phase == PH_CAM) != 0ull;     // all lanes are in PH_CAM together; that one evaluation per wave is not counted in the statistics
-        if (!camRound) nEvals += (uint32_t)__popcll(am);
+        if (LEAN) { if (!camRound) ft_wave_word_add(waveSt + ST_EVALS, (uint32_t)__popcll(am)); }
+        else if (!camRound) nEvals += (uint32_t)__popcll(am);
         const bool coop = (uint32_t)__popcll(am) <= a.tailK;           // tailK = 0: never
         float dCoop = 0.0f; uint32_t leafCoop = 0;
         if (coop && am != 0ull) {
             const f3 qm = query_point();
             if (VARIANT == 1) {                                        // smooth union of spheres: all the rays at once, 64 / rays lanes each
                 ft_eval_smooth_spheres_packed<MATH>(a.S, qm, active, am, (uint32_t)__popcll(am), ldsC, coopRow, dCoop, leafCoop);
-                if (!camRound) coopEvals += (uint32_t)__popcll(am);
+                if (LEAN) { if (!camRound) ft_wave_word_add(waveSt + ST_COOP, (uint32_t)__popcll(am)); }
+                else if (!camRound) coopEvals += (uint32_t)__popcll(am);
             } else {                                                   // general scenes: one ray after the other, all 64 lanes each
                 unsigned long long m = am;
                 while (m != 0ull) {
@@ -2068,12 +2119,14 @@ __device__ __forceinline__ void ft_trace_body(const FtRenderArgs& a) {
         }
         // ---- lean kernel: drop the children whose terms no ray of this wave can feel this round ("Exact child culling") ----
         uint32_t cullN = FT_CULL_NONE;
-        if (VARIANT != 3 && a.cull != 0u && !coop && am != 0ull) {
-            cullN = ft_cull_children(a.S, query_point(), active, am, ldsC, coopRow);
+        if (VARIANT != 3 && FT_WORD_AT_USE(LEAN, a.cull) != 0u && !coop && am != 0ull) {
+            cullN = ft_cull_children<LEAN>(a.S, query_point(), active, am, ldsC, coopRow);
             if (cullN != FT_CULL_NONE) {
                 const uint32_t cnt = (as_const(a.S.instr) + a.S.cullPc)->count;
                 const uint32_t looked = cnt < FT_CULL_MAX ? cnt : FT_CULL_MAX;
-                cullTotal += looked * (uint32_t)__popcll(am) >> 6; cullSkipped += (looked - (cullN & 0xffffu)) * (uint32_t)__popcll(am) >> 6;   // in units of 64 pairs
+                const uint32_t total = looked * (uint32_t)__popcll(am) >> 6, skipped = (looked - (cullN & 0xffffu)) * (uint32_t)__popcll(am) >> 6;   // in units of 64 pairs
+                if (LEAN) { ft_wave_word_add(waveSt + ST_CULL_TOTAL, total); ft_wave_word_add(waveSt + ST_CULL_SKIPPED, skipped); }
+                else { cullTotal += total; cullSkipped += skipped; }
             }
         }
         if (active) {
@@ -2149,27 +2202,29 @@ __device__ __forceinline__ void ft_trace_body(const FtRenderArgs& a) {
             }
             default: break;
             }
-            settle<EXT, FORM>(a, s);
+            settle<EXT, FORM, LEAN>(a, s);
         }
         FT_UDBG_T1(7, tRound);
     }
 
     // ---- statistics -------------------------------------------------------------------------
     const uint32_t* cw = reinterpret_cast<const uint32_t*>(ft_lds) + (tid >> 6);      // this wave's statistics words
+    if (LEAN) { nEvals = waveSt[ST_EVALS]; coopEvals = waveSt[ST_COOP]; cullTotal = waveSt[ST_CULL_TOTAL]; cullSkipped = waveSt[ST_CULL_SKIPPED]; }
     const unsigned long long e = nEvals, sh = cw[FT_C_SHADOW * 4], hp = cw[FT_C_HITP * 4], hs = cw[FT_C_HITS * 4], pr = cw[FT_C_PRIMARY * 4], ex = cw[FT_C_EXT * 4];
     const unsigned long long fl = cw[FT_C_FLAGS * 4] & 3u, fc = cw[FT_C_FLAGS * 4] & 4u;
     if (lane == 0) {
-        atomicAdd(&a.stats->sdf_evals, e);
-        atomicAdd(&a.stats->rays_shadow, sh);
-        atomicAdd(&a.stats->hits_primary, hp);
-        atomicAdd(&a.stats->hits_shadow, hs);
-        atomicAdd(&a.stats->rays_primary, pr);
-        if (ex) atomicAdd(&a.stats->rays_ext, ex);
-        atomicAdd(&a.stats->wave_evals, (unsigned long long)waveEvals);
-        if (coopEvals) atomicAdd(&a.stats->coop_evals, (unsigned long long)coopEvals);
-        if (cullTotal) { atomicAdd(&a.stats->cull_total, (unsigned long long)cullTotal); atomicAdd(&a.stats->cull_skipped, (unsigned long long)cullSkipped); }
-        if (fl | fc) atomicOr(&a.stats->flags, fl | fc);
-        if (blockIdx.x == 0 && tid == 0) { atomicAdd(&a.stats->clk_shader, clock64() - clk0[0]); atomicAdd(&a.stats->clk_ref, wall_clock64() - clk0[1]); }
+        const FtRenderArgs& u = FT_ARGS_AT_USE(LEAN, a);              // the statistics block's address is not held across the rounds
+        atomicAdd(&u.stats->sdf_evals, e);
+        atomicAdd(&u.stats->rays_shadow, sh);
+        atomicAdd(&u.stats->hits_primary, hp);
+        atomicAdd(&u.stats->hits_shadow, hs);
+        atomicAdd(&u.stats->rays_primary, pr);
+        if (ex) atomicAdd(&u.stats->rays_ext, ex);
+        atomicAdd(&u.stats->wave_evals, (unsigned long long)waveEvals);
+        if (coopEvals) atomicAdd(&u.stats->coop_evals, (unsigned long long)coopEvals);
+        if (cullTotal) { atomicAdd(&u.stats->cull_total, (unsigned long long)cullTotal); atomicAdd(&u.stats->cull_skipped, (unsigned long long)cullSkipped); }
+        if (fl | fc) atomicOr(&u.stats->flags, fl | fc);
+        if (LEAN ? (tid == 0 && reinterpret_cast<const uint32_t*>(ft_lds)[FT_LDS_REPORT_WORD] != 0u) : (blockIdx.x == 0 && tid == 0)) { atomicAdd(&u.stats->clk_shader, clock64() - clk0[0]); atomicAdd(&u.stats->clk_ref, wall_clock64() - clk0[1]); }
     }
 #ifdef FT_UNION_PROFILE
     for (uint32_t k = 0; k < 12; ++k) {
