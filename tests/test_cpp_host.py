@@ -8,7 +8,7 @@ import pytest
 
 import fraytracer_amd as ft
 from fraytracer_amd import synthetic as syn
-from helpers import assert_bit_equal
+from helpers import assert_bit_equal, options_left_at_defaults  # noqa: F401  (options_left_at_defaults: a fixture)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HOST = os.path.join(ROOT, "host", "cpp")

@@ -12,16 +12,10 @@ import pytest
 
 import fraytracer_amd as ft
 import gate_scenes as G
+from helpers import host  # noqa: F401  (a fixture)
 
 MEASURED = 0.19
 F = np.float32
-
-
-@pytest.fixture(scope="module")
-def host():
-    d = ft.Device(-1)
-    yield d
-    d.close()
 
 
 def classify(host, scene):

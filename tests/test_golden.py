@@ -9,7 +9,7 @@ import pytest
 
 import fraytracer_amd as ft
 from fraytracer_amd import synthetic as syn
-from helpers import assert_bit_equal
+from helpers import assert_bit_equal, options, options_left_at_defaults  # noqa: F401  (options_left_at_defaults: a fixture)
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
 import make_golden  # noqa: E402
@@ -81,12 +81,9 @@ def test_hip_glibc_mode_reproduces_the_glibc_golden(gpu, name):
     """FT_MATH_GLIBC_FMA on the GPU reproduces glibc 2.35's FMA-build results whatever libm the host has: the restatement runs on the device"""
     z = np.load(os.path.join(GOLDEN, name + ".npz"), allow_pickle=False)
     W, H = (int(v) for v in z["size"])
-    gpu.set_option("math", 1)
-    try:
+    with options(gpu, math=1):
         img, st = gpu.scene(make_golden.GLIBC_CASES[name][0]()).render(syn.EPSILON, syn.RAY_LENGTH, ft.ImageSize(W, H), syn.default_camera())
         tm = ft.Image.toColors(2.2, None, z["image"], gpu)
-    finally:
-        gpu.set_option("math", 0)
     assert_bit_equal(img, z["image"], name)
     assert [st["rays_primary"], st["rays_shadow"], st["hits_primary"], st["hits_shadow"], st["flags"]] == z["counts"].tolist()
     assert np.array_equal(tm, z["tonemap"])

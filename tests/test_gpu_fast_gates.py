@@ -4,7 +4,6 @@ flushed, through the general interpreter (eval_distance), the lean lane evaluato
 latency evaluator (packs of 1, 8 and 32 rays born at every family, among them packs in which exactly one ray fails a guard) and whole frames; the union walks' and the carved tails' fast square roots at the same bounds;
 smooth-union runs that fill the stage exactly, exceed it, or lie behind a stage another run has filled.  Everything bit for bit against the CPU
 oracle, counters included; in the glibc arithmetic as well where ft_glibc_expf_main is called without its special cases."""
-import contextlib
 import functools
 
 import numpy as np
@@ -12,40 +11,14 @@ import pytest
 
 import fraytracer_amd as ft
 import gate_scenes as G
-from helpers import assert_bit_equal
+from helpers import assert_bit_equal, check_counts, glibc_mode, options, options_left_at_defaults  # noqa: F401  (glibc_mode, options_left_at_defaults: fixtures)
 from test_gpu_field import NORMAL_EPS, oracle_field
-from test_gpu_parity import check_counts
 
 pytestmark = pytest.mark.gpu
 
 F = np.float32
 ALL_ON = dict(cert=1, occl=1, cull=1, reuse=1)
 ALL_OFF = dict(cert=0, occl=0, cull=0, reuse=0)
-
-
-@contextlib.contextmanager
-def options(gpu, **opts):
-    old = {k: gpu.get_option(k) for k in opts}
-    try:
-        for k, v in opts.items():
-            gpu.set_option(k, v)
-        yield
-    finally:
-        for k, v in old.items():
-            gpu.set_option(k, v)
-
-
-@pytest.fixture
-def glibc_mode(gpu, oracle):
-    """FT_OPT_MATH = the glibc build this host's libm resolves to, with the oracle switched to the C runtime's expf / logf / powf"""
-    variant = ft.glibc_build_of_this_host()
-    gpu.set_option("math", variant)
-    oracle.lib.orc_set_libm(1)
-    try:
-        yield variant
-    finally:
-        oracle.lib.orc_set_libm(0)
-        gpu.set_option("math", 0)
 
 
 @functools.lru_cache(maxsize=None)

@@ -10,7 +10,7 @@ import pytest
 import fraytracer_amd as ft
 from fraytracer_amd import _lib
 from fraytracer_amd import synthetic as syn
-from helpers import assert_bit_equal
+from helpers import assert_bit_equal, glibc_mode, options, options_left_at_defaults  # noqa: F401  (glibc_mode, options_left_at_defaults: fixtures)
 
 pytestmark = pytest.mark.gpu
 
@@ -138,11 +138,8 @@ def test_grid_stride_every_workgroup_takes_a_second_brick(gpu, oracle):
     origin, step = lattice_around(ds.boundary(), 0.6, counts)
     pts = ft.lattice_points(origin, step, counts).reshape(-1, 3)
     d, _, _ = oracle_field(oracle, os_, pts)
-    gpu.set_option("max_blocks_per_cu", 1)
-    try:
+    with options(gpu, max_blocks_per_cu=1):
         got = ds.sample_lattice(origin, step, counts)
-    finally:
-        gpu.set_option("max_blocks_per_cu", 0)
     assert got.normal is None and got.material is None
     assert_bit_equal(got.distance.reshape(-1), d, "grid-stride distance")
 
@@ -342,12 +339,9 @@ def test_options_change_no_bit(gpu, oracle, name):
     base = ds.sample_lattice(origin, step, COUNTS, normal_epsilon=NORMAL_EPS, material=True)
     for opt in ("cull", "carved", "lazy_union"):
         for v in (0, 1):
-            gpu.set_option(opt, v)
-            try:
+            with options(gpu, **{opt: v}):
                 got = ds.sample_lattice(origin, step, COUNTS, normal_epsilon=NORMAL_EPS, material=True)
                 pt = ds.sample_points(pts, normal_epsilon=NORMAL_EPS)
-            finally:
-                gpu.set_option(opt, 1)
             assert_bit_equal(got.distance, base.distance, f"{opt} = {v}: distance")
             assert_bit_equal(got.normal, base.normal, f"{opt} = {v}: normal")
             assert np.array_equal(got.material, base.material), (opt, v)
@@ -437,19 +431,6 @@ def test_bounded_is_try_distance(gpu, oracle, name):
         form = scene.Object.kids[1]
         assert_bit_equal(ft.SdfForm.sample(form, origin, step, COUNTS, bounded=True, device=gpu).distance.reshape(-1), ft.SdfForm.tryDistance(form, pts, device=gpu), "tryDistance")
         assert_bit_equal(ft.SdfForm.normal(form, NORMAL_EPS, pts[inside], device=gpu), nrm, "SdfForm.normal")
-
-
-@pytest.fixture
-def glibc_mode(gpu, oracle):
-    """FT_OPT_MATH = the glibc build this host's libm resolves to, with the oracle switched to the C runtime's expf / logf / powf"""
-    variant = ft.glibc_build_of_this_host()
-    gpu.set_option("math", variant)
-    oracle.lib.orc_set_libm(1)
-    try:
-        yield variant
-    finally:
-        oracle.lib.orc_set_libm(0)
-        gpu.set_option("math", 0)
 
 
 @pytest.mark.parametrize("name", ["c3_64", "mixed_nested"])

@@ -7,7 +7,7 @@ import pytest
 import fraytracer_amd as ft
 from fraytracer_amd import SdfForm, SdfLight, SdfMaterial, SdfObject, SdfScene
 from fraytracer_amd import synthetic as syn
-from helpers import assert_bit_equal
+from helpers import assert_bit_equal, options, options_left_at_defaults  # noqa: F401  (options_left_at_defaults: a fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -127,22 +127,17 @@ def test_options_do_not_change_the_buffers(gpu, option, off):
     cam = syn.default_camera()
     W, H = 72, 53
     cases = [syn.console_scene(n=200)[0], syn.config3(n=64)[0], syn.mixed_nested()[0], syn.config5()[0]]
-    before = gpu.get_option(option)
-    try:
-        for scene in cases:
-            ds = gpu.scene(scene)
-            want, want_img, _ = ds.render_hits(EPS, LEN, ft.ImageSize(W, H), cam, shade=True)
-            want_only, _, _ = ds.render_hits(EPS, LEN, ft.ImageSize(W, H), cam)
-            gpu.set_option(option, off)
+    for scene in cases:
+        ds = gpu.scene(scene)
+        want, want_img, _ = ds.render_hits(EPS, LEN, ft.ImageSize(W, H), cam, shade=True)
+        want_only, _, _ = ds.render_hits(EPS, LEN, ft.ImageSize(W, H), cam)
+        with options(gpu, **{option: off}):
             got, img, _ = ds.render_hits(EPS, LEN, ft.ImageSize(W, H), cam, shade=True)
             got_only, _, _ = ds.render_hits(EPS, LEN, ft.ImageSize(W, H), cam)
-            gpu.set_option(option, before)
-            for a, b in ((got, want), (got_only, want_only), (got_only, want)):
-                assert np.array_equal(a.records.view(np.uint32), b.records.view(np.uint32)), option
-                assert np.array_equal(a.material, b.material), option
-            assert_bit_equal(img, want_img, f"{option} = {off}: image")
-    finally:
-        gpu.set_option(option, before)
+        for a, b in ((got, want), (got_only, want_only), (got_only, want)):
+            assert np.array_equal(a.records.view(np.uint32), b.records.view(np.uint32)), option
+            assert np.array_equal(a.material, b.material), option
+        assert_bit_equal(img, want_img, f"{option} = {off}: image")
 
 
 def test_hits_only_statistics(gpu, oracle):

@@ -2,6 +2,7 @@
 of ray r is set iff the ray's colour under the whitened Object, a black background and light i alone, white, is above zero — the one case in
 which SdfScene.fs:23 executed.  The six scenes (one per kernel family), rays, records and the three relight lights are those of
 tests/test_gpu_shade_hits.py, computed once there and shared.  Every comparison is exact."""
+import contextlib
 import ctypes as C
 import json
 import os
@@ -14,7 +15,7 @@ import pytest
 import fraytracer_amd as ft
 from fraytracer_amd import _lib
 from fraytracer_amd import synthetic as syn
-from helpers import assert_bit_equal, host_ptr as ptr
+from helpers import assert_bit_equal, glibc_math, host_ptr as ptr, options, options_left_at_defaults  # noqa: F401  (options_left_at_defaults: a fixture)
 from test_gpu_rays_device import EPS, LEN, pixel_rays, same_bits, scenes
 from test_gpu_shade_hits import BG, LIGHTS, N_SCENES, SHORTCUTS, _case, whitened
 
@@ -90,24 +91,20 @@ COUNTERS = ("rays_primary", "hits_primary", "rays_ext", "rays_shadow", "hits_sha
 def test_mask_against_the_oracle(gpu, vc):
     c = vc.c
     relit = gpu.scene(c.scene).relight(BG, LIGHTS)
-    cert = gpu.get_option("cert")
-    try:
+    with contextlib.closing(relit), options(gpu) as set_:
         vis, st = relit.light_visibility(c.rec)
         assert vis.shape == (len(c.rays),) and vis.dtype == np.uint32
         assert same_bits(vis, vc.mask), (c.name, int((vis != vc.mask).sum()))
         assert not (vis >> np.uint32(3)).any(), c.name
         assert st["rays_primary"] == 0 and st["hits_primary"] == 0 and st["rays_ext"] == 0, (c.name, st)
         assert st["rays_shadow"] == c.cnt["rays_shadow"] and st["hits_shadow"] == c.cnt["hits_shadow"] and st["flags"] == 0, (c.name, st, c.cnt)
-        gpu.set_option("cert", 0)                             # sdf_evals is compared too
+        set_(cert=0)                                          # sdf_evals is compared too
         _, sh = relit.shade_hits(c.rec)
         vis0, st0 = relit.light_visibility(c.rec)
         assert same_bits(vis0, vc.mask), c.name
         for key in COUNTERS:
             assert st0[key] == sh[key], (c.name, key, st0[key], sh[key])
         assert st0["sdf_evals"] > 0
-    finally:
-        gpu.set_option("cert", cert)
-        relit.close()
 
 
 def test_identity_a_host_forms_and_frames(gpu, vc):
@@ -199,19 +196,14 @@ def test_identity_c_and_selection(gpu, vc):
 
 @pytest.mark.parametrize("option,value", SHORTCUTS, ids=[f"{o}={v:#x}" for o, v in SHORTCUTS])
 def test_shortcuts_do_not_change_the_masks(gpu, option, value):
-    before = gpu.get_option(option)
-    try:
-        for k in range(N_SCENES):
-            v = _vis(k, gpu)
-            relit = gpu.scene(v.c.scene).relight(BG, LIGHTS)
-            gpu.set_option(option, value)
+    for k in range(N_SCENES):
+        v = _vis(k, gpu)
+        relit = gpu.scene(v.c.scene).relight(BG, LIGHTS)
+        with options(gpu, **{option: value}):
             vis, st = relit.light_visibility(v.c.rec)
-            gpu.set_option(option, before)
-            assert same_bits(vis, v.mask), (option, value, v.c.name)
-            assert st["rays_shadow"] == v.c.cnt["rays_shadow"] and st["hits_shadow"] == v.c.cnt["hits_shadow"], (option, v.c.name)
-            relit.close()
-    finally:
-        gpu.set_option(option, before)
+        assert same_bits(vis, v.mask), (option, value, v.c.name)
+        assert st["rays_shadow"] == v.c.cnt["rays_shadow"] and st["hits_shadow"] == v.c.cnt["hits_shadow"], (option, v.c.name)
+        relit.close()
 
 
 def test_glibc_arithmetic(gpu, oracle):
@@ -219,9 +211,7 @@ def test_glibc_arithmetic(gpu, oracle):
     c = _case(1, gpu)
     ds = gpu.scene(c.scene)
     relit = ds.relight(BG, LIGHTS)
-    gpu.set_option("math", ft.glibc_build_of_this_host())
-    oracle.lib.orc_set_libm(1)
-    try:
+    with contextlib.closing(relit), glibc_math(gpu, oracle):
         rec, _ = oracle.Oracle().scene(c.scene).object_try_trace(c.rays)
         want_rgb, cnt = oracle.Oracle().scene(c.relit_scene).trace_rays(c.rays)
         want, _ = oracle_bits(oracle, c.scene.Object, c.rays, LIGHTS)
@@ -231,10 +221,6 @@ def test_glibc_arithmetic(gpu, oracle):
         assert st["rays_shadow"] == cnt["rays_shadow"] and st["hits_shadow"] == cnt["hits_shadow"]
         rgb, _ = relit.shade_visible(rec, vis)
         assert_bit_equal(rgb, want_rgb, "glibc: shade_visible = oracle trace_rays with libm")
-    finally:
-        oracle.lib.orc_set_libm(0)
-        gpu.set_option("math", 0)
-        relit.close()
 
 
 @pytest.mark.parametrize("n", [1, 63, 64, 65])

@@ -4,7 +4,7 @@ import pytest
 
 import fraytracer_amd as ft
 from fraytracer_amd import synthetic as syn
-from helpers import assert_bit_equal
+from helpers import assert_bit_equal, check_counts, glibc_math, glibc_mode, options, options_left_at_defaults  # noqa: F401  (glibc_mode, options_left_at_defaults: fixtures)
 
 pytestmark = pytest.mark.gpu
 
@@ -22,14 +22,6 @@ def render_both(gpu, oracle, scene, W, H, **kw):
     g, gst = ds.render(EPS, LEN, ft.ImageSize(W, H), cam)
     o, ocnt = os_.render(EPS, LEN, W, H, cam.as_array())
     return g, gst, o, ocnt
-
-
-def check_counts(gst, ocnt):
-    assert gst["rays_primary"] == ocnt["rays_primary"]
-    assert gst["rays_shadow"] == ocnt["rays_shadow"]
-    assert gst["hits_primary"] == ocnt["hits_primary"]
-    assert gst["hits_shadow"] == ocnt["hits_shadow"]
-    assert gst["flags"] == ocnt["flags"] == 0
 
 
 def test_product_build_is_the_one_under_test(gpu):
@@ -105,19 +97,6 @@ def test_smooth_union_guard_fallbacks(gpu, oracle):
     with np.errstate(all="ignore"):
         assert_bit_equal(d, O.form_distance(form, pts), "smooth-union distance incl. guard fallbacks")
     assert np.isinf(d).any() and np.isnan(d).any()
-
-
-@pytest.fixture
-def glibc_mode(gpu, oracle):
-    """FT_OPT_MATH = the glibc build this host's libm resolves to, with the oracle switched to the C runtime's expf / logf / powf"""
-    variant = ft.glibc_build_of_this_host()
-    gpu.set_option("math", variant)
-    oracle.lib.orc_set_libm(1)
-    try:
-        yield variant
-    finally:
-        oracle.lib.orc_set_libm(0)
-        gpu.set_option("math", 0)
 
 
 def test_glibc_restatement_on_the_device(gpu, oracle):
@@ -199,9 +178,8 @@ def test_glibc_math_mode_renders_what_the_oracle_renders_with_libm(gpu, oracle, 
     o, ocnt = os_.render(EPS, LEN, 256, 256, cam.as_array())
     assert_bit_equal(g, o, "C3 256^2 in glibc mode")
     check_counts(gst, ocnt)
-    gpu.set_option("math", 0)
-    g0, _ = ds.render(EPS, LEN, ft.ImageSize(256, 256), cam)
-    gpu.set_option("math", glibc_mode)
+    with options(gpu, math=0):
+        g0, _ = ds.render(EPS, LEN, ft.ImageSize(256, 256), cam)
     assert not np.array_equal(g0.view(np.uint32), g.view(np.uint32))           # the two arithmetics are different functions
     g4, _ = ds.render(EPS, LEN, ft.ImageSize(96, 96), cam, spp=4, ao_samples=3, ao_radius=0.5)
     o4, _ = os_.render(EPS, LEN, 96, 96, cam.as_array(), spp=4, ao_samples=3, ao_radius=0.5)
@@ -230,8 +208,8 @@ def test_glibc_math_mode_renders_what_the_oracle_renders_with_libm(gpu, oracle, 
     c2, _ = syn.config2(seed=4, size=64)
     ds4 = gpu.scene(c2)
     a, _ = ds4.render(EPS, LEN, ft.ImageSize(64, 64), cam)
-    gpu.set_option("math", 0)
-    b, _ = ds4.render(EPS, LEN, ft.ImageSize(64, 64), cam)
+    with options(gpu, math=0):
+        b, _ = ds4.render(EPS, LEN, ft.ImageSize(64, 64), cam)
     assert_bit_equal(a, b, "C2 is the same in every math mode")
 
 
@@ -256,8 +234,7 @@ def test_latency_mode_is_bit_identical(gpu, oracle, k):
     children), grid unions of every primitive kind, slots, on-demand sub-programs, NaN rays, EXTENSION builds, the glibc arithmetic."""
     from fraytracer_amd import SdfForm, SdfObject, SdfMaterial, SdfScene
     cam = syn.default_camera()
-    gpu.set_option("tail_k", k)
-    try:
+    with options(gpu, tail_k=k):
         cases = [("C3 n=256", syn.config3(n=256, size=96)[0], 96, {}), ("C3 n=37", syn.config3(n=37, size=64)[0], 64, {}),
                  ("C3 n=300 (two segments)", syn.config3(n=300, size=48)[0], 48, {}), ("C3 ext", syn.config3(n=64, size=64)[0], 64, dict(spp=4, ao_samples=3, ao_radius=0.5)),
                  ("C2", syn.config2(seed=6, size=96)[0], 96, {}), ("C2 boxes + AO", syn.config2(boxes=True, size=64)[0], 64, dict(ao_samples=4, ao_radius=0.5)),
@@ -291,17 +268,11 @@ def test_latency_mode_is_bit_identical(gpu, oracle, k):
         orr, ocnt = osn.trace_rays(nan_rays)
         assert_bit_equal(gr, orr, "NaN rays"); assert gst["flags"] == ocnt["flags"] == 3
         # the glibc arithmetic through the cooperative lean evaluation
-        variant = ft.glibc_build_of_this_host()
-        gpu.set_option("math", variant); oracle.lib.orc_set_libm(1)
-        try:
+        with glibc_math(gpu, oracle):
             ds, os_ = both(gpu, oracle, syn.config3(n=256, size=64)[0])
             g, _ = ds.render(EPS, LEN, ft.ImageSize(64, 64), cam)
             o, _ = os_.render(EPS, LEN, 64, 64, cam.as_array())
             assert_bit_equal(g, o, f"C3 in glibc mode, tail_k = {k}")
-        finally:
-            gpu.set_option("math", 0); oracle.lib.orc_set_libm(0)
-    finally:
-        gpu.set_option("tail_k", -1)
 
 
 def test_hand_out_options_do_not_change_the_frame(gpu, oracle):
@@ -311,9 +282,9 @@ def test_hand_out_options_do_not_change_the_frame(gpu, oracle):
     scene, _ = syn.config3(n=64, size=200)
     ds, os_ = both(gpu, oracle, scene)
     want, ocnt = os_.render(EPS, LEN, 200, 136, cam.as_array())
-    try:
+    with options(gpu) as set_:
         for chunk, guided, k in ((64, 1, 32), (32, 0, 32), (16, 0, 32), (32, 1, 0), (16, 0, 2), (64, 0, -1)):
-            gpu.set_option("chunk", chunk); gpu.set_option("guided", guided); gpu.set_option("tail_k", k)
+            set_(chunk=chunk, guided=guided, tail_k=k)
             g, gst = ds.render(EPS, LEN, ft.ImageSize(200, 136), cam)
             assert_bit_equal(g, want, f"chunk {chunk}, guided {guided}, tail_k {k}")
             check_counts(gst, ocnt)
@@ -321,10 +292,8 @@ def test_hand_out_options_do_not_change_the_frame(gpu, oracle):
         ds2, os2 = both(gpu, oracle, c2)
         want2, _ = os2.render(EPS, LEN, 96, 96, cam.as_array())
         for chunk in (32, 16):
-            gpu.set_option("chunk", chunk)
+            set_(chunk=chunk)
             assert_bit_equal(ds2.render(EPS, LEN, ft.ImageSize(96, 96), cam)[0], want2, f"C2, chunk {chunk}")
-    finally:
-        gpu.set_option("chunk", 64); gpu.set_option("guided", 0); gpu.set_option("tail_k", -1)
 
 
 def test_child_culling_is_exact_and_happens(gpu, oracle):
@@ -333,34 +302,30 @@ def test_child_culling_is_exact_and_happens(gpu, oracle):
     (child, ray) pairs is dropped, with it off none — for several strengths, child counts beyond one culling row, a second (non-culled)
     run's worth of children, both arithmetics, and with the latency mode forced on (which bypasses the pass)."""
     cam = syn.default_camera()
-    try:
+    with options(gpu) as set_:
         # the pass needs the rays of a wave (one 8x8 tile) close together, i.e. a fine pixel pitch = 1 / max(W, H): wide, low frames
         for n, W, H, strength in ((256, 3072, 24, 0.25), (300, 2048, 16, 0.5), (64, 1024, 24, 0.1), (40, 64, 56, 1.0), (256, 96, 88, 0.3)):
             scene, _ = syn.config3(n=n, size=W, strength=strength)
             ds, os_ = both(gpu, oracle, scene)
             want, ocnt = os_.render(EPS, LEN, W, H, cam.as_array())
             for cull in (1, 0):
-                gpu.set_option("cull", cull)
+                set_(cull=cull)
                 g, gst = ds.render(EPS, LEN, ft.ImageSize(W, H), cam)
                 assert_bit_equal(g, want, f"{n} spheres, strength {strength}, cull {cull}")
                 check_counts(gst, ocnt)
                 if cull == 0: assert gst["culled_fraction"] == 0.0
                 elif W >= 1024 and strength <= 0.25: assert gst["culled_fraction"] > 0.05, gst   # (a softer union decays too slowly to drop anything in a ball of radius 4)
-        gpu.set_option("cull", 1); gpu.set_option("tail_k", 64)
+        set_(cull=1, tail_k=64)
         scene, _ = syn.config3(n=256, size=2048)
         ds, os_ = both(gpu, oracle, scene)
         g, gst = ds.render(EPS, LEN, ft.ImageSize(2048, 16), cam)
         assert_bit_equal(g, os_.render(EPS, LEN, 2048, 16, cam.as_array())[0], "latency mode forced: no culling pass")
         assert gst["culled_fraction"] == 0.0
-        gpu.set_option("tail_k", -1); gpu.set_option("math", ft.glibc_build_of_this_host()); oracle.lib.orc_set_libm(1)
-        try:
+        set_(tail_k=-1)
+        with glibc_math(gpu, oracle):
             g, gst = ds.render(EPS, LEN, ft.ImageSize(2048, 16), cam)
             assert_bit_equal(g, os_.render(EPS, LEN, 2048, 16, cam.as_array())[0], "culling in glibc mode")
             assert gst["culled_fraction"] > 0.05, gst
-        finally:
-            gpu.set_option("math", 0); oracle.lib.orc_set_libm(0)
-    finally:
-        gpu.set_option("cull", 1); gpu.set_option("tail_k", -1)
 
 
 def test_child_culling_in_the_general_kernels(gpu, oracle):
@@ -387,7 +352,7 @@ def test_child_culling_in_the_general_kernels(gpu, oracle):
                              enumerate(rng.pointOnSphere(3.5) for _ in range(12))])
     cases = [("smooth union in a union", in_union, {}, True), ("smooth union in an intersect", in_intersect, {}, True), ("run behind other kinds", behind_others, {}, True),
              ("glass blob (EXTENSION)", glass, dict(spp=4, spectral=4, max_bounces=4), False), ("smooth union beside on-demand children", crowd, {}, False)]
-    try:
+    with options(gpu) as set_:
         for name, obj, kw, must_cull in cases:
             scene = SdfScene(obj, syn.BACKGROUND, syn.program_lights())
             ds, os_ = both(gpu, oracle, scene)
@@ -395,15 +360,13 @@ def test_child_culling_in_the_general_kernels(gpu, oracle):
             for W, H in ((1536, 16), (96, 64)):
                 want, ocnt = os_.render(EPS, LEN, W, H, cam.as_array(), **kw)
                 for cull in (1, 0):
-                    gpu.set_option("cull", cull)
+                    set_(cull=cull)
                     g, gst = ds.render(EPS, LEN, ft.ImageSize(W, H), cam, **kw)
                     assert_bit_equal(g, want, f"{name} {W}x{H}, cull {cull}")
                     check_counts(gst, ocnt)
                     if cull == 0: assert gst["culled_fraction"] == 0.0
                     elif must_cull and W >= 1024: assert gst["culled_fraction"] > 0.005, (name, gst["culled_fraction"])   # (how much depends on how the strip cuts the blob: 2 - 30 %)
             ds.close()
-    finally:
-        gpu.set_option("cull", 1)
 
 
 def test_escape_shortcut_changes_no_pixel(gpu, oracle):
@@ -415,13 +378,13 @@ def test_escape_shortcut_changes_no_pixel(gpu, oracle):
     cases = [("C3 lean", syn.config3(n=64, size=256)[0], 256, 64), ("C2", syn.config2(seed=4, size=128)[0], 128, 96),
              ("Program.fs structure", syn.console_scene(n=120, size=160)[0], 160, 120), ("mixed nested", syn.mixed_nested()[0], 96, 96),
              ("combinator zoo (calls)", syn.combinator_zoo()[0], 96, 80)]
-    try:
+    with options(gpu) as set_:
         for name, scene, W, H in cases:
             ds, os_ = both(gpu, oracle, scene)
             want, ocnt = os_.render(EPS, LEN, W, H, cam.as_array())
             evals = {}
             for esc in (1, 0):
-                gpu.set_option("escape", esc)
+                set_(escape=esc)
                 g, gst = ds.render(EPS, LEN, ft.ImageSize(W, H), cam)
                 assert_bit_equal(g, want, f"{name}, escape {esc}")
                 check_counts(gst, ocnt)
@@ -431,7 +394,7 @@ def test_escape_shortcut_changes_no_pixel(gpu, oracle):
                 kw = dict(spp=4, ao_samples=3, ao_radius=0.7)
                 want_x = os_.render(EPS, LEN, W, H, cam.as_array(), **kw)[0]
                 for esc in (1, 0):
-                    gpu.set_option("escape", esc)
+                    set_(escape=esc)
                     assert_bit_equal(ds.render(EPS, LEN, ft.ImageSize(W, H), cam, **kw)[0], want_x, f"{name} with AO and 4 spp, escape {esc}")
             cx, cy, cz, R = ds.support_sphere()
             assert R > 0
@@ -446,7 +409,7 @@ def test_escape_shortcut_changes_no_pixel(gpu, oracle):
             d[110:120] *= np.float32(37.5)                                                                                    # non-unit directions
             rays = np.concatenate([o, d, rng.uniform(0.5, 60.0, (n, 1)).astype(np.float32), np.full((n, 1), 0.01, np.float32)], axis=1).astype(np.float32)
             for esc in (1, 0):
-                gpu.set_option("escape", esc)
+                set_(escape=esc)
                 with np.errstate(all="ignore"):
                     assert_bit_equal(ds.trace_rays(rays)[0], os_.trace_rays(rays)[0], f"{name}: ray buffer, escape {esc}")
                     gf, of = ds.form_try_trace(rays), os_.form_try_trace(rays)
@@ -458,12 +421,10 @@ def test_escape_shortcut_changes_no_pixel(gpu, oracle):
         kw = dict(spp=4, spectral=4, max_bounces=6)
         want5, ocnt5 = os5.render(EPS, LEN, 96, 96, cam.as_array(), **kw)
         for esc in (1, 0):
-            gpu.set_option("escape", esc)
+            set_(escape=esc)
             g5, gst5 = ds5.render(EPS, LEN, ft.ImageSize(96, 96), cam, **kw)
             assert_bit_equal(g5, want5, f"glass, escape {esc}")
             assert gst5["rays_ext"] == ocnt5["rays_ext"] and gst5["hits_primary"] == ocnt5["hits_primary"]
-    finally:
-        gpu.set_option("escape", 1)
 
 
 def test_lazy_union_under_intersect_changes_no_pixel(gpu, oracle):
@@ -491,7 +452,7 @@ def test_lazy_union_under_intersect_changes_no_pixel(gpu, oracle):
              ("union under subtract", SdfScene(holed, syn.BACKGROUND, syn.program_lights())), ("form-level subtract(intersect(union, sphere), capsule)", SdfScene(form_level, syn.BACKGROUND, syn.program_lights())),
              ("torus as second child", SdfScene(by_torus, syn.BACKGROUND, syn.program_lights())), ("carved", SdfScene(carved, syn.BACKGROUND, syn.program_lights())),
              ("intersects inside a union", SdfScene(nested, syn.BACKGROUND, syn.program_lights()))]
-    try:
+    with options(gpu) as set_:
         for name, scene in cases:
             ds, os_ = both(gpu, oracle, scene)
             W, H = 200, 136
@@ -503,7 +464,7 @@ def test_lazy_union_under_intersect_changes_no_pixel(gpu, oracle):
             want_obj = os_.object_try_trace(rays)
             want_obj = want_obj[0] if isinstance(want_obj, tuple) else want_obj
             for lazy in (1, 0):
-                gpu.set_option("lazy_union", lazy)
+                set_(lazy_union=lazy)
                 g, gst = ds.render(EPS, LEN, ft.ImageSize(W, H), cam)
                 assert_bit_equal(g, want, f"{name}, lazy_union {lazy}")
                 check_counts(gst, ocnt)
@@ -511,8 +472,6 @@ def test_lazy_union_under_intersect_changes_no_pixel(gpu, oracle):
                 assert_bit_equal(got_obj[0] if isinstance(got_obj, tuple) else got_obj, want_obj, f"{name}: SdfObject.tryTrace (materials), lazy_union {lazy}")
                 with np.errstate(all="ignore"):
                     assert_bit_equal(ds.trace_rays(rays)[0], os_.trace_rays(rays)[0], f"{name}: ray buffer, lazy_union {lazy}")
-    finally:
-        gpu.set_option("lazy_union", 1)
 
 
 def test_culling_on_random_smooth_unions(gpu, oracle):
@@ -747,11 +706,8 @@ def test_host_output_pipeline_is_bit_identical(gpu, oracle):
     ds = gpu.scene(scene)
     for (W, H) in [(1536, 1024), (2048, 2048), (300, 5000), (64, 64)]:
         S = ft.ImageSize(W, H)
-        gpu.set_option("host_chunks", 1); gpu.set_option("host_pin", 0)            # one launch, one pageable copy after it
-        try:
+        with options(gpu, host_chunks=1, host_pin=0):              # one launch, one pageable copy after it
             want, st0 = ds.render(EPS, LEN, S, cam)
-        finally:
-            gpu.set_option("host_chunks", 0); gpu.set_option("host_pin", 1)
         got, st = ds.render(EPS, LEN, S, cam)                      # fresh pageable array: pinned inside the call
         assert_bit_equal(got, want, f"{W}x{H} pageable")
         for k in ("rays_primary", "rays_shadow", "hits_primary", "hits_shadow", "sdf_evals"):
@@ -1439,7 +1395,7 @@ def test_carved_union_kernels_against_oracle(gpu, oracle):
     eps = rr.choice([0.01, 0.05, 0.3, 2.0, 1e-3], (600, 1)).astype(np.float32)
     rays = np.concatenate([o, d, np.full((600, 1), 30, np.float32), eps], axis=1).astype(np.float32)
     rays[0, 0] = np.nan; rays[1, 1] = 3e4; rays[2, 2] = -1e30; rays[3, 3:6] = 0.0; rays[4, 6] = np.inf; rays[5, 0:3] = 0.0
-    try:
+    with options(gpu) as set_:
         for name, scene in _carved_cases():
             ds, os_ = both(gpu, oracle, scene)
             assert ds.info()["fast_path"] == 3, name
@@ -1447,7 +1403,7 @@ def test_carved_union_kernels_against_oracle(gpu, oracle):
             with np.errstate(all="ignore"):
                 want_rays, want_rcnt = os_.trace_rays(rays)
             for carved, lazy, esc in ((1, 1, 1), (0, 1, 1), (1, 0, 1), (1, 1, 0)):
-                gpu.set_option("carved", carved); gpu.set_option("lazy_union", lazy); gpu.set_option("escape", esc)
+                set_(carved=carved, lazy_union=lazy, escape=esc)
                 g, gst = ds.render(EPS, LEN, ft.ImageSize(W, H), cam)
                 tag = f"{name}: carved {carved}, lazy {lazy}, escape {esc}"
                 assert_bit_equal(g, want, tag)
@@ -1457,8 +1413,6 @@ def test_carved_union_kernels_against_oracle(gpu, oracle):
                 assert_bit_equal(got_rays, want_rays, tag + " (ray buffer)")
                 assert rst["flags"] == want_rcnt["flags"], (tag, rst["flags"], want_rcnt["flags"])
             ds.close()
-    finally:
-        gpu.set_option("carved", 1); gpu.set_option("lazy_union", 1); gpu.set_option("escape", 1)
 
 
 def _offset_scenes(off):
@@ -1497,7 +1451,7 @@ def test_escape_shortcut_at_its_edge(gpu, oracle, offset):
     unit and non-unit directions (a point light's shadow direction is diff / |diff|^2), scenes 7000 away from the origin.  Colours, ray / hit
     counters and flags must be the oracle's with the shortcut on and off — the oracle has no shortcut at all."""
     rng = np.random.default_rng(5)
-    try:
+    with options(gpu) as set_:
         for name, scene in _offset_scenes(offset):
             ds, os_ = both(gpu, oracle, scene)
             cx, cy, cz, R = ds.support_sphere()
@@ -1522,7 +1476,7 @@ def test_escape_shortcut_at_its_edge(gpu, oracle, offset):
                 want, ocnt = os_.trace_rays(rays)
             evals = {}
             for esc in (1, 0):
-                gpu.set_option("escape", esc)
+                set_(escape=esc)
                 with np.errstate(all="ignore"):
                     got, gst = ds.trace_rays(rays)
                 assert_bit_equal(got, want, f"{name} at {offset}, escape {esc}")
@@ -1533,8 +1487,6 @@ def test_escape_shortcut_at_its_edge(gpu, oracle, offset):
             if name == "carved" and offset == (0.0, 0.0, 0.0):
                 assert evals[1] < evals[0], evals                                  # the shortcut is alive (not gated away) where it matters
             ds.close()
-    finally:
-        gpu.set_option("escape", 1)
 
 
 def test_a_scene_of_nan_constants_takes_no_escape_shortcut(gpu, oracle):
@@ -1555,16 +1507,14 @@ def test_a_scene_of_nan_constants_takes_no_escape_shortcut(gpu, oracle):
         rays = np.array([[0, 0, -5, 0, 0, 1, 30, 0.01], [0, 3, -5, 0, 0, 1, 30, 0.01], [4, 0, 0, 1, 0, 0, 30, 0.01], [0, 0, -5, 0, 0, -1, 30, 0.01]], np.float32)
         with np.errstate(all="ignore"):
             want, ocnt = os_.trace_rays(rays)
-        try:
+        with options(gpu) as set_:
             for esc in (1, 0):
-                gpu.set_option("escape", esc)
+                set_(escape=esc)
                 with np.errstate(all="ignore"):
                     got, gst = ds.trace_rays(rays)
                 assert_bit_equal(got, want, f"NaN constants, escape {esc}")
                 assert gst["flags"] == ocnt["flags"], (esc, gst["flags"], ocnt["flags"])
             flagged += ocnt["flags"] != 0
-        finally:
-            gpu.set_option("escape", 1)
         ds.close()
     assert flagged >= 3            # NaN distance (flag 1) or MathF.Sign(NaN) (flag 2) was really met
 
@@ -1586,7 +1536,7 @@ def test_reusing_the_centre_probe_as_a_secondary_rays_first_step_changes_no_pixe
     d = rr.normal(size=(300, 3)).astype(np.float32); d /= np.linalg.norm(d, axis=1, keepdims=True)
     rays = np.concatenate([o, d, np.full((300, 1), 30, np.float32), rr.choice([0.01, 0.2, 1.0], (300, 1)).astype(np.float32)], axis=1).astype(np.float32)
     rays[0, 0] = np.nan
-    try:
+    with options(gpu) as set_:
         for name, scene, kw in cases:
             ds, os_ = both(gpu, oracle, scene)
             W, H = 112, 80
@@ -1595,7 +1545,7 @@ def test_reusing_the_centre_probe_as_a_secondary_rays_first_step_changes_no_pixe
                 want_rays, rcnt = os_.trace_rays(rays)
             evals = {}
             for reuse in (1, 0):
-                gpu.set_option("reuse", reuse)
+                set_(reuse=reuse)
                 g, gst = ds.render(EPS, LEN, ft.ImageSize(W, H), cam, **kw)
                 assert_bit_equal(g, want, f"{name}, reuse {reuse}")
                 check_counts(gst, ocnt)
@@ -1608,15 +1558,12 @@ def test_reusing_the_centre_probe_as_a_secondary_rays_first_step_changes_no_pixe
                 # the NaN ray's query point — the reference, whose running minimum is NaN by then, never reaches that child; bits 0 and 2 are exact
                 assert rst["flags"] & ~2 == rcnt["flags"] & ~2 and (rst["flags"] & 1), (name, rst["flags"], rcnt["flags"])
                 if ds.info()["fast_path"] in (1, 3) and not kw: assert rst["flags"] == rcnt["flags"], (name, rst["flags"], rcnt["flags"])
-            gpu.set_option("escape", 0)                                # without the escape shortcut every secondary ray makes its first step: exactly one evaluation each is saved
-            try:
+            with options(gpu, escape=0):                  # without the escape shortcut every secondary ray makes its first step: exactly one evaluation each is saved
                 n = {}
                 for reuse in (1, 0):
-                    gpu.set_option("reuse", reuse)
+                    set_(reuse=reuse)
                     _, st = ds.render(EPS, LEN, ft.ImageSize(W, H), cam, **{k: v for k, v in kw.items() if k != "max_bounces" and k != "spectral"})
                     n[reuse] = (st["sdf_evals"], st["rays_primary"] + st["rays_shadow"] + (st["rays_ext"] if kw.get("ao_radius", 0.0) > 0.0 else 0))     # an occlusion ray of Length <= 0 makes no evaluation to save
-            finally:
-                gpu.set_option("escape", 1)
             if "max_bounces" not in kw:
                 assert n[0][0] - n[1][0] == n[1][1], (name, n)
             assert evals[1] <= evals[0]
@@ -1630,13 +1577,11 @@ def test_reusing_the_centre_probe_as_a_secondary_rays_first_step_changes_no_pixe
             cam2 = Camera.lookAt(Position=pos, LookAt=(0.3, 0.2, 5.0), Up=(0.0, 1.0, 0.0), Lens=Lens.create(60.0))
             want, ocnt = os_.render(EPS, LEN, 72, 56, cam2.as_array())
             for reuse in (1, 0):
-                gpu.set_option("reuse", reuse)
+                set_(reuse=reuse)
                 g, gst = ds.render(EPS, LEN, ft.ImageSize(72, 56), cam2)
                 assert_bit_equal(g, want, f"{name}, reuse {reuse}")
                 check_counts(gst, ocnt)
             ds.close()
-    finally:
-        gpu.set_option("reuse", 1); gpu.set_option("escape", 1)
 
 
 def test_launch_rules_count_what_was_recorded(gpu):

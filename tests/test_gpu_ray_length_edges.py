@@ -6,7 +6,6 @@ oracle's, bit for bit; for radii <= 0 the frame is also the one without occlusio
 
 On the parent of the commit that added this file, with FT_OPT_REUSE on (the default), the cases with a radius <= 0 and the zero-Length shadow ray
 fail; with it off they pass."""
-import contextlib
 import json
 import os
 import subprocess
@@ -18,8 +17,7 @@ import pytest
 import fraytracer_amd as ft
 from fraytracer_amd import synthetic as syn
 import edge_scenes as edge
-from helpers import assert_bit_equal
-from test_gpu_parity import check_counts, glibc_mode  # noqa: F401  (glibc_mode is a fixture)
+from helpers import assert_bit_equal, check_counts, glibc_mode, options, options_left_at_defaults  # noqa: F401  (glibc_mode, options_left_at_defaults: fixtures)
 
 pytestmark = pytest.mark.gpu
 
@@ -37,18 +35,6 @@ SAMPLING = [(1, 1), (1, 4), (4, 4), (4, 16)]      # (spp, ao_samples)
 MODES = {"reuse on": dict(reuse=1), "reuse off": dict(reuse=0), "reuse on, no other shortcut": dict(reuse=1, escape=0, cert=0, occl=0)}
 SMOOTH = ["lean", "general", "calls", "glass"]    # the scenes that hold a unionSmooth: the _libm twins of their kernels
 VIEWS = {"lean": 2, "cavity": 1, "general": 2, "calls": 2, "glass": 2}      # cameras inside; one outside is added
-
-
-@contextlib.contextmanager
-def options(gpu, **opts):
-    old = {k: gpu.get_option(k) for k in opts}
-    try:
-        for k, v in opts.items():
-            gpu.set_option(k, v)
-        yield
-    finally:
-        for k, v in old.items():
-            gpu.set_option(k, v)
 
 
 _FAMILY, _WANT, _DS = {}, {}, {}
@@ -191,15 +177,12 @@ def test_occlusion_rays_in_the_glibc_math_modes(gpu, oracle, glibc_mode):
                     check(g, gst, want(oracle, name, libm=1, **kw), what)
                     if radius <= 0.0:
                         assert_bit_equal(g, want(oracle, name, libm=1)[0], what + ": the frame without occlusion rays")
-                gpu.set_option("math", 3 - glibc_mode)
-                try:
+                with options(gpu, math=3 - glibc_mode):
                     plain, pst = ds.render(EPS, LEN, ft.ImageSize(W, H), cams[0], **ext)
                     for radius in (0.0, -1.0):
                         g, gst = ds.render(EPS, LEN, ft.ImageSize(W, H), cams[0], **dict(ext, spp=1, ao_samples=4, ao_radius=radius))
                         assert_bit_equal(g, plain, f"{name}, the other glibc variant, ao_radius {radius!r}, reuse {reuse}")
                         check_counts(gst, pst)
-                finally:
-                    gpu.set_option("math", glibc_mode)
 
 
 # ---- primary rays: the shared camera evaluation (start_job: camKnown && s.len > 0) must not turn a ray of Length <= 0 into a hit at step 0 ---------

@@ -12,13 +12,12 @@ import pytest
 
 import fraytracer_amd as ft
 from fraytracer_amd import synthetic as syn
-from helpers import assert_bit_equal
+from helpers import COUNTERS, assert_bit_equal, options, options_left_at_defaults  # noqa: F401  (options_left_at_defaults: a fixture)
 
 pytestmark = pytest.mark.gpu
 
 EPS, LEN = syn.EPSILON, syn.RAY_LENGTH
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-COUNTERS = ("rays_primary", "rays_shadow", "hits_primary", "hits_shadow", "flags")
 
 
 def scenes():
@@ -81,9 +80,7 @@ def same_bits(a, b):
 
 
 def test_shade_records_and_material_in_one_launch(gpu, oracle):
-    cert = gpu.get_option("cert")
-    gpu.set_option("cert", 0)                                # sdf_evals is compared too
-    try:
+    with options(gpu, cert=0):                               # sdf_evals is compared too
         for k, (name, scene, W, H) in enumerate(scenes()):
             ds = gpu.scene(scene)
             rays, _ = ray_buffer(oracle, ds, k, W, H)
@@ -97,8 +94,6 @@ def test_shade_records_and_material_in_one_launch(gpu, oracle):
             for c in COUNTERS + ("sdf_evals",):
                 assert st[c] == ref_st[c], (name, c, st[c], ref_st[c])
             assert st["rays_primary"] == len(rays) and st["hits_primary"] == int(hits.hit.sum()), name
-    finally:
-        gpu.set_option("cert", cert)
     ds = gpu.scene(scenes()[1][1])                           # certificate on (the lean kernel's default): every counter but sdf_evals
     rays, _ = ray_buffer(oracle, ds, 1, 36, 27)
     _, _, st = ds.trace_rays_hits(rays)
@@ -108,9 +103,7 @@ def test_shade_records_and_material_in_one_launch(gpu, oracle):
 
 
 def test_hits_only(gpu, oracle):
-    cert = gpu.get_option("cert")
-    gpu.set_option("cert", 0)
-    try:
+    with options(gpu, cert=0):
         for k, (name, scene, W, H) in enumerate(scenes()):
             ds = gpu.scene(scene)
             rays, _ = ray_buffer(oracle, ds, k, W, H)
@@ -125,8 +118,6 @@ def test_hits_only(gpu, oracle):
             assert st["rays_shadow"] == 0 and st["hits_shadow"] == 0, name
             only, _, _ = ds.trace_rays_hits(rays, shade=False, records=False)
             assert only.records is None and np.array_equal(only.material, hits.material), name
-    finally:
-        gpu.set_option("cert", cert)
 
 
 def test_materials(gpu, oracle):
@@ -151,23 +142,18 @@ def test_materials(gpu, oracle):
 
 @pytest.mark.parametrize("option", ["cull", "escape", "lazy_union", "carved", "reuse", "cert"])
 def test_shortcuts_do_not_change_the_results(gpu, oracle, option):
-    before = gpu.get_option(option)
-    try:
-        for k, (name, scene, W, H) in enumerate(scenes()):
-            ds = gpu.scene(scene)
-            rays, _ = ray_buffer(oracle, ds, k, W, H)
-            gpu.set_option(option, before)
-            want, want_rgb, _ = ds.trace_rays_hits(rays)
-            want_only, _, _ = ds.trace_rays_hits(rays, shade=False)
-            gpu.set_option(option, 0)
+    for k, (name, scene, W, H) in enumerate(scenes()):
+        ds = gpu.scene(scene)
+        rays, _ = ray_buffer(oracle, ds, k, W, H)
+        want, want_rgb, _ = ds.trace_rays_hits(rays)
+        want_only, _, _ = ds.trace_rays_hits(rays, shade=False)
+        with options(gpu, **{option: 0}):
             got, rgb, _ = ds.trace_rays_hits(rays)
             got_only, _, _ = ds.trace_rays_hits(rays, shade=False)
-            for a, b in ((got, want), (got_only, want_only), (got_only, want)):
-                assert same_bits(a.records, b.records), (option, name)
-                assert np.array_equal(a.material, b.material), (option, name)
-            assert_bit_equal(rgb, want_rgb, f"{option} = 0, {name}: rgb")
-    finally:
-        gpu.set_option(option, before)
+        for a, b in ((got, want), (got_only, want_only), (got_only, want)):
+            assert same_bits(a.records, b.records), (option, name)
+            assert np.array_equal(a.material, b.material), (option, name)
+        assert_bit_equal(rgb, want_rgb, f"{option} = 0, {name}: rgb")
 
 
 def test_plain_trace_rays_stays_on_the_carved_kernels(gpu, oracle):

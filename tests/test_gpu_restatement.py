@@ -16,23 +16,11 @@ import pytest
 
 import fraytracer_amd as ft
 import form_scenes as S
-from helpers import assert_bit_equal
+from helpers import assert_bit_equal, options, options_left_at_defaults  # noqa: F401  (options_left_at_defaults: a fixture)
 
 pytestmark = pytest.mark.gpu
 
 ARRANGEMENTS = [dict(carved=c, lazy_union=l, tail_k=t) for c, l, t in itertools.product((1, 0), (1, 0), (-1, 64))]
-
-
-@contextlib.contextmanager
-def options(gpu, **opts):
-    old = {k: gpu.get_option(k) for k in opts}
-    try:
-        for k, v in opts.items():
-            gpu.set_option(k, v)
-        yield
-    finally:
-        for k, v in old.items():
-            gpu.set_option(k, v)
 
 
 @contextlib.contextmanager

@@ -5,6 +5,7 @@ family), frame sizes and rays are those of tests/test_gpu_rays_device.py: the pi
 Evaluation counts measured on the MI355X with cert = 0 and reuse = 0 (test_evaluation_count asserts the identity and prints the figures), as
 sdf_evals of shade_hits = trace_rays - object_try_trace: console_like 31450 = 42950 - 11500, config3 19801 = 35189 - 15388, mixed_nested
 8248 = 16237 - 7989, console_scene 38757 = 54915 - 16158, config2 boxes 22937 = 35569 - 12632, config5 15654 = 26165 - 10511."""
+import contextlib
 import json
 import os
 import subprocess
@@ -16,8 +17,8 @@ import pytest
 import fraytracer_amd as ft
 from fraytracer_amd import synthetic as syn
 from fraytracer_amd.api import Material, Object
-from helpers import assert_bit_equal
-from test_gpu_rays_device import COUNTERS, EPS, LEN, ray_buffer, same_bits, scenes
+from helpers import COUNTERS, assert_bit_equal, options, options_left_at_defaults  # noqa: F401  (options_left_at_defaults: a fixture)
+from test_gpu_rays_device import EPS, LEN, ray_buffer, same_bits, scenes
 
 pytestmark = pytest.mark.gpu
 
@@ -122,23 +123,17 @@ def test_evaluation_count(gpu, case):
     """no centre probe ran, so every shadow ray's first evaluation is computed: with the certificate and the reuse off for all three calls,
     sdf_evals(shade_hits) = sdf_evals(trace_rays) - sdf_evals(object_try_trace) on the relit scene"""
     c = case
-    before = {k: gpu.get_option(k) for k in ("cert", "reuse")}
     relit = relit_of(gpu, c)
-    try:
-        gpu.set_option("cert", 0); gpu.set_option("reuse", 0)
+    with contextlib.closing(relit), options(gpu, cert=0, reuse=0) as set_:
         _, st = relit.shade_hits(c.rec)
         _, tr = relit.trace_rays(c.rays)
         _, ob = relit.object_try_trace(c.rays)
         print(f"{c.name}: sdf_evals shade_hits {st['sdf_evals']} trace_rays {tr['sdf_evals']} object_try_trace {ob['sdf_evals']}")
         assert st["sdf_evals"] == tr["sdf_evals"] - ob["sdf_evals"], (c.name, st["sdf_evals"], tr["sdf_evals"], ob["sdf_evals"])
         assert st["sdf_evals"] > 0
-        gpu.set_option("reuse", 1)                            # the option does not reach ft_shade_hits: there is nothing to reuse
+        set_(reuse=1)                                         # the option does not reach ft_shade_hits: there is nothing to reuse
         _, st1 = relit.shade_hits(c.rec)
         assert st1["sdf_evals"] == st["sdf_evals"], c.name
-    finally:
-        for k, v in before.items():
-            gpu.set_option(k, v)
-        relit.close()
 
 
 SHORTCUTS = [("escape", 0), ("cert", 0), ("cert_policy", 0x01010100), ("cull", 0), ("lazy_union", 0), ("carved", 0), ("tail_k", 64)]
@@ -146,19 +141,14 @@ SHORTCUTS = [("escape", 0), ("cert", 0), ("cert_policy", 0x01010100), ("cull", 0
 
 @pytest.mark.parametrize("option,value", SHORTCUTS, ids=[f"{o}={v:#x}" for o, v in SHORTCUTS])
 def test_shortcuts_do_not_change_the_colours(gpu, option, value):
-    before = gpu.get_option(option)
-    try:
-        for k in range(N_SCENES):
-            c = _case(k, gpu)
-            relit = relit_of(gpu, c)
-            gpu.set_option(option, value)
+    for k in range(N_SCENES):
+        c = _case(k, gpu)
+        relit = relit_of(gpu, c)
+        with options(gpu, **{option: value}):
             rgb, st = relit.shade_hits(c.rec)
-            gpu.set_option(option, before)
-            assert_bit_equal(rgb, c.want, f"{option} = {value:#x}, {c.name}")
-            assert st["rays_shadow"] == c.cnt["rays_shadow"] and st["hits_shadow"] == c.cnt["hits_shadow"], (option, c.name)
-            relit.close()
-    finally:
-        gpu.set_option(option, before)
+        assert_bit_equal(rgb, c.want, f"{option} = {value:#x}, {c.name}")
+        assert st["rays_shadow"] == c.cnt["rays_shadow"] and st["hits_shadow"] == c.cnt["hits_shadow"], (option, c.name)
+        relit.close()
 
 
 @pytest.mark.parametrize("math", [1, 2], ids=["glibc_fma", "glibc_sse2"])
@@ -168,24 +158,16 @@ def test_shortcuts_in_glibc_arithmetic(gpu, math):
     c = _case(1, gpu)
     ds = gpu.scene(c.scene)
     relit = ds.relight(BG, LIGHTS)
-    before = {o: gpu.get_option(o) for o, _ in SHORTCUTS}
-    try:
-        gpu.set_option("math", math)
+    with contextlib.closing(relit), options(gpu, math=math):
         rec, _ = ds.object_try_trace(c.rays)
         want, want_st = relit.trace_rays(c.rays)
         rgb, st = relit.shade_hits(rec)
         assert_bit_equal(rgb, want, f"math {math}: shade = trace_rays")
         assert st["rays_shadow"] == want_st["rays_shadow"] and st["hits_shadow"] == want_st["hits_shadow"]
         for option, value in SHORTCUTS:
-            gpu.set_option(option, value)
-            got, _ = relit.shade_hits(rec)
-            gpu.set_option(option, before[option])
+            with options(gpu, **{option: value}):
+                got, _ = relit.shade_hits(rec)
             assert_bit_equal(got, want, f"math {math}, {option} = {value:#x}")
-    finally:
-        gpu.set_option("math", 0)
-        for o, v in before.items():
-            gpu.set_option(o, v)
-        relit.close()
 
 
 def test_records_are_data(gpu, case, oracle):
@@ -216,13 +198,11 @@ def test_records_are_data(gpu, case, oracle):
 def test_relight_equals_a_scene_built_from_scratch(gpu, case):
     c = case
     cam, size = syn.default_camera(), ft.ImageSize(c.W, c.H)
-    cert = gpu.get_option("cert")
     src = gpu.scene(c.scene)
     relit = src.relight(BG, LIGHTS)
     src.close()                                               # releasing the source first must not matter
     fresh = gpu.scene(c.relit_scene)
-    try:
-        gpu.set_option("cert", 0)                             # sdf_evals is compared too
+    with contextlib.closing(relit), options(gpu, cert=0):     # sdf_evals is compared too
         img, st = relit.render(EPS, LEN, size, cam)
         want, want_st = fresh.render(EPS, LEN, size, cam)
         assert_bit_equal(img, want, f"{c.name}: relit.render = render of ft_scene_create's scene")
@@ -230,9 +210,6 @@ def test_relight_equals_a_scene_built_from_scratch(gpu, case):
         for key in COUNTERS + ("sdf_evals", "rays_ext"):
             assert st[key] == want_st[key], (c.name, key, st[key], want_st[key])
         assert relit.info() == fresh.info(), c.name
-    finally:
-        gpu.set_option("cert", cert)
-        relit.close()
 
 
 DEVICE_FORMS = r"""

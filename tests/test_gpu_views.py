@@ -6,7 +6,7 @@ import pytest
 
 import fraytracer_amd as ft
 from fraytracer_amd import synthetic as syn
-from helpers import assert_bit_equal
+from helpers import assert_bit_equal, options, options_left_at_defaults  # noqa: F401  (options_left_at_defaults: a fixture)
 from test_gpu_hits import scenes
 
 pytestmark = pytest.mark.gpu
@@ -65,22 +65,16 @@ def test_every_kernel_family_equals_single_renders_and_the_oracle(gpu, oracle):
         fp = ds.info()["fast_path"]
         families.add(fp)
         cams = cameras(ds)
-        gpu.set_option("cert", 0)                              # the certificate's firing depends on how waves are packed: counted below
-        try:
+        with options(gpu, cert=0):                             # the certificate's firing depends on how waves are packed: counted below
             imgs, _, _ = check_views(ds, W, H, cams, name)
-        finally:
-            gpu.set_option("cert", 1)
         imgs_c, st_c = ds.render_views(EPS, LEN, ft.ImageSize(W, H), cams)
         want, total, _ = singles(ds, W, H, cams)
         for k in range(len(cams)):
             assert_bit_equal(imgs_c[k], want[k], f"{name}: view {k} = render (certificate on)")
         for k in EXACT:
             assert st_c[k] == total[k], (name, k)
-        gpu.set_option("cert", 0)
-        try:
+        with options(gpu, cert=0):
             _, total_off, _ = singles(ds, W, H, cams)
-        finally:
-            gpu.set_option("cert", 1)
         assert st_c["sdf_evals"] <= total_off["sdf_evals"], name
         orc, _ = oracle.Oracle().scene(scene).render(EPS, LEN, W, H, cams[0].as_array())
         assert_bit_equal(imgs[0], orc, f"{name}: Program.fs camera = oracle")
@@ -93,13 +87,10 @@ def test_counters_are_the_sums_with_the_certificate_off(gpu):
                         (syn.config5()[0], 64, 57)):
         ds = gpu.scene(scene)
         cams = cameras(ds)
-        gpu.set_option("cert", 0)
-        try:
+        with options(gpu, cert=0) as set_:
             for reuse in (1, 0):
-                gpu.set_option("reuse", reuse)
+                set_(reuse=reuse)
                 check_views(ds, W, H, cams, f"fast_path {ds.info()['fast_path']} reuse {reuse}")
-        finally:
-            gpu.set_option("reuse", 1); gpu.set_option("cert", 1)
 
 
 def test_extension_params_per_view(gpu, oracle):
@@ -118,7 +109,6 @@ def test_extension_params_per_view(gpu, oracle):
 
 OPTIONS = [("reuse", 0), ("cert", 0), ("escape", 0), ("cull", 0), ("carved", 0), ("chunk", 16), ("chunk", 32), ("guided", 1),
            ("tail_k", 64), ("tail_k", 0)]
-DEFAULTS = {"reuse": 1, "cert": 1, "escape": 1, "cull": 1, "carved": 1, "chunk": 64, "guided": 0, "tail_k": -1, "math": 0}
 
 
 def test_options_leave_every_view_unchanged(gpu):
@@ -127,12 +117,9 @@ def test_options_leave_every_view_unchanged(gpu):
         cams = cameras(ds)
         base, _, _ = singles(ds, W, H, cams)
         for opt, v in OPTIONS + ([("math", ft.glibc_build_of_this_host())] if ds.info()["fast_path"] == 1 else []):
-            gpu.set_option(opt, v)
-            try:
+            with options(gpu, **{opt: v}):
                 imgs, _ = ds.render_views(EPS, LEN, ft.ImageSize(W, H), cams)
                 want = base if opt != "math" else singles(ds, W, H, cams)[0]
-            finally:
-                gpu.set_option(opt, DEFAULTS[opt])
             for k in range(len(cams)):
                 assert_bit_equal(imgs[k], want[k], f"fast_path {ds.info()['fast_path']} {opt}={v}: view {k}")
 
@@ -143,11 +130,8 @@ def test_guided_hand_out_with_part_tiles(gpu):
     cams = [look((8.0 * np.cos(a), 1.0, 8.0 * np.sin(a)), (0.0, 0.0, 0.0)) for a in np.linspace(0.0, 6.0, 12)]
     want, _, _ = singles(ds, 200, 193, cams)
     for chunk in (64, 32):
-        gpu.set_option("guided", 1); gpu.set_option("chunk", chunk)
-        try:
+        with options(gpu, guided=1, chunk=chunk):
             imgs, _ = ds.render_views(EPS, LEN, ft.ImageSize(200, 193), cams)
-        finally:
-            gpu.set_option("guided", 0); gpu.set_option("chunk", 64)
         for k in range(len(cams)):
             assert_bit_equal(imgs[k], want[k], f"guided chunk {chunk}: view {k}")
 

@@ -6,7 +6,7 @@ import pytest
 
 import fraytracer_amd as ft
 from fraytracer_amd import synthetic as syn
-from helpers import assert_bit_equal
+from helpers import assert_bit_equal, options, options_left_at_defaults  # noqa: F401  (options_left_at_defaults: a fixture)
 from test_gpu_hits import scenes
 from test_gpu_views import cameras, look
 
@@ -49,12 +49,9 @@ def test_each_view_equals_a_single_call_and_the_oracle(gpu, oracle):
         ds = gpu.scene(scene)
         families.add(ds.info()["fast_path"])
         cams = cameras(ds)
-        gpu.set_option("cert", 0)                              # the certificate's firing depends on how waves are packed: counted below
-        try:
+        with options(gpu, cert=0):                             # the certificate's firing depends on how waves are packed: counted below
             hits, _, _ = check_views_hits(ds, W, H, cams, f"{name} hits only")
             check_views_hits(ds, W, H, cams, f"{name} shaded", shade=True)
-        finally:
-            gpu.set_option("cert", 1)
         got, _, st_c = ds.render_views_hits(EPS, LEN, ft.ImageSize(W, H), cams)
         assert np.array_equal(got.records.view(np.uint32), hits.records.view(np.uint32)), f"{name}: certificate on"
         assert np.array_equal(got.material, hits.material), f"{name}: certificate on"
@@ -77,8 +74,7 @@ def test_shading_and_extension_params(gpu):
              ("config3 spp 4 (lean EXTENSION)", syn.config3(n=64)[0], dict(spp=4)),
              ("config5 glass spectral", syn.config5()[0], dict(spp=4, max_bounces=4, spectral=4))]
     W, H = 64, 57
-    gpu.set_option("cert", 0)
-    try:
+    with options(gpu, cert=0):
         for name, scene, ext in cases:
             ds = gpu.scene(scene)
             cams = cameras(ds)[:3]
@@ -90,8 +86,6 @@ def test_shading_and_extension_params(gpu):
             only, _, _ = ds.render_views_hits(EPS, LEN, ft.ImageSize(W, H), cams)
             assert np.array_equal(hits.records.view(np.uint32), only.records.view(np.uint32)), name
             assert np.array_equal(hits.material, only.material), name
-    finally:
-        gpu.set_option("cert", 1)
 
 
 def test_batches_split_at_64_views(gpu):
@@ -134,9 +128,7 @@ def test_options_and_glibc_math_change_no_bit(gpu):
         base_only, _, _ = ds.render_views_hits(EPS, LEN, ft.ImageSize(W, H), cams)
         assert np.array_equal(base.records.view(np.uint32), base_only.records.view(np.uint32))
         for opt, v in OPTIONS + [("math", ft.glibc_build_of_this_host())]:
-            before = gpu.get_option(opt)
-            gpu.set_option(opt, v)
-            try:
+            with options(gpu, **{opt: v}):
                 got, img, _ = ds.render_views_hits(EPS, LEN, ft.ImageSize(W, H), cams, shade=True)
                 only, _, _ = ds.render_views_hits(EPS, LEN, ft.ImageSize(W, H), cams)
                 if opt == "math":                              # glibc math: its own bits, the same in the batch and in single calls
@@ -146,8 +138,6 @@ def test_options_and_glibc_math_change_no_bit(gpu):
                     want_img = np.stack([i for _, i, _ in want])
                 else:
                     want_rec, want_mat, want_img = base.records, base.material, base_img
-            finally:
-                gpu.set_option(opt, before)
             what = f"fast_path {ds.info()['fast_path']} {opt}={v}"
             assert np.array_equal(got.records.view(np.uint32), want_rec.view(np.uint32)), f"{what}: records"
             assert np.array_equal(only.records.view(np.uint32), want_rec.view(np.uint32)), f"{what}: hits only"

@@ -7,13 +7,7 @@ import pytest
 import fraytracer_amd as ft
 from fraytracer_amd import synthetic as syn
 from fraytracer_amd import SdfForm, SdfObject, SdfMaterial, SdfScene
-
-
-@pytest.fixture(scope="module")
-def host():
-    d = ft.Device(-1)
-    yield d
-    d.close()
+from helpers import host  # noqa: F401  (a fixture)
 
 
 def all_forms(scene):

@@ -14,12 +14,11 @@ import fraytracer_amd as ft
 from fraytracer_amd import distributed
 from fraytracer_amd import synthetic as syn
 import edge_scenes as edge
-from helpers import assert_bit_equal
+from helpers import COUNTERS, assert_bit_equal, options, options_left_at_defaults  # noqa: F401  (options_left_at_defaults: a fixture)
 
 pytestmark = pytest.mark.gpu
 
 EPS, LEN = syn.EPSILON, syn.RAY_LENGTH
-COUNTERS = ("rays_primary", "rays_shadow", "hits_primary", "hits_shadow", "flags")
 SWITCHES = ("cert", "occl", "cull", "reuse")
 LIGHTS = [ft.SdfLight.directional((-0.5, -1.0, 1.0), (0.5, 0.5, 0.5)),
           ft.SdfLight.directional((0.3, -0.2, -1.0), (0.2, 0.3, 0.4)),           # from behind the cloud as the default camera sees it
@@ -54,20 +53,6 @@ def ds(gpu):
     d.close()
 
 
-@pytest.fixture
-def options(gpu):
-    """set options for one test; every one of them is put back afterwards"""
-    old = {}
-
-    def set_(**opts):
-        for k, v in opts.items():
-            old.setdefault(k, gpu.get_option(k))
-            gpu.set_option(k, v)
-    yield set_
-    for k, v in old.items():
-        gpu.set_option(k, v)
-
-
 def check(got, gst, wanted, what):
     assert_bit_equal(got, wanted[0], what)
     for k in COUNTERS:
@@ -87,17 +72,18 @@ def test_every_exit_of_settle(ds, oracle):
     check(got, st, wanted, "72 x 56")
 
 
-def test_option_combinations(ds, oracle, options):
+def test_option_combinations(gpu, ds, oracle):
     """cert, occl, cull, reuse in all 16 combinations at 96 x 96: the frame and the ray / hit counters never move; what is evaluated does not depend on
     the culling pass"""
     size = 96
     wanted = want(oracle, size, size)
     evals = {}
-    for combo in itertools.product((0, 1), repeat=4):
-        options(**dict(zip(SWITCHES, combo)))
-        got, st = ds.render(EPS, LEN, ft.ImageSize(size, size), syn.default_camera())
-        check(got, st, wanted, str(dict(zip(SWITCHES, combo))))
-        evals[combo] = st["sdf_evals"]
+    with options(gpu) as set_:
+        for combo in itertools.product((0, 1), repeat=4):
+            set_(**dict(zip(SWITCHES, combo)))
+            got, st = ds.render(EPS, LEN, ft.ImageSize(size, size), syn.default_camera())
+            check(got, st, wanted, str(dict(zip(SWITCHES, combo))))
+            evals[combo] = st["sdf_evals"]
     for (cert, occl, cull, reuse), n in evals.items():
         assert n == evals[(cert, occl, 1 - cull, reuse)], (cert, occl, reuse, evals)
     assert evals[(1, 1, 1, 1)] < evals[(0, 0, 1, 1)] < evals[(0, 0, 1, 0)], evals      # each shortcut is on when its switch says so
@@ -149,7 +135,7 @@ def test_sibling_forms(ds, oracle):
     assert lit == st["rays_shadow"] - st["hits_shadow"] and int(vis.max()) < 1 << len(LIGHTS)
 
 
-def test_edges_of_the_first_step(ds, oracle, options):
+def test_edges_of_the_first_step(gpu, ds, oracle):
     """a camera inside the blob (a hit at the camera itself) and rays of Length <= 0 — in latency mode and out of it"""
     w, h = 48, 40
     cam = edge.camera_at(edge.interior_points(oracle, relit(), 1, 0.15)[0])
@@ -165,14 +151,15 @@ def test_edges_of_the_first_step(ds, oracle, options):
     with np.errstate(all="ignore"):
         want_rgb, cnt = os_.trace_rays(rays)
     assert cnt["flags"] == 0 and 0 < cnt["hits_primary"] < n
-    for tail_k in (0, -1):                                            # never, and the default
-        options(tail_k=tail_k)
-        got, st = ds.render(EPS, LEN, ft.ImageSize(w, h), cam)
-        check(got, st, inside, f"camera inside, tail_k {tail_k}")
-        got, st = ds.trace_rays(rays)
-        assert_bit_equal(got, want_rgb, f"ray buffer, tail_k {tail_k}")
-        for k in COUNTERS[1:]:
-            assert st[k] == cnt[k], (tail_k, k, st[k], cnt[k])
+    with options(gpu) as set_:
+        for tail_k in (0, -1):                                            # never, and the default
+            set_(tail_k=tail_k)
+            got, st = ds.render(EPS, LEN, ft.ImageSize(w, h), cam)
+            check(got, st, inside, f"camera inside, tail_k {tail_k}")
+            got, st = ds.trace_rays(rays)
+            assert_bit_equal(got, want_rgb, f"ray buffer, tail_k {tail_k}")
+            for k in COUNTERS[1:]:
+                assert st[k] == cnt[k], (tail_k, k, st[k], cnt[k])
 
 
 def test_a_ray_that_ends_on_the_step_cap(ds, oracle):

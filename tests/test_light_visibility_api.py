@@ -12,7 +12,7 @@ import pytest
 import fraytracer_amd as ft
 from fraytracer_amd import _lib, api
 from fraytracer_amd import synthetic as syn
-from helpers import HEADER, ROOT, assert_cpp_compiles, assert_declared_exported_bound, dev_ptr as _p, host_ptr as ptr
+from helpers import HEADER, ROOT, assert_cpp_compiles, assert_declared_exported_bound, dev_ptr as _p, host_ptr as ptr, host  # noqa: F401  (host: a fixture)
 
 NAMES = ("ft_light_visibility", "ft_light_visibility_device", "ft_shade_visible", "ft_shade_visible_device")
 BG = (0.02, 0.03, 0.05)
@@ -21,13 +21,6 @@ LIGHTS = (ft.SdfLight.directional((0.6, -1.0, -0.3), (0.9, 0.8, 0.7)), ft.SdfLig
 OK, INVALID, NO_DEVICE, UNSUPPORTED = _lib.FT_OK, _lib.FT_ERR_INVALID, _lib.FT_ERR_NO_DEVICE, _lib.FT_ERR_UNSUPPORTED
 ALL = 0xFFFFFFFF
 REC, VIN, VOUT, RGB = 4096, 8192, 12288, 16384                # device addresses that are never touched: no device exists
-
-
-@pytest.fixture
-def host():
-    dev = ft.Device(-1)
-    yield dev
-    dev.close()
 
 
 def lit(host, n_lights=3):

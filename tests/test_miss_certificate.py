@@ -11,7 +11,7 @@ import pytest
 
 import fraytracer_amd as ft
 from fraytracer_amd import synthetic as syn
-from helpers import assert_bit_equal
+from helpers import COUNTERS, assert_bit_equal, glibc_math, host, options, options_left_at_defaults, seg_dist  # noqa: F401  (host, options_left_at_defaults: fixtures)
 
 EPS, LEN = 0.01, 30.0
 # FT_OPT_CERT_POLICY: primary rays from step 0, shadow rays from step 1, whenever one lane is due, again after every further step
@@ -27,19 +27,6 @@ def margin(escR, cinf, strength, n):
     eGeo = 8.0 * u * 5.0 * escR + 16.0 * u * (cinf + 10.0 * escR)
     eSum = strength * ((2.0 * n + 4096.0) * 2.0 ** -23 + 2e-4)
     return (2.0 * delta + 2.0 * eGeo + eSum) * 1.01 + 1e-6, delta
-
-
-def seg_dist(C, a, b):
-    ab = b - a
-    t = np.clip(((C - a) @ ab) / (ab @ ab), 0.0, 1.0)
-    return np.linalg.norm(C - (a + t[:, None] * ab), axis=1)
-
-
-@pytest.fixture(scope="module")
-def host():
-    d = ft.Device(-1)
-    yield d
-    d.close()
 
 
 @pytest.mark.parametrize("strength", [0.05, 0.25, 1.0])
@@ -106,17 +93,15 @@ def _render(gpu, oracle, scene, size, opts, eps=EPS, length=LEN, cam=None, **ext
     want, ocnt = oracle.Oracle().scene(scene).render(eps, length, size.X, size.Y, cam.as_array(), nthreads=16, **ext)
     out = {}
     try:
-        for name, o in opts.items():
-            for k, v in o.items():
-                gpu.set_option(k, v)
-            got, st = ds.render(eps, length, size, cam, **ext)
-            assert_bit_equal(got, want, name)
-            for k in ("rays_primary", "rays_shadow", "hits_primary", "hits_shadow", "flags"):
-                assert st[k] == ocnt[k], (name, k, st[k], ocnt[k])
-            out[name] = st
+        with options(gpu) as set_:
+            for name, o in opts.items():
+                set_(**o)
+                got, st = ds.render(eps, length, size, cam, **ext)
+                assert_bit_equal(got, want, name)
+                for k in COUNTERS:
+                    assert st[k] == ocnt[k], (name, k, st[k], ocnt[k])
+                out[name] = st
     finally:
-        for k, v in (("cert", 1), ("cert_policy", 0), ("escape", 1), ("tail_k", -1)):
-            gpu.set_option(k, v)
         ds.close()
     return out
 
@@ -153,13 +138,8 @@ def test_epsilon_range(gpu, oracle, eps):
 @pytest.mark.gpu
 def test_glibc_arithmetic(gpu, oracle):
     scene, _ = syn.config3(n=128, size=64)
-    gpu.set_option("math", ft.glibc_build_of_this_host())
-    oracle.lib.orc_set_libm(1)
-    try:
+    with glibc_math(gpu, oracle):
         _render(gpu, oracle, scene, ft.ImageSize(64, 64), OPTS)
-    finally:
-        gpu.set_option("math", 0)
-        oracle.lib.orc_set_libm(0)
 
 
 @pytest.mark.gpu
@@ -199,18 +179,16 @@ def test_grazing_rays_and_cameras_inside(gpu, oracle, seed):
         want, ocnt = os_.trace_rays(rays)
     evals = {}
     try:
-        for name, o in OPTS.items():
-            for k, val in o.items():
-                gpu.set_option(k, val)
-            with np.errstate(all="ignore"):
-                got, st = ds.trace_rays(rays)
-            assert_bit_equal(got, want, name)
-            for k in ("rays_shadow", "hits_primary", "hits_shadow", "flags"):
-                assert st[k] == ocnt[k], (name, k, st[k], ocnt[k])
-            evals[name] = st["sdf_evals"]
+        with options(gpu) as set_:
+            for name, o in OPTS.items():
+                set_(**o)
+                with np.errstate(all="ignore"):
+                    got, st = ds.trace_rays(rays)
+                assert_bit_equal(got, want, name)
+                for k in COUNTERS[1:]:
+                    assert st[k] == ocnt[k], (name, k, st[k], ocnt[k])
+                evals[name] = st["sdf_evals"]
     finally:
-        for k, val in (("cert", 1), ("cert_policy", 0), ("escape", 1)):
-            gpu.set_option(k, val)
         ds.close()
     assert evals["every_step"] < evals["off"], evals
 

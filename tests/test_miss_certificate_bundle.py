@@ -10,7 +10,7 @@ import pytest
 
 import fraytracer_amd as ft
 from fraytracer_amd import synthetic as syn
-from helpers import assert_bit_equal
+from helpers import assert_bit_equal, glibc_math, host, options, options_left_at_defaults, seg_dist  # noqa: F401  (host, options_left_at_defaults: fixtures)
 
 EPS, LEN = 0.01, 30.0
 
@@ -28,7 +28,6 @@ BUNDLE_OFF = s32(SHIPPED_LANES | (3 << 30))
 COLS = {"bundle_only": {"cert": 1, "cert_policy": BUNDLE_ONLY}, "bundle_and_lanes": {"cert": 1, "cert_policy": BUNDLE_AND_LANES},
         "bundle_off": {"cert": 1, "cert_policy": BUNDLE_OFF}, "cert_off": {"cert": 0, "cert_policy": BUNDLE_ONLY},
         "escape_off": {"cert": 1, "cert_policy": BUNDLE_AND_LANES, "escape": 0}}
-RESET = (("cert", 1), ("cert_policy", 0), ("escape", 1), ("tail_k", -1), ("math", 0))
 
 
 # ---------------------------------------------------------------- CPU: the bound ----------------------------------------------------------------
@@ -49,12 +48,6 @@ def scene_of(C, R, strength, lights=None):
     forms = [syn.SdfForm.Primitive.sphere(Center=tuple(float(v) for v in c), Radius=float(r)) for c, r in zip(C, R)]
     obj = syn.SdfObject.create(syn.SdfMaterial.createSolid((0.9, 0.6, 0.3)), syn.SdfForm.unionSmooth(strength, forms))
     return syn.SdfScene(obj, syn.BACKGROUND, lights or [syn.SdfLight.directional((-0.5, -1.0, 1.0), (0.5, 0.5, 0.5))])
-
-
-def seg_dist(P, a, b):
-    ab = b - a
-    t = np.clip(((P - a) @ ab) / (ab @ ab), 0.0, 1.0)
-    return np.linalg.norm(P - (a + t[:, None] * ab), axis=1)
 
 
 def lane_segment(K, o, d, eps, length):
@@ -162,13 +155,6 @@ SCENES = [(31, s, False) for s in (0.05, 0.25, 1.0)] + [(257, s, False) for s in
 FAMILIES = ["cone96", "cone4096", "parallel", "straddle", "one", "identical", "empty"]
 
 
-@pytest.fixture(scope="module")
-def host():
-    d = ft.Device(-1)
-    yield d
-    d.close()
-
-
 @pytest.mark.parametrize("axis", ["lane", "mean"])
 def test_bundle_sum_bounds_every_members_flat_sum(host, axis):
     """2 000 and more random bundles per axis choice: the bundle's sum is >= the flat certificate sum of every member, lanes outside the gate or without
@@ -214,7 +200,7 @@ def test_bundle_sum_bounds_every_members_flat_sum(host, axis):
 
 def test_policy_word(host):
     """bits 30-31 select the bundle's schedule; every word refused before is refused, the new bits come back as set, word 0 reads back as 0"""
-    try:
+    with options(host) as set_:
         assert host.get_option("cert_policy") == 0
         for bad in (1, 65 << 16, s32(1 | (1 << 30)), s32((65 << 16) | (2 << 30)), s32(3 << 30), s32((255 << 16) | (3 << 30)), 0x00FF0000):
             with pytest.raises(ft.FrayTracerError) as e:
@@ -222,12 +208,10 @@ def test_policy_word(host):
             assert e.value.code == -1, bad
             assert host.get_option("cert_policy") == 0
         for word in (BUNDLE_ONLY, BUNDLE_AND_LANES, BUNDLE_OFF, s32(SHIPPED_LANES | (2 << 30)), EVERY_STEP, SHIPPED_LANES, 0x01010100, 1 | (6 << 8) | (16 << 16)):
-            host.set_option("cert_policy", word)
+            set_(cert_policy=word)
             assert host.get_option("cert_policy") == word
-        host.set_option("cert_policy", 0)
+        set_(cert_policy=0)
         assert host.get_option("cert_policy") == 0
-    finally:
-        host.set_option("cert_policy", 0)
 
 
 # ---------------------------------------------------------------- GPU ----------------------------------------------------------------
@@ -235,19 +219,15 @@ def test_policy_word(host):
 def run_columns(gpu, call, want, ocnt, counters, cols=COLS, extra=None):
     """call() under every policy column -> {column: stats}; every float and every counter equal to the oracle's"""
     out = {}
-    try:
+    with options(gpu) as set_:
         for name, o in cols.items():
-            for k, v in dict(o, **(extra or {})).items():
-                gpu.set_option(k, v)
+            set_(**dict(o, **(extra or {})))
             with np.errstate(all="ignore"):
                 got, st = call()
             assert_bit_equal(got, want, name)
             for k in counters:
                 assert st[k] == ocnt[k], (name, k, st[k], ocnt[k])
             out[name] = st
-    finally:
-        for k, v in RESET:
-            gpu.set_option(k, v)
     return out
 
 
@@ -288,13 +268,8 @@ def test_c3_frames(gpu, oracle, strength):
 
 @pytest.mark.gpu
 def test_c3_frame_glibc_arithmetic(gpu, oracle):
-    gpu.set_option("math", ft.glibc_build_of_this_host())
-    oracle.lib.orc_set_libm(1)
-    try:
-        st = render_columns(gpu, oracle, syn.config3(n=256, size=96)[0], 96, 96, extra={"math": ft.glibc_build_of_this_host()})
-    finally:
-        gpu.set_option("math", 0)
-        oracle.lib.orc_set_libm(0)
+    with glibc_math(gpu, oracle) as variant:
+        st = render_columns(gpu, oracle, syn.config3(n=256, size=96)[0], 96, 96, extra={"math": variant})
     assert st["bundle_only"]["sdf_evals"] < st["cert_off"]["sdf_evals"]
 
 
@@ -349,9 +324,7 @@ def test_views(gpu, oracle):
     try:
         for refill in (64, 1):                                       # refill_min 1: lanes of a wave take rays of the next view as they fall idle
             st = run_columns(gpu, lambda: ds.render_views(EPS, LEN, ft.ImageSize(32, 32), cams), want, ocnt, FRAME_COUNTERS, extra={"refill_min": refill})
-            gpu.set_option("refill_min", 64)
     finally:
-        gpu.set_option("refill_min", 64)
         ds.close()
     assert st["bundle_only"]["sdf_evals"] < st["cert_off"]["sdf_evals"]
 

@@ -4,6 +4,7 @@ A run of >= 32 spheres is grouped into at most 32 clusters; the certificate sums
 cluster by its members' exact terms only where a lane needs it.  The CPU tests check the grouping (every child in exactly one cluster, inside its
 ball, in double on the float32 values) and that the cluster bound is never below the flat float64 bound.  The GPU tests compare colours and
 counters with the oracle on the same layouts under the default policy, an every-step policy and with the certificate off."""
+import contextlib
 import math
 
 import numpy as np
@@ -11,7 +12,7 @@ import pytest
 
 import fraytracer_amd as ft
 from fraytracer_amd import synthetic as syn
-from helpers import assert_bit_equal
+from helpers import COUNTERS, assert_bit_equal, host, options, options_left_at_defaults, seg_dist  # noqa: F401  (host, options_left_at_defaults: fixtures)
 
 EPS, LEN = 0.01, 30.0
 EVERY_STEP = 0 | (1 << 8) | (1 << 16) | (1 << 24)
@@ -53,19 +54,6 @@ def scene_of(C, R, strength):
     forms = [syn.SdfForm.Primitive.sphere(Center=tuple(float(v) for v in c), Radius=float(r)) for c, r in zip(C, R)]
     obj = syn.SdfObject.create(syn.SdfMaterial.createSolid((0.9, 0.6, 0.3)), syn.SdfForm.unionSmooth(strength, forms))
     return syn.SdfScene(obj, syn.BACKGROUND, [syn.SdfLight.directional((-0.5, -1.0, 1.0), (0.5, 0.5, 0.5))])
-
-
-def seg_dist(P, a, b):
-    ab = b - a
-    t = np.clip(((P - a) @ ab) / (ab @ ab), 0.0, 1.0)
-    return np.linalg.norm(P - (a + t[:, None] * ab), axis=1)
-
-
-@pytest.fixture(scope="module")
-def host():
-    d = ft.Device(-1)
-    yield d
-    d.close()
 
 
 @pytest.mark.parametrize("strength", [0.05, 0.25, 1.0])
@@ -129,19 +117,14 @@ def _render(gpu, oracle, scene, size, opts):
     ds = gpu.scene(scene)
     want, ocnt = oracle.Oracle().scene(scene).render(EPS, LEN, size.X, size.Y, cam.as_array(), nthreads=16)
     out = {}
-    try:
+    with contextlib.closing(ds), options(gpu) as set_:
         for name, o in opts.items():
-            for k, v in o.items():
-                gpu.set_option(k, v)
+            set_(**o)
             got, st = ds.render(EPS, LEN, size, cam)
             assert_bit_equal(got, want, name)
-            for k in ("rays_primary", "rays_shadow", "hits_primary", "hits_shadow", "flags"):
+            for k in COUNTERS:
                 assert st[k] == ocnt[k], (name, k, st[k], ocnt[k])
             out[name] = st
-    finally:
-        for k, v in (("cert", 1), ("cert_policy", 0)):
-            gpu.set_option(k, v)
-        ds.close()
     return out
 
 

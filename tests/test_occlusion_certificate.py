@@ -4,6 +4,7 @@ A shadow ray of a scene that is one smooth union of spheres ends as a hit once i
 a point with f <= -hitM, hitM = occE (t / epsilon + 2) + occB, at a parameter t <= Length * occLenInv.  The CPU tests pin the constants to their
 formula and hold a float64 restatement of that condition against the oracle's own float32 marches; the GPU tests compare colours, ray / hit counters and flags with the oracle, which has no
 certificate at all, with the option off, on, and tried on every round."""
+import contextlib
 import math
 
 import numpy as np
@@ -11,7 +12,7 @@ import pytest
 
 import fraytracer_amd as ft
 from fraytracer_amd import synthetic as syn
-from helpers import assert_bit_equal
+from helpers import COUNTERS, assert_bit_equal, host, options, options_left_at_defaults, oracle_libm  # noqa: F401  (host, options_left_at_defaults: fixtures)
 
 EPS, LEN = 0.01, 30.0
 EVERY_ROUND = 1                      # FT_OPT_OCCL_POLICY: period 1
@@ -85,13 +86,6 @@ class Model:
             ok = (t <= k["reach"]) & (nst < N_CAP) & (hitM <= k["cap"]) & (hitM * 1.001 < -f)
         self.t_of = np.where(ok, t, np.inf).min(1)                      # the smallest witness parameter (inf: none)
         return gate & ok.any(1)
-
-
-@pytest.fixture(scope="module")
-def host():
-    d = ft.Device(-1)
-    yield d
-    d.close()
 
 
 START = {0.05: 4.7, 0.25: 6.0, 1.0: 10.0}      # outside the surface; at strength 0.05 every term of the union underflows farther out and nothing is ever hit
@@ -264,40 +258,29 @@ def test_option_and_its_mirrors(host):
     fs = open(os.path.join(root, "host", "fsharp", "FrayTracer.Hip.fs")).read()
     assert re.search(r"for opt in \[ 9; 10; 11; 17 \] do", fs)
     assert host.get_option("occl") == 1 and host.get_option("occl_policy") == 0
-    for v in (1, 2 | 3 << 8 | 16 << 16, 255, 0):
-        host.set_option("occl_policy", v)
-        assert host.get_option("occl_policy") == v
+    with options(host) as set_:
+        for v in (1, 2 | 3 << 8 | 16 << 16, 255, 0):
+            set_(occl_policy=v)
+            assert host.get_option("occl_policy") == v
     for name, v in (("occl", 2), ("occl_policy", -1), ("occl_policy", 65 << 16)):
         with pytest.raises(ft.FrayTracerError):
             host.set_option(name, v)
 
 
 # ------------------------------------------------------------------------------------------------ GPU
-def _set(gpu, o):
-    for k, v in o.items():
-        gpu.set_option(k, v)
-
-
-RESET = {"occl": 1, "occl_policy": 0, "tail_k": -1, "math": 0, "cert": 1, "cert_policy": 0}
-COUNTERS = ("rays_primary", "rays_shadow", "hits_primary", "hits_shadow", "flags")
-
-
 def _render(gpu, oracle, scene, size, opts=OPTS, eps=EPS, length=LEN, extra=None, **ext):
     cam = syn.default_camera()
     ds = gpu.scene(scene)
     want, ocnt = oracle.Oracle().scene(scene).render(eps, length, size, size, cam.as_array(), nthreads=16, **ext)
     out = {}
-    try:
+    with contextlib.closing(ds), options(gpu) as set_:
         for name, o in opts.items():
-            _set(gpu, dict(o, **(extra or {})))
+            set_(**dict(o, **(extra or {})))
             got, st = ds.render(eps, length, ft.ImageSize(size, size), cam, **ext)
             assert_bit_equal(got, want, name)
             for k in COUNTERS:
                 assert st[k] == ocnt[k], (name, k, st[k], ocnt[k])
             out[name] = st
-    finally:
-        _set(gpu, RESET)
-        ds.close()
     return out
 
 
@@ -327,16 +310,13 @@ def test_rays_across_a_gap_where_the_sum_underflows(gpu, oracle):
         scene, _, _ = two_clusters(light=light)
         want, ocnt = oracle.Oracle().scene(scene).trace_rays(rays)
         ds = gpu.scene(scene)
-        try:
+        with contextlib.closing(ds), options(gpu) as set_:
             for name, o in OPTS.items():
-                _set(gpu, o)
+                set_(**o)
                 got, st = ds.trace_rays(rays)
                 assert_bit_equal(got, want, f"{name} light {light}")
                 for k in COUNTERS[1:]:
                     assert st[k] == ocnt[k], (name, light, k, st[k], ocnt[k])
-        finally:
-            _set(gpu, RESET)
-            ds.close()
         assert ocnt["hits_primary"] == n
         cast += ocnt["rays_shadow"]; missed = locals().get("missed", 0) + ocnt["rays_shadow"] - ocnt["hits_shadow"]
     assert cast == n and 0 < missed                                    # one light casts every ray's shadow ray across the gap; those that evaluate +inf miss
@@ -345,11 +325,8 @@ def test_rays_across_a_gap_where_the_sum_underflows(gpu, oracle):
 @pytest.mark.gpu
 def test_glibc_arithmetic(gpu, oracle):
     scene, _ = syn.config3(n=256, size=96)
-    oracle.lib.orc_set_libm(1)
-    try:
+    with oracle_libm(oracle):
         st = _render(gpu, oracle, scene, 96, extra={"math": ft.glibc_build_of_this_host()})
-    finally:
-        oracle.lib.orc_set_libm(0)
     assert st["on"]["sdf_evals"] < st["off"]["sdf_evals"]
 
 
@@ -423,18 +400,15 @@ def test_views_launch(gpu, oracle):
     want = [oracle.Oracle().scene(scene).render(EPS, LEN, 64, 64, c.as_array(), nthreads=16) for c in cams]
     ds = gpu.scene(scene)
     evals = {}
-    try:
+    with contextlib.closing(ds), options(gpu) as set_:
         for name, o in OPTS.items():
-            _set(gpu, o)
+            set_(**o)
             got, st = ds.render_views(EPS, LEN, ft.ImageSize(64, 64), cams)
             for v in range(2):
                 assert_bit_equal(got[v], want[v][0], f"{name} view {v}")
             for k in COUNTERS:
                 assert st[k] == want[0][1][k] + want[1][1][k], (name, k)
             evals[name] = st["sdf_evals"]
-    finally:
-        _set(gpu, RESET)
-        ds.close()
     assert evals["on"] < evals["off"] and evals["every_round"] < evals["off"]
 
 
@@ -454,9 +428,9 @@ def test_ray_buffer_shade_and_visibility_forms(gpu, oracle):
     rec, _ = os_.object_try_trace(rays)
     ds = gpu.scene(scene)
     evals, masks = {}, {}
-    try:
+    with contextlib.closing(ds), options(gpu) as set_:
         for name, o in OPTS.items():
-            _set(gpu, o)
+            set_(**o)
             got, st = ds.trace_rays(rays)
             assert_bit_equal(got, want, name + " trace_rays")
             for k in COUNTERS[1:]:
@@ -469,9 +443,6 @@ def test_ray_buffer_shade_and_visibility_forms(gpu, oracle):
             assert int(vis.sum()) == ocnt["rays_shadow"] - ocnt["hits_shadow"] and int(vis.max()) == 1
             masks[name] = vis
             evals[name] = (st["sdf_evals"], sh["sdf_evals"], vs["sdf_evals"])
-    finally:
-        _set(gpu, RESET)
-        ds.close()
     assert np.array_equal(masks["on"], masks["off"]) and np.array_equal(masks["every_round"], masks["off"])
     for i in range(3):
         assert evals["on"][i] < evals["off"][i] and evals["every_round"][i] < evals["off"][i], evals

@@ -7,6 +7,7 @@ It bounds the effect of the substitution; it does not pin parity with the F# pro
 import numpy as np
 
 from fraytracer_amd import synthetic as syn
+from helpers import oracle_libm
 
 EPS, LEN = syn.EPSILON, syn.RAY_LENGTH
 
@@ -16,13 +17,9 @@ def test_c3_with_the_c_librarys_exp_and_log(oracle):
     cam = syn.default_camera()
     os_ = oracle.Oracle().scene(scene)
     n = 192
-    try:
-        oracle.lib.orc_set_libm(0)
-        a, ca = os_.render(EPS, LEN, n, n, cam.as_array())
-        oracle.lib.orc_set_libm(1)
+    a, ca = os_.render(EPS, LEN, n, n, cam.as_array())
+    with oracle_libm(oracle):
         b, cb = os_.render(EPS, LEN, n, n, cam.as_array())
-    finally:
-        oracle.lib.orc_set_libm(0)
     assert ca["hits_primary"] == cb["hits_primary"] and ca["hits_shadow"] == cb["hits_shadow"]      # no hit / miss flips
     same = (a.view(np.uint32) == b.view(np.uint32)).all(axis=2)
     rel = (np.abs(a.astype(np.float64) - b) / np.maximum(np.abs(a.astype(np.float64)), 1e-3)).max(axis=2)

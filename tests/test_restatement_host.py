@@ -14,16 +14,9 @@ import pytest
 import fraytracer_amd as ft
 import form_scenes as S
 import restatement as R
-from helpers import assert_bit_equal
+from helpers import assert_bit_equal, host  # noqa: F401  (host: a fixture)
 
 F = np.float32
-
-
-@pytest.fixture(scope="module")
-def host():
-    d = ft.Device(-1)
-    yield d
-    d.close()
 
 
 def oracle_scene(oracle, b):

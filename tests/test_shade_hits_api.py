@@ -12,20 +12,13 @@ import pytest
 import fraytracer_amd as ft
 from fraytracer_amd import _lib, api
 from fraytracer_amd import synthetic as syn
-from helpers import HEADER, ROOT, assert_cpp_compiles, assert_declared_exported_bound, dev_ptr as _p, host_ptr as ptr
+from helpers import HEADER, ROOT, assert_cpp_compiles, assert_declared_exported_bound, dev_ptr as _p, host_ptr as ptr, host  # noqa: F401  (host: a fixture)
 
 NAMES = ("ft_scene_relight", "ft_shade_hits", "ft_shade_hits_device")
 BG = (0.02, 0.03, 0.05)
 LIGHTS = (ft.SdfLight.directional((0.6, -1.0, -0.3), (0.9, 0.8, 0.7)), ft.SdfLight.point((3.0, 4.0, -6.0), (30.0, 40.0, 50.0)),
           ft.SdfLight.directional((0.0, 1.0, 0.2), (0.3, 0.3, 0.3)))
 INVALID, NO_DEVICE, UNSUPPORTED = _lib.FT_ERR_INVALID, _lib.FT_ERR_NO_DEVICE, _lib.FT_ERR_UNSUPPORTED
-
-
-@pytest.fixture
-def host():
-    dev = ft.Device(-1)
-    yield dev
-    dev.close()
 
 
 def test_symbols_are_declared_exported_and_bound():

@@ -18,7 +18,7 @@ import pytest
 import fraytracer_amd as ft
 from fraytracer_amd import _lib
 from fraytracer_amd import synthetic as syn
-from helpers import assert_bit_equal
+from helpers import assert_bit_equal, glibc_math, options, options_left_at_defaults  # noqa: F401  (options_left_at_defaults: a fixture)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EPS, LEN = 0.01, 30.0
@@ -156,15 +156,6 @@ def frames():
     f.close()
 
 
-@pytest.fixture(autouse=True)
-def defaults_again(request):
-    yield
-    if "gpu" in request.fixturenames:
-        g = request.getfixturevalue("gpu")
-        for k, v in (("order", 1), ("guided", 0), ("math", 0)):
-            g.set_option(k, v)
-
-
 def read_slot(ds, which):
     """ft_scene_tile_costs / ft_scene_tile_order (internal): the scene's lane-0 slot -> uint32 array, None where the slot holds none"""
     fn = getattr(_lib.lib, "ft_scene_tile_" + which)
@@ -201,12 +192,13 @@ def launches(gpu, frames, ds, size, cam, want, what, reorders=True, **tiling):
     """three launches with option 1 (index order, then twice reordered — the launch itself says whether it was), one with option 0: all four frames
     equal `want` bit for bit and their counters are equal per launch -> the four stats"""
     sts = []
-    for i, order in enumerate((1, 1, 1, 0)):
-        gpu.set_option("order", order)
-        got, st = frames.render(gpu, ds, size, cam, **tiling)
-        assert_bit_equal(got, want, f"{what}, launch {len(sts)} (order {order})")
-        assert used_order(ds) == (reorders and i in (1, 2)), (what, i)
-        sts.append(st)
+    with options(gpu) as set_:
+        for i, order in enumerate((1, 1, 1, 0)):
+            set_(order=order)
+            got, st = frames.render(gpu, ds, size, cam, **tiling)
+            assert_bit_equal(got, want, f"{what}, launch {len(sts)} (order {order})")
+            assert used_order(ds) == (reorders and i in (1, 2)), (what, i)
+            sts.append(st)
     for i, st in enumerate(sts):
         print(what, i, {k: st[k] for k in COUNTERS})
     for k in COUNTERS:
@@ -243,19 +235,13 @@ def test_striped_share(gpu, frames, c3_oracle):
 
 @pytest.mark.gpu
 def test_glibc_arithmetic(gpu, frames, oracle):
-    build = ft.glibc_build_of_this_host()
-    gpu.set_option("math", build)
-    oracle.lib.orc_set_libm(1)
-    try:
+    with glibc_math(gpu, oracle):
         want, _ = oracle.Oracle().scene(c3()).render(EPS, LEN, W, H, syn.default_camera().as_array(), nthreads=16)
         ds = gpu.scene(c3())
         try:
             launches(gpu, frames, ds, ft.ImageSize(W, H), syn.default_camera(), want, "C3 glibc")
         finally:
             ds.close()
-    finally:
-        oracle.lib.orc_set_libm(0)
-        gpu.set_option("math", 0)
 
 
 @pytest.mark.gpu
@@ -318,18 +304,18 @@ def test_a_slot_is_never_used_for_another_grid(gpu, frames):
            (ft.ImageSize(160, 160), cam, {}), (ft.ImageSize(160, 160), moved, {})]
     ds = gpu.scene(syn.config3(n=256, size=160)[0])
     try:
-        gpu.set_option("order", 0)
-        plain = [frames.render(gpu, ds, size, c, **t) for size, c, t in seq]
-        assert read_slot(ds, "costs") is None
-        gpu.set_option("order", 1)
-        for i, (size, c, t) in enumerate(seq):
-            got, st = frames.render(gpu, ds, size, c, **t)
-            assert_bit_equal(got, plain[i][0], f"launch {i}")
-            for k in COUNTERS:
-                assert st[k] == plain[i][1][k], (i, k, st[k], plain[i][1][k])
-            tiles = ((t.get("n_columns", size.X) + 7) // 8) * ((size.Y + 7) // 8)
-            assert len(read_slot(ds, "order")) == tiles                             # the slot follows the launch's grid
-            assert used_order(ds) == (i == 4), i                                    # only the moved camera finds its key in the slot
+        with options(gpu, order=0) as set_:
+            plain = [frames.render(gpu, ds, size, c, **t) for size, c, t in seq]
+            assert read_slot(ds, "costs") is None
+            set_(order=1)
+            for i, (size, c, t) in enumerate(seq):
+                got, st = frames.render(gpu, ds, size, c, **t)
+                assert_bit_equal(got, plain[i][0], f"launch {i}")
+                for k in COUNTERS:
+                    assert st[k] == plain[i][1][k], (i, k, st[k], plain[i][1][k])
+                tiles = ((t.get("n_columns", size.X) + 7) // 8) * ((size.Y + 7) // 8)
+                assert len(read_slot(ds, "order")) == tiles                             # the slot follows the launch's grid
+                assert used_order(ds) == (i == 4), i                                    # only the moved camera finds its key in the slot
     finally:
         ds.close()
 
@@ -340,16 +326,16 @@ def test_two_scenes_on_one_context(gpu, frames):
     size, cam = ft.ImageSize(96, 104), syn.default_camera()
     dss = [gpu.scene(s) for s in scenes]
     try:
-        gpu.set_option("order", 0)
-        plain = [frames.render(gpu, ds, size, cam) for ds in dss]
-        gpu.set_option("order", 1)
-        for rep in range(3):
-            for i, ds in enumerate(dss):
-                got, st = frames.render(gpu, ds, size, cam)
-                assert_bit_equal(got, plain[i][0], f"scene {i}, launch {rep}")
-                assert used_order(ds) == (rep > 0), (i, rep)
-                for k in COUNTERS:
-                    assert st[k] == plain[i][1][k], (i, rep, k)
+        with options(gpu, order=0) as set_:
+            plain = [frames.render(gpu, ds, size, cam) for ds in dss]
+            set_(order=1)
+            for rep in range(3):
+                for i, ds in enumerate(dss):
+                    got, st = frames.render(gpu, ds, size, cam)
+                    assert_bit_equal(got, plain[i][0], f"scene {i}, launch {rep}")
+                    assert used_order(ds) == (rep > 0), (i, rep)
+                    for k in COUNTERS:
+                        assert st[k] == plain[i][1][k], (i, rep, k)
     finally:
         for ds in dss:
             ds.close()
@@ -362,27 +348,26 @@ def test_options_0_and_2_and_the_guided_hand_out_keep_index_order(gpu, frames, c
     nTiles = ((W + 7) // 8) * ((H + 7) // 8)
     ds = gpu.scene(c3())
     try:
-        gpu.set_option("order", 0)
-        for _ in range(2):
-            plain, st0 = frames.render(gpu, ds, size, cam)
-            assert_bit_equal(plain, want, "option 0")
-            assert read_slot(ds, "costs") is None and read_slot(ds, "order") is None
-        gpu.set_option("order", 2)
-        for _ in range(2):
-            got, _ = frames.render(gpu, ds, size, cam)
-            assert_bit_equal(got, want, "option 2")
-            assert len(read_slot(ds, "costs")) == nTiles and read_slot(ds, "order") is None and not used_order(ds)
-        gpu.set_option("order", 0)
-        frames.render(gpu, ds, size, cam)
-        assert read_slot(ds, "costs") is None                                       # option 0 forgets what was recorded
-        gpu.set_option("order", 1)
-        gpu.set_option("guided", 1)
-        for _ in range(3):
-            got, st = frames.render(gpu, ds, size, cam)
-            assert_bit_equal(got, plain, "guided hand-out with option 1")
-            assert read_slot(ds, "order") is None and not used_order(ds)            # never combined: index order, nothing recorded
-            for k in ("rays_primary", "rays_shadow", "hits_primary", "flags"):
-                assert st[k] == st0[k], k
+        with options(gpu, order=0) as set_:
+            for _ in range(2):
+                plain, st0 = frames.render(gpu, ds, size, cam)
+                assert_bit_equal(plain, want, "option 0")
+                assert read_slot(ds, "costs") is None and read_slot(ds, "order") is None
+            set_(order=2)
+            for _ in range(2):
+                got, _ = frames.render(gpu, ds, size, cam)
+                assert_bit_equal(got, want, "option 2")
+                assert len(read_slot(ds, "costs")) == nTiles and read_slot(ds, "order") is None and not used_order(ds)
+            set_(order=0)
+            frames.render(gpu, ds, size, cam)
+            assert read_slot(ds, "costs") is None                                       # option 0 forgets what was recorded
+            set_(order=1, guided=1)
+            for _ in range(3):
+                got, st = frames.render(gpu, ds, size, cam)
+                assert_bit_equal(got, plain, "guided hand-out with option 1")
+                assert read_slot(ds, "order") is None and not used_order(ds)            # never combined: index order, nothing recorded
+                for k in ("rays_primary", "rays_shadow", "hits_primary", "flags"):
+                    assert st[k] == st0[k], k
     finally:
         ds.close()
 
@@ -646,35 +631,30 @@ def test_costs_add_up_to_the_rounds_of_the_launch(gpu, frames, order, reuse):
     moved = ft.Camera.lookAt(Lens=ft.Lens.create(60.0), **MOVED)
     ds = gpu.scene(c3_small())
     try:
-        gpu.set_option("order", order)
-        gpu.set_option("reuse", reuse)
+        with options(gpu, order=order, reuse=reuse) as set_:
+            def launch(what, camera, reordered):
+                _, st = frames.render(gpu, ds, size, camera)
+                cost = read_slot(ds, "costs")
+                assert cost is not None and len(cost) == TILES2
+                assert used_order(ds) == reordered, what
+                total, rounds = int(cost.sum(dtype=np.uint64)), st["wave_evals"]
+                print(f"order {order} reuse {reuse}, {what}: sum of costs {total}, wave_evals {rounds}, difference {rounds - total}")
+                assert total <= rounds, (what, total, rounds)
+                if reuse == 0:
+                    assert total == rounds, (what, total, rounds)
+                else:
+                    waves = rounds - total
+                    assert waves % 4 == 0 and 0 < waves <= 4 * ((TILES2 * 64 + 255) // 256), (what, total, rounds)
+                return cost, rounds - total
 
-        def launch(what, camera, reordered):
-            _, st = frames.render(gpu, ds, size, camera)
-            cost = read_slot(ds, "costs")
-            assert cost is not None and len(cost) == TILES2
-            assert used_order(ds) == reordered, what
-            total, rounds = int(cost.sum(dtype=np.uint64)), st["wave_evals"]
-            print(f"order {order} reuse {reuse}, {what}: sum of costs {total}, wave_evals {rounds}, difference {rounds - total}")
-            assert total <= rounds, (what, total, rounds)
-            if reuse == 0:
-                assert total == rounds, (what, total, rounds)
-            else:
-                waves = rounds - total
-                assert waves % 4 == 0 and 0 < waves <= 4 * ((TILES2 * 64 + 255) // 256), (what, total, rounds)
-            return cost, rounds - total
-
-        first, waves = launch("first launch of a fresh scene", cam, False)
-        other, w = launch("moved camera", moved, order == 1)                       # the same key: the slot's order, built for another view
-        assert w == waves
-        assert not np.array_equal(first, other)                                     # other costs
-        gpu.set_option("tail_k", 64)
-        _, w = launch("tail_k 64", cam, order == 1)
-        assert w == waves
-        gpu.set_option("tail_k", -1)
-        gpu.set_option("math", ft.glibc_build_of_this_host())
-        launch("glibc arithmetic", cam, False)                                      # another kernel: another key, index order
+            first, waves = launch("first launch of a fresh scene", cam, False)
+            other, w = launch("moved camera", moved, order == 1)                       # the same key: the slot's order, built for another view
+            assert w == waves
+            assert not np.array_equal(first, other)                                     # other costs
+            set_(tail_k=64)
+            _, w = launch("tail_k 64", cam, order == 1)
+            assert w == waves
+            set_(tail_k=-1, math=ft.glibc_build_of_this_host())
+            launch("glibc arithmetic", cam, False)                                      # another kernel: another key, index order
     finally:
-        gpu.set_option("tail_k", -1)
-        gpu.set_option("reuse", 1)
         ds.close()
