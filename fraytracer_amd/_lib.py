@@ -83,6 +83,13 @@ class Lattice(C.Structure):                  # ft_lattice: point (i, j, k) = ori
 FT_FIELD_BOUNDED = 1
 
 
+class MeshInfo(C.Structure):                 # ft_mesh_info
+    _fields_ = [("n_vertices", C.c_int64), ("n_triangles", C.c_int64), ("n_skipped", C.c_int64), ("has_normal", C.c_int32), ("has_material", C.c_int32)]
+
+
+FT_MESH_NORMAL, FT_MESH_MATERIAL = 1, 2
+
+
 class TonemapParams(C.Structure):
     _fields_ = [("gamma", C.c_float), ("dither", C.c_int32), ("seed", C.c_uint32), ("bmp_order", C.c_int32)]
 
@@ -164,6 +171,13 @@ SYMBOLS = {
     "ft_sample_points_device": (C.c_int, [_P, _P, _P, C.c_int64, C.c_float, C.c_uint32, _P, _P, _P]),
     "ft_sample_lattice": (C.c_int, [_P, _P, C.POINTER(Lattice), C.c_float, C.c_uint32, _P, _P, _P]),
     "ft_sample_lattice_device": (C.c_int, [_P, _P, C.POINTER(Lattice), C.c_float, C.c_uint32, _P, _P, _P]),
+    "ft_mesh_lattice": (C.c_int, [_P, _P, C.POINTER(Lattice), C.c_float, C.c_float, C.c_uint32, C.POINTER(_P)]),
+    "ft_mesh_values_device": (C.c_int, [_P, C.POINTER(Lattice), _P, C.c_float, C.POINTER(_P)]),
+    "ft_mesh_values": (C.c_int, [_P, C.POINTER(Lattice), _P, C.c_float, C.POINTER(_P)]),
+    "ft_mesh_get_info": (C.c_int, [_P, C.POINTER(MeshInfo)]),
+    "ft_mesh_device_buffers": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(_P)]),
+    "ft_mesh_read": (C.c_int, [_P, _P, _P, _P, _P]),
+    "ft_mesh_destroy": (None, [_P]),
     "ft_scene_clone": (C.c_int, [_P, _P, C.POINTER(_P)]),
     "ft_render_multi": (C.c_int, [C.POINTER(_P), C.POINTER(_P), C.c_int32, C.POINTER(CameraS), C.POINTER(RenderParams), _P, C.POINTER(Stats)]),
     "ft_scene_info_get": (C.c_int, [_P, C.POINTER(SceneInfo)]),

@@ -161,6 +161,12 @@ class SdfForm:
         return _form_scene(form, device).sample_lattice(origin, step, counts, normal_epsilon=normal_epsilon, bounded=bounded)
 
     @staticmethod
+    def mesh(form, origin, step, counts, iso=0.0, normal_epsilon=None, device=None):
+        """the surface sdf.Distance = iso as triangles, extracted on the GPU from the lattice lattice_points(origin, step, counts) -> Mesh, with
+        SdfForm.normal per vertex where normal_epsilon is given (DeviceScene.mesh_lattice)"""
+        return _form_scene(form, device).mesh_lattice(origin, step, counts, iso=iso, normal_epsilon=normal_epsilon)
+
+    @staticmethod
     def normalFromRay(form, rays, device=None):
         """SdfForm.normalFromRay (SdfForm.fs:106-115) at the position of each ray [n, 8] -> float32 [n, 3]: forward
         differences with h = Epsilon / 8 at Ray.get(-Epsilon), evaluated on the GPU"""
@@ -494,6 +500,29 @@ class Device:
                 self._scenes.append(got)
             return got
 
+    def mesh_values(self, values, origin, step, iso=0.0):
+        """ft_mesh_values: the surface {values = iso} of a float32 lattice [nx, ny, nz] (point (i, j, k) at lattice_points(origin, step,
+        values.shape)) as triangles, extracted on the device -> Mesh without normals and materials.  A device tensor (see is_device_tensor;
+        float32, contiguous) is meshed where it lies by ft_mesh_values_device on the caller's current stream, and the Mesh holds tensors of its
+        device; the values are only read."""
+        on_device = is_device_tensor(values)
+        if on_device:
+            if str(values.dtype).rsplit(".", 1)[-1] != "float32" or not values.is_contiguous():
+                raise ValueError("mesh_values: a device tensor must be float32 and contiguous (no silent copy on the device)")
+            vals = values
+        else:
+            vals = np.ascontiguousarray(values, dtype=np.float32)
+        if len(tuple(vals.shape)) != 3:
+            raise ValueError(f"mesh_values: values must have shape [nx, ny, nz], not {list(vals.shape)}")
+        lat, _ = _lattice(origin, step, tuple(int(d) for d in vals.shape))
+        handle = C.c_void_p()
+        if on_device:
+            with self.on_current_stream(vals):
+                check(lib.ft_mesh_values_device(self._ctx, C.byref(lat), _dptr(vals.data_ptr()), float(iso), C.byref(handle)))
+                return _read_mesh(handle, vals, None)
+        check(lib.ft_mesh_values(self._ctx, C.byref(lat), _hptr(vals), float(iso), C.byref(handle)))
+        return _read_mesh(handle, None, None)
+
     def selftest_libm(self, op, variant, y=0.0, lo_bits=0, n_chunks=256):
         """ft_selftest_libm: checksums of the device restatement of glibc's expf (op 0) / logf (1) / powf(x, y) (2) per 2^24 inputs"""
         sums = (C.c_uint64 * n_chunks)()
@@ -655,6 +684,72 @@ class FieldSamples:
     def descriptor(self, handle):
         """the SdfMaterial description (SdfMaterial.createSolid / createGlass value) a material handle was realised from; None for -1"""
         return self._materials.get(int(handle))
+
+
+class Mesh:
+    """What mesh_lattice / mesh_values return: `vertices` float32 [nv, 3], `triangles` int32 [nt, 3] (counter-clockwise seen from the outside),
+    `normal` float32 [nv, 3] and `material` int32 [nv] (the handle of the material object.Material.Color picks at the vertex) — None where not
+    asked for — and `skipped`, the tetrahedra left out for a non-finite corner value; numpy arrays, or device tensors where the call was given
+    one.  The rule that fixes every bit of it is the header's ("Meshing")."""
+
+    def __init__(self, vertices, triangles, normal=None, material=None, skipped=0, materials=None):
+        self.vertices = vertices
+        self.triangles = triangles
+        self.normal = normal
+        self.material = material
+        self.skipped = int(skipped)
+        self._materials = dict(materials or {})
+
+    def descriptor(self, handle):
+        """the SdfMaterial description (SdfMaterial.createSolid / createGlass value) a material handle was realised from; None for -1"""
+        return self._materials.get(int(handle))
+
+    @staticmethod
+    def _host(a):
+        return None if a is None else (a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a))
+
+    def save_obj(self, path):
+        """Wavefront OBJ: v lines (9 significant digits: float32 round-trips), vn lines where the mesh has normals, f lines with 1-based indices"""
+        v, t, n = self._host(self.vertices), self._host(self.triangles), self._host(self.normal)
+        with open(path, "w") as f:
+            f.write(f"# {len(v)} vertices, {len(t)} triangles\n")
+            for p in v:
+                f.write("v %.9g %.9g %.9g\n" % tuple(float(c) for c in p))
+            if n is not None:
+                for p in n:
+                    f.write("vn %.9g %.9g %.9g\n" % tuple(float(c) for c in p))
+            for a, b, c in (t + 1).tolist():
+                f.write(f"f {a}//{a} {b}//{b} {c}//{c}\n" if n is not None else f"f {a} {b} {c}\n")
+
+    def save_stl(self, path):
+        """binary STL: per triangle its unit normal (from the vertices, float32; zero for a zero-area triangle) and its three corners"""
+        v, t = self._host(self.vertices), self._host(self.triangles)
+        corners = v[t.astype(np.int64)].astype(np.float32).reshape(-1, 3, 3)
+        with np.errstate(all="ignore"):
+            nrm = np.cross(corners[:, 1] - corners[:, 0], corners[:, 2] - corners[:, 0]).astype(np.float32)
+            length = np.sqrt((nrm * nrm).sum(axis=1, dtype=np.float32))
+            nrm = np.where(length[:, None] > 0, nrm / length[:, None], np.float32(0.0)).astype(np.float32)
+        rec = np.zeros(len(t), np.dtype([("n", "<f4", 3), ("v", "<f4", (3, 3)), ("attr", "<u2")]))
+        rec["n"], rec["v"] = nrm, corners
+        with open(path, "wb") as f:
+            f.write(b"fraytracer_amd mesh".ljust(80, b" "))
+            f.write(np.uint32(len(t)).tobytes())
+            f.write(rec.tobytes())
+
+
+def _read_mesh(handle, like, materials):
+    """an ft_mesh -> Mesh of numpy arrays (like = None) or of tensors of like's device, through ft_mesh_read; the handle is destroyed"""
+    try:
+        info = _lib.MeshInfo()
+        check(lib.ft_mesh_get_info(handle, C.byref(info)))
+        nv, nt = int(info.n_vertices), int(info.n_triangles)
+        parts = (_empty(like, (nv, 3)), _empty(like, (nt, 3), "int32"), _empty(like, (nv, 3)) if info.has_normal else None,
+                 _empty(like, (nv,), "int32") if info.has_material else None)
+        ptr = _hptr if like is None else (lambda a: None if a is None else _dptr(a.data_ptr()))
+        check(lib.ft_mesh_read(handle, *map(ptr, parts)))
+        return Mesh(*parts, skipped=info.n_skipped, materials=materials)
+    finally:
+        lib.ft_mesh_destroy(handle)
 
 
 def _torch_int32(t):
@@ -1101,6 +1196,22 @@ class DeviceScene:
         return self._field(n, like, lambda e, f, *o: check(lib.ft_sample_lattice(ctx, sc, C.byref(lat), e, f, *o)),
                            lambda e, f, *o: check(lib.ft_sample_lattice_device(ctx, sc, C.byref(lat), e, f, *map(_dptr, o))),
                            normal_epsilon, distance, material, bounded)
+
+    def mesh_lattice(self, origin, step, counts, iso=0.0, normal_epsilon=None, material=False, like=None):
+        """ft_mesh_lattice: the surface scene.Object.Form.Distance = iso as triangles, extracted on the device from the distances on
+        lattice_points(origin, step, counts) (never bounded) -> Mesh.  normal_epsilon: also SdfForm.normal sdf normal_epsilon v per vertex;
+        material: also the handle of the material object.Material.Color picks at v (Mesh.descriptor) — both exactly what sample_points gives
+        for the vertices.  like: a device tensor — the Mesh then holds tensors of its device, and the launches run on the caller's current
+        stream."""
+        lat, _ = _lattice(origin, step, counts)
+        if like is not None and not is_device_tensor(like):
+            raise ValueError("like: a device tensor (see is_device_tensor) or None")
+        flags = (_lib.FT_MESH_NORMAL if normal_epsilon is not None else 0) | (_lib.FT_MESH_MATERIAL if material else 0)
+        eps = float(normal_epsilon) if normal_epsilon is not None else 0.0
+        handle = C.c_void_p()
+        with (self.device.on_current_stream(like) if like is not None else contextlib.nullcontext()):
+            check(lib.ft_mesh_lattice(self.device._ctx, self._scene, C.byref(lat), float(iso), eps, flags, C.byref(handle)))
+            return _read_mesh(handle, like, self.materials)
 
     def sample_points_device(self, d_points_ptr, n, d_distance_ptr=None, d_normal_ptr=None, d_material_ptr=None, normal_epsilon=0.0, flags=0):
         """asynchronous ft_sample_points_device: n points (12 B each) at d_points_ptr -> n float32 distances, n x 3 float32 normals, n int32

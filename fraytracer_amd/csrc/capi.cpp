@@ -13,6 +13,7 @@
 #include "../../include/fraytracer_hip.h"
 #include "build_hash.h"      // FT_SOURCE_HASH: written by the Makefile (source_hash.py)
 #include "ft_kernels.h"
+#include "ft_mesh.h"
 #include "scene.hpp"
 
 #ifndef FT_BUILD_KIND
@@ -73,6 +74,7 @@ struct ft_ctx {
     int optOcclPolicy = 0;                                 // FT_OPT_OCCL_POLICY: 0 = the shipped schedule (FT_OCCL_PERIOD ...)
     int optOrder = 1;                                      // FT_OPT_ORDER: 1 = frames hand their heavy tiles out first, from the costs the scene's last launch of the same grid recorded; 2 = record only; 0 = off
     int fieldBrick = -1;                                   // brick shape of the lattice launches: -1 by kernel family (launchField), else an index into FT_FIELD_BRICKS (ft_ctx_field_brick: the probe's shapes)
+    uint32_t meshTile = FT_MESH_TILE_DEFAULT;              // lattice points per workgroup of the mesher's kernels (ft_ctx_mesh_tile: the probe's tiles)
     uint32_t orderNum = 1, orderDen = 1;                   // a tile is heavy from orderNum / orderDen of the mean cost on (ft_ctx_tile_order_rule: the probes' other rules)
 };
 
@@ -1615,6 +1617,176 @@ int ft_sample_lattice_device(ft_ctx* c, const ft_scene* s, const ft_lattice* lat
 int ft_ctx_field_brick(ft_ctx* c, int32_t shape) {
     if (!c || shape < -1 || shape > 2) return setErr(FT_ERR_INVALID, "bad argument");
     c->fieldBrick = shape;
+    return FT_OK;
+}
+
+// ---- meshing: ft_mesh_lattice, ft_mesh_values, ft_mesh_values_device and what reads a mesh (mesh.hip; the rule is the header's "Meshing") ----------
+struct ft_mesh {
+    ft_ctx* ctx = nullptr;
+    int64_t nV = 0, nT = 0, nSkipped = 0;
+    bool hasNormal = false, hasMaterial = false;
+    void* dVertices = nullptr; void* dTriangles = nullptr; void* dNormals = nullptr; void* dMaterials = nullptr;
+};
+
+namespace {
+
+// the scene (scene form only), the lattice, its values (values forms only; host or device memory as the entry point says) and where the mesh goes
+struct MeshRequest { const ft_scene* s; const ft_lattice* lat; const void* values; float iso, eps; uint32_t flags; ft_mesh** out; };
+enum class MeshForm { Scene, HostValues, DeviceValues };
+
+// Everything that can be refused without a device, in the header's order.  *nothing: a count of 1, FT_OK with an empty mesh and nothing to launch.
+int checkMesh(const ft_ctx* c, const MeshRequest& r, MeshForm form, bool* nothing) {
+    *nothing = false;
+    if (r.out) *r.out = nullptr;
+    if (!c) return setErr(FT_ERR_INVALID, "null context");
+    if (form == MeshForm::Scene && (!r.s || r.s->ctx != c)) return setErr(FT_ERR_INVALID, "bad argument (scene must belong to this context)");
+    if (!r.lat) return setErr(FT_ERR_INVALID, "null lattice");
+    if (form != MeshForm::Scene && !r.values) return setErr(FT_ERR_INVALID, "mesh: null values");
+    if (!r.out) return setErr(FT_ERR_INVALID, "null out pointer");
+    const int32_t cnt[3] = {r.lat->nx, r.lat->ny, r.lat->nz};
+    for (int32_t v : cnt) if (v < 1 || v > 16777216) return setErr(FT_ERR_INVALID, "lattice: every count must be 1 .. 16777216");
+    if (r.flags & ~(uint32_t)(FT_MESH_NORMAL | FT_MESH_MATERIAL)) return setErr(FT_ERR_INVALID, "mesh: unknown flag bits");
+    if (form == MeshForm::DeviceValues && (reinterpret_cast<uintptr_t>(r.values) & 3u)) return setErr(FT_ERR_INVALID, "mesh: the device values must be 4-byte aligned");
+    // three counts of at most 2^24: the product of two fits 2^48, and the third is applied only below the limit
+    const uint64_t two = (uint64_t)r.lat->nx * (uint64_t)r.lat->ny;
+    if (two >= 0xFFFF0000ull || two * (uint64_t)r.lat->nz >= 0xFFFF0000ull) return setErr(FT_ERR_UNSUPPORTED, "more than 2^32 points in one call");
+    *nothing = r.lat->nx == 1 || r.lat->ny == 1 || r.lat->nz == 1;
+    return FT_OK;
+}
+
+// The extraction: values (device memory, n floats) -> m's vertices and triangles.  work: 5 B per point and 12 B per tile behind `workAt` bytes of
+// the context's scratch (already ensured).  Synchronises the context's stream once, between the scan and the allocations.
+struct MeshWork { size_t mask, vbase, tileV, tileT, tileS, totals, end; };
+MeshWork meshWork(size_t at, size_t n, size_t nTiles) {
+    MeshWork w{};
+    w.mask = align256(at); w.vbase = align256(w.mask + n); w.tileV = align256(w.vbase + 4 * n); w.tileT = align256(w.tileV + 4 * nTiles);
+    w.tileS = align256(w.tileT + 4 * nTiles); w.totals = align256(w.tileS + 4 * nTiles); w.end = w.totals + 256;
+    return w;
+}
+int launchMesh(ft_ctx* c, int kernel, const FtMeshArgs& a) {
+    int perCU = 0;
+    HIP_TRY(ft_mesh_occupancy(kernel, a.tile, &perCU));
+    static const char* const names[4] = {"mesh count", "mesh scan", "mesh vertices", "mesh triangles"};
+    int rc = clampPerCU(c, names[kernel], perCU); if (rc) return rc;
+    const unsigned blocks = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)c->numCUs * perCU, a.nTiles));
+    return timedLaunch(c, c->stream, "ft_launch_mesh", [&] { return ft_launch_mesh(kernel, &a, blocks, c->stream); });
+}
+int extractMesh(ft_ctx* c, const ft_lattice& l, const float* dValues, float iso, const MeshWork& w, ft_mesh* m) {
+    FtMeshArgs a{};
+    a.values = dValues; a.iso = iso;
+    a.nx = (uint32_t)l.nx; a.ny = (uint32_t)l.ny; a.nz = (uint32_t)l.nz;
+    a.n = a.nx * a.ny * a.nz;                                          // below 0xFFFF0000 (checkMesh)
+    a.tile = c->meshTile;
+    a.nTiles = (uint32_t)(((uint64_t)a.n + a.tile - 1u) / a.tile);
+    a.origin[0] = l.origin.x; a.origin[1] = l.origin.y; a.origin[2] = l.origin.z;
+    a.step[0] = l.step.x; a.step[1] = l.step.y; a.step[2] = l.step.z;
+    unsigned char* base = static_cast<unsigned char*>(c->scratch);
+    a.mask = base + w.mask; a.vbase = reinterpret_cast<uint32_t*>(base + w.vbase);
+    a.tileV = reinterpret_cast<uint32_t*>(base + w.tileV); a.tileT = reinterpret_cast<uint32_t*>(base + w.tileT); a.tileS = reinterpret_cast<uint32_t*>(base + w.tileS);
+    a.totals = reinterpret_cast<unsigned long long*>(base + w.totals);
+    int rc;
+    if ((rc = launchMesh(c, FT_MESH_K_COUNT, a)) || (rc = launchMesh(c, FT_MESH_K_SCAN, a))) return rc;
+    unsigned long long totals[3] = {0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(totals, a.totals, sizeof totals, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));                          // the one synchronisation: the outputs cannot be sized before the count
+    if (totals[0] >= (1ull << 31) || totals[1] >= (1ull << 31)) return setErr(FT_ERR_UNSUPPORTED, "mesh: 2^31 or more vertices or triangles (the index type is int32)");
+    m->nV = (int64_t)totals[0]; m->nT = (int64_t)totals[1]; m->nSkipped = (int64_t)totals[2];
+    if (m->nV) HIP_TRY(hipMalloc(&m->dVertices, (size_t)m->nV * 12));
+    if (m->nT) HIP_TRY(hipMalloc(&m->dTriangles, (size_t)m->nT * 12));
+    a.vertices = static_cast<float*>(m->dVertices); a.triangles = static_cast<int32_t*>(m->dTriangles);
+    a.nV = (uint32_t)m->nV; a.nT = (uint32_t)m->nT;
+    if (m->nV && (rc = launchMesh(c, FT_MESH_K_VERTICES, a))) return rc;              // triangles only join vertices: none without them
+    if (m->nT && (rc = launchMesh(c, FT_MESH_K_TRIANGLES, a))) return rc;
+    return FT_OK;
+}
+
+int buildMesh(ft_ctx* c, const MeshRequest& r, MeshForm form) {
+    bool nothing;
+    int rc = checkMesh(c, r, form, &nothing); if (rc) return rc;
+    ft_mesh* m = new ft_mesh();
+    m->ctx = c;
+    m->hasNormal = (r.flags & FT_MESH_NORMAL) != 0u; m->hasMaterial = (r.flags & FT_MESH_MATERIAL) != 0u;
+    if (nothing) { *r.out = m; return FT_OK; }
+    auto fail = [&](int code) { if (c->hasDevice) (void)hipStreamSynchronize(c->stream); ft_mesh_destroy(m); return code; };
+    if ((rc = requireDevice(c))) return fail(rc);
+    const ft_lattice& l = *r.lat;
+    const size_t n = (size_t)l.nx * l.ny * l.nz, tile = c->meshTile, nTiles = (n + tile - 1) / tile;
+    const MeshWork w = meshWork(form == MeshForm::DeviceValues ? 0 : n * 4, n, nTiles);
+    if ((rc = ensureScratch(c, w.end))) return fail(rc);
+    const float* dValues = form == MeshForm::DeviceValues ? static_cast<const float*>(r.values) : static_cast<const float*>(c->scratch);
+    if (form == MeshForm::HostValues) {
+        const hipError_t e = hipMemcpyAsync(c->scratch, r.values, n * 4, hipMemcpyHostToDevice, c->stream);
+        if (e != hipSuccess) return fail(hipFail(e, "mesh: upload"));
+    } else if (form == MeshForm::Scene) {
+        if ((rc = launchField(c, r.s, FieldRequest{nullptr, 0, r.lat, 0.0f, 0u, c->scratch, nullptr, nullptr}))) return fail(rc);
+    }
+    if ((rc = extractMesh(c, l, dValues, r.iso, w, m))) return fail(rc);
+    if (form == MeshForm::Scene && m->nV && (m->hasNormal || m->hasMaterial)) {
+        hipError_t e = hipSuccess;
+        if (m->hasNormal) e = hipMalloc(&m->dNormals, (size_t)m->nV * 12);
+        if (e == hipSuccess && m->hasMaterial) e = hipMalloc(&m->dMaterials, (size_t)m->nV * 4);
+        if (e != hipSuccess) return fail(hipFail(e, "hipMalloc"));
+        // one points-form launch over the vertex buffer: what ft_sample_points_device gives for those points
+        if ((rc = launchField(c, r.s, FieldRequest{m->dVertices, m->nV, nullptr, r.eps, 0u, nullptr, m->dNormals, m->dMaterials}))) return fail(rc);
+    }
+    *r.out = m;
+    return FT_OK;
+}
+
+}  // namespace
+
+int ft_mesh_lattice(ft_ctx* c, const ft_scene* s, const ft_lattice* lattice, float iso, float normal_epsilon, uint32_t flags, ft_mesh** out) {
+    return buildMesh(c, MeshRequest{s, lattice, nullptr, iso, normal_epsilon, flags, out}, MeshForm::Scene);
+}
+int ft_mesh_values_device(ft_ctx* c, const ft_lattice* lattice, const void* d_values, float iso, ft_mesh** out) {
+    return buildMesh(c, MeshRequest{nullptr, lattice, d_values, iso, 0.0f, 0u, out}, MeshForm::DeviceValues);
+}
+int ft_mesh_values(ft_ctx* c, const ft_lattice* lattice, const float* values, float iso, ft_mesh** out) {
+    return buildMesh(c, MeshRequest{nullptr, lattice, values, iso, 0.0f, 0u, out}, MeshForm::HostValues);
+}
+int ft_mesh_get_info(const ft_mesh* m, ft_mesh_info* o) {
+    if (!m || !o) return setErr(FT_ERR_INVALID, "null argument");
+    o->n_vertices = m->nV; o->n_triangles = m->nT; o->n_skipped = m->nSkipped;
+    o->has_normal = m->hasNormal ? 1 : 0; o->has_material = m->hasMaterial ? 1 : 0;
+    return FT_OK;
+}
+int ft_mesh_device_buffers(const ft_mesh* m, void** d_vertices, void** d_triangles, void** d_normals, void** d_materials) {
+    if (!m) return setErr(FT_ERR_INVALID, "null mesh");
+    if (d_vertices) *d_vertices = m->dVertices;
+    if (d_triangles) *d_triangles = m->dTriangles;
+    if (d_normals) *d_normals = m->dNormals;
+    if (d_materials) *d_materials = m->dMaterials;
+    return FT_OK;
+}
+int ft_mesh_read(const ft_mesh* m, ft_vec3* vertices, int32_t* triangles, ft_vec3* normals, int32_t* materials) {
+    if (!m) return setErr(FT_ERR_INVALID, "null mesh");
+    if ((normals && !m->hasNormal) || (materials && !m->hasMaterial)) return setErr(FT_ERR_INVALID, "mesh: built without the normals or materials asked for");
+    if (!m->ctx->hasDevice) return FT_OK;                              // an empty mesh of a host-only context: nothing to copy
+    int rc = requireDevice(m->ctx); if (rc) return rc;
+    const struct { void* host; const void* dev; size_t bytes; } parts[4] = {
+        {vertices, m->dVertices, (size_t)m->nV * 12}, {triangles, m->dTriangles, (size_t)m->nT * 12},
+        {normals, m->dNormals, (size_t)m->nV * 12}, {materials, m->dMaterials, (size_t)m->nV * 4}};
+    hipError_t e = hipSuccess;
+    for (const auto& p : parts)
+        if (e == hipSuccess && p.host && p.dev && p.bytes) e = hipMemcpyAsync(p.host, p.dev, p.bytes, hipMemcpyDefault, m->ctx->stream);      // host or device destination
+    const hipError_t se = hipStreamSynchronize(m->ctx->stream);        // nothing of the call is left in flight, whatever happened
+    if (e != hipSuccess) return hipFail(e, "ft_mesh_read");
+    if (se != hipSuccess) return hipFail(se, "ft_mesh_read");
+    return FT_OK;
+}
+void ft_mesh_destroy(ft_mesh* m) {
+    if (!m) return;
+    if (m->ctx->hasDevice && (m->dVertices || m->dTriangles || m->dNormals || m->dMaterials)) {
+        (void)hipSetDevice(m->ctx->device);
+        for (void* p : {m->dVertices, m->dTriangles, m->dNormals, m->dMaterials}) if (p) (void)hipFree(p);      // waits for whatever still uses it
+    }
+    delete m;
+}
+// Internal (not in the header, like ft_ctx_field_brick; tools/mesh_probe.py): the lattice points per workgroup of this context's mesher launches, one
+// of 128, 256, 512, 1024.  Every tile gives the same mesh.
+int ft_ctx_mesh_tile(ft_ctx* c, int32_t tile) {
+    if (!c || (tile != 128 && tile != 256 && tile != 512 && tile != 1024)) return setErr(FT_ERR_INVALID, "bad argument");
+    c->meshTile = (uint32_t)tile;
     return FT_OK;
 }
 

@@ -19,6 +19,7 @@
 //                                                       (ft_light_visibility, ft_shade_visible)
 //   Field::sampleLattice / samplePoints                 sdf.Distance, SdfForm.normal and the material at the points of a lattice or a point buffer
 //                                                       (ft_sample_lattice, ft_sample_points; SdfForm.fs:7-12, 106-112)
+//   Mesh::ofLattice / ofValues                          the surface distance = iso as triangles, extracted on the device (ft_mesh_lattice, ft_mesh_values)
 #pragma once
 #include <stdexcept>
 #include <string>
@@ -290,6 +291,41 @@ inline Samples samplePoints(const SdfScene& scene, const std::vector<ft_vec3>& p
     return out;
 }
 }  // namespace Field
+
+// The surface {distance = iso} as triangles, extracted on the device from the distances on a lattice (ft_mesh_lattice: marching tetrahedra on the
+// Kuhn subdivision; the header states the rule).  triangles: three vertex indices each, counter-clockwise seen from the outside; normal and material
+// per vertex where asked for (SdfForm.normal sdf normalEpsilon v; the handle of the material object.Material.Color v picks)
+namespace Mesh {
+struct Triangles { std::vector<ft_vec3> vertices; std::vector<int32_t> triangles; std::vector<ft_vec3> normal; std::vector<int32_t> material; int64_t skipped = 0; };
+struct Request { float iso = 0.0f; bool normal = false; float normalEpsilon = 0.0f; bool material = false; };
+inline Triangles read(ft_mesh* mesh) {
+    struct Owner { ft_mesh* m; ~Owner() { ft_mesh_destroy(m); } } own{mesh};
+    ft_mesh_info info{};
+    check(ft_mesh_get_info(mesh, &info));
+    Triangles out;
+    out.skipped = info.n_skipped;
+    out.vertices.resize((size_t)info.n_vertices);
+    out.triangles.resize(3 * (size_t)info.n_triangles);
+    if (info.has_normal) out.normal.resize((size_t)info.n_vertices);
+    if (info.has_material) out.material.resize((size_t)info.n_vertices);
+    check(ft_mesh_read(mesh, out.vertices.data(), out.triangles.data(), info.has_normal ? out.normal.data() : nullptr,
+                       info.has_material ? out.material.data() : nullptr));
+    return out;
+}
+inline Triangles ofLattice(const SdfScene& scene, const ft_lattice& lattice, const Request& r = Request{}) {
+    SceneOfCall s(scene);
+    ft_mesh* mesh = nullptr;
+    s.done(ft_mesh_lattice(s.ctx, s.get(), &lattice, r.iso, r.normalEpsilon, (r.normal ? FT_MESH_NORMAL : 0u) | (r.material ? FT_MESH_MATERIAL : 0u), &mesh), nullptr);
+    return read(mesh);
+}
+// any float32 lattice already in host memory: nx * ny * nz values, k contiguous (ft_mesh_values)
+inline Triangles ofValues(ft_ctx* ctx, const ft_lattice& lattice, const std::vector<float>& values, float iso = 0.0f) {
+    if (values.size() != (size_t)lattice.nx * (size_t)lattice.ny * (size_t)lattice.nz) throw std::invalid_argument("Mesh::ofValues: one value per lattice point");
+    ft_mesh* mesh = nullptr;
+    check(ft_mesh_values(ctx, &lattice, values.data(), iso, &mesh));
+    return read(mesh);
+}
+}  // namespace Mesh
 
 // SdfObject.tryTrace / SdfForm.tryTrace (SdfObject.fs:66-78, SdfForm.fs:93-104) over a ray buffer; hit == 0 is ValueNone
 inline std::vector<ft_object_trace_result> tryTrace(const SdfObjectV& object, const std::vector<ft_ray>& rays) {

@@ -47,6 +47,9 @@ type FtTonemapParams = { Gamma : float32; Dither : int; Seed : uint32; BmpOrder 
 /// ft_lattice: point (i, j, k) = Origin + (i, j, k) * Step per coordinate (one float32 product, one float32 sum); results at (i * Ny + j) * Nz + k
 [<Struct; StructLayout(LayoutKind.Sequential)>]
 type FtLattice = { Origin : Vector3; Step : Vector3; Nx : int; Ny : int; Nz : int }
+/// ft_mesh_info (32 bytes)
+[<Struct; StructLayout(LayoutKind.Sequential)>]
+type FtMeshInfo = { NVertices : int64; NTriangles : int64; NSkipped : int64; HasNormal : int; HasMaterial : int }
 
 /// ft_form_trace_result: SdfFormTraceResult voption (Types.fs:32-37), Hit = 0 is ValueNone
 [<Struct; StructLayout(LayoutKind.Sequential)>]
@@ -110,6 +113,16 @@ module Native =
     [<DllImport(Lib)>] extern int ft_sample_points_device(nativeint ctx, nativeint scene, nativeint dPoints, int64 n, float32 normalEpsilon, uint32 flags, nativeint dDistance, nativeint dNormal, nativeint dMaterial)
     [<DllImport(Lib)>] extern int ft_sample_lattice(nativeint ctx, nativeint scene, nativeint lattice, float32 normalEpsilon, uint32 flags, nativeint outDistance, nativeint outNormal, nativeint outMaterial)
     [<DllImport(Lib)>] extern int ft_sample_lattice_device(nativeint ctx, nativeint scene, nativeint lattice, float32 normalEpsilon, uint32 flags, nativeint dDistance, nativeint dNormal, nativeint dMaterial)
+    // meshing: the surface {distance = iso} of the lattice as triangles (marching tetrahedra on the Kuhn subdivision; the header states the rule).
+    // mesh: a plain nativeint out-parameter (pin a nativeint or pass the address of a mutable one); flags 1u = per-vertex normals, 2u = materials;
+    // ft_mesh_read copies to pinned arrays (0n: that part is not asked for); a mesh outlives its scene, not its context
+    [<DllImport(Lib)>] extern int ft_mesh_lattice(nativeint ctx, nativeint scene, nativeint lattice, float32 iso, float32 normalEpsilon, uint32 flags, nativeint mesh)
+    [<DllImport(Lib)>] extern int ft_mesh_values_device(nativeint ctx, nativeint lattice, nativeint dValues, float32 iso, nativeint mesh)
+    [<DllImport(Lib)>] extern int ft_mesh_values(nativeint ctx, nativeint lattice, nativeint values, float32 iso, nativeint mesh)
+    [<DllImport(Lib)>] extern int ft_mesh_get_info(nativeint mesh, nativeint info)
+    [<DllImport(Lib)>] extern int ft_mesh_device_buffers(nativeint mesh, nativeint dVertices, nativeint dTriangles, nativeint dNormals, nativeint dMaterials)
+    [<DllImport(Lib)>] extern int ft_mesh_read(nativeint mesh, nativeint vertices, nativeint triangles, nativeint normals, nativeint materials)
+    [<DllImport(Lib)>] extern void ft_mesh_destroy(nativeint mesh)
     [<DllImport(Lib)>] extern int ft_form_try_trace(nativeint ctx, nativeint scene, Ray[] rays, int64 n, [<Out>] FtFormTraceResult[] out, FtStats& stats)
     [<DllImport(Lib)>] extern int ft_object_try_trace(nativeint ctx, nativeint scene, Ray[] rays, int64 n, [<Out>] FtObjectTraceResult[] out, FtStats& stats)
     // ray buffers in device memory (rays 16-byte aligned, 32 B each): no scratch, no copy, not synchronised; pair with ft_collect_stats
@@ -348,6 +361,33 @@ module Field =
             out
         finally
             pinO.Free (); pinL.Free ()
+
+/// The surface of the distance field as triangles under a native scene handle, extracted on the GPU.
+module Mesh =
+    /// vertices and triangles (three indices each, counter-clockwise seen from the outside) of the surface Distance = iso on the lattice (ft_mesh_lattice)
+    let ofLattice (scene : nativeint) (iso : float32) (lattice : FtLattice) : Vector3[] * int[] =
+        let pinL = GCHandle.Alloc (box lattice, GCHandleType.Pinned)
+        let handle : nativeint[] = [| 0n |]
+        let pinH = GCHandle.Alloc (handle, GCHandleType.Pinned)
+        try
+            Native.check (Native.ft_mesh_lattice (Native.ctx.Value, scene, pinL.AddrOfPinnedObject (), iso, 0.0f, 0u, pinH.AddrOfPinnedObject ())) |> ignore
+            try
+                let info : FtMeshInfo[] = Array.zeroCreate 1
+                let pinI = GCHandle.Alloc (info, GCHandleType.Pinned)
+                try Native.check (Native.ft_mesh_get_info (handle.[0], pinI.AddrOfPinnedObject ())) |> ignore finally pinI.Free ()
+                let vertices : Vector3[] = Array.zeroCreate (int info.[0].NVertices)
+                let triangles : int[] = Array.zeroCreate (3 * int info.[0].NTriangles)
+                let pinV = GCHandle.Alloc (vertices, GCHandleType.Pinned)
+                let pinT = GCHandle.Alloc (triangles, GCHandleType.Pinned)
+                try
+                    Native.check (Native.ft_mesh_read (handle.[0], pinV.AddrOfPinnedObject (), pinT.AddrOfPinnedObject (), 0n, 0n)) |> ignore
+                    vertices, triangles
+                finally
+                    pinT.Free (); pinV.Free ()
+            finally
+                Native.ft_mesh_destroy handle.[0]
+        finally
+            pinH.Free (); pinL.Free ()
 
 module Image =
     /// GPU sibling of `scene |> FrayTracer.SdfScene.trace |> FrayTracer.Image.render epsilon length imageSize camera`

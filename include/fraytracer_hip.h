@@ -427,6 +427,64 @@ int ft_sample_points_device(ft_ctx*, const ft_scene*, const void* d_points, int6
 int ft_sample_lattice_device(ft_ctx*, const ft_scene*, const ft_lattice*, float normal_epsilon, uint32_t flags,
                              void* d_distance, void* d_normal, void* d_material);
 
+/* Meshing: the surface {distance = iso} of a lattice of distances as triangles, extracted on the device — marching tetrahedra on the Kuhn
+ * subdivision of every lattice cell.  The result is a pure function of the lattice's values; this is the rule, every bit of it.
+ *
+ * Input: a lattice (ft_lattice above: point rule p(q), index (i * ny + j) * nz + k), a float32 value d[q] per lattice point and a level iso.
+ * Signed value: s[q] = d[q] - iso, one float32 subtraction.  Point q is inside iff s[q] < 0: +0, -0 and NaN are not inside.
+ * Edge directions: seven, (di, dj, dk) with e = 4 * di + 2 * dj + dk - 1, i.e. 0 (0,0,1), 1 (0,1,0), 2 (0,1,1), 3 (1,0,0), 4 (1,0,1),
+ *     5 (1,1,0), 6 (1,1,1).  Edge (q, e) joins q and q' = q + dir(e), exists where both ends are lattice points, and is owned by q.
+ * Vertices: edge (q, e) carries a vertex iff s[q] and s[q'] are both finite and exactly one end is inside.  Its position, per coordinate in
+ *     float32 with every operation rounded on its own, never a fused multiply-add:
+ *         t = s[q] / (s[q] - s[q']), one true division;  v = p(q) + t * (p(q') - p(q)),
+ *     always computed from the owner towards the far end, once, and shared by every triangle that uses it.  Vertices are numbered by the
+ *     owner's linear index (i * ny + j) * nz + k, then by e.
+ * Tetrahedra: cell (i, j, k), 0 <= i < nx - 1 and likewise j, k, is cut into six, one per permutation pi of the axes (i, j, k) in
+ *     lexicographic order, with the corners c0 = (i, j, k), c1 = c0 + unit(pi1), c2 = c1 + unit(pi2), c3 = (i + 1, j + 1, k + 1); all their
+ *     edges are among the seven directions.  A tetrahedron with a non-finite corner value emits nothing and is counted in n_skipped.
+ * Triangles: one or three corners inside: one triangle on the three crossing edges; two corners inside, a1 < a2 inside and b1 < b2 outside
+ *     in corner order: the quad cycle (a1 b1, a1 b2, a2 b2, a2 b1).
+ * Orientation is combinatorial: decided on the integer corner offsets alone, never from floats (a zero or negative step does not change it).
+ *     The vertex order is counter-clockwise seen from the outside: the triangle's normal points from the inside corners towards the outside
+ *     ones.  Every triangle is rotated so that its smallest vertex index comes first; a quad is oriented the same way, rotated so that its
+ *     smallest vertex index is q0, and emitted as (q0, q1, q2), then (q0, q2, q3).
+ * Triangle order: by the cell's linear index (in the points' indexing), then by tetrahedron, then by the two triangles of a quad.
+ * Consequences: every triangle edge is shared by exactly two triangles in opposite directions, except where the surface leaves the lattice;
+ *     a corner value of exactly iso gives zero-area triangles but keeps the surface closed; a vertex next to a non-finite value may be
+ *     referenced by no triangle.  A lattice with a count of 1 has no cells: FT_OK and an empty mesh, no vertices either, no device needed.
+ *     The index type is int32: a mesh with 2^31 or more vertices or triangles is FT_ERR_UNSUPPORTED.
+ *
+ * ft_mesh_lattice evaluates the scene's distance on the lattice into the context's scratch (ft_sample_lattice_device's launch, never
+ * FT_FIELD_BOUNDED: a sphere's boundary is its surface, and NaN outside it would empty the mesh), then extracts.  flags: FT_MESH_NORMAL and
+ * FT_MESH_MATERIAL add per vertex SdfForm.normal (normal_epsilon, read only with FT_MESH_NORMAL) and the material handle, from one points-form
+ * field launch over the vertex buffer: exactly what ft_sample_points_device gives for those points.
+ * ft_mesh_values / ft_mesh_values_device mesh any float32 lattice already in host / device memory (nx * ny * nz values, k contiguous; the
+ * device pointer 4-byte aligned; the values are only read): no scene, no normals, no materials.
+ * The extraction cannot size its outputs before it has counted: each constructor synchronises the context's stream ONCE, to read the two
+ * totals, then allocates exactly, then emits on the context's stream without synchronising again (ft_mesh_read does; the buffers of
+ * ft_mesh_device_buffers are ordered with whatever the context launches next).  Scratch: 4 B per point for ft_mesh_lattice's and
+ * ft_mesh_values' distances, 5 B per point and 12 B per tile of points for the extraction.
+ * Refusals, all made before the device is asked for, in this order: FT_ERR_INVALID for NULL where none is allowed (context, scene, lattice,
+ * values, out), a scene of another context, a count < 1 or > 16777216, unknown flag bits, a misaligned device pointer; FT_ERR_UNSUPPORTED for
+ * nx * ny * nz >= 0xFFFF0000 (and for a scene whose LDS footprint no kernel fits); then FT_ERR_NO_DEVICE on a host-only context; FT_ERR_HIP
+ * for a failed allocation.  On any failure *out is NULL.
+ * A mesh owns device memory of its context: it outlives its scene but not its context.  ft_mesh_read copies to the caller's buffers (n_vertices x
+ * 3 float32, n_triangles x 3 int32, n_vertices x 3 float32, n_vertices x int32; host memory, or device memory: the direction of each copy is
+ * taken from the address), synchronises the context's stream and accepts NULL for any part; asking for normals or materials the mesh was not
+ * built with is FT_ERR_INVALID.  ft_mesh_device_buffers gives the device addresses (NULL for a part the mesh does not have or
+ * that is empty); each of its out-parameters may be NULL. */
+#define FT_MESH_NORMAL 1u
+#define FT_MESH_MATERIAL 2u
+typedef struct ft_mesh ft_mesh;                       /* opaque; owns device memory of its context */
+typedef struct ft_mesh_info { int64_t n_vertices, n_triangles, n_skipped; int32_t has_normal, has_material; } ft_mesh_info;
+int ft_mesh_lattice(ft_ctx*, const ft_scene*, const ft_lattice*, float iso, float normal_epsilon, uint32_t flags, ft_mesh** out);
+int ft_mesh_values_device(ft_ctx*, const ft_lattice*, const void* d_values, float iso, ft_mesh** out);
+int ft_mesh_values(ft_ctx*, const ft_lattice*, const float* values, float iso, ft_mesh** out);
+int ft_mesh_get_info(const ft_mesh*, ft_mesh_info* out);
+int ft_mesh_device_buffers(const ft_mesh*, void** d_vertices, void** d_triangles, void** d_normals, void** d_materials);
+int ft_mesh_read(const ft_mesh*, ft_vec3* vertices, int32_t* triangles, ft_vec3* normals, int32_t* materials);
+void ft_mesh_destroy(ft_mesh*);
+
 /* Single-process multi-GPU form (what an F# host would call): the flattened scene is
  * re-uploaded to each further device with ft_scene_clone, every device renders its column
  * stripes (stripe_rank = index in ctxs[], stripe_ranks = n) on its own host thread, and the
