@@ -90,6 +90,18 @@ class MeshInfo(C.Structure):                 # ft_mesh_info
 FT_MESH_NORMAL, FT_MESH_MATERIAL = 1, 2
 
 
+class Polyline(C.Structure):                 # ft_polyline: points [first, first + count) of slice `slice`
+    _fields_ = [("first", C.c_int32), ("count", C.c_int32), ("slice", C.c_int32), ("closed", C.c_int32)]
+
+
+class SlicesInfo(C.Structure):               # ft_slices_info
+    _fields_ = [("n_points", C.c_int64), ("n_polylines", C.c_int64), ("n_closed", C.c_int64), ("n_skipped", C.c_int64),
+                ("axis", C.c_int32), ("n_slices", C.c_int32), ("has_normal", C.c_int32), ("has_material", C.c_int32)]
+
+
+FT_SLICE_NORMAL, FT_SLICE_MATERIAL = 1, 2
+
+
 class TonemapParams(C.Structure):
     _fields_ = [("gamma", C.c_float), ("dither", C.c_int32), ("seed", C.c_uint32), ("bmp_order", C.c_int32)]
 
@@ -178,6 +190,13 @@ SYMBOLS = {
     "ft_mesh_device_buffers": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(_P)]),
     "ft_mesh_read": (C.c_int, [_P, _P, _P, _P, _P]),
     "ft_mesh_destroy": (None, [_P]),
+    "ft_slice_lattice": (C.c_int, [_P, _P, C.POINTER(Lattice), C.c_int32, C.c_float, C.c_float, C.c_uint32, C.POINTER(_P)]),
+    "ft_slice_values": (C.c_int, [_P, C.POINTER(Lattice), _P, C.c_int32, C.c_float, C.POINTER(_P)]),
+    "ft_slice_values_device": (C.c_int, [_P, C.POINTER(Lattice), _P, C.c_int32, C.c_float, C.POINTER(_P)]),
+    "ft_slices_get_info": (C.c_int, [_P, C.POINTER(SlicesInfo)]),
+    "ft_slices_device_buffers": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(_P)]),
+    "ft_slices_read": (C.c_int, [_P, _P, _P, _P, _P]),
+    "ft_slices_destroy": (None, [_P]),
     "ft_scene_clone": (C.c_int, [_P, _P, C.POINTER(_P)]),
     "ft_render_multi": (C.c_int, [C.POINTER(_P), C.POINTER(_P), C.c_int32, C.POINTER(CameraS), C.POINTER(RenderParams), _P, C.POINTER(Stats)]),
     "ft_scene_info_get": (C.c_int, [_P, C.POINTER(SceneInfo)]),

@@ -167,6 +167,12 @@ class SdfForm:
         return _form_scene(form, device).mesh_lattice(origin, step, counts, iso=iso, normal_epsilon=normal_epsilon)
 
     @staticmethod
+    def slice(form, origin, step, counts, axis=2, iso=0.0, normal_epsilon=None, device=None):
+        """the contours sdf.Distance = iso of every lattice plane normal to `axis`, extracted and chained on the GPU from the lattice
+        lattice_points(origin, step, counts) -> Contours, with SdfForm.normal per point where normal_epsilon is given (DeviceScene.slice_lattice)"""
+        return _form_scene(form, device).slice_lattice(origin, step, counts, axis=axis, iso=iso, normal_epsilon=normal_epsilon)
+
+    @staticmethod
     def normalFromRay(form, rays, device=None):
         """SdfForm.normalFromRay (SdfForm.fs:106-115) at the position of each ray [n, 8] -> float32 [n, 3]: forward
         differences with h = Epsilon / 8 at Ray.get(-Epsilon), evaluated on the GPU"""
@@ -523,6 +529,29 @@ class Device:
         check(lib.ft_mesh_values(self._ctx, C.byref(lat), _hptr(vals), float(iso), C.byref(handle)))
         return _read_mesh(handle, None, None)
 
+    def slice_values(self, values, origin, step, axis=2, iso=0.0):
+        """ft_slice_values: the contours {values = iso} of a float32 lattice [nx, ny, nz] in every lattice plane normal to `axis`, as ordered
+        polylines chained on the device -> Contours without normals and materials.  A device tensor (see is_device_tensor; float32, contiguous) is
+        sliced where it lies by ft_slice_values_device on the caller's current stream, and the Contours hold tensors of its device; the values are
+        only read."""
+        on_device = is_device_tensor(values)
+        if on_device:
+            if str(values.dtype).rsplit(".", 1)[-1] != "float32" or not values.is_contiguous():
+                raise ValueError("slice_values: a device tensor must be float32 and contiguous (no silent copy on the device)")
+            vals = values
+        else:
+            vals = np.ascontiguousarray(values, dtype=np.float32)
+        if len(tuple(vals.shape)) != 3:
+            raise ValueError(f"slice_values: values must have shape [nx, ny, nz], not {list(vals.shape)}")
+        lat, _ = _lattice(origin, step, tuple(int(d) for d in vals.shape))
+        handle = C.c_void_p()
+        if on_device:
+            with self.on_current_stream(vals):
+                check(lib.ft_slice_values_device(self._ctx, C.byref(lat), _dptr(vals.data_ptr()), int(axis), float(iso), C.byref(handle)))
+                return _read_slices(handle, vals, None)
+        check(lib.ft_slice_values(self._ctx, C.byref(lat), _hptr(vals), int(axis), float(iso), C.byref(handle)))
+        return _read_slices(handle, None, None)
+
     def selftest_libm(self, op, variant, y=0.0, lo_bits=0, n_chunks=256):
         """ft_selftest_libm: checksums of the device restatement of glibc's expf (op 0) / logf (1) / powf(x, y) (2) per 2^24 inputs"""
         sums = (C.c_uint64 * n_chunks)()
@@ -750,6 +779,69 @@ def _read_mesh(handle, like, materials):
         return Mesh(*parts, skipped=info.n_skipped, materials=materials)
     finally:
         lib.ft_mesh_destroy(handle)
+
+
+class Contours:
+    """What slice_lattice / slice_values return: `points` float32 [n, 3] and `polylines` int32 [m, 4] with the columns of ft_polyline (first, count,
+    slice, closed): polyline r is points[first : first + count] in slice `slice`, closed (a loop, its first point not repeated; counter-clockwise seen
+    from +axis around the inside, clockwise around a hole) or open.  `normal` float32 [n, 3] and `material` int32 [n] are None where not asked for;
+    `skipped` counts the triangles left out for a non-finite corner value; `axis` and `slices` say which planes.  numpy arrays, or device tensors
+    where the call was given one.  The rule that fixes every bit of it is the header's ("Slicing")."""
+
+    def __init__(self, points, polylines, normal=None, material=None, skipped=0, closed=0, axis=2, slices=0, materials=None):
+        self.points = points
+        self.polylines = polylines
+        self.normal = normal
+        self.material = material
+        self.skipped = int(skipped)
+        self.closed = int(closed)
+        self.axis = int(axis)
+        self.slices = int(slices)
+        self._materials = dict(materials or {})
+
+    def descriptor(self, handle):
+        """the SdfMaterial description a material handle was realised from; None for -1"""
+        return self._materials.get(int(handle))
+
+    def layer(self, w):
+        """the polylines of slice w in the rule's order: a list of (points float32 [m, 3], closed)"""
+        pts, rec = Mesh._host(self.points), Mesh._host(self.polylines)
+        return [(pts[first:first + count], bool(closed)) for first, count, plane, closed in rec.tolist() if plane == w]
+
+    def write_svg(self, path, w, stroke=None):
+        """slice w as an SVG drawing, u to the right and v up: one path per polyline (9 significant digits: float32 round-trips), closed ones
+        ending in Z; filled by the even-odd rule, so that holes stay open"""
+        u, v = (self.axis + 1) % 3, (self.axis + 2) % 3
+        pts = Mesh._host(self.points)
+        lines = self.layer(w)
+        if len(pts):
+            lo, hi = pts[:, [u, v]].min(axis=0).astype(float), pts[:, [u, v]].max(axis=0).astype(float)
+        else:
+            lo, hi = np.zeros(2), np.ones(2)
+        size = np.maximum(hi - lo, 1e-9)
+        width = float(stroke) if stroke is not None else float(size.max()) / 400.0
+        with open(path, "w") as f:
+            f.write('<svg xmlns="http://www.w3.org/2000/svg" viewBox="%.9g %.9g %.9g %.9g">\n' % (lo[0], -hi[1], size[0], size[1]))
+            f.write('<g transform="scale(1,-1)" fill="#ccc" fill-rule="evenodd" stroke="#000" stroke-width="%.9g">\n' % width)
+            for p, closed in lines:
+                d = " L ".join("%.9g %.9g" % (float(q[u]), float(q[v])) for q in p)
+                f.write('<path d="M %s%s"%s/>\n' % (d, " Z" if closed else "", "" if closed else ' fill="none"'))
+            f.write("</g>\n</svg>\n")
+
+
+def _read_slices(handle, like, materials):
+    """an ft_slices -> Contours of numpy arrays (like = None) or of tensors of like's device, through ft_slices_read; the handle is destroyed"""
+    try:
+        info = _lib.SlicesInfo()
+        check(lib.ft_slices_get_info(handle, C.byref(info)))
+        n, m = int(info.n_points), int(info.n_polylines)
+        parts = (_empty(like, (n, 3)), _empty(like, (m, 4), "int32"), _empty(like, (n, 3)) if info.has_normal else None,
+                 _empty(like, (n,), "int32") if info.has_material else None)
+        ptr = _hptr if like is None else (lambda a: None if a is None else _dptr(a.data_ptr()))
+        check(lib.ft_slices_read(handle, *map(ptr, parts)))
+        return Contours(*parts, skipped=info.n_skipped, closed=info.n_closed, axis=info.axis, slices=info.n_slices, materials=materials)
+    finally:
+        lib.ft_slices_destroy(handle)
 
 
 def _torch_int32(t):
@@ -1212,6 +1304,22 @@ class DeviceScene:
         with (self.device.on_current_stream(like) if like is not None else contextlib.nullcontext()):
             check(lib.ft_mesh_lattice(self.device._ctx, self._scene, C.byref(lat), float(iso), eps, flags, C.byref(handle)))
             return _read_mesh(handle, like, self.materials)
+
+    def slice_lattice(self, origin, step, counts, axis=2, iso=0.0, normal_epsilon=None, material=False, like=None):
+        """ft_slice_lattice: the contours scene.Object.Form.Distance = iso of every lattice plane normal to `axis` (0, 1, 2: x, y, z), extracted
+        and chained on the device from the distances on lattice_points(origin, step, counts) (never bounded) -> Contours.  normal_epsilon: also
+        SdfForm.normal per point; material: also the handle of the material object.Material.Color picks there (Contours.descriptor) — both
+        exactly what sample_points gives for the points.  like: a device tensor — the Contours then hold tensors of its device, and the launches
+        run on the caller's current stream."""
+        lat, _ = _lattice(origin, step, counts)
+        if like is not None and not is_device_tensor(like):
+            raise ValueError("like: a device tensor (see is_device_tensor) or None")
+        flags = (_lib.FT_SLICE_NORMAL if normal_epsilon is not None else 0) | (_lib.FT_SLICE_MATERIAL if material else 0)
+        eps = float(normal_epsilon) if normal_epsilon is not None else 0.0
+        handle = C.c_void_p()
+        with (self.device.on_current_stream(like) if like is not None else contextlib.nullcontext()):
+            check(lib.ft_slice_lattice(self.device._ctx, self._scene, C.byref(lat), int(axis), float(iso), eps, flags, C.byref(handle)))
+            return _read_slices(handle, like, self.materials)
 
     def sample_points_device(self, d_points_ptr, n, d_distance_ptr=None, d_normal_ptr=None, d_material_ptr=None, normal_epsilon=0.0, flags=0):
         """asynchronous ft_sample_points_device: n points (12 B each) at d_points_ptr -> n float32 distances, n x 3 float32 normals, n int32

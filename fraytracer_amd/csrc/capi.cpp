@@ -14,6 +14,7 @@
 #include "build_hash.h"      // FT_SOURCE_HASH: written by the Makefile (source_hash.py)
 #include "ft_kernels.h"
 #include "ft_mesh.h"
+#include "ft_slice.h"
 #include "scene.hpp"
 
 #ifndef FT_BUILD_KIND
@@ -75,6 +76,10 @@ struct ft_ctx {
     int optOrder = 1;                                      // FT_OPT_ORDER: 1 = frames hand their heavy tiles out first, from the costs the scene's last launch of the same grid recorded; 2 = record only; 0 = off
     int fieldBrick = -1;                                   // brick shape of the lattice launches: -1 by kernel family (launchField), else an index into FT_FIELD_BRICKS (ft_ctx_field_brick: the probe's shapes)
     uint32_t meshTile = FT_MESH_TILE_DEFAULT;              // lattice points per workgroup of the mesher's kernels (ft_ctx_mesh_tile: the probe's tiles)
+    uint32_t sliceTile = FT_SLICE_TILE_DEFAULT;            // items per workgroup of the slicer's tiled kernels (ft_ctx_slice_tile: the tests' and the probe's tiles)
+    int sliceStop = 0;                                     // 0: whole extractions; 1 / 2: they end after the link kernel / the jump rounds, empty (ft_ctx_slice_probe: the probe's stages)
+    int64_t sliceLast[2] = {0, 0};                         // vertices and jump rounds R of the context's last extraction (ft_ctx_slice_probe)
+    void* sliceWork = nullptr; size_t sliceWorkBytes = 0;  // the slicer's per-vertex work (sized after its first totals, when the scratch still holds the lattice)
     uint32_t orderNum = 1, orderDen = 1;                   // a tile is heavy from orderNum / orderDen of the mean cost on (ft_ctx_tile_order_rule: the probes' other rules)
 };
 
@@ -615,6 +620,7 @@ void ft_ctx_destroy(ft_ctx* c) {
         if (c->planes) (void)hipFree(c->planes);
         if (c->aux) (void)hipFree(c->aux);
         if (c->cams) (void)hipFree(c->cams);
+        if (c->sliceWork) (void)hipFree(c->sliceWork);
         for (auto& r : c->hostRegs) (void)hipHostUnregister(r.first);
         for (auto e : c->syncEvents) (void)hipEventDestroy(e);
         if (c->lane1) { (void)hipStreamSynchronize(c->lane1); (void)hipStreamDestroy(c->lane1); }
@@ -1787,6 +1793,247 @@ void ft_mesh_destroy(ft_mesh* m) {
 int ft_ctx_mesh_tile(ft_ctx* c, int32_t tile) {
     if (!c || (tile != 128 && tile != 256 && tile != 512 && tile != 1024)) return setErr(FT_ERR_INVALID, "bad argument");
     c->meshTile = (uint32_t)tile;
+    return FT_OK;
+}
+
+// ---- slicing: ft_slice_lattice, ft_slice_values, ft_slice_values_device and what reads the contours (slice.hip; the rule is the header's "Slicing") ----
+struct ft_slices {
+    ft_ctx* ctx = nullptr;
+    int64_t nP = 0, nL = 0, nClosed = 0, nSkipped = 0;
+    int32_t axis = 0, nSlices = 0;
+    bool hasNormal = false, hasMaterial = false;
+    void* dPoints = nullptr; void* dPolylines = nullptr; void* dNormals = nullptr; void* dMaterials = nullptr;
+};
+
+namespace {
+
+struct SliceRequest { const ft_scene* s; const ft_lattice* lat; const void* values; int32_t axis; float iso, eps; uint32_t flags; ft_slices** out; };
+
+// Everything that can be refused without a device, in the header's order (the mesher's, with the axis between the counts and the flag bits).  *nothing: a
+// count of 1 in the plane, FT_OK with an empty result and nothing to launch.
+int checkSlice(const ft_ctx* c, const SliceRequest& r, MeshForm form, bool* nothing) {
+    static_assert(sizeof(ft_polyline) == 16 && sizeof(ft_slices_info) == 48, "layout");
+    *nothing = false;
+    if (r.out) *r.out = nullptr;
+    if (!c) return setErr(FT_ERR_INVALID, "null context");
+    if (form == MeshForm::Scene && (!r.s || r.s->ctx != c)) return setErr(FT_ERR_INVALID, "bad argument (scene must belong to this context)");
+    if (!r.lat) return setErr(FT_ERR_INVALID, "null lattice");
+    if (form != MeshForm::Scene && !r.values) return setErr(FT_ERR_INVALID, "slice: null values");
+    if (!r.out) return setErr(FT_ERR_INVALID, "null out pointer");
+    const int32_t cnt[3] = {r.lat->nx, r.lat->ny, r.lat->nz};
+    for (int32_t v : cnt) if (v < 1 || v > 16777216) return setErr(FT_ERR_INVALID, "lattice: every count must be 1 .. 16777216");
+    if (r.axis < 0 || r.axis > 2) return setErr(FT_ERR_INVALID, "slice: the axis must be 0, 1 or 2");
+    if (r.flags & ~(uint32_t)(FT_SLICE_NORMAL | FT_SLICE_MATERIAL)) return setErr(FT_ERR_INVALID, "slice: unknown flag bits");
+    if (form == MeshForm::DeviceValues && (reinterpret_cast<uintptr_t>(r.values) & 3u)) return setErr(FT_ERR_INVALID, "slice: the device values must be 4-byte aligned");
+    // three counts of at most 2^24: the product of two fits 2^48, and the third is applied only below the limit
+    const uint64_t two = (uint64_t)r.lat->nx * (uint64_t)r.lat->ny;
+    if (two >= 0xFFFF0000ull || two * (uint64_t)r.lat->nz >= 0xFFFF0000ull) return setErr(FT_ERR_UNSUPPORTED, "more than 2^32 points in one call");
+    *nothing = cnt[(r.axis + 1) % 3] == 1 || cnt[(r.axis + 2) % 3] == 1;
+    return FT_OK;
+}
+
+// the lattice passes' work behind `at` bytes of the context's scratch: 5 B per point and 12 B per tile, as the mesher's
+struct SliceWork { size_t mask, vbase, tileA, tileB, tileC, totals, end; };
+SliceWork sliceWork(size_t at, size_t n, size_t nTiles) {
+    SliceWork w{};
+    w.mask = align256(at); w.vbase = align256(w.mask + n); w.tileA = align256(w.vbase + 4 * n); w.tileB = align256(w.tileA + 4 * nTiles);
+    w.tileC = align256(w.tileB + 4 * nTiles); w.totals = align256(w.tileC + 4 * nTiles); w.end = w.totals + 256;
+    return w;
+}
+
+const char* const kSliceKernels[FT_SLICE_KERNELS] = {"slice count", "slice scan", "slice emit", "slice link", "slice lead", "slice jump", "slice cut", "slice tail",
+                                                     "slice heads", "slice vertex scan", "slice records", "slice scatter"};
+// the workgroups of one launch: `items` tiles, or vertices in the untiled kernels
+int sliceBlocks(ft_ctx* c, int kernel, const FtSliceArgs& a, uint64_t items, unsigned* blocks) {
+    int perCU = 0;
+    const hipError_t e = ft_slice_occupancy(kernel, a.tile, &perCU);
+    if (e != hipSuccess) return hipFail(e, (std::string("occupancy of the ") + kSliceKernels[kernel] + " kernel").c_str());
+    int rc = clampPerCU(c, kSliceKernels[kernel], perCU); if (rc) return rc;
+    const unsigned flat = ft_slice_block(kernel, 0u);                  // 0 for the tiled kernels: their workgroup is the tile
+    const uint64_t want = flat ? (items + flat - 1) / flat : items;
+    *blocks = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)c->numCUs * perCU, want));
+    return FT_OK;
+}
+int launchSlice(ft_ctx* c, int kernel, const FtSliceArgs& a, uint64_t items) {
+    unsigned blocks = 1;
+    int rc = sliceBlocks(c, kernel, a, items, &blocks); if (rc) return rc;
+    return timedLaunch(c, c->stream, "ft_launch_slice", [&] { return ft_launch_slice(kernel, &a, blocks, c->stream); });
+}
+// `first` (lead or cut) and the jump rounds behind it, under one event pair; a's from / to end up swapped where the rounds are odd
+int launchSliceRounds(ft_ctx* c, int first, FtSliceArgs& a, unsigned rounds) {
+    unsigned b0 = 1, b1 = 1;
+    int rc;
+    if ((rc = sliceBlocks(c, first, a, a.nV, &b0)) || (rc = sliceBlocks(c, FT_SLICE_K_JUMP, a, a.nV, &b1))) return rc;
+    rc = timedLaunch(c, c->stream, "ft_launch_slice_jumps", [&] {
+        const hipError_t e = ft_launch_slice(first, &a, b0, c->stream);
+        return e != hipSuccess ? e : ft_launch_slice_jumps(&a, rounds, b1, c->stream);
+    });
+    if (rc == FT_OK && (rounds & 1u)) std::swap(a.from, a.to);
+    return rc;
+}
+
+// The extraction: values (device memory, n floats) -> m's points and polylines.  Synchronises the context's stream twice: for the vertex and segment
+// totals (the per-vertex work is sized from them) and for the point and polyline totals (the outputs are).
+int extractSlices(ft_ctx* c, const ft_lattice& l, const float* dValues, int32_t axis, float iso, const SliceWork& w, ft_slices* m) {
+    FtSliceArgs a{};
+    a.values = dValues; a.iso = iso; a.axis = (uint32_t)axis;
+    a.nx = (uint32_t)l.nx; a.ny = (uint32_t)l.ny; a.nz = (uint32_t)l.nz;
+    a.n = a.nx * a.ny * a.nz;                                          // below 0xFFFF0000 (checkSlice)
+    a.tile = c->sliceTile;
+    a.nTiles = (uint32_t)(((uint64_t)a.n + a.tile - 1u) / a.tile);
+    a.origin[0] = l.origin.x; a.origin[1] = l.origin.y; a.origin[2] = l.origin.z;
+    a.step[0] = l.step.x; a.step[1] = l.step.y; a.step[2] = l.step.z;
+    unsigned char* base = static_cast<unsigned char*>(c->scratch);
+    a.mask = base + w.mask; a.vbase = reinterpret_cast<uint32_t*>(base + w.vbase);
+    a.tileA = reinterpret_cast<uint32_t*>(base + w.tileA); a.tileB = reinterpret_cast<uint32_t*>(base + w.tileB); a.tileC = reinterpret_cast<uint32_t*>(base + w.tileC);
+    a.totals = reinterpret_cast<unsigned long long*>(base + w.totals);
+    int rc;
+    if ((rc = launchSlice(c, FT_SLICE_K_COUNT, a, a.nTiles)) || (rc = launchSlice(c, FT_SLICE_K_SCAN, a, 1))) return rc;
+    unsigned long long totals[3] = {0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(totals, a.totals, sizeof totals, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));                          // the first synchronisation: vertices, segments, skipped triangles
+    m->nSkipped = (int64_t)totals[2];
+    if (totals[0] >= (1ull << 31)) return setErr(FT_ERR_UNSUPPORTED, "slice: 2^31 or more points or polylines (the index type is int32)");
+    if (!totals[0] || !totals[1]) return FT_OK;                        // no segment: no polyline
+    const size_t nV = (size_t)totals[0], nVT = (nV + a.tile - 1) / a.tile;
+    a.nV = (uint32_t)nV; a.nVTiles = (uint32_t)nVT;
+    // the per-vertex work: 12 + 11 * 4 + 1 B per vertex, 12 B per tile of vertices
+    size_t at = 0;
+    auto take = [&](size_t bytes) { const size_t o = at; at = align256(at + bytes); return o; };
+    const size_t oPos = take(nV * 12), oSlice = take(nV * 4), oNext = take(nV * 4), oPrev = take(nV * 4), oLen = take(nV * 4), oOff = take(nV * 4);
+    size_t oState[6];
+    for (size_t& o : oState) o = take(nV * 4);
+    const size_t oCyc = take(nV), oA = take(nVT * 4), oB = take(nVT * 4), oC = take(nVT * 4), oTotals = take(256);
+    if ((rc = ensureBytes(c->sliceWork, c->sliceWorkBytes, at))) return rc;
+    unsigned char* wk = static_cast<unsigned char*>(c->sliceWork);
+    auto words = [&](size_t o) { return reinterpret_cast<uint32_t*>(wk + o); };
+    a.vpos = reinterpret_cast<float*>(wk + oPos); a.vslice = words(oSlice); a.next = words(oNext); a.prev = words(oPrev); a.len = words(oLen); a.off = words(oOff);
+    a.from = FtSliceState{words(oState[0]), words(oState[1]), words(oState[2])};
+    a.to = FtSliceState{words(oState[3]), words(oState[4]), words(oState[5])};
+    a.cyc = wk + oCyc; a.vtA = words(oA); a.vtB = words(oB); a.vtC = words(oC);
+    a.vtotals = reinterpret_cast<unsigned long long*>(wk + oTotals);
+    HIP_TRY(hipMemsetAsync(a.next, 0xff, oLen - oNext, c->stream));     // next and prev, adjacent: FT_SLICE_NONE
+    HIP_TRY(hipMemsetAsync(a.len, 0, nV * 4, c->stream));
+    if ((rc = launchSlice(c, FT_SLICE_K_EMIT, a, a.nTiles)) || (rc = launchSlice(c, FT_SLICE_K_LINK, a, a.nTiles))) return rc;
+    unsigned rounds = 0;
+    while (((uint64_t)1 << rounds) < (uint64_t)nV) ++rounds;          // 2^rounds >= the vertex total: a window of that many hops covers any cycle
+    c->sliceLast[0] = (int64_t)nV; c->sliceLast[1] = (int64_t)rounds;
+    if (c->sliceStop == 1) return FT_OK;
+    if ((rc = launchSliceRounds(c, FT_SLICE_K_LEAD, a, rounds)) || (rc = launchSliceRounds(c, FT_SLICE_K_CUT, a, rounds))) return rc;
+    if (c->sliceStop == 2) return FT_OK;
+    if ((rc = launchSlice(c, FT_SLICE_K_TAIL, a, nV)) || (rc = launchSlice(c, FT_SLICE_K_HEADS, a, nVT)) || (rc = launchSlice(c, FT_SLICE_K_VSCAN, a, 1))) return rc;
+    HIP_TRY(hipMemcpyAsync(totals, a.vtotals, sizeof totals, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));                          // the second synchronisation: polylines, points, closed polylines
+    if (totals[0] >= (1ull << 31) || totals[1] >= (1ull << 31)) return setErr(FT_ERR_UNSUPPORTED, "slice: 2^31 or more points or polylines (the index type is int32)");
+    m->nL = (int64_t)totals[0]; m->nP = (int64_t)totals[1]; m->nClosed = (int64_t)totals[2];
+    if (!m->nL) return FT_OK;
+    HIP_TRY(hipMalloc(&m->dPoints, (size_t)m->nP * 12));
+    HIP_TRY(hipMalloc(&m->dPolylines, (size_t)m->nL * sizeof(ft_polyline)));
+    a.points = static_cast<float*>(m->dPoints); a.polylines = static_cast<int32_t*>(m->dPolylines);
+    a.nP = (uint32_t)m->nP; a.nL = (uint32_t)m->nL;
+    if ((rc = launchSlice(c, FT_SLICE_K_RECORDS, a, nVT)) || (rc = launchSlice(c, FT_SLICE_K_SCATTER, a, nV))) return rc;
+    return FT_OK;
+}
+
+int buildSlices(ft_ctx* c, const SliceRequest& r, MeshForm form) {
+    bool nothing;
+    int rc = checkSlice(c, r, form, &nothing); if (rc) return rc;
+    ft_slices* m = new ft_slices();
+    m->ctx = c;
+    m->axis = r.axis;
+    m->nSlices = r.axis == 0 ? r.lat->nx : (r.axis == 1 ? r.lat->ny : r.lat->nz);
+    m->hasNormal = (r.flags & FT_SLICE_NORMAL) != 0u; m->hasMaterial = (r.flags & FT_SLICE_MATERIAL) != 0u;
+    if (nothing) { *r.out = m; return FT_OK; }
+    auto fail = [&](int code) { if (c->hasDevice) (void)hipStreamSynchronize(c->stream); ft_slices_destroy(m); return code; };
+    if ((rc = requireDevice(c))) return fail(rc);
+    const ft_lattice& l = *r.lat;
+    const size_t n = (size_t)l.nx * l.ny * l.nz, tile = c->sliceTile, nTiles = (n + tile - 1) / tile;
+    const SliceWork w = sliceWork(form == MeshForm::DeviceValues ? 0 : n * 4, n, nTiles);
+    if ((rc = ensureScratch(c, w.end))) return fail(rc);
+    const float* dValues = form == MeshForm::DeviceValues ? static_cast<const float*>(r.values) : static_cast<const float*>(c->scratch);
+    if (form == MeshForm::HostValues) {
+        const hipError_t e = hipMemcpyAsync(c->scratch, r.values, n * 4, hipMemcpyHostToDevice, c->stream);
+        if (e != hipSuccess) return fail(hipFail(e, "slice: upload"));
+    } else if (form == MeshForm::Scene) {
+        if ((rc = launchField(c, r.s, FieldRequest{nullptr, 0, r.lat, 0.0f, 0u, c->scratch, nullptr, nullptr}))) return fail(rc);
+    }
+    if ((rc = extractSlices(c, l, dValues, r.axis, r.iso, w, m))) return fail(rc);
+    if (form == MeshForm::Scene && m->nP && (m->hasNormal || m->hasMaterial)) {
+        hipError_t e = hipSuccess;
+        if (m->hasNormal) e = hipMalloc(&m->dNormals, (size_t)m->nP * 12);
+        if (e == hipSuccess && m->hasMaterial) e = hipMalloc(&m->dMaterials, (size_t)m->nP * 4);
+        if (e != hipSuccess) return fail(hipFail(e, "hipMalloc"));
+        // one points-form launch over the finished point buffer: what ft_sample_points_device gives for those points
+        if ((rc = launchField(c, r.s, FieldRequest{m->dPoints, m->nP, nullptr, r.eps, 0u, nullptr, m->dNormals, m->dMaterials}))) return fail(rc);
+    }
+    *r.out = m;
+    return FT_OK;
+}
+
+}  // namespace
+
+int ft_slice_lattice(ft_ctx* c, const ft_scene* s, const ft_lattice* lattice, int32_t axis, float iso, float normal_epsilon, uint32_t flags, ft_slices** out) {
+    return buildSlices(c, SliceRequest{s, lattice, nullptr, axis, iso, normal_epsilon, flags, out}, MeshForm::Scene);
+}
+int ft_slice_values_device(ft_ctx* c, const ft_lattice* lattice, const void* d_values, int32_t axis, float iso, ft_slices** out) {
+    return buildSlices(c, SliceRequest{nullptr, lattice, d_values, axis, iso, 0.0f, 0u, out}, MeshForm::DeviceValues);
+}
+int ft_slice_values(ft_ctx* c, const ft_lattice* lattice, const float* values, int32_t axis, float iso, ft_slices** out) {
+    return buildSlices(c, SliceRequest{nullptr, lattice, values, axis, iso, 0.0f, 0u, out}, MeshForm::HostValues);
+}
+int ft_slices_get_info(const ft_slices* m, ft_slices_info* o) {
+    if (!m || !o) return setErr(FT_ERR_INVALID, "null argument");
+    o->n_points = m->nP; o->n_polylines = m->nL; o->n_closed = m->nClosed; o->n_skipped = m->nSkipped;
+    o->axis = m->axis; o->n_slices = m->nSlices;
+    o->has_normal = m->hasNormal ? 1 : 0; o->has_material = m->hasMaterial ? 1 : 0;
+    return FT_OK;
+}
+int ft_slices_device_buffers(const ft_slices* m, void** d_points, void** d_polylines, void** d_normals, void** d_materials) {
+    if (!m) return setErr(FT_ERR_INVALID, "null slices");
+    if (d_points) *d_points = m->dPoints;
+    if (d_polylines) *d_polylines = m->dPolylines;
+    if (d_normals) *d_normals = m->dNormals;
+    if (d_materials) *d_materials = m->dMaterials;
+    return FT_OK;
+}
+int ft_slices_read(const ft_slices* m, ft_vec3* points, ft_polyline* polylines, ft_vec3* normals, int32_t* materials) {
+    if (!m) return setErr(FT_ERR_INVALID, "null slices");
+    if ((normals && !m->hasNormal) || (materials && !m->hasMaterial)) return setErr(FT_ERR_INVALID, "slice: built without the normals or materials asked for");
+    if (!m->ctx->hasDevice) return FT_OK;                              // an empty result of a host-only context: nothing to copy
+    int rc = requireDevice(m->ctx); if (rc) return rc;
+    const struct { void* host; const void* dev; size_t bytes; } parts[4] = {
+        {points, m->dPoints, (size_t)m->nP * 12}, {polylines, m->dPolylines, (size_t)m->nL * sizeof(ft_polyline)},
+        {normals, m->dNormals, (size_t)m->nP * 12}, {materials, m->dMaterials, (size_t)m->nP * 4}};
+    hipError_t e = hipSuccess;
+    for (const auto& p : parts)
+        if (e == hipSuccess && p.host && p.dev && p.bytes) e = hipMemcpyAsync(p.host, p.dev, p.bytes, hipMemcpyDefault, m->ctx->stream);      // host or device destination
+    const hipError_t se = hipStreamSynchronize(m->ctx->stream);        // nothing of the call is left in flight, whatever happened
+    if (e != hipSuccess) return hipFail(e, "ft_slices_read");
+    if (se != hipSuccess) return hipFail(se, "ft_slices_read");
+    return FT_OK;
+}
+void ft_slices_destroy(ft_slices* m) {
+    if (!m) return;
+    if (m->ctx->hasDevice && (m->dPoints || m->dPolylines || m->dNormals || m->dMaterials)) {
+        (void)hipSetDevice(m->ctx->device);
+        for (void* p : {m->dPoints, m->dPolylines, m->dNormals, m->dMaterials}) if (p) (void)hipFree(p);      // waits for whatever still uses it
+    }
+    delete m;
+}
+// Internal (not in the header, like ft_ctx_mesh_tile; tools/slice_probe.py and the tests): the items per workgroup of this context's slicer launches, one
+// of 128, 256, 512, 1024.  Every tile gives the same contours.
+int ft_ctx_slice_tile(ft_ctx* c, int32_t tile) {
+    if (!c || (tile != 128 && tile != 256 && tile != 512 && tile != 1024)) return setErr(FT_ERR_INVALID, "bad argument");
+    c->sliceTile = (uint32_t)tile;
+    return FT_OK;
+}
+// Internal (tools/slice_probe.py): stop = 0 whole extractions, 1 / 2 this context's extractions end after the link kernel / after the jump rounds and
+// give an empty result, so that a stage's kernel time is a difference of two figures; last (may be NULL): the vertices and the jump rounds R of the
+// context's last extraction.
+int ft_ctx_slice_probe(ft_ctx* c, int32_t stop, int64_t* last) {
+    if (!c || stop < 0 || stop > 2) return setErr(FT_ERR_INVALID, "bad argument");
+    c->sliceStop = stop;
+    if (last) { last[0] = c->sliceLast[0]; last[1] = c->sliceLast[1]; }
     return FT_OK;
 }
 

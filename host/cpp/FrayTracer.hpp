@@ -327,6 +327,45 @@ inline Triangles ofValues(ft_ctx* ctx, const ft_lattice& lattice, const std::vec
 }
 }  // namespace Mesh
 
+// The contours {distance = iso} of every lattice plane normal to `axis` as ordered polylines, extracted and chained on the device (ft_slice_lattice;
+// the header's "Slicing" states the rule).  polylines: points [first, first + count) of slice `slice`, closed (a loop: counter-clockwise seen from
+// +axis around the inside, clockwise around a hole) or open; normal and material per point where asked for
+namespace Slice {
+struct Contours {
+    std::vector<ft_vec3> points; std::vector<ft_polyline> polylines; std::vector<ft_vec3> normal; std::vector<int32_t> material;
+    int64_t closed = 0, skipped = 0; int32_t axis = 2, slices = 0;
+};
+struct Request { int32_t axis = 2; float iso = 0.0f; bool normal = false; float normalEpsilon = 0.0f; bool material = false; };
+inline Contours read(ft_slices* slices) {
+    struct Owner { ft_slices* s; ~Owner() { ft_slices_destroy(s); } } own{slices};
+    ft_slices_info info{};
+    check(ft_slices_get_info(slices, &info));
+    Contours out;
+    out.closed = info.n_closed; out.skipped = info.n_skipped; out.axis = info.axis; out.slices = info.n_slices;
+    out.points.resize((size_t)info.n_points);
+    out.polylines.resize((size_t)info.n_polylines);
+    if (info.has_normal) out.normal.resize((size_t)info.n_points);
+    if (info.has_material) out.material.resize((size_t)info.n_points);
+    check(ft_slices_read(slices, out.points.data(), out.polylines.data(), info.has_normal ? out.normal.data() : nullptr,
+                         info.has_material ? out.material.data() : nullptr));
+    return out;
+}
+inline Contours ofLattice(const SdfScene& scene, const ft_lattice& lattice, const Request& r = Request{}) {
+    SceneOfCall s(scene);
+    ft_slices* slices = nullptr;
+    s.done(ft_slice_lattice(s.ctx, s.get(), &lattice, r.axis, r.iso, r.normalEpsilon, (r.normal ? FT_SLICE_NORMAL : 0u) | (r.material ? FT_SLICE_MATERIAL : 0u), &slices),
+           nullptr);
+    return read(slices);
+}
+// any float32 lattice already in host memory: nx * ny * nz values, k contiguous (ft_slice_values)
+inline Contours ofValues(ft_ctx* ctx, const ft_lattice& lattice, const std::vector<float>& values, int32_t axis = 2, float iso = 0.0f) {
+    if (values.size() != (size_t)lattice.nx * (size_t)lattice.ny * (size_t)lattice.nz) throw std::invalid_argument("Slice::ofValues: one value per lattice point");
+    ft_slices* slices = nullptr;
+    check(ft_slice_values(ctx, &lattice, values.data(), axis, iso, &slices));
+    return read(slices);
+}
+}  // namespace Slice
+
 // SdfObject.tryTrace / SdfForm.tryTrace (SdfObject.fs:66-78, SdfForm.fs:93-104) over a ray buffer; hit == 0 is ValueNone
 inline std::vector<ft_object_trace_result> tryTrace(const SdfObjectV& object, const std::vector<ft_ray>& rays) {
     SceneOfCall s(object);

@@ -50,6 +50,12 @@ type FtLattice = { Origin : Vector3; Step : Vector3; Nx : int; Ny : int; Nz : in
 /// ft_mesh_info (32 bytes)
 [<Struct; StructLayout(LayoutKind.Sequential)>]
 type FtMeshInfo = { NVertices : int64; NTriangles : int64; NSkipped : int64; HasNormal : int; HasMaterial : int }
+/// ft_polyline (16 bytes): points [First, First + Count) of slice Slice; Closed = 1 is a loop
+[<Struct; StructLayout(LayoutKind.Sequential)>]
+type FtPolyline = { First : int; Count : int; Slice : int; Closed : int }
+/// ft_slices_info (48 bytes)
+[<Struct; StructLayout(LayoutKind.Sequential)>]
+type FtSlicesInfo = { NPoints : int64; NPolylines : int64; NClosed : int64; NSkipped : int64; Axis : int; NSlices : int; HasNormal : int; HasMaterial : int }
 
 /// ft_form_trace_result: SdfFormTraceResult voption (Types.fs:32-37), Hit = 0 is ValueNone
 [<Struct; StructLayout(LayoutKind.Sequential)>]
@@ -123,6 +129,16 @@ module Native =
     [<DllImport(Lib)>] extern int ft_mesh_device_buffers(nativeint mesh, nativeint dVertices, nativeint dTriangles, nativeint dNormals, nativeint dMaterials)
     [<DllImport(Lib)>] extern int ft_mesh_read(nativeint mesh, nativeint vertices, nativeint triangles, nativeint normals, nativeint materials)
     [<DllImport(Lib)>] extern void ft_mesh_destroy(nativeint mesh)
+    // slicing: per lattice plane normal to axis (0, 1, 2) the contour {distance = iso} as ordered polylines, chained on the device (the header's
+    // "Slicing" states the rule).  slices: a plain nativeint out-parameter, as mesh above; flags 1u = per-point normals, 2u = materials;
+    // ft_slices_read copies to pinned arrays (Vector3[], FtPolyline[]; 0n: that part is not asked for); the contours outlive their scene, not their context
+    [<DllImport(Lib)>] extern int ft_slice_lattice(nativeint ctx, nativeint scene, nativeint lattice, int axis, float32 iso, float32 normalEpsilon, uint32 flags, nativeint slices)
+    [<DllImport(Lib)>] extern int ft_slice_values(nativeint ctx, nativeint lattice, nativeint values, int axis, float32 iso, nativeint slices)
+    [<DllImport(Lib)>] extern int ft_slice_values_device(nativeint ctx, nativeint lattice, nativeint dValues, int axis, float32 iso, nativeint slices)
+    [<DllImport(Lib)>] extern int ft_slices_get_info(nativeint slices, nativeint info)
+    [<DllImport(Lib)>] extern int ft_slices_device_buffers(nativeint slices, nativeint dPoints, nativeint dPolylines, nativeint dNormals, nativeint dMaterials)
+    [<DllImport(Lib)>] extern int ft_slices_read(nativeint slices, nativeint points, nativeint polylines, nativeint normals, nativeint materials)
+    [<DllImport(Lib)>] extern void ft_slices_destroy(nativeint slices)
     [<DllImport(Lib)>] extern int ft_form_try_trace(nativeint ctx, nativeint scene, Ray[] rays, int64 n, [<Out>] FtFormTraceResult[] out, FtStats& stats)
     [<DllImport(Lib)>] extern int ft_object_try_trace(nativeint ctx, nativeint scene, Ray[] rays, int64 n, [<Out>] FtObjectTraceResult[] out, FtStats& stats)
     // ray buffers in device memory (rays 16-byte aligned, 32 B each): no scratch, no copy, not synchronised; pair with ft_collect_stats

@@ -485,6 +485,65 @@ int ft_mesh_device_buffers(const ft_mesh*, void** d_vertices, void** d_triangles
 int ft_mesh_read(const ft_mesh*, ft_vec3* vertices, int32_t* triangles, ft_vec3* normals, int32_t* materials);
 void ft_mesh_destroy(ft_mesh*);
 
+/* Slicing: per lattice plane the contour {distance = iso} of a lattice of distances as ordered, consistently oriented polylines, extracted and
+ * chained on the device.  A slice is exactly the section of the mesher's surface by a lattice plane: the Kuhn subdivision of a cell, restricted to a
+ * cell face, is the face's two triangles split by the (0,0)-(1,1) diagonal.  The result is a pure function of the lattice's values; this is the rule,
+ * every bit of it.  What it shares with "Meshing" above is stated there.
+ *
+ * Input: a lattice, a float32 value d[q] per point and a level iso as in "Meshing", and an axis a in {0, 1, 2} (x, y, z), the planes' normal.
+ * Planes: slice w, 0 <= w < n_a, is the 2D lattice of the points whose index along a is w.  Its in-plane axes are u = (a + 1) % 3 and
+ *     v = (a + 2) % 3, so (u, v, a) is right-handed.  A count of 1 along a is one slice.  A count of 1 along u or v leaves no cells: FT_OK, an empty
+ *     result, no device needed.
+ * Signed value and inside: the mesher's, s[q] = d[q] - iso, inside iff s[q] < 0.
+ * Edges: the mesher's seven directions and their numbers e, of which each plane uses the three with no component along a, +v, +u and +u+v:
+ *     e 0, 1, 2 for axis 0; 0, 3, 4 for axis 1; 1, 3, 5 for axis 2.
+ * Vertices: ownership, the existence rule and the position are the mesher's, operation for operation, all three coordinates: a contour point is
+ *     bit for bit the vertex the mesher puts on the same edge.  A vertex's key is (q, e) with the mesher's e; keys order by q, then e.
+ * Triangles: cell (cu, cv) of slice w, with c0 its point of smallest indices, is cut in two, in this order: T0 = {c0, c0 + u, c0 + u + v}, then
+ *     T1 = {c0, c0 + v, c0 + u + v}.  A triangle with a non-finite corner value emits nothing and is counted in n_skipped.  A triangle with one or
+ *     two corners inside emits one segment, between the vertices of its two crossing edges.
+ * Direction is combinatorial: decided from the integer (u, v) corner offsets alone, never from floats or the sign of a step.  With u to the right and
+ *     v up, the inside corners lie to the segment's left: with L the corner that differs from the other two, M1 and M2, the segment runs from the
+ *     vertex on (L, M1) to the one on (L, M2) iff (det(M2 - M1, L - M1) > 0) == (L is inside).  Outer boundaries therefore run counter-clockwise
+ *     seen from +a, and holes run clockwise.  Every vertex is the start of at most one segment and the end of at most one.
+ * Polylines: a polyline is a maximal chain of segments joined at shared vertices.  Closed: a cycle of m segments, written as its m points, starting
+ *     at the vertex of smallest key and following the segments' direction.  Open: a chain whose first vertex no segment ends in (where the contour
+ *     leaves the lattice or meets a skipped triangle), written as its m + 1 points from that vertex to the last.  A vertex that no segment uses is
+ *     not written.  Polylines are ordered by the key of their first point, and each carries the slice it lies in: for axis 0 that order is already
+ *     slice by slice; for axes 1 and 2 it is not, and ft_polyline.slice tells them apart.
+ * Consequences: on an all-finite lattice every polyline is closed unless it ends on the lattice's border; a value of exactly iso gives zero-length
+ *     segments but keeps loops closed.  Counts and indices are int32: 2^31 or more points or polylines is FT_ERR_UNSUPPORTED.
+ *
+ * Lifetime and forms are the mesher's, item for item: ft_slice_lattice evaluates the scene's distance on the lattice into the context's scratch
+ * (never FT_FIELD_BOUNDED), then extracts; FT_SLICE_NORMAL and FT_SLICE_MATERIAL add per point SdfForm.normal (normal_epsilon, read only with
+ * FT_SLICE_NORMAL) and the material handle from one points-form field launch over the finished point buffer: exactly what
+ * ft_sample_points_device gives for those points.  ft_slice_values / ft_slice_values_device slice any float32 lattice already in host / device
+ * memory (the device pointer 4-byte aligned; the values are only read): no scene, no normals, no materials.
+ * The extraction cannot size its outputs before it has counted: each constructor synchronises the context's stream TWICE, once to read the vertex
+ * and segment totals (the chaining's work is sized from them) and once to read the point and polyline totals; then it allocates exactly and writes
+ * the points and the records on the context's stream without synchronising again (ft_slices_read does).  The chaining is pointer doubling, R rounds
+ * with 2^R at least the vertex total, run twice and launched without a synchronisation between them; nothing is written at or beyond the counted
+ * totals.  Scratch: as the mesher's for the lattice; 57 B per vertex and 12 B per tile of vertices of chaining work that the context keeps.
+ * Refusals, all made before the device is asked for, in the mesher's order, with an axis outside 0 .. 2 (FT_ERR_INVALID) after the counts and
+ * before the flag bits.  On any failure *out is NULL.
+ * The contours own device memory of their context: they outlive their scene but not their context.  ft_slices_read copies to the caller's buffers
+ * (n_points x 3 float32, n_polylines x ft_polyline, n_points x 3 float32, n_points x int32; host or device memory: the direction of each copy is
+ * taken from the address), synchronises the context's stream and accepts NULL for any part; asking for normals or materials the contours were not
+ * built with is FT_ERR_INVALID.  ft_slices_device_buffers gives the device addresses (NULL for a part that is missing or empty); each of its
+ * out-parameters may be NULL. */
+#define FT_SLICE_NORMAL 1u
+#define FT_SLICE_MATERIAL 2u
+typedef struct ft_slices ft_slices;                   /* opaque; owns device memory of its context */
+typedef struct ft_polyline { int32_t first, count, slice, closed; } ft_polyline;   /* 16 B: points [first, first + count) */
+typedef struct ft_slices_info { int64_t n_points, n_polylines, n_closed, n_skipped; int32_t axis, n_slices, has_normal, has_material; } ft_slices_info;  /* 48 B */
+int ft_slice_lattice(ft_ctx*, const ft_scene*, const ft_lattice*, int32_t axis, float iso, float normal_epsilon, uint32_t flags, ft_slices** out);
+int ft_slice_values(ft_ctx*, const ft_lattice*, const float* values, int32_t axis, float iso, ft_slices** out);
+int ft_slice_values_device(ft_ctx*, const ft_lattice*, const void* d_values, int32_t axis, float iso, ft_slices** out);
+int ft_slices_get_info(const ft_slices*, ft_slices_info* out);
+int ft_slices_device_buffers(const ft_slices*, void** d_points, void** d_polylines, void** d_normals, void** d_materials);
+int ft_slices_read(const ft_slices*, ft_vec3* points, ft_polyline* polylines, ft_vec3* normals, int32_t* materials);
+void ft_slices_destroy(ft_slices*);
+
 /* Single-process multi-GPU form (what an F# host would call): the flattened scene is
  * re-uploaded to each further device with ft_scene_clone, every device renders its column
  * stripes (stripe_rank = index in ctxs[], stripe_ranks = n) on its own host thread, and the
