@@ -3,7 +3,7 @@
 distance field is evaluated on a lattice around the scene and the surface is extracted on the GPU (DeviceScene.mesh_lattice), then written as
 Wavefront OBJ (or binary STL).
 
-    python examples/mesh.py [--tori 1000] [--points 256] [--span 1.05] [--normals] [--out scene.obj]
+    python examples/mesh.py [--tori 1000] [--points 256] [--span 1.05] [--normals] [--refine 8] [--out scene.obj]
 """
 import argparse
 import os
@@ -20,6 +20,7 @@ ap.add_argument("--tori", type=int, default=1000)
 ap.add_argument("--points", type=int, default=256, help="lattice points per axis")
 ap.add_argument("--span", type=float, default=1.05, help="half-width of the lattice in boundary radii")
 ap.add_argument("--normals", action="store_true", help="per-vertex SdfForm.normal (epsilon = a hundredth of the lattice step)")
+ap.add_argument("--refine", type=int, default=None, help="bisection rounds (0 .. 32) that move every vertex along its lattice edge onto the surface")
 ap.add_argument("--out", default="scene.obj", help="*.obj or *.stl")
 args = ap.parse_args()
 
@@ -31,7 +32,7 @@ step = 2.0 * half / (args.points - 1)
 
 t0 = time.perf_counter()
 mesh = ds.mesh_lattice((cx - half, cy - half, cz - half), (step,) * 3, (args.points,) * 3,
-                       normal_epsilon=0.01 * step if args.normals else None)
+                       normal_epsilon=0.01 * step if args.normals else None, refine=args.refine)
 print(f"{len(mesh.vertices)} vertices, {len(mesh.triangles)} triangles in {time.perf_counter() - t0:.3f} s")
 (mesh.save_stl if args.out.lower().endswith(".stl") else mesh.save_obj)(args.out)
 print("wrote", args.out)

@@ -3,7 +3,7 @@
 a 3D-printing slicer sees it: the distance field is evaluated on a lattice around the scene, and per lattice plane the contour {distance = 0} is
 extracted and chained into ordered, oriented loops on the GPU (DeviceScene.slice_lattice), then drawn one file per layer.
 
-    python examples/slice.py [--tori 1000] [--points 256] [--layers 64] [--axis 2] [--span 1.05] [--out layers]
+    python examples/slice.py [--tori 1000] [--points 256] [--layers 64] [--axis 2] [--span 1.05] [--refine 8] [--out layers]
 """
 import argparse
 import os
@@ -21,6 +21,7 @@ ap.add_argument("--points", type=int, default=256, help="lattice points per in-p
 ap.add_argument("--layers", type=int, default=64, help="lattice planes along the axis")
 ap.add_argument("--axis", type=int, default=2, choices=(0, 1, 2), help="the planes' normal: 0 x, 1 y, 2 z")
 ap.add_argument("--span", type=float, default=1.05, help="half-width of the lattice in boundary radii")
+ap.add_argument("--refine", type=int, default=None, help="bisection rounds (0 .. 32) that move every vertex along its lattice edge onto the surface")
 ap.add_argument("--out", default="layers", help="directory of the layer_NNNN.svg files")
 args = ap.parse_args()
 
@@ -34,7 +35,7 @@ step = [2.0 * half / (n - 1) if n > 1 else 0.0 for n in counts]
 origin = [c - half if n > 1 else c for c, n in zip((cx, cy, cz), counts)]
 
 t0 = time.perf_counter()
-contours = ds.slice_lattice(origin, step, counts, axis=args.axis)
+contours = ds.slice_lattice(origin, step, counts, axis=args.axis, refine=args.refine)
 print(f"{len(contours.polylines)} polylines ({contours.closed} closed), {len(contours.points)} points in {contours.slices} layers "
       f"in {time.perf_counter() - t0:.3f} s")
 os.makedirs(args.out, exist_ok=True)

@@ -197,6 +197,10 @@ SYMBOLS = {
     "ft_slices_device_buffers": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(_P)]),
     "ft_slices_read": (C.c_int, [_P, _P, _P, _P, _P]),
     "ft_slices_destroy": (None, [_P]),
+    "ft_mesh_lattice_refined": (C.c_int, [_P, _P, C.POINTER(Lattice), C.c_float, C.c_float, C.c_uint32, C.c_int32, C.POINTER(_P)]),
+    "ft_slice_lattice_refined": (C.c_int, [_P, _P, C.POINTER(Lattice), C.c_int32, C.c_float, C.c_float, C.c_uint32, C.c_int32, C.POINTER(_P)]),
+    "ft_refine_segments": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_float, C.c_int32, _P, _P]),
+    "ft_refine_segments_device": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_float, C.c_int32, _P, _P]),
     "ft_scene_clone": (C.c_int, [_P, _P, C.POINTER(_P)]),
     "ft_render_multi": (C.c_int, [C.POINTER(_P), C.POINTER(_P), C.c_int32, C.POINTER(CameraS), C.POINTER(RenderParams), _P, C.POINTER(Stats)]),
     "ft_scene_info_get": (C.c_int, [_P, C.POINTER(SceneInfo)]),

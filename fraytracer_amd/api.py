@@ -161,16 +161,24 @@ class SdfForm:
         return _form_scene(form, device).sample_lattice(origin, step, counts, normal_epsilon=normal_epsilon, bounded=bounded)
 
     @staticmethod
-    def mesh(form, origin, step, counts, iso=0.0, normal_epsilon=None, device=None):
+    def mesh(form, origin, step, counts, iso=0.0, normal_epsilon=None, device=None, refine=None):
         """the surface sdf.Distance = iso as triangles, extracted on the GPU from the lattice lattice_points(origin, step, counts) -> Mesh, with
-        SdfForm.normal per vertex where normal_epsilon is given (DeviceScene.mesh_lattice)"""
-        return _form_scene(form, device).mesh_lattice(origin, step, counts, iso=iso, normal_epsilon=normal_epsilon)
+        SdfForm.normal per vertex where normal_epsilon is given; refine: bisection rounds that move the vertices onto the surface
+        (DeviceScene.mesh_lattice)"""
+        return _form_scene(form, device).mesh_lattice(origin, step, counts, iso=iso, normal_epsilon=normal_epsilon, refine=refine)
 
     @staticmethod
-    def slice(form, origin, step, counts, axis=2, iso=0.0, normal_epsilon=None, device=None):
+    def slice(form, origin, step, counts, axis=2, iso=0.0, normal_epsilon=None, device=None, refine=None):
         """the contours sdf.Distance = iso of every lattice plane normal to `axis`, extracted and chained on the GPU from the lattice
-        lattice_points(origin, step, counts) -> Contours, with SdfForm.normal per point where normal_epsilon is given (DeviceScene.slice_lattice)"""
-        return _form_scene(form, device).slice_lattice(origin, step, counts, axis=axis, iso=iso, normal_epsilon=normal_epsilon)
+        lattice_points(origin, step, counts) -> Contours, with SdfForm.normal per point where normal_epsilon is given; refine: bisection rounds
+        that move the points onto the surface (DeviceScene.slice_lattice)"""
+        return _form_scene(form, device).slice_lattice(origin, step, counts, axis=axis, iso=iso, normal_epsilon=normal_epsilon, refine=refine)
+
+    @staticmethod
+    def crossings(form, a, b, iso=0.0, steps=8, device=None):
+        """where the segments from a [..., 3] to b [..., 3] cross sdf.Distance = iso, by bisection on the GPU -> (points float32 [..., 3], status
+        int32 [...]; status 0: no bracket, the point is NaN) (DeviceScene.refine_segments)"""
+        return _form_scene(form, device).refine_segments(a, b, iso=iso, steps=steps)
 
     @staticmethod
     def normalFromRay(form, rays, device=None):
@@ -1289,12 +1297,13 @@ class DeviceScene:
                            lambda e, f, *o: check(lib.ft_sample_lattice_device(ctx, sc, C.byref(lat), e, f, *map(_dptr, o))),
                            normal_epsilon, distance, material, bounded)
 
-    def mesh_lattice(self, origin, step, counts, iso=0.0, normal_epsilon=None, material=False, like=None):
+    def mesh_lattice(self, origin, step, counts, iso=0.0, normal_epsilon=None, material=False, like=None, refine=None):
         """ft_mesh_lattice: the surface scene.Object.Form.Distance = iso as triangles, extracted on the device from the distances on
         lattice_points(origin, step, counts) (never bounded) -> Mesh.  normal_epsilon: also SdfForm.normal sdf normal_epsilon v per vertex;
         material: also the handle of the material object.Material.Color picks at v (Mesh.descriptor) — both exactly what sample_points gives
         for the vertices.  like: a device tensor — the Mesh then holds tensors of its device, and the launches run on the caller's current
-        stream."""
+        stream.  refine: None, or the bisection rounds (0 .. 32) of ft_mesh_lattice_refined: every vertex moves along its lattice edge onto
+        the surface, to within the edge's length * 2^-refine; triangles are unchanged, normals and materials are taken at the refined vertices."""
         lat, _ = _lattice(origin, step, counts)
         if like is not None and not is_device_tensor(like):
             raise ValueError("like: a device tensor (see is_device_tensor) or None")
@@ -1302,15 +1311,19 @@ class DeviceScene:
         eps = float(normal_epsilon) if normal_epsilon is not None else 0.0
         handle = C.c_void_p()
         with (self.device.on_current_stream(like) if like is not None else contextlib.nullcontext()):
-            check(lib.ft_mesh_lattice(self.device._ctx, self._scene, C.byref(lat), float(iso), eps, flags, C.byref(handle)))
+            if refine is None:
+                check(lib.ft_mesh_lattice(self.device._ctx, self._scene, C.byref(lat), float(iso), eps, flags, C.byref(handle)))
+            else:
+                check(lib.ft_mesh_lattice_refined(self.device._ctx, self._scene, C.byref(lat), float(iso), eps, flags, int(refine), C.byref(handle)))
             return _read_mesh(handle, like, self.materials)
 
-    def slice_lattice(self, origin, step, counts, axis=2, iso=0.0, normal_epsilon=None, material=False, like=None):
+    def slice_lattice(self, origin, step, counts, axis=2, iso=0.0, normal_epsilon=None, material=False, like=None, refine=None):
         """ft_slice_lattice: the contours scene.Object.Form.Distance = iso of every lattice plane normal to `axis` (0, 1, 2: x, y, z), extracted
         and chained on the device from the distances on lattice_points(origin, step, counts) (never bounded) -> Contours.  normal_epsilon: also
         SdfForm.normal per point; material: also the handle of the material object.Material.Color picks there (Contours.descriptor) — both
         exactly what sample_points gives for the points.  like: a device tensor — the Contours then hold tensors of its device, and the launches
-        run on the caller's current stream."""
+        run on the caller's current stream.  refine: None, or the bisection rounds (0 .. 32) of ft_slice_lattice_refined: the points are then the
+        refined mesh vertices of the same edges (mesh_lattice), the polylines unchanged."""
         lat, _ = _lattice(origin, step, counts)
         if like is not None and not is_device_tensor(like):
             raise ValueError("like: a device tensor (see is_device_tensor) or None")
@@ -1318,8 +1331,43 @@ class DeviceScene:
         eps = float(normal_epsilon) if normal_epsilon is not None else 0.0
         handle = C.c_void_p()
         with (self.device.on_current_stream(like) if like is not None else contextlib.nullcontext()):
-            check(lib.ft_slice_lattice(self.device._ctx, self._scene, C.byref(lat), int(axis), float(iso), eps, flags, C.byref(handle)))
+            if refine is None:
+                check(lib.ft_slice_lattice(self.device._ctx, self._scene, C.byref(lat), int(axis), float(iso), eps, flags, C.byref(handle)))
+            else:
+                check(lib.ft_slice_lattice_refined(self.device._ctx, self._scene, C.byref(lat), int(axis), float(iso), eps, flags, int(refine), C.byref(handle)))
             return _read_slices(handle, like, self.materials)
+
+    def refine_segments(self, a, b, iso=0.0, steps=8):
+        """ft_refine_segments: where the segments from a [..., 3] to b [..., 3] cross scene.Object.Form.Distance = iso -> (points float32 [..., 3],
+        status int32 [...]).  status 1: exactly one end is inside (distance - iso < 0) and both distances are finite; the point is then the
+        bracket's interpolation after `steps` (0 .. 32) bisection rounds, within |b - a| * 2^-steps of the surface: a crossing, not
+        necessarily the first.  status 0: the point is three NaN.  Device tensors (see is_device_tensor; float32, contiguous, same shape) are
+        refined where they lie by ft_refine_segments_device on the caller's current stream, and the results are tensors of their device."""
+        ctx, sc = self.device._ctx, self._scene
+        if is_device_tensor(a) or is_device_tensor(b):
+            if not (is_device_tensor(a) and is_device_tensor(b)):
+                raise ValueError("segments: both ends must be device tensors, or neither")
+            lead = check_device_points(a)
+            if check_device_points(b) != lead:
+                raise ValueError(f"segments: the ends' shapes differ: {list(a.shape)} and {list(b.shape)}")
+            n = int(np.prod(lead, dtype=np.int64))
+            points, status = _empty(a, lead + (3,)), _empty(a, lead, "int32")
+            if n:
+                with self.device.on_current_stream(a):
+                    self.refine_segments_device(a.data_ptr(), b.data_ptr(), n, points.data_ptr(), status.data_ptr(), iso=iso, steps=steps)
+            return points, status
+        pa, pb = np.ascontiguousarray(a, dtype=np.float32), np.ascontiguousarray(b, dtype=np.float32)
+        if pa.ndim < 1 or pa.shape[-1] != 3 or pa.shape != pb.shape:
+            raise ValueError(f"segments: both shapes must be the same [..., 3], not {list(pa.shape)} and {list(pb.shape)}")
+        points, status = np.empty(pa.shape, np.float32), np.empty(pa.shape[:-1], np.int32)
+        check(lib.ft_refine_segments(ctx, sc, _hptr(pa), _hptr(pb), pa.size // 3, float(iso), int(steps), _hptr(points), _hptr(status)))
+        return points, status
+
+    def refine_segments_device(self, d_a_ptr, d_b_ptr, n, d_point_ptr=None, d_status_ptr=None, iso=0.0, steps=8):
+        """asynchronous ft_refine_segments_device: n segments (ends 12 B apart at d_a_ptr, d_b_ptr) -> n x 3 float32 points, n int32 status
+        (pointers as int, None = not asked; every buffer 4-byte aligned); on the context's stream, not synchronised"""
+        check(lib.ft_refine_segments_device(self.device._ctx, self._scene, _dptr(d_a_ptr), _dptr(d_b_ptr), n, float(iso), int(steps),
+                                            _dptr(d_point_ptr), _dptr(d_status_ptr)))
 
     def sample_points_device(self, d_points_ptr, n, d_distance_ptr=None, d_normal_ptr=None, d_material_ptr=None, normal_epsilon=0.0, flags=0):
         """asynchronous ft_sample_points_device: n points (12 B each) at d_points_ptr -> n float32 distances, n x 3 float32 normals, n int32

@@ -15,6 +15,7 @@
 #include "ft_kernels.h"
 #include "ft_mesh.h"
 #include "ft_slice.h"
+#include "ft_refine.h"
 #include "scene.hpp"
 
 #ifndef FT_BUILD_KIND
@@ -80,6 +81,8 @@ struct ft_ctx {
     int sliceStop = 0;                                     // 0: whole extractions; 1 / 2: they end after the link kernel / the jump rounds, empty (ft_ctx_slice_probe: the probe's stages)
     int64_t sliceLast[2] = {0, 0};                         // vertices and jump rounds R of the context's last extraction (ft_ctx_slice_probe)
     void* sliceWork = nullptr; size_t sliceWorkBytes = 0;  // the slicer's per-vertex work (sized after its first totals, when the scratch still holds the lattice)
+    void* refineWork = nullptr; size_t refineWorkBytes = 0; // the refinement's per-bracket work (FT_REFINE_ITEM_BYTES each; sized from the vertex total the constructor reads, or from a segment count)
+    int refineSkipField = 0;                               // 1: a refinement launches everything but its field rounds, and gives other positions (ft_ctx_refine_probe: the probe's stages)
     uint32_t orderNum = 1, orderDen = 1;                   // a tile is heavy from orderNum / orderDen of the mean cost on (ft_ctx_tile_order_rule: the probes' other rules)
 };
 
@@ -621,6 +624,7 @@ void ft_ctx_destroy(ft_ctx* c) {
         if (c->aux) (void)hipFree(c->aux);
         if (c->cams) (void)hipFree(c->cams);
         if (c->sliceWork) (void)hipFree(c->sliceWork);
+        if (c->refineWork) (void)hipFree(c->refineWork);
         for (auto& r : c->hostRegs) (void)hipHostUnregister(r.first);
         for (auto e : c->syncEvents) (void)hipEventDestroy(e);
         if (c->lane1) { (void)hipStreamSynchronize(c->lane1); (void)hipStreamDestroy(c->lane1); }
@@ -1626,6 +1630,151 @@ int ft_ctx_field_brick(ft_ctx* c, int32_t shape) {
     return FT_OK;
 }
 
+// ---- refinement: brackets bisected onto the surface (refine.hip; the rule is the header's "Refinement").  What the refined constructors and
+// ft_refine_segments share ----
+namespace {
+
+// the context's refinement work for n brackets: [A x y z | B x y z | sA | sB | M (n x 3) | D(M) | D(b) for segments], every array on a 256-byte boundary
+struct RefineWork { size_t arr[8], mid, dist, distB, end; };
+RefineWork refineWork(size_t n, bool segments) {
+    RefineWork w{};
+    size_t at = 0;
+    auto take = [&](size_t bytes) { const size_t o = at; at = align256(at + bytes); return o; };
+    for (size_t& o : w.arr) o = take(n * 4);
+    w.mid = take(n * 12); w.dist = take(n * 4); w.distB = segments ? take(n * 4) : 0;
+    w.end = at;
+    return w;
+}
+// the argument block over the context's work (already ensured): everything but what says where the brackets come from
+FtRefineArgs refineArgs(ft_ctx* c, const RefineWork& w, size_t n, float iso) {
+    FtRefineArgs g{};
+    unsigned char* wk = static_cast<unsigned char*>(c->refineWork);
+    auto floats = [&](size_t o) { return reinterpret_cast<float*>(wk + o); };
+    for (int ax = 0; ax < 3; ++ax) { g.br.a[ax] = floats(w.arr[ax]); g.br.b[ax] = floats(w.arr[3 + ax]); }
+    g.br.sa = floats(w.arr[6]); g.br.sb = floats(w.arr[7]);
+    g.mid = floats(w.mid); g.dist = floats(w.dist);
+    g.iso = iso; g.nV = (uint32_t)n;
+    return g;
+}
+int launchRefine(ft_ctx* c, int kernel, const FtRefineArgs& g, uint64_t items) {
+    static const char* const names[FT_REFINE_KERNELS] = {"refine lattice", "refine segments", "refine round"};
+    int perCU = 0;
+    const hipError_t e = ft_refine_occupancy(kernel, &perCU);
+    if (e != hipSuccess) return hipFail(e, (std::string("occupancy of the ") + names[kernel] + " kernel").c_str());
+    int rc = clampPerCU(c, names[kernel], perCU); if (rc) return rc;
+    const uint64_t want = (items + FT_REFINE_BLOCK - 1) / FT_REFINE_BLOCK;
+    const unsigned blocks = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)c->numCUs * perCU, want));
+    return timedLaunch(c, c->stream, "ft_launch_refine", [&] { return ft_launch_refine(kernel, &g, blocks, c->stream); });
+}
+// `first` (lattice or segments: it forms the brackets and, with no round, finishes them), then per round one points-form field launch over the midpoint
+// buffer, distance only, and the round kernel; the last round writes the finish into `out` (n x 3).  1 + 2 * steps launches on the context's stream,
+// none synchronised.
+int launchRefinement(ft_ctx* c, const ft_scene* s, int first, uint64_t firstItems, FtRefineArgs g, int32_t steps, float* out) {
+    g.out = out;
+    g.last = steps == 0 ? 1u : 0u;
+    int rc = launchRefine(c, first, g, firstItems); if (rc) return rc;
+    for (int32_t r = 0; r < steps; ++r) {
+        if (!c->refineSkipField && (rc = launchField(c, s, FieldRequest{g.mid, (int64_t)g.nV, nullptr, 0.0f, 0u, const_cast<float*>(g.dist), nullptr, nullptr}))) return rc;
+        g.last = r + 1 == steps ? 1u : 0u;
+        if ((rc = launchRefine(c, FT_REFINE_K_ROUND, g, g.nV))) return rc;
+    }
+    return FT_OK;
+}
+// the brackets of a lattice's owned edges (mask and vbase: what the count and emit passes left in the context's scratch), refined into `out` (nV x 3)
+int refineLattice(ft_ctx* c, const ft_scene* s, const ft_lattice& l, const float* dValues, const uint8_t* mask, const uint32_t* vbase, uint32_t edges,
+                  float iso, size_t nV, int32_t steps, float* out) {
+    FtRefineArgs g = refineArgs(c, refineWork(nV, false), nV, iso);
+    g.values = dValues;
+    g.nx = (uint32_t)l.nx; g.ny = (uint32_t)l.ny; g.nz = (uint32_t)l.nz;
+    g.n = g.nx * g.ny * g.nz;
+    g.origin[0] = l.origin.x; g.origin[1] = l.origin.y; g.origin[2] = l.origin.z;
+    g.step[0] = l.step.x; g.step[1] = l.step.y; g.step[2] = l.step.z;
+    g.mask = mask; g.vbase = vbase; g.edges = edges;
+    return launchRefinement(c, s, FT_REFINE_K_LATTICE, g.n, g, steps, out);
+}
+
+struct SegmentsRequest { const void* a; const void* b; int64_t n; float iso; int32_t steps; void* point; void* status; };
+
+// Everything that can be refused without a device, in ft_sample_points' order.  *nothing: FT_OK with nothing to launch.
+int checkSegments(const ft_ctx* c, const ft_scene* s, const SegmentsRequest& r, bool deviceMemory, bool* nothing) {
+    *nothing = false;
+    if (!c) return setErr(FT_ERR_INVALID, "null context");
+    if (!s || s->ctx != c) return setErr(FT_ERR_INVALID, "bad argument (scene must belong to this context)");
+    if (!r.point && !r.status) return setErr(FT_ERR_INVALID, "refine: no output asked for");
+    if (r.steps < 0 || r.steps > FT_REFINE_MAX_STEPS) return setErr(FT_ERR_INVALID, "refine: the steps must be 0 .. 32");
+    if (!r.a || !r.b || r.n < 0) return setErr(FT_ERR_INVALID, "refine: null segment ends or a negative count");
+    const void* all[4] = {r.a, r.b, r.point, r.status};
+    if (deviceMemory)
+        for (const void* p : all) if (reinterpret_cast<uintptr_t>(p) & 3u) return setErr(FT_ERR_INVALID, "refine: every device buffer must be 4-byte aligned");
+    for (int i = 0; i < 2; ++i) if (all[i] == r.point || all[i] == r.status) return setErr(FT_ERR_INVALID, "refine: input and output must not overlap");
+    if (r.point && r.point == r.status) return setErr(FT_ERR_INVALID, "refine: outputs must not overlap");
+    if ((uint64_t)r.n >= 0xFFFF0000ull) return setErr(FT_ERR_UNSUPPORTED, "more than 2^32 points in one call");
+    *nothing = r.n == 0;
+    return FT_OK;
+}
+// the launches: device memory throughout, the context's stream, not synchronised; the arguments have passed checkSegments, the context has a device
+int launchSegments(ft_ctx* c, const ft_scene* s, const SegmentsRequest& r) {
+    const size_t n = (size_t)r.n;
+    const RefineWork w = refineWork(n, true);
+    int rc = ensureBytes(c->refineWork, c->refineWorkBytes, w.end); if (rc) return rc;
+    FtRefineArgs g = refineArgs(c, w, n, r.iso);
+    float* distB = reinterpret_cast<float*>(static_cast<unsigned char*>(c->refineWork) + w.distB);
+    g.segA = static_cast<const float*>(r.a); g.segB = static_cast<const float*>(r.b);
+    g.distA = g.dist; g.distB = distB;
+    g.status = static_cast<int32_t*>(r.status);
+    if ((rc = launchField(c, s, FieldRequest{r.a, r.n, nullptr, 0.0f, 0u, const_cast<float*>(g.dist), nullptr, nullptr}))) return rc;
+    if ((rc = launchField(c, s, FieldRequest{r.b, r.n, nullptr, 0.0f, 0u, distB, nullptr, nullptr}))) return rc;
+    if (!r.point) g.mid = nullptr;                                     // only the status: no bracket is kept, no round runs
+    return launchRefinement(c, s, FT_REFINE_K_SEGMENTS, n, g, r.point ? r.steps : 0, static_cast<float*>(r.point));
+}
+
+}  // namespace
+
+int ft_refine_segments_device(ft_ctx* c, const ft_scene* s, const void* d_a, const void* d_b, int64_t n, float iso, int32_t steps, void* d_point, void* d_status) {
+    const SegmentsRequest r{d_a, d_b, n, iso, steps, d_point, d_status};
+    bool nothing;
+    int rc = checkSegments(c, s, r, true, &nothing); if (rc || nothing) return rc;
+    if ((rc = requireDevice(c))) return rc;
+    return launchSegments(c, s, r);
+}
+// host form: [a | b | point | status] in the context's scratch (HostStaging), the device form, the outputs down; synchronises
+int ft_refine_segments(ft_ctx* c, const ft_scene* s, const ft_vec3* a, const ft_vec3* b, int64_t n, float iso, int32_t steps, ft_vec3* out_point, int32_t* out_status) {
+    SegmentsRequest r{a, b, n, iso, steps, out_point, out_status};
+    bool nothing;
+    int rc = checkSegments(c, s, r, false, &nothing); if (rc || nothing) return rc;
+    if ((rc = requireDevice(c))) return rc;
+    const size_t count = (size_t)n, bAt = align256(count * 12);
+    HostStaging stage(c, "refine", HostParts{{{out_point, 12}, {out_status, 4}, {nullptr, 0}}}, false);
+    if ((rc = stage.plan(bAt + count * 12, count))) return rc;
+    if ((rc = stage.upload(0, a, count * 12)) || (rc = stage.upload(bAt, b, count * 12))) return rc;
+    r.a = stage.input(0); r.b = stage.input(bAt); r.point = stage.part(0); r.status = stage.part(1);
+    stage.copyOut(launchSegments(c, s, r), 0, count, count);
+    return stage.finish();
+}
+// Internal (not in the header, like ft_ctx_mesh_tile; the tests): one round of the rule over n caller-given brackets in device memory — eight arrays of n
+// floats, `stride` floats apart, in the order A.x A.y A.z B.x B.y B.z sA sB — with their midpoints d_mid (n x 3) and the midpoints' distances d_dist (n).
+// last = 0: the brackets are updated in place and d_mid receives the next midpoints; last = 1: d_out (n x 3) receives the finish.  Synchronises.
+int ft_ctx_refine_round(ft_ctx* c, void* d_bracket, int64_t stride, void* d_mid, const void* d_dist, int64_t n, float iso, int32_t last, void* d_out) {
+    int rc = requireDevice(c); if (rc) return rc;
+    if (!d_bracket || !d_mid || !d_dist || n < 1 || stride < n || (uint64_t)n >= 0xFFFF0000ull || (last && !d_out)) return setErr(FT_ERR_INVALID, "bad argument");
+    FtRefineArgs g{};
+    float* base = static_cast<float*>(d_bracket);
+    for (int ax = 0; ax < 3; ++ax) { g.br.a[ax] = base + (size_t)ax * stride; g.br.b[ax] = base + (size_t)(3 + ax) * stride; }
+    g.br.sa = base + (size_t)6 * stride; g.br.sb = base + (size_t)7 * stride;
+    g.mid = static_cast<float*>(d_mid); g.dist = static_cast<const float*>(d_dist);
+    g.iso = iso; g.nV = (uint32_t)n; g.last = last ? 1u : 0u; g.out = static_cast<float*>(d_out);
+    if ((rc = launchRefine(c, FT_REFINE_K_ROUND, g, (uint64_t)n))) return rc;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return FT_OK;
+}
+// Internal (tools/refine_probe.py): skip_field = 1 this context's refinements launch everything but their field rounds (the midpoints' distances are
+// whatever the work buffer holds, so the positions are not the rule's), so that the field rounds' kernel time is a difference of two figures
+int ft_ctx_refine_probe(ft_ctx* c, int32_t skip_field) {
+    if (!c || skip_field < 0 || skip_field > 1) return setErr(FT_ERR_INVALID, "bad argument");
+    c->refineSkipField = skip_field;
+    return FT_OK;
+}
+
 // ---- meshing: ft_mesh_lattice, ft_mesh_values, ft_mesh_values_device and what reads a mesh (mesh.hip; the rule is the header's "Meshing") ----------
 struct ft_mesh {
     ft_ctx* ctx = nullptr;
@@ -1637,7 +1786,8 @@ struct ft_mesh {
 namespace {
 
 // the scene (scene form only), the lattice, its values (values forms only; host or device memory as the entry point says) and where the mesh goes
-struct MeshRequest { const ft_scene* s; const ft_lattice* lat; const void* values; float iso, eps; uint32_t flags; ft_mesh** out; };
+// refine: the bisection rounds of ft_mesh_lattice_refined, -1 for the unrefined forms
+struct MeshRequest { const ft_scene* s; const ft_lattice* lat; const void* values; float iso, eps; uint32_t flags; ft_mesh** out; int32_t refine = -1; bool refined = false; };
 enum class MeshForm { Scene, HostValues, DeviceValues };
 
 // Everything that can be refused without a device, in the header's order.  *nothing: a count of 1, FT_OK with an empty mesh and nothing to launch.
@@ -1652,6 +1802,7 @@ int checkMesh(const ft_ctx* c, const MeshRequest& r, MeshForm form, bool* nothin
     const int32_t cnt[3] = {r.lat->nx, r.lat->ny, r.lat->nz};
     for (int32_t v : cnt) if (v < 1 || v > 16777216) return setErr(FT_ERR_INVALID, "lattice: every count must be 1 .. 16777216");
     if (r.flags & ~(uint32_t)(FT_MESH_NORMAL | FT_MESH_MATERIAL)) return setErr(FT_ERR_INVALID, "mesh: unknown flag bits");
+    if (r.refined && (r.refine < 0 || r.refine > FT_REFINE_MAX_STEPS)) return setErr(FT_ERR_INVALID, "mesh: refine_steps must be 0 .. 32");
     if (form == MeshForm::DeviceValues && (reinterpret_cast<uintptr_t>(r.values) & 3u)) return setErr(FT_ERR_INVALID, "mesh: the device values must be 4-byte aligned");
     // three counts of at most 2^24: the product of two fits 2^48, and the third is applied only below the limit
     const uint64_t two = (uint64_t)r.lat->nx * (uint64_t)r.lat->ny;
@@ -1677,7 +1828,7 @@ int launchMesh(ft_ctx* c, int kernel, const FtMeshArgs& a) {
     const unsigned blocks = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)c->numCUs * perCU, a.nTiles));
     return timedLaunch(c, c->stream, "ft_launch_mesh", [&] { return ft_launch_mesh(kernel, &a, blocks, c->stream); });
 }
-int extractMesh(ft_ctx* c, const ft_lattice& l, const float* dValues, float iso, const MeshWork& w, ft_mesh* m) {
+int extractMesh(ft_ctx* c, const ft_lattice& l, const float* dValues, float iso, const MeshWork& w, ft_mesh* m, bool refined) {
     FtMeshArgs a{};
     a.values = dValues; a.iso = iso;
     a.nx = (uint32_t)l.nx; a.ny = (uint32_t)l.ny; a.nz = (uint32_t)l.nz;
@@ -1699,6 +1850,7 @@ int extractMesh(ft_ctx* c, const ft_lattice& l, const float* dValues, float iso,
     m->nV = (int64_t)totals[0]; m->nT = (int64_t)totals[1]; m->nSkipped = (int64_t)totals[2];
     if (m->nV) HIP_TRY(hipMalloc(&m->dVertices, (size_t)m->nV * 12));
     if (m->nT) HIP_TRY(hipMalloc(&m->dTriangles, (size_t)m->nT * 12));
+    if (refined && m->nV && (rc = ensureBytes(c->refineWork, c->refineWorkBytes, refineWork((size_t)m->nV, false).end))) return rc;
     a.vertices = static_cast<float*>(m->dVertices); a.triangles = static_cast<int32_t*>(m->dTriangles);
     a.nV = (uint32_t)m->nV; a.nT = (uint32_t)m->nT;
     if (m->nV && (rc = launchMesh(c, FT_MESH_K_VERTICES, a))) return rc;              // triangles only join vertices: none without them
@@ -1726,7 +1878,13 @@ int buildMesh(ft_ctx* c, const MeshRequest& r, MeshForm form) {
     } else if (form == MeshForm::Scene) {
         if ((rc = launchField(c, r.s, FieldRequest{nullptr, 0, r.lat, 0.0f, 0u, c->scratch, nullptr, nullptr}))) return fail(rc);
     }
-    if ((rc = extractMesh(c, l, dValues, r.iso, w, m))) return fail(rc);
+    if ((rc = extractMesh(c, l, dValues, r.iso, w, m, r.refined))) return fail(rc);
+    // behind the vertex emit, before anything reads the vertices: the mask and vbase of the extraction are still in the scratch
+    if (r.refined && m->nV) {
+        const unsigned char* base = static_cast<const unsigned char*>(c->scratch);
+        if ((rc = refineLattice(c, r.s, l, dValues, base + w.mask, reinterpret_cast<const uint32_t*>(base + w.vbase), FT_REFINE_EDGES_MESH, r.iso, (size_t)m->nV,
+                                r.refine, static_cast<float*>(m->dVertices)))) return fail(rc);
+    }
     if (form == MeshForm::Scene && m->nV && (m->hasNormal || m->hasMaterial)) {
         hipError_t e = hipSuccess;
         if (m->hasNormal) e = hipMalloc(&m->dNormals, (size_t)m->nV * 12);
@@ -1743,6 +1901,9 @@ int buildMesh(ft_ctx* c, const MeshRequest& r, MeshForm form) {
 
 int ft_mesh_lattice(ft_ctx* c, const ft_scene* s, const ft_lattice* lattice, float iso, float normal_epsilon, uint32_t flags, ft_mesh** out) {
     return buildMesh(c, MeshRequest{s, lattice, nullptr, iso, normal_epsilon, flags, out}, MeshForm::Scene);
+}
+int ft_mesh_lattice_refined(ft_ctx* c, const ft_scene* s, const ft_lattice* lattice, float iso, float normal_epsilon, uint32_t flags, int32_t refine_steps, ft_mesh** out) {
+    return buildMesh(c, MeshRequest{s, lattice, nullptr, iso, normal_epsilon, flags, out, refine_steps, true}, MeshForm::Scene);
 }
 int ft_mesh_values_device(ft_ctx* c, const ft_lattice* lattice, const void* d_values, float iso, ft_mesh** out) {
     return buildMesh(c, MeshRequest{nullptr, lattice, d_values, iso, 0.0f, 0u, out}, MeshForm::DeviceValues);
@@ -1807,7 +1968,8 @@ struct ft_slices {
 
 namespace {
 
-struct SliceRequest { const ft_scene* s; const ft_lattice* lat; const void* values; int32_t axis; float iso, eps; uint32_t flags; ft_slices** out; };
+// refine: the bisection rounds of ft_slice_lattice_refined, -1 for the unrefined forms
+struct SliceRequest { const ft_scene* s; const ft_lattice* lat; const void* values; int32_t axis; float iso, eps; uint32_t flags; ft_slices** out; int32_t refine = -1; bool refined = false; };
 
 // Everything that can be refused without a device, in the header's order (the mesher's, with the axis between the counts and the flag bits).  *nothing: a
 // count of 1 in the plane, FT_OK with an empty result and nothing to launch.
@@ -1824,6 +1986,7 @@ int checkSlice(const ft_ctx* c, const SliceRequest& r, MeshForm form, bool* noth
     for (int32_t v : cnt) if (v < 1 || v > 16777216) return setErr(FT_ERR_INVALID, "lattice: every count must be 1 .. 16777216");
     if (r.axis < 0 || r.axis > 2) return setErr(FT_ERR_INVALID, "slice: the axis must be 0, 1 or 2");
     if (r.flags & ~(uint32_t)(FT_SLICE_NORMAL | FT_SLICE_MATERIAL)) return setErr(FT_ERR_INVALID, "slice: unknown flag bits");
+    if (r.refined && (r.refine < 0 || r.refine > FT_REFINE_MAX_STEPS)) return setErr(FT_ERR_INVALID, "slice: refine_steps must be 0 .. 32");
     if (form == MeshForm::DeviceValues && (reinterpret_cast<uintptr_t>(r.values) & 3u)) return setErr(FT_ERR_INVALID, "slice: the device values must be 4-byte aligned");
     // three counts of at most 2^24: the product of two fits 2^48, and the third is applied only below the limit
     const uint64_t two = (uint64_t)r.lat->nx * (uint64_t)r.lat->ny;
@@ -1874,7 +2037,9 @@ int launchSliceRounds(ft_ctx* c, int first, FtSliceArgs& a, unsigned rounds) {
 
 // The extraction: values (device memory, n floats) -> m's points and polylines.  Synchronises the context's stream twice: for the vertex and segment
 // totals (the per-vertex work is sized from them) and for the point and polyline totals (the outputs are).
-int extractSlices(ft_ctx* c, const ft_lattice& l, const float* dValues, int32_t axis, float iso, const SliceWork& w, ft_slices* m) {
+// refineScene: NULL, or the scene whose field refines the vertices (refineSteps rounds) between the emit and the scatter.
+int extractSlices(ft_ctx* c, const ft_lattice& l, const float* dValues, int32_t axis, float iso, const SliceWork& w, ft_slices* m, const ft_scene* refineScene,
+                  int32_t refineSteps) {
     FtSliceArgs a{};
     a.values = dValues; a.iso = iso; a.axis = (uint32_t)axis;
     a.nx = (uint32_t)l.nx; a.ny = (uint32_t)l.ny; a.nz = (uint32_t)l.nz;
@@ -1905,6 +2070,7 @@ int extractSlices(ft_ctx* c, const ft_lattice& l, const float* dValues, int32_t 
     for (size_t& o : oState) o = take(nV * 4);
     const size_t oCyc = take(nV), oA = take(nVT * 4), oB = take(nVT * 4), oC = take(nVT * 4), oTotals = take(256);
     if ((rc = ensureBytes(c->sliceWork, c->sliceWorkBytes, at))) return rc;
+    if (refineScene && (rc = ensureBytes(c->refineWork, c->refineWorkBytes, refineWork(nV, false).end))) return rc;
     unsigned char* wk = static_cast<unsigned char*>(c->sliceWork);
     auto words = [&](size_t o) { return reinterpret_cast<uint32_t*>(wk + o); };
     a.vpos = reinterpret_cast<float*>(wk + oPos); a.vslice = words(oSlice); a.next = words(oNext); a.prev = words(oPrev); a.len = words(oLen); a.off = words(oOff);
@@ -1915,6 +2081,10 @@ int extractSlices(ft_ctx* c, const ft_lattice& l, const float* dValues, int32_t 
     HIP_TRY(hipMemsetAsync(a.next, 0xff, oLen - oNext, c->stream));     // next and prev, adjacent: FT_SLICE_NONE
     HIP_TRY(hipMemsetAsync(a.len, 0, nV * 4, c->stream));
     if ((rc = launchSlice(c, FT_SLICE_K_EMIT, a, a.nTiles)) || (rc = launchSlice(c, FT_SLICE_K_LINK, a, a.nTiles))) return rc;
+    if (refineScene) {                                                 // behind the emit, long before the scatter reads vpos; the chaining never reads positions
+        static const uint32_t edges[3] = FT_REFINE_EDGES_SLICE;
+        if ((rc = refineLattice(c, refineScene, l, dValues, a.mask, a.vbase, edges[axis], iso, nV, refineSteps, a.vpos))) return rc;
+    }
     unsigned rounds = 0;
     while (((uint64_t)1 << rounds) < (uint64_t)nV) ++rounds;          // 2^rounds >= the vertex total: a window of that many hops covers any cycle
     c->sliceLast[0] = (int64_t)nV; c->sliceLast[1] = (int64_t)rounds;
@@ -1957,7 +2127,7 @@ int buildSlices(ft_ctx* c, const SliceRequest& r, MeshForm form) {
     } else if (form == MeshForm::Scene) {
         if ((rc = launchField(c, r.s, FieldRequest{nullptr, 0, r.lat, 0.0f, 0u, c->scratch, nullptr, nullptr}))) return fail(rc);
     }
-    if ((rc = extractSlices(c, l, dValues, r.axis, r.iso, w, m))) return fail(rc);
+    if ((rc = extractSlices(c, l, dValues, r.axis, r.iso, w, m, r.refined ? r.s : nullptr, r.refine))) return fail(rc);
     if (form == MeshForm::Scene && m->nP && (m->hasNormal || m->hasMaterial)) {
         hipError_t e = hipSuccess;
         if (m->hasNormal) e = hipMalloc(&m->dNormals, (size_t)m->nP * 12);
@@ -1974,6 +2144,10 @@ int buildSlices(ft_ctx* c, const SliceRequest& r, MeshForm form) {
 
 int ft_slice_lattice(ft_ctx* c, const ft_scene* s, const ft_lattice* lattice, int32_t axis, float iso, float normal_epsilon, uint32_t flags, ft_slices** out) {
     return buildSlices(c, SliceRequest{s, lattice, nullptr, axis, iso, normal_epsilon, flags, out}, MeshForm::Scene);
+}
+int ft_slice_lattice_refined(ft_ctx* c, const ft_scene* s, const ft_lattice* lattice, int32_t axis, float iso, float normal_epsilon, uint32_t flags, int32_t refine_steps,
+                             ft_slices** out) {
+    return buildSlices(c, SliceRequest{s, lattice, nullptr, axis, iso, normal_epsilon, flags, out, refine_steps, true}, MeshForm::Scene);
 }
 int ft_slice_values_device(ft_ctx* c, const ft_lattice* lattice, const void* d_values, int32_t axis, float iso, ft_slices** out) {
     return buildSlices(c, SliceRequest{nullptr, lattice, d_values, axis, iso, 0.0f, 0u, out}, MeshForm::DeviceValues);

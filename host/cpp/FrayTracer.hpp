@@ -19,6 +19,7 @@
 //                                                       (ft_light_visibility, ft_shade_visible)
 //   Field::sampleLattice / samplePoints                 sdf.Distance, SdfForm.normal and the material at the points of a lattice or a point buffer
 //                                                       (ft_sample_lattice, ft_sample_points; SdfForm.fs:7-12, 106-112)
+//   Field::refineSegments                               where segments cross a level of the field, by bisection on the device (ft_refine_segments)
 //   Mesh::ofLattice / ofValues                          the surface distance = iso as triangles, extracted on the device (ft_mesh_lattice, ft_mesh_values)
 #pragma once
 #include <stdexcept>
@@ -290,6 +291,18 @@ inline Samples samplePoints(const SdfScene& scene, const std::vector<ft_vec3>& p
                             r.normal ? out.normal.data() : nullptr, r.material ? out.material.data() : nullptr), nullptr);
     return out;
 }
+// where the segments a[r] .. b[r] cross the level iso, by `steps` bisection rounds (ft_refine_segments): status 1 and the crossing found (a crossing, not
+// necessarily the first), or status 0 and three NaN where the ends' distances are not finite or not on opposite sides
+struct Crossings { std::vector<ft_vec3> points; std::vector<int32_t> status; };
+inline Crossings refineSegments(const SdfScene& scene, const std::vector<ft_vec3>& a, const std::vector<ft_vec3>& b, float iso = 0.0f, int32_t steps = 8) {
+    if (a.size() != b.size()) throw std::invalid_argument("Field::refineSegments: one b per a");
+    SceneOfCall s(scene);
+    Crossings out;
+    out.points.resize(a.size());
+    out.status.assign(a.size(), 0);
+    s.done(ft_refine_segments(s.ctx, s.get(), a.data(), b.data(), (int64_t)a.size(), iso, steps, out.points.data(), out.status.data()), nullptr);
+    return out;
+}
 }  // namespace Field
 
 // The surface {distance = iso} as triangles, extracted on the device from the distances on a lattice (ft_mesh_lattice: marching tetrahedra on the
@@ -297,7 +310,8 @@ inline Samples samplePoints(const SdfScene& scene, const std::vector<ft_vec3>& p
 // per vertex where asked for (SdfForm.normal sdf normalEpsilon v; the handle of the material object.Material.Color v picks)
 namespace Mesh {
 struct Triangles { std::vector<ft_vec3> vertices; std::vector<int32_t> triangles; std::vector<ft_vec3> normal; std::vector<int32_t> material; int64_t skipped = 0; };
-struct Request { float iso = 0.0f; bool normal = false; float normalEpsilon = 0.0f; bool material = false; };
+// refineSteps: -1 the mesher's vertices; 0 .. 32 bisection rounds that move every vertex along its lattice edge onto the surface (ft_mesh_lattice_refined)
+struct Request { float iso = 0.0f; bool normal = false; float normalEpsilon = 0.0f; bool material = false; int32_t refineSteps = -1; };
 inline Triangles read(ft_mesh* mesh) {
     struct Owner { ft_mesh* m; ~Owner() { ft_mesh_destroy(m); } } own{mesh};
     ft_mesh_info info{};
@@ -315,7 +329,9 @@ inline Triangles read(ft_mesh* mesh) {
 inline Triangles ofLattice(const SdfScene& scene, const ft_lattice& lattice, const Request& r = Request{}) {
     SceneOfCall s(scene);
     ft_mesh* mesh = nullptr;
-    s.done(ft_mesh_lattice(s.ctx, s.get(), &lattice, r.iso, r.normalEpsilon, (r.normal ? FT_MESH_NORMAL : 0u) | (r.material ? FT_MESH_MATERIAL : 0u), &mesh), nullptr);
+    const uint32_t flags = (r.normal ? FT_MESH_NORMAL : 0u) | (r.material ? FT_MESH_MATERIAL : 0u);
+    s.done(r.refineSteps < 0 ? ft_mesh_lattice(s.ctx, s.get(), &lattice, r.iso, r.normalEpsilon, flags, &mesh)
+                             : ft_mesh_lattice_refined(s.ctx, s.get(), &lattice, r.iso, r.normalEpsilon, flags, r.refineSteps, &mesh), nullptr);
     return read(mesh);
 }
 // any float32 lattice already in host memory: nx * ny * nz values, k contiguous (ft_mesh_values)
@@ -335,7 +351,8 @@ struct Contours {
     std::vector<ft_vec3> points; std::vector<ft_polyline> polylines; std::vector<ft_vec3> normal; std::vector<int32_t> material;
     int64_t closed = 0, skipped = 0; int32_t axis = 2, slices = 0;
 };
-struct Request { int32_t axis = 2; float iso = 0.0f; bool normal = false; float normalEpsilon = 0.0f; bool material = false; };
+// refineSteps: as Mesh::Request's (ft_slice_lattice_refined): the points are then the refined mesh vertices of the same edges
+struct Request { int32_t axis = 2; float iso = 0.0f; bool normal = false; float normalEpsilon = 0.0f; bool material = false; int32_t refineSteps = -1; };
 inline Contours read(ft_slices* slices) {
     struct Owner { ft_slices* s; ~Owner() { ft_slices_destroy(s); } } own{slices};
     ft_slices_info info{};
@@ -353,8 +370,9 @@ inline Contours read(ft_slices* slices) {
 inline Contours ofLattice(const SdfScene& scene, const ft_lattice& lattice, const Request& r = Request{}) {
     SceneOfCall s(scene);
     ft_slices* slices = nullptr;
-    s.done(ft_slice_lattice(s.ctx, s.get(), &lattice, r.axis, r.iso, r.normalEpsilon, (r.normal ? FT_SLICE_NORMAL : 0u) | (r.material ? FT_SLICE_MATERIAL : 0u), &slices),
-           nullptr);
+    const uint32_t flags = (r.normal ? FT_SLICE_NORMAL : 0u) | (r.material ? FT_SLICE_MATERIAL : 0u);
+    s.done(r.refineSteps < 0 ? ft_slice_lattice(s.ctx, s.get(), &lattice, r.axis, r.iso, r.normalEpsilon, flags, &slices)
+                             : ft_slice_lattice_refined(s.ctx, s.get(), &lattice, r.axis, r.iso, r.normalEpsilon, flags, r.refineSteps, &slices), nullptr);
     return read(slices);
 }
 // any float32 lattice already in host memory: nx * ny * nz values, k contiguous (ft_slice_values)

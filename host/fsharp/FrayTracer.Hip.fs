@@ -133,6 +133,12 @@ module Native =
     // "Slicing" states the rule).  slices: a plain nativeint out-parameter, as mesh above; flags 1u = per-point normals, 2u = materials;
     // ft_slices_read copies to pinned arrays (Vector3[], FtPolyline[]; 0n: that part is not asked for); the contours outlive their scene, not their context
     [<DllImport(Lib)>] extern int ft_slice_lattice(nativeint ctx, nativeint scene, nativeint lattice, int axis, float32 iso, float32 normalEpsilon, uint32 flags, nativeint slices)
+    // refinement (the header's "Refinement" states the rule): the same constructors with refineSteps (0 .. 32) bisection rounds that move every vertex along
+    // its lattice edge onto the surface, and the same machinery for caller-given segments (outPoint / outStatus: pinned Vector3[] / int[], either may be 0n)
+    [<DllImport(Lib)>] extern int ft_mesh_lattice_refined(nativeint ctx, nativeint scene, nativeint lattice, float32 iso, float32 normalEpsilon, uint32 flags, int refineSteps, nativeint mesh)
+    [<DllImport(Lib)>] extern int ft_slice_lattice_refined(nativeint ctx, nativeint scene, nativeint lattice, int axis, float32 iso, float32 normalEpsilon, uint32 flags, int refineSteps, nativeint slices)
+    [<DllImport(Lib)>] extern int ft_refine_segments(nativeint ctx, nativeint scene, Vector3[] a, Vector3[] b, int64 n, float32 iso, int steps, nativeint outPoint, nativeint outStatus)
+    [<DllImport(Lib)>] extern int ft_refine_segments_device(nativeint ctx, nativeint scene, nativeint dA, nativeint dB, int64 n, float32 iso, int steps, nativeint dPoint, nativeint dStatus)
     [<DllImport(Lib)>] extern int ft_slice_values(nativeint ctx, nativeint lattice, nativeint values, int axis, float32 iso, nativeint slices)
     [<DllImport(Lib)>] extern int ft_slice_values_device(nativeint ctx, nativeint lattice, nativeint dValues, int axis, float32 iso, nativeint slices)
     [<DllImport(Lib)>] extern int ft_slices_get_info(nativeint slices, nativeint info)

@@ -544,6 +544,55 @@ int ft_slices_device_buffers(const ft_slices*, void** d_points, void** d_polylin
 int ft_slices_read(const ft_slices*, ft_vec3* points, ft_polyline* polylines, ft_vec3* normals, int32_t* materials);
 void ft_slices_destroy(ft_slices*);
 
+/* Refinement: mesh and contour vertices moved onto the surface {distance = iso} by bisection of their lattice edge, on the device, and the same
+ * machinery as a query of its own.  The mesher's vertex is the linear interpolation of the two end values of a lattice edge: it is off the surface by
+ * whatever the field does between two lattice points.  The scene forms still hold the field when the vertices exist, so they can bisect the edge R
+ * times and interpolate on the last bracket.  The topology does not change: only positions move.  This is the rule, every bit of it.
+ *
+ * Bracket: two points A, B (float32 x 3) with signed values sA, sB.  Both values are finite and exactly one of sA < 0, sB < 0 holds; inside is the
+ *     mesher's s < 0.
+ * Round, repeated R times:
+ *         M = (A + B) * 0.5f per coordinate: one float32 sum, rounded, then one product, rounded;
+ *         sM = D(M) - iso, with D(M) the bits ft_eval_distance / ft_sample_points give for M and one float32 subtraction.
+ *     If sM is not finite the bracket stays as it is.  Otherwise, if (sM < 0) == (sA < 0) then (A, sA) = (M, sM), else (B, sB) = (M, sM).
+ *     There is no other stopping rule: a bracket that can no longer shrink is a fixed point of this rule.
+ * Finish: t = sA / (sA - sB), v = A + t * (B - A): the mesher's operations, rounded one by one, never fused, always from A towards B.
+ * Mesh and contour vertices: edge (q, e) starts with A = p(q), the owner, B = p(q'), sA = s[q] and sB = s[q'], taken from the lattice.  With R = 0
+ *     the finish is the mesher's formula on the mesher's operands: the result is bit-equal to the unrefined one.  A vertex is refined once and shared
+ *     by every triangle or segment that uses it; a refined contour point is bit for bit the refined mesh vertex on the same edge.  Numbering,
+ *     triangles, orientation, polylines, their order and n_skipped are those of the unrefined result, word for word.
+ * Accuracy: the field is 1-Lipschitz and a zero of D - iso lies inside a bracket of length L * 2^-R (L: the lattice edge's length), so
+ *     |D(v) - iso| <= L * 2^-R up to the evaluation's float32 noise, which takes over beyond R = 12 on scenes of unit size.
+ *
+ * ft_mesh_lattice_refined and ft_slice_lattice_refined are ft_mesh_lattice and ft_slice_lattice in every respect, with the refinement between the
+ * vertex emit and whatever reads the vertices: for the mesher the normal / material launch, for the slicer the scatter into the point buffer and then
+ * the normal / material launch.  Normals and materials are therefore taken at the refined positions.  refine_steps is R, 0 .. 32; outside that it is
+ * FT_ERR_INVALID, checked right after the flag bits; every other refusal keeps the parent's place.  They add no synchronisation (the mesher still
+ * synchronises once, the slicer twice): one launch forms the brackets from the values, and from the mask and vertex index the count and emit passes
+ * left in the context's scratch; then per round one points-form field launch over the midpoints, distance only, and one launch of the round.  That
+ * makes 1 + 2 R launches on the context's stream behind the emit.  Work memory: 48 B per vertex (eight bracket arrays, the midpoint, its
+ * distance), in a buffer the context keeps, sized from the vertex total the constructor already reads.  There are no refined *_values forms: they
+ * have no field.
+ *
+ * ft_refine_segments: where does the segment from a[r] to b[r] cross the level?  sA = D(a) - iso, sB = D(b) - iso.  out_status[r] is 1 where both are
+ * finite and exactly one is inside: then out_point[r] is the finish after `steps` rounds.  Otherwise the status is 0 and the point is three NaN.
+ * Bisection finds A crossing, not the first one: a segment that crosses the level three times has status 1 and gives any of the three; one that
+ * crosses it twice has status 0.  Either output may be NULL, but not both; with out_point NULL no round runs.  Host and device forms follow the
+ * contracts of ft_sample_points / ft_sample_points_device.  Refusals, all made before the device is asked for, in this order: FT_ERR_INVALID for a
+ * NULL context or scene or a scene of another context, no output asked for, steps outside 0 .. 32, NULL ends or n < 0, a misaligned device buffer
+ * (every one 4-byte aligned; points are 12 B apart), an output identical to an input or to the other output; FT_ERR_UNSUPPORTED for
+ * n >= 0xFFFF0000; n = 0: FT_OK, nothing launched; then FT_ERR_NO_DEVICE on a host-only context.  The host form stages through the context's scratch
+ * (24 B per segment up, 12 + 4 B down for the outputs asked for) and synchronises; the device form is launched on the context's stream and NOT
+ * synchronised.  Work memory: 52 B per segment in the same buffer. */
+int ft_mesh_lattice_refined(ft_ctx*, const ft_scene*, const ft_lattice*, float iso, float normal_epsilon, uint32_t flags, int32_t refine_steps,
+                            ft_mesh** out);
+int ft_slice_lattice_refined(ft_ctx*, const ft_scene*, const ft_lattice*, int32_t axis, float iso, float normal_epsilon, uint32_t flags,
+                             int32_t refine_steps, ft_slices** out);
+int ft_refine_segments(ft_ctx*, const ft_scene*, const ft_vec3* a, const ft_vec3* b, int64_t n, float iso, int32_t steps, ft_vec3* out_point,
+                       int32_t* out_status);
+int ft_refine_segments_device(ft_ctx*, const ft_scene*, const void* d_a, const void* d_b, int64_t n, float iso, int32_t steps, void* d_point,
+                              void* d_status);
+
 /* Single-process multi-GPU form (what an F# host would call): the flattened scene is
  * re-uploaded to each further device with ft_scene_clone, every device renders its column
  * stripes (stripe_rank = index in ctxs[], stripe_ranks = n) on its own host thread, and the
