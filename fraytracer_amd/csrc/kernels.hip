@@ -404,9 +404,12 @@ __device__ __forceinline__ bool fast_point_ok(f3 p, bool active = true) {
     return __ballot(active && bad) == 0ull;
 }
 
-// the regime of the lean evaluators' sphere runs at p, both wave-uniform: the fast runs' precondition, and with it the near radius
-__device__ __forceinline__ void ft_sphere_regime(const FtSceneDev& S, const f3 p, bool& fastOk, bool& nearOk) {
-    fastOk = fast_point_ok(p);
+// the regime of the lean evaluators' sphere runs at p, both wave-uniform: the fast runs' precondition, and with it the near radius.
+// LEAN (the lean trace kernel) with `known`: this round's culling pass has tested the very same point in the very same lanes (ft_cull_children returns no survivors
+// where fast_point_ok fails, and the evaluation runs with exactly the `active` lanes of the pass), so the precondition is not formed a second time
+template <bool LEAN = false>
+__device__ __forceinline__ void ft_sphere_regime(const FtSceneDev& S, const f3 p, bool& fastOk, bool& nearOk, bool known = false) {
+    fastOk = (LEAN && known) || fast_point_ok(p);
     nearOk = fastOk && near_point_ok(p, S.nearR2);
 }
 
@@ -848,12 +851,51 @@ __device__ __forceinline__ float ft_wave_max_all(float v) {            // v >= 0
     v = __builtin_fmaxf(v, ft_dpp<0x114>(0.0f, v)); v = __builtin_fmaxf(v, ft_dpp<0x118>(0.0f, v));
     return __builtin_fmaxf(__builtin_fmaxf(ft_readlane_f(v, 15), ft_readlane_f(v, 31)), __builtin_fmaxf(ft_readlane_f(v, 47), ft_readlane_f(v, 63)));
 }
+// The same maximum in 7 VALU instructions instead of 25, for the lean trace kernel (LEAN in ft_trace_body), whose round takes it three times in the culling pass
+// and up to five times in the certificates.  The compiler cannot fold ft_dpp's move into v_max_f32 (0 is no identity of fmax, and fmaxf canonicalises both operands
+// first): a step above is v_mov, v_mov_dpp, two canonicalising v_max and the v_max itself, and the four rows meet through four v_readlane and five more v_max.  Here a step
+// is ONE v_max_f32 with the shift on its first operand — bound_ctrl: a lane without a source lane reads 0, as `old` = 0 above — and the rows meet through row_bcast:15
+// (lane 15 of rows 0 and 2 into rows 1 and 3) and row_bcast:31 (lane 31 into rows 2 and 3), so that lane 63 holds the wave's maximum.  A maximum rounds nothing, so
+// the order the rows meet in cannot show; every row's lane 15 has met the 0 its lane 0 read, so the result is max(0, every lane's v) as above, whatever the lanes hold,
+// and a quiet NaN is dropped by v_max_f32 as by fmaxf (no operand here can be a signalling NaN: each is the result of an arithmetic instruction, or an epsilon that passed
+// a comparison).  The s_nop are the wait states between a VALU write of a VGPR and a DPP read (2) or a v_readlane (1) of it, and — the last one — between v_readlane's
+// write of the SGPR and the VALU instruction that reads that SGPR next (2: what the compiler puts behind every v_readlane of its own whose result feeds a VALU
+// instruction on this target).  All of them stand in the string: the compiler's hazard pass does not look inside an asm statement, so it pads neither the instructions
+// in it nor the first use of its result.  All 64 lanes must execute.
+__device__ __forceinline__ float ft_wave_max_all_lean(float v) {
+    uint32_t r;
+    asm("s_nop 1\n\tv_max_f32_dpp %1, %1, %1 row_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+        "s_nop 1\n\tv_max_f32_dpp %1, %1, %1 row_shr:2 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+        "s_nop 1\n\tv_max_f32_dpp %1, %1, %1 row_shr:4 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+        "s_nop 1\n\tv_max_f32_dpp %1, %1, %1 row_shr:8 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+        "s_nop 1\n\tv_max_f32_dpp %1, %1, %1 row_bcast:15 row_mask:0xa bank_mask:0xf\n\t"
+        "s_nop 1\n\tv_max_f32_dpp %1, %1, %1 row_bcast:31 row_mask:0xc bank_mask:0xf\n\t"
+        "s_nop 1\n\tv_readlane_b32 %0, %1, 63\n\t"
+        "s_nop 1"
+        : "=s"(r), "+v"(v));
+    return __uint_as_float(r);
+}
+template <bool LEAN> __device__ __forceinline__ float ft_wave_max(float v) { return LEAN ? ft_wave_max_all_lean(v) : ft_wave_max_all(v); }
 __device__ __forceinline__ float ft_wave_scan_incl(float v, float& total) {            // inclusive prefix sum in lane order; total = lane 63's (wave-uniform)
     const uint32_t lane = threadIdx.x & 63u;
     v += ft_dpp<0x111>(0.0f, v); v += ft_dpp<0x112>(0.0f, v); v += ft_dpp<0x114>(0.0f, v); v += ft_dpp<0x118>(0.0f, v);   // inclusive within each row of 16
     const float r0 = ft_readlane_f(v, 15), r1 = ft_readlane_f(v, 31), r2 = ft_readlane_f(v, 47), r3 = ft_readlane_f(v, 63);
     const float p2 = r0 + r1, p3 = p2 + r2;
     v += lane >= 48u ? p3 : (lane >= 32u ? p2 : (lane >= 16u ? r0 : 0.0f));
+    total = p3 + r3;
+    return v;
+}
+// The same prefix sum for the lean trace kernel's culling pass — the same additions in the same order — with each row's offset moved into place under a row mask
+// instead of selected by three lane compares, whose masks cost the kernel six SGPRs from its first instruction to its last.
+__device__ __forceinline__ float ft_wave_scan_incl_lean(float v, float& total) {
+    v += ft_dpp<0x111>(0.0f, v); v += ft_dpp<0x112>(0.0f, v); v += ft_dpp<0x114>(0.0f, v); v += ft_dpp<0x118>(0.0f, v);
+    const float r0 = ft_readlane_f(v, 15), r1 = ft_readlane_f(v, 31), r2 = ft_readlane_f(v, 47), r3 = ft_readlane_f(v, 63);
+    const float p2 = r0 + r1, p3 = p2 + r2;
+    int off = 0;                                                       // quad_perm [0, 1, 2, 3]: every lane reads itself; rows outside the mask keep what they have
+    off = __builtin_amdgcn_update_dpp(off, __float_as_int(r0), 0xe4, 0x2, 0xf, false);
+    off = __builtin_amdgcn_update_dpp(off, __float_as_int(p2), 0xe4, 0x4, 0xf, false);
+    off = __builtin_amdgcn_update_dpp(off, __float_as_int(p3), 0xe4, 0x8, 0xf, false);
+    v += __int_as_float(off);
     total = p3 + r3;
     return v;
 }
@@ -878,18 +920,55 @@ __device__ __forceinline__ uint32_t ft_cull_children(const FtSceneDev& S, const 
     const f3 q00 = ft_readlane3(p, __ffsll((long long)am) - 1);
     const float fx = p.x - q00.x, fy = p.y - q00.y, fz = p.z - q00.z;
     const float far2 = active ? (fx * fx + fy * fy) + fz * fz : 0.0f;
-    const float farMax = ft_wave_max_all(far2);
+    const float farMax = ft_wave_max<HELD>(far2);
     const unsigned long long fm = __ballot(active && far2 == farMax);  // never empty: the maximum is some active lane's (kept safe all the same)
     const f3 q01 = ft_readlane3(p, __ffsll((long long)(fm != 0ull ? fm : am)) - 1);
     const f3 q0 = mk3(0.5f * (q00.x + q01.x), 0.5f * (q00.y + q01.y), 0.5f * (q00.z + q01.z));
     const float ex = p.x - q0.x, ey = p.y - q0.y, ez = p.z - q0.z;
-    const float rho2 = ft_wave_max_all(active ? (ex * ex + ey * ey) + ez * ez : 0.0f);
+    const float rho2 = ft_wave_max<HELD>(active ? (ex * ex + ey * ey) + ez * ez : 0.0f);
     const float rho = __builtin_amdgcn_sqrtf(rho2) * 1.001f + 1e-6f;   // >= |p - q0| of every active lane (v_sqrt_f32: 1 ulp)
     const uint32_t n = count < FT_CULL_MAX ? count : FT_CULL_MAX;
     const float4* src = reinterpret_cast<const float4*>(ldsC + in->data);
     float4* dst = reinterpret_cast<float4*>(row);
     float carry = 0.0f;                                                // sum of the lower bounds of the passes done (wave-uniform)
     uint32_t kept = 0;
+    if (HELD) {
+        // The lean trace kernel's passes, a second statement of the general loop below on purpose: routing that loop through this lambda renames registers in 32 kernels
+        // that have nothing to do with the change (tried; same instructions, other register numbers), and those keep their machine code.  What holds the two together
+        // is tests/test_gpu_round_overhead.py: the same scenes' counters, recorded from the general wording, replayed on this one, on whole and ragged passes.
+        // Every float expression and every sum below is the general loop's, in its order — what a pass decides hangs on the exponent
+        // of `slow` and on `x`.  What differs enters no decision: a whole pass (64 children: all four of C3's) knows that every lane has a child, so the index select,
+        // the `have` terms and the masked exponential go; the lanes' addresses are formed once; "some child came close" is gathered as a lane mask and asked once
+        // behind the passes; a survivor's place in the row comes from v_mbcnt; and the shift of the prefix sums reads its 0 through bound_ctrl.
+        const float slack = 0.01f + rho;
+        unsigned long long close = 0ull;                               // lanes whose child of some pass has its centre within the margin of some ray's point
+        auto pass = [&](const float4 prm, const bool have) __attribute__((always_inline)) {
+            const float dx = prm.x - q0.x, dy = prm.y - q0.y, dz = prm.z - q0.z;
+            const float dq = __builtin_amdgcn_sqrtf((dx * dx + dy * dy) + dz * dz);
+            const float dc = dq - prm.w;
+            close |= __builtin_amdgcn_ballot_w64(have && !(dq - rho >= 1e-5f * dq + 1e-6f));
+            const float dlo = dc - slack, dhi = dc + slack;
+            const float low = have ? __builtin_amdgcn_exp2f(__builtin_fmaxf(si * dhi * 1.44269504f - 0.02f, -200.0f)) : 0.0f;
+            float passTotal;
+            const float incl = ft_wave_scan_incl_lean(low, passTotal);
+            const float excl = __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(incl), 0x138, 0xf, 0xf, true));   // wave_shr:1; lane 0 reads 0
+            const float slow = (carry + excl) * 0.99609375f;
+            const uint32_t sbits = __float_as_uint(slow);
+            const float x = __builtin_fminf(__builtin_fmaxf(si * dlo * 1.44269504f, -1000.0f), 1000.0f);
+            const bool drop = have && x == x && sbits >= 0x00800000u && sbits < 0x7f800000u && x + 0.02f <= (float)((int)(sbits >> 23) - 127 - 24);
+            const bool keep = have && !drop;
+            const unsigned long long km = __ballot(keep);
+            if (keep) dst[kept + __builtin_amdgcn_mbcnt_hi((uint32_t)(km >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)km, 0u))] = prm;
+            kept += (uint32_t)__popcll(km);
+            carry += passTotal;
+        };
+        const float4* mine = src + lane;
+        const uint32_t whole = n & ~63u;
+        uint32_t base = 0;
+        for (; base < whole; base += 64u) pass(mine[base], true);
+        if (base < n) { const bool have = base + lane < n; pass(src[have ? base + lane : n - 1u], have); }
+        return kept | (close == 0ull ? FT_CULL_NOCLAMP : 0u);
+    }
     bool apart = true;                                                 // every child looked at keeps its centre away from every ray's point (wave-uniform)
     for (uint32_t base = 0; base < n; base += 64u) {
         const uint32_t i = base + lane;
@@ -958,13 +1037,13 @@ __device__ __forceinline__ float ft_run_spheres(const FtSceneDev& S, const float
     return acc;
 }
 
-template <int MATH>
+template <int MATH, bool LEAN = false>                                 // LEAN (the lean trace kernel): the fast runs' precondition comes from the culling pass where that ran
 __device__ __forceinline__ void ft_eval_smooth_spheres(const FtSceneDev& S, const f3 p, const float* __restrict__ ldsC,
                                                        float& outD, uint32_t& outLeaf, const float* __restrict__ cullRow = nullptr, uint32_t cullN = FT_CULL_NONE) {
     float acc = 0.0f;
     uint32_t leaf = 0;
     bool fastOk, nearOk;
-    ft_sphere_regime(S, p, fastOk, nearOk);
+    ft_sphere_regime<LEAN>(S, p, fastOk, nearOk, cullN != FT_CULL_NONE);
     for (uint32_t pc = 0; pc < S.nInstr; ++pc) {
         const FtInstr FT_CONST* in = as_const(S.instr) + pc;
         const uint32_t op = in->op;
@@ -1478,6 +1557,7 @@ __device__ __forceinline__ int ft_axis_lane(unsigned long long mm) {
 // the sum is a tree of 6 + passes roundings per term instead of n, inside eSum's (2n + 4096) 2^-23, and the threshold is ft_cert_threshold's, 0.9999 included.
 // Cost: 4 wave maxima, 8 v_readlane and n / 64 passes of ~20 VALU — about 200 wave-instructions for 256 children, whatever the number of members.
 // Executed by all 64 lanes.  minMembers >= 1.  -> this lane is a member and the bundle holds.
+template <bool LEAN = false>                                           // LEAN (the lean trace kernel): the wave maxima in their short form (ft_wave_max_all_lean)
 __device__ __forceinline__ bool ft_bundle_certificate(const FtSceneDev& S, const float* __restrict__ ldsC, bool cand, const f3 o, const f3 dir, float eps, float len,
                                                       uint32_t steps, uint32_t minMembers) {
     float t0, t1;
@@ -1498,14 +1578,14 @@ __device__ __forceinline__ bool ft_bundle_certificate(const FtSceneDev& S, const
     const float bl = __builtin_amdgcn_sqrtf(__builtin_fmaf(h.z, h.z, __builtin_fmaf(h.y, h.y, h.x * h.x)));
     // maxima of values >= 0 (other lanes: 0).  A member's values are finite: a NaN or infinite origin or direction fails the gate (dd, ww), so ft_wave_max_all's
     // v >= 0 holds in every lane; a NaN that got through all the same would be dropped by v_max and is why W is tested as !(W <= escR).  The interval's ends as distances from the axis lane's own: tc1 - lo_l and hi_l - tc0 are >= tc1 - tc0 > 0 there
-    const float Wr = ft_wave_max_all(mem ? __builtin_fmaf(bl, t1, al) : 0.0f);
-    const float epsMax = ft_wave_max_all(mem ? eps : 0.0f);
+    const float Wr = ft_wave_max<LEAN>(mem ? __builtin_fmaf(bl, t1, al) : 0.0f);
+    const float epsMax = ft_wave_max<LEAN>(mem ? eps : 0.0f);
     const float Rc = (S.escR + epsMax + S.certClip) * 1.001f;
     const float W = Wr * 1.001f + (1e-6f + 4e-6f * Rc);
     const float xt = A * (epsMax + S.certM);
     if (!(W <= S.escR) || !(xt >= -100.0f)) return false;              // unrelated rays (or a NaN): no bound worth its passes; the threshold stays a normal number
-    const float dLo = ft_wave_max_all(mem ? __builtin_fmaxf(tc1 - (sl + t0), 0.0f) : 0.0f);
-    const float dHi = ft_wave_max_all(mem ? __builtin_fmaxf((sl + t1) - tc0, 0.0f) : 0.0f);
+    const float dLo = ft_wave_max<LEAN>(mem ? __builtin_fmaxf(tc1 - (sl + t0), 0.0f) : 0.0f);
+    const float dHi = ft_wave_max<LEAN>(mem ? __builtin_fmaxf((sl + t1) - tc0, 0.0f) : 0.0f);
     const float i0 = (tc1 - dLo) - 4e-6f * Rc, i1 = (tc0 + dHi) + 4e-6f * Rc;
     const f3 p0 = oc + dc * i0, sv = dc * (i1 - i0);                   // the axis segment p0 + t sv, 0 <= t <= 1
     const float iss = 1.0f / ft_dot(sv, sv);
@@ -1517,6 +1597,12 @@ __device__ __forceinline__ bool ft_bundle_certificate(const FtSceneDev& S, const
         const float4 prm = c[i < n ? i : n - 1u];
         const float term = __builtin_amdgcn_exp2f((__builtin_amdgcn_sqrtf(ft_seg_dist2(prm, p0, sv, iss)) - (prm.w + W)) * A);
         sum += i < n ? term : 0.0f;
+        // LEAN: a try that must fail stops after the pass that shows it — most tries fail, a bundle that passes close to one sphere on that sphere's term alone.
+        // Every term is >= 0 or NaN, and for a, b >= 0 the rounded sum is >= a (a + b >= a, and rounding to nearest never crosses the float a).  `total` below is
+        // reached from every lane's `sum` by such additions alone — the rest of this loop, the row shifts, the four rows — so total >= sum in every lane, or total
+        // is NaN: a lane with sum >= thr (a normal number, xt >= -100) means !(total < thr), which is what a failed try returns.  A NaN sum compares false and
+        // decides nothing here.  No guard band: nothing is estimated, the full sum is bounded from below by one of its own partial sums.
+        if (LEAN && __ballot(sum >= thr) != 0ull) return false;
     }
     float total;
     ft_wave_scan_incl(sum, total);
@@ -1542,6 +1628,7 @@ __device__ __forceinline__ bool ft_bundle_certificate(const FtSceneDev& S, const
 // cannot underflow to 0 (its value would be +inf, a miss), and the terms it flushes are the n 2^-26 of the sum that eSum already carries.
 // Float32: closest approaches and distances are eGeo's (in occB); the comparisons carry 0.1 % more.  A NaN anywhere fails a comparison: no certificate.
 // Executed by all 64 lanes.  -> this lane's march ends in a hit.
+template <bool LEAN = false>                                           // LEAN: as for ft_bundle_certificate
 __device__ __forceinline__ bool ft_occlusion_certificate(const FtRenderArgs& a, const float* __restrict__ ldsC, bool cand, const f3 o, const f3 dir, float eps, float len,
                                                          uint32_t steps) {
     const FtSceneDev& S = a.S;
@@ -1575,7 +1662,7 @@ __device__ __forceinline__ bool ft_occlusion_certificate(const FtRenderArgs& a, 
         const float nr = (prm.w + a.occ.near) - approach(mk3(prm.x, prm.y, prm.z), oc, dc, idc, tc, tAx);
         if (i < n && nr > best) { best = nr; bi = i; }
     }
-    const float nearest = ft_wave_max_all(best);
+    const float nearest = ft_wave_max<LEAN>(best);
     if (!(nearest > 0.0f)) return false;
     const int src = __ffsll((long long)__ballot(best == nearest)) - 1;
     const float4 sp = c[(uint32_t)__builtin_amdgcn_readlane((int)bi, src)];    // bi < n in every lane
@@ -2038,7 +2125,7 @@ __device__ __forceinline__ void ft_trace_body(const FtRenderArgs& a) {
         if (VARIANT == 1 && FT_WORD_AT_USE(LEAN, a.occPeriod) != 0u && waveEvals % a.occPeriod == 0u) {                // EXTENSION builds: shadow rays outside glass bodies; AO rays march
             const bool cand = s.phase == PH_SHADOW && s.steps - a.occFrom < a.occPeriod && (!EXT || !s.inside());
             if ((uint32_t)__popcll(__ballot(cand)) >= a.occMin) {
-                const bool hit = ft_occlusion_certificate(FT_ARGS_AT_USE(LEAN, a), ldsC + 0, cand, s.o, s.dir, s.eps, s.len, s.steps);   // its constants: read in the rounds that try
+                const bool hit = ft_occlusion_certificate<LEAN>(FT_ARGS_AT_USE(LEAN, a), ldsC + 0, cand, s.o, s.dir, s.eps, s.len, s.steps);   // its constants: read in the rounds that try
                 if (hit) { ft_count(FT_C_HITS); s.lidx += 1; s.phase = PH_LIGHTS; settle<EXT, FORM, LEAN>(a, s); }      // shadowed (SdfLight.fs:20)
                 if (__ballot(hit) != 0ull && __ballot(s.phase >= PH_MARCH) == 0ull) continue;                     // every lane resolved: refill now
             }
@@ -2054,7 +2141,7 @@ __device__ __forceinline__ void ft_trace_body(const FtRenderArgs& a) {
                 for (uint32_t ph = SHADE ? PH_SHADOW : PH_MARCH; ph <= PH_SHADOW; ph += PH_SHADOW - PH_MARCH) {
                     const bool cand = s.phase == ph && (ph == PH_MARCH || s.steps >= a.bundleShadow) && (!EXT || !s.inside());
                     if ((uint32_t)__popcll(__ballot(cand)) < a.bundleMin) continue;
-                    if (ft_bundle_certificate(FT_ARGS_AT_USE(LEAN, a).S, ldsC + 0, cand, s.o, s.dir, s.eps, s.len, s.steps, a.bundleMin)) ends = true;
+                    if (ft_bundle_certificate<LEAN>(FT_ARGS_AT_USE(LEAN, a).S, ldsC + 0, cand, s.o, s.dir, s.eps, s.len, s.steps, a.bundleMin)) ends = true;
                 }
             }
             // per lane: once enough lanes are due, the wave tries it for all of them at once
@@ -2135,7 +2222,7 @@ __device__ __forceinline__ void ft_trace_body(const FtRenderArgs& a) {
             if (coop) { d = dCoop; leaf = leafCoop; }
             else {
                 const f3 q = query_point();
-                if (VARIANT == 1) ft_eval_smooth_spheres<MATH>(a.S, q, ldsC, d, leaf, coopRow, cullN);
+                if (VARIANT == 1) ft_eval_smooth_spheres<MATH, LEAN>(a.S, q, ldsC, d, leaf, coopRow, cullN);
                 else if (VARIANT == 3) ft_eval_carved<K>(a.S, a.carve, q, d, leaf, a.lazy == 0u ? __builtin_inff() : s.eps);
                 else ft_eval<VARIANT == 2, MATH>(a.S, q, sd, sl, ldsC, d, leaf,          // lazy unions: off (+inf) inside a glass body, whose exit is a "hit" at large values
                                                   (EXT && s.inside()) || a.lazy == 0u ? __builtin_inff() : s.eps, coopRow, cullN);
