@@ -2264,6 +2264,62 @@ int ft_selftest_libm(ft_ctx* c, int32_t op, int32_t variant, float y, uint32_t l
     return FT_OK;
 }
 
+// Internal (not in the header, like ft_ctx_mesh_tile; tests/test_gpu_wave_primitives.py): the wave primitives of kernels.hip on n_waves x 64 host floats,
+// every wave with all 64 lanes live.  op 0: out receives FT_WAVE_PROBE_PLANES planes of n_waves x 64 floats (both maxima, both prefix sums with their
+// totals, both exclusive prefixes); op 1: four planes, four lean maxima back to back (kernels.hip ft_selftest_wave_kernel).  scale multiplies every
+// input in front of a maximum; the tests pass 1.
+int ft_selftest_wave(ft_ctx* c, int32_t op, const float* x, float scale, int32_t n_waves, float* out) {
+    int rc = requireDevice(c); if (rc) return rc;
+    if (!x || !out || op < 0 || op > 1 || n_waves < 1 || n_waves > 65536) return setErr(FT_ERR_INVALID, "bad argument");
+    const size_t plane = (size_t)n_waves * 64 * 4, outBytes = (op == 0 ? FT_WAVE_PROBE_PLANES : 4) * plane;
+    if ((rc = ensureScratch(c, align256(plane) + outBytes))) return rc;
+    unsigned char* base = static_cast<unsigned char*>(c->scratch);
+    HIP_TRY(hipMemcpyAsync(base, x, plane, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(ft_launch_selftest_wave(op, reinterpret_cast<const float*>(base), scale, (uint32_t)n_waves, reinterpret_cast<float*>(base + align256(plane)), c->stream));
+    HIP_TRY(hipMemcpyAsync(out, base + align256(plane), outBytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return FT_OK;
+}
+
+// Internal (tests/test_gpu_cull_pass.py): both wordings of the culling pass (kernels.hip ft_cull_children<false>, <true>) on n_waves x 64 host points,
+// wave w under the lane mask masks[w] (never 0).  words: 2 per wave, the general wording's return first; rows: 2 x FT_CULL_ROW floats per wave in the
+// same order, FT_CULL_PROBE_FILL where no pass wrote.  A scene without a cull site gives FT_CULL_NONE twice and untouched rows.
+int ft_selftest_cull(ft_ctx* c, const ft_scene* s, const ft_vec3* pts, const uint64_t* masks, int32_t n_waves, uint32_t* words, float* rows) {
+    int rc = requireDevice(c); if (rc) return rc;
+    if (!s || s->ctx != c) return setErr(FT_ERR_INVALID, "bad argument (scene must belong to this context)");
+    if (!pts || !masks || !words || !rows || n_waves < 1 || n_waves > 4096) return setErr(FT_ERR_INVALID, "bad argument");
+    for (int32_t w = 0; w < n_waves; ++w) if (masks[w] == 0) return setErr(FT_ERR_INVALID, "a wave's lane mask must not be empty");
+    int maxLds = 0;
+    HIP_TRY(hipDeviceGetAttribute(&maxLds, hipDeviceAttributeMaxSharedMemoryPerBlock, c->device));
+    const size_t lds = ft_selftest_cull_lds_bytes(s->dev.nStage);
+    if (lds > (size_t)maxLds) return setErr(FT_ERR_UNSUPPORTED, "scene needs " + std::to_string(lds) + " bytes of LDS per workgroup; the device offers " + std::to_string(maxLds));
+    const size_t pBytes = align256((size_t)n_waves * 64 * 12), mBytes = align256((size_t)n_waves * 8), wBytes = align256((size_t)n_waves * 8),
+                 rBytes = (size_t)n_waves * 2 * FT_CULL_ROW * 4;
+    if ((rc = ensureScratch(c, pBytes + mBytes + wBytes + rBytes))) return rc;
+    unsigned char* base = static_cast<unsigned char*>(c->scratch);
+    HIP_TRY(hipMemcpyAsync(base, pts, (size_t)n_waves * 64 * 12, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(base + pBytes, masks, (size_t)n_waves * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(ft_launch_selftest_cull(&s->dev, reinterpret_cast<const float*>(base), reinterpret_cast<const unsigned long long*>(base + pBytes), (uint32_t)n_waves,
+                                    reinterpret_cast<uint32_t*>(base + pBytes + mBytes), reinterpret_cast<float*>(base + pBytes + mBytes + wBytes), c->stream));
+    HIP_TRY(hipMemcpyAsync(words, base + pBytes + mBytes, (size_t)n_waves * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(rows, base + pBytes + mBytes + wBytes, rBytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return FT_OK;
+}
+// Internal (the same test): the scene's cull site as flattened — site[0] the run's child count (0: no site), site[1] its flags (FT_FLAG_INIT: the run
+// starts its accumulator), site[2] the bits of its strength's negative inverse; records (may be NULL): the first min(count, capacity) children, 4 floats each
+int ft_scene_cull_site(const ft_scene* s, uint32_t site[3], float* records, int32_t capacity) {
+    if (!s || !site || capacity < 0 || (capacity > 0 && !records)) return setErr(FT_ERR_INVALID, "bad argument");
+    const ft::FlatScene& f = s->flat;
+    site[0] = site[1] = site[2] = 0u;
+    if (f.hdr.cullPc == 0xffffffffu) return FT_OK;
+    const FtInstr& in = f.instr[f.hdr.cullPc];
+    site[0] = in.count; site[1] = in.flags; memcpy(&site[2], &in.f0, 4);
+    const size_t n = std::min<size_t>(in.count, (size_t)capacity);
+    if (n) memcpy(records, f.consts.data() + in.data, n * 16);
+    return FT_OK;
+}
+
 // ---- internal hooks for multi.cpp (not part of the public ABI) ------------------------------------------
 int ft_ctx_device_(const ft_ctx* c) { return (c && c->hasDevice) ? c->device : -1; }
 void* ft_ctx_stream_(const ft_ctx* c) { return c ? (void*)c->stream : nullptr; }

@@ -195,6 +195,15 @@ hipError_t ft_launch_tonemap(const float* frame, uint32_t X, uint32_t Y, uint32_
 // ft_render_multi: gathered slabs [rank][stripe][...] -> frame [stripe][rank][...] on the device
 hipError_t ft_launch_deinterleave(const float* recv, float* frame, unsigned long long stripeFloats, uint32_t nStripes, uint32_t nRanks, hipStream_t st);
 hipError_t ft_launch_selftest(int op, uint32_t lo, uint32_t hi, unsigned long long* d_mismatches, hipStream_t st);
+// Probes of the wave primitives and of the culling pass (kernels.hip "Probes"; capi.cpp ft_selftest_wave, ft_selftest_cull; the tests only).
+// wave: nWaves x 64 inputs -> FT_WAVE_PROBE_PLANES planes of nWaves x 64 floats (op 1 writes the first four).  cull: nWaves x 64 points and nWaves
+// masks -> two return words and two rows of FT_CULL_ROW floats per wave, the general wording first; rows no pass wrote hold FT_CULL_PROBE_FILL.
+#define FT_WAVE_PROBE_PLANES 8
+#define FT_CULL_PROBE_FILL 0xffc0deadu   // a NaN that no scene record holds
+hipError_t ft_launch_selftest_wave(int op, const float* x, float scale, uint32_t nWaves, float* out, hipStream_t st);
+size_t ft_selftest_cull_lds_bytes(uint32_t nStage);
+hipError_t ft_launch_selftest_cull(const FtSceneDev* S, const float* pts, const unsigned long long* masks, uint32_t nWaves, uint32_t* words, float* rows,
+                                   hipStream_t st);
 // the kernel handle of a key given piecewise, nullptr where no such kernel exists (internal, like ft_trace_occupancy; tests/test_trace_kernel_table.py)
 const void* ft_trace_kernel_for(unsigned variant, unsigned carveKind, bool ext, bool libm, bool views, unsigned shade);
 hipError_t ft_trace_occupancy(const FtTraceKey& key, size_t ldsBytes, int* blocksPerCU);

@@ -841,7 +841,7 @@ __device__ __forceinline__ f3 ft_readlane3(f3 v, int l) {
 }
 // Wave-wide maximum and prefix sum for the pass, from DPP row shifts and v_readlane: no LDS traffic, no dependent round trips (the first version
 // used ds_bpermute shuffles: 40 dependent LDS round trips per round — the pass cost 3.7 ms of a 34 ms frame).  All 64 lanes must execute.
-// Checked against the host in tools/experiments/dpp_scan.hip.
+// Checked bit for bit against a numpy restatement, general and lean forms alike, by tests/test_gpu_wave_primitives.py (the probe ft_selftest_wave_kernel below).
 template <int CTRL> __device__ __forceinline__ float ft_dpp(float old, float v) {      // lanes without a source lane keep `old`
     return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(old), __float_as_int(v), CTRL, 0xf, 0xf, false));
 }
@@ -856,7 +856,8 @@ __device__ __forceinline__ float ft_wave_max_all(float v) {            // v >= 0
 // first): a step above is v_mov, v_mov_dpp, two canonicalising v_max and the v_max itself, and the four rows meet through four v_readlane and five more v_max.  Here a step
 // is ONE v_max_f32 with the shift on its first operand — bound_ctrl: a lane without a source lane reads 0, as `old` = 0 above — and the rows meet through row_bcast:15
 // (lane 15 of rows 0 and 2 into rows 1 and 3) and row_bcast:31 (lane 31 into rows 2 and 3), so that lane 63 holds the wave's maximum.  A maximum rounds nothing, so
-// the order the rows meet in cannot show; every row's lane 15 has met the 0 its lane 0 read, so the result is max(0, every lane's v) as above, whatever the lanes hold,
+// the order the rows meet in cannot show; lane 15 of a row folds its row's 16 values (the 0 a lane without a source reads stays in the lower lanes), so the result is
+// the maximum of the lanes' v as above: max(0, v) for v >= 0 wherever some lane holds a number, which every caller sees to with the 0 of its idle lanes,
 // and a quiet NaN is dropped by v_max_f32 as by fmaxf (no operand here can be a signalling NaN: each is the result of an arithmetic instruction, or an epsilon that passed
 // a comparison).  The s_nop are the wait states between a VALU write of a VGPR and a DPP read (2) or a v_readlane (1) of it, and — the last one — between v_readlane's
 // write of the SGPR and the VALU instruction that reads that SGPR next (2: what the compiler puts behind every v_readlane of its own whose result feeds a VALU
@@ -3045,6 +3046,87 @@ extern "C" hipError_t ft_launch_eval_points(const FtSceneDev* S, int math, const
     else hipLaunchKernelGGL(ft_eval_points_kernel, dim3(blocks), dim3(FT_BLOCK), ldsBytes, st, *S, pts, n, outD, outM);
     return hipGetLastError();
 }
+// ------------------------------------------------------------------------------------------------
+// Probes of the wave primitives and of the culling pass (capi.cpp ft_selftest_wave, ft_selftest_cull: internal entry points; no product entry
+// point reaches these kernels).  They run the primitives and both wordings of ft_cull_children on inputs the tests make by hand
+// (tests/test_gpu_wave_primitives.py, tests/test_gpu_cull_pass.py) and write everything they return.
+// ------------------------------------------------------------------------------------------------
+// One wave per workgroup, all 64 lanes live, one input value per lane; plane k of `out` (nWaves x 64 floats each) receives, per lane,
+//   op 0:  0 ft_wave_max_all   1 ft_wave_max_all_lean   2, 3 ft_wave_scan_incl and its total   4, 5 ft_wave_scan_incl_lean and its total
+//          6 ft_wave_shift_right1 of plane 2   7 plane 4 through the lean pass's mov_dpp wave_shr:1 bound_ctrl
+//   op 1:  0 .. 3 four lean maxima back to back, each of a value formed from the one before (as ft_bundle_certificate's Wr, epsMax, dLo, dHi):
+//          m0 = max(x scale), m1 = max(m0 - x), m2 = max(x m1), m3 = max(x + m2)
+// Every maximum is handed the result of a VALU instruction (x * scale, scale = 1: an argument, so that the product is formed), as in the kernels:
+// the wait states ft_wave_max_all_lean writes by hand start from there.
+extern "C" __global__ void __launch_bounds__(64) ft_selftest_wave_kernel(int op, const float* __restrict__ x, float scale, float* __restrict__ out) {
+    const size_t n = (size_t)gridDim.x * 64u, i = (size_t)blockIdx.x * 64u + threadIdx.x;
+    const float v = x[i];
+    if (op == 1) {
+        const float m0 = ft_wave_max_all_lean(v * scale);
+        const float m1 = ft_wave_max_all_lean(m0 - v);
+        const float m2 = ft_wave_max_all_lean(v * m1);
+        const float m3 = ft_wave_max_all_lean(v + m2);
+        out[i] = m0; out[n + i] = m1; out[2 * n + i] = m2; out[3 * n + i] = m3;
+        return;
+    }
+    float scaleLean = scale;
+    asm volatile("" : "+s"(scaleLean));                                // a product of its own for the lean maximum, formed right in front of it
+    const float y = v * scale;
+    const float maxAll = ft_wave_max_all(y);
+    const float maxLean = ft_wave_max_all_lean(v * scaleLean);
+    float total, totalLean;
+    const float incl = ft_wave_scan_incl(y, total);
+    const float inclLean = ft_wave_scan_incl_lean(y, totalLean);
+    const float excl = ft_wave_shift_right1(incl);
+    const float exclLean = __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(inclLean), 0x138, 0xf, 0xf, true));   // as in ft_cull_children<true>
+    out[i] = maxAll; out[n + i] = maxLean;
+    out[2 * n + i] = incl; out[3 * n + i] = total; out[4 * n + i] = inclLean; out[5 * n + i] = totalLean;
+    out[6 * n + i] = excl; out[7 * n + i] = exclLean;
+}
+extern "C" hipError_t ft_launch_selftest_wave(int op, const float* x, float scale, uint32_t nWaves, float* out, hipStream_t st) {
+    hipLaunchKernelGGL(ft_selftest_wave_kernel, dim3(nWaves), dim3(64), 0, st, op, x, scale, out);
+    return hipGetLastError();
+}
+
+// The culling pass, both wordings on the same (p, active, am): wave w of the launch takes points 64 w .. 64 w + 63 (one per lane) and the lane mask
+// masks[w] (never 0: the callers of ft_cull_children guarantee am != 0; capi.cpp refuses one).  The scene's constants are staged as the evaluating
+// kernels stage them (ft_lds_layout with no value slots), and every wave owns TWO rows behind them, each pre-filled with FT_CULL_PROBE_FILL:
+// words[2 w], rows[2 w] are what ft_cull_children<false> (the general loop) returns and leaves in its row, words[2 w + 1], rows[2 w + 1] the same of
+// ft_cull_children<true> (the lean trace kernel's passes).  A wave beyond nWaves leaves after the staging (wave-uniform): whole waves run the pass.
+extern "C" __global__ void __launch_bounds__(FT_BLOCK) ft_selftest_cull_kernel(const FtSceneDev S, const float* __restrict__ pts, const unsigned long long* __restrict__ masks,
+                                                                               uint32_t nWaves, uint32_t* __restrict__ words, float* __restrict__ rows) {
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    const FtLdsLayout L = ft_lds_layout(0u, S.nStage, false, true);
+    float* ldsC = ft_lds + L.consts;
+    for (uint32_t i = tid; i < S.nStage; i += FT_BLOCK) ldsC[i] = S.consts[i];
+    const uint32_t waveInBlock = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
+    float* rowG = ft_lds + L.rows + 2u * waveInBlock * FT_CULL_ROW;
+    float* rowL = rowG + FT_CULL_ROW;
+    for (uint32_t i = lane; i < 2u * FT_CULL_ROW; i += 64u) reinterpret_cast<uint32_t*>(rowG)[i] = FT_CULL_PROBE_FILL;
+    __syncthreads();
+    const uint32_t wave = blockIdx.x * (FT_BLOCK / 64) + waveInBlock;
+    if (wave >= nWaves) return;                                        // wave-uniform
+    const unsigned long long am = as_const(masks)[wave];
+    const bool active = ((am >> lane) & 1ull) != 0ull;
+    const float* q = pts + 3ull * (64ull * wave + lane);
+    const f3 p = mk3(q[0], q[1], q[2]);
+    const uint32_t wG = ft_cull_children<false>(S, p, active, am, ldsC, rowG);
+    const uint32_t wL = ft_cull_children<true>(S, p, active, am, ldsC, rowL);
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");             // the rows were written by other lanes of this wave
+    if (lane == 0u) { words[2u * wave] = wG; words[2u * wave + 1u] = wL; }
+    uint32_t* o = reinterpret_cast<uint32_t*>(rows) + 2ull * FT_CULL_ROW * wave;
+    for (uint32_t i = lane; i < 2u * FT_CULL_ROW; i += 64u) o[i] = reinterpret_cast<const uint32_t*>(rowG)[i];
+}
+extern "C" size_t ft_selftest_cull_lds_bytes(uint32_t nStage) {
+    return 4u * ((size_t)ft_lds_layout(0u, nStage, false, true).rows + 2u * FT_CULL_ROW * (FT_BLOCK / 64));
+}
+extern "C" hipError_t ft_launch_selftest_cull(const FtSceneDev* S, const float* pts, const unsigned long long* masks, uint32_t nWaves, uint32_t* words, float* rows,
+                                              hipStream_t st) {
+    const unsigned blocks = (nWaves + FT_BLOCK / 64 - 1u) / (FT_BLOCK / 64);
+    hipLaunchKernelGGL(ft_selftest_cull_kernel, dim3(blocks), dim3(FT_BLOCK), ft_selftest_cull_lds_bytes(S->nStage), st, *S, pts, masks, nWaves, words, rows);
+    return hipGetLastError();
+}
+
 // checksums of the glibc restatements over whole ranges of float bit patterns (ft_selftest_libm): chunk c covers the 2^24 patterns from
 // lo + c * 2^24; sum of splitmix64((input bits << 32) | result bits), NaN results canonicalised — the host forms the same sums with the real libm
 __device__ __forceinline__ ft_u64 ft_splitmix64(ft_u64 z) {
