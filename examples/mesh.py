@@ -3,7 +3,7 @@
 distance field is evaluated on a lattice around the scene and the surface is extracted on the GPU (DeviceScene.mesh_lattice), then written as
 Wavefront OBJ (or binary STL).
 
-    python examples/mesh.py [--tori 1000] [--points 256] [--span 1.05] [--normals] [--refine 8] [--out scene.obj]
+    python examples/mesh.py [--tori 1000] [--points 256] [--span 1.05] [--normals] [--refine 8] [--shells] [--keep-largest K | --keep-closed] [--out scene.obj]
 """
 import argparse
 import os
@@ -21,8 +21,14 @@ ap.add_argument("--points", type=int, default=256, help="lattice points per axis
 ap.add_argument("--span", type=float, default=1.05, help="half-width of the lattice in boundary radii")
 ap.add_argument("--normals", action="store_true", help="per-vertex SdfForm.normal (epsilon = a hundredth of the lattice step)")
 ap.add_argument("--refine", type=int, default=None, help="bisection rounds (0 .. 32) that move every vertex along its lattice edge onto the surface")
+ap.add_argument("--shells", action="store_true", help="label the mesh's connected pieces on the GPU and print a table of them")
+ap.add_argument("--keep-largest", type=int, default=None, metavar="K", help="keep only the K shells with the most triangles")
+ap.add_argument("--keep-closed", action="store_true", help="keep only the shells without a border edge")
 ap.add_argument("--out", default="scene.obj", help="*.obj or *.stl")
 args = ap.parse_args()
+if args.keep_largest is not None and args.keep_closed:
+    ap.error("--keep-largest and --keep-closed exclude each other")
+keep = args.keep_largest if args.keep_largest is not None else ("closed" if args.keep_closed else None)
 
 scene, _ = syn.console_scene(seed=19, n=args.tori)                         # Program.fs:14-83
 ds = ft.Device.default(0).scene(scene)
@@ -32,7 +38,14 @@ step = 2.0 * half / (args.points - 1)
 
 t0 = time.perf_counter()
 mesh = ds.mesh_lattice((cx - half, cy - half, cz - half), (step,) * 3, (args.points,) * 3,
-                       normal_epsilon=0.01 * step if args.normals else None, refine=args.refine)
+                       normal_epsilon=0.01 * step if args.normals else None, refine=args.refine, shells=args.shells, keep=keep)
 print(f"{len(mesh.vertices)} vertices, {len(mesh.triangles)} triangles in {time.perf_counter() - t0:.3f} s")
+if mesh.shells is not None:
+    sh = mesh.shells
+    print(f"{len(sh)} shells, {sh.info['n_closed']} closed, {sh.info['n_unused_vertices']} unused vertices, {sh.info['n_border_edges']} border edges")
+    if args.shells:
+        print(f"{'shell':>6} {'vertices':>10} {'triangles':>10} {'border':>8} {'closed':>7} {'euler':>6}")
+        for s, (rec, closed, chi) in enumerate(zip(sh.records.tolist(), sh.closed.tolist(), sh.euler.tolist())):
+            print(f"{s:>6} {rec[1]:>10} {rec[2]:>10} {rec[3]:>8} {'yes' if closed else 'no':>7} {chi:>6}")
 (mesh.save_stl if args.out.lower().endswith(".stl") else mesh.save_obj)(args.out)
 print("wrote", args.out)

@@ -102,6 +102,14 @@ class SlicesInfo(C.Structure):               # ft_slices_info
 FT_SLICE_NORMAL, FT_SLICE_MATERIAL = 1, 2
 
 
+class Shell(C.Structure):                    # ft_shell: a shell's smallest vertex (the key of the numbering) and its counts; closed iff n_border_edges == 0
+    _fields_ = [("first_vertex", C.c_int32), ("n_vertices", C.c_int32), ("n_triangles", C.c_int32), ("n_border_edges", C.c_int32)]
+
+
+class ShellsInfo(C.Structure):               # ft_shells_info
+    _fields_ = [(k, C.c_int64) for k in ("n_vertices", "n_triangles", "n_shells", "n_closed", "n_unused_vertices", "n_border_edges")]
+
+
 class TonemapParams(C.Structure):
     _fields_ = [("gamma", C.c_float), ("dither", C.c_int32), ("seed", C.c_uint32), ("bmp_order", C.c_int32)]
 
@@ -201,6 +209,14 @@ SYMBOLS = {
     "ft_slice_lattice_refined": (C.c_int, [_P, _P, C.POINTER(Lattice), C.c_int32, C.c_float, C.c_float, C.c_uint32, C.c_int32, C.POINTER(_P)]),
     "ft_refine_segments": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_float, C.c_int32, _P, _P]),
     "ft_refine_segments_device": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_float, C.c_int32, _P, _P]),
+    "ft_mesh_shells": (C.c_int, [_P, C.POINTER(_P)]),
+    "ft_shells_triangles": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.POINTER(_P)]),
+    "ft_shells_triangles_device": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.POINTER(_P)]),
+    "ft_shells_get_info": (C.c_int, [_P, C.POINTER(ShellsInfo)]),
+    "ft_shells_device_buffers": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P)]),
+    "ft_shells_read": (C.c_int, [_P, _P, _P, _P]),
+    "ft_shells_destroy": (None, [_P]),
+    "ft_mesh_select": (C.c_int, [_P, _P, _P, C.c_int64, C.POINTER(_P)]),
     "ft_scene_clone": (C.c_int, [_P, _P, C.POINTER(_P)]),
     "ft_render_multi": (C.c_int, [C.POINTER(_P), C.POINTER(_P), C.c_int32, C.POINTER(CameraS), C.POINTER(RenderParams), _P, C.POINTER(Stats)]),
     "ft_scene_info_get": (C.c_int, [_P, C.POINTER(SceneInfo)]),

@@ -161,11 +161,11 @@ class SdfForm:
         return _form_scene(form, device).sample_lattice(origin, step, counts, normal_epsilon=normal_epsilon, bounded=bounded)
 
     @staticmethod
-    def mesh(form, origin, step, counts, iso=0.0, normal_epsilon=None, device=None, refine=None):
+    def mesh(form, origin, step, counts, iso=0.0, normal_epsilon=None, device=None, refine=None, shells=False, keep=None):
         """the surface sdf.Distance = iso as triangles, extracted on the GPU from the lattice lattice_points(origin, step, counts) -> Mesh, with
         SdfForm.normal per vertex where normal_epsilon is given; refine: bisection rounds that move the vertices onto the surface
-        (DeviceScene.mesh_lattice)"""
-        return _form_scene(form, device).mesh_lattice(origin, step, counts, iso=iso, normal_epsilon=normal_epsilon, refine=refine)
+        (DeviceScene.mesh_lattice); shells, keep: label the mesh's shells, keep some of them (DeviceScene.mesh_lattice)"""
+        return _form_scene(form, device).mesh_lattice(origin, step, counts, iso=iso, normal_epsilon=normal_epsilon, refine=refine, shells=shells, keep=keep)
 
     @staticmethod
     def slice(form, origin, step, counts, axis=2, iso=0.0, normal_epsilon=None, device=None, refine=None):
@@ -514,11 +514,11 @@ class Device:
                 self._scenes.append(got)
             return got
 
-    def mesh_values(self, values, origin, step, iso=0.0):
+    def mesh_values(self, values, origin, step, iso=0.0, shells=False, keep=None):
         """ft_mesh_values: the surface {values = iso} of a float32 lattice [nx, ny, nz] (point (i, j, k) at lattice_points(origin, step,
         values.shape)) as triangles, extracted on the device -> Mesh without normals and materials.  A device tensor (see is_device_tensor;
         float32, contiguous) is meshed where it lies by ft_mesh_values_device on the caller's current stream, and the Mesh holds tensors of its
-        device; the values are only read."""
+        device; the values are only read.  shells, keep: as in DeviceScene.mesh_lattice."""
         on_device = is_device_tensor(values)
         if on_device:
             if str(values.dtype).rsplit(".", 1)[-1] != "float32" or not values.is_contiguous():
@@ -533,9 +533,35 @@ class Device:
         if on_device:
             with self.on_current_stream(vals):
                 check(lib.ft_mesh_values_device(self._ctx, C.byref(lat), _dptr(vals.data_ptr()), float(iso), C.byref(handle)))
-                return _read_mesh(handle, vals, None)
+                return _read_mesh(handle, vals, None, shells, keep)
         check(lib.ft_mesh_values(self._ctx, C.byref(lat), _hptr(vals), float(iso), C.byref(handle)))
-        return _read_mesh(handle, None, None)
+        return _read_mesh(handle, None, None, shells, keep)
+
+    def shells(self, triangles, n_vertices, like=None):
+        """ft_shells_triangles: the shells (connected pieces, by shared vertex) of any indexed triangle mesh -> Shells.  triangles: int32 [nT, 3], every
+        index in 0 .. n_vertices - 1 and the three of a triangle different (anything else is FT_ERR_INVALID); a numpy array, or a device tensor
+        (int32, contiguous), which is labelled where it lies by ft_shells_triangles_device on the caller's current stream and gives tensors of its
+        device.  like: a device tensor — a host triangle list then gives tensors of like's device as well."""
+        on_device = is_device_tensor(triangles)
+        if like is not None and not is_device_tensor(like):
+            raise ValueError("like: a device tensor (see is_device_tensor) or None")
+        if on_device:
+            if str(triangles.dtype).rsplit(".", 1)[-1] != "int32" or not triangles.is_contiguous():
+                raise ValueError("shells: a device tensor must be int32 and contiguous (no silent copy on the device)")
+            tri = triangles
+        else:
+            tri = np.ascontiguousarray(triangles, dtype=np.int32)
+        if len(tuple(tri.shape)) != 2 or int(tri.shape[1]) != 3:
+            raise ValueError(f"shells: triangles must have shape [nT, 3], not {list(tri.shape)}")
+        handle = C.c_void_p()
+        nt, nv = int(tri.shape[0]), int(n_vertices)
+        if on_device:
+            with self.on_current_stream(tri):
+                check(lib.ft_shells_triangles_device(self._ctx, _dptr(tri.data_ptr()), nt, nv, C.byref(handle)))
+                return _read_shells(handle, tri)
+        with (self.on_current_stream(like) if like is not None else contextlib.nullcontext()):
+            check(lib.ft_shells_triangles(self._ctx, _hptr(tri), nt, nv, C.byref(handle)))
+            return _read_shells(handle, like)
 
     def slice_values(self, values, origin, step, axis=2, iso=0.0):
         """ft_slice_values: the contours {values = iso} of a float32 lattice [nx, ny, nz] in every lattice plane normal to `axis`, as ordered
@@ -729,12 +755,13 @@ class Mesh:
     asked for — and `skipped`, the tetrahedra left out for a non-finite corner value; numpy arrays, or device tensors where the call was given
     one.  The rule that fixes every bit of it is the header's ("Meshing")."""
 
-    def __init__(self, vertices, triangles, normal=None, material=None, skipped=0, materials=None):
+    def __init__(self, vertices, triangles, normal=None, material=None, skipped=0, materials=None, shells=None):
         self.vertices = vertices
         self.triangles = triangles
         self.normal = normal
         self.material = material
         self.skipped = int(skipped)
+        self.shells = shells                                          # a Shells where the mesh was made with shells=True or keep=...; else None
         self._materials = dict(materials or {})
 
     def descriptor(self, handle):
@@ -745,9 +772,11 @@ class Mesh:
     def _host(a):
         return None if a is None else (a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a))
 
-    def save_obj(self, path):
-        """Wavefront OBJ: v lines (9 significant digits: float32 round-trips), vn lines where the mesh has normals, f lines with 1-based indices"""
+    def save_obj(self, path, groups=False):
+        """Wavefront OBJ: v lines (9 significant digits: float32 round-trips), vn lines where the mesh has normals, f lines with 1-based indices.
+        groups: where the mesh carries shells, the faces are written shell by shell, each under a line `g shell_<s>` (within a shell in their old order)"""
         v, t, n = self._host(self.vertices), self._host(self.triangles), self._host(self.normal)
+        of = self._host(self.shells.triangle_shell) if groups and self.shells is not None else None
         with open(path, "w") as f:
             f.write(f"# {len(v)} vertices, {len(t)} triangles\n")
             for p in v:
@@ -755,8 +784,14 @@ class Mesh:
             if n is not None:
                 for p in n:
                     f.write("vn %.9g %.9g %.9g\n" % tuple(float(c) for c in p))
-            for a, b, c in (t + 1).tolist():
-                f.write(f"f {a}//{a} {b}//{b} {c}//{c}\n" if n is not None else f"f {a} {b} {c}\n")
+            if of is None:
+                for a, b, c in (t + 1).tolist():
+                    f.write(f"f {a}//{a} {b}//{b} {c}//{c}\n" if n is not None else f"f {a} {b} {c}\n")
+                return
+            for s in range(len(self.shells.records)):
+                f.write(f"g shell_{s}\n")
+                for a, b, c in (t[of == s] + 1).tolist():
+                    f.write(f"f {a}//{a} {b}//{b} {c}//{c}\n" if n is not None else f"f {a} {b} {c}\n")
 
     def save_stl(self, path):
         """binary STL: per triangle its unit normal (from the vertices, float32; zero for a zero-area triangle) and its three corners"""
@@ -774,8 +809,23 @@ class Mesh:
             f.write(rec.tobytes())
 
 
-def _read_mesh(handle, like, materials):
-    """an ft_mesh -> Mesh of numpy arrays (like = None) or of tensors of like's device, through ft_mesh_read; the handle is destroyed"""
+def _read_mesh(handle, like, materials, shells=False, keep=None):
+    """an ft_mesh -> Mesh of numpy arrays (like = None) or of tensors of like's device, through ft_mesh_read; the handle is destroyed.  shells: the
+    Mesh carries its Shells, computed on the handle before it is destroyed; keep (implies shells): the shells to keep (_keep_mask) — the Mesh is then
+    ft_mesh_select's, with the shells of the selected mesh"""
+    if keep is not None:
+        selected = C.c_void_p()
+        try:
+            sh = C.c_void_p()
+            check(lib.ft_mesh_shells(handle, C.byref(sh)))
+            mask = _keep_mask(_read_shells(sh, None, destroy=False), keep)
+            try:
+                check(lib.ft_mesh_select(handle, sh, _hptr(mask), len(mask), C.byref(selected)))
+            finally:
+                lib.ft_shells_destroy(sh)
+        finally:
+            lib.ft_mesh_destroy(handle)
+        return _read_mesh(selected, like, materials, shells=True)
     try:
         info = _lib.MeshInfo()
         check(lib.ft_mesh_get_info(handle, C.byref(info)))
@@ -784,9 +834,78 @@ def _read_mesh(handle, like, materials):
                  _empty(like, (nv,), "int32") if info.has_material else None)
         ptr = _hptr if like is None else (lambda a: None if a is None else _dptr(a.data_ptr()))
         check(lib.ft_mesh_read(handle, *map(ptr, parts)))
-        return Mesh(*parts, skipped=info.n_skipped, materials=materials)
+        found = None
+        if shells:
+            sh = C.c_void_p()
+            check(lib.ft_mesh_shells(handle, C.byref(sh)))
+            found = _read_shells(sh, like)
+        return Mesh(*parts, skipped=info.n_skipped, materials=materials, shells=found)
     finally:
         lib.ft_mesh_destroy(handle)
+
+
+class Shells:
+    """What Device.shells and a mesh made with shells=True carry: `vertex_shell` int32 [nV] (-1: a vertex no triangle names), `triangle_shell` int32
+    [nT], `records` int32 [S, 4] with the columns of ft_shell (first_vertex, n_vertices, n_triangles, n_border_edges) and `info`, a dict of
+    ft_shells_info's six counts; numpy arrays, or device tensors where the call was given one.  Shells are numbered by their smallest vertex.  The
+    rule that fixes every bit of it is the header's ("Shells")."""
+
+    def __init__(self, vertex_shell, triangle_shell, records, info):
+        self.vertex_shell = vertex_shell
+        self.triangle_shell = triangle_shell
+        self.records = records
+        self.info = dict(info)
+
+    def __len__(self):
+        return int(self.info["n_shells"])
+
+    @property
+    def closed(self):
+        """bool [S]: no border edge"""
+        return Mesh._host(self.records).reshape(-1, 4)[:, 3] == 0
+
+    @property
+    def euler(self):
+        """int64 [S]: V - (3 F + B) // 2 + F per shell, the Euler characteristic where no directed side occurs twice (every mesher output)"""
+        r = Mesh._host(self.records).reshape(-1, 4).astype(np.int64)
+        return r[:, 1] - (3 * r[:, 2] + r[:, 3]) // 2 + r[:, 2]
+
+
+def _read_shells(handle, like, destroy=True):
+    """an ft_shells -> Shells of numpy arrays (like = None) or of tensors of like's device, through ft_shells_read; the handle is destroyed"""
+    try:
+        info = _lib.ShellsInfo()
+        check(lib.ft_shells_get_info(handle, C.byref(info)))
+        parts = (_empty(like, (int(info.n_vertices),), "int32"), _empty(like, (int(info.n_triangles),), "int32"), _empty(like, (int(info.n_shells), 4), "int32"))
+        ptr = _hptr if like is None else (lambda a: _dptr(a.data_ptr()))
+        check(lib.ft_shells_read(handle, *map(ptr, parts)))
+        return Shells(*parts, info={k: int(getattr(info, k)) for k, _ in info._fields_})
+    finally:
+        if destroy:
+            lib.ft_shells_destroy(handle)
+
+
+def _keep_mask(shells, keep):
+    """keep= of the mesh methods as one byte per shell: an int k (the k shells with the most triangles, ties going to the lower number), "closed", a
+    bool array of length S, or a callable Shells -> bool array"""
+    n = len(shells)
+    if callable(keep):
+        keep = keep(shells)
+    if isinstance(keep, str):
+        if keep != "closed":
+            raise ValueError(f'keep: the only name is "closed", not {keep!r}')
+        mask = shells.closed
+    elif isinstance(keep, (int, np.integer)) and not isinstance(keep, (bool, np.bool_)):
+        if keep < 0:
+            raise ValueError("keep: a count of shells must be >= 0")
+        tris = Mesh._host(shells.records).reshape(-1, 4)[:, 2]
+        mask = np.zeros(n, bool)
+        mask[sorted(range(n), key=lambda s: (-int(tris[s]), s))[:int(keep)]] = True
+    else:
+        mask = np.asarray(Mesh._host(keep))
+        if mask.dtype != np.bool_ or mask.shape != (n,):
+            raise ValueError(f"keep: a bool array of length {n} (one per shell), not {mask.dtype} {list(mask.shape)}")
+    return np.ascontiguousarray(mask, dtype=np.uint8)
 
 
 class Contours:
@@ -1297,13 +1416,16 @@ class DeviceScene:
                            lambda e, f, *o: check(lib.ft_sample_lattice_device(ctx, sc, C.byref(lat), e, f, *map(_dptr, o))),
                            normal_epsilon, distance, material, bounded)
 
-    def mesh_lattice(self, origin, step, counts, iso=0.0, normal_epsilon=None, material=False, like=None, refine=None):
+    def mesh_lattice(self, origin, step, counts, iso=0.0, normal_epsilon=None, material=False, like=None, refine=None, shells=False, keep=None):
         """ft_mesh_lattice: the surface scene.Object.Form.Distance = iso as triangles, extracted on the device from the distances on
         lattice_points(origin, step, counts) (never bounded) -> Mesh.  normal_epsilon: also SdfForm.normal sdf normal_epsilon v per vertex;
         material: also the handle of the material object.Material.Color picks at v (Mesh.descriptor) — both exactly what sample_points gives
         for the vertices.  like: a device tensor — the Mesh then holds tensors of its device, and the launches run on the caller's current
         stream.  refine: None, or the bisection rounds (0 .. 32) of ft_mesh_lattice_refined: every vertex moves along its lattice edge onto
-        the surface, to within the edge's length * 2^-refine; triangles are unchanged, normals and materials are taken at the refined vertices."""
+        the surface, to within the edge's length * 2^-refine; triangles are unchanged, normals and materials are taken at the refined vertices.
+        shells: the Mesh carries `.shells`, its connected pieces labelled on the device (ft_mesh_shells).  keep (implies shells): only some shells,
+        through ft_mesh_select — an int k (the k shells with the most triangles, ties going to the lower number), "closed", a bool array of
+        length S or a callable Shells -> bool array; `.shells` are then those of the selected mesh."""
         lat, _ = _lattice(origin, step, counts)
         if like is not None and not is_device_tensor(like):
             raise ValueError("like: a device tensor (see is_device_tensor) or None")
@@ -1315,7 +1437,7 @@ class DeviceScene:
                 check(lib.ft_mesh_lattice(self.device._ctx, self._scene, C.byref(lat), float(iso), eps, flags, C.byref(handle)))
             else:
                 check(lib.ft_mesh_lattice_refined(self.device._ctx, self._scene, C.byref(lat), float(iso), eps, flags, int(refine), C.byref(handle)))
-            return _read_mesh(handle, like, self.materials)
+            return _read_mesh(handle, like, self.materials, shells, keep)
 
     def slice_lattice(self, origin, step, counts, axis=2, iso=0.0, normal_epsilon=None, material=False, like=None, refine=None):
         """ft_slice_lattice: the contours scene.Object.Form.Distance = iso of every lattice plane normal to `axis` (0, 1, 2: x, y, z), extracted

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
+#include <atomic>
 #include <array>
 #include <cmath>
 #include <cstdlib>
@@ -16,6 +17,7 @@
 #include "ft_mesh.h"
 #include "ft_slice.h"
 #include "ft_refine.h"
+#include "ft_shells.h"
 #include "scene.hpp"
 
 #ifndef FT_BUILD_KIND
@@ -82,6 +84,10 @@ struct ft_ctx {
     int64_t sliceLast[2] = {0, 0};                         // vertices and jump rounds R of the context's last extraction (ft_ctx_slice_probe)
     void* sliceWork = nullptr; size_t sliceWorkBytes = 0;  // the slicer's per-vertex work (sized after its first totals, when the scratch still holds the lattice)
     void* refineWork = nullptr; size_t refineWorkBytes = 0; // the refinement's per-bracket work (FT_REFINE_ITEM_BYTES each; sized from the vertex total the constructor reads, or from a segment count)
+    uint32_t shellsTile = FT_SHELLS_TILE_DEFAULT;          // items per workgroup of the shell labelling's tiled kernels (ft_ctx_shells_tile: the tests' and the probe's tiles)
+    int shellsStop = 0;                                    // 0: whole labellings; 1 / 2 / 3: they end after the incidence lists / the iterations / the vertex labels, with no shell (ft_ctx_shells_probe: the probe's stages)
+    int64_t shellsLast[2] = {0, 0};                        // iterations and synchronisations of the context's last labelling (ft_ctx_shells_last)
+    void* shellsWork = nullptr; size_t shellsWorkBytes = 0; // the shell labelling's and the selection's work (ft_shells.h says how much per vertex and triangle)
     int refineSkipField = 0;                               // 1: a refinement launches everything but its field rounds, and gives other positions (ft_ctx_refine_probe: the probe's stages)
     uint32_t orderNum = 1, orderDen = 1;                   // a tile is heavy from orderNum / orderDen of the mean cost on (ft_ctx_tile_order_rule: the probes' other rules)
 };
@@ -625,6 +631,7 @@ void ft_ctx_destroy(ft_ctx* c) {
         if (c->cams) (void)hipFree(c->cams);
         if (c->sliceWork) (void)hipFree(c->sliceWork);
         if (c->refineWork) (void)hipFree(c->refineWork);
+        if (c->shellsWork) (void)hipFree(c->shellsWork);
         for (auto& r : c->hostRegs) (void)hipHostUnregister(r.first);
         for (auto e : c->syncEvents) (void)hipEventDestroy(e);
         if (c->lane1) { (void)hipStreamSynchronize(c->lane1); (void)hipStreamDestroy(c->lane1); }
@@ -1779,6 +1786,7 @@ int ft_ctx_refine_probe(ft_ctx* c, int32_t skip_field) {
 struct ft_mesh {
     ft_ctx* ctx = nullptr;
     int64_t nV = 0, nT = 0, nSkipped = 0;
+    uint64_t serial = 0;                                   // unique per mesh of the process: what an ft_shells remembers of the mesh it was built from
     bool hasNormal = false, hasMaterial = false;
     void* dVertices = nullptr; void* dTriangles = nullptr; void* dNormals = nullptr; void* dMaterials = nullptr;
 };
@@ -1789,6 +1797,14 @@ namespace {
 // refine: the bisection rounds of ft_mesh_lattice_refined, -1 for the unrefined forms
 struct MeshRequest { const ft_scene* s; const ft_lattice* lat; const void* values; float iso, eps; uint32_t flags; ft_mesh** out; int32_t refine = -1; bool refined = false; };
 enum class MeshForm { Scene, HostValues, DeviceValues };
+
+ft_mesh* newMesh(ft_ctx* c) {
+    static std::atomic<uint64_t> serial{0};
+    ft_mesh* m = new ft_mesh();
+    m->ctx = c;
+    m->serial = ++serial;                                              // never 0: that is "built from no mesh"
+    return m;
+}
 
 // Everything that can be refused without a device, in the header's order.  *nothing: a count of 1, FT_OK with an empty mesh and nothing to launch.
 int checkMesh(const ft_ctx* c, const MeshRequest& r, MeshForm form, bool* nothing) {
@@ -1861,8 +1877,7 @@ int extractMesh(ft_ctx* c, const ft_lattice& l, const float* dValues, float iso,
 int buildMesh(ft_ctx* c, const MeshRequest& r, MeshForm form) {
     bool nothing;
     int rc = checkMesh(c, r, form, &nothing); if (rc) return rc;
-    ft_mesh* m = new ft_mesh();
-    m->ctx = c;
+    ft_mesh* m = newMesh(c);
     m->hasNormal = (r.flags & FT_MESH_NORMAL) != 0u; m->hasMaterial = (r.flags & FT_MESH_MATERIAL) != 0u;
     if (nothing) { *r.out = m; return FT_OK; }
     auto fail = [&](int code) { if (c->hasDevice) (void)hipStreamSynchronize(c->stream); ft_mesh_destroy(m); return code; };
@@ -2208,6 +2223,302 @@ int ft_ctx_slice_probe(ft_ctx* c, int32_t stop, int64_t* last) {
     if (!c || stop < 0 || stop > 2) return setErr(FT_ERR_INVALID, "bad argument");
     c->sliceStop = stop;
     if (last) { last[0] = c->sliceLast[0]; last[1] = c->sliceLast[1]; }
+    return FT_OK;
+}
+
+// ---- shells: ft_mesh_shells, ft_shells_triangles, ft_shells_triangles_device, what reads them, and ft_mesh_select (shells.hip; the rule is the header's "Shells") ----
+struct ft_shells {
+    ft_ctx* ctx = nullptr;
+    int64_t nV = 0, nT = 0, nS = 0, nClosed = 0, nUnused = 0, nBorder = 0;
+    uint64_t meshSerial = 0;                               // ft_mesh::serial of the mesh they were built from; 0: from a triangle list
+    void* dVertexShell = nullptr; void* dTriangleShell = nullptr; void* dRecords = nullptr;
+};
+
+namespace {
+
+enum class ShellsForm { Mesh, HostTriangles, DeviceTriangles };
+constexpr int64_t FT_SHELLS_MAX_TRIANGLES = 715827883;     // 3 * nT no longer fits int32 from here on
+
+// Everything that can be refused without a device, in the header's order.  *nothing: no triangle, FT_OK with every vertex unused and nothing to launch.
+int checkShells(const ft_ctx* c, ShellsForm form, const void* triangles, int64_t nT, int64_t nV, ft_shells** out, bool* nothing) {
+    static_assert(sizeof(ft_shell) == 16 && sizeof(ft_shells_info) == 48, "layout");
+    *nothing = false;
+    if (out) *out = nullptr;
+    if (!c) return setErr(FT_ERR_INVALID, "null context");
+    if (!triangles && nT != 0) return setErr(FT_ERR_INVALID, "shells: null triangles");
+    if (!out) return setErr(FT_ERR_INVALID, "null out pointer");
+    if (nT < 0 || nV < 0 || nV >= ((int64_t)1 << 31)) return setErr(FT_ERR_INVALID, "shells: the counts must be >= 0 and n_vertices below 2^31");
+    if (form == ShellsForm::DeviceTriangles && (reinterpret_cast<uintptr_t>(triangles) & 3u)) return setErr(FT_ERR_INVALID, "shells: the device triangles must be 4-byte aligned");
+    if (nT >= FT_SHELLS_MAX_TRIANGLES) return setErr(FT_ERR_UNSUPPORTED, "shells: 715827883 or more triangles (3 * n_triangles must fit int32)");
+    if (nT > 0 && nV == 0) return setErr(FT_ERR_INVALID, "shells: triangles without vertices");
+    if (form == ShellsForm::HostTriangles) {
+        const int32_t* t = static_cast<const int32_t*>(triangles);
+        for (int64_t i = 0; i < nT; ++i, t += 3) {
+            const bool ok = t[0] >= 0 && t[1] >= 0 && t[2] >= 0 && t[0] < nV && t[1] < nV && t[2] < nV && t[0] != t[1] && t[1] != t[2] && t[0] != t[2];
+            if (!ok) return setErr(FT_ERR_INVALID, "shells: triangle " + std::to_string(i) + " has an index outside 0 .. n_vertices - 1, or one twice");
+        }
+    }
+    *nothing = nT == 0;
+    return FT_OK;
+}
+
+const char* const kShellsKernels[FT_SHELLS_KERNELS] = {
+    "shells init", "shells degree", "shells degree sums", "shells scan", "shells offsets", "shells fill", "shells shortcut", "shells hook", "shells apply",
+    "shells stagnant hook", "shells second shortcut", "shells verify", "shells first", "shells leader sums", "shells number", "shells label vertices",
+    "shells label triangles", "shells summary", "shells keep vertex sums", "shells keep triangle sums", "shells keep vertices", "shells keep triangles"};
+
+// the workgroups of one launch, by the kernel's domain: vertices, triangles or shells; tiles of them in the tiled kernels
+int shellsBlocks(ft_ctx* c, int kernel, const FtShellsArgs& a, unsigned* blocks) {
+    int perCU = 0;
+    const hipError_t e = ft_shells_occupancy(kernel, a.tile, &perCU);
+    if (e != hipSuccess) return hipFail(e, (std::string("occupancy of the ") + kShellsKernels[kernel] + " kernel").c_str());
+    int rc = clampPerCU(c, kShellsKernels[kernel], perCU); if (rc) return rc;
+    const int domain = ft_shells_domain(kernel);
+    const uint64_t items = domain == 0 ? a.nV : (domain == 1 ? a.nT : (domain == 2 ? a.nS : 1));
+    const unsigned per = ft_shells_block(kernel, a.tile);
+    *blocks = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)c->numCUs * perCU, (items + per - 1) / per));
+    return FT_OK;
+}
+int launchShells(ft_ctx* c, int kernel, const FtShellsArgs& a) {
+    unsigned blocks = 1;
+    int rc = shellsBlocks(c, kernel, a, &blocks); if (rc) return rc;
+    return timedLaunch(c, c->stream, "ft_launch_shells", [&] { return ft_launch_shells(kernel, &a, blocks, c->stream); });
+}
+
+// The labelling of nT > 0 triangles over nV > 0 vertices in device memory -> s's labels, records and totals.  Synchronises the context's stream once
+// per batch of FT_SHELLS_BATCH iterations (the 4-byte stop flag) and once for the totals.
+int labelShells(ft_ctx* c, const int32_t* dTriangles, ft_shells* s) {
+    const size_t nV = (size_t)s->nV, nT = (size_t)s->nT, tile = c->shellsTile;
+    const size_t nVT = (nV + tile - 1) / tile, nTT = (nT + tile - 1) / tile, room = nV / 3 + 1;
+    size_t at = 0;
+    auto take = [&](size_t bytes) { const size_t o = at; at = align256(at + bytes); return o; };
+    size_t oWord[8];
+    for (size_t& o : oWord) o = take(nV * 4);
+    const size_t oInc = take(nT * 12), oA = take(std::max(nVT, nTT) * 4), oC = take(std::max(nVT, nTT) * 4), oRec = take(room * sizeof(ft_shell)), oTotals = take(256),
+                 oFlags = take(768);
+    int rc;
+    if ((rc = ensureBytes(c->shellsWork, c->shellsWorkBytes, at))) return rc;
+    HIP_TRY(hipMalloc(&s->dVertexShell, nV * 4));
+    HIP_TRY(hipMalloc(&s->dTriangleShell, nT * 4));
+    unsigned char* wk = static_cast<unsigned char*>(c->shellsWork);
+    auto words = [&](size_t o) { return reinterpret_cast<uint32_t*>(wk + o); };
+    FtShellsArgs a{};
+    a.triangles = dTriangles;
+    a.nV = (uint32_t)nV; a.nT = (uint32_t)nT; a.tile = (uint32_t)tile; a.nVTiles = (uint32_t)nVT; a.nTTiles = (uint32_t)nTT; a.scanTiles = a.nVTiles;
+    a.parent = words(oWord[0]); a.parent2 = words(oWord[1]); a.stamp = words(oWord[2]); a.hook = words(oWord[3]); a.first = words(oWord[4]);
+    a.degree = words(oWord[5]); a.offset = words(oWord[6]); a.cursor = words(oWord[7]);
+    a.incidence = words(oInc); a.tileA = words(oA); a.tileC = words(oC);
+    a.totals = reinterpret_cast<unsigned long long*>(wk + oTotals); a.flags = words(oFlags);
+    a.nS = (uint32_t)room; a.records = reinterpret_cast<int32_t*>(wk + oRec);
+    a.vertexShell = static_cast<int32_t*>(s->dVertexShell); a.triangleShell = static_cast<int32_t*>(s->dTriangleShell);
+    HIP_TRY(hipMemsetAsync(wk + oTotals, 0, 256 + 768, c->stream));     // totals and flags, adjacent
+    for (int k : {FT_SHELLS_K_INIT, FT_SHELLS_K_DEGREE, FT_SHELLS_K_DEGREE_SUMS, FT_SHELLS_K_SCAN, FT_SHELLS_K_OFFSETS, FT_SHELLS_K_FILL})
+        if ((rc = launchShells(c, k, a))) return rc;
+    if (c->shellsStop == 1) return FT_OK;
+    unsigned blocksV = 1, blocksT = 1;
+    if ((rc = shellsBlocks(c, FT_SHELLS_K_SHORTCUT, a, &blocksV)) || (rc = shellsBlocks(c, FT_SHELLS_K_HOOK, a, &blocksT))) return rc;
+    for (int k : {FT_SHELLS_K_APPLY, FT_SHELLS_K_STAGNANT, FT_SHELLS_K_SHORTCUT2, FT_SHELLS_K_VERIFY}) {      // a failed query names its kernel
+        unsigned unused = 1;
+        if ((rc = shellsBlocks(c, k, a, &unused))) return rc;
+    }
+    const unsigned cap = ft_shells_iteration_cap(nV);
+    unsigned done = 0, batch = 0;
+    c->shellsLast[0] = c->shellsLast[1] = 0;
+    for (bool open = true; open; ++batch) {
+        if (done >= cap)
+            return setErr(FT_ERR_UNSUPPORTED, "shells: the labelling has not finished after its proven bound of " + std::to_string(cap) + " iterations (internal error)");
+        const unsigned count = std::min<unsigned>(FT_SHELLS_BATCH, cap - done);
+        a.iteration = done + 1u; a.flagWord = batch;
+        if ((rc = timedLaunch(c, c->stream, "ft_launch_shells_iterations", [&] { return ft_launch_shells_iterations(&a, count, blocksV, blocksT, c->stream); }))) return rc;
+        done += count;
+        uint32_t flag = 0;
+        HIP_TRY(hipMemcpyAsync(&flag, a.flags + batch, 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));                      // one 4-byte flag per batch
+        c->shellsLast[0] = (int64_t)done; c->shellsLast[1] += 1;
+        if (batch == 0 && (flag & FT_SHELLS_FLAG_INVALID))             // the first pass' verdict (flag word 0), at the first synchronisation
+            return setErr(FT_ERR_INVALID, "shells: a triangle has an index outside 0 .. n_vertices - 1, or one twice");
+        open = (flag & FT_SHELLS_FLAG_OPEN) != 0u;
+    }
+    if (c->shellsStop == 2) return FT_OK;
+    for (int k : {FT_SHELLS_K_FIRST, FT_SHELLS_K_LEADER_SUMS, FT_SHELLS_K_SCAN, FT_SHELLS_K_NUMBER, FT_SHELLS_K_LABEL_VERTICES, FT_SHELLS_K_LABEL_TRIANGLES,
+                  FT_SHELLS_K_SUMMARY}) {
+        if (c->shellsStop == 3 && k == FT_SHELLS_K_LABEL_TRIANGLES) return FT_OK;
+        if ((rc = launchShells(c, k, a))) return rc;
+    }
+    unsigned long long totals[4] = {0, 0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(totals, a.totals, sizeof totals, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));                          // the one for the totals: shells, used vertices, closed shells, border edges
+    c->shellsLast[1] += 1;
+    if (totals[0] > room || totals[1] > nV) return setErr(FT_ERR_HIP, "shells: impossible totals (internal error)");
+    s->nS = (int64_t)totals[0]; s->nUnused = (int64_t)(nV - totals[1]); s->nClosed = (int64_t)totals[2]; s->nBorder = (int64_t)totals[3];
+    if (s->nS) {
+        HIP_TRY(hipMalloc(&s->dRecords, (size_t)s->nS * sizeof(ft_shell)));
+        HIP_TRY(hipMemcpyAsync(s->dRecords, a.records, (size_t)s->nS * sizeof(ft_shell), hipMemcpyDeviceToDevice, c->stream));
+    }
+    return FT_OK;
+}
+
+int buildShells(ft_ctx* c, ShellsForm form, const void* triangles, int64_t nT, int64_t nV, uint64_t meshSerial, ft_shells** out) {
+    bool nothing;
+    int rc = checkShells(c, form, triangles, nT, nV, out, &nothing); if (rc) return rc;
+    ft_shells* s = new ft_shells();
+    s->ctx = c; s->nV = nV; s->nT = nT; s->meshSerial = meshSerial;
+    auto fail = [&](int code) { if (c->hasDevice) (void)hipStreamSynchronize(c->stream); ft_shells_destroy(s); return code; };
+    if (nothing) {                                                     // every vertex unused; on a host-only context ft_shells_read writes the -1 itself
+        s->nUnused = nV;
+        if (c->hasDevice && nV) {
+            if ((rc = requireDevice(c))) return fail(rc);
+            hipError_t e = hipMalloc(&s->dVertexShell, (size_t)nV * 4);
+            if (e == hipSuccess) e = hipMemsetAsync(s->dVertexShell, 0xff, (size_t)nV * 4, c->stream);
+            if (e != hipSuccess) return fail(hipFail(e, "shells: empty labels"));
+        }
+        *out = s;
+        return FT_OK;
+    }
+    if ((rc = requireDevice(c))) return fail(rc);
+    const int32_t* dTriangles = static_cast<const int32_t*>(triangles);
+    if (form == ShellsForm::HostTriangles) {                           // staged through the context's scratch
+        if ((rc = ensureScratch(c, (size_t)nT * 12))) return fail(rc);
+        const hipError_t e = hipMemcpyAsync(c->scratch, triangles, (size_t)nT * 12, hipMemcpyHostToDevice, c->stream);
+        if (e != hipSuccess) return fail(hipFail(e, "shells: upload"));
+        dTriangles = static_cast<const int32_t*>(c->scratch);
+    }
+    if ((rc = labelShells(c, dTriangles, s))) return fail(rc);
+    *out = s;
+    return FT_OK;
+}
+
+}  // namespace
+
+int ft_mesh_shells(const ft_mesh* m, ft_shells** out) {
+    if (out) *out = nullptr;
+    if (!m) return setErr(FT_ERR_INVALID, "null mesh");
+    return buildShells(m->ctx, ShellsForm::Mesh, m->dTriangles, m->nT, m->nV, m->serial, out);
+}
+int ft_shells_triangles(ft_ctx* c, const int32_t* triangles, int64_t n_triangles, int64_t n_vertices, ft_shells** out) {
+    return buildShells(c, ShellsForm::HostTriangles, triangles, n_triangles, n_vertices, 0, out);
+}
+int ft_shells_triangles_device(ft_ctx* c, const void* d_triangles, int64_t n_triangles, int64_t n_vertices, ft_shells** out) {
+    return buildShells(c, ShellsForm::DeviceTriangles, d_triangles, n_triangles, n_vertices, 0, out);
+}
+int ft_shells_get_info(const ft_shells* s, ft_shells_info* o) {
+    if (!s || !o) return setErr(FT_ERR_INVALID, "null argument");
+    o->n_vertices = s->nV; o->n_triangles = s->nT; o->n_shells = s->nS; o->n_closed = s->nClosed; o->n_unused_vertices = s->nUnused; o->n_border_edges = s->nBorder;
+    return FT_OK;
+}
+int ft_shells_device_buffers(const ft_shells* s, void** d_vertex_shell, void** d_triangle_shell, void** d_records) {
+    if (!s) return setErr(FT_ERR_INVALID, "null shells");
+    if (d_vertex_shell) *d_vertex_shell = s->dVertexShell;
+    if (d_triangle_shell) *d_triangle_shell = s->dTriangleShell;
+    if (d_records) *d_records = s->dRecords;
+    return FT_OK;
+}
+int ft_shells_read(const ft_shells* s, int32_t* vertex_shell, int32_t* triangle_shell, ft_shell* records) {
+    if (!s) return setErr(FT_ERR_INVALID, "null shells");
+    if (!s->ctx->hasDevice) {                                          // empty shells of a host-only context: every vertex is unused
+        if (vertex_shell && s->nV) std::memset(vertex_shell, 0xff, (size_t)s->nV * 4);
+        return FT_OK;
+    }
+    int rc = requireDevice(s->ctx); if (rc) return rc;
+    const struct { void* host; const void* dev; size_t bytes; } parts[3] = {
+        {vertex_shell, s->dVertexShell, (size_t)s->nV * 4}, {triangle_shell, s->dTriangleShell, (size_t)s->nT * 4}, {records, s->dRecords, (size_t)s->nS * sizeof(ft_shell)}};
+    hipError_t e = hipSuccess;
+    for (const auto& p : parts)
+        if (e == hipSuccess && p.host && p.dev && p.bytes) e = hipMemcpyAsync(p.host, p.dev, p.bytes, hipMemcpyDefault, s->ctx->stream);      // host or device destination
+    const hipError_t se = hipStreamSynchronize(s->ctx->stream);        // nothing of the call is left in flight, whatever happened
+    if (e != hipSuccess) return hipFail(e, "ft_shells_read");
+    if (se != hipSuccess) return hipFail(se, "ft_shells_read");
+    return FT_OK;
+}
+void ft_shells_destroy(ft_shells* s) {
+    if (!s) return;
+    if (s->ctx->hasDevice && (s->dVertexShell || s->dTriangleShell || s->dRecords)) {
+        (void)hipSetDevice(s->ctx->device);
+        for (void* p : {s->dVertexShell, s->dTriangleShell, s->dRecords}) if (p) (void)hipFree(p);      // waits for whatever still uses it
+    }
+    delete s;
+}
+
+// The selection.  Synchronises the context's stream once, for the kept vertices and triangles; then allocates exactly and scatters.
+int ft_mesh_select(const ft_mesh* m, const ft_shells* s, const uint8_t* keep, int64_t n_keep, ft_mesh** out) {
+    if (out) *out = nullptr;
+    if (!m) return setErr(FT_ERR_INVALID, "null mesh");
+    if (!s) return setErr(FT_ERR_INVALID, "null shells");
+    if (!keep && n_keep != 0) return setErr(FT_ERR_INVALID, "select: null keep");
+    if (!out) return setErr(FT_ERR_INVALID, "null out pointer");
+    if (s->ctx != m->ctx || s->meshSerial != m->serial) return setErr(FT_ERR_INVALID, "select: the shells were not built from this mesh");
+    if (n_keep != s->nS) return setErr(FT_ERR_INVALID, "select: n_keep must be the number of shells");
+    ft_ctx* c = m->ctx;
+    ft_mesh* r = newMesh(c);
+    r->hasNormal = m->hasNormal; r->hasMaterial = m->hasMaterial; r->nSkipped = m->nSkipped;
+    bool any = false;
+    for (int64_t i = 0; i < n_keep; ++i) any = any || keep[i] != 0;
+    if (!any) { *out = r; return FT_OK; }                              // no shell kept (or none there): an empty mesh, no device needed
+    auto fail = [&](int code) { if (c->hasDevice) (void)hipStreamSynchronize(c->stream); ft_mesh_destroy(r); return code; };
+    int rc;
+    if ((rc = requireDevice(c))) return fail(rc);
+    const size_t nV = (size_t)m->nV, nT = (size_t)m->nT, nS = (size_t)s->nS, tile = c->shellsTile;
+    const size_t nVT = (nV + tile - 1) / tile, nTT = (nT + tile - 1) / tile;
+    size_t at = 0;
+    auto take = [&](size_t bytes) { const size_t o = at; at = align256(at + bytes); return o; };
+    const size_t oRemap = take(nV * 4), oAV = take(nVT * 4), oAT = take(nTT * 4), oC = take(std::max(nVT, nTT) * 4), oKeep = take(nS), oTotals = take(256);
+    if ((rc = ensureBytes(c->shellsWork, c->shellsWorkBytes, at))) return fail(rc);
+    unsigned char* wk = static_cast<unsigned char*>(c->shellsWork);
+    auto words = [&](size_t o) { return reinterpret_cast<uint32_t*>(wk + o); };
+    FtShellsArgs av{};
+    av.triangles = static_cast<const int32_t*>(m->dTriangles);
+    av.nV = (uint32_t)nV; av.nT = (uint32_t)nT; av.tile = (uint32_t)tile; av.nVTiles = (uint32_t)nVT; av.nTTiles = (uint32_t)nTT; av.nS = (uint32_t)nS;
+    av.vertexShell = static_cast<int32_t*>(s->dVertexShell); av.triangleShell = static_cast<int32_t*>(s->dTriangleShell);
+    av.keep = wk + oKeep; av.remap = words(oRemap); av.tileC = words(oC);
+    av.srcVertices = static_cast<const uint32_t*>(m->dVertices); av.srcNormals = static_cast<const uint32_t*>(m->dNormals); av.srcMaterials = static_cast<const uint32_t*>(m->dMaterials);
+    FtShellsArgs at_ = av;                                             // the triangles' pass: sums, prefixes and total of its own
+    av.tileA = words(oAV); av.scanTiles = av.nVTiles; av.totals = reinterpret_cast<unsigned long long*>(wk + oTotals);
+    at_.tileA = words(oAT); at_.scanTiles = at_.nTTiles; at_.totals = av.totals + 2;
+    hipError_t e = hipMemcpyAsync(wk + oKeep, keep, nS, hipMemcpyHostToDevice, c->stream);
+    if (e != hipSuccess) return fail(hipFail(e, "select: upload"));
+    if ((rc = launchShells(c, FT_SHELLS_K_KEEP_VERTEX_SUMS, av)) || (rc = launchShells(c, FT_SHELLS_K_SCAN, av)) ||
+        (rc = launchShells(c, FT_SHELLS_K_KEEP_TRIANGLE_SUMS, at_)) || (rc = launchShells(c, FT_SHELLS_K_SCAN, at_))) return fail(rc);
+    unsigned long long totals[4] = {0, 0, 0, 0};
+    e = hipMemcpyAsync(totals, av.totals, sizeof totals, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);          // the one synchronisation: the kept vertices and triangles
+    if (e != hipSuccess) return fail(hipFail(e, "select: totals"));
+    if (totals[0] > nV || totals[2] > nT) return fail(setErr(FT_ERR_HIP, "select: impossible totals (internal error)"));
+    r->nV = (int64_t)totals[0]; r->nT = (int64_t)totals[2];
+    if (r->nV) e = hipMalloc(&r->dVertices, (size_t)r->nV * 12);
+    if (e == hipSuccess && r->nT) e = hipMalloc(&r->dTriangles, (size_t)r->nT * 12);
+    if (e == hipSuccess && r->nV && m->dNormals) e = hipMalloc(&r->dNormals, (size_t)r->nV * 12);
+    if (e == hipSuccess && r->nV && m->dMaterials) e = hipMalloc(&r->dMaterials, (size_t)r->nV * 4);
+    if (e != hipSuccess) return fail(hipFail(e, "hipMalloc"));
+    av.nVOut = at_.nVOut = (uint32_t)r->nV; av.nTOut = at_.nTOut = (uint32_t)r->nT;
+    av.dstVertices = static_cast<uint32_t*>(r->dVertices); av.dstNormals = static_cast<uint32_t*>(r->dNormals); av.dstMaterials = static_cast<uint32_t*>(r->dMaterials);
+    at_.dstTriangles = static_cast<int32_t*>(r->dTriangles);
+    if (!r->dNormals) av.srcNormals = nullptr;
+    if (!r->dMaterials) av.srcMaterials = nullptr;
+    if (r->nV && (rc = launchShells(c, FT_SHELLS_K_KEEP_VERTICES, av))) return fail(rc);
+    if (r->nT && (rc = launchShells(c, FT_SHELLS_K_KEEP_TRIANGLES, at_))) return fail(rc);
+    *out = r;
+    return FT_OK;
+}
+// Internal (not in the header, like ft_ctx_mesh_tile; tools/shells_probe.py and the tests): the items per workgroup of this context's tiled shell
+// kernels, one of 128, 256, 512, 1024.  Every tile gives the same result.
+int ft_ctx_shells_tile(ft_ctx* c, int32_t tile) {
+    if (!c || (tile != 128 && tile != 256 && tile != 512 && tile != 1024)) return setErr(FT_ERR_INVALID, "bad argument");
+    c->shellsTile = (uint32_t)tile;
+    return FT_OK;
+}
+// Internal (the tests and the probe): the iterations and the synchronisations of the context's last labelling
+int ft_ctx_shells_last(ft_ctx* c, int64_t* last) {
+    if (!c || !last) return setErr(FT_ERR_INVALID, "bad argument");
+    last[0] = c->shellsLast[0]; last[1] = c->shellsLast[1];
+    return FT_OK;
+}
+
+// Internal (tools/shells_probe.py): stop = 0 whole labellings; 1 / 2 / 3: this context's labellings end after the incidence lists / after the
+// iterations / after the vertex labels and give shells that are not the rule's (no shell, labels unwritten), so that a stage's kernel time is a
+// difference of two figures
+int ft_ctx_shells_probe(ft_ctx* c, int32_t stop) {
+    if (!c || stop < 0 || stop > 3) return setErr(FT_ERR_INVALID, "bad argument");
+    c->shellsStop = stop;
     return FT_OK;
 }
 

@@ -22,6 +22,7 @@
 //   Field::refineSegments                               where segments cross a level of the field, by bisection on the device (ft_refine_segments)
 //   Mesh::ofLattice / ofValues                          the surface distance = iso as triangles, extracted on the device (ft_mesh_lattice, ft_mesh_values)
 #pragma once
+#include <algorithm>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -309,10 +310,46 @@ inline Crossings refineSegments(const SdfScene& scene, const std::vector<ft_vec3
 // Kuhn subdivision; the header states the rule).  triangles: three vertex indices each, counter-clockwise seen from the outside; normal and material
 // per vertex where asked for (SdfForm.normal sdf normalEpsilon v; the handle of the material object.Material.Color v picks)
 namespace Mesh {
-struct Triangles { std::vector<ft_vec3> vertices; std::vector<int32_t> triangles; std::vector<ft_vec3> normal; std::vector<int32_t> material; int64_t skipped = 0; };
+// vertexShell, triangleShell, shells, shellsInfo: filled where the request asked for shells (the header's "Shells": the mesh's connected pieces, numbered
+// by their smallest vertex; -1 for a vertex no triangle names)
+struct Triangles {
+    std::vector<ft_vec3> vertices; std::vector<int32_t> triangles; std::vector<ft_vec3> normal; std::vector<int32_t> material; int64_t skipped = 0;
+    std::vector<int32_t> vertexShell, triangleShell; std::vector<ft_shell> shells; ft_shells_info shellsInfo{};
+};
 // refineSteps: -1 the mesher's vertices; 0 .. 32 bisection rounds that move every vertex along its lattice edge onto the surface (ft_mesh_lattice_refined)
-struct Request { float iso = 0.0f; bool normal = false; float normalEpsilon = 0.0f; bool material = false; int32_t refineSteps = -1; };
-inline Triangles read(ft_mesh* mesh) {
+// shells: also label the mesh's shells (ft_mesh_shells); keepLargest: > 0 keeps only that many shells, the ones with the most triangles, ties going to
+// the lower number (ft_mesh_select), and implies shells — the labels are then those of the selected mesh
+struct Request { float iso = 0.0f; bool normal = false; float normalEpsilon = 0.0f; bool material = false; int32_t refineSteps = -1; bool shells = false; int32_t keepLargest = 0; };
+struct ShellsOwner { ft_shells* s = nullptr; ~ShellsOwner() { ft_shells_destroy(s); } };
+inline void readShells(ft_mesh* mesh, Triangles& out) {
+    ShellsOwner sh;
+    check(ft_mesh_shells(mesh, &sh.s));
+    check(ft_shells_get_info(sh.s, &out.shellsInfo));
+    out.vertexShell.resize((size_t)out.shellsInfo.n_vertices);
+    out.triangleShell.resize((size_t)out.shellsInfo.n_triangles);
+    out.shells.resize((size_t)out.shellsInfo.n_shells);
+    check(ft_shells_read(sh.s, out.vertexShell.data(), out.triangleShell.data(), out.shells.data()));
+}
+// the mesh of the keepLargest largest shells of `mesh`, which is destroyed
+inline ft_mesh* keepLargest(ft_mesh* mesh, int32_t k) {
+    struct Owner { ft_mesh* m; ~Owner() { ft_mesh_destroy(m); } } own{mesh};
+    ShellsOwner sh;
+    check(ft_mesh_shells(mesh, &sh.s));
+    ft_shells_info info{};
+    check(ft_shells_get_info(sh.s, &info));
+    std::vector<ft_shell> records((size_t)info.n_shells);
+    check(ft_shells_read(sh.s, nullptr, nullptr, records.data()));
+    std::vector<size_t> order(records.size());
+    for (size_t i = 0; i < order.size(); ++i) order[i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return records[a].n_triangles > records[b].n_triangles; });
+    std::vector<uint8_t> keep(records.size(), 0);
+    for (size_t i = 0; i < order.size() && i < (size_t)k; ++i) keep[order[i]] = 1;
+    ft_mesh* selected = nullptr;
+    check(ft_mesh_select(mesh, sh.s, keep.data(), (int64_t)keep.size(), &selected));
+    return selected;
+}
+inline Triangles read(ft_mesh* mesh, const Request& r = Request{}) {
+    if (r.keepLargest > 0) mesh = keepLargest(mesh, r.keepLargest);
     struct Owner { ft_mesh* m; ~Owner() { ft_mesh_destroy(m); } } own{mesh};
     ft_mesh_info info{};
     check(ft_mesh_get_info(mesh, &info));
@@ -324,6 +361,7 @@ inline Triangles read(ft_mesh* mesh) {
     if (info.has_material) out.material.resize((size_t)info.n_vertices);
     check(ft_mesh_read(mesh, out.vertices.data(), out.triangles.data(), info.has_normal ? out.normal.data() : nullptr,
                        info.has_material ? out.material.data() : nullptr));
+    if (r.shells || r.keepLargest > 0) readShells(mesh, out);
     return out;
 }
 inline Triangles ofLattice(const SdfScene& scene, const ft_lattice& lattice, const Request& r = Request{}) {
@@ -332,7 +370,7 @@ inline Triangles ofLattice(const SdfScene& scene, const ft_lattice& lattice, con
     const uint32_t flags = (r.normal ? FT_MESH_NORMAL : 0u) | (r.material ? FT_MESH_MATERIAL : 0u);
     s.done(r.refineSteps < 0 ? ft_mesh_lattice(s.ctx, s.get(), &lattice, r.iso, r.normalEpsilon, flags, &mesh)
                              : ft_mesh_lattice_refined(s.ctx, s.get(), &lattice, r.iso, r.normalEpsilon, flags, r.refineSteps, &mesh), nullptr);
-    return read(mesh);
+    return read(mesh, r);
 }
 // any float32 lattice already in host memory: nx * ny * nz values, k contiguous (ft_mesh_values)
 inline Triangles ofValues(ft_ctx* ctx, const ft_lattice& lattice, const std::vector<float>& values, float iso = 0.0f) {

@@ -145,6 +145,18 @@ module Native =
     [<DllImport(Lib)>] extern int ft_slices_device_buffers(nativeint slices, nativeint dPoints, nativeint dPolylines, nativeint dNormals, nativeint dMaterials)
     [<DllImport(Lib)>] extern int ft_slices_read(nativeint slices, nativeint points, nativeint polylines, nativeint normals, nativeint materials)
     [<DllImport(Lib)>] extern void ft_slices_destroy(nativeint slices)
+    // shells (the header's "Shells" states the rule): the connected pieces of a mesh or of any indexed triangle list, labelled on the device.  shells and
+    // mesh out-parameters are plain nativeints, as above; info: a pinned int64[6] (vertices, triangles, shells, closed, unused vertices, border edges);
+    // ft_shells_read copies to pinned int[] arrays (records: four ints per shell — first vertex, vertices, triangles, border edges; 0n: not asked for);
+    // keep: a pinned byte[] with one byte per shell.  The shells outlive their mesh, the selected mesh outlives both
+    [<DllImport(Lib)>] extern int ft_mesh_shells(nativeint mesh, nativeint shells)
+    [<DllImport(Lib)>] extern int ft_shells_triangles(nativeint ctx, nativeint triangles, int64 nTriangles, int64 nVertices, nativeint shells)
+    [<DllImport(Lib)>] extern int ft_shells_triangles_device(nativeint ctx, nativeint dTriangles, int64 nTriangles, int64 nVertices, nativeint shells)
+    [<DllImport(Lib)>] extern int ft_shells_get_info(nativeint shells, nativeint info)
+    [<DllImport(Lib)>] extern int ft_shells_device_buffers(nativeint shells, nativeint dVertexShell, nativeint dTriangleShell, nativeint dRecords)
+    [<DllImport(Lib)>] extern int ft_shells_read(nativeint shells, nativeint vertexShell, nativeint triangleShell, nativeint records)
+    [<DllImport(Lib)>] extern void ft_shells_destroy(nativeint shells)
+    [<DllImport(Lib)>] extern int ft_mesh_select(nativeint mesh, nativeint shells, nativeint keep, int64 nKeep, nativeint selected)
     [<DllImport(Lib)>] extern int ft_form_try_trace(nativeint ctx, nativeint scene, Ray[] rays, int64 n, [<Out>] FtFormTraceResult[] out, FtStats& stats)
     [<DllImport(Lib)>] extern int ft_object_try_trace(nativeint ctx, nativeint scene, Ray[] rays, int64 n, [<Out>] FtObjectTraceResult[] out, FtStats& stats)
     // ray buffers in device memory (rays 16-byte aligned, 32 B each): no scratch, no copy, not synchronised; pair with ft_collect_stats

@@ -593,6 +593,66 @@ int ft_refine_segments(ft_ctx*, const ft_scene*, const ft_vec3* a, const ft_vec3
 int ft_refine_segments_device(ft_ctx*, const ft_scene*, const void* d_a, const void* d_b, int64_t n, float iso, int32_t steps, void* d_point,
                               void* d_status);
 
+/* Shells: the connected pieces of an indexed triangle mesh, labelled on the device, with a record per piece, and the selection of some of them as a
+ * mesh of its own.  Only connectivity is read, never a float; every output is an integer and a pure function of the triangle list; this is the rule,
+ * every bit of it.
+ *
+ * Input: nV >= 0 vertices and nT >= 0 triangles of three int32 vertex indices each, 0 <= index < nV, the three indices of one triangle pairwise
+ *     different.  The mesher guarantees both conditions; the generic entries check them.
+ * Used vertex: a vertex named by at least one triangle.
+ * Shell: a connected component of the graph whose nodes are the used vertices and whose edges are the triangles' sides.  Connectivity is by shared
+ *     vertex: two triangles that share one vertex only are one shell.  Zero-area triangles connect like any other.
+ * Numbering: shells are numbered 0 .. S - 1 in ascending order of their smallest vertex index.
+ * Labels: vertex_shell[v] is the vertex's shell, or -1 for an unused vertex (for example one next to a non-finite value that no triangle
+ *     references); triangle_shell[t] is the shell of the triangle's vertices.
+ * Directed sides: triangle (t0, t1, t2) has the sides t0 -> t1, t1 -> t2, t2 -> t0.
+ * Border edge: side a -> b is a border edge iff no triangle has the side b -> a.  Each side is judged on its own: a side that occurs twice is not a
+ *     border edge if its reverse occurs once.
+ * Record: ft_shell { first_vertex, n_vertices, n_triangles, n_border_edges }, 16 B.  first_vertex is the shell's smallest vertex, the key of the
+ *     numbering.  A shell is closed iff n_border_edges == 0.
+ * Info: ft_shells_info: the input's two counts, the shells, the closed ones, the unused vertices and the border edges of all shells together.
+ * Limit: counts are int32.  n_triangles >= 715827883 (where 3 * nT no longer fits int32) is FT_ERR_UNSUPPORTED.
+ * Empty input: nT == 0 gives zero shells and every vertex unused: FT_OK, no device needed, like the mesher's empty mesh.
+ * Selection: given one byte per shell, shell s is kept iff keep[s] != 0.  The result is an ft_mesh that holds exactly the used vertices of the kept
+ *     shells, in their old relative order (the new index is the rank among the kept), and the kept triangles in their old order with the indices
+ *     remapped; normals and materials are gathered where the source has them; n_skipped is copied from the source.  The remap is monotone, so every
+ *     triangle still starts with its smallest index and the kept shells keep their relative numbering: shells(select(m, keep)) equals the kept
+ *     records with first_vertex remapped, in order.  No shell kept gives an empty mesh.
+ *
+ * ft_mesh_shells labels a mesh where it lies.  ft_shells_triangles labels any indexed mesh in host memory (staged through the context's scratch,
+ * 12 B per triangle); ft_shells_triangles_device one in device memory (4-byte aligned, only read).  The shells own device memory of their context
+ * and are independent of the mesh once built: they outlive it, but not their context.
+ * Refusals, all made before the device is asked for, in this order: FT_ERR_INVALID for NULL where none is allowed (mesh, context, triangles unless
+ * n_triangles is 0, out), a negative count or n_vertices >= 2^31, a misaligned device pointer; FT_ERR_UNSUPPORTED for the triangle limit;
+ * FT_ERR_INVALID for triangles without vertices and, in ft_shells_triangles, for an index outside 0 .. n_vertices - 1 or twice in one triangle
+ * (it validates its indices on the host before it uploads); empty input: FT_OK; then FT_ERR_NO_DEVICE on a host-only context; FT_ERR_HIP for a failed
+ * allocation.  ft_shells_triangles_device validates the indices on the device in its first pass and reports FT_ERR_INVALID at the constructor's
+ * first synchronisation; no kernel indexes anything with an unchecked value.  On any failure *out is NULL.
+ * Synchronisations: the labelling iterates (hooking of roots plus shortcutting after Shiloach and Vishkin; at most floor(log_{3/2} nV) + 2
+ * iterations, which the host loop carries as a hard cap: at the cap it returns an error, never a partial labelling) and the iterations needed depend
+ * on the data.  A constructor synchronises the context's stream ceil(I / 4) + 1 times, I the iterations it ran: one read of a 4-byte flag per batch
+ * of B = 4 iterations, written by a verify launch of its own, plus one for the totals; the labels and records are then complete
+ * (ft_shells_device_buffers' addresses are ordered with whatever the context launches next).  Work memory, in a buffer the context keeps: 36 B per
+ * vertex, 12 B per triangle, 16 B per three vertices, 4 B per tile of vertices and of triangles.
+ * ft_shells_read copies to the caller's buffers (n_vertices x int32, n_triangles x int32, n_shells x ft_shell; host memory, or device memory: the
+ * direction of each copy is taken from the address), synchronises the context's stream and accepts NULL for any part.
+ * ft_mesh_select: keep is host memory, n_keep == n_shells.  FT_ERR_INVALID for NULL (mesh, shells, keep unless n_keep is 0, out), for shells that
+ * were not built from that mesh (every mesh carries a serial number that its shells remember: equal counts alone do not pass; shells of a triangle
+ * list select nothing), then for n_keep != n_shells; no shell kept: FT_OK and an empty mesh, no device needed; then FT_ERR_NO_DEVICE, FT_ERR_HIP.
+ * It synchronises ONCE, for its two totals, then allocates exactly and scatters without synchronising again.  The result is a mesh like any other:
+ * it outlives the source mesh and the shells. */
+typedef struct ft_shells ft_shells;                   /* opaque; owns device memory of its context; independent of the mesh once built */
+typedef struct ft_shell { int32_t first_vertex, n_vertices, n_triangles, n_border_edges; } ft_shell;   /* 16 B */
+typedef struct ft_shells_info { int64_t n_vertices, n_triangles, n_shells, n_closed, n_unused_vertices, n_border_edges; } ft_shells_info;   /* 48 B */
+int ft_mesh_shells(const ft_mesh*, ft_shells** out);
+int ft_shells_triangles(ft_ctx*, const int32_t* triangles, int64_t n_triangles, int64_t n_vertices, ft_shells** out);
+int ft_shells_triangles_device(ft_ctx*, const void* d_triangles, int64_t n_triangles, int64_t n_vertices, ft_shells** out);
+int ft_shells_get_info(const ft_shells*, ft_shells_info* out);
+int ft_shells_device_buffers(const ft_shells*, void** d_vertex_shell, void** d_triangle_shell, void** d_records);
+int ft_shells_read(const ft_shells*, int32_t* vertex_shell, int32_t* triangle_shell, ft_shell* records);
+void ft_shells_destroy(ft_shells*);
+int ft_mesh_select(const ft_mesh*, const ft_shells*, const uint8_t* keep, int64_t n_keep, ft_mesh** out);
+
 /* Single-process multi-GPU form (what an F# host would call): the flattened scene is
  * re-uploaded to each further device with ft_scene_clone, every device renders its column
  * stripes (stripe_rank = index in ctxs[], stripe_ranks = n) on its own host thread, and the
