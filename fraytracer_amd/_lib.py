@@ -110,6 +110,16 @@ class ShellsInfo(C.Structure):               # ft_shells_info
     _fields_ = [(k, C.c_int64) for k in ("n_vertices", "n_triangles", "n_shells", "n_closed", "n_unused_vertices", "n_border_edges")]
 
 
+class ShellMeasure(C.Structure):             # ft_shell_measure: a shell's area, signed volume, first moment, box; 72 B
+    _fields_ = [("area", C.c_double), ("volume", C.c_double), ("moment", C.c_double * 3), ("bbox_min", C.c_float * 3), ("bbox_max", C.c_float * 3),
+                ("n_unmeasured", C.c_int32), ("extent_exponent", C.c_int32)]
+
+
+# the same record as a numpy dtype (the arrays Measures is built over)
+SHELL_MEASURE_DTYPE = [("area", "<f8"), ("volume", "<f8"), ("moment", "<f8", (3,)), ("bbox_min", "<f4", (3,)), ("bbox_max", "<f4", (3,)),
+                       ("n_unmeasured", "<i4"), ("extent_exponent", "<i4")]
+
+
 class TonemapParams(C.Structure):
     _fields_ = [("gamma", C.c_float), ("dither", C.c_int32), ("seed", C.c_uint32), ("bmp_order", C.c_int32)]
 
@@ -217,6 +227,8 @@ SYMBOLS = {
     "ft_shells_read": (C.c_int, [_P, _P, _P, _P]),
     "ft_shells_destroy": (None, [_P]),
     "ft_mesh_select": (C.c_int, [_P, _P, _P, C.c_int64, C.POINTER(_P)]),
+    "ft_shells_measure": (C.c_int, [_P, _P, _P]),
+    "ft_mesh_measure": (C.c_int, [_P, _P]),
     "ft_scene_clone": (C.c_int, [_P, _P, C.POINTER(_P)]),
     "ft_render_multi": (C.c_int, [C.POINTER(_P), C.POINTER(_P), C.c_int32, C.POINTER(CameraS), C.POINTER(RenderParams), _P, C.POINTER(Stats)]),
     "ft_scene_info_get": (C.c_int, [_P, C.POINTER(SceneInfo)]),

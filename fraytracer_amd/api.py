@@ -161,11 +161,11 @@ class SdfForm:
         return _form_scene(form, device).sample_lattice(origin, step, counts, normal_epsilon=normal_epsilon, bounded=bounded)
 
     @staticmethod
-    def mesh(form, origin, step, counts, iso=0.0, normal_epsilon=None, device=None, refine=None, shells=False, keep=None):
+    def mesh(form, origin, step, counts, iso=0.0, normal_epsilon=None, device=None, refine=None, shells=False, keep=None, measures=False):
         """the surface sdf.Distance = iso as triangles, extracted on the GPU from the lattice lattice_points(origin, step, counts) -> Mesh, with
         SdfForm.normal per vertex where normal_epsilon is given; refine: bisection rounds that move the vertices onto the surface
-        (DeviceScene.mesh_lattice); shells, keep: label the mesh's shells, keep some of them (DeviceScene.mesh_lattice)"""
-        return _form_scene(form, device).mesh_lattice(origin, step, counts, iso=iso, normal_epsilon=normal_epsilon, refine=refine, shells=shells, keep=keep)
+        (DeviceScene.mesh_lattice); shells, keep, measures: label the mesh's shells, keep some of them, measure them (DeviceScene.mesh_lattice)"""
+        return _form_scene(form, device).mesh_lattice(origin, step, counts, iso=iso, normal_epsilon=normal_epsilon, refine=refine, shells=shells, keep=keep, measures=measures)
 
     @staticmethod
     def slice(form, origin, step, counts, axis=2, iso=0.0, normal_epsilon=None, device=None, refine=None):
@@ -514,11 +514,11 @@ class Device:
                 self._scenes.append(got)
             return got
 
-    def mesh_values(self, values, origin, step, iso=0.0, shells=False, keep=None):
+    def mesh_values(self, values, origin, step, iso=0.0, shells=False, keep=None, measures=False):
         """ft_mesh_values: the surface {values = iso} of a float32 lattice [nx, ny, nz] (point (i, j, k) at lattice_points(origin, step,
         values.shape)) as triangles, extracted on the device -> Mesh without normals and materials.  A device tensor (see is_device_tensor;
         float32, contiguous) is meshed where it lies by ft_mesh_values_device on the caller's current stream, and the Mesh holds tensors of its
-        device; the values are only read.  shells, keep: as in DeviceScene.mesh_lattice."""
+        device; the values are only read.  shells, keep, measures: as in DeviceScene.mesh_lattice."""
         on_device = is_device_tensor(values)
         if on_device:
             if str(values.dtype).rsplit(".", 1)[-1] != "float32" or not values.is_contiguous():
@@ -533,9 +533,9 @@ class Device:
         if on_device:
             with self.on_current_stream(vals):
                 check(lib.ft_mesh_values_device(self._ctx, C.byref(lat), _dptr(vals.data_ptr()), float(iso), C.byref(handle)))
-                return _read_mesh(handle, vals, None, shells, keep)
+                return _read_mesh(handle, vals, None, shells, keep, measures)
         check(lib.ft_mesh_values(self._ctx, C.byref(lat), _hptr(vals), float(iso), C.byref(handle)))
-        return _read_mesh(handle, None, None, shells, keep)
+        return _read_mesh(handle, None, None, shells, keep, measures)
 
     def shells(self, triangles, n_vertices, like=None):
         """ft_shells_triangles: the shells (connected pieces, by shared vertex) of any indexed triangle mesh -> Shells.  triangles: int32 [nT, 3], every
@@ -755,13 +755,14 @@ class Mesh:
     asked for — and `skipped`, the tetrahedra left out for a non-finite corner value; numpy arrays, or device tensors where the call was given
     one.  The rule that fixes every bit of it is the header's ("Meshing")."""
 
-    def __init__(self, vertices, triangles, normal=None, material=None, skipped=0, materials=None, shells=None):
+    def __init__(self, vertices, triangles, normal=None, material=None, skipped=0, materials=None, shells=None, measure=None):
         self.vertices = vertices
         self.triangles = triangles
         self.normal = normal
         self.material = material
         self.skipped = int(skipped)
         self.shells = shells                                          # a Shells where the mesh was made with shells=True or keep=...; else None
+        self.measure = measure                                        # a Measures of one record, the whole mesh's, where it was made with measures=True; else None
         self._materials = dict(materials or {})
 
     def descriptor(self, handle):
@@ -809,23 +810,24 @@ class Mesh:
             f.write(rec.tobytes())
 
 
-def _read_mesh(handle, like, materials, shells=False, keep=None):
+def _read_mesh(handle, like, materials, shells=False, keep=None, measures=False):
     """an ft_mesh -> Mesh of numpy arrays (like = None) or of tensors of like's device, through ft_mesh_read; the handle is destroyed.  shells: the
     Mesh carries its Shells, computed on the handle before it is destroyed; keep (implies shells): the shells to keep (_keep_mask) — the Mesh is then
-    ft_mesh_select's, with the shells of the selected mesh"""
+    ft_mesh_select's, with the shells of the selected mesh; measures (implies shells): the Shells carry their Measures and the Mesh its own"""
     if keep is not None:
         selected = C.c_void_p()
         try:
             sh = C.c_void_p()
             check(lib.ft_mesh_shells(handle, C.byref(sh)))
-            mask = _keep_mask(_read_shells(sh, None, destroy=False), keep)
             try:
+                wanted = measures or (isinstance(keep, str) and keep == "bodies")
+                mask = _keep_mask(_read_shells(sh, None, destroy=False, mesh=handle if wanted else None), keep)
                 check(lib.ft_mesh_select(handle, sh, _hptr(mask), len(mask), C.byref(selected)))
             finally:
                 lib.ft_shells_destroy(sh)
         finally:
             lib.ft_mesh_destroy(handle)
-        return _read_mesh(selected, like, materials, shells=True)
+        return _read_mesh(selected, like, materials, shells=True, measures=measures)
     try:
         info = _lib.MeshInfo()
         check(lib.ft_mesh_get_info(handle, C.byref(info)))
@@ -834,12 +836,14 @@ def _read_mesh(handle, like, materials, shells=False, keep=None):
                  _empty(like, (nv,), "int32") if info.has_material else None)
         ptr = _hptr if like is None else (lambda a: None if a is None else _dptr(a.data_ptr()))
         check(lib.ft_mesh_read(handle, *map(ptr, parts)))
-        found = None
-        if shells:
+        found = whole = None
+        if shells or measures:
             sh = C.c_void_p()
             check(lib.ft_mesh_shells(handle, C.byref(sh)))
-            found = _read_shells(sh, like)
-        return Mesh(*parts, skipped=info.n_skipped, materials=materials, shells=found)
+            found = _read_shells(sh, like, mesh=handle if measures else None)
+        if measures:
+            whole = _read_measures(like, 1 if nv or nt else 0, lambda out: lib.ft_mesh_measure(handle, out))
+        return Mesh(*parts, skipped=info.n_skipped, materials=materials, shells=found, measure=whole)
     finally:
         lib.ft_mesh_destroy(handle)
 
@@ -848,13 +852,15 @@ class Shells:
     """What Device.shells and a mesh made with shells=True carry: `vertex_shell` int32 [nV] (-1: a vertex no triangle names), `triangle_shell` int32
     [nT], `records` int32 [S, 4] with the columns of ft_shell (first_vertex, n_vertices, n_triangles, n_border_edges) and `info`, a dict of
     ft_shells_info's six counts; numpy arrays, or device tensors where the call was given one.  Shells are numbered by their smallest vertex.  The
-    rule that fixes every bit of it is the header's ("Shells")."""
+    rule that fixes every bit of it is the header's ("Shells").  `measures`: a Measures, one record per shell, where the mesh was made with
+    measures=True; else None."""
 
-    def __init__(self, vertex_shell, triangle_shell, records, info):
+    def __init__(self, vertex_shell, triangle_shell, records, info, measures=None):
         self.vertex_shell = vertex_shell
         self.triangle_shell = triangle_shell
         self.records = records
         self.info = dict(info)
+        self.measures = measures
 
     def __len__(self):
         return int(self.info["n_shells"])
@@ -871,30 +877,86 @@ class Shells:
         return r[:, 1] - (3 * r[:, 2] + r[:, 3]) // 2 + r[:, 2]
 
 
-def _read_shells(handle, like, destroy=True):
-    """an ft_shells -> Shells of numpy arrays (like = None) or of tensors of like's device, through ft_shells_read; the handle is destroyed"""
+class Measures:
+    """Per-shell measures (ft_shell_measure, the header's "Measures"): `records` is the [S] record array — a numpy structured array with the fields
+    of ft_shell_measure, or, where the call was given a device tensor, a float32 tensor [S, 18] of its device holding the same 72 bytes per shell.
+    The properties give numpy arrays (a device tensor is read back): area float64 [S], volume float64 [S] (positive for a closed body, negative
+    for a closed cavity; no meaning for an open shell), moment float64 [S, 3] (the integral of x over the volume), bbox_min / bbox_max float32
+    [S, 3], n_unmeasured int32 [S] (triangles with a non-finite coordinate), extent_exponent int.  Every bit of them is fixed by the rule;
+    `centroid` = moment / volume is plain numpy and is not."""
+
+    def __init__(self, records):
+        self.records = records
+
+    def __len__(self):
+        return int(self.records.shape[0])
+
+    def host(self):
+        """the records as a numpy structured array [S]"""
+        r = self.records
+        if isinstance(r, np.ndarray):
+            return r
+        return np.ascontiguousarray(r.detach().cpu().numpy()).view(np.dtype(_lib.SHELL_MEASURE_DTYPE)).reshape(-1)
+
+    area = property(lambda self: self.host()["area"])
+    volume = property(lambda self: self.host()["volume"])
+    moment = property(lambda self: self.host()["moment"])
+    bbox_min = property(lambda self: self.host()["bbox_min"])
+    bbox_max = property(lambda self: self.host()["bbox_max"])
+    n_unmeasured = property(lambda self: self.host()["n_unmeasured"])
+
+    @property
+    def extent_exponent(self):
+        e = self.host()["extent_exponent"]
+        return int(e[0]) if len(e) else 0
+
+    @property
+    def centroid(self):
+        """float64 [S, 3]: moment / volume (nan where the volume is 0)"""
+        h = self.host()
+        with np.errstate(all="ignore"):
+            return h["moment"] / h["volume"][:, None]
+
+
+def _read_measures(like, n, call):
+    """n records written by call(out pointer) -> Measures over a numpy record array (like = None) or a float32 tensor [n, 18] of like's device"""
+    if like is None:
+        rec = np.zeros(n, np.dtype(_lib.SHELL_MEASURE_DTYPE))
+        check(call(_hptr(rec) if n else None))
+    else:
+        rec = like.new_empty((n, 18), dtype=like.new_empty(0).float().dtype)
+        check(call(_dptr(rec.data_ptr()) if n else None))
+    return Measures(rec)
+
+
+def _read_shells(handle, like, destroy=True, mesh=None):
+    """an ft_shells -> Shells of numpy arrays (like = None) or of tensors of like's device, through ft_shells_read; the handle is destroyed.  mesh: the
+    ft_mesh the shells were built from — the Shells then carry its shells' Measures (ft_shells_measure)"""
     try:
         info = _lib.ShellsInfo()
         check(lib.ft_shells_get_info(handle, C.byref(info)))
         parts = (_empty(like, (int(info.n_vertices),), "int32"), _empty(like, (int(info.n_triangles),), "int32"), _empty(like, (int(info.n_shells), 4), "int32"))
         ptr = _hptr if like is None else (lambda a: _dptr(a.data_ptr()))
         check(lib.ft_shells_read(handle, *map(ptr, parts)))
-        return Shells(*parts, info={k: int(getattr(info, k)) for k, _ in info._fields_})
+        found = None if mesh is None else _read_measures(like, int(info.n_shells), lambda out: lib.ft_shells_measure(mesh, handle, out))
+        return Shells(*parts, info={k: int(getattr(info, k)) for k, _ in info._fields_}, measures=found)
     finally:
         if destroy:
             lib.ft_shells_destroy(handle)
 
 
 def _keep_mask(shells, keep):
-    """keep= of the mesh methods as one byte per shell: an int k (the k shells with the most triangles, ties going to the lower number), "closed", a
-    bool array of length S, or a callable Shells -> bool array"""
+    """keep= of the mesh methods as one byte per shell: an int k (the k shells with the most triangles, ties going to the lower number), "closed",
+    "bodies" (closed and of positive volume: needs the shells' measures), a bool array of length S, or a callable Shells -> bool array"""
     n = len(shells)
     if callable(keep):
         keep = keep(shells)
     if isinstance(keep, str):
-        if keep != "closed":
-            raise ValueError(f'keep: the only name is "closed", not {keep!r}')
-        mask = shells.closed
+        if keep not in ("closed", "bodies"):
+            raise ValueError(f'keep: the names are "closed" and "bodies", not {keep!r}')
+        if keep == "bodies" and shells.measures is None:
+            raise ValueError('keep="bodies": these shells carry no measures')
+        mask = shells.closed if keep == "closed" else shells.closed & (shells.measures.volume > 0)
     elif isinstance(keep, (int, np.integer)) and not isinstance(keep, (bool, np.bool_)):
         if keep < 0:
             raise ValueError("keep: a count of shells must be >= 0")
@@ -1416,7 +1478,7 @@ class DeviceScene:
                            lambda e, f, *o: check(lib.ft_sample_lattice_device(ctx, sc, C.byref(lat), e, f, *map(_dptr, o))),
                            normal_epsilon, distance, material, bounded)
 
-    def mesh_lattice(self, origin, step, counts, iso=0.0, normal_epsilon=None, material=False, like=None, refine=None, shells=False, keep=None):
+    def mesh_lattice(self, origin, step, counts, iso=0.0, normal_epsilon=None, material=False, like=None, refine=None, shells=False, keep=None, measures=False):
         """ft_mesh_lattice: the surface scene.Object.Form.Distance = iso as triangles, extracted on the device from the distances on
         lattice_points(origin, step, counts) (never bounded) -> Mesh.  normal_epsilon: also SdfForm.normal sdf normal_epsilon v per vertex;
         material: also the handle of the material object.Material.Color picks at v (Mesh.descriptor) — both exactly what sample_points gives
@@ -1425,7 +1487,10 @@ class DeviceScene:
         the surface, to within the edge's length * 2^-refine; triangles are unchanged, normals and materials are taken at the refined vertices.
         shells: the Mesh carries `.shells`, its connected pieces labelled on the device (ft_mesh_shells).  keep (implies shells): only some shells,
         through ft_mesh_select — an int k (the k shells with the most triangles, ties going to the lower number), "closed", a bool array of
-        length S or a callable Shells -> bool array; `.shells` are then those of the selected mesh."""
+        length S or a callable Shells -> bool array; `.shells` are then those of the selected mesh.  measures (implies shells): `.shells.measures`
+        holds each shell's area, signed volume, first moment and box and `.measure` the whole mesh's, computed on the device (ft_shells_measure,
+        ft_mesh_measure; with keep: of the selected mesh); the callable form of keep then receives Shells that carry their measures, and
+        keep="bodies" keeps the closed shells of positive volume: no cavities, no debris of open pieces."""
         lat, _ = _lattice(origin, step, counts)
         if like is not None and not is_device_tensor(like):
             raise ValueError("like: a device tensor (see is_device_tensor) or None")
@@ -1437,7 +1502,7 @@ class DeviceScene:
                 check(lib.ft_mesh_lattice(self.device._ctx, self._scene, C.byref(lat), float(iso), eps, flags, C.byref(handle)))
             else:
                 check(lib.ft_mesh_lattice_refined(self.device._ctx, self._scene, C.byref(lat), float(iso), eps, flags, int(refine), C.byref(handle)))
-            return _read_mesh(handle, like, self.materials, shells, keep)
+            return _read_mesh(handle, like, self.materials, shells, keep, measures)
 
     def slice_lattice(self, origin, step, counts, axis=2, iso=0.0, normal_epsilon=None, material=False, like=None, refine=None):
         """ft_slice_lattice: the contours scene.Object.Form.Distance = iso of every lattice plane normal to `axis` (0, 1, 2: x, y, z), extracted

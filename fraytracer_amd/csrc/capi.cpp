@@ -18,6 +18,7 @@
 #include "ft_slice.h"
 #include "ft_refine.h"
 #include "ft_shells.h"
+#include "ft_measure.h"
 #include "scene.hpp"
 
 #ifndef FT_BUILD_KIND
@@ -88,6 +89,9 @@ struct ft_ctx {
     int shellsStop = 0;                                    // 0: whole labellings; 1 / 2 / 3: they end after the incidence lists / the iterations / the vertex labels, with no shell (ft_ctx_shells_probe: the probe's stages)
     int64_t shellsLast[2] = {0, 0};                        // iterations and synchronisations of the context's last labelling (ft_ctx_shells_last)
     void* shellsWork = nullptr; size_t shellsWorkBytes = 0; // the shell labelling's and the selection's work (ft_shells.h says how much per vertex and triangle)
+    void* measureWork = nullptr; size_t measureWorkBytes = 0; // the measures' per-shell sums, box keys, counters and staged records (ft_measure.h says how much per shell)
+    int measureStop = 0, measureEager = 0;                 // ft_ctx_measure_probe (the probe's stages): calls end after the extent kernel (1) or the terms kernel (2) and write no record; the terms kernel flushes at every iteration
+    unsigned measureGrid = 0;                              // 0: the measures' kernels fill the device; else their workgroups (ft_ctx_measure_grid: the tests' and the probe's grids)
     int refineSkipField = 0;                               // 1: a refinement launches everything but its field rounds, and gives other positions (ft_ctx_refine_probe: the probe's stages)
     uint32_t orderNum = 1, orderDen = 1;                   // a tile is heavy from orderNum / orderDen of the mean cost on (ft_ctx_tile_order_rule: the probes' other rules)
 };
@@ -632,6 +636,7 @@ void ft_ctx_destroy(ft_ctx* c) {
         if (c->sliceWork) (void)hipFree(c->sliceWork);
         if (c->refineWork) (void)hipFree(c->refineWork);
         if (c->shellsWork) (void)hipFree(c->shellsWork);
+        if (c->measureWork) (void)hipFree(c->measureWork);
         for (auto& r : c->hostRegs) (void)hipHostUnregister(r.first);
         for (auto e : c->syncEvents) (void)hipEventDestroy(e);
         if (c->lane1) { (void)hipStreamSynchronize(c->lane1); (void)hipStreamDestroy(c->lane1); }
@@ -2519,6 +2524,149 @@ int ft_ctx_shells_last(ft_ctx* c, int64_t* last) {
 int ft_ctx_shells_probe(ft_ctx* c, int32_t stop) {
     if (!c || stop < 0 || stop > 3) return setErr(FT_ERR_INVALID, "bad argument");
     c->shellsStop = stop;
+    return FT_OK;
+}
+
+// ---- measures: ft_shells_measure, ft_mesh_measure (measure.hip; the rule is the header's "Measures") ------------------------------------------------
+namespace {
+
+const char* const kMeasureKernels[FT_MEASURE_KERNELS] = {"measure extent and box", "measure terms", "measure finish", "measure convert"};
+
+int launchMeasure(ft_ctx* c, int kernel, const FtMeasureArgs& a) {
+    int perCU = 0;
+    const hipError_t e = ft_measure_occupancy(kernel, &perCU);
+    if (e != hipSuccess) return hipFail(e, (std::string("occupancy of the ") + kMeasureKernels[kernel] + " kernel").c_str());
+    int rc = clampPerCU(c, kMeasureKernels[kernel], perCU); if (rc) return rc;
+    const int domain = ft_measure_domain(kernel);
+    const uint64_t items = domain == 0 ? a.nV : (domain == 1 ? a.nT : a.nS);
+    unsigned blocks = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)c->numCUs * perCU, (items + FT_MEASURE_BLOCK - 1) / FT_MEASURE_BLOCK));
+    if (c->measureGrid) blocks = c->measureGrid;
+    return timedLaunch(c, c->stream, "ft_launch_measure", [&] { return ft_launch_measure(kernel, &a, blocks, c->stream); });
+}
+
+// is `p` device memory of this process (a host-only context never asks the runtime: everything is host memory to it)
+bool measureOutOnDevice(const ft_ctx* c, const void* p) {
+    if (!c->hasDevice || !p) return false;
+    hipPointerAttribute_t attr;
+    if (hipPointerGetAttributes(&attr, p) != hipSuccess) { (void)hipGetLastError(); return false; }      // plain malloc memory: "invalid value"
+    return attr.type == hipMemoryTypeDevice;
+}
+
+// The work memory of a call over nS shells, and the three launches.  Labels NULL: every vertex and triangle has label 0.  `out`: nS records in host
+// or device memory (toDevice); the host form stages them in the work memory and synchronises the stream once.
+int runMeasure(ft_ctx* c, const void* dVertices, size_t nV, const void* dTriangles, size_t nT, const void* dVertexShell, const void* dTriangleShell, size_t nS,
+               ft_shell_measure* out, bool toDevice) {
+    static_assert(sizeof(ft_shell_measure) == FT_MEASURE_RECORD_BYTES, "layout");
+    size_t at = 0;
+    auto take = [&](size_t bytes) { const size_t o = at; at = align256(at + bytes); return o; };
+    // zeroed: sums, maximum keys, counters, extent (adjacent); set to 0xff: minimum keys
+    const size_t oSums = take(nS * 2 * FT_MEASURE_SUMS * 8), oMax = take(nS * 12), oBad = take(nS * 4), oExtent = take(4), oMin = take(nS * 12), zeroed = oMin;
+    const size_t oStage = take(nS * sizeof(ft_shell_measure));
+    int rc;
+    if ((rc = ensureBytes(c->measureWork, c->measureWorkBytes, at))) return rc;
+    unsigned char* wk = static_cast<unsigned char*>(c->measureWork);
+    FtMeasureArgs a{};
+    a.vertices = static_cast<const uint32_t*>(dVertices); a.triangles = static_cast<const int32_t*>(dTriangles);
+    a.vertexShell = static_cast<const int32_t*>(dVertexShell); a.triangleShell = static_cast<const int32_t*>(dTriangleShell);
+    a.nV = (uint32_t)nV; a.nT = (uint32_t)nT; a.nS = (uint32_t)nS;
+    a.sums = reinterpret_cast<unsigned long long*>(wk + oSums);
+    a.boxMax = reinterpret_cast<uint32_t*>(wk + oMax); a.unmeasured = reinterpret_cast<uint32_t*>(wk + oBad); a.extent = reinterpret_cast<uint32_t*>(wk + oExtent);
+    a.boxMin = reinterpret_cast<uint32_t*>(wk + oMin);
+    a.out = toDevice ? static_cast<void*>(out) : static_cast<void*>(wk + oStage);
+    a.eager = c->measureEager;
+    HIP_TRY(hipMemsetAsync(wk, 0, zeroed, c->stream));
+    HIP_TRY(hipMemsetAsync(wk + oMin, 0xff, nS * 12, c->stream));
+    if (nV && (rc = launchMeasure(c, FT_MEASURE_K_EXTENT, a))) return rc;
+    if (c->measureStop == 1) return FT_OK;
+    if (nT && (rc = launchMeasure(c, FT_MEASURE_K_TERMS, a))) return rc;
+    if (c->measureStop == 2) return FT_OK;
+    if ((rc = launchMeasure(c, FT_MEASURE_K_FINISH, a))) return rc;
+    if (toDevice) return FT_OK;
+    hipError_t e = hipMemcpyAsync(out, wk + oStage, nS * sizeof(ft_shell_measure), hipMemcpyDeviceToHost, c->stream);
+    const hipError_t se = hipStreamSynchronize(c->stream);             // the one synchronisation of the host form
+    if (e == hipSuccess) e = se;
+    return e == hipSuccess ? FT_OK : hipFail(e, "measure: records");
+}
+
+// what both public entries share once their own NULL checks are done: alignment, empty input, device, run
+int measureMesh(const ft_mesh* m, const ft_shells* s, size_t nS, ft_shell_measure* out) {
+    ft_ctx* c = m->ctx;
+    const bool nothing = nS == 0 || (m->nV == 0 && m->nT == 0);
+    if (!out && !nothing) return setErr(FT_ERR_INVALID, "null out pointer");
+    const bool toDevice = measureOutOnDevice(c, out);
+    if (toDevice && (reinterpret_cast<uintptr_t>(out) & 7u)) return setErr(FT_ERR_INVALID, "measure: the device records must be 8-byte aligned");
+    if (nothing) return FT_OK;
+    int rc = requireDevice(c); if (rc) return rc;
+    return runMeasure(c, m->dVertices, (size_t)m->nV, m->dTriangles, (size_t)m->nT, s ? s->dVertexShell : nullptr, s ? s->dTriangleShell : nullptr, nS, out, toDevice);
+}
+
+}  // namespace
+
+int ft_shells_measure(const ft_mesh* m, const ft_shells* s, ft_shell_measure* out) {
+    if (!m) return setErr(FT_ERR_INVALID, "null mesh");
+    if (!s) return setErr(FT_ERR_INVALID, "null shells");
+    if (!out && s->nS != 0 && (m->nV != 0 || m->nT != 0)) return setErr(FT_ERR_INVALID, "null out pointer");
+    if (s->ctx != m->ctx || s->meshSerial != m->serial) return setErr(FT_ERR_INVALID, "measure: the shells were not built from this mesh");
+    return measureMesh(m, s, (size_t)s->nS, out);
+}
+int ft_mesh_measure(const ft_mesh* m, ft_shell_measure* out) {
+    if (!m) return setErr(FT_ERR_INVALID, "null mesh");
+    return measureMesh(m, nullptr, 1, out);
+}
+
+// Internal (not in the header, like ft_ctx_shells_tile; the tests and tools/measure_probe.py): the measures of host arrays with arbitrary labels —
+// vertices float32 [nV][3], triangles int32 [nT][3], vertex_label int32 [nV] and triangle_label int32 [nT] (either may be NULL: label 0), nS shells ->
+// nS records in host memory.  Nothing is validated on the host: the kernels check every index and label (an index outside 0 .. nV - 1 makes the
+// triangle unmeasured, a label outside 0 .. nS - 1 leaves the triangle or vertex out).
+int ft_ctx_measure_triangles(ft_ctx* c, const float* vertices, int64_t nV, const int32_t* triangles, int64_t nT, const int32_t* vertex_label,
+                             const int32_t* triangle_label, int64_t nS, ft_shell_measure* out) {
+    if (!c) return setErr(FT_ERR_INVALID, "null context");
+    if ((!vertices && nV) || (!triangles && nT) || (!out && nS)) return setErr(FT_ERR_INVALID, "null argument");
+    if (nV < 0 || nT < 0 || nS < 0 || nV >= ((int64_t)1 << 31) || nT >= ((int64_t)1 << 31) || nS >= ((int64_t)1 << 31)) return setErr(FT_ERR_INVALID, "measure: counts must be in 0 .. 2^31 - 1");
+    if (nS == 0) return FT_OK;
+    int rc = requireDevice(c); if (rc) return rc;
+    size_t at = 0;
+    auto take = [&](size_t bytes) { const size_t o = at; at = align256(at + bytes); return o; };
+    const size_t oV = take((size_t)nV * 12), oT = take((size_t)nT * 12), oVL = take((size_t)nV * 4), oTL = take((size_t)nT * 4);
+    if ((rc = ensureScratch(c, std::max<size_t>(at, 256)))) return rc;
+    unsigned char* base = static_cast<unsigned char*>(c->scratch);
+    const struct { size_t at; const void* host; size_t bytes; } parts[4] = {
+        {oV, vertices, (size_t)nV * 12}, {oT, triangles, (size_t)nT * 12}, {oVL, vertex_label, (size_t)nV * 4}, {oTL, triangle_label, (size_t)nT * 4}};
+    for (const auto& p : parts)
+        if (p.host && p.bytes) HIP_TRY(hipMemcpyAsync(base + p.at, p.host, p.bytes, hipMemcpyHostToDevice, c->stream));
+    return runMeasure(c, base + oV, (size_t)nV, base + oT, (size_t)nT, vertex_label ? base + oVL : nullptr, triangle_label ? base + oTL : nullptr, (size_t)nS, out, false);
+}
+// Internal (the tests): the finish kernel's conversion alone — sums: n pairs {low, high} of 64-bit words (two's complement) in host memory ->
+// out[i] = fl64(sums[i]) * 2^-s as a double, in host memory
+int ft_ctx_measure_finish(ft_ctx* c, const uint64_t* sums, int64_t n, int32_t s, double* out) {
+    if (!c) return setErr(FT_ERR_INVALID, "null context");
+    if (n < 0 || n >= ((int64_t)1 << 31) || ((!sums || !out) && n)) return setErr(FT_ERR_INVALID, "bad argument");
+    if (n == 0) return FT_OK;
+    int rc = requireDevice(c); if (rc) return rc;
+    const size_t in = align256((size_t)n * 16);
+    if ((rc = ensureScratch(c, in + (size_t)n * 8))) return rc;
+    unsigned char* base = static_cast<unsigned char*>(c->scratch);
+    HIP_TRY(hipMemcpyAsync(base, sums, (size_t)n * 16, hipMemcpyHostToDevice, c->stream));
+    FtMeasureArgs a{};
+    a.nS = (uint32_t)n; a.sums = reinterpret_cast<unsigned long long*>(base); a.out = base + in; a.scale = s;
+    if ((rc = launchMeasure(c, FT_MEASURE_K_CONVERT, a))) return rc;
+    HIP_TRY(hipMemcpyAsync(out, base + in, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return FT_OK;
+}
+// Internal (the tests and the probe): the workgroups of this context's measure launches; 0: as many as fill the device.  Every grid gives the same bytes.
+int ft_ctx_measure_grid(ft_ctx* c, int32_t workgroups) {
+    if (!c || workgroups < 0 || workgroups > 65536) return setErr(FT_ERR_INVALID, "bad argument");
+    c->measureGrid = (unsigned)workgroups;
+    return FT_OK;
+}
+
+// Internal (tools/measure_probe.py): stop = 0 whole calls; 1 / 2: this context's measure calls end after the extent kernel / after the terms kernel and
+// write no record, so that a stage's kernel time is a difference of two figures.  eager = 1: the terms kernel flushes every lane's partial sums at
+// every iteration — the form without the accumulation in registers, which gives the same bytes
+int ft_ctx_measure_probe(ft_ctx* c, int32_t stop, int32_t eager) {
+    if (!c || stop < 0 || stop > 2 || eager < 0 || eager > 1) return setErr(FT_ERR_INVALID, "bad argument");
+    c->measureStop = stop; c->measureEager = eager;
     return FT_OK;
 }
 

@@ -315,13 +315,18 @@ namespace Mesh {
 struct Triangles {
     std::vector<ft_vec3> vertices; std::vector<int32_t> triangles; std::vector<ft_vec3> normal; std::vector<int32_t> material; int64_t skipped = 0;
     std::vector<int32_t> vertexShell, triangleShell; std::vector<ft_shell> shells; ft_shells_info shellsInfo{};
+    // shellMeasures (one per shell) and measure (the whole mesh): filled where the request asked for measures (the header's "Measures")
+    std::vector<ft_shell_measure> shellMeasures; ft_shell_measure measure{};
 };
 // refineSteps: -1 the mesher's vertices; 0 .. 32 bisection rounds that move every vertex along its lattice edge onto the surface (ft_mesh_lattice_refined)
 // shells: also label the mesh's shells (ft_mesh_shells); keepLargest: > 0 keeps only that many shells, the ones with the most triangles, ties going to
-// the lower number (ft_mesh_select), and implies shells — the labels are then those of the selected mesh
-struct Request { float iso = 0.0f; bool normal = false; float normalEpsilon = 0.0f; bool material = false; int32_t refineSteps = -1; bool shells = false; int32_t keepLargest = 0; };
+// the lower number (ft_mesh_select), and implies shells — the labels are then those of the selected mesh.  measures: also each shell's and the whole
+// mesh's area, signed volume, first moment and box (ft_shells_measure, ft_mesh_measure; implies shells); keepBodies: keeps only the closed shells of
+// positive volume — no cavities, no open debris — before keepLargest is applied to what is left
+struct Request { float iso = 0.0f; bool normal = false; float normalEpsilon = 0.0f; bool material = false; int32_t refineSteps = -1; bool shells = false; int32_t keepLargest = 0;
+                 bool measures = false; bool keepBodies = false; };
 struct ShellsOwner { ft_shells* s = nullptr; ~ShellsOwner() { ft_shells_destroy(s); } };
-inline void readShells(ft_mesh* mesh, Triangles& out) {
+inline void readShells(ft_mesh* mesh, Triangles& out, bool measures = false) {
     ShellsOwner sh;
     check(ft_mesh_shells(mesh, &sh.s));
     check(ft_shells_get_info(sh.s, &out.shellsInfo));
@@ -329,6 +334,27 @@ inline void readShells(ft_mesh* mesh, Triangles& out) {
     out.triangleShell.resize((size_t)out.shellsInfo.n_triangles);
     out.shells.resize((size_t)out.shellsInfo.n_shells);
     check(ft_shells_read(sh.s, out.vertexShell.data(), out.triangleShell.data(), out.shells.data()));
+    if (!measures) return;
+    out.shellMeasures.resize(out.shells.size());
+    check(ft_shells_measure(mesh, sh.s, out.shellMeasures.data()));
+    check(ft_mesh_measure(mesh, &out.measure));                        // an empty mesh: nothing is written, the record stays zero
+}
+// the mesh of the closed shells of positive volume of `mesh`, which is destroyed
+inline ft_mesh* keepBodies(ft_mesh* mesh) {
+    struct Owner { ft_mesh* m; ~Owner() { ft_mesh_destroy(m); } } own{mesh};
+    ShellsOwner sh;
+    check(ft_mesh_shells(mesh, &sh.s));
+    ft_shells_info info{};
+    check(ft_shells_get_info(sh.s, &info));
+    std::vector<ft_shell> records((size_t)info.n_shells);
+    std::vector<ft_shell_measure> measures(records.size());
+    check(ft_shells_read(sh.s, nullptr, nullptr, records.data()));
+    check(ft_shells_measure(mesh, sh.s, measures.data()));
+    std::vector<uint8_t> keep(records.size(), 0);
+    for (size_t i = 0; i < keep.size(); ++i) keep[i] = records[i].n_border_edges == 0 && measures[i].volume > 0.0;
+    ft_mesh* selected = nullptr;
+    check(ft_mesh_select(mesh, sh.s, keep.data(), (int64_t)keep.size(), &selected));
+    return selected;
 }
 // the mesh of the keepLargest largest shells of `mesh`, which is destroyed
 inline ft_mesh* keepLargest(ft_mesh* mesh, int32_t k) {
@@ -349,6 +375,7 @@ inline ft_mesh* keepLargest(ft_mesh* mesh, int32_t k) {
     return selected;
 }
 inline Triangles read(ft_mesh* mesh, const Request& r = Request{}) {
+    if (r.keepBodies) mesh = keepBodies(mesh);
     if (r.keepLargest > 0) mesh = keepLargest(mesh, r.keepLargest);
     struct Owner { ft_mesh* m; ~Owner() { ft_mesh_destroy(m); } } own{mesh};
     ft_mesh_info info{};
@@ -361,7 +388,7 @@ inline Triangles read(ft_mesh* mesh, const Request& r = Request{}) {
     if (info.has_material) out.material.resize((size_t)info.n_vertices);
     check(ft_mesh_read(mesh, out.vertices.data(), out.triangles.data(), info.has_normal ? out.normal.data() : nullptr,
                        info.has_material ? out.material.data() : nullptr));
-    if (r.shells || r.keepLargest > 0) readShells(mesh, out);
+    if (r.shells || r.keepLargest > 0 || r.measures || r.keepBodies) readShells(mesh, out, r.measures);
     return out;
 }
 inline Triangles ofLattice(const SdfScene& scene, const ft_lattice& lattice, const Request& r = Request{}) {

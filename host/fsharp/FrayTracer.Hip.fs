@@ -56,6 +56,10 @@ type FtPolyline = { First : int; Count : int; Slice : int; Closed : int }
 /// ft_slices_info (48 bytes)
 [<Struct; StructLayout(LayoutKind.Sequential)>]
 type FtSlicesInfo = { NPoints : int64; NPolylines : int64; NClosed : int64; NSkipped : int64; Axis : int; NSlices : int; HasNormal : int; HasMaterial : int }
+/// ft_shell_measure (72 bytes): a shell's area, signed volume (positive: a body, negative: a cavity), first moment (the centroid is Moment / Volume),
+/// box, the triangles left out for a non-finite coordinate, and the call's extent exponent E.  moment[3] and the two float[3] boxes are spelled out
+[<Struct; StructLayout(LayoutKind.Sequential)>]
+type FtShellMeasure = { Area : float; Volume : float; MomentX : float; MomentY : float; MomentZ : float; BboxMin : Vector3; BboxMax : Vector3; NUnmeasured : int; ExtentExponent : int }
 
 /// ft_form_trace_result: SdfFormTraceResult voption (Types.fs:32-37), Hit = 0 is ValueNone
 [<Struct; StructLayout(LayoutKind.Sequential)>]
@@ -157,6 +161,10 @@ module Native =
     [<DllImport(Lib)>] extern int ft_shells_read(nativeint shells, nativeint vertexShell, nativeint triangleShell, nativeint records)
     [<DllImport(Lib)>] extern void ft_shells_destroy(nativeint shells)
     [<DllImport(Lib)>] extern int ft_mesh_select(nativeint mesh, nativeint shells, nativeint keep, int64 nKeep, nativeint selected)
+    // measures (the header's "Measures" states the rule): per shell, or for the whole mesh, area, signed volume, first moment and box, summed exactly on
+    // the device.  records: a pinned FtShellMeasure[] (ShellMeasure records of 72 bytes: one per shell, or one), or device memory, 8-byte aligned
+    [<DllImport(Lib)>] extern int ft_shells_measure(nativeint mesh, nativeint shells, nativeint records)
+    [<DllImport(Lib)>] extern int ft_mesh_measure(nativeint mesh, nativeint record)
     [<DllImport(Lib)>] extern int ft_form_try_trace(nativeint ctx, nativeint scene, Ray[] rays, int64 n, [<Out>] FtFormTraceResult[] out, FtStats& stats)
     [<DllImport(Lib)>] extern int ft_object_try_trace(nativeint ctx, nativeint scene, Ray[] rays, int64 n, [<Out>] FtObjectTraceResult[] out, FtStats& stats)
     // ray buffers in device memory (rays 16-byte aligned, 32 B each): no scratch, no copy, not synchronised; pair with ft_collect_stats

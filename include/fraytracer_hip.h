@@ -653,6 +653,66 @@ int ft_shells_read(const ft_shells*, int32_t* vertex_shell, int32_t* triangle_sh
 void ft_shells_destroy(ft_shells*);
 int ft_mesh_select(const ft_mesh*, const ft_shells*, const uint8_t* keep, int64_t n_keep, ft_mesh** out);
 
+/* Measures: per shell of a labelled mesh its area, signed volume, first moment and box, computed on the device where the mesh lies.  Floating-point
+ * sums are not associative, so the rule makes the sums exact: every triangle gives float64 terms by a fixed sequence of individually rounded
+ * operations, every term is rounded ONCE to a multiple of a power of two that the call fixes in advance, and the quantised terms are added as
+ * integers, where order cannot matter.  Every bit of every result is a pure function of the input; this is the rule, all of it.
+ *
+ * Input: vertices float32[nV][3], triangles int32[nT][3], a label per triangle and per vertex (ft_shells' triangle_shell and vertex_shell; in the
+ *     whole-mesh form every triangle and every vertex has label 0 and there is one shell).
+ * Extent: m is the largest |x| over all finite coordinates of all nV vertices, used by a triangle or not.  E = 0 if m == 0 (or no coordinate is
+ *     finite), else ilogb(m) + 1, so that m < 2^E; denormals count by their true exponent.  Hence -148 <= E <= 128 (the smallest positive float32
+ *     is 2^-149).
+ * Measured triangles: a triangle is measured iff its three indices are in 0 .. nV - 1 (the mesher guarantees it) and all nine of its coordinates
+ *     are finite.  Any other triangle adds nothing to any sum and 1 to its shell's n_unmeasured.  Zero-area triangles are measured.
+ * Terms of a measured triangle (a, b, c): the nine float32 coordinates are widened to float64 (exact); then every -, *, + is one float64
+ *     operation, never fused, operands in the order written:
+ *         u = b - a,  v = c - a
+ *         n = (u.y v.z - u.z v.y,  u.z v.x - u.x v.z,  u.x v.y - u.y v.x)
+ *         A_t = 0.5 * sqrt((n.x n.x + n.y n.y) + n.z n.z)                    sqrt correctly rounded
+ *         W_t = (a.x (b.y c.z - b.z c.y) + a.y (b.z c.x - b.x c.z)) + a.z (b.x c.y - b.y c.x)     six times the signed volume of (0, a, b, c)
+ *         M_t,i = W_t * ((a_i + b_i) + c_i)                                    i = x, y, z
+ * Bounds, from |coordinate| < 2^E (exact values first, then the roundings):
+ *     area:    |u_i|, |v_i| < 2^(E+1), so |n_i| < 2 * 2^(2E+2) = 2^(2E+3), |n|^2 < 3 * 2^(4E+6) and A_t < 0.5 * sqrt(3) * 2^(2E+3) < 2^(2E+3).
+ *              B_A = 2E + 3.
+ *     volume:  each of the three brackets is below 2 * 2^(2E) in magnitude, each product with a coordinate below 2^(3E+1), their sum below
+ *              3 * 2^(3E+1) < 2^(3E+3).  B_W = 3E + 3.
+ *     moment:  |(a_i + b_i) + c_i| < 3 * 2^E, so |M_t,i| < 3 * 2^(3E+1) * 3 * 2^E = 18 * 2^(4E) < 2^(4E+5).  B_M = 4E + 5.
+ *     Each term is reached by about a dozen roundings of relative size 2^-53 of intermediates that obey the same bounds, and each exact bound
+ *     leaves a factor of at least 1.15 (area; 1.33 volume, 1.77 moment) to its power of two, so a rounded term stays below 2^B, let alone 2^(B+1).
+ *     No intermediate leaves float64's normal range: the smallest non-zero product of four float32 values is 2^-596, the largest term 2^517.
+ * Quantisation: for a kind K with bound exponent B_K, s_K = 90 - B_K and q = round-half-to-even(term * 2^s_K) as a mathematical integer, so
+ *     |q| <= 2^91 (2^90 by the bounds above).  With nT < 2^31 every sum lies inside +-2^122: a 128-bit two's-complement accumulator never
+ *     overflows.
+ * Sums: per shell and kind Q_K = the sum of q over the shell's measured triangles, exactly.
+ * Results: S_K = fl64(Q_K) * 2^(-s_K): the int128 -> float64 conversion rounds half to even, the scaling is exact (every exponent stays inside
+ *     float64's normal range for -148 <= E <= 128).  area = S_A, volume = S_W / 6.0, moment[i] = S_M,i / 24.0, each one float64 division.
+ *     moment is the integral of x over the enclosed volume; the centroid is moment / volume.
+ * Sign: with the mesher's orientation (counter-clockwise seen from the outside) a closed body has volume > 0 and a closed cavity volume < 0.  The
+ *     volume and moment of an open shell are the rule's numbers and mean nothing geometric.
+ * Box: per shell, bbox_min[i] / bbox_max[i] over the finite values of coordinate i of the vertices labelled with that shell, compared by the
+ *     ordered-integer key of the float32 bits (bits ^ 0x80000000 for a clear sign bit, ~bits for a set one, so -0 < +0): the result is one of the
+ *     input bit patterns.  A shell without a finite value in a coordinate gets +inf / -inf there.
+ * Record: ft_shell_measure, 72 B.  extent_exponent is E, the same in every record of a call.
+ * Empty input: a mesh without vertices and triangles, or zero shells, gives FT_OK with nothing written and needs no device.
+ *
+ * ft_shells_measure writes n_shells records, ft_mesh_measure one record for the whole mesh.  out is host memory or device memory (8-byte aligned):
+ * the direction is taken from the address, as in ft_shells_read.  The host form synchronises the context's stream once; the device form does not
+ * synchronise: the records are ordered with whatever the context launches next.  A selected mesh (ft_mesh_select) measures like any other.
+ * Refusals, all made before the device is asked for, in this order: FT_ERR_INVALID for NULL (mesh, shells; out unless nothing would be written),
+ * for shells that were not built from that mesh (the serial number ft_mesh_select checks: shells of a triangle list measure nothing), for a
+ * misaligned device pointer; empty input: FT_OK; then FT_ERR_NO_DEVICE on a host-only context; FT_ERR_HIP for a failed allocation.
+ * Work memory, in a buffer the context keeps: 108 B per shell (five 128-bit sums, six box keys, one counter), 72 B per shell of staging for the
+ * host form, and the 4-byte extent. */
+typedef struct ft_shell_measure {
+    double area, volume, moment[3];
+    float bbox_min[3], bbox_max[3];
+    int32_t n_unmeasured;         /* triangles of the shell that were not measured */
+    int32_t extent_exponent;      /* E */
+} ft_shell_measure;               /* 72 B */
+int ft_shells_measure(const ft_mesh*, const ft_shells*, ft_shell_measure* out);
+int ft_mesh_measure(const ft_mesh*, ft_shell_measure* out);
+
 /* Single-process multi-GPU form (what an F# host would call): the flattened scene is
  * re-uploaded to each further device with ft_scene_clone, every device renders its column
  * stripes (stripe_rank = index in ctxs[], stripe_ranks = n) on its own host thread, and the
