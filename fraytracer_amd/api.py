@@ -461,6 +461,10 @@ class Device:
                # exact shortcuts like "cert" / "cert_policy" (same frame, counters and flags; sdf_evals falls):
                # FT_OPT_OCCL, the occlusion certificate (1 default, 0 off), and FT_OPT_OCCL_POLICY, its schedule word
                "occl": _lib.FT_OPT_OCCL, "occl_policy": _lib.FT_OPT_OCCL_POLICY}
+    # options of a stream of frames, named like the ones above but kept apart from them (OPTIONS is the list the ABI test pins):
+    # FT_OPT_TRY_HINT, 1 (default) a tile's bundle-certificate tries follow what its last frame recorded, 2 record only, 0 off; same frame, fewer sdf_evals
+    # (tests/helpers.py options_left_at_defaults walks OPTIONS only: a test that changes one of these restores it itself, tests/test_try_hint.py checks its own)
+    STREAM_OPTIONS = {"try_hint": _lib.FT_OPT_TRY_HINT}
 
     def set_option(self, name, value):
         """ft_ctx_set_option: per-context switches (the library reads no environment variables)"""
@@ -472,7 +476,7 @@ class Device:
         return int(v.value)
 
     def _option_id(self, name):
-        return self.OPTIONS[name]
+        return self.OPTIONS[name] if name in self.OPTIONS else self.STREAM_OPTIONS[name]
 
     # constructor twins ---------------------------------------------------------------------------
     def sphere(self, c, r): return check(lib.ft_form_sphere(self._ctx, C.byref(_lib.Sphere(_vec(c), r))))

@@ -78,6 +78,7 @@ struct ft_ctx {
     int optOccl = 1;                                       // FT_OPT_OCCL: the lean kernel's occlusion certificate (kernels.hip ft_occlusion_certificate); needs optEscape
     int optOcclPolicy = 0;                                 // FT_OPT_OCCL_POLICY: 0 = the shipped schedule (FT_OCCL_PERIOD ...)
     int optOrder = 1;                                      // FT_OPT_ORDER: 1 = frames hand their heavy tiles out first, from the costs the scene's last launch of the same grid recorded; 2 = record only; 0 = off
+    int optTryHint = 1;                                    // FT_OPT_TRY_HINT: 1 = a frame's tiles schedule their bundle-certificate tries from what the scene's last launch of the same grid recorded per tile; 2 = record only; 0 = off
     int fieldBrick = -1;                                   // brick shape of the lattice launches: -1 by kernel family (launchField), else an index into FT_FIELD_BRICKS (ft_ctx_field_brick: the probe's shapes)
     uint32_t meshTile = FT_MESH_TILE_DEFAULT;              // lattice points per workgroup of the mesher's kernels (ft_ctx_mesh_tile: the probe's tiles)
     uint32_t sliceTile = FT_SLICE_TILE_DEFAULT;            // items per workgroup of the slicer's tiled kernels (ft_ctx_slice_tile: the tests' and the probe's tiles)
@@ -99,6 +100,8 @@ struct ft_ctx {
 // FT_OPT_ORDER: what a scene keeps per render lane between two frame launches (launchTrace; kernels.hip "Tile order").  cost, order and work are one
 // allocation; key is everything that fixes the tile grid and the kernel of the launch that recorded cost — not the camera, epsilon, Length or lights:
 // an order made for another view is only another permutation.
+// FT_OPT_TRY_HINT: hint is the third array of that allocation, one word per tile (ft_kernels.h "Try hints"), under the same key: a hint made for another view only
+// moves a tile's tries.
 struct TileOrderKey {
     int32_t W, H, x0, nCols;
     uint32_t stripeW, stripeRanks, stripeRank, nJobs, variant, libm;
@@ -108,9 +111,11 @@ struct TileOrderKey {
     }
 };
 struct TileOrderSlot {
-    uint32_t* cost = nullptr; uint32_t* order = nullptr; void* work = nullptr;
+    uint32_t* cost = nullptr; uint32_t* order = nullptr; uint32_t* hint = nullptr; void* work = nullptr;
     uint32_t capTiles = 0;
     bool keyed = false, hasOrder = false;                  // key describes cost; order was built from cost
+    float hintCam[12] = {};                                // the camera of the launch that filled hint: a launch follows the words only from a view close to it (tileOrder)
+    bool hasHint = false, usedHint = false; TileOrderKey hintKey{};   // usedHint: that launch followed the words before it; a launch of hintKey's grid filled hint (its own flag and key: FT_OPT_ORDER = 0 clears keyed and records no costs)
     bool usedOrder = false;                                // the launch that recorded cost handed its tiles out in an order (ft_scene_tile_order_used)
     TileOrderKey key{};
 };
@@ -345,11 +350,12 @@ TileOrderSlot* tileOrderSlot(const ft_scene* s, int lane, uint32_t nTiles) {
     if (t.capTiles >= nTiles) return &t;
     if (t.cost) (void)hipFree(t.cost);                    // waits for whatever still uses it
     t = TileOrderSlot{};
-    const size_t words = 2 * (size_t)nTiles, bytes = align256(words * sizeof(uint32_t)) + ft_tile_order_work_bytes(nTiles);
+    const size_t words = 3 * (size_t)nTiles, bytes = align256(words * sizeof(uint32_t)) + ft_tile_order_work_bytes(nTiles);
     void* p = nullptr;
     if (hipMalloc(&p, bytes) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
     t.cost = static_cast<uint32_t*>(p);
     t.order = t.cost + nTiles;
+    t.hint = t.order + nTiles;
     t.work = static_cast<unsigned char*>(p) + align256(words * sizeof(uint32_t));
     t.capTiles = nTiles;
     return &t;
@@ -457,18 +463,58 @@ void occlSchedule(const ft_ctx* c, const ft::FlatScene& f, FtRenderArgs& a) {
 // An eligible launch records what each tile cost.  Where the slot's last launch had the same grid and kernel, it also hands the tiles out in
 // the order built from that launch's costs.  A context with FT_OPT_GUIDED set is never eligible: the guided hand-out changes the grab size.
 // A launch that is not eligible leaves the slot alone.  -> the slot the launch records into, nullptr: none
+// (With FT_OPT_ORDER = 0 and FT_OPT_TRY_HINT on, the slot is still allocated and a.tileCost set — the kernel records hints where it records costs — so
+// the kernel writes costs nobody reads: the slot stays unkeyed for the order and ft_scene_tile_costs reports none.)
+// FT_OPT_TRY_HINT.  The same launches are eligible, and record per tile the rounds their bundle certificates held on (the kernel writes them where it writes
+// the costs, so a.tileCost is set for them too).  A launch follows the words of the slot's last launch where that had the same grid and kernel AND its
+// certificate schedule is word 0 of FT_OPT_CERT_POLICY with the per-lane tries left out (certSchedule's tile-width rule): an explicit word is taken as it
+// stands, and a wide-tiled frame keeps the schedule its evaluation counts are known by.  A slot that cannot be had leaves the frame unhinted.
+// The view must also be close to the one the words were recorded from: measured on C3 at 4096^2, a camera turned by 1 or 8 pixels a frame gains from
+// its last frame's hints and one turned by 64 pixels a frame loses (+0.8 % sdf_evals, +2 % kernel time: holds found up to three rounds late), so a launch whose
+// image moved by more than FT_HINT_MAX_SHIFT pixels, two tiles, records and does not follow.
+constexpr double FT_HINT_MAX_SHIFT = 16.0;
+// An upper estimate, in pixels, of how far the image of the scene moves between two cameras (12 floats each: position, forward, up, right as scaled):
+// the turn of the forward direction, the change of the up and right vectors at the frame's edge, and the move of the position seen from the near side
+// of the support sphere, each over one pixel's size at unit distance.  +inf where it cannot be told.
+double cameraShiftPixels(const float* p, const float* q, float maxSize, const ft::FlatScene& f) {
+    auto len = [](const double* v) { return std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]); };
+    double d[4][3], fp[3], fq[3], ec[3];
+    for (int v = 0; v < 4; ++v) for (int i = 0; i < 3; ++i) d[v][i] = (double)q[3 * v + i] - (double)p[3 * v + i];
+    for (int i = 0; i < 3; ++i) { fp[i] = p[3 + i]; fq[i] = q[3 + i]; ec[i] = (double)q[i] - f.hdr.escC[i]; }
+    const double lp = len(fp), lq = len(fq);
+    const double up[3] = {q[6], q[7], q[8]}, rt[3] = {q[9], q[10], q[11]};
+    const double side = std::max(len(up), len(rt));
+    if (!(lp > 0.0) || !(lq > 0.0) || !(side > 0.0) || !(maxSize > 0.0f)) return INFINITY;
+    const double pixel = side / (double)maxSize / lq;                                      // as certSchedule prices a tile
+    const double turn[3] = {fq[0] / lq - fp[0] / lp, fq[1] / lq - fp[1] / lp, fq[2] / lq - fp[2] / lp};
+    const double nearSide = std::max(len(ec) - (double)f.hdr.escR, 0.1 * (double)f.hdr.escR);
+    const double moved = len(d[0]);
+    if (moved > 0.0 && !(nearSide > 0.0)) return INFINITY;
+    const double shift = len(turn) / pixel + (len(d[2]) + len(d[3])) / side * 0.5 * (double)maxSize + (moved > 0.0 ? moved / nearSide / pixel : 0.0);
+    return shift == shift ? shift : INFINITY;
+}
 TileOrderSlot* tileOrder(const ft_ctx* c, const ft_scene* s, int lane, const FtTraceKey& key, FtRenderArgs& a) {
-    a.tileCost = nullptr; a.tileOrder = nullptr;
+    a.tileCost = nullptr; a.tileOrder = nullptr; a.tileHint = nullptr; a.tryHint = 0u;
     TileOrderSlot* slot = nullptr;
     if (key.form == FT_FORM_FRAME && !key.ext && key.variant == 1u && a.mode == 0u && a.spp == 1u && a.chunk == 64u && a.refillMin == 64u && !c->optGuided && a.shrink1 == a.nJobs && a.nJobs >= 64u) {
         if (c->optOrder == 0) { s->orderSlots[lane].keyed = s->orderSlots[lane].hasOrder = s->orderSlots[lane].usedOrder = false; }
-        else slot = tileOrderSlot(s, lane, a.nJobs >> 6);
+        if (c->optTryHint == 0) s->orderSlots[lane].hasHint = false;
+        if (c->optOrder != 0 || c->optTryHint != 0) slot = tileOrderSlot(s, lane, a.nJobs >> 6);
     }
     if (slot) {
         const TileOrderKey k{a.W, a.H, a.x0, a.nCols, a.stripeW, a.stripeRanks, a.stripeRank, a.nJobs, key.variant, key.libm ? 1u : 0u};
         a.tileCost = slot->cost;
-        if (c->optOrder == 1 && slot->keyed && slot->hasOrder && slot->key == k) a.tileOrder = slot->order;
-        slot->key = k; slot->keyed = true; slot->hasOrder = false; slot->usedOrder = a.tileOrder != nullptr;
+        if (c->optOrder != 0) {
+            if (c->optOrder == 1 && slot->keyed && slot->hasOrder && slot->key == k) a.tileOrder = slot->order;
+            slot->key = k; slot->keyed = true; slot->hasOrder = false; slot->usedOrder = a.tileOrder != nullptr;
+        }
+        if (c->optTryHint != 0) {
+            const bool bundleAlone = c->optCertPolicy == 0 && a.cert != 0u && a.bundlePeriod != 0u && a.certPrim == 0xffffffffu && a.certShadow == 0xffffffffu;
+            a.tileHint = slot->hint;
+            if (c->optTryHint == 1 && bundleAlone && slot->hasHint && slot->hintKey == k && cameraShiftPixels(slot->hintCam, a.cam, a.maxSize, s->flat) <= FT_HINT_MAX_SHIFT) a.tryHint = 1u;
+            slot->hintKey = k; slot->hasHint = true; slot->usedHint = a.tryHint != 0u;
+            memcpy(slot->hintCam, a.cam, sizeof(slot->hintCam));
+        }
     }
     return slot;
 }
@@ -531,6 +577,7 @@ constexpr OptionSpec kOptions[] = {
     {FT_OPT_ORDER, &ft_ctx::optOrder, 0, 2, "FT_OPT_ORDER: 0 off, 1 heavy tiles first, 2 record only"},
     {FT_OPT_OCCL, &ft_ctx::optOccl, 0, 1, "FT_OPT_OCCL: 0 or 1"},
     {FT_OPT_OCCL_POLICY, &ft_ctx::optOcclPolicy, 0, 0x40ffff, "FT_OPT_OCCL_POLICY: 0, or bits 0-7 period, 8-15 first step, 16-23 candidates (0 .. 64)"},
+    {FT_OPT_TRY_HINT, &ft_ctx::optTryHint, 0, 2, "FT_OPT_TRY_HINT: 0 off, 1 tries scheduled from the last frame, 2 record only"},
 };
 const OptionSpec* findOption(int32_t id) {
     for (const OptionSpec& o : kOptions) if (o.id == id) return &o;
@@ -803,6 +850,45 @@ static long long readTileOrderSlot(const ft_scene* s, bool order, uint32_t* out,
 }
 long long ft_scene_tile_costs(const ft_scene* s, uint32_t* out, long long cap) { return readTileOrderSlot(s, false, out, cap); }
 long long ft_scene_tile_order(const ft_scene* s, uint32_t* out, long long cap) { return readTileOrderSlot(s, true, out, cap); }
+// Internal (tests/test_try_hint.py, tools/try_hint_probe.py): the try hints of the scene's lane-0 slot (FT_OPT_TRY_HINT; ft_kernels.h "Try hints").
+// ft_selftest_try_hints copies them to `out` as the tile costs are; ft_selftest_try_hints_fill overwrites them — mode 0: every word = value, mode 1: words
+// from a generator seeded with value, every byte value possible — so that the next frame follows hints no frame could have left.
+// Both return the tile count, 0 where the slot holds no hints, or a negative error code.
+long long ft_selftest_try_hints(const ft_scene* s, uint32_t* out, long long cap) {
+    if (!s || !s->ctx || (!out && cap > 0) || cap < 0) return setErr(FT_ERR_INVALID, "bad argument");
+    int rc = requireDevice(s->ctx); if (rc) return rc;
+    const TileOrderSlot& t = s->orderSlots[0];
+    if (!t.hasHint) return 0;
+    const long long n = (long long)(t.hintKey.nJobs >> 6);
+    HIP_TRY(hipStreamSynchronize(s->ctx->stream));
+    if (std::min(n, cap) > 0) HIP_TRY(hipMemcpy(out, t.hint, (size_t)std::min(n, cap) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return n;
+}
+long long ft_selftest_try_hints_fill(const ft_scene* s, int32_t mode, uint32_t value) {
+    if (!s || !s->ctx || mode < 0 || mode > 1) return setErr(FT_ERR_INVALID, "bad argument");
+    int rc = requireDevice(s->ctx); if (rc) return rc;
+    const TileOrderSlot& t = s->orderSlots[0];
+    if (!t.hasHint) return 0;
+    const size_t n = t.hintKey.nJobs >> 6;
+    std::vector<uint32_t> w(n, value);
+    if (mode == 1) { uint64_t x = value * 2654435761ull + 88172645463325252ull; for (uint32_t& v : w) { x ^= x << 13; x ^= x >> 7; x ^= x << 17; v = (uint32_t)(x >> 24); } }
+    HIP_TRY(hipStreamSynchronize(s->ctx->stream));
+    HIP_TRY(hipMemcpy(t.hint, w.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice));
+    return (long long)n;
+}
+// Internal: the slot's words replaced by `words` (n = the slot's tile count): hints recorded from another view put under this one
+long long ft_selftest_try_hints_write(const ft_scene* s, const uint32_t* words, long long n) {
+    if (!s || !s->ctx || !words) return setErr(FT_ERR_INVALID, "bad argument");
+    int rc = requireDevice(s->ctx); if (rc) return rc;
+    const TileOrderSlot& t = s->orderSlots[0];
+    if (!t.hasHint) return 0;
+    if (n != (long long)(t.hintKey.nJobs >> 6)) return setErr(FT_ERR_INVALID, "not the slot's tile count");
+    HIP_TRY(hipStreamSynchronize(s->ctx->stream));
+    HIP_TRY(hipMemcpy(t.hint, words, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice));
+    return n;
+}
+// Internal: 1 where the scene's last frame launch on lane 0 that recorded try hints also followed the ones it found, else 0
+int ft_selftest_try_hints_used(const ft_scene* s) { return s && s->orderSlots[0].hasHint && s->orderSlots[0].usedHint ? 1 : 0; }
 // Internal: 1 where the scene's last recording frame launch on lane 0 handed its tiles out in a built order, 0 where it ran in index order
 int ft_scene_tile_order_used(const ft_scene* s) { return s && s->orderSlots[0].keyed && s->orderSlots[0].usedOrder ? 1 : 0; }
 // Internal (tools/tile_order_probe.py, tests/test_tile_order.py): tiles count as heavy from num / den of the mean cost on (the shipped rule is 1 / 1;

@@ -20,6 +20,28 @@
 #define FT_LDS_REPORT_WORD 36
 static_assert(FT_LDS_WAVE_WORD >= FT_LDS_TILE_WORD + 2 * (256 / 64) && FT_LDS_WAVE_WORD + 4 * (256 / 64) <= FT_LDS_CNT_WORDS, "the wave sums lie behind the tile words, inside the header");
 static_assert(FT_LDS_TILE_WORD >= 36 && FT_LDS_TILE_WORD + 2 * (256 / 64) <= FT_LDS_CNT_WORDS, "the tile words lie behind the clocks, inside the header");
+// FT_LDS_HINT_WORD .. + 2 * FT_BLOCK / 64 - 1 per wave the try hint of the tile it works on and the rounds its bundles have held on (kernels.hip "Try hints"):
+// the statistics' unused rows, zeroed with them
+#define FT_LDS_HINT_WORD 24
+static_assert(FT_LDS_HINT_WORD + 2 * (256 / 64) <= 32, "the hint words lie in the statistics' unused rows");
+
+// Try hints (FT_OPT_TRY_HINT): one 32-bit word per 8x8 tile.  Bits 0-7: the earliest evaluation round of the tile, counted from the round its wave took it, on
+// which the bundle certificate of its primary rays held; bits 8-15: the same for its shadow rays.  Rounds from 254 on are noted as 254; FT_HINT_NONE: on none.
+// The schedule a hinted tile follows is kernels.hip ft_try_due.
+#define FT_HINT_NONE 255u
+#define FT_HINT_MAX 254u
+#define FT_HINT_USED 0x10000u  // set on the word a wave keeps in LDS: the tile's tries follow it (clear: the launch's period)
+#define FT_HINT_AFTER 2u       // a family's tries behind its first hold, or behind its hinted round while nothing has held: every 2nd round (the shipped period)
+#define FT_HINT_IDLE 4u        // whatever the hint, and all a family is tried on where none of its bundles held: every 4th round of the tile, its first included
+FT_HD uint32_t ft_hint_pack(uint32_t primary, uint32_t shadow) { return (primary & 255u) | (shadow & 255u) << 8; }
+FT_HD uint32_t ft_hint_primary(uint32_t w) { return w & 255u; }
+FT_HD uint32_t ft_hint_shadow(uint32_t w) { return (w >> 8) & 255u; }
+// the word after a bundle of the primary (else the shadow) family held on round r of the tile: the smaller round stays
+FT_HD uint32_t ft_hint_note(uint32_t w, bool primary, uint32_t r) {
+    const uint32_t v = r < FT_HINT_MAX ? r : FT_HINT_MAX, p = ft_hint_primary(w), s = ft_hint_shadow(w);
+    return primary ? ft_hint_pack(v < p ? v : p, s) : ft_hint_pack(p, v < s ? v : s);
+}
+
 #ifdef FT_UNION_PROFILE
 #define FT_LDS_DBG_ROWS 13
 #else
@@ -115,8 +137,12 @@ struct FtRenderArgs {
     // steps — each ray meets exactly one such round — where at least occMin (>= 1) lanes hold such a ray
     uint32_t occPeriod, occFrom, occMin;
     FtOccl occ;
+    // try hints (the launches that record tileCost; kernels.hip "Try hints"; appended): tileHint, where not NULL, holds one word per tile (above) and
+    // receives what this launch's bundles did; tryHint = 1: the word a tile's last frame left schedules its bundle tries (needs tileHint)
+    uint32_t* tileHint;
+    uint32_t tryHint, pad1;
 };
-static_assert(offsetof(FtRenderArgs, occ) == 860 && sizeof(FtRenderArgs) == 888, "the kernels' argument block does not move");
+static_assert(offsetof(FtRenderArgs, occ) == 860 && offsetof(FtRenderArgs, tileHint) == 888 && sizeof(FtRenderArgs) == 904, "the kernels' argument block does not move");
 #define FT_MAX_VIEWS 64       // views per launch (one PH_CAM value per lane); ft_render_views splits larger batches
 
 // The forms of the trace kernel (kernels.hip FT_TRACE_FORMS builds every one of them from the same table of builds): what a job is and what it leaves.

@@ -1988,6 +1988,24 @@ __device__ __forceinline__ unsigned long long wave_sum(uint32_t v) {
     return x;
 }
 
+// Try hints (FT_OPT_TRY_HINT; DESIGN.md section 4 "Try hints"): is the bundle certificate of one family tried on round r of the tile (r counts the wave's
+// evaluation rounds since it took the tile), h being the earliest round the family's bundle held on in the tile's last frame and n the earliest it has held
+// on in this one (FT_HINT_NONE: on none)?
+//   always      every FT_HINT_IDLE-th round, the tile's first included: what a hint that no longer fits the view costs is bounded by it (a tile that has
+//               become all sky ends before its first evaluation round whatever its hint says)
+//   h a round   also at h - 1 and at h
+//   afterwards  every FT_HINT_AFTER-th round counted from n — from h while nothing has held.  Counted from this frame's own hold, so that a still camera's
+//               frames try on the same rounds from the second hinted frame on, whichever of h - 1 and h the first hold came on
+// Wave-uniform integers only, but not free: the round count lives in a VGPR in the lean kernel, so the tile's round, the comparisons and the three
+// words read from LDS come out as a few dozen VALU instructions per round (v_readfirstlane, v_sub, v_cmp) beside the scalar ones.  The gate decides when
+// a try runs and nothing else, so every schedule renders the same frame.
+__device__ __forceinline__ bool ft_try_due(uint32_t h, uint32_t n, uint32_t r) {
+    if (r % FT_HINT_IDLE == 0u) return true;
+    if (h != FT_HINT_NONE && (r + 1u == h || r == h)) return true;
+    const uint32_t from = n != FT_HINT_NONE ? n : h;
+    return from != FT_HINT_NONE && r > from && (r - from) % FT_HINT_AFTER == 0u;
+}
+
 template <int VARIANT, bool EXT, int MATH = 0, int K = 0, int FORM = FT_FORM_FRAME>
 __device__ __forceinline__ void ft_trace_body(const FtRenderArgs& a) {
     constexpr bool VIEWS = FORM == FT_FORM_VIEWS, SHADE = FORM == FT_FORM_SHADE || FORM == FT_FORM_VIS;
@@ -2028,6 +2046,10 @@ __device__ __forceinline__ void ft_trace_body(const FtRenderArgs& a) {
     uint32_t* tileSt = reinterpret_cast<uint32_t*>(ft_lds) + FT_LDS_TILE_WORD + (tid >> 6);
     constexpr uint32_t TILE_EVALS = FT_BLOCK / 64;                     // word offset of the second value
     if (ORDER && lane == 0) tileSt[0] = 0xffffffffu;
+    // try hints: the tile's hint word as the rounds read it (FT_HINT_USED set: follow it; 0: the shipped schedule) and the earliest rounds its bundles have
+    // held on so far (ft_hint_pack), in two more of the header's words per wave; both are written at the grab
+    uint32_t* hintSt = reinterpret_cast<uint32_t*>(ft_lds) + FT_LDS_HINT_WORD + (tid >> 6);
+    constexpr uint32_t HINT_NOTE = FT_BLOCK / 64;                      // word offset of the notes
     uint32_t coopEvals = 0;                                            // evaluations done in latency mode (wave-uniform)
     uint32_t nEvals = 0;                                               // scene evaluations of this wave's rays (wave-uniform: summed per round)
     // LEAN: those four sums are only ever added to, so they wait in this wave's words of the LDS header (as tileSt does) instead of in four SGPRs that
@@ -2070,7 +2092,10 @@ __device__ __forceinline__ void ft_trace_body(const FtRenderArgs& a) {
                 // by one lane; every tile is taken once, so every cost is written once, by this grab or by the one that finds the queue empty
                 if (ORDER && u.tileCost != nullptr && lane == 0) {
                     const uint32_t t = tileSt[0];
-                    if (t < (u.nJobs >> 6)) u.tileCost[t] = waveEvals - tileSt[TILE_EVALS];
+                    if (t < (u.nJobs >> 6)) {
+                        u.tileCost[t] = waveEvals - tileSt[TILE_EVALS];
+                        if (u.tileHint != nullptr) u.tileHint[t] = hintSt[HINT_NOTE];     // try hints: what the tile's next frame schedules its tries from
+                    }
                     tileSt[0] = 0xffffffffu;
                 }
                 // Guided hand-out at the end of the queue (FT_OPT_GUIDED, lean kernel, OFF by default; everywhere else shrink1 = shrink2 = nJobs):
@@ -2098,7 +2123,12 @@ __device__ __forceinline__ void ft_trace_body(const FtRenderArgs& a) {
                         tile = (uint32_t)__builtin_amdgcn_readfirstlane((int)u.tileOrder[tile]);
                         chunkNext = tile << 6; chunkEnd = chunkNext + 64u;
                     }
-                    if (lane == 0) { tileSt[0] = tile; tileSt[TILE_EVALS] = waveEvals; }
+                    if (lane == 0) {
+                        tileSt[0] = tile; tileSt[TILE_EVALS] = waveEvals;
+                        // try hints: the word the tile's last frame left (read before this wave writes it, after the tile's last round), or none
+                        hintSt[0] = u.tryHint != 0u ? (u.tileHint[tile] & 0xffffu) | FT_HINT_USED : 0u;
+                        hintSt[HINT_NOTE] = ft_hint_pack(FT_HINT_NONE, FT_HINT_NONE);
+                    }
                 }
             }
             uint32_t avail = chunkEnd - chunkNext;
@@ -2136,13 +2166,22 @@ __device__ __forceinline__ void ft_trace_body(const FtRenderArgs& a) {
         if (VARIANT == 1 && FT_WORD_AT_USE(LEAN, a.cert) != 0u) {                          // EXTENSION builds: not inside a glass body (the march runs on -Distance there)
             // the bundle of the wave's primary rays, then that of its shadow rays (never mixed: one axis serves one family of directions), every
             // bundlePeriod-th evaluation round of the wave; a bundle that fails changes nothing
+            // Try hints (the builds that record tile costs): where the tile came with a hint word, each family's tries follow it (ft_try_due) in place of
+            // the period; the word and the round count at the grab wait in the LDS header and are read here, not held across the round
             bool ends = false;
-            if (FT_WORD_AT_USE(LEAN, a.bundlePeriod) != 0u && waveEvals % a.bundlePeriod == 0u) {
+            const uint32_t hint = ORDER ? (uint32_t)__builtin_amdgcn_readfirstlane((int)hintSt[0]) : 0u;
+            const uint32_t noted = ORDER ? (uint32_t)__builtin_amdgcn_readfirstlane((int)hintSt[HINT_NOTE]) : 0u;
+            const uint32_t tileRound = ORDER ? waveEvals - (uint32_t)__builtin_amdgcn_readfirstlane((int)tileSt[TILE_EVALS]) : 0u;
+            if (FT_WORD_AT_USE(LEAN, a.bundlePeriod) != 0u && ((ORDER && hint != 0u) || waveEvals % a.bundlePeriod == 0u)) {
 #pragma unroll 1
                 for (uint32_t ph = SHADE ? PH_SHADOW : PH_MARCH; ph <= PH_SHADOW; ph += PH_SHADOW - PH_MARCH) {
+                    if (ORDER && hint != 0u && !ft_try_due(ph == PH_MARCH ? ft_hint_primary(hint) : ft_hint_shadow(hint), ph == PH_MARCH ? ft_hint_primary(noted) : ft_hint_shadow(noted), tileRound)) continue;
                     const bool cand = s.phase == ph && (ph == PH_MARCH || s.steps >= a.bundleShadow) && (!EXT || !s.inside());
                     if ((uint32_t)__popcll(__ballot(cand)) < a.bundleMin) continue;
-                    if (ft_bundle_certificate<LEAN>(FT_ARGS_AT_USE(LEAN, a).S, ldsC + 0, cand, s.o, s.dir, s.eps, s.len, s.steps, a.bundleMin)) ends = true;
+                    const bool held = ft_bundle_certificate<LEAN>(FT_ARGS_AT_USE(LEAN, a).S, ldsC + 0, cand, s.o, s.dir, s.eps, s.len, s.steps, a.bundleMin);
+                    if (held) ends = true;
+                    // try hints: the earliest round of the tile a bundle of this family held on, noted by one lane (the words lie idle where nothing records)
+                    if (ORDER && __ballot(held) != 0ull && lane == 0) hintSt[HINT_NOTE] = ft_hint_note(hintSt[HINT_NOTE], ph == PH_MARCH, tileRound);
                 }
             }
             // per lane: once enough lanes are due, the wave tries it for all of them at once

@@ -51,6 +51,8 @@ public:
     void setOption(ft_option option, int value) { check(ft_ctx_set_option(ctx_, (int32_t)option, value)); }
     // FT_OPT_ORDER (on by default): a scene's repeated frames hand out last frame's heavy tiles first; setOption(FT_OPT_ORDER, 0) keeps index order
     // FT_OPT_OCCL (on by default): shadow rays proved to end in a hit stop marching; setOption(FT_OPT_OCCL, 0) marches every one; FT_OPT_OCCL_POLICY: its schedule
+    // FT_OPT_TRY_HINT (on by default): a scene's repeated frames try each tile's bundle certificates around the rounds they held on in the last frame;
+    // setOption(FT_OPT_TRY_HINT, 0) keeps every frame on the first frame's schedule, 2 records without following
     int getOption(ft_option option) const { int32_t v = 0; check(ft_ctx_get_option(ctx_, (int32_t)option, &v)); return v; }
     static std::string buildInfo() { return ft_build_info(); }
     Context(const Context&) = delete;

@@ -219,6 +219,11 @@ module Native =
     /// Same frame, counters and flags; 0 = index order, 2 = record only
     let setTileOrder (mode : int) = if ft_ctx_set_option (ctx.Value, 16, mode) < 0 then failwith (Marshal.PtrToStringAnsi (ft_last_error ()))
 
+    /// FT_OPT_TRY_HINT (19), on by default: a frame records per 8x8 tile on which of its evaluation rounds the bundle certificates of its primary and of its
+    /// shadow rays first held, and the scene's next frame of the same size tries each tile's bundles around those rounds only (any stream of frames:
+    /// the tries that decide nothing are left out).  Same frame, rays, hits and flags; 0 = every frame on the first frame's schedule, 2 = record only
+    let setTryHint (mode : int) = if ft_ctx_set_option (ctx.Value, 19, mode) < 0 then failwith (Marshal.PtrToStringAnsi (ft_last_error ()))
+
     let check (h : int) =
         if h < 0 then failwith (Marshal.PtrToStringAnsi (ft_last_error ())) else h
 

@@ -154,6 +154,12 @@ typedef enum ft_option {
                                    * |direction| > 1 (a point light's) and EXTENSION ambient-occlusion rays keep marching; 0: off */
     FT_OPT_OCCL_POLICY = 18,      /* 0 (default schedule) or, for experiments, when that proof is tried: bits 0-7 every how many evaluation rounds of a wave (0: the shipped 2,
                                    * 1: every round, 255: off), 8-15 the steps a shadow ray takes first, 16-23 the shadow rays a try waits for (0: the shipped 1; .. 64) */
+    FT_OPT_TRY_HINT = 19,         /* 1 (default): a frame of the smooth-union-of-spheres kernel (the launches FT_OPT_ORDER covers) records per 8x8 tile on which of the tile's evaluation
+                                   * rounds the bundle certificate of its primary rays and that of its shadow rays first held, and the scene's next frame of the same size, column range and
+                                   * stripe layout on the same render lane tries each tile's bundles around those rounds instead of on every second round of the wave.  Only when a
+                                   * try runs changes: same frame, rays, hits and flags; sdf_evals and wave_evals fall.  Followed only under FT_OPT_CERT_POLICY = 0 on frames that word
+                                   * gives the bundle alone, and from a camera whose image moved by at most 16 pixels since the frame that recorded; a first frame, an explicit policy
+                                   * word and every other launch keep their schedule.  2: record only; 0: off */
     FT_OPT_GUIDED = 7             /* 1: the last jobs of a launch are handed out in half and quarter tiles (lean kernel); 0 (default): whole tiles only */
 } ft_option;
 /* MathF.Exp / MathF.Log (SdfForm.unionSmooth, SdfForm.fs:80,82) and MathF.Pow (FColor.gammaInverse, FColor.fs:50-55) are the C runtime's
