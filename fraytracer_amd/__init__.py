@@ -6,7 +6,7 @@ Importing it fails if the shared library has not been built; there is no CPU fal
 """
 from ._lib import FrayTracerError, LIB_PATH, build_info, source_hash
 from .api import (FColor, SdfForm, SdfMaterial, SdfObject, SdfLight, SdfScene, Lens, Camera, ImageSize, Image, Ray,
-                  Device, DeviceScene, PixelHits, FieldSamples, Mesh, Contours, Shells, Measures, SceneTrace, realise, render_multi, glibc_build_of_this_host, lattice_points)
+                  Device, DeviceScene, PixelHits, FieldSamples, Mesh, Contours, Shells, Measures, ContourMeasures, SceneTrace, realise, render_multi, glibc_build_of_this_host, lattice_points)
 
 __all__ = ["FColor", "SdfForm", "SdfMaterial", "SdfObject", "SdfLight", "SdfScene", "Lens", "Camera", "ImageSize",
-           "Image", "Ray", "Device", "DeviceScene", "PixelHits", "SceneTrace", "realise", "render_multi", "FrayTracerError", "LIB_PATH", "build_info", "source_hash", "glibc_build_of_this_host", "FieldSamples", "lattice_points", "Mesh", "Contours", "Shells", "Measures"]
+           "Image", "Ray", "Device", "DeviceScene", "PixelHits", "SceneTrace", "realise", "render_multi", "FrayTracerError", "LIB_PATH", "build_info", "source_hash", "glibc_build_of_this_host", "FieldSamples", "lattice_points", "Mesh", "Contours", "Shells", "Measures", "ContourMeasures"]

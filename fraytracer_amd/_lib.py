@@ -120,6 +120,24 @@ SHELL_MEASURE_DTYPE = [("area", "<f8"), ("volume", "<f8"), ("moment", "<f8", (3,
                        ("n_unmeasured", "<i4"), ("extent_exponent", "<i4")]
 
 
+class ContourMeasure(C.Structure):           # ft_contour_measure: a polyline's length, signed area, first moment, box in the plane; 56 B
+    _fields_ = [("length", C.c_double), ("area", C.c_double), ("moment", C.c_double * 2), ("bbox_min", C.c_float * 2), ("bbox_max", C.c_float * 2),
+                ("n_unmeasured", C.c_int32), ("extent_exponent", C.c_int32)]
+
+
+class SliceMeasure(C.Structure):             # ft_slice_measure: the same per slice, holes subtracted, and the slice's counts; 72 B
+    _fields_ = [("length", C.c_double), ("area", C.c_double), ("moment", C.c_double * 2), ("bbox_min", C.c_float * 2), ("bbox_max", C.c_float * 2),
+                ("n_polylines", C.c_int32), ("n_closed", C.c_int32), ("n_outer", C.c_int32), ("n_holes", C.c_int32), ("n_unmeasured", C.c_int32),
+                ("extent_exponent", C.c_int32)]
+
+
+# the same records as numpy dtypes (the arrays ContourMeasures is built over)
+CONTOUR_MEASURE_DTYPE = [("length", "<f8"), ("area", "<f8"), ("moment", "<f8", (2,)), ("bbox_min", "<f4", (2,)), ("bbox_max", "<f4", (2,)),
+                         ("n_unmeasured", "<i4"), ("extent_exponent", "<i4")]
+SLICE_MEASURE_DTYPE = [("length", "<f8"), ("area", "<f8"), ("moment", "<f8", (2,)), ("bbox_min", "<f4", (2,)), ("bbox_max", "<f4", (2,)),
+                       ("n_polylines", "<i4"), ("n_closed", "<i4"), ("n_outer", "<i4"), ("n_holes", "<i4"), ("n_unmeasured", "<i4"), ("extent_exponent", "<i4")]
+
+
 class TonemapParams(C.Structure):
     _fields_ = [("gamma", C.c_float), ("dither", C.c_int32), ("seed", C.c_uint32), ("bmp_order", C.c_int32)]
 
@@ -229,6 +247,7 @@ SYMBOLS = {
     "ft_mesh_select": (C.c_int, [_P, _P, _P, C.c_int64, C.POINTER(_P)]),
     "ft_shells_measure": (C.c_int, [_P, _P, _P]),
     "ft_mesh_measure": (C.c_int, [_P, _P]),
+    "ft_slices_measure": (C.c_int, [_P, _P, _P]),
     "ft_scene_clone": (C.c_int, [_P, _P, C.POINTER(_P)]),
     "ft_render_multi": (C.c_int, [C.POINTER(_P), C.POINTER(_P), C.c_int32, C.POINTER(CameraS), C.POINTER(RenderParams), _P, C.POINTER(Stats)]),
     "ft_scene_info_get": (C.c_int, [_P, C.POINTER(SceneInfo)]),

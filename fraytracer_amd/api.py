@@ -168,11 +168,11 @@ class SdfForm:
         return _form_scene(form, device).mesh_lattice(origin, step, counts, iso=iso, normal_epsilon=normal_epsilon, refine=refine, shells=shells, keep=keep, measures=measures)
 
     @staticmethod
-    def slice(form, origin, step, counts, axis=2, iso=0.0, normal_epsilon=None, device=None, refine=None):
+    def slice(form, origin, step, counts, axis=2, iso=0.0, normal_epsilon=None, device=None, refine=None, measures=False):
         """the contours sdf.Distance = iso of every lattice plane normal to `axis`, extracted and chained on the GPU from the lattice
         lattice_points(origin, step, counts) -> Contours, with SdfForm.normal per point where normal_epsilon is given; refine: bisection rounds
-        that move the points onto the surface (DeviceScene.slice_lattice)"""
-        return _form_scene(form, device).slice_lattice(origin, step, counts, axis=axis, iso=iso, normal_epsilon=normal_epsilon, refine=refine)
+        that move the points onto the surface; measures: measure the polylines and the slices (DeviceScene.slice_lattice)"""
+        return _form_scene(form, device).slice_lattice(origin, step, counts, axis=axis, iso=iso, normal_epsilon=normal_epsilon, refine=refine, measures=measures)
 
     @staticmethod
     def crossings(form, a, b, iso=0.0, steps=8, device=None):
@@ -567,11 +567,11 @@ class Device:
             check(lib.ft_shells_triangles(self._ctx, _hptr(tri), nt, nv, C.byref(handle)))
             return _read_shells(handle, like)
 
-    def slice_values(self, values, origin, step, axis=2, iso=0.0):
+    def slice_values(self, values, origin, step, axis=2, iso=0.0, measures=False):
         """ft_slice_values: the contours {values = iso} of a float32 lattice [nx, ny, nz] in every lattice plane normal to `axis`, as ordered
         polylines chained on the device -> Contours without normals and materials.  A device tensor (see is_device_tensor; float32, contiguous) is
         sliced where it lies by ft_slice_values_device on the caller's current stream, and the Contours hold tensors of its device; the values are
-        only read."""
+        only read.  measures: as in DeviceScene.slice_lattice."""
         on_device = is_device_tensor(values)
         if on_device:
             if str(values.dtype).rsplit(".", 1)[-1] != "float32" or not values.is_contiguous():
@@ -586,9 +586,9 @@ class Device:
         if on_device:
             with self.on_current_stream(vals):
                 check(lib.ft_slice_values_device(self._ctx, C.byref(lat), _dptr(vals.data_ptr()), int(axis), float(iso), C.byref(handle)))
-                return _read_slices(handle, vals, None)
+                return _read_slices(handle, vals, None, measures)
         check(lib.ft_slice_values(self._ctx, C.byref(lat), _hptr(vals), int(axis), float(iso), C.byref(handle)))
-        return _read_slices(handle, None, None)
+        return _read_slices(handle, None, None, measures)
 
     def selftest_libm(self, op, variant, y=0.0, lo_bits=0, n_chunks=256):
         """ft_selftest_libm: checksums of the device restatement of glibc's expf (op 0) / logf (1) / powf(x, y) (2) per 2^24 inputs"""
@@ -979,9 +979,10 @@ class Contours:
     slice, closed): polyline r is points[first : first + count] in slice `slice`, closed (a loop, its first point not repeated; counter-clockwise seen
     from +axis around the inside, clockwise around a hole) or open.  `normal` float32 [n, 3] and `material` int32 [n] are None where not asked for;
     `skipped` counts the triangles left out for a non-finite corner value; `axis` and `slices` say which planes.  numpy arrays, or device tensors
-    where the call was given one.  The rule that fixes every bit of it is the header's ("Slicing")."""
+    where the call was given one.  The rule that fixes every bit of it is the header's ("Slicing").  `measures` (a ContourMeasures, one record per
+    polyline) and `layer_measures` (one record per slice) where the contours were made with measures=True; else None."""
 
-    def __init__(self, points, polylines, normal=None, material=None, skipped=0, closed=0, axis=2, slices=0, materials=None):
+    def __init__(self, points, polylines, normal=None, material=None, skipped=0, closed=0, axis=2, slices=0, materials=None, measures=None, layer_measures=None):
         self.points = points
         self.polylines = polylines
         self.normal = normal
@@ -990,6 +991,8 @@ class Contours:
         self.closed = int(closed)
         self.axis = int(axis)
         self.slices = int(slices)
+        self.measures = measures
+        self.layer_measures = layer_measures
         self._materials = dict(materials or {})
 
     def descriptor(self, handle):
@@ -1022,8 +1025,70 @@ class Contours:
             f.write("</g>\n</svg>\n")
 
 
-def _read_slices(handle, like, materials):
-    """an ft_slices -> Contours of numpy arrays (like = None) or of tensors of like's device, through ft_slices_read; the handle is destroyed"""
+class ContourMeasures:
+    """Per-polyline or per-slice contour measures (ft_contour_measure / ft_slice_measure, the header's "Contour measures"): `records` is the record
+    array — a numpy structured array with the struct's fields, or, where the call was given a device tensor, a float32 tensor [n, 14] (polylines)
+    or [n, 18] (slices) of its device holding the same 56 or 72 bytes per record.  The properties give numpy arrays (a device tensor is read back):
+    length float64 [n], area float64 [n] (per polyline positive for a closed outer boundary, negative for a closed hole, with positive steps in the
+    plane; per slice the enclosed area, holes subtracted), moment float64 [n, 2] (the integral of (u, v) over the area), bbox_min / bbox_max float32
+    [n, 2], n_unmeasured int32 [n], extent_exponent int; per slice also n_polylines, n_closed, n_outer, n_holes.  Every bit of them is fixed by the
+    rule; `centroid` = moment / area is plain numpy and is not."""
+
+    def __init__(self, records, per_slice=False):
+        self.records = records
+        self.per_slice = bool(per_slice)
+
+    def __len__(self):
+        return int(self.records.shape[0])
+
+    def host(self):
+        """the records as a numpy structured array [n]"""
+        r = self.records
+        if isinstance(r, np.ndarray):
+            return r
+        dtype = np.dtype(_lib.SLICE_MEASURE_DTYPE if self.per_slice else _lib.CONTOUR_MEASURE_DTYPE)
+        return np.ascontiguousarray(r.detach().cpu().numpy()).view(dtype).reshape(-1)
+
+    length = property(lambda self: self.host()["length"])
+    area = property(lambda self: self.host()["area"])
+    moment = property(lambda self: self.host()["moment"])
+    bbox_min = property(lambda self: self.host()["bbox_min"])
+    bbox_max = property(lambda self: self.host()["bbox_max"])
+    n_unmeasured = property(lambda self: self.host()["n_unmeasured"])
+    n_polylines = property(lambda self: self.host()["n_polylines"])      # the four counts: per-slice records only
+    n_closed = property(lambda self: self.host()["n_closed"])
+    n_outer = property(lambda self: self.host()["n_outer"])
+    n_holes = property(lambda self: self.host()["n_holes"])
+
+    @property
+    def extent_exponent(self):
+        e = self.host()["extent_exponent"]
+        return int(e[0]) if len(e) else 0
+
+    @property
+    def centroid(self):
+        """float64 [n, 2]: moment / area in the plane's (u, v) (nan where the area is 0)"""
+        h = self.host()
+        with np.errstate(all="ignore"):
+            return h["moment"] / h["area"][:, None]
+
+
+def _read_contour_measures(handle, like, n_polylines, n_slices):
+    """ft_slices_measure of an ft_slices -> (ContourMeasures per polyline, ContourMeasures per slice) over numpy record arrays (like = None) or
+    float32 tensors [n, 14] and [n, 18] of like's device"""
+    if like is None:
+        per_line, per_slice = np.zeros(n_polylines, np.dtype(_lib.CONTOUR_MEASURE_DTYPE)), np.zeros(n_slices, np.dtype(_lib.SLICE_MEASURE_DTYPE))
+        check(lib.ft_slices_measure(handle, _hptr(per_line) if n_polylines else None, _hptr(per_slice) if n_slices else None))
+    else:
+        f32 = like.new_empty(0).float().dtype
+        per_line, per_slice = like.new_empty((n_polylines, 14), dtype=f32), like.new_empty((n_slices, 18), dtype=f32)
+        check(lib.ft_slices_measure(handle, _dptr(per_line.data_ptr()) if n_polylines else None, _dptr(per_slice.data_ptr()) if n_slices else None))
+    return ContourMeasures(per_line), ContourMeasures(per_slice, per_slice=True)
+
+
+def _read_slices(handle, like, materials, measures=False):
+    """an ft_slices -> Contours of numpy arrays (like = None) or of tensors of like's device, through ft_slices_read; the handle is destroyed.
+    measures: the Contours carry their ContourMeasures, computed on the handle before it is destroyed"""
     try:
         info = _lib.SlicesInfo()
         check(lib.ft_slices_get_info(handle, C.byref(info)))
@@ -1032,7 +1097,9 @@ def _read_slices(handle, like, materials):
                  _empty(like, (n,), "int32") if info.has_material else None)
         ptr = _hptr if like is None else (lambda a: None if a is None else _dptr(a.data_ptr()))
         check(lib.ft_slices_read(handle, *map(ptr, parts)))
-        return Contours(*parts, skipped=info.n_skipped, closed=info.n_closed, axis=info.axis, slices=info.n_slices, materials=materials)
+        per_line, per_slice = _read_contour_measures(handle, like, m, int(info.n_slices)) if measures else (None, None)
+        return Contours(*parts, skipped=info.n_skipped, closed=info.n_closed, axis=info.axis, slices=info.n_slices, materials=materials,
+                        measures=per_line, layer_measures=per_slice)
     finally:
         lib.ft_slices_destroy(handle)
 
@@ -1508,13 +1575,15 @@ class DeviceScene:
                 check(lib.ft_mesh_lattice_refined(self.device._ctx, self._scene, C.byref(lat), float(iso), eps, flags, int(refine), C.byref(handle)))
             return _read_mesh(handle, like, self.materials, shells, keep, measures)
 
-    def slice_lattice(self, origin, step, counts, axis=2, iso=0.0, normal_epsilon=None, material=False, like=None, refine=None):
+    def slice_lattice(self, origin, step, counts, axis=2, iso=0.0, normal_epsilon=None, material=False, like=None, refine=None, measures=False):
         """ft_slice_lattice: the contours scene.Object.Form.Distance = iso of every lattice plane normal to `axis` (0, 1, 2: x, y, z), extracted
         and chained on the device from the distances on lattice_points(origin, step, counts) (never bounded) -> Contours.  normal_epsilon: also
         SdfForm.normal per point; material: also the handle of the material object.Material.Color picks there (Contours.descriptor) — both
         exactly what sample_points gives for the points.  like: a device tensor — the Contours then hold tensors of its device, and the launches
         run on the caller's current stream.  refine: None, or the bisection rounds (0 .. 32) of ft_slice_lattice_refined: the points are then the
-        refined mesh vertices of the same edges (mesh_lattice), the polylines unchanged."""
+        refined mesh vertices of the same edges (mesh_lattice), the polylines unchanged.  measures: `.measures` holds each polyline's length, signed
+        area, first moment and box in the plane and `.layer_measures` the same per slice, holes subtracted, with the slice's outer loops and holes
+        counted, computed on the device (ft_slices_measure)."""
         lat, _ = _lattice(origin, step, counts)
         if like is not None and not is_device_tensor(like):
             raise ValueError("like: a device tensor (see is_device_tensor) or None")
@@ -1526,7 +1595,7 @@ class DeviceScene:
                 check(lib.ft_slice_lattice(self.device._ctx, self._scene, C.byref(lat), int(axis), float(iso), eps, flags, C.byref(handle)))
             else:
                 check(lib.ft_slice_lattice_refined(self.device._ctx, self._scene, C.byref(lat), int(axis), float(iso), eps, flags, int(refine), C.byref(handle)))
-            return _read_slices(handle, like, self.materials)
+            return _read_slices(handle, like, self.materials, measures)
 
     def refine_segments(self, a, b, iso=0.0, steps=8):
         """ft_refine_segments: where the segments from a [..., 3] to b [..., 3] cross scene.Object.Form.Distance = iso -> (points float32 [..., 3],

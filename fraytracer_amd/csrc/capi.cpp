@@ -8,6 +8,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <string>
 #include <vector>
 
@@ -19,6 +20,7 @@
 #include "ft_refine.h"
 #include "ft_shells.h"
 #include "ft_measure.h"
+#include "ft_contour_measure.h"
 #include "scene.hpp"
 
 #ifndef FT_BUILD_KIND
@@ -93,6 +95,9 @@ struct ft_ctx {
     void* measureWork = nullptr; size_t measureWorkBytes = 0; // the measures' per-shell sums, box keys, counters and staged records (ft_measure.h says how much per shell)
     int measureStop = 0, measureEager = 0;                 // ft_ctx_measure_probe (the probe's stages): calls end after the extent kernel (1) or the terms kernel (2) and write no record; the terms kernel flushes at every iteration
     unsigned measureGrid = 0;                              // 0: the measures' kernels fill the device; else their workgroups (ft_ctx_measure_grid: the tests' and the probe's grids)
+    void* contourWork = nullptr; size_t contourWorkBytes = 0; // the contour measures' per-polyline and per-slice sums, box keys, counters and staged records (ft_contour_measure.h says how much)
+    int contourEager = 0;                                  // ft_ctx_contour_measure_probe: the terms kernel adds every lane's terms by itself
+    unsigned contourGrid = 0;                              // 0: the contour measures' kernels fill the device; else their workgroups (ft_ctx_contour_measure_grid)
     int refineSkipField = 0;                               // 1: a refinement launches everything but its field rounds, and gives other positions (ft_ctx_refine_probe: the probe's stages)
     uint32_t orderNum = 1, orderDen = 1;                   // a tile is heavy from orderNum / orderDen of the mean cost on (ft_ctx_tile_order_rule: the probes' other rules)
 };
@@ -684,6 +689,7 @@ void ft_ctx_destroy(ft_ctx* c) {
         if (c->refineWork) (void)hipFree(c->refineWork);
         if (c->shellsWork) (void)hipFree(c->shellsWork);
         if (c->measureWork) (void)hipFree(c->measureWork);
+        if (c->contourWork) (void)hipFree(c->contourWork);
         for (auto& r : c->hostRegs) (void)hipHostUnregister(r.first);
         for (auto e : c->syncEvents) (void)hipEventDestroy(e);
         if (c->lane1) { (void)hipStreamSynchronize(c->lane1); (void)hipStreamDestroy(c->lane1); }
@@ -2753,6 +2759,148 @@ int ft_ctx_measure_grid(ft_ctx* c, int32_t workgroups) {
 int ft_ctx_measure_probe(ft_ctx* c, int32_t stop, int32_t eager) {
     if (!c || stop < 0 || stop > 2 || eager < 0 || eager > 1) return setErr(FT_ERR_INVALID, "bad argument");
     c->measureStop = stop; c->measureEager = eager;
+    return FT_OK;
+}
+
+// ---- contour measures: ft_slices_measure (contour_measure.hip; the rule is the header's "Contour measures") -------------------------------------------
+namespace {
+
+const char* const kContourKernels[FT_CONTOUR_KERNELS] = {"contour extent and box", "contour terms", "contour polylines", "contour slices"};
+
+int launchContour(ft_ctx* c, int kernel, const FtContourArgs& a) {
+    int perCU = 0;
+    const hipError_t e = ft_contour_occupancy(kernel, &perCU);
+    if (e != hipSuccess) return hipFail(e, (std::string("occupancy of the ") + kContourKernels[kernel] + " kernel").c_str());
+    int rc = clampPerCU(c, kContourKernels[kernel], perCU); if (rc) return rc;
+    const int domain = ft_contour_domain(kernel);
+    const uint64_t items = domain == 0 ? a.nP : (domain == 1 ? a.nL : a.nW);
+    unsigned blocks = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)c->numCUs * perCU, (items + FT_CONTOUR_BLOCK - 1) / FT_CONTOUR_BLOCK));
+    if (c->contourGrid) blocks = c->contourGrid;
+    return timedLaunch(c, c->stream, "ft_launch_contour", [&] { return ft_launch_contour(kernel, &a, blocks, c->stream); });
+}
+
+// What can be refused about the two outputs without a device, in the header's order: both NULL although something would be written, a misaligned device
+// pointer, one address for both.  *pDev / *sDev: the output is device memory.
+int checkContourOuts(const ft_ctx* c, const void* outP, const void* outS, size_t nL, size_t nW, bool* pDev, bool* sDev) {
+    static_assert(sizeof(ft_contour_measure) == FT_CONTOUR_RECORD_BYTES && sizeof(ft_slice_measure) == FT_CONTOUR_SLICE_RECORD_BYTES, "layout");
+    *pDev = *sDev = false;
+    if (!outP && !outS && (nL || nW)) return setErr(FT_ERR_INVALID, "contour measures: null out pointers");
+    *pDev = measureOutOnDevice(c, outP); *sDev = measureOutOnDevice(c, outS);
+    if ((*pDev && (reinterpret_cast<uintptr_t>(outP) & 7u)) || (*sDev && (reinterpret_cast<uintptr_t>(outS) & 7u)))
+        return setErr(FT_ERR_INVALID, "contour measures: the device records must be 8-byte aligned");
+    if (outP && outP == outS) return setErr(FT_ERR_INVALID, "contour measures: the two outputs must not be the same address");
+    return FT_OK;
+}
+
+// the slice records of contours without points and polylines: zeros and the +inf / -inf box, E = 0
+void emptySliceRecords(ft_slice_measure* out, size_t nW) {
+    ft_slice_measure r;
+    std::memset(&r, 0, sizeof r);
+    for (int x = 0; x < 2; ++x) { r.bbox_min[x] = std::numeric_limits<float>::infinity(); r.bbox_max[x] = -std::numeric_limits<float>::infinity(); }
+    for (size_t w = 0; w < nW; ++w) out[w] = r;
+}
+
+// The work memory of a call over nL polylines and nW slices, and the four launches.  Points and polylines are device memory.  Each output is NULL, host
+// memory (staged in the work memory; the stream is synchronised once, after both copies are queued) or device memory (written in place, nothing synchronised).
+int runContour(ft_ctx* c, const void* dPoints, size_t nP, const void* dPolylines, size_t nL, int32_t axis, size_t nW, ft_contour_measure* outP, bool pDev,
+               ft_slice_measure* outS, bool sDev) {
+    size_t at = 0;
+    auto take = [&](size_t bytes) { const size_t o = at; at = align256(at + bytes); return o; };
+    // zeroed: sums, maximum keys, counters, extent (adjacent); set to 0xff: minimum keys (adjacent)
+    const size_t oSums = take(nL * 2 * FT_CONTOUR_SUMS * 8), oMax = take(nL * 8), oBad = take(nL * 4), oSSums = take(nW * 2 * FT_CONTOUR_SUMS * 8), oSMax = take(nW * 8),
+                 oCount = take(nW * 4 * FT_CONTOUR_COUNTERS), oExtent = take(4), oMin = take(nL * 8), zeroed = oMin, oSMin = take(nW * 8), ones = at - oMin;
+    const size_t oStageP = take(outP && !pDev ? nL * sizeof(ft_contour_measure) : 0), oStageS = take(outS && !sDev ? nW * sizeof(ft_slice_measure) : 0);
+    int rc;
+    if ((rc = ensureBytes(c->contourWork, c->contourWorkBytes, std::max<size_t>(at, 256)))) return rc;
+    unsigned char* wk = static_cast<unsigned char*>(c->contourWork);
+    auto words = [&](size_t o) { return reinterpret_cast<uint32_t*>(wk + o); };
+    FtContourArgs a{};
+    a.points = static_cast<const uint32_t*>(dPoints); a.polylines = static_cast<const int32_t*>(dPolylines);
+    a.nP = (uint32_t)nP; a.nL = (uint32_t)nL; a.nW = (uint32_t)nW; a.axis = (uint32_t)axis;
+    a.sums = reinterpret_cast<unsigned long long*>(wk + oSums); a.boxMin = words(oMin); a.boxMax = words(oMax); a.unmeasured = words(oBad);
+    a.sliceSums = reinterpret_cast<unsigned long long*>(wk + oSSums); a.sliceBoxMin = words(oSMin); a.sliceBoxMax = words(oSMax); a.sliceCounters = words(oCount);
+    a.extent = words(oExtent);
+    a.outPolylines = !outP ? nullptr : (pDev ? static_cast<void*>(outP) : static_cast<void*>(wk + oStageP));
+    a.outSlices = !outS ? nullptr : (sDev ? static_cast<void*>(outS) : static_cast<void*>(wk + oStageS));
+    a.eager = c->contourEager;
+    HIP_TRY(hipMemsetAsync(wk, 0, zeroed, c->stream));
+    if (ones) HIP_TRY(hipMemsetAsync(wk + oMin, 0xff, ones, c->stream));
+    if (nP && (rc = launchContour(c, FT_CONTOUR_K_EXTENT, a))) return rc;
+    if (nP && nL && (rc = launchContour(c, FT_CONTOUR_K_TERMS, a))) return rc;
+    if (nL && (outP || outS) && (rc = launchContour(c, FT_CONTOUR_K_POLYLINES, a))) return rc;
+    if (nW && outS && (rc = launchContour(c, FT_CONTOUR_K_SLICES, a))) return rc;
+    const bool pHost = outP && !pDev && nL, sHost = outS && !sDev && nW;
+    if (!pHost && !sHost) return FT_OK;
+    hipError_t e = hipSuccess;
+    if (pHost) e = hipMemcpyAsync(outP, wk + oStageP, nL * sizeof(ft_contour_measure), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess && sHost) e = hipMemcpyAsync(outS, wk + oStageS, nW * sizeof(ft_slice_measure), hipMemcpyDeviceToHost, c->stream);
+    const hipError_t se = hipStreamSynchronize(c->stream);             // the one synchronisation of a call with a host output
+    if (e == hipSuccess) e = se;
+    return e == hipSuccess ? FT_OK : hipFail(e, "contour measures: records");
+}
+
+}  // namespace
+
+int ft_slices_measure(const ft_slices* m, ft_contour_measure* out_polylines, ft_slice_measure* out_slices) {
+    if (!m) return setErr(FT_ERR_INVALID, "null slices");
+    ft_ctx* c = m->ctx;
+    const size_t nL = (size_t)m->nL, nW = (size_t)m->nSlices;
+    bool pDev, sDev;
+    int rc = checkContourOuts(c, out_polylines, out_slices, nL, nW, &pDev, &sDev); if (rc) return rc;
+    if (nL == 0 && !sDev) {                                            // empty contours: no device needed; a device output only exists where a device does
+        if (out_slices) emptySliceRecords(out_slices, nW);
+        return FT_OK;
+    }
+    if ((rc = requireDevice(c))) return rc;
+    return runContour(c, m->dPoints, (size_t)m->nP, m->dPolylines, nL, m->axis, nW, out_polylines, pDev, out_slices, sDev);
+}
+
+// Internal (not in the header, like ft_ctx_measure_triangles; the tests and tools/contour_measure_probe.py): the contour measures of host arrays —
+// points float32 [nP][3], polylines ft_polyline [nL], an axis and nW slices -> nL and nW records (either output may be NULL; host or device memory).
+// Validated on the host before anything is uploaded: every [first, first + count) lies in 0 .. nP, every slice in 0 .. nW - 1, and `first` ascends
+// without overlap (first[l + 1] >= first[l] + count[l]: what the slicer writes and the kernels' search relies on).  The kernels check every word again.
+int ft_ctx_measure_polylines(ft_ctx* c, const float* points, int64_t nP, const ft_polyline* polylines, int64_t nL, int32_t axis, int64_t nW,
+                             ft_contour_measure* out_polylines, ft_slice_measure* out_slices) {
+    if (!c) return setErr(FT_ERR_INVALID, "null context");
+    if ((!points && nP) || (!polylines && nL)) return setErr(FT_ERR_INVALID, "null argument");
+    if (nP < 0 || nL < 0 || nW < 0 || nP >= ((int64_t)1 << 31) || nL >= ((int64_t)1 << 31) || nW >= ((int64_t)1 << 31))
+        return setErr(FT_ERR_INVALID, "contour measures: counts must be in 0 .. 2^31 - 1");
+    if (axis < 0 || axis > 2) return setErr(FT_ERR_INVALID, "contour measures: the axis must be 0, 1 or 2");
+    bool pDev, sDev;
+    int rc = checkContourOuts(c, out_polylines, out_slices, (size_t)nL, (size_t)nW, &pDev, &sDev); if (rc) return rc;
+    int64_t end = 0;
+    for (int64_t l = 0; l < nL; ++l) {
+        const ft_polyline& p = polylines[l];
+        if (p.first < 0 || p.count < 0 || (int64_t)p.first + p.count > nP) return setErr(FT_ERR_INVALID, "contour measures: a polyline's points lie outside 0 .. n_points");
+        if (p.slice < 0 || p.slice >= nW) return setErr(FT_ERR_INVALID, "contour measures: a polyline's slice lies outside 0 .. n_slices - 1");
+        if (p.first < end) return setErr(FT_ERR_INVALID, "contour measures: the polylines' points must ascend without overlap");
+        end = (int64_t)p.first + p.count;
+    }
+    if (nL == 0 && nP == 0 && !sDev) {
+        if (out_slices) emptySliceRecords(out_slices, (size_t)nW);
+        return FT_OK;
+    }
+    if ((rc = requireDevice(c))) return rc;
+    size_t at = 0;
+    auto take = [&](size_t bytes) { const size_t o = at; at = align256(at + bytes); return o; };
+    const size_t oP = take((size_t)nP * 12), oL = take((size_t)nL * sizeof(ft_polyline));
+    if ((rc = ensureScratch(c, std::max<size_t>(at, 256)))) return rc;
+    unsigned char* base = static_cast<unsigned char*>(c->scratch);
+    if (nP) HIP_TRY(hipMemcpyAsync(base + oP, points, (size_t)nP * 12, hipMemcpyHostToDevice, c->stream));
+    if (nL) HIP_TRY(hipMemcpyAsync(base + oL, polylines, (size_t)nL * sizeof(ft_polyline), hipMemcpyHostToDevice, c->stream));
+    return runContour(c, base + oP, (size_t)nP, base + oL, (size_t)nL, axis, (size_t)nW, out_polylines, pDev, out_slices, sDev);
+}
+// Internal (the tests and the probe): the workgroups of this context's contour-measure launches; 0: as many as fill the device.  Every grid gives the same bytes.
+int ft_ctx_contour_measure_grid(ft_ctx* c, int32_t workgroups) {
+    if (!c || workgroups < 0 || workgroups > 65536) return setErr(FT_ERR_INVALID, "bad argument");
+    c->contourGrid = (unsigned)workgroups;
+    return FT_OK;
+}
+// Internal (tools/contour_measure_probe.py and the tests): eager = 1: the terms kernel adds every lane's terms by itself — the form without the
+// segmented reduction across the wave, which gives the same bytes
+int ft_ctx_contour_measure_probe(ft_ctx* c, int32_t eager) {
+    if (!c || eager < 0 || eager > 1) return setErr(FT_ERR_INVALID, "bad argument");
+    c->contourEager = eager;
     return FT_OK;
 }
 

@@ -24,6 +24,7 @@ FILES = ["fraytracer_amd/csrc/kernels.hip", "fraytracer_amd/csrc/ft_math.h", "fr
          "fraytracer_amd/csrc/multi.cpp", "fraytracer_amd/csrc/mesh.hip", "fraytracer_amd/csrc/ft_mesh.h", "fraytracer_amd/csrc/slice.hip", "fraytracer_amd/csrc/ft_slice.h",
          "fraytracer_amd/csrc/refine.hip", "fraytracer_amd/csrc/ft_refine.h", "fraytracer_amd/csrc/shells.hip", "fraytracer_amd/csrc/ft_shells.h",
          "fraytracer_amd/csrc/measure.hip", "fraytracer_amd/csrc/ft_measure.h",
+         "fraytracer_amd/csrc/contour_measure.hip", "fraytracer_amd/csrc/ft_contour_measure.h",
          "fraytracer_amd/csrc/loop_layout.py", "fraytracer_amd/csrc/Makefile", "include/fraytracer_hip.h"]
 
 

@@ -417,10 +417,15 @@ namespace Slice {
 struct Contours {
     std::vector<ft_vec3> points; std::vector<ft_polyline> polylines; std::vector<ft_vec3> normal; std::vector<int32_t> material;
     int64_t closed = 0, skipped = 0; int32_t axis = 2, slices = 0;
+    // measures (one per polyline) and layerMeasures (one per slice, holes subtracted): filled where the request asked for measures (the header's
+    // "Contour measures"); the centroid of a record is moment / area in the plane's (u, v)
+    std::vector<ft_contour_measure> measures; std::vector<ft_slice_measure> layerMeasures;
 };
-// refineSteps: as Mesh::Request's (ft_slice_lattice_refined): the points are then the refined mesh vertices of the same edges
-struct Request { int32_t axis = 2; float iso = 0.0f; bool normal = false; float normalEpsilon = 0.0f; bool material = false; int32_t refineSteps = -1; };
-inline Contours read(ft_slices* slices) {
+// refineSteps: as Mesh::Request's (ft_slice_lattice_refined): the points are then the refined mesh vertices of the same edges.  measures: also each
+// polyline's and each slice's length, signed area, first moment and box (ft_slices_measure)
+struct Request { int32_t axis = 2; float iso = 0.0f; bool normal = false; float normalEpsilon = 0.0f; bool material = false; int32_t refineSteps = -1;
+                 bool measures = false; };
+inline Contours read(ft_slices* slices, bool measures = false) {
     struct Owner { ft_slices* s; ~Owner() { ft_slices_destroy(s); } } own{slices};
     ft_slices_info info{};
     check(ft_slices_get_info(slices, &info));
@@ -432,6 +437,11 @@ inline Contours read(ft_slices* slices) {
     if (info.has_material) out.material.resize((size_t)info.n_points);
     check(ft_slices_read(slices, out.points.data(), out.polylines.data(), info.has_normal ? out.normal.data() : nullptr,
                          info.has_material ? out.material.data() : nullptr));
+    if (measures) {
+        out.measures.resize(out.polylines.size());
+        out.layerMeasures.resize((size_t)info.n_slices);
+        check(ft_slices_measure(slices, out.measures.empty() ? nullptr : out.measures.data(), out.layerMeasures.empty() ? nullptr : out.layerMeasures.data()));
+    }
     return out;
 }
 inline Contours ofLattice(const SdfScene& scene, const ft_lattice& lattice, const Request& r = Request{}) {
@@ -440,14 +450,14 @@ inline Contours ofLattice(const SdfScene& scene, const ft_lattice& lattice, cons
     const uint32_t flags = (r.normal ? FT_SLICE_NORMAL : 0u) | (r.material ? FT_SLICE_MATERIAL : 0u);
     s.done(r.refineSteps < 0 ? ft_slice_lattice(s.ctx, s.get(), &lattice, r.axis, r.iso, r.normalEpsilon, flags, &slices)
                              : ft_slice_lattice_refined(s.ctx, s.get(), &lattice, r.axis, r.iso, r.normalEpsilon, flags, r.refineSteps, &slices), nullptr);
-    return read(slices);
+    return read(slices, r.measures);
 }
 // any float32 lattice already in host memory: nx * ny * nz values, k contiguous (ft_slice_values)
-inline Contours ofValues(ft_ctx* ctx, const ft_lattice& lattice, const std::vector<float>& values, int32_t axis = 2, float iso = 0.0f) {
+inline Contours ofValues(ft_ctx* ctx, const ft_lattice& lattice, const std::vector<float>& values, int32_t axis = 2, float iso = 0.0f, bool measures = false) {
     if (values.size() != (size_t)lattice.nx * (size_t)lattice.ny * (size_t)lattice.nz) throw std::invalid_argument("Slice::ofValues: one value per lattice point");
     ft_slices* slices = nullptr;
     check(ft_slice_values(ctx, &lattice, values.data(), axis, iso, &slices));
-    return read(slices);
+    return read(slices, measures);
 }
 }  // namespace Slice
 

@@ -60,6 +60,13 @@ type FtSlicesInfo = { NPoints : int64; NPolylines : int64; NClosed : int64; NSki
 /// box, the triangles left out for a non-finite coordinate, and the call's extent exponent E.  moment[3] and the two float[3] boxes are spelled out
 [<Struct; StructLayout(LayoutKind.Sequential)>]
 type FtShellMeasure = { Area : float; Volume : float; MomentX : float; MomentY : float; MomentZ : float; BboxMin : Vector3; BboxMax : Vector3; NUnmeasured : int; ExtentExponent : int }
+/// ft_contour_measure (56 bytes): a polyline's length, signed area (positive: an outer boundary, negative: a hole), first moment in the plane's (u, v)
+/// (the centroid is Moment / Area), box, the segments left out for a non-finite coordinate, and the call's extent exponent E
+[<Struct; StructLayout(LayoutKind.Sequential)>]
+type FtContourMeasure = { Length : float; Area : float; MomentU : float; MomentV : float; BboxMinU : float32; BboxMinV : float32; BboxMaxU : float32; BboxMaxV : float32; NUnmeasured : int; ExtentExponent : int }
+/// ft_slice_measure (72 bytes): the same per slice, holes subtracted, and the slice's polylines, closed ones, outer loops and holes
+[<Struct; StructLayout(LayoutKind.Sequential)>]
+type FtSliceMeasure = { Length : float; Area : float; MomentU : float; MomentV : float; BboxMinU : float32; BboxMinV : float32; BboxMaxU : float32; BboxMaxV : float32; NPolylines : int; NClosed : int; NOuter : int; NHoles : int; NUnmeasured : int; ExtentExponent : int }
 
 /// ft_form_trace_result: SdfFormTraceResult voption (Types.fs:32-37), Hit = 0 is ValueNone
 [<Struct; StructLayout(LayoutKind.Sequential)>]
@@ -165,6 +172,10 @@ module Native =
     // the device.  records: a pinned FtShellMeasure[] (ShellMeasure records of 72 bytes: one per shell, or one), or device memory, 8-byte aligned
     [<DllImport(Lib)>] extern int ft_shells_measure(nativeint mesh, nativeint shells, nativeint records)
     [<DllImport(Lib)>] extern int ft_mesh_measure(nativeint mesh, nativeint record)
+    // contour measures (the header's "Contour measures" states the rule): per polyline and per slice of a stack of contours, length, signed area,
+    // first moment and box, summed exactly on the device.  polylines: a pinned FtContourMeasure[] (one per polyline), slices: a pinned
+    // FtSliceMeasure[] (one per slice), or device memory, 8-byte aligned; either may be 0n, but not both
+    [<DllImport(Lib)>] extern int ft_slices_measure(nativeint slices, nativeint polylines, nativeint slices_out)
     [<DllImport(Lib)>] extern int ft_form_try_trace(nativeint ctx, nativeint scene, Ray[] rays, int64 n, [<Out>] FtFormTraceResult[] out, FtStats& stats)
     [<DllImport(Lib)>] extern int ft_object_try_trace(nativeint ctx, nativeint scene, Ray[] rays, int64 n, [<Out>] FtObjectTraceResult[] out, FtStats& stats)
     // ray buffers in device memory (rays 16-byte aligned, 32 B each): no scratch, no copy, not synchronised; pair with ft_collect_stats

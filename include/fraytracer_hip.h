@@ -719,6 +719,76 @@ typedef struct ft_shell_measure {
 int ft_shells_measure(const ft_mesh*, const ft_shells*, ft_shell_measure* out);
 int ft_mesh_measure(const ft_mesh*, ft_shell_measure* out);
 
+/* Contour measures: per polyline of a stack of contours its length, signed enclosed area, first moment and box in the plane, and the same per slice,
+ * computed on the device where the points lie.  What "Measures" does for shells: float64 terms by a fixed sequence of individually rounded
+ * operations, one quantisation per term, exact integer sums.  Every bit of every result is a pure function of the input; this is the rule, all of it.
+ * What it shares with "Measures" is stated there.
+ *
+ * Input: points float32[nP][3]; nL polylines {first, count, slice, closed} (ft_polyline: the points [first, first + count)); an axis a in {0, 1, 2}
+ *     and a slice count nW.  The in-plane coordinates are u = (a + 1) % 3 and v = (a + 2) % 3, as in "Slicing".  Nothing reads the coordinate along
+ *     a, except the extent.
+ * Extent: E is "Measures"' extent, taken over all finite coordinates (all three) of all nP points, part of a polyline or not.
+ * Segments: polyline l with count = m has the segments (P_i, P_i+1), 0 <= i < m - 1, and, if closed != 0, the closing segment (P_m-1, P_0).  (A
+ *     closed polyline of one point has the one segment (P_0, P_0); a polyline of no points has none.)
+ * Measured segments: a segment is measured iff its four in-plane coordinates are finite.  Any other segment adds nothing to any sum and 1 to its
+ *     polyline's n_unmeasured.  Zero-length segments are measured.
+ * Terms of a measured segment (P, Q): the four float32 coordinates are widened to float64 (exact); then every -, *, + is one float64 operation,
+ *     never fused, operands in the order written:
+ *         du = Q.u - P.u,  dv = Q.v - P.v
+ *         L_t   = sqrt(du du + dv dv)                                           sqrt correctly rounded
+ *         C_t   = P.u Q.v - Q.u P.v                                             twice the signed area of (0, P, Q)
+ *         M_t,u = C_t (P.u + Q.u)
+ *         M_t,v = C_t (P.v + Q.v)
+ * Bounds, from |coordinate| < 2^E (exact values first, then the roundings):
+ *     length:  |du|, |dv| < 2^(E+1), so du^2 + dv^2 < 2 * 2^(2E+2) = 2^(2E+3) and L_t < sqrt(2) * 2^(E+1) < 2^(E+2).  B_L = E + 2.
+ *     area:    each of the two products is below 2^(2E) in magnitude, their difference below 2 * 2^(2E) = 2^(2E+1) < 2^(2E+2).  B_C = 2E + 2.
+ *     moment:  |P.u + Q.u| < 2^(E+1), so |M_t| < 2^(2E+1) * 2^(E+1) = 2^(3E+2) < 2^(3E+3).  B_M = 3E + 3.
+ *     Each term is reached by at most six roundings of relative size 2^-53 of intermediates that obey the same bounds, and each exact bound leaves a
+ *     factor of at least 1.41 (length; 2 area, 2 moment) to its power of two, so a rounded term stays below 2^B, let alone 2^(B+1).
+ *     No intermediate leaves float64's normal range for -148 <= E <= 128: the smallest non-zero product of three float32 values (or of two float32
+ *     differences) is at least 2^-447, the largest term below 2^387; the quantisation scales by 2^s with -297 <= s <= 531, so a scaled non-zero
+ *     term is at least 2^-744, still normal, and none goes beyond 2^91.
+ * Quantisation, sums, results: "Measures"' word for word.  s_K = 90 - B_K, q = round-half-to-even(term * 2^s_K) as a mathematical integer; the
+ *     sums are 128-bit two's-complement integers; S_K = fl64(Q_K) * 2^(-s_K).  A polyline has fewer than 2^31 segments and a call fewer than 2^31
+ *     points, so no sum, per polyline or per slice, leaves +-2^122.
+ * Polyline record: ft_contour_measure, 56 B.  length = S_L; area = S_C / 2.0; moment[0] = S_M,u / 6.0 and moment[1] = S_M,v / 6.0, each one float64
+ *     division.  moment is the integral of (u, v) over the enclosed area; the centroid is moment / area.  bbox_min[2] / bbox_max[2]: over the finite
+ *     u and the finite v of the polyline's points, by "Measures"' ordered key, +inf / -inf without a finite value.  n_unmeasured.  extent_exponent is
+ *     E, the same in every record of a call.
+ * Sign: with positive steps along u and v a closed outer boundary has area > 0 and a closed hole area < 0: "Slicing"'s direction rule makes outer
+ *     boundaries run counter-clockwise in the lattice's (u, v) indices, and a negative step along u or v (not both) mirrors the plane and flips the
+ *     sign.  The area and moment of an open polyline are the rule's numbers over its m - 1 segments and mean nothing geometric.
+ * Slice record: ft_slice_measure, 72 B, for each slice w, 0 <= w < nW.  Q_L(w) is the exact integer sum of Q_L over all polylines with slice == w;
+ *     Q_C(w) and Q_M(w) are the exact integer sums over the closed ones only; they are converted and divided as above, so holes subtract and area is
+ *     the section's enclosed area.  n_polylines, n_closed; n_outer counts the closed polylines with Q_C > 0, n_holes those with Q_C < 0;
+ *     n_unmeasured is the sum of the polylines'; the box is over all of the slice's polylines' points; extent_exponent is E.  A slice without
+ *     polylines has zeros and the +inf / -inf box.
+ * Empty input: contours without polylines give FT_OK and need no device; the n_slices slice records (zeros, the +inf / -inf box, E = 0) are still
+ *     written if asked for.
+ *
+ * ft_slices_measure writes n_polylines records to out_polylines and n_slices records to out_slices, in the contours' order.  Either output may be
+ * NULL, but not both, unless nothing would be written.  Each is host memory or device memory (8-byte aligned): the direction is taken from the
+ * address, as in ft_shells_measure.  A host output synchronises the context's stream once (once for both); with device outputs nothing is
+ * synchronised: the records are ordered with whatever the context launches next.  The contours may have outlived their scene.
+ * Refusals, all made before the device is asked for, in this order: FT_ERR_INVALID for NULL (the contours; both outputs although something would be
+ * written), for a misaligned device pointer, for out_polylines identical to out_slices; empty contours: FT_OK; then FT_ERR_NO_DEVICE on a host-only
+ * context; FT_ERR_HIP for a failed allocation.
+ * Work memory, in a buffer the context keeps: 84 B per polyline (four 128-bit sums, four box keys, one counter), 100 B per slice (four 128-bit sums,
+ * four box keys, five counters), the 4-byte extent, and 56 B per polyline and 72 B per slice of staging for the outputs that are host memory. */
+typedef struct ft_contour_measure {
+    double length, area, moment[2];
+    float bbox_min[2], bbox_max[2];
+    int32_t n_unmeasured;         /* segments of the polyline that were not measured */
+    int32_t extent_exponent;      /* E */
+} ft_contour_measure;             /* 56 B */
+typedef struct ft_slice_measure {
+    double length, area, moment[2];
+    float bbox_min[2], bbox_max[2];
+    int32_t n_polylines, n_closed, n_outer, n_holes, n_unmeasured;
+    int32_t extent_exponent;      /* E */
+} ft_slice_measure;               /* 72 B */
+int ft_slices_measure(const ft_slices*, ft_contour_measure* out_polylines, ft_slice_measure* out_slices);
+
 /* Single-process multi-GPU form (what an F# host would call): the flattened scene is
  * re-uploaded to each further device with ft_scene_clone, every device renders its column
  * stripes (stripe_rank = index in ctxs[], stripe_ranks = n) on its own host thread, and the
