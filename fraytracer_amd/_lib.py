@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # FRAYTRACER_HIP_LIB: diagnostic builds only (tools/union_divergence.py); the product is the in-tree library
 LIB_PATH = os.environ.get("FRAYTRACER_HIP_LIB") or os.path.join(_HERE, "libfraytracer_hip.so")
 
-FT_OPT_REFILL_MIN, FT_OPT_MAX_BLOCKS_PER_CU, FT_OPT_HOST_CHUNKS, FT_OPT_HOST_PIN, FT_OPT_TAIL_K, FT_OPT_MATH, FT_OPT_GUIDED, FT_OPT_CHUNK, FT_OPT_CULL, FT_OPT_ESCAPE, FT_OPT_LAZY_UNION, FT_OPT_CARVED, FT_OPT_REUSE, FT_OPT_CERT, FT_OPT_CERT_POLICY, FT_OPT_ORDER, FT_OPT_OCCL, FT_OPT_OCCL_POLICY, FT_OPT_TRY_HINT = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19
+FT_OPT_REFILL_MIN, FT_OPT_MAX_BLOCKS_PER_CU, FT_OPT_HOST_CHUNKS, FT_OPT_HOST_PIN, FT_OPT_TAIL_K, FT_OPT_MATH, FT_OPT_GUIDED, FT_OPT_CHUNK, FT_OPT_CULL, FT_OPT_ESCAPE, FT_OPT_LAZY_UNION, FT_OPT_CARVED, FT_OPT_REUSE, FT_OPT_CERT, FT_OPT_CERT_POLICY, FT_OPT_ORDER, FT_OPT_OCCL, FT_OPT_OCCL_POLICY, FT_OPT_TRY_HINT, FT_OPT_DEPART = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20
 FT_MATH_FIXED, FT_MATH_GLIBC_FMA, FT_MATH_GLIBC_SSE2 = 0, 1, 2
 FT_OK, FT_ERR_INVALID, FT_ERR_NO_DEVICE, FT_ERR_HIP, FT_ERR_UNSUPPORTED, FT_ERR_EMPTY, FT_ERR_COMM = 0, -1, -2, -3, -4, -5, -6
 
@@ -256,6 +256,7 @@ SYMBOLS = {
     "ft_scene_support_sphere": (C.c_int, [_P, C.POINTER(C.c_float)]),
     "ft_scene_miss_certificate": (C.c_int, [_P, C.POINTER(C.c_float)]),
     "ft_scene_occlusion_certificate": (C.c_int, [_P, C.POINTER(C.c_float)]),
+    "ft_scene_departure_certificate": (C.c_int, [_P, C.POINTER(C.c_float)]),
     "ft_scene_miss_certificate_clusters": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_int32]),
     "ft_math_eval": (C.c_int, [_P, C.c_int32, _P, _P, C.c_int64, _P]),
     "ft_selftest_fastmath": (C.c_int, [_P, C.POINTER(C.c_uint64)]),

@@ -464,7 +464,9 @@ class Device:
     # options of a stream of frames, named like the ones above but kept apart from them (OPTIONS is the list the ABI test pins):
     # FT_OPT_TRY_HINT, 1 (default) a tile's bundle-certificate tries follow what its last frame recorded, 2 record only, 0 off; same frame, fewer sdf_evals
     # (tests/helpers.py options_left_at_defaults walks OPTIONS only: a test that changes one of these restores it itself, tests/test_try_hint.py checks its own)
-    STREAM_OPTIONS = {"try_hint": _lib.FT_OPT_TRY_HINT}
+    # FT_OPT_DEPART, 1 (default) the frames that follow try hints try their shadow rays' miss certificate at birth under a margin that grows along the ray,
+    # 2 every camera launch of the lean family, 0 off; same frame, fewer sdf_evals (tests/test_gpu_departure_certificate.py checks its own)
+    STREAM_OPTIONS = {"try_hint": _lib.FT_OPT_TRY_HINT, "depart": _lib.FT_OPT_DEPART}
 
     def set_option(self, name, value):
         """ft_ctx_set_option: per-context switches (the library reads no environment variables)"""
@@ -1208,6 +1210,12 @@ class DeviceScene:
         v = (C.c_float * 7)()
         check(lib.ft_scene_occlusion_certificate(self._scene, v))
         return dict(zip(("step", "base", "eps_min", "cap", "len_inv", "near", "reach"), (float(x) for x in v)))
+
+    def departure_certificate(self):
+        """{step, base, kappa, eps_min, clip, len_factor, steps}: the constants of the smooth-union kernel's departure certificate (base < 0: none)"""
+        v = (C.c_float * 7)()
+        check(lib.ft_scene_departure_certificate(self._scene, v))
+        return dict(zip(("step", "base", "kappa", "eps_min", "clip", "len_factor", "steps"), (float(x) for x in v)))
 
     def miss_certificate_clusters(self):
         """(clusters, members): clusters a float32 array (K, 4) of centre xyz and radius, members a list of K arrays (n_c, 4) of the children

@@ -81,6 +81,7 @@ struct ft_ctx {
     int optOcclPolicy = 0;                                 // FT_OPT_OCCL_POLICY: 0 = the shipped schedule (FT_OCCL_PERIOD ...)
     int optOrder = 1;                                      // FT_OPT_ORDER: 1 = frames hand their heavy tiles out first, from the costs the scene's last launch of the same grid recorded; 2 = record only; 0 = off
     int optTryHint = 1;                                    // FT_OPT_TRY_HINT: 1 = a frame's tiles schedule their bundle-certificate tries from what the scene's last launch of the same grid recorded per tile; 2 = record only; 0 = off
+    int optDepart = 1;                                     // FT_OPT_DEPART: 1 = the launches that follow try hints try their shadow rays' miss certificate at birth under the margin that grows along the ray; 2 = every lean launch that passes the gate; 0 = off
     int fieldBrick = -1;                                   // brick shape of the lattice launches: -1 by kernel family (launchField), else an index into FT_FIELD_BRICKS (ft_ctx_field_brick: the probe's shapes)
     uint32_t meshTile = FT_MESH_TILE_DEFAULT;              // lattice points per workgroup of the mesher's kernels (ft_ctx_mesh_tile: the probe's tiles)
     uint32_t sliceTile = FT_SLICE_TILE_DEFAULT;            // items per workgroup of the slicer's tiled kernels (ft_ctx_slice_tile: the tests' and the probe's tiles)
@@ -524,6 +525,31 @@ TileOrderSlot* tileOrder(const ft_ctx* c, const ft_scene* s, int lane, const FtT
     return slot;
 }
 
+// Departure certificate (FT_OPT_DEPART; scene.cpp "Departure certificate"): the margin of the per-lane miss certificate's tries, and where it is tilted
+// their schedule.  Every launch gets the scene's flat margin (slope 0: what the per-lane tries have always conceded).  The tilted one goes to
+//   1  the launches that follow try hints (a.tryHint: same slot key, a camera within FT_HINT_MAX_SHIFT, word 0, narrow tiles, FT_OPT_TRY_HINT = 1) and no
+//      other: first frames, wide-tiled frames, explicit words, views, ray buffers and EXTENSION launches count what they counted, to the last evaluation
+//   2  every launch of the lean family (tests, fuzz),
+// where certificates run at all (a.cert), the scene has the constants, and the launch has ONE epsilon no smaller than the scene's floor: a camera launch
+// (mode 0, no hit records).  slope = depE / epsilon and base = 2 depE + depB + depK slope^2 are formed here in double; a lane of another epsilon (none
+// in these launches) would be left out by epsMin.  Under word 0 the shadow rays are due at the step they are born with (1 with FT_OPT_REUSE, as
+// occlSchedule counts).  Where certSchedule's tile-width rule left the per-lane tries out (every launch that follows hints), primary rays stay out and a
+// wave tries once FT_DEPART_MIN lanes wait, and again FT_DEPART_REPEAT steps after a failure; a wide-tiled frame (option 2 only) keeps its primary
+// tries, due lanes and repeat, under the tilted margin too.  An explicit word is taken as it stands and only the margin of its tries changes.
+constexpr uint32_t FT_DEPART_MIN = 16u, FT_DEPART_REPEAT = 3u;   // measured: profiles/departure_certificate_policies.txt
+void departSchedule(const ft_ctx* c, const ft::FlatScene& f, FtRenderArgs& a) {
+    a.dep = FtCertMargin{0.0f, 0.0f, f.hdr.certM, f.hdr.certClip, f.hdr.certLenF, 0.0f, f.hdr.certSteps, 0u};
+    const bool asked = c->optDepart == 2 || (c->optDepart == 1 && a.tryHint != 0u);
+    if (!(asked && a.cert != 0u && f.dep.b >= 0.0f && a.mode == 0u && a.shade == 0u && a.eps >= f.dep.epsMin && a.eps <= f.hdr.escR)) return;
+    const double slope = (double)f.dep.e / (double)a.eps * (1.0 + 1e-6);
+    const double base = (2.0 * (double)f.dep.e + (double)f.dep.b + (double)f.dep.k * slope * slope) * (1.0 + 1e-6);
+    a.dep = FtCertMargin{(float)slope, (float)(slope / 0.9 * (1.0 + 1e-6)), (float)base, f.dep.clip, f.dep.lenF, a.eps, f.dep.steps, 0u};
+    if (c->optCertPolicy == 0) {
+        if (a.certShadow == 0xffffffffu) { a.certMin = FT_DEPART_MIN; a.certRepeat = FT_DEPART_REPEAT; }   // narrow tiles: the tries are the shadow rays' alone
+        a.certShadow = a.reuse;
+    }
+}
+
 // launch the persistent trace kernel over nJobs jobs
 // lane 0 = the context's stream; lane 1 = a second stream with its own job counter, so that two launches can be in flight
 // (the drain of one overlaps the start of the next: DESIGN.md section 6)
@@ -550,6 +576,7 @@ int launchTrace(ft_ctx* c, const ft_scene* s, FtRenderArgs& a, int lane = 0) {
     certSchedule(c, s->flat, plan.variant, a);
     occlSchedule(c, s->flat, a);
     TileOrderSlot* slot = tileOrder(c, s, lane, key, a);
+    departSchedule(c, s->flat, a);
     HIP_TRY(hipMemsetAsync(counter, 0, sizeof(uint32_t), stream));
     if ((rc = timedLaunch(c, stream, "ft_launch_trace", [&] { return ft_launch_trace(&a, blocks, plan.lds, stream); }))) return rc;
     if (slot && c->optOrder == 1) {                        // behind the frame on its own stream: no synchronisation, nothing comes back to the host
@@ -583,6 +610,7 @@ constexpr OptionSpec kOptions[] = {
     {FT_OPT_OCCL, &ft_ctx::optOccl, 0, 1, "FT_OPT_OCCL: 0 or 1"},
     {FT_OPT_OCCL_POLICY, &ft_ctx::optOcclPolicy, 0, 0x40ffff, "FT_OPT_OCCL_POLICY: 0, or bits 0-7 period, 8-15 first step, 16-23 candidates (0 .. 64)"},
     {FT_OPT_TRY_HINT, &ft_ctx::optTryHint, 0, 2, "FT_OPT_TRY_HINT: 0 off, 1 tries scheduled from the last frame, 2 record only"},
+    {FT_OPT_DEPART, &ft_ctx::optDepart, 0, 2, "FT_OPT_DEPART: 0 off, 1 on the launches that follow try hints, 2 on every launch that passes the gate"},
 };
 const OptionSpec* findOption(int32_t id) {
     for (const OptionSpec& o : kOptions) if (o.id == id) return &o;
@@ -3056,6 +3084,12 @@ int ft_scene_occlusion_certificate(const ft_scene* s, float out[7]) {
     if (!s || !out) return setErr(FT_ERR_INVALID, "null argument");
     static_assert(sizeof(FtOccl) == 7 * sizeof(float), "out[7] is FtOccl, field by field");
     memcpy(out, &s->flat.occ, sizeof(FtOccl));
+    return FT_OK;
+}
+int ft_scene_departure_certificate(const ft_scene* s, float out[7]) {
+    if (!s || !out) return setErr(FT_ERR_INVALID, "null argument");
+    const FtDepart& d = s->flat.dep;
+    out[0] = d.e; out[1] = d.b; out[2] = d.k; out[3] = d.epsMin; out[4] = d.clip; out[5] = d.lenF; out[6] = (float)d.steps;
     return FT_OK;
 }
 int ft_scene_miss_certificate_clusters(const ft_scene* s, int32_t* nClusters, int32_t* nChildren, float* out, int32_t capacity) {

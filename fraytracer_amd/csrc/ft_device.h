@@ -124,6 +124,15 @@ struct FtSceneDev {             // passed by value as kernel argument
 // factor; near: how far from a sphere f can still be <= 0; reach: the largest t* (the float32 sum cannot underflow before it)
 struct FtOccl { float e, b, epsMin, cap, lenInv, near, reach; };
 
+// Departure certificate (kernels.hip ft_miss_certificate with a tilted margin; scene.cpp "Departure certificate"): the scene's constants.  b < 0: none.
+// e: drift per step (occE); b: the margin's constant part; k: kappa = k slope^2, the pad of the per-child bound; epsMin: the smallest epsilon tried;
+// clip: the clip ball's pad (the largest drift conceded); lenF / steps: the count-down's padding factor and the steps a certified march may still take
+struct FtDepart { float e, b, k, epsMin, clip, lenF; uint32_t steps; };
+// The margin one call of ft_miss_certificate concedes, from the argument block (wave-uniform): base + slope t at line parameter t.  slope = 0 with the
+// scene's certM, certClip, certLenF and certSteps is the flat certificate; the tilted one is the host's (capi.cpp departSchedule).  slope09 = slope / 0.9:
+// what a cluster bound pays per unit of its radius; epsMin: the lanes below it are left out
+struct FtCertMargin { float slope, slope09, base, clip, lenF, epsMin; uint32_t steps, pad; };
+
 // "Carved union" kernels (FtSceneDev.fastPath == 3; kernels.hip ft_eval_carved): the whole program is ONE grid union of plain primitives
 // followed by at most FT_CARVE_TAIL intersect / subtract steps with one primitive each — the shape of the reference's own scene,
 // subtract(intersect(union [1000 tori], [sphere]), sphere) (Program.fs:67-77).  The flattener records the tail here and lays the union's

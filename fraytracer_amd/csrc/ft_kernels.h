@@ -141,8 +141,11 @@ struct FtRenderArgs {
     // receives what this launch's bundles did; tryHint = 1: the word a tile's last frame left schedules its bundle tries (needs tileHint)
     uint32_t* tileHint;
     uint32_t tryHint, pad1;
+    // departure certificate (lean kernel; FT_OPT_DEPART; appended): the margin of the per-lane miss certificate's tries (ft_device.h FtCertMargin).  The flat
+    // margin of the scene, slope 0, on every launch the option leaves alone: those count what they counted (capi.cpp departSchedule)
+    FtCertMargin dep;
 };
-static_assert(offsetof(FtRenderArgs, occ) == 860 && offsetof(FtRenderArgs, tileHint) == 888 && sizeof(FtRenderArgs) == 904, "the kernels' argument block does not move");
+static_assert(offsetof(FtRenderArgs, occ) == 860 && offsetof(FtRenderArgs, tileHint) == 888 && offsetof(FtRenderArgs, dep) == 904 && sizeof(FtRenderArgs) == 936, "the kernels' argument block does not move");
 #define FT_MAX_VIEWS 64       // views per launch (one PH_CAM value per lane); ft_render_views splits larger batches
 
 // The forms of the trace kernel (kernels.hip FT_TRACE_FORMS builds every one of them from the same table of builds): what a job is and what it leaves.

@@ -1431,30 +1431,41 @@ __device__ __forceinline__ bool ft_never_enters(const FtSceneDev& S, const f3 o,
 }
 
 // The gate and the clipped segment that both miss certificates below share (ft_miss_certificate, ft_bundle_certificate): -> the lane passes the gate and its line o + t dir has a non-empty part t0 < t < t1 inside the
-// clip ball (t0 >= 0, t1 <= Length * certLenF).
+// clip ball (t0 >= 0, t1 <= Length * certLenF).  epsMin, clip, lenF, stepsLeft: 0, certClip, certLenF and certSteps for the flat margin; the departure
+// certificate's own where the margin is tilted (FtCertMargin).
 __device__ __forceinline__ bool ft_cert_segment(const FtSceneDev& S, bool test, const f3 o, const f3 dir, float eps, float len, uint32_t steps,
-                                                float& t0, float& t1) {
+                                                float epsMin, float clip, float lenF, uint32_t stepsLeft, float& t0, float& t1) {
     const f3 w = o - mk3(S.escC[0], S.escC[1], S.escC[2]);
     const float ww = ft_dot(w, w), dd = ft_dot(dir, dir), b = ft_dot(w, dir);
-    bool ok = test && S.certM >= 0.0f && S.escR >= 0.0f && eps >= 0.0f && eps <= S.escR && len > 0.0f && len < 1e9f && dd >= 0.81f && dd <= 1.44f &&
-              ww <= S.certRho2 && steps < FT_STEP_CAP - S.certSteps;
-    const float R = (S.escR + eps + S.certClip) * 1.001f;              // the 0.1 % covers the rounding of the end points below
+    bool ok = test && S.certM >= 0.0f && S.escR >= 0.0f && eps >= epsMin && eps <= S.escR && len > 0.0f && len < 1e9f && dd >= 0.81f && dd <= 1.44f &&
+              ww <= S.certRho2 && steps < FT_STEP_CAP - stepsLeft;
+    const float R = (S.escR + eps + clip) * 1.001f;                    // the 0.1 % covers the rounding of the end points below
     const float disc = b * b - dd * (ww - R * R);
     ok = ok && disc > 0.0f;
     const float sq = __builtin_amdgcn_sqrtf(ok ? disc : 0.0f), idd = 1.0f / dd;
-    t0 = __builtin_fmaxf((-b - sq) * idd, 0.0f); t1 = __builtin_fminf((sq - b) * idd, len * S.certLenF);
+    t0 = __builtin_fmaxf((-b - sq) * idd, 0.0f); t1 = __builtin_fminf((sq - b) * idd, len * lenF);
     return ok && t1 > t0;
+}
+__device__ __forceinline__ bool ft_cert_segment(const FtSceneDev& S, bool test, const f3 o, const f3 dir, float eps, float len, uint32_t steps,
+                                                float& t0, float& t1) {
+    return ft_cert_segment(S, test, o, dir, eps, len, steps, 0.0f, S.certClip, S.certLenF, S.certSteps, t0, t1);
 }
 
 // Squared distance of the centre of record prm from the segment p0 + t sv, 0 <= t <= 1 (iss = 1 / |sv|^2): projection, clamp, residual.  Both miss
 // certificates below bound with it: fused multiply-adds, not the reference's arithmetic.
+// t: the clamped projection itself, for the margin that grows along the segment.
 template <class P>
-__device__ __forceinline__ float ft_seg_dist2(const P prm, const f3 p0, const f3 sv, const float iss) {
+__device__ __forceinline__ float ft_seg_dist2(const P prm, const f3 p0, const f3 sv, const float iss, float& t) {
     const float vx = prm.x - p0.x, vy = prm.y - p0.y, vz = prm.z - p0.z;
-    float t = __builtin_fmaf(vz, sv.z, __builtin_fmaf(vy, sv.y, vx * sv.x)) * iss;
+    t = __builtin_fmaf(vz, sv.z, __builtin_fmaf(vy, sv.y, vx * sv.x)) * iss;
     t = __builtin_amdgcn_fmed3f(t, 0.0f, 1.0f);
     const float ex = __builtin_fmaf(-t, sv.x, vx), ey = __builtin_fmaf(-t, sv.y, vy), ez = __builtin_fmaf(-t, sv.z, vz);
     return __builtin_fmaf(ez, ez, __builtin_fmaf(ey, ey, ex * ex));
+}
+template <class P>
+__device__ __forceinline__ float ft_seg_dist2(const P prm, const f3 p0, const f3 sv, const float iss) {
+    float t;
+    return ft_seg_dist2(prm, p0, sv, iss, t);
 }
 
 // the threshold both miss certificates below hold their sums of terms 2^(A (dist - r)) against, from its log2 xt = A (epsilon + certM)
@@ -1473,17 +1484,21 @@ __device__ __forceinline__ float ft_cert_threshold(float xt) { return __builtin_
 // Gated like the escape shortcut: a support sphere and the certificate's constants (certM >= 0: none with a non-finite constant anywhere), 0 <= epsilon <= escR,
 // Length < 1e9, and the drift bound's own conditions: 0.81 <= |dir|^2 <= 1.44, a start within sqrt(certRho2) of escC, certSteps short of the step cap.
 // A run of >= 32 children sums cluster bounds first and refines only the clusters a lane needs (certK != 0, below).
+// The margin m (wave-uniform, from the argument block): base + slope t at line parameter t.  slope = 0 with base = certM is the flat certificate above, with
+// the same bits in its sums (a product with 0 adds -0).  slope > 0 is the departure certificate (scene.cpp "Departure certificate"): a child's term is
+// 2^(A (d_i(t_c) - slope t_c)) at the clamped closest approach t_c that ft_seg_dist2 forms anyway, one more fused multiply-add, the threshold carries
+// slope t0 and the base carries kappa; a cluster's bound pays slope R / 0.9 on top (its members' t_c lie within R / 0.9 of its own).
 // Executed by all 64 lanes (wave-uniform loop); `test`: the lanes that ask.  -> the certificate holds in this lane.
-__device__ __forceinline__ bool ft_miss_certificate(const FtSceneDev& S, const float* __restrict__ ldsC, bool test, const f3 o, const f3 dir, float eps, float len,
-                                                    uint32_t steps) {
+__device__ __forceinline__ bool ft_miss_certificate(const FtSceneDev& S, const FtCertMargin& m, const float* __restrict__ ldsC, bool test, const f3 o, const f3 dir,
+                                                    float eps, float len, uint32_t steps) {
     const FtInstr FT_CONST* in = as_const(S.instr);                    // instruction 0: the run (scene.cpp sets certM only for {RUN, FIN, SETLEAF})
     const float si = in->f0;
     const uint32_t n = in->count;
     const float4* c = reinterpret_cast<const float4*>(ldsC + in->data);
     float t0, t1;
-    bool ok = ft_cert_segment(S, test, o, dir, eps, len, steps, t0, t1);
+    bool ok = ft_cert_segment(S, test, o, dir, eps, len, steps, m.epsMin, m.clip, m.lenF, m.steps, t0, t1);
     const float A = si * 1.44269504f;                                  // terms are 2^(A (dist - r))
-    const float xt = A * (eps + S.certM);
+    const float xt = A * (eps + __builtin_fmaf(m.slope, t0, m.base));
     ok = ok && xt >= -100.0f;                                          // the threshold stays a normal number, far above flushed terms
     if (__ballot(ok) == 0ull) return false;
     const float thr = ft_cert_threshold(xt);
@@ -1492,7 +1507,10 @@ __device__ __forceinline__ bool ft_miss_certificate(const FtSceneDev& S, const f
     const float iss = 1.0f / ft_dot(sv, sv);
     float sum = 0.0f;
     uint32_t i = 0;
-    auto term = [&](const auto prm) { return __builtin_amdgcn_exp2f((__builtin_amdgcn_sqrtf(ft_seg_dist2(prm, p0, sv, iss)) - prm.w) * A); };
+    const float slopeU = ok ? m.slope * (t1 - t0) : 0.0f;              // the slope per unit of the segment's own parameter
+    auto lifted = [&](const auto prm) { float tc; const float d2 = ft_seg_dist2(prm, p0, sv, iss, tc); return __builtin_fmaf(-slopeU, tc, __builtin_amdgcn_sqrtf(d2) - prm.w); };
+    auto term = [&](const auto prm) { return __builtin_amdgcn_exp2f(lifted(prm) * A); };
+    auto bound = [&](const auto prm) { return __builtin_amdgcn_exp2f(__builtin_fmaf(-m.slope09, prm.w, lifted(prm)) * A); };
     if (S.certK != 0u) {
         // Cluster bound (scene.cpp certClusters): n_c 2^(A (dist(S, C) - R)) >= the sum of the cluster's member terms, since dist(S, c_i) - r_i >=
         // dist(S, C) - R for each member and A < 0.  Pass 1 sums the K bounds: a lane below thr holds.  Each lane marks the clusters whose bound reaches
@@ -1505,7 +1523,7 @@ __device__ __forceinline__ bool ft_miss_certificate(const FtSceneDev& S, const f
         float all = 0.0f, rest = 0.0f;
         uint32_t mark = 0u;
         for (uint32_t k = 0; k < S.certK; ++k) {
-            const float bnd = term(cl[2u * k]) * (float)__float_as_uint(cl[2u * k + 1u].x);
+            const float bnd = bound(cl[2u * k]) * (float)__float_as_uint(cl[2u * k + 1u].x);
             all += bnd;
             if (bnd >= mthr) mark |= 1u << k;
             else rest += bnd;
@@ -2184,13 +2202,15 @@ __device__ __forceinline__ void ft_trace_body(const FtRenderArgs& a) {
                     if (ORDER && __ballot(held) != 0ull && lane == 0) hintSt[HINT_NOTE] = ft_hint_note(hintSt[HINT_NOTE], ph == PH_MARCH, tileRound);
                 }
             }
-            // per lane: once enough lanes are due, the wave tries it for all of them at once
+            // per lane: once enough lanes are due, the wave tries it for all of them at once, under the launch's margin (u.dep: the scene's flat certM, or the
+            // departure certificate's tilted one on the launches FT_OPT_DEPART names — capi.cpp departSchedule).  A hold here is not noted in the tile's hint word:
+            // the word records what the bundles of the rays that are left did (DESIGN.md section 4 "Departure certificate")
             const bool due = !ends && (s.phase == PH_MARCH || s.phase == PH_SHADOW) && s.steps >= s.certAt && (!EXT || !s.inside());
             bool tried = false;
             if ((uint32_t)__popcll(__ballot(due)) >= a.certMin) {
                 tried = true;
                 const FtRenderArgs& u = FT_ARGS_AT_USE(LEAN, a);      // the certificate's constants and the retry rule: read in the rounds that try
-                const bool holds = ft_miss_certificate(u.S, ldsC + 0, due, s.o, s.dir, s.eps, s.len, s.steps);
+                const bool holds = ft_miss_certificate(u.S, u.dep, ldsC + 0, due, s.o, s.dir, s.eps, s.len, s.steps);
                 if (due) {
                     if (holds) ends = true;
                     else s.certAt = u.certRepeat != 0u ? s.steps + u.certRepeat : 0xffffffffu;

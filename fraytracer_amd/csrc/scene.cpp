@@ -1068,6 +1068,58 @@ static void occlusionCertificate(FlatScene& out, const CertTerms& t) {
     out.occ.near = (float)(strength * std::log((double)run.count) * 1.001 + occB);   // f(x) <= 0 needs one d_i(x) <= s ln n: the try's cheap exit, nothing rests on it
 }
 
+// Departure certificate (kernels.hip ft_miss_certificate with a margin that grows along the ray; FT_OPT_DEPART): the miss certificate's flat margin pays
+// the drift of the longest march of the scene, and a lit shadow ray, born within epsilon .. 2 epsilon of the surface it leaves, creeps until it has that
+// much clearance.  The occlusion certificate's count, mirrored: a march's drift is paid for by the steps it can take.  A try stands at the lane's float32
+// origin o with direction dir, 0.81 <= |dir|^2 <= 1.44, and asks of the line x(t) = o + t dir
+//     f(x(t)) - m(t) >= epsilon,   m(t) = depE (t / epsilon + 2) + depB + kappa,   for every t of the clipped segment (below).
+// T_k: the sum of the k steps taken from o on (real numbers), p_k the marched float32 point.  Induction over the steps, while the line is inside
+// B(c, Rb) (the start gate certRho2, as for the flat certificate): suppose every earlier value was >= epsilon.
+//   * Then T_k >= k epsilon, so k <= T_k / epsilon, and each step added at most e(3 Rb) (start within Rb of c, steps <= 1.5 Rb long, as in "Miss
+//     certificate"): |p_k - x(T_k)| <= (k + 2) e <= (T_k / epsilon + 2) depE, depE = 1.01 e = occE.  Inside B(c, Rb) T_k <= tMax = 2 Rb / 0.9, and the
+//     kernel tries only epsilon >= depEpsMin, where (tMax / epsilon + 2) depE <= depCap = escR / 20 and tMax / epsilon + 4 <= Ncap = 2^17.
+//   * An evaluated point q with |q - c| >= r + padEval + epsilon is no hit and returns >= epsilon (support property, padEval).  Any other p_k lies
+//     within depCap of x(T_k), so |x(T_k) - c| < escR + epsilon + depCap: the clip radius (depClip = depCap; the flat certificate's step length h is
+//     not needed, epsilon >= depEpsMin bounds the steps), with T_k in [0, Length depLenF) (below).  x(T_k) is on the certified segment, f is
+//     1-Lipschitz, so f(p_k) >= f(x(T_k)) - (T_k / epsilon + 2) depE >= epsilon + depB + kappa, and the reference's float32 value is >= epsilon:
+//     no hit, and the next step is >= epsilon.
+//   * Outside B(c, Rb) the line recedes and the escape proof's argument applies as for the flat certificate, the drift at the exit being <= depCap
+//     <= escR / 20 where that proof has delta < escR / 4.  Steps left: <= Ncap + 2000 receding ones: depSteps; Length: the float32 count-down loses
+//     <= u Length per step, depLenF = 1 + (Ncap + 2002) 4u.  Both are held no smaller than the flat certificate's, so the gate is never wider.
+//   * |dir| != 1 does not enter: T is the line's parameter, and the drift is counted in steps.  depB still carries 1e-6 tMax, as occB does.  A point
+//     light's shadow ray has |dir| = 1 / distance and stays out by the flat gate on |dir|^2.
+//   * Underflow: flushed terms make the reference's value larger (+inf where every term flushes: a miss).  The certificate's own sum is protected as
+//     the flat one's: the threshold's exponent stays >= -100.
+// depB = (3 eGeo + eSum + 1e-6 tMax) 1.01 + 1e-6: occB's terms, with a third eGeo for the float32 parameter u_c of the closest approach, the products
+// slope u_c (t1 - t0) and slope t0, and the threshold's own sum (each below 2^-21 of depCap).
+// Per child: the tilted term needs no new minimisation.  Let D(t) = |x(t) - c_i|, a = |dir|, t_c the closest approach clamped to the segment (what
+// ft_seg_dist2 forms).  On the segment D(t)^2 >= D_c^2 + a^2 (t - t_c)^2 (the cross term is 0 for an inner t_c and >= 0 on the segment's side of a
+// clamped one), so with tau = t - t_c and sigma = slope
+//     D(t) - sigma t >= sqrt(D_c^2 + a^2 tau^2) - sigma tau - sigma t_c >= D_c sqrt(1 - sigma^2 / a^2) - sigma t_c >= D_c - sigma t_c - kappa,
+// kappa = 0.505 b sigma^2 / a^2 for sigma^2 / a^2 <= 0.039 (sqrt(1 - x) >= 1 - 0.505 x there; sigma <= depCap / tMax < 0.009 a), b >= D_c: every
+// child's centre lies within escR of c and the segment within the clip radius <= 2.06 escR, so b = 4.2 escR, a^2 >= 0.81: kappa = depK sigma^2,
+// depK = 1.01 * 0.505 * 4.2 escR / 0.81.  The host forms sigma = depE / epsilon and base = 2 depE + depB + depK sigma^2 per launch (capi.cpp
+// departSchedule).  A cluster bound takes the cluster's own t_C: a member's t_c lies within |c_i - C| / a <= R / 0.9 of it (projection and clamp
+// contract), and dist(S, c_i) - r_i >= dist(S, C) - R as before, so the bound pays sigma R / 0.9 more; this only loosens a bound that pass 2 refines.
+static void departureCertificate(FlatScene& out, const CertTerms& t) {
+    if (!t.ok) return;
+    const FtSceneDev& h = out.hdr;
+    const double escR = t.escR, u = t.u, nCap = 131072.0;
+    const double tMax = 2.0 * t.Rb / 0.9;
+    const double depE = 1.01 * t.e3, depB = (3.0 * t.eGeo + t.eSum + 1e-6 * tMax) * 1.01 + 1e-6, depCap = 0.05 * escR;
+    const double depK = 1.01 * 0.505 * 4.2 * escR / 0.81;
+    if (!(4.0 * depE < depCap && depB < depCap)) return;
+    const double epsMin = 1.01 * std::max(tMax * depE / (depCap - 2.0 * depE), tMax / (nCap - 4.0));
+    if (!(epsMin <= escR)) return;
+    out.dep.e = (float)(depE * (1.0 + 1e-6));
+    out.dep.b = (float)(depB * (1.0 + 1e-6));
+    out.dep.k = (float)(depK * (1.0 + 1e-6));
+    out.dep.epsMin = (float)(epsMin * (1.0 + 1e-6));
+    out.dep.clip = (float)(depCap * (1.0 + 1e-6));
+    out.dep.lenF = std::max(h.certLenF, (float)(1.0 + (nCap + 2002.0) * 4.0 * u));
+    out.dep.steps = std::max(h.certSteps, (uint32_t)(nCap + 2000.0));
+}
+
 // Flatten: run the Flattener over the tree, decide the exact shortcuts' constants step by step (each step above carries its proof), append lights,
 // materials and padding.
 bool flatten(const Builder& b, int object, const float bg[3], const int* lights, int nLights, FlatScene& out, std::string& err) {
@@ -1085,7 +1137,9 @@ bool flatten(const Builder& b, int object, const float bg[3], const int* lights,
     h.fastQ = (fl.anyUnion && fl.unionFastQ) ? 1u : 0u;
     const double escCInf = supportSphere(b, form, h);
     kernelFamily(out, !fl.calls.empty());
-    occlusionCertificate(out, missCertificate(out, escCInf));
+    const CertTerms certTerms = missCertificate(out, escCInf);
+    occlusionCertificate(out, certTerms);
+    departureCertificate(out, certTerms);
     for (int i = 0; i < nLights; ++i) {
         if (lights[i] < 0 || (size_t)lights[i] >= b.lights.size()) { err = "invalid light handle"; return false; }
         out.lights.push_back(b.lights[lights[i]].dev);

@@ -91,6 +91,7 @@ struct FlatScene {                                            // host copy of ev
     static FtSceneDev noShortcuts() { FtSceneDev d{}; d.nSlots = 1; d.escR = -1.0f; d.certM = -1.0f; d.certLenF = 1.0f; d.cullPc = 0xffffffffu; return d; }
     FtSceneDev hdr = noShortcuts();
     FtOccl occ{0.0f, -1.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};    // occlusion certificate (scene.cpp "Occlusion certificate"); b = -1: none
+    FtDepart dep{0.0f, -1.0f, 0.0f, 0.0f, 0.0f, 1.0f, 0u};    // departure certificate (scene.cpp "Departure certificate"); b = -1: none
     std::vector<FtInstr> instr;                               // main program [0, hdr.nInstr), then the sub-programs of call children
     std::vector<float> consts;                                // consts[0, hdr.nStage) is mirrored in LDS by every workgroup
     std::vector<FtGrid> grids;

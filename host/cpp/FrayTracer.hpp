@@ -53,6 +53,8 @@ public:
     // FT_OPT_OCCL (on by default): shadow rays proved to end in a hit stop marching; setOption(FT_OPT_OCCL, 0) marches every one; FT_OPT_OCCL_POLICY: its schedule
     // FT_OPT_TRY_HINT (on by default): a scene's repeated frames try each tile's bundle certificates around the rounds they held on in the last frame;
     // setOption(FT_OPT_TRY_HINT, 0) keeps every frame on the first frame's schedule, 2 records without following
+    // FT_OPT_DEPART (on by default): the frames that follow try hints end lit shadow rays where they are born; setOption(FT_OPT_DEPART, 0) marches them as
+    // before, 2 tries on every camera launch of the kernel family
     int getOption(ft_option option) const { int32_t v = 0; check(ft_ctx_get_option(ctx_, (int32_t)option, &v)); return v; }
     static std::string buildInfo() { return ft_build_info(); }
     Context(const Context&) = delete;

@@ -235,6 +235,10 @@ module Native =
     /// the tries that decide nothing are left out).  Same frame, rays, hits and flags; 0 = every frame on the first frame's schedule, 2 = record only
     let setTryHint (mode : int) = if ft_ctx_set_option (ctx.Value, 19, mode) < 0 then failwith (Marshal.PtrToStringAnsi (ft_last_error ()))
 
+    /// FT_OPT_DEPART (20), on by default: on the frames that follow try hints a shadow ray's miss certificate is tried where the ray is born, under a margin
+    /// that grows along the ray: a lit shadow ray ends at birth.  Same frame, rays, hits and flags; 0 = off, 2 = on every camera launch of the kernel family
+    let setDepart (mode : int) = if ft_ctx_set_option (ctx.Value, 20, mode) < 0 then failwith (Marshal.PtrToStringAnsi (ft_last_error ()))
+
     let check (h : int) =
         if h < 0 then failwith (Marshal.PtrToStringAnsi (ft_last_error ())) else h
 

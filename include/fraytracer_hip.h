@@ -160,6 +160,11 @@ typedef enum ft_option {
                                    * try runs changes: same frame, rays, hits and flags; sdf_evals and wave_evals fall.  Followed only under FT_OPT_CERT_POLICY = 0 on frames that word
                                    * gives the bundle alone, and from a camera whose image moved by at most 16 pixels since the frame that recorded; a first frame, an explicit policy
                                    * word and every other launch keep their schedule.  2: record only; 0: off */
+    FT_OPT_DEPART = 20,           /* 1 (default): on the frames that follow try hints (FT_OPT_TRY_HINT above) the smooth-union-of-spheres kernel tries each shadow ray's miss certificate where
+                                   * the ray is born, under a margin that starts near zero and grows along the ray with the steps a march could take; a lit shadow ray then ends at
+                                   * birth instead of creeping away from the surface it left.  Exact: same frame, rays, hits and flags; sdf_evals and wave_evals fall.  A first
+                                   * frame, a wide-tiled frame, an explicit FT_OPT_CERT_POLICY word, views, ray buffers and EXTENSION launches count exactly what they counted.
+                                   * 2: on every camera launch of that kernel family (tests); 0: off.  Only while FT_OPT_ESCAPE and FT_OPT_CERT are on */
     FT_OPT_GUIDED = 7             /* 1: the last jobs of a launch are handed out in half and quarter tiles (lean kernel); 0 (default): whole tiles only */
 } ft_option;
 /* MathF.Exp / MathF.Log (SdfForm.unionSmooth, SdfForm.fs:80,82) and MathF.Pow (FColor.gammaInverse, FColor.fs:50-55) are the C runtime's
@@ -822,6 +827,8 @@ int ft_scene_miss_certificate(const ft_scene*, float out[5]);
  * from a sphere beyond which the form is positive, the largest parameter occReach (up to it the float32 sum of the form cannot underflow).  A shadow ray ends as a hit where its line has a point at which the form is proved to be at most
  * -(occE (t / epsilon + 2) + occB), at a parameter t <= min(Length * occLenInv, occReach) */
 int ft_scene_occlusion_certificate(const ft_scene*, float out[7]);
+/* the departure certificate's constants (FT_OPT_DEPART): drift per step, constant part, kappa's factor, smallest epsilon, clip pad, Length factor, steps; out[1] < 0: none */
+int ft_scene_departure_certificate(const ft_scene*, float out[7]);
 /* the clusters of the certificate's bound (n_clusters = 0: the scene has none, and the certificate sums every child): n_clusters records of 8 floats
  * {centre xyz, radius, member count, first member} (the last two are int32 bits), then the n_children children (x, y, z, r) in cluster order.
  * out = NULL: only the counts; otherwise capacity >= 8 n_clusters + 4 n_children floats */
